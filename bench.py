@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- Mcell-steps/s of the projection + advection time step (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one iteration of the simulation_run loop (src/simulation.c:479-548: predictor, MAC
 projection, velocity advection, approximate projection, CFL) on a 3-D 256^3 triply periodic
 Taylor-Green box with default parameters, one box per GPU.  Inputs are
-resident in HBM before the timed region.  Prints ONE JSON line on rank 0, with
+resident in HBM before the timed region.  Prints ONE JSON line on rank 0 (value, ms_per_step:
+the K timed steps after W warm-up steps).  Only with --full, measured after the timed steps:
   roofline      the exact-order relax loop (4 pipelined sweeps) of the 256^3 level (dominant
                 kernel), timed with HIP events on the stream the kernels run on: 24 B per cell
                 and sweep algorithmic traffic
+  particles     config D: the particle event of --particles tracers, alone and with the step
   cpu_baseline  the repo's CPU oracle (a port of the reference algorithm; the reference itself
-                cannot be built here) on a bounded sample, 1 core.
+                cannot be built here) on a bounded sample, 1 core (unless --no-cpu-baseline).
+--dump-outputs DIR: after the timed steps, rank 0 writes the state its last step left (see
+dump_outputs) as DIR/<name>.npy, float64, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -189,6 +193,26 @@ def measure_roofline(dom, args, n):
     return roofline
 
 
+DUMP_CELLS = 1 << 20     # cells sampled per field: 4 fields x 8 MiB of float64
+
+
+def dump_outputs(sim, out_dir):
+    """What a caller of the step receives: the velocity components and the pressure at the same
+    fixed, seeded sample of interior cells (all cells when there are at most DUMP_CELLS; flat
+    C-order indices from np.random.default_rng(0), sorted), and [t, dt] of the simulation."""
+    os.makedirs(out_dir, exist_ok=True)
+    fields = dict(zip("uvw", sim.u))
+    fields["p"] = sim.p
+    cells = None
+    for name, var in fields.items():
+        a = var.download()[(slice(1, -1),) * sim.dom.dim].ravel()
+        if cells is None:
+            cells = np.arange(a.size) if a.size <= DUMP_CELLS else \
+                np.sort(np.random.default_rng(0).choice(a.size, DUMP_CELLS, replace=False))
+        np.save(os.path.join(out_dir, name + ".npy"), a[cells])
+    np.save(os.path.join(out_dir, "time.npy"), np.array([sim.t, sim.dt], dtype=np.float64))
+
+
 def free_port():
     import socket
     with socket.socket() as so:
@@ -203,9 +227,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--level", type=int, default=8, help="Refine level (8 = 256^3)")
     ap.add_argument("--mode", default="exact", choices=["exact", "redblack"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, particle and CPU baseline entries")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the fields of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--particles", type=int, default=2000000,
-                    help="tracers of the config D line (0 = skip)")
+                    help="with --full: tracers of the config D line (0 = skip)")
     ap.add_argument("--self-mpi", action="store_true",
                     help="lab: one rank whose six sides are GfsBoundaryMpi sides facing the box itself "
                          "(RCCL send / recv to self): the code path of a box in an N > 1 run, on one GPU")
@@ -329,6 +357,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sim, args.dump_outputs)
 
     # roofline of the dominant kernel: the exact-order relax loop of the 256^3 level (nrelax = 4
     # sweeps with the homogeneous BC between them, src/poisson.c:1070-1089) -- on a periodic box one
@@ -337,16 +367,17 @@ def main():
     # (with several boxes the relax loop of a box has the halo exchange between its sweeps: the kernel
     # entry is then measured by rank 0 on a periodic box of its own, after the timed region)
     roofline = None
-    rdom = dom if world == 1 and not args.self_mpi else (
-        gfship.Domain(3, args.level, [gfship.SIDE_PERIODIC] * 6, device=local_rank) if rank == 0
-        else None)
-    if rdom is not None:
-        roofline = measure_roofline(rdom, args, n)
+    if args.full:
+        rdom = dom if world == 1 and not args.self_mpi else (
+            gfship.Domain(3, args.level, [gfship.SIDE_PERIODIC] * 6, device=local_rank) if rank == 0
+            else None)
+        if rdom is not None:
+            roofline = measure_roofline(rdom, args, n)
 
     # config D: the same box with 2e6 GfsParticle tracers (positions from the
     # fixed-seed LCG, ids 1..Np): the particle event alone, and the step with the event in it
     particles = None
-    if world == 1 and args.particles > 0:
+    if args.full and world == 1 and args.particles > 0:
         from particle_cases import lcg_positions_fast
         pos, ids = lcg_positions_fast(args.particles)
         pl = gfship.ParticleList(sim, pos, ids)
@@ -426,7 +457,7 @@ def main():
                            "per": "rank 0"}
         if particles is not None:
             out["particles"] = particles
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))
     if dist is not None:

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in "$@"; do
   O=$R/gpurun_out/ab_$v; rm -rf $O; mkdir -p $O
   if [ "$v" = main ]; then unset GFSHIP_LIB; else export GFSHIP_LIB=$R/gerris-fft-particles_amd/lib/libgfship_$v.so; fi
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O -o b -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --particles 0 > $O/log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O -o b -- python3 $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --particles 0 > $O/log 2>&1
   f=$(find $O -name "b_kernel_stats.csv" | head -1)
   echo "== $v"
   python3 - "$f" "$RE" <<'PY'

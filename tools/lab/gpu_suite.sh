@@ -10,7 +10,7 @@ echo "tests rc=$rc"; tail -12 $O/tests.log
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o b -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --particles 0 > $O/trace.log 2>&1
 python3 $R/tools/lab/step_breakdown.py $O/trace > $O/step_breakdown.txt 2>&1; head -34 $O/step_breakdown.txt
-cd $R && timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+cd $R && timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 python3 - <<PY
 import json
 d = json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/kstat${2:+_$2}
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -o b -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --particles 0 > $O/log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -o b -- python3 $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --particles 0 > $O/log 2>&1
 f=$(find $O -name "b_kernel_stats.csv" | head -1)
 python3 - "$f" "$1" <<'PY'
 import csv, re, sys

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 RE=$1; O=$R/gpurun_out/pmc_${2:-k}
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --particles 0"
+B="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --particles 0"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --kernel-include-regex "$RE" --output-format csv -d $O/fetch -o f -- $B > $O/fetch.log 2>&1 && \
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --kernel-include-regex "$RE" --output-format csv -d $O/write -o w -- $B > $O/write.log 2>&1 && \
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_VALU --kernel-trace --kernel-include-regex "$RE" --output-format csv -d $O/sq1 -o s -- $B > $O/sq1.log 2>&1 && \

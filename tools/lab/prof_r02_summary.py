@@ -70,7 +70,7 @@ for (n, k), ds in sorted(by_level.items()):
     ds.sort()
     lev["level_n%d" % n] = {"kernel": k, "tiles": (n // 16) ** 2, "dispatches": len(ds),
                             "median_us": ds[len(ds) // 2], "min_us": ds[0], "max_us": ds[-1]}
-json.dump({"command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 5 "
+json.dump({"command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 5 "
                       "--warmup 1 --no-cpu-baseline",
            "note": "dispatches of the sweep-loop kernels in the kernel trace grouped by level (ring kernel "
                    "for n >= 128, six-wave kernel below); at 256^3 the 4-sweep loops of the steps and of "
@@ -139,7 +139,7 @@ for key, prefix, bytes_, what in (
         e.update({"algorithmic_bytes_per_launch": bytes_, "achieved_GBps": bytes_ / (us * 1e-6) / 1e9,
                   "frac_of_8TBps": bytes_ / (us * 1e-6) / 1e9 / PEAK})
     entries[key] = e
-json.dump({"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline",
+json.dump({"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline",
            "note": "average durations of r02_kernel_stats_bench_256.csv x algorithmic bytes per launch; the "
                    "particle gathers are served mostly by L2 / Infinity Cache (sorted by cell), so their "
                    "`achieved' is not HBM traffic",

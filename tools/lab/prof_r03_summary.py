@@ -78,7 +78,7 @@ for (n, k), ds in sorted(by_level.items()):
     ds.sort()
     lev["level_n%d" % n] = {"kernel": k, "tiles": (n // 16) ** 2, "dispatches": len(ds),
                             "median_us": ds[len(ds) // 2], "min_us": ds[0], "max_us": ds[-1]}
-json.dump({"command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 5 "
+json.dump({"command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 5 "
                       "--warmup 1 --no-cpu-baseline",
            "note": "dispatches of the sweep-loop kernels in the kernel trace grouped by level; at 256^3 the "
                    "4-sweep loops of the steps and of the roofline entry plus single-sweep launches",
@@ -167,7 +167,7 @@ for k, c in new.items():
     us, _, _ = avg_us(k.split("<")[0])
     alg = (120 + 72) * CELLS if "advect3" in k else (48 + 8) * CELLS
     adv[k] = digest(c, us / 1e3 if us else None, alg)
-json.dump({"command": "rocprofv3 --pmc <group> --kernel-trace --kernel-include-regex <kernel> -- python3 bench.py "
+json.dump({"command": "rocprofv3 --pmc <group> --kernel-trace --kernel-include-regex <kernel> -- python3 bench.py --full "
                       "--steps 3|4 --warmup 1 --no-cpu-baseline --particles 0; one run per group (FETCH_SIZE; "
                       "WRITE_SIZE; SQ waves / wait / VALU; SQ LDS / VMEM): tools/lab/prof_r03_a.sh, "
                       "tools/lab/pmc_kernel.sh",
@@ -213,7 +213,7 @@ for key, prefix, bytes_, what in (
         e.update({"algorithmic_bytes_per_launch": bytes_, "achieved_GBps": bytes_ / (us * 1e-6) / 1e9,
                   "frac_of_8TBps": bytes_ / (us * 1e-6) / 1e9 / PEAK})
     entries[key] = e
-json.dump({"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline",
+json.dump({"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline",
            "note": "average durations of r03_kernel_stats_bench_256.csv x algorithmic bytes per launch; the "
                    "particle gathers are served mostly by L2 / Infinity Cache (sorted by cell), so their "
                    "`achieved' is not HBM traffic",

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/selfmpi
 mkdir -p $O
-cd $R && timeout -k 10 200 python bench.py --self-mpi --steps 5 --warmup 2 --no-cpu-baseline --particles 0 > $O/bench.json 2> $O/bench.err
+cd $R && timeout -k 10 200 python bench.py --full --self-mpi --steps 5 --warmup 2 --no-cpu-baseline --particles 0 > $O/bench.json 2> $O/bench.err
 cat $O/bench.json | cut -c 1-400
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace -o b -- python3 $R/bench.py --self-mpi --steps 5 --warmup 1 --no-cpu-baseline --particles 0 > $O/trace.log 2>&1
