@@ -1853,9 +1853,6 @@ int run_tree (Run & R)
   if (!R.device_vars.empty ()) return refuse ("a turbulent-viscosity variable");
   if (R.snapshot.has_tree) return refuse ("cell data in the simulation file");
   if (R.dtmax != DBL_MAX) return refuse ("Time { dtmax }");
-  for (int c = 0; c < 3; c++) {
-    if (R.visc[c] != 0. && R.dim == 3) return refuse ("GfsSourceDiffusion (octrees)");
-  }
   for (auto & kv : R.adv_set)
     if (kv.first != "cfl" && !(kv.first == "gradient" && kv.second == "gfs_center_gradient") &&
 	!(kv.first == "gc" && atoi (kv.second.c_str ()) == 1))

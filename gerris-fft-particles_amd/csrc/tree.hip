@@ -32,6 +32,7 @@
 #include <cmath>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <new>
 
 using namespace gfship;
@@ -155,6 +156,7 @@ struct gfship_tree {
   double visc[3] = { 0., 0., 0. };
   gfship_multilevel_params diffusion_params[3];
   double src[3] = { 0., 0., 0. };   // GfsSource {} U|V|W g: constant intensities
+  int diffusion_exact = -1;         // octrees: every diffusion coefficient the stencils read is w (-1: not checked yet)
 };
 
 namespace {
@@ -303,7 +305,7 @@ t_relax_loop (Topo T, const Cell * cells, const int * lev_off, int nlev, const G
 	const Cell c = cells[t];
 	const int g = T.gi (c);
 	u[g] = op == 0 ? relax_cell (T, c, R, rhs[g], omega, max_level) :
-	  diffusion_relax_cell (T, c, R, rhs[g], w, max_level);
+	  diffusion_relax_cell (T, c, R, rhs[g], WConst { w }, max_level);
       }
       __syncthreads ();
     }
@@ -717,7 +719,7 @@ __global__ void t_diffusion_rhs (Topo T, const Cell * cells, int n, const double
   if (t >= n) return;
   const Cell c = cells[t];
   DevReader R = { v };
-  rhs[T.gi (c)] += diffusion_rhs_cell (T, c, R, w, pbeta);
+  rhs[T.gi (c)] += diffusion_rhs_cell (T, c, R, WConst { w }, pbeta);
 }
 
 // gfs_diffusion_residual (src/poisson.c:1519-1556) on the leaves + gfs_domain_norm_variable
@@ -731,7 +733,7 @@ __global__ void t_diffusion_residual (Topo T, const Cell * cells, int n, const d
     const Cell c = cells[t];
     DevReader R = { u };
     const int g = T.gi (c);
-    r = diffusion_residual_cell (T, c, R, rhs[g], w);
+    r = diffusion_residual_cell (T, c, R, rhs[g], WConst { w });
     res[g] = r;
     const double size = T.size (c);
     vol = T.dim == 3 ? size*size*size : size*size;
@@ -1539,6 +1541,147 @@ double tape_interpolation_gen (const Topo & T, Cell fine, Cell A, int dface, Tap
   return pa;
 }
 
+// ---- the diffusion coefficients of a tree ----------------------------------------------------
+// gfs_diffusion_coefficients with a constant D (src/poisson.c:1280-1303,826-853,1350-1390): diffusion_coef
+// over the faces of the leaves -- f[d].v = w on the cell of a face, = w on the neighbour of the same level,
+// += w/(FTT_CELLS/2) on a coarser neighbour -- then face_coeff_from_below on the non-leaf cells, children
+// first: (c0 + c1 + c2 + c3)/4, and 0 on every face of a cell with exactly one non-zero face towards an interior
+// neighbour.  In 2-D all of this is exactly w; in 3-D (w/4 + w/4) + w/4 and the sums of four children may
+// round on the way.  Written once for two arithmetics: A::V = double (the coefficients of one w, as the reference
+// computes them: the host check) or the form of the expression in w (WArithForm, below).
+template <class A>
+void diffusion_coefficients_gen (const Topo & T, A & ar, std::vector<typename A::V> & f)
+{
+  const int nd = T.nd ();
+  int ncell = 0;
+  for (int l = 0; l <= T.depth; l++) ncell += T.lsize (l);
+  f.assign ((size_t) ncell*nd, ar.zero ());
+  auto at = [&] (Cell c, int d) -> typename A::V & { return f[(size_t) T.gi (c)*nd + d]; };
+  // diffusion_coef, ftt_face_traverse of the leaves: a coarse leaf sees the faces of its fine neighbours
+  // from the fine side (each face once)
+  for (int l = 0; l <= T.depth; l++)
+    for (int q = 0; q < T.lsize (l); q++) {
+      const Cell c = { l, q };
+      if (T.flag[T.gi (c)] != LEAF || !T.interior (c)) continue;
+      for (int d = 0; d < nd; d++) {
+	const Cell nb = T.neighbor (c, d);
+	if (!exists (nb)) continue;
+	if (nb.l < c.l) {
+	  at (c, d) = ar.leaf ();
+	  at (nb, d ^ 1) = ar.addq (at (nb, d ^ 1));
+	}
+	else if (T.leaf (nb)) {
+	  at (c, d) = ar.leaf ();
+	  at (nb, d ^ 1) = ar.leaf ();
+	}
+	else if (!T.interior (nb))      /* a refined ghost cell: its children are not leaves of the traversal */
+	  for (int i = 0; i < T.ncd (); i++) {
+	    const Cell ch = T.child_direction (nb, d ^ 1, i);
+	    if (!exists (ch)) continue;
+	    at (ch, d ^ 1) = ar.leaf ();
+	    at (c, d) = ar.addq (at (c, d));
+	  }
+      }
+    }
+  // face_coeff_from_below, the interior non-leaf cells from the deepest level up
+  for (int l = T.depth; l >= 0; l--)
+    for (int q = 0; q < T.lsize (l); q++) {
+      const Cell c = { l, q };
+      if (T.flag[T.gi (c)] != NODE || !T.interior (c)) continue;
+      unsigned neighbors = 0;
+      for (int d = 0; d < nd; d++) {
+	typename A::V ch[4];
+	int n = 0;
+	for (int i = 0; i < T.ncd (); i++) {
+	  const Cell cc = T.child_direction (c, d, i);
+	  ch[i] = exists (cc) ? at (cc, d) : ar.zero ();
+	  n += exists (cc);
+	}
+	at (c, d) = ar.below (ch, T.ncd (), n);
+	const Cell nb = T.neighbor (c, d);
+	if (ar.nonzero (at (c, d)) && exists (nb) && T.interior (nb))
+	  neighbors++;
+      }
+      if (neighbors == 1)
+	for (int d = 0; d < nd; d++) at (c, d) = ar.zero ();
+    }
+}
+
+struct WArithDouble {       // the reference's arithmetic for one w
+  typedef double V;
+  double w, q;
+  V zero () const { return 0.; }
+  V leaf () const { return w; }
+  V addq (V a) const { return a + q; }
+  V below (const V * c, int nc, int n) const
+  {
+    (void) n;
+    double f = 0.;
+    for (int i = 0; i < nc; i++) f += c[i];
+    return f/nc;
+  }
+  bool nonzero (V a) const { return a != 0.; }
+};
+
+// The form of a coefficient as an expression in w: EXACT (= w for every w > 0), ZERO, a sum of k quarters (k < 0
+// stores -k), or anything else (OTHER).  Four equal addends summed from 0 give four times the addend exactly in
+// binary floating point: 2x is exact, fl (3x) is off by at most half an ulp of 4x, and when it is off by exactly that
+// (a tie, 3M = 2 mod 4 for the mantissa M of x) M is even and fl (fl (3x) + x) rounds back to 4x.  So the coarse side
+// of a fine-coarse face, 0 + w/4 + w/4 + w/4 + w/4 (3-D) or 0 + w/2 + w/2 (2-D), is w, and so is
+// face_coeff_from_below of children that are all w -- whatever w is, although (w + w) + w itself may round.
+struct WArithForm {
+  typedef int V;
+  enum { ZERO = 0, EXACT = 1, OTHER = 2 };
+  int ncd;                          /* FTT_CELLS/2 */
+  V zero () const { return ZERO; }
+  V leaf () const { return EXACT; }
+  V addq (V a) const
+  {
+    const int k = a == ZERO ? 1 : a < 0 ? - a + 1 : 0;      /* quarters so far + 1, or 0: not a sum of quarters */
+    if (k == 0) return OTHER;
+    return k == ncd ? EXACT : - k;
+  }
+  V below (const V * c, int nc, int n) const
+  {
+    bool all = n == nc && (nc == 2 || nc == 4);
+    for (int i = 0; i < nc; i++) all = all && c[i] == EXACT;
+    if (all) return EXACT;
+    for (int i = 0; i < nc; i++) if (c[i] != ZERO) return OTHER;
+    return ZERO;
+  }
+  bool nonzero (V a) const { return a != ZERO; }
+};
+
+// the device runs the diffusion stencils of a tree with the same weight w on every face (WConst): true when every
+// coefficient that diffusion_relax / _residual / _rhs read on this tree, on any level of the multigrid cycle, is w
+// for every w (a coefficient of another form would make the device differ from the reference: refused)
+bool diffusion_weights_exact (const Topo & T)
+{
+  WArithForm ar = { T.ncd () };
+  std::vector<int> form;
+  diffusion_coefficients_gen (T, ar, form);
+  struct ZeroReader { double operator() (const Topo &, Cell) const { return 0.; } };
+  struct WRecord {          // which f[d].v does the stencil read?
+    std::vector<size_t> * out;
+    double operator() (const Topo & T, Cell c, int d) const { out->push_back ((size_t) T.gi (c)*T.nd () + d); return 1.; }
+  };
+  std::vector<size_t> read;
+  ZeroReader zr;
+  WRecord wr = { &read };
+  for (int l = 0; l <= T.depth; l++)
+    for (int q = 0; q < T.lsize (l); q++) {
+      const Cell c = { l, q };
+      if (T.flag[T.gi (c)] == NONE || !T.interior (c)) continue;
+      read.clear ();
+      (void) diffusion_relax_cell (T, c, zr, 0., wr, l);           /* a cell of the sweep of its own level */
+      if (T.leaf (c))
+	(void) diffusion_residual_cell (T, c, zr, 0., wr);         /* a leaf on the finer levels, residual, rhs */
+      for (size_t k : read)
+	if (form[k] != WArithForm::EXACT) return false;
+    }
+  return true;
+}
+
 // one cell of the sweep of level max_level: what face_gradient (tree.hpp) does for each direction
 void tape_cell_gen (const Topo & T, Cell cell, int max_level, TapeOut & o)
 {
@@ -2230,7 +2373,8 @@ int diffusion_cycle (gfship_tree * tr, unsigned levelmin, unsigned depth, unsign
 }
 
 // variable_diffusion (src/timestep.c:923-949) + gfs_diffusion (:735-788) of velocity component c; the
-// right-hand side is V_DRHS.  Quadtrees: every face carries the weight beta dt D (face_gradient_w)
+// right-hand side is V_DRHS.  Every face carries the weight beta dt D (face_gradient_w, WConst; octrees:
+// diffusion_weights_exact)
 int variable_diffusion (gfship_tree * tr, int c)
 {
   int e;
@@ -2878,6 +3022,119 @@ int gfship_tree_host_check (int dim, gfship_refine_fn refine, void * ctx, const 
   return e;
 }
 
+namespace {
+struct WDirect {            // the coefficients f[d].v of a cell from an array of them (the host check)
+  const double * f;
+  __host__ __device__ inline double operator() (const Topo & T, Cell c, int d) const { return f[(size_t) T.gi (c)*T.nd () + d]; }
+};
+}
+
+// gfship_tree_host_check for the diffusion relax (op 1) with the coefficients of one w
+int gfship_tree_host_check_diffusion (int dim, gfship_refine_fn refine, void * ctx, const int * side,
+				      unsigned nrelax, double w, long long stats[6])
+{
+  GFSHIP_CHECK (refine && stats && nrelax >= 1 && w > 0., GFSHIP_EINVAL, "gfship_tree_host_check_diffusion: bad argument");
+  gfship_tree * tr = nullptr;
+  g_host_only = true;
+  int e = gfship_tree_create_sides (&tr, dim, refine, ctx, side, 0);
+  if (e) { g_host_only = false; return e; }
+  const Topo & T = tr->H;
+  for (int k = 0; k < 6; k++) stats[k] = 0;
+  const int nd = T.nd ();
+  // the coefficients as the reference computes them for this w (the plans of the device take w on every face)
+  std::vector<double> fdir;
+  WArithDouble ard = { w, w/(T.nc ()/2) };
+  diffusion_coefficients_gen (T, ard, fdir);
+  for (int g = 0; g < tr->ncell; g++)
+    for (int d = 0; d < nd; d++) {
+      const double a = fdir[(size_t) g*nd + d];
+      if (a != 0. && a != w) stats[2]++;
+    }
+  if (!diffusion_weights_exact (T)) stats[2] = - stats[2] - 1;      /* the tree would be refused */
+  const Sgn6 sg = homogeneous_signs_u (tr, 0);
+  struct HostReader {
+    const double * p;
+    double operator() (const Topo & T, Cell c) const { return p[T.gi (c)]; }
+  };
+  for (int m = 0; m <= T.depth && !e; m++) {
+    Sweep & S = tr->sweep[m];
+    Sweep::Loop P;
+    e = loop_plan (tr, m, nrelax, &S, &P, &sg);
+    if (e) break;
+    std::vector<double> u0 (tr->ncell), rhs (tr->ncell);
+    unsigned long long seed = 88172645463325252ull + 7*m;
+    for (int g = 0; g < tr->ncell; g++) {
+      seed ^= seed << 13; seed ^= seed >> 7; seed ^= seed << 17;
+      u0[g] = (double) (seed % 2000001)/1e6 - 1.;
+      seed ^= seed << 13; seed ^= seed >> 7; seed ^= seed << 17;
+      rhs[g] = (double) (seed % 2000001)/1e6 - 1.;
+    }
+    // (1) the sequential program through the tree-walking stencil code with the reference's coefficients
+    std::vector<double> a = u0;
+    std::vector<Cell> order;
+    traverse (T, root_cell (T), T_LEVEL_LEAFS, m, [&] (Cell c) { order.push_back (c); });
+    for (unsigned sw = 0; sw < nrelax; sw++) {
+      for (const Ghost & G : S.h_ghosts) a[G.g] = sg.s[G.side]*a[G.img];
+      HostReader R = { a.data () };
+      for (Cell c : order) {
+	const int g = T.gi (c);
+	a[g] = diffusion_relax_cell (T, c, R, rhs[g], WDirect { fdir.data () }, m);
+      }
+    }
+    // (2) the plan of the whole loop (the weight w on every face), the nodes of a level backwards
+    std::vector<double> c3 = u0;
+    {
+      stats[1] += P.nlev;
+      size_t k0 = 0;
+      const size_t nn = P.h_node_g.size ();
+      while (k0 < nn) {
+	size_t k1 = k0;
+	while (k1 < nn && P.h_node_level[k1] == P.h_node_level[k0]) k1++;
+	std::vector<std::pair<int, double>> out;
+	for (size_t k = k1; k-- > k0; ) {
+	  std::vector<double> vals;
+	  for (int q = P.h_node_off[3*k + 2]; q < P.h_node_off[3*(k + 1) + 2]; q++) vals.push_back (c3[P.h_tv[q]]);
+	  TapeCursor cur = { P.h_ti.data () + P.h_node_off[3*k], P.h_td.data () + P.h_node_off[3*k + 1], vals.data () };
+	  const int g = P.h_node_g[k];
+	  double x;
+	  if (*cur.ti == K_GHOST)
+	    x = (*cur.td)*(*cur.tv);
+	  else {      /* t_relax_nodes, op 1 */
+	    cur.tv++;
+	    double ga, gb;
+	    tape_cell (cur, nd, T.dim, T.ncd (), ga, gb, w);
+	    int l = 0;
+	    while (g >= T.off[l + 1]) l++;
+	    const double h = 1./(1 << l);
+	    const double aa = 1.*h*h;
+	    ga = 1. + ga/aa;
+	    x = (gb/aa + rhs[g])/ga;
+	  }
+	  out.push_back ({ g, x });
+	}
+	for (auto & kv : out) c3[kv.first] = kv.second;
+	k0 = k1;
+      }
+    }
+    // (3) the flow plan with the kernel's timing of loads and stores
+    std::vector<double> c4 = u0;
+    if (P.flow)
+      stats[4] += flow_emulate (*P.flow, T.dim, c4, rhs, 1., 1, w);
+    else {
+      stats[5]++;
+      c4 = a;
+    }
+    stats[0] += (long long) order.size ()*nrelax;
+    for (int g = 0; g < tr->ncell; g++)
+      if (memcmp (&a[g], &c3[g], sizeof (double)) || memcmp (&a[g], &c4[g], sizeof (double)))
+	stats[3]++;
+    loop_free (P);
+  }
+  tree_free (tr);
+  g_host_only = false;
+  return e;
+}
+
 /* the cells of the sweep of level `level' and the number of dependency levels they form */
 int gfship_tree_sweep_levels (const gfship_tree * tr, int level, int * ncells, int * nlevels)
 {
@@ -2903,10 +3160,14 @@ int gfship_tree_set_viscosity (gfship_tree * tr, int c, double nu)
   GFSHIP_CHECK (tr, GFSHIP_EINVAL, "gfship_tree_set_viscosity: null tree");
   GFSHIP_CHECK (c >= 0 && c < tr->H.dim, GFSHIP_EINVAL, "component %d out of range", c);
   GFSHIP_CHECK (nu >= 0., GFSHIP_EINVAL, "the diffusion coefficient must be positive");
-  /* octrees: the face coefficients of the coarse side of a fine-coarse face are sums of four quarters that
-     may round (src/poisson.c:1280-1303): they would have to be kept per face */
-  GFSHIP_CHECK (nu == 0. || tr->H.dim == 2, GFSHIP_EUNSUPPORTED,
-		"GfsSourceDiffusion on a refined tree is supported on quadtrees (2-D)");
+  /* the coefficients of gfs_diffusion_coefficients (src/poisson.c:1280-1303,826-853) are w on every face the
+     stencils read, quadtrees and octrees alike (diffusion_weights_exact): checked once per octree */
+  if (nu != 0. && tr->H.dim == 3 && tr->diffusion_exact < 0) {
+    try { tr->diffusion_exact = diffusion_weights_exact (tr->H) ? 1 : 0; }
+    catch (const std::bad_alloc &) { set_error ("gfship_tree_set_viscosity: out of host memory"); return GFSHIP_EUNSUPPORTED; }
+  }
+  GFSHIP_CHECK (nu == 0. || tr->H.dim == 2 || tr->diffusion_exact == 1, GFSHIP_EUNSUPPORTED,
+		"GfsSourceDiffusion on this octree: a diffusion coefficient is not the same number on every face");
   tr->visc[c] = nu;
   return GFSHIP_OK;
 }

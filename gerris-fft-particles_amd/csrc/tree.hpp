@@ -362,15 +362,23 @@ __host__ __device__ inline double face_interpolated_value_generic (const Topo & 
 }
 
 // face_weighted_gradient (src/fluid.c:833-893) / gfs_face_cm_weighted_gradient (:1300-1400, no metric)
-// with the SAME weight w on every face: the face coefficients of gfs_diffusion_coefficients with a
-// constant D on a quadtree (diffusion_coef gives every leaf face w, the coarse side of a fine-coarse
-// face w/2 + w/2 and face_coeff_from_below (w + w)/2, all exactly w; in 3-D the sums of four quarters
-// may round: not used there)
-template <class V>
-__host__ __device__ inline Grad2 face_gradient_w (const Topo & T, const Face & face, V & v, int max_level, double w)
+// with the face coefficients of gfs_diffusion_coefficients for a constant D.  W gives f[d].v of a cell: the
+// kernels use WConst, the same w on every face -- what diffusion_coef and face_coeff_from_below give on a quadtree
+// (w/2 + w/2, (w + w)/2) and, exactly too, on an octree (four quarters, four children: diffusion_weights_exact in
+// tree.hip checks every face of a tree before it takes viscosity); the host check reads the reference's own
+// coefficients through another W
+struct WConst {
+  double w;
+  __host__ __device__ inline double operator() (const Topo &, Cell, int) const { return w; }
+};
+template <class V, class W>
+__host__ __device__ inline Grad2 face_gradient_w (const Topo & T, const Face & face, V & v, int max_level, const W & wf)
 {
   Grad2 g = { 0., 0. };
-  if (!exists (face.neighbor) || w == 0.)
+  if (!exists (face.neighbor))
+    return g;
+  const double w = wf (T, face.cell, face.d);
+  if (w == 0.)
     return g;
   const int level = face.cell.l;
   if (face.neighbor.l < level) {
@@ -390,9 +398,10 @@ __host__ __device__ inline Grad2 face_gradient_w (const Topo & T, const Face & f
     for (int i = 0; i < n; i++) {
       f.cell = T.child_direction (face.neighbor, f.d, i);
       if (exists (f.cell)) {
+	const double wc = wf (T, f.cell, f.d);
 	const Grad3 gcf = gradient_fine_coarse (T, f, v);
-	g.a += w*gcf.b;
-	g.b += w*(gcf.a*v (T, f.cell) - gcf.c);
+	g.a += wc*gcf.b;
+	g.b += wc*(gcf.a*v (T, f.cell) - gcf.c);
       }
     }
     if (T.dim > 2) {
@@ -404,8 +413,8 @@ __host__ __device__ inline Grad2 face_gradient_w (const Topo & T, const Face & f
 }
 
 // diffusion_relax, src/poisson.c:1455-1484 (rhoc = 1): the new value of u at `cell'
-template <class V>
-__host__ __device__ inline double diffusion_relax_cell (const Topo & T, Cell cell, V & u, double res, double w,
+template <class V, class W>
+__host__ __device__ inline double diffusion_relax_cell (const Topo & T, Cell cell, V & u, double res, const W & w,
 							int max_level)
 {
   Grad2 g = { 0., 0. };
@@ -424,8 +433,8 @@ __host__ __device__ inline double diffusion_relax_cell (const Topo & T, Cell cel
 }
 
 // diffusion_residual, src/poisson.c:1519-1556 (rhoc = 1)
-template <class V>
-__host__ __device__ inline double diffusion_residual_cell (const Topo & T, Cell cell, V & u, double rhs, double w)
+template <class V, class W>
+__host__ __device__ inline double diffusion_residual_cell (const Topo & T, Cell cell, V & u, double rhs, const W & w)
 {
   Grad2 g = { 0., 0. };
   Face f;
@@ -445,8 +454,8 @@ __host__ __device__ inline double diffusion_residual_cell (const Topo & T, Cell 
 }
 
 // diffusion_rhs, src/poisson.c:1392-1421 (rhoc = 1): what is added to rhs
-template <class V>
-__host__ __device__ inline double diffusion_rhs_cell (const Topo & T, Cell cell, V & v, double w, double pbeta)
+template <class V, class W>
+__host__ __device__ inline double diffusion_rhs_cell (const Topo & T, Cell cell, V & v, const W & w, double pbeta)
 {
   double f = 0.;
   const double h = T.size (cell), value = v (T, cell);

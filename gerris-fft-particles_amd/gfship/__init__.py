@@ -181,6 +181,7 @@ SIGNATURES = {
     "gfship_tree_sweep_levels": (_i, [_vp, _i, _pi, _pi]),
     "gfship_tree_divergence": (_i, [_vp]),
     "gfship_tree_host_check": (_i, [_i, C.c_void_p, _vp, _pi, _u, C.POINTER(C.c_longlong)]),
+    "gfship_tree_host_check_diffusion": (_i, [_i, C.c_void_p, _vp, _pi, _u, _d, C.POINTER(C.c_longlong)]),
 }
 
 
@@ -703,6 +704,20 @@ def tree_host_check(refine, dim=2, sides=None, nrelax=4):
     arr = (C.c_int * 6)(*(list(sides) + [0] * 6)[:6]) if sides is not None else None
     stats = (C.c_longlong * 4)()
     _check(lib().gfship_tree_host_check(dim, C.cast(cb, C.c_void_p), None, arr, nrelax, stats))
+    return tuple(stats)
+
+
+def tree_host_check_diffusion(refine, w, dim=3, sides=None, nrelax=4):
+    """gfship_tree_host_check_diffusion: the diffusion relax plans of a tree with the face coefficients of
+    the weight w validated on the host; returns (cell updates, levels of the loop plans, faces whose
+    coefficient is not w, differing values, flow hazards, levels without a flow plan)"""
+    if dim == 2:
+        cb = REFINE_FN(lambda x, y, z, ctx: float(refine(x, y)))
+    else:
+        cb = REFINE_FN(lambda x, y, z, ctx: float(refine(x, y, z)))
+    arr = (C.c_int * 6)(*(list(sides) + [0] * 6)[:6]) if sides is not None else None
+    stats = (C.c_longlong * 6)()
+    _check(lib().gfship_tree_host_check_diffusion(dim, C.cast(cb, C.c_void_p), None, arr, nrelax, float(w), stats))
     return tuple(stats)
 
 

@@ -593,8 +593,11 @@ int  gfship_tree_add_tracer (gfship_tree * tree, int gradient);
    923-949, src/poisson.c:1271-1690: coefficients with their fine-coarse forms, gfs_diffusion_rhs,
    diffusion_relax in tree order with the homogeneous conditions of the component, gfs_diffusion_cycle with
    10 nrelax sweeps on the first level), the explicit term as MAC source of the face values and in the
-   CFL condition.  Quadtrees only (GFSHIP_EUNSUPPORTED on an octree); with Dirichlet walls this is the
-   lid-driven cavity of test/lid on a refined tree. */
+   CFL condition.  Quadtrees and octrees: the coefficients of the coarse side of a fine-coarse face
+   (0 + w/4 + w/4 + w/4 + w/4 in 3-D) and of face_coeff_from_below are exactly w = beta dt nu on the trees
+   this library builds; set_viscosity checks that of the tree once (GFSHIP_EUNSUPPORTED if a face read by
+   the stencils had another coefficient).  With Dirichlet walls this is the lid-driven cavity of test/lid
+   (a cube in 3-D) on a refined tree. */
 int  gfship_tree_set_bc_u (gfship_tree * tree, int c, int d, int kind);
 int  gfship_tree_set_viscosity (gfship_tree * tree, int c, double nu);
 /* GfsSource {} U|V|W g with a constant intensity on a tree (as gfship_sim_set_source: MAC source of the face
@@ -614,6 +617,15 @@ int  gfship_tree_divergence (gfship_tree * tree);
    loop plans, [3] = number of values that differ between (a), (b), (c): 0 for valid plans */
 int  gfship_tree_host_check (int dim, gfship_refine_fn refine, void * ctx, const int * side,
 			     unsigned nrelax, long long stats[4]);
+/* the same for the diffusion relax (diffusion_relax, src/poisson.c:1455-1484) with the coefficients of
+   gfs_diffusion_coefficients for the face weight w > 0 (the homogeneous conditions of U): for every level
+   (a) the reference's program with the coefficients computed in the reference's order for this w, (b) the
+   plan of the whole loop, (c) its flow plan with the kernel's timing, both with w on every face as the
+   device runs them.  stats[0] = cell updates, [1] = levels of the loop plans, [2] = faces whose coefficient
+   is not w (negative: - that number - 1 when the tree would be refused), [3] = values that differ: 0 for
+   valid plans, [4] = hazards of the flow plans, [5] = levels without a flow plan */
+int  gfship_tree_host_check_diffusion (int dim, gfship_refine_fn refine, void * ctx, const int * side,
+				       unsigned nrelax, double w, long long stats[6]);
 /* diagnostics: the cells of the sweep of gfs_relax on `level' (the cells of the level and the
    coarser leaves) and the number of dependency levels its tree order leaves on the device */
 int  gfship_tree_sweep_levels (const gfship_tree * tree, int level, int * ncells, int * nlevels);

@@ -2,7 +2,8 @@
 """Time steps of the refined-tree path (gfship_tree) on an octree / quadtree with BOX
 extra levels inside the central cube / square: leaves, dependency levels of the finest sweep, ms per
 step, Mleaf-steps/s.  Not the benchmarked path (that is bench.py); a measurement to quote.
-usage: tree_bench.py [dim] [level] [box] [steps]"""
+usage: tree_bench.py [dim] [level] [box] [steps] [nu]
+nu: GfsSourceDiffusion on every velocity component (default 0: inviscid)"""
 import os
 import sys
 import time
@@ -17,6 +18,7 @@ dim = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 level = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 box = int(sys.argv[3]) if len(sys.argv) > 3 else 2
 steps = int(sys.argv[4]) if len(sys.argv) > 4 else 5
+nu = float(sys.argv[5]) if len(sys.argv) > 5 else 0.
 inside = lambda *a: all(-0.25 <= v <= 0.25 for v in a)
 t0 = time.time()
 if dim == 3:
@@ -40,6 +42,9 @@ for l in range(g.depth + 1):
         v = 1. + 2. * np.sin(2 * np.pi * x) * np.cos(2 * np.pi * y)
     g.upload(g.U, l, u)
     g.upload(g.V, l, v)
+if nu != 0.:
+    for c in range(dim):
+        g.set_viscosity(c, nu)
 g.set_time(1e30, 0.8)
 g.start()
 g.step()
@@ -51,5 +56,6 @@ nc, nl = g.sweep_levels(g.depth)
 print({"dim": dim, "levels": [level, g.depth], "leaves": nleaves, "finest_sweep_cells": nc,
        "finest_sweep_dependency_levels": nl, "tree_build_s": round(t_build, 2),
        "ms_per_step": round(ms, 2), "Mleaf_steps_per_s": round(nleaves / ms / 1e3, 3),
-       "niter": [g.projection_params.niter, g.approx_projection_params.niter]})
+       "niter": [g.projection_params.niter, g.approx_projection_params.niter],
+       **({"nu": nu, "diffusion_niter": [g.diffusion_params(c).niter for c in range(dim)]} if nu != 0. else {})})
 g.destroy()
