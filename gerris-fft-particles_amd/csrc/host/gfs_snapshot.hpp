@@ -11,8 +11,9 @@
 //
 // (simulation_write src/simulation.c:77-170, domain_write src/domain.c:168-209, gfs_box_write
 // src/boundary.c:1819-1851).  The tree is binary (`binary = 1': guint flags, double -1., one double
-// per variable, pre-order) or text (one line per cell: `flags -1 v1 v2 ...' in %g).  Shared by the
-// front end (restart, OutputSimulation) and by the comparison tool; host code only.
+// per variable, pre-order) or text (one line per cell: `flags -1 v1 v2 ...' in %g).  The tree is whatever the
+// leaf bits of the records say (a uniform box or a refined quadtree / octree).  Shared by the front end (restart,
+// OutputSimulation) and by the comparison tool; host code only.
 #pragma once
 #include "gfs_text.hpp"
 #include <cstdint>
@@ -20,12 +21,18 @@
 
 namespace gfs {
 
+// a cell of the tree of a file: its level, its integer coordinates on that level (0-based, growing with x, y, z;
+// k = 0 in 2-D), whether it is a leaf, and the index of its record in the image (= its position in file order)
+struct TreeCell { int level, i, j, k; bool leaf; size_t rec; };
+
 struct SimulationFile {
   std::string text;                     // the file without the cell data (what the parser reads)
   bool has_tree = false, binary = false;
   std::vector<std::string> variables;   // variables = a,b,c of the graph parameters
   std::string tree;                     // the cell data as the binary image (converted if text)
-  int dim = 0, depth = -1;
+  int dim = 0, depth = -1;              // depth: the deepest level of the tree
+  bool uniform = true;                  // every leaf is on that level
+  std::vector<TreeCell> cells;          // the tree of the file, taken from its leaf bits, in file order
 };
 
 inline std::vector<std::string> split_commas (const std::string & s)
@@ -43,26 +50,43 @@ inline std::vector<std::string> split_commas (const std::string & s)
 
 inline size_t tree_record (size_t nvars) { return 4 + 8 + 8*nvars; }
 
-inline size_t tree_cells (int dim, int depth)
+// The tree of a binary image: the records are walked in pre-order (cell_read_binary, src/ftt.c:1913-1975: a
+// cell without the leaf bit is followed by its FTT_CELLS children, whose ids must be 0 .. FTT_CELLS - 1 in turn).
+// Returns the cells in file order; throws if the image ends inside the tree.
+inline std::vector<TreeCell> tree_view (const char * p, size_t avail, size_t rec, int dim,
+					const std::string & name)
 {
-  size_t cells = 0, c = 1;
-  for (int l = 0; l <= depth; l++) { cells += c; c *= dim == 3 ? 8 : 4; }
-  return cells;
-}
-
-// depth of the (uniform) tree whose binary image starts at p: follow the first children
-inline int tree_depth_binary (const char * p, size_t avail, size_t rec)
-{
-  int depth = 0;
-  size_t o = 0;
-  while (o + rec <= avail) {
+  std::vector<TreeCell> out;
+  struct Frame { int level, i, j, k, next; };
+  std::vector<Frame> stack;
+  const int nc = dim == 3 ? 8 : 4;
+  TreeCell c = { 0, 0, 0, 0, false, 0 };
+  unsigned expect = 0;
+  for (;;) {
+    if ((out.size () + 1)*rec > avail) throw ParseError (name + ": truncated cell data");
     uint32_t flags;
-    memcpy (&flags, p + o, 4);
-    if (flags & 16u) return depth;
-    depth++;
-    o += rec;
+    memcpy (&flags, p + out.size ()*rec, 4);
+    if ((flags & 7u) != expect)
+      throw ParseError (name + ": FTT_CELL_ID (cell) != (flags & FTT_FLAG_ID): make sure the file has " +
+			std::to_string (dim) + " spatial dimensions");
+    c.leaf = (flags & 16u) != 0;
+    c.rec = out.size ();
+    out.push_back (c);
+    if (!c.leaf) {
+      if (c.level >= 30) throw ParseError (name + ": the tree of the cell data is too deep");
+      stack.push_back ({ c.level, c.i, c.j, c.k, 0 });
+    }
+    while (!stack.empty () && stack.back ().next == nc) stack.pop_back ();
+    if (stack.empty ()) break;
+    Frame & f = stack.back ();
+    const int n = f.next++;     /* child n: bit 0 = +x half, bit 1 = -y half, bit 2 = -z half */
+    c.level = f.level + 1;
+    c.i = 2*f.i + (n & 1);
+    c.j = 2*f.j + 1 - ((n >> 1) & 1);
+    c.k = dim == 3 ? 2*f.k + 1 - ((n >> 2) & 1) : 0;
+    expect = (unsigned) n;
   }
-  return -1;
+  return out;
 }
 
 // a text tree (ftt_cell_write + gfs_cell_write) into the binary image; returns the characters used
@@ -94,9 +118,8 @@ inline size_t tree_text_to_binary (const std::string & s, size_t b, size_t nvars
       if (!number (x)) throw ParseError ("cell data: expecting a number");
       out.append ((const char *) &x, 8);
     }
+    if (level > depth) depth = level;
     if (flags & 16u) {
-      if (depth < 0) depth = level;
-      else if (depth != level) throw ParseError ("cell data: the tree is not uniform");
       // next sibling, or up
       while (!todo.empty () && --todo.back () == 0) { todo.pop_back (); level--; }
       if (todo.empty ()) break;
@@ -142,14 +165,19 @@ inline SimulationFile split_simulation_file (const std::string & all, const std:
   if (F.binary) {
     if (b >= all.size () || all[b] != '\n') throw ParseError (name + ": expecting a newline before the binary cell data");
     b++;
-    F.depth = tree_depth_binary (all.data () + b, all.size () - b, rec);
-    if (F.depth < 0) throw ParseError (name + ": truncated binary cell data");
-    used = tree_cells (dim, F.depth)*rec;
-    if (b + used > all.size ()) throw ParseError (name + ": truncated binary cell data");
+    F.cells = tree_view (all.data () + b, all.size () - b, rec, dim, name);
+    used = F.cells.size ()*rec;
     F.tree.assign (all, b, used);
   }
-  else
+  else {
     used = tree_text_to_binary (all, b, F.variables.size (), dim, F.tree, F.depth);
+    F.cells = tree_view (F.tree.data (), F.tree.size (), rec, dim, name);
+  }
+  F.depth = 0;
+  for (const TreeCell & c : F.cells)
+    if (c.level > F.depth) F.depth = c.level;
+  for (const TreeCell & c : F.cells)
+    if (c.leaf && c.level != F.depth) F.uniform = false;
   size_t close = b + used;
   while (close < all.size () && isspace ((unsigned char) all[close])) close++;
   if (close >= all.size () || all[close] != '}')

@@ -1,10 +1,14 @@
 // gfscompare.cpp -- gfshipcompare2D / gfshipcompare3D: difference between the solutions of two
 // simulation files for one variable, the way the reference's tools/gfscompare.c does it for two
-// files with the same (here: uniform) tree:
+// files with any two trees (uniform boxes, refined quadtrees / octrees, of different depths):
 //
 //   gfshipcompare3D [-C] [-w] [-v] [-H] FILE1 FILE2 VAR
 //
-//   e = VAR(FILE1) - VAR(FILE2) on every leaf (difference_tree, tools/gfscompare.c:163-214);
+//   difference_tree + inject (tools/gfscompare.c:153-214): every cell of FILE1 is located in FILE2 at its own
+//     level; where FILE2 is coarser the parent takes over.  A cell none of whose children got an error gets
+//     e = VAR(FILE1, cell) - VAR(FILE2, located cell) -- the located cell may be a non-leaf cell of FILE2: the
+//     value its record holds is used -- and hands it to all its descendants.  The norms run over the leaves
+//     of FILE1 (difference, :244-268);
 //   -C  --constant      subtract the weighted mean of e first: "apply a constant shift to one of
 //                       the field, minimizing the error between the two fields (useful for
 //                       pressure)" (difference_constant :223-243, :657-669);
@@ -13,12 +17,14 @@
 //                       "total err first: %10.3e second: %10.3e infty: %10.3e w: %g" on stderr
 //                       (:567-595, :683-686; gfs_norm_add / gfs_norm_update src/fluid.c:2139-2171);
 //   -H  --histogram     "(error, volume fraction)" pairs on stdout (:268-269).
-// Exit status 0; 1 when the files cannot be compared (different trees, unknown variable).
+// Exit status 0; 1 when the files cannot be compared (another dimension, no cell data, unknown variable).
 // Host arithmetic over two files: no device is involved.
 #include <cmath>
 #include <cstdio>
 #include <fstream>
+#include <functional>
 #include <sstream>
+#include <unordered_map>
 #include "gfs_snapshot.hpp"
 
 using namespace gfs;
@@ -115,46 +121,90 @@ int main (int argc, char ** argv)
   int v1 = variable_index (F1, var), v2 = variable_index (F2, var);
   if (v1 < 0) { fprintf (stderr, "gfscompare: unknown variable `%s' for `%s'\nTry `gfscompare --help' for more information.\n", var.c_str (), pos[0]); return 1; }
   if (v2 < 0) { fprintf (stderr, "gfscompare: unknown variable `%s' for `%s'\nTry `gfscompare --help' for more information.\n", var.c_str (), pos[1]); return 1; }
-  if (F1.depth != F2.depth) {
-    /* difference_tree locates every cell of FILE1 in FILE2 at its own level: on uniform trees of
-       different depths no leaf has a counterpart */
-    fprintf (stderr, "gfscompare: the files are not comparable\n");
-    return 1;
-  }
-  std::vector<double> a = tree_leaves (F1.tree, F1.variables.size (), (size_t) v1);
-  std::vector<double> b = tree_leaves (F2.tree, F2.variables.size (), (size_t) v2);
-  const double h = 1./(1 << F1.depth);
-  const double volume = dim == 3 ? h*h*h : h*h;       /* ftt_cell_volume */
-  const double w = weighted ? volume*1. : 1.;
+  const size_t rec1 = tree_record (F1.variables.size ()), rec2 = tree_record (F2.variables.size ());
+  auto value = [] (const SimulationFile & F, size_t rec, size_t cell, int v) {
+    double x;
+    memcpy (&x, F.tree.data () + cell*rec + 12 + 8*(size_t) v, 8);
+    return x;
+  };
+  auto volume = [dim] (const TreeCell & c) {       /* ftt_cell_volume */
+    const double h = 1./(1 << c.level);
+    return dim == 3 ? h*h*h : h*h;
+  };
   if (verbose)
     for (int f = 0; f < 2; f++) {
-      const std::vector<double> & x = f ? b : a;
+      const SimulationFile & F = f ? F2 : F1;
       Norm n;
-      double mn = 1e300, mx = -1e300, sum = 0., sum2 = 0.;
-      for (double v : x) {
-	norm_add (n, v, volume);
+      double mn = 1e300, mx = -1e300, sum = 0., sum2 = 0., cnt = 0.;
+      for (const TreeCell & c : F.cells) {
+	if (!c.leaf) continue;
+	const double v = value (F, f ? rec2 : rec1, c.rec, f ? v2 : v1);
+	norm_add (n, v, volume (c));
 	if (v < mn) mn = v;
 	if (v > mx) mx = v;
-	sum += v; sum2 += v*v;
+	sum += v; sum2 += v*v; cnt += 1.;
       }
       norm_update (n);
-      double mean = sum/x.size ();
-      double sd = sqrt (fmax (0., sum2/x.size () - mean*mean));
+      double mean = sum/cnt;
+      double sd = sqrt (fmax (0., sum2/cnt - mean*mean));
       fprintf (stderr, "%s:\n  first: %g second: %g infty: %g w: %g\n  min: %g avg: %g | %g max: %g\n",
 	       pos[f], n.first, n.second, n.infty, n.w, mn, mean, sd, mx);
     }
-  std::vector<double> e (a.size ());
-  for (size_t q = 0; q < a.size (); q++) e[q] = a[q] - b[q];
+  // gfs_domain_locate (FILE2, centre of the cell, its level): the cell of FILE2 with the same level and coordinates,
+  // if FILE2 is refined that far there
+  auto key = [] (const TreeCell & c) {
+    return ((((uint64_t) c.level << 19 | (uint64_t) c.k) << 19 | (uint64_t) c.j) << 19) | (uint64_t) c.i;
+  };
+  if (F1.depth > 19 || F2.depth > 19) { fprintf (stderr, "gfscompare: the files are not comparable\n"); return 1; }
+  std::unordered_map<uint64_t, size_t> in2;
+  in2.reserve (F2.cells.size ()*2);
+  for (const TreeCell & c : F2.cells) in2[key (c)] = c.rec;
+  const int nc = dim == 3 ? 8 : 4;
+  const std::vector<TreeCell> & C1 = F1.cells;
+  std::vector<double> err (C1.size (), 0.);
+  struct Walk {
+    const std::vector<TreeCell> & C;
+    int nc;
+    void skip (size_t & q) const { const bool leaf = C[q++].leaf; if (!leaf) for (int n = 0; n < nc; n++) skip (q); }
+  } walk = { C1, nc };
+  std::function<bool (size_t &)> difference_tree = [&] (size_t & q) -> bool {
+    const size_t me = q;
+    auto located = in2.find (key (C1[me]));
+    if (located == in2.end ()) {     /* ftt_cell_level (locate) != level */
+      walk.skip (q);
+      return false;
+    }
+    bool added = false;
+    q++;
+    if (!C1[me].leaf)
+      for (int n = 0; n < nc; n++)
+	if (difference_tree (q)) added = true;
+    if (!added) {
+      const double e = value (F1, rec1, me, v1) - value (F2, rec2, located->second, v2);
+      for (size_t d = me; d < q; d++) err[d] = e;      /* inject: the records of a subtree follow each other */
+    }
+    return true;
+  };
+  {
+    size_t q = 0;
+    if (!difference_tree (q)) { fprintf (stderr, "gfscompare: the files are not comparable\n"); return 1; }
+  }
+  std::vector<double> e, ew;
+  for (const TreeCell & c : C1)
+    if (c.leaf) {
+      e.push_back (err[c.rec]);
+      ew.push_back (weighted ? volume (c) : 1.);
+    }
   double shift = 0.;
   if (constant) {
     double sum = 0., weight = 0.;
-    for (double x : e) { sum += w*x; weight += w; }
+    for (size_t q = 0; q < e.size (); q++) { sum += ew[q]*e[q]; weight += ew[q]; }
     shift = weight > 0. ? sum/weight : 0.;
   }
   Norm n;
-  for (double x : e) {
-    norm_add (n, x - shift, w);
-    if (histogram) printf ("%g %g\n", x, 1.);
+  for (size_t q = 0; q < e.size (); q++) {
+    norm_add (n, e[q] - shift, ew[q]);
+    if (histogram) printf ("%g %g\n", e[q], 1.);
   }
   norm_update (n);
   if (verbose)

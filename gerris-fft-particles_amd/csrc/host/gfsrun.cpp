@@ -38,6 +38,7 @@
 #include "gfship.h"
 #include "gfs_text.hpp"
 #include "gfs_snapshot.hpp"
+#include <unordered_map>
 #include "gfs_function.hpp"
 
 using namespace gfs;
@@ -566,6 +567,30 @@ void write_simulation (Run & R, FILE * fp, const std::vector<int> & list, bool b
     fprintf (fp, "  %s\n", ot.second.c_str ());
   }
   fputs ("}\n", fp);
+  if (R.tree_mode) {
+    // a refined tree: the image of gfship_tree_snapshot_write, every cell of every level (the non-leaf cells
+    // hold the result of the last gfs_cell_coarse_init); size = the number of leaves (box_size, src/boundary.c:1814-1831)
+    std::vector<int> tv;
+    for (int q : list) {
+      if (R.vars[q].dev < 0) {
+	fprintf (stderr, "gfship: GfsOutputSimulation: the variable `%s' is not kept on a refined tree\n", R.vars[q].name.c_str ());
+	exit (1);
+      }
+      tv.push_back (R.vars[q].dev);
+    }
+    std::string image (gfship_tree_snapshot_bytes (R.tree, (int) tv.size ()), '\0');
+    if (image.empty ()) CHECK (-1);
+    CHECK (gfship_tree_snapshot_write (R.tree, (int) tv.size (), tv.data (), &image[0], image.size ()));
+    fprintf (fp, "GfsBox { id = 1 pid = -1 size = %zu x = 0 y = 0 z = 0%s%s } {\n", R.leaf_l.size (),
+	     R.box_text.empty () ? "" : " ", R.box_text.c_str ());
+    if (binary)
+      fwrite (image.data (), 1, image.size (), fp);
+    else
+      gfs::tree_write_text (fp, image, tv.size ());
+    fputs ("}\n", fp);
+    fputs (R.edges_text.c_str (), fp);
+    return;
+  }
   // the cell data: device variables straight from the device image; host-only variables (Div of a
   // GfsPoisson file ...) go through a temporary device variable
   std::vector<gfship_field> f, tmp;
@@ -1700,6 +1725,30 @@ double refine_hook (double x, double y, double z, void * ctx)
   return eval (R, R.refine_fn, p, -1);
 }
 
+// a file that carries its tree (cell_read, src/ftt.c:1807-1866: the tree of the file IS the tree): the hook is
+// asked at the centre of a cell, -0.5 + (i + 0.5)/2^l, which identifies l; a cell the file refines asks for one
+// level more
+struct FileTree {
+  int dim;
+  std::unordered_map<uint64_t, bool> leaf;      // cell -> leaf bit
+  static uint64_t key (int l, int i, int j, int k) {
+    return ((((uint64_t) l << 19 | (uint64_t) k) << 19 | (uint64_t) j) << 19) | (uint64_t) i;
+  }
+};
+
+double file_refine_hook (double x, double y, double z, void * ctx)
+{
+  const FileTree & F = *(const FileTree *) ctx;
+  for (int l = 0; l <= 19; l++) {
+    const double n = (double) (1 << l), i = (x + 0.5)*n - 0.5;
+    if (i != floor (i)) continue;
+    const double j = (y + 0.5)*n - 0.5, k = F.dim == 3 ? (z + 0.5)*n - 0.5 : 0.;
+    auto c = F.leaf.find (FileTree::key (l, (int) i, (int) j, (int) k));
+    return c != F.leaf.end () && !c->second ? l + 1 : l;
+  }
+  return 0.;
+}
+
 // the leaves of the tree in the order of ftt_cell_traverse (pre-order, children 0..3: bit 0 = +x,
 // bit 1 = -y, src/ftt.c:301-316)
 void tree_leaves (Run & R, const std::vector<std::vector<unsigned char>> & flag, int l, int i, int j, int k)
@@ -1851,14 +1900,14 @@ int run_tree (Run & R)
   if (!R.plists.empty ()) return refuse ("a particle list");
   if (!R.init_spectra.empty ()) return refuse ("GfsInitSpectra");
   if (!R.device_vars.empty ()) return refuse ("a turbulent-viscosity variable");
-  if (R.snapshot.has_tree) return refuse ("cell data in the simulation file");
   if (R.dtmax != DBL_MAX) return refuse ("Time { dtmax }");
   for (auto & kv : R.adv_set)
     if (kv.first != "cfl" && !(kv.first == "gradient" && kv.second == "gfs_center_gradient") &&
 	!(kv.first == "gc" && atoi (kv.second.c_str ()) == 1))
       return refuse ("this AdvectionParams setting");
   static const char * ok[] = { "OutputErrorNorm", "OutputScalarNorm", "OutputScalarSum", "OutputScalarStats",
-			       "OutputTime", "OutputProjectionStats", "EventScript", "EventStop" };
+			       "OutputTime", "OutputProjectionStats", "EventScript", "EventStop",
+			       "OutputSimulation" };
   for (auto & e : R.events) {
     bool found = false;
     for (const char * c : ok) if (e->cls == c) found = true;
@@ -1903,12 +1952,54 @@ int run_tree (Run & R)
       }
     }
   open_pipes (R);
-  CHECK (gfship_tree_create_sides (&R.tree, R.dim, refine_hook, &R, R.side, R.device));
+  FileTree ft;
+  if (R.snapshot.has_tree) {
+    if (R.snapshot.depth > 19) return refuse ("a file with more than 19 levels");
+    ft.dim = R.dim;
+    for (const gfs::TreeCell & c : R.snapshot.cells)
+      ft.leaf[FileTree::key (c.level, c.i, c.j, c.k)] = c.leaf;
+    if (R.refine_fn)      /* gfs_simulation_refine after the file is read: it must find nothing to add */
+      for (const gfs::TreeCell & c : R.snapshot.cells) {
+	const double h = 1./(1 << c.level);
+	double p[3] = { -0.5 + (c.i + 0.5)*h, -0.5 + (c.j + 0.5)*h, R.dim == 3 ? -0.5 + (c.k + 0.5)*h : 0. };
+	if (c.leaf && c.level < eval (R, R.refine_fn, p, -1)) {
+	  fprintf (stderr, "gfship: line %d: GfsRefine asks for more than the tree of the file holds "
+		   "(a restart into another tree is not supported)\n", R.refine_line);
+	  return 1;
+	}
+      }
+    CHECK (gfship_tree_create_sides (&R.tree, R.dim, file_refine_hook, &ft, R.side, R.device));
+  }
+  else
+    CHECK (gfship_tree_create_sides (&R.tree, R.dim, refine_hook, &R, R.side, R.device));
   int depth = gfship_tree_depth (R.tree);
   std::vector<std::vector<unsigned char>> flag (depth + 1);
   for (int l = 0; l <= depth; l++) {
     flag[l].resize (R.tree_level_size (l));
     CHECK (gfship_tree_flags (R.tree, l, flag[l].data ()));
+  }
+  if (R.snapshot.has_tree) {
+    // the tree the library built must be the tree of the file: the balance (oct_new with check_neighbors) and
+    // the corner rule would otherwise have added cells
+    size_t cells = 0;
+    bool same = true;
+    for (int l = 0; l <= depth; l++) {
+      const size_t r = (1 << l) + 2;
+      for (int k = 1; k <= (R.dim == 3 ? 1 << l : 1); k++)
+	for (int j = 1; j <= 1 << l; j++)
+	  for (int i = 1; i <= 1 << l; i++) {
+	    const unsigned char f = flag[l][i + r*(j + (R.dim == 3 ? r*k : 0))];
+	    if (!f) continue;
+	    cells++;
+	    auto c = ft.leaf.find (FileTree::key (l, i - 1, j - 1, R.dim == 3 ? k - 1 : 0));
+	    if (c == ft.leaf.end () || c->second != (f == 1)) same = false;
+	  }
+    }
+    if (!same || cells != R.snapshot.cells.size ()) {
+      fprintf (stderr, "gfship: the tree of the file is not one this program builds (%zu cells in the file, %zu "
+	       "after the 2:1 balance and the corner rule)\n", R.snapshot.cells.size (), cells);
+      return 1;
+    }
   }
   tree_leaves (R, flag, 0, 1, 1, 1);
   R.vars[R.var_index ("P")].dev = GFSHIP_TREE_P;
@@ -1945,6 +2036,23 @@ int run_tree (Run & R)
   for (auto & kv : R.adv_set)
     if (kv.first == "cfl") cfl = atof (kv.second.c_str ());
   apply_init (R);
+  if (R.snapshot.has_tree) {
+    // gfs_box_read -> cell_read[_binary] + gfs_cell_read[_binary]: all levels of the variables of the file; then the
+    // branch time.i > 0 of simulation_run
+    std::vector<int> tv;
+    for (const std::string & nm : R.snapshot.variables) {
+      int q = R.var_index (nm);
+      if (q < 0 || R.vars[q].dev < 0) {
+	fprintf (stderr, "gfship: the variable `%s' of the file is not kept on a refined tree\n", nm.c_str ());
+	return 1;
+      }
+      tv.push_back (R.vars[q].dev);
+      R.vars[q].host_time = -1.;
+    }
+    CHECK (gfship_tree_snapshot_read (R.tree, (int) tv.size (), tv.data (), R.snapshot.tree.data (), R.snapshot.tree.size ()));
+    R.snapshot.tree.clear ();
+    CHECK (gfship_tree_restart (R.tree, R.t, R.i));
+  }
   events_init (R);
   CHECK (gfship_tree_set_time (R.tree, R.end, cfl));
   CHECK (gfship_tree_set_next_event (R.tree, next_event_hook, &R));
@@ -2384,7 +2492,18 @@ int main (int argc, char ** argv)
     R.snapshot.text.clear ();
     for (const std::string & nm : R.snapshot.variables)
       R.get_or_add_variable (nm);        /* gfs_domain_add_variable of domain_read, src/domain.c:283-293 */
-    if (R.snapshot.has_tree && R.level == 0 && R.snapshot.depth > 0)
+    if (R.snapshot.has_tree && !R.snapshot.uniform) {
+      /* the tree of the file is the tree (cell_read, src/ftt.c:1807-1866): gfship_tree */
+      if (R.sim_class != "Simulation") {
+	fprintf (stderr, "gfship: cell data on a refined tree is read for a GfsSimulation only\n");
+	return 1;
+      }
+      R.tree_mode = true;
+      R.level = R.snapshot.depth;
+      for (const gfs::TreeCell & c : R.snapshot.cells)
+	if (c.leaf && c.level < R.level) R.level = c.level;      /* the coarsest leaves */
+    }
+    else if (R.snapshot.has_tree && R.level == 0 && R.snapshot.depth > 0)
       R.level = R.snapshot.depth;        /* no GfsRefine in a file that carries its tree */
     return check_only ? check (R) : run (R);
   }

@@ -157,6 +157,13 @@ struct gfship_tree {
   gfship_multilevel_params diffusion_params[3];
   double src[3] = { 0., 0., 0. };   // GfsSource {} U|V|W g: constant intensities
   int diffusion_exact = -1;         // octrees: every diffusion coefficient the stencils read is w (-1: not checked yet)
+  // the file image of the tree (gfship_tree_snapshot_*), built on first use: every interior cell (the leaves, then
+  // the non-leaf cells level by level) and, per cell of the dense levels, the index of its record in the pre-order
+  // of ftt_cell_write
+  Cell * snap_cells = nullptr; int snap_ncells = 0;
+  unsigned long long * snap_off = nullptr;
+  unsigned long long snap_records = 0;
+  bool restarted = false;           // gfship_tree_restart with i > 0: gfship_tree_start takes the branch time.i > 0
 };
 
 namespace {
@@ -2248,6 +2255,8 @@ int gather_un (gfship_tree * tr, int kind, int dmask)
   return 0;
 }
 
+int correct_normal_velocities (gfship_tree * tr, const double * p, int gvar, double dt);
+
 // mac_projection, src/timestep.c:356-444
 int mac_projection (gfship_tree * tr, gfship_multilevel_params * par, double dt, double * p, int gvar)
 {
@@ -2258,6 +2267,15 @@ int mac_projection (gfship_tree * tr, gfship_multilevel_params * par, double dt,
   t_divergence<<<blocks (tr->nleaves), 256, 0, tr->stream>>> (tr->D, tr->leaves, tr->nleaves, p6 (tr, V_UN), tr->var[V_DIV], dt);
   KCHECK ();
   if ((e = poisson_solve (tr, par, p, tr->var[V_DIV], dt))) return e;
+  return correct_normal_velocities (tr, p, gvar, dt);
+}
+
+// gfs_correct_normal_velocities + gfs_scale_gradients + the conditions of g: the end of mac_projection, and with
+// dt = 0 (the face velocities stay as they are) gfs_update_gradients, src/timestep.c:305-322
+int correct_normal_velocities (gfship_tree * tr, const double * p, int gvar, double dt)
+{
+  int e;
+  const int dim = tr->H.dim;
   // gfs_correct_normal_velocities, src/timestep.c:163-179: FTT_XY (the x faces, then the y faces) in
   // 2-D, FTT_XYZ (one traversal) in 3-D
   for (int k = 0; k < (dim == 2 ? 2 : 1); k++) {
@@ -2534,9 +2552,186 @@ int coarse_init (gfship_tree * tr)   /* src/adaptive.c:43-58 */
   return from_below_n (tr, V, nv);
 }
 
+
+// ---- the file image of the tree ------------------------------------------------------------------
+// ftt_cell_write_binary (src/ftt.c:1771-1799) walks the tree in pre-order, children n = 0 .. FTT_CELLS - 1, and
+// writes per cell `guint flags' = child id | FTT_FLAG_LEAF on every leaf, then gfs_cell_write_binary
+// (src/domain.c:3176-3207): a double -1. (no solid fractions) and one double per variable.  On a refined tree the
+// position of a record is not a closed form of the coordinates: the sizes of the subtrees are summed bottom-up, the
+// offsets handed down top-down, one launch per level each, once per tree.
+
+#define TSNAP_FLAG_LEAF 16u          /* FTT_FLAG_LEAF = 1 << 4, src/ftt.h:115 */
+#define TSNAP_MAXVARS 16
+
+struct SnapVars { double * v[TSNAP_MAXVARS]; int nvars; };
+
+__global__ void t_snap_sub_leaves (Topo T, const Cell * cells, int n, unsigned long long * sub)
+{
+  int t = blockIdx.x*blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  sub[T.gi (cells[t])] = 1;
+}
+
+__global__ void t_snap_sub (Topo T, const Cell * cells, int n, unsigned long long * sub)
+{
+  int t = blockIdx.x*blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const Cell c = cells[t];
+  unsigned long long s = 1;
+  for (int k = 0; k < T.nc (); k++) {
+    const Cell ch = T.child (c, k);
+    if (exists (ch))
+      s += sub[T.gi (ch)];
+  }
+  sub[T.gi (c)] = s;
+}
+
+__global__ void t_snap_off (Topo T, const Cell * cells, int n, const unsigned long long * sub, unsigned long long * off)
+{
+  int t = blockIdx.x*blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const Cell c = cells[t];
+  unsigned long long o = off[T.gi (c)] + 1;
+  for (int k = 0; k < T.nc (); k++) {
+    const Cell ch = T.child (c, k);
+    if (exists (ch)) {
+      off[T.gi (ch)] = o;
+      o += sub[T.gi (ch)];
+    }
+  }
+}
+
+// records are multiples of 4 bytes: 4-byte accesses
+__device__ __forceinline__ void tsnap_put_u32 (unsigned char * p, unsigned v) { *(unsigned *) p = v; }
+__device__ __forceinline__ unsigned tsnap_get_u32 (const unsigned char * p) { return *(const unsigned *) p; }
+__device__ __forceinline__ void tsnap_put_f64 (unsigned char * p, double v)
+{
+  const unsigned long long b = (unsigned long long) __double_as_longlong (v);
+  tsnap_put_u32 (p, (unsigned) b);
+  tsnap_put_u32 (p + 4, (unsigned) (b >> 32));
+}
+__device__ __forceinline__ double tsnap_get_f64 (const unsigned char * p)
+{
+  const unsigned long long b = (unsigned long long) tsnap_get_u32 (p) | ((unsigned long long) tsnap_get_u32 (p + 4) << 32);
+  return __longlong_as_double ((long long) b);
+}
+
+// one thread per cell of the tree
+template <bool READ>
+__global__ void __launch_bounds__(256)
+t_snapshot (Topo T, const Cell * cells, int n, const unsigned long long * off, SnapVars V, unsigned char * image,
+	    unsigned long long * err)
+{
+  int t = blockIdx.x*blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const Cell c = cells[t];
+  const int g = T.gi (c);
+  const unsigned rec = 12u + 8u*V.nvars;
+  unsigned char * p = image + off[g]*rec;
+  const unsigned id = c.l == 0 ? 0u : (unsigned) T.id (c);       /* the root has no FTT_FLAG_ID */
+  const bool leaf = T.flag[g] == LEAF;
+  if (READ) {
+    // cell_read_binary (src/ftt.c:1915-1945): the child id must match; the tree of the file must be this
+    // tree; no solid fractions (gfs_cell_read_binary, src/domain.c:3227-3236)
+    // a sequential reader stops at the first record it cannot take: *err keeps the least 4*record + kind of
+    // error (0: child id, 1: leaf bit, 2: solid fraction)
+    const unsigned f = tsnap_get_u32 (p);
+    if ((f & 7u) != id) atomicMin (err, 4ull*off[g]);
+    else if (((f & TSNAP_FLAG_LEAF) != 0) != leaf) atomicMin (err, 4ull*off[g] + 1);
+    else if (tsnap_get_f64 (p + 4) != -1.) atomicMin (err, 4ull*off[g] + 2);
+    for (int v = 0; v < V.nvars; v++)
+      V.v[v][g] = tsnap_get_f64 (p + 12 + 8*v);
+  }
+  else {
+    tsnap_put_u32 (p, id | (leaf ? TSNAP_FLAG_LEAF : 0u));
+    tsnap_put_f64 (p + 4, -1.);
+    for (int v = 0; v < V.nvars; v++)
+      tsnap_put_f64 (p + 12 + 8*v, V.v[v][g]);
+  }
+}
+
+void snapshot_tables_free (gfship_tree * tr)
+{
+  (void) hipFree (tr->snap_cells); tr->snap_cells = nullptr;
+  (void) hipFree (tr->snap_off); tr->snap_off = nullptr;
+  tr->snap_ncells = 0;
+  tr->snap_records = 0;
+}
+
+int snapshot_tables (gfship_tree * tr)
+{
+  if (tr->snap_off) return 0;
+  GFSHIP_HIP (hipSetDevice (tr->device));
+  const Topo & T = tr->H;
+  int ncells = tr->nleaves;
+  for (int l = 0; l < T.depth; l++) ncells += tr->nnonleaf[l];
+  unsigned long long * sub = nullptr;
+  auto fail = [&] (hipError_t e, const char * what) {
+    (void) hipFree (sub);
+    snapshot_tables_free (tr);
+    return hip_fail (e, what, __FILE__, __LINE__);
+  };
+#define SNAPHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail (e_, #call); } while (0)
+  SNAPHIP (hipMalloc ((void **) &tr->snap_cells, (size_t) ncells*sizeof (Cell)));
+  SNAPHIP (hipMalloc ((void **) &tr->snap_off, (size_t) tr->ncell*sizeof (unsigned long long)));
+  SNAPHIP (hipMalloc ((void **) &sub, (size_t) tr->ncell*sizeof (unsigned long long)));
+  SNAPHIP (hipMemsetAsync (sub, 0, (size_t) tr->ncell*sizeof (unsigned long long), tr->stream));
+  SNAPHIP (hipMemsetAsync (tr->snap_off, 0, (size_t) tr->ncell*sizeof (unsigned long long), tr->stream));
+  int at = 0;
+  SNAPHIP (hipMemcpyAsync (tr->snap_cells, tr->leaves, (size_t) tr->nleaves*sizeof (Cell), hipMemcpyDeviceToDevice, tr->stream));
+  at += tr->nleaves;
+  for (int l = 0; l < T.depth; l++)
+    if (tr->nnonleaf[l]) {
+      SNAPHIP (hipMemcpyAsync (tr->snap_cells + at, tr->nonleaf[l], (size_t) tr->nnonleaf[l]*sizeof (Cell),
+			       hipMemcpyDeviceToDevice, tr->stream));
+      at += tr->nnonleaf[l];
+    }
+  t_snap_sub_leaves<<<blocks (tr->nleaves), 256, 0, tr->stream>>> (tr->D, tr->leaves, tr->nleaves, sub);
+  SNAPHIP (hipGetLastError ());
+  for (int l = T.depth - 1; l >= 0; l--)
+    if (tr->nnonleaf[l]) {
+      t_snap_sub<<<blocks (tr->nnonleaf[l]), 256, 0, tr->stream>>> (tr->D, tr->nonleaf[l], tr->nnonleaf[l], sub);
+      SNAPHIP (hipGetLastError ());
+    }
+  for (int l = 0; l < T.depth; l++)
+    if (tr->nnonleaf[l]) {
+      t_snap_off<<<blocks (tr->nnonleaf[l]), 256, 0, tr->stream>>> (tr->D, tr->nonleaf[l], tr->nnonleaf[l], sub, tr->snap_off);
+      SNAPHIP (hipGetLastError ());
+    }
+  unsigned long long records = 0;
+  const Cell root = root_cell (T);
+  SNAPHIP (hipMemcpyAsync (&records, sub + T.gi (root), sizeof (records), hipMemcpyDeviceToHost, tr->stream));
+  SNAPHIP (hipStreamSynchronize (tr->stream));
+#undef SNAPHIP
+  (void) hipFree (sub);
+  if (records != (unsigned long long) ncells) {      /* every interior cell is in exactly one list */
+    snapshot_tables_free (tr);
+    set_error ("gfship_tree_snapshot: %llu records for %d cells", records, ncells);
+    return GFSHIP_EINVAL;
+  }
+  tr->snap_ncells = ncells;
+  tr->snap_records = records;
+  return 0;
+}
+
+int snapshot_vars (gfship_tree * tr, int nvars, const int * vars, SnapVars * V)
+{
+  GFSHIP_CHECK (tr && (vars || nvars == 0), GFSHIP_EINVAL, "gfship_tree_snapshot: null argument");
+  GFSHIP_CHECK (nvars >= 0 && nvars <= TSNAP_MAXVARS, GFSHIP_EINVAL, "at most %d variables", TSNAP_MAXVARS);
+  V->nvars = nvars;
+  for (int v = 0; v < nvars; v++) {
+    GFSHIP_CHECK (vars[v] >= 0 && vars[v] < abi_nvar, GFSHIP_EINVAL, "gfship_tree_snapshot: variable %d", vars[v]);
+    GFSHIP_CHECK (vars[v] < GFSHIP_TREE_T0 || vars[v] > GFSHIP_TREE_T1 || vars[v] - GFSHIP_TREE_T0 < tr->ntracers,
+		  GFSHIP_EINVAL, "gfship_tree_snapshot: the tree has no tracer T%d", vars[v] - GFSHIP_TREE_T0);
+    V->v[v] = tr->var[abi_var[vars[v]]];
+  }
+  return 0;
+}
+
 void tree_free (gfship_tree * tr)
 {
   if (!tr) return;
+  snapshot_tables_free (tr);
   (void) hipFree (tr->dflag);
   (void) hipFree (tr->d_nbtab); (void) hipFree (tr->d_child0); (void) hipFree (tr->d_cmask); (void) hipFree (tr->d_idtab);
   for (double * p : tr->var) (void) hipFree (p);
@@ -3205,9 +3400,99 @@ int gfship_tree_start (gfship_tree * tr)
     if ((e = bc_scalar (tr, tr->var[V_T + k]))) return e;
   if ((e = coarse_init (tr))) return e;
   if ((e = set_timestep (tr))) return e;
+  if (tr->restarted) {
+    /* time.i > 0, src/simulation.c:475-476: no projection, no half step of the tracers; gfs_update_gradients
+       (src/timestep.c:305-322) rebuilds g from P, which the first iteration reads */
+    for (int c = 0; c < tr->H.dim; c++)
+      GFSHIP_HIP (hipMemsetAsync (tr->var[V_G + c], 0, tr->ncell*sizeof (double), tr->stream));
+    return correct_normal_velocities (tr, tr->var[V_P], V_G, 0.);
+  }
   if ((e = approximate_projection (tr, &tr->approx_projection_params, tr->dt))) return e;
   if ((e = set_timestep (tr))) return e;
   return advance_tracers (tr, tr->dt/2.);
+}
+
+/* a simulation read from a file with GfsTime { i = ... t = ... }: the state comes from gfship_tree_snapshot_read,
+   gfship_tree_start then takes the branch time.i > 0 of simulation_run (src/simulation.c:456-476) */
+int gfship_tree_restart (gfship_tree * tr, double t, unsigned i)
+{
+  GFSHIP_CHECK (tr, GFSHIP_EINVAL, "gfship_tree_restart: null tree");
+  tr->t = tr->tnext = t;
+  tr->iter = i;
+  tr->restarted = i > 0;
+  return GFSHIP_OK;
+}
+
+/* ftt_cell_write_binary + gfs_cell_write_binary (src/ftt.c:1771-1799, src/domain.c:3176-3207): the bytes between
+   the braces of a GfsBox with `binary = 1', for the variables `vars' (GFSHIP_TREE_*) in that order */
+size_t gfship_tree_snapshot_bytes (const gfship_tree * ctr, int nvars)
+{
+  gfship_tree * tr = const_cast<gfship_tree *> (ctr);      /* the tables are a cache */
+  if (!tr || nvars < 0 || snapshot_tables (tr)) return 0;
+  return (size_t) (tr->snap_records*(12ull + 8ull*(unsigned long long) nvars));
+}
+
+int gfship_tree_snapshot_write (gfship_tree * tr, int nvars, const int * vars, void * host_buf, size_t bytes)
+{
+  SnapVars V;
+  int e;
+  if ((e = snapshot_vars (tr, nvars, vars, &V))) return e;
+  GFSHIP_HIP (hipSetDevice (tr->device));
+  if ((e = snapshot_tables (tr))) return e;
+  const size_t need = gfship_tree_snapshot_bytes (tr, nvars);
+  GFSHIP_CHECK (host_buf && bytes >= need, GFSHIP_EINVAL, "the buffer must hold %zu bytes", need);
+  unsigned char * image = nullptr;
+  GFSHIP_HIP (hipMalloc ((void **) &image, need));
+  t_snapshot<false><<<blocks (tr->snap_ncells), 256, 0, tr->stream>>> (tr->D, tr->snap_cells, tr->snap_ncells, tr->snap_off,
+      V, image, (unsigned long long *) nullptr);
+  hipError_t he = hipGetLastError ();
+  if (he == hipSuccess)
+    he = hipMemcpyAsync (host_buf, image, need, hipMemcpyDeviceToHost, tr->stream);
+  if (he == hipSuccess)
+    he = hipStreamSynchronize (tr->stream);
+  (void) hipFree (image);
+  GFSHIP_HIP (he);
+  return GFSHIP_OK;
+}
+
+/* cell_read_binary + gfs_cell_read_binary (src/ftt.c:1913-1975, src/domain.c:3227-3250) into a tree that already
+   has the refinement of the file: every record is checked against it */
+int gfship_tree_snapshot_read (gfship_tree * tr, int nvars, const int * vars, const void * host_buf, size_t bytes)
+{
+  SnapVars V;
+  int e;
+  if ((e = snapshot_vars (tr, nvars, vars, &V))) return e;
+  GFSHIP_HIP (hipSetDevice (tr->device));
+  if ((e = snapshot_tables (tr))) return e;
+  const size_t need = gfship_tree_snapshot_bytes (tr, nvars);
+  GFSHIP_CHECK (host_buf != nullptr, GFSHIP_EINVAL, "null buffer");
+  GFSHIP_CHECK (bytes == need, GFSHIP_EINVAL,
+		"the cell data of this tree (%llu cells) with %d variables is %zu bytes, not %zu",
+		tr->snap_records, nvars, need, bytes);
+  unsigned char * image = nullptr;
+  GFSHIP_HIP (hipMalloc ((void **) &image, need + 16));
+  unsigned long long * err = (unsigned long long *) (image + ((need + 7) & ~(size_t) 7));
+  unsigned long long herr = ~0ull;
+  hipError_t he = hipMemsetAsync (err, 0xff, sizeof (herr), tr->stream);
+  if (he == hipSuccess)
+    he = hipMemcpyAsync (image, host_buf, need, hipMemcpyHostToDevice, tr->stream);
+  if (he == hipSuccess) {
+    t_snapshot<true><<<blocks (tr->snap_ncells), 256, 0, tr->stream>>> (tr->D, tr->snap_cells, tr->snap_ncells, tr->snap_off,
+	V, image, err);
+    he = hipGetLastError ();
+  }
+  if (he == hipSuccess)
+    he = hipMemcpyAsync (&herr, err, sizeof (herr), hipMemcpyDeviceToHost, tr->stream);
+  if (he == hipSuccess)
+    he = hipStreamSynchronize (tr->stream);
+  (void) hipFree (image);
+  GFSHIP_HIP (he);
+  const int kind = herr == ~0ull ? -1 : (int) (herr & 3);
+  GFSHIP_CHECK (kind != 0, GFSHIP_EINVAL,
+		"FTT_CELL_ID (cell) != (flags & FTT_FLAG_ID): make sure the file has %d spatial dimensions", tr->H.dim);
+  GFSHIP_CHECK (kind != 1, GFSHIP_EUNSUPPORTED, "the tree of the file is not the tree of this simulation");
+  GFSHIP_CHECK (kind != 2, GFSHIP_EUNSUPPORTED, "the file has solid fractions (mixed cells)");
+  return GFSHIP_OK;
 }
 
 /* one iteration of the loop, src/simulation.c:479-548 */

@@ -178,6 +178,10 @@ SIGNATURES = {
     "gfship_tree_diffusion_params": (C.POINTER(MultilevelParams), [_vp, _i]),
     "gfship_tree_start": (_i, [_vp]),
     "gfship_tree_step": (_i, [_vp]),
+    "gfship_tree_snapshot_bytes": (C.c_size_t, [_vp, _i]),
+    "gfship_tree_snapshot_write": (_i, [_vp, _i, _pi, _vp, C.c_size_t]),
+    "gfship_tree_snapshot_read": (_i, [_vp, _i, _pi, _vp, C.c_size_t]),
+    "gfship_tree_restart": (_i, [_vp, _d, _u]),
     "gfship_tree_sweep_levels": (_i, [_vp, _i, _pi, _pi]),
     "gfship_tree_divergence": (_i, [_vp]),
     "gfship_tree_host_check": (_i, [_i, C.c_void_p, _vp, _pi, _u, C.POINTER(C.c_longlong)]),
@@ -798,6 +802,27 @@ class Tree:
 
     def step(self):
         _check(lib().gfship_tree_step(self.ptr))
+
+    def snapshot(self, variables):
+        """the binary cell data of the GfsBox (gfship_tree_snapshot_write) for the variables (Tree.P ...) as bytes"""
+        n = len(variables)
+        h = (C.c_int * n)(*variables)
+        size = lib().gfship_tree_snapshot_bytes(self.ptr, n)
+        if size == 0:
+            _check(-1)
+        buf = C.create_string_buffer(size)
+        _check(lib().gfship_tree_snapshot_write(self.ptr, n, h, buf, size))
+        return buf.raw
+
+    def snapshot_read(self, variables, data):
+        n = len(variables)
+        h = (C.c_int * n)(*variables)
+        buf = C.create_string_buffer(bytes(data), len(data))
+        _check(lib().gfship_tree_snapshot_read(self.ptr, n, h, buf, len(data)))
+
+    def restart(self, t, i):
+        """GfsTime { t = i = } of a simulation file: start() then takes the branch time.i > 0"""
+        _check(lib().gfship_tree_restart(self.ptr, t, i))
 
     def set_bc(self, d, kind):
         _check(lib().gfship_tree_set_bc(self.ptr, d, kind))

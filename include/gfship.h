@@ -606,6 +606,23 @@ int  gfship_tree_set_source (gfship_tree * tree, int c, double g);
 gfship_multilevel_params * gfship_tree_diffusion_params (gfship_tree * tree, int c);
 int  gfship_tree_start (gfship_tree * tree);
 int  gfship_tree_step (gfship_tree * tree);
+/* The cell data of a simulation file of a refined tree: what gfs_box_write puts between the braces of a GfsBox
+   with `binary = 1' -- ftt_cell_write_binary (src/ftt.c:1771-1799: pre-order, children 0 .. FTT_CELLS - 1, per
+   cell `guint flags' = child id | FTT_FLAG_LEAF on every leaf) and gfs_cell_write_binary (src/domain.c:3176-3207:
+   a double -1., then one double per variable).  vars: GFSHIP_TREE_* (tracers included), in file order.  The
+   records of the non-leaf cells hold what those cells hold: the result of the last gfs_cell_coarse_init.
+     gfship_tree_snapshot_bytes: the size of the image (0 on error); builds and caches the offset tables;
+     gfship_tree_snapshot_write: builds the image on the device and copies it into host_buf;
+     gfship_tree_snapshot_read: cell_read_binary + gfs_cell_read_binary (src/ftt.c:1913-1975, src/domain.c:3227-3250)
+       into a tree of the same refinement; `bytes' must be gfship_tree_snapshot_bytes; fails if a child id
+       (GFSHIP_EINVAL), a leaf bit or a solid fraction (GFSHIP_EUNSUPPORTED) is not that of this tree;
+     gfship_tree_restart: GfsTime { t = i = } of the file; with i > 0 gfship_tree_start takes the branch
+       time.i > 0 of simulation_run (src/simulation.c:456-476): conditions, gfs_cell_coarse_init, the time step
+       and gfs_update_gradients (src/timestep.c:305-322) -- no projection, no half step of the tracers. */
+size_t gfship_tree_snapshot_bytes (const gfship_tree * tree, int nvars);
+int  gfship_tree_snapshot_write (gfship_tree * tree, int nvars, const int * vars, void * host_buf, size_t bytes);
+int  gfship_tree_snapshot_read (gfship_tree * tree, int nvars, const int * vars, const void * host_buf, size_t bytes);
+int  gfship_tree_restart (gfship_tree * tree, double t, unsigned i);
 /* the derived variable `Divergence' (gfs_divergence, src/fluid.c:2357-2376, with
    gfs_face_interpolated_value_generic :2200-2221) of the leaves into GFSHIP_TREE_DIV */
 int  gfship_tree_divergence (gfship_tree * tree);

@@ -2,8 +2,12 @@
 """Time steps of the refined-tree path (gfship_tree) on an octree / quadtree with BOX
 extra levels inside the central cube / square: leaves, dependency levels of the finest sweep, ms per
 step, Mleaf-steps/s.  Not the benchmarked path (that is bench.py); a measurement to quote.
-usage: tree_bench.py [dim] [level] [box] [steps] [nu]
-nu: GfsSourceDiffusion on every velocity component (default 0: inviscid)"""
+usage: tree_bench.py [dim] [level] [box] [steps] [nu] [--snapshot]
+nu: GfsSourceDiffusion on every velocity component (default 0: inviscid)
+--snapshot: also time the file image of the tree (gfship_tree_snapshot_write) for P, Pmac, U, V
+(, W): the first call, which builds the offset tables, and the median of 20 more (kernel + copy to the host),
+ending in the stream synchronise of the call.  The share of the kernel and of the copy comes from a kernel and
+memory-copy trace of the same command."""
 import os
 import sys
 import time
@@ -14,6 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gerris-fft-particles_amd"))
 import gfship
 
+snapshot = "--snapshot" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--snapshot"]
 dim = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 level = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 box = int(sys.argv[3]) if len(sys.argv) > 3 else 2
@@ -53,9 +59,26 @@ for _ in range(steps):
     g.step()
 ms = (time.time() - t0) / steps * 1e3
 nc, nl = g.sweep_levels(g.depth)
+snap = {}
+if snapshot:
+    vars_ = [g.P, g.PMAC, g.U, g.V] + ([g.W] if dim == 3 else [])
+    t0 = time.time()
+    image = g.snapshot(vars_)
+    first = (time.time() - t0) * 1e3
+    times = []
+    for _ in range(20):
+        t0 = time.time()
+        g.snapshot(vars_)
+        times.append((time.time() - t0) * 1e3)
+    ncells = len(image) // (12 + 8 * len(vars_))
+    snap = {"snapshot_cells": ncells, "snapshot_image_bytes": len(image),
+            "snapshot_bytes_moved": len(image) + 8 * len(vars_) * ncells,
+            "snapshot_first_ms": round(first, 3), "snapshot_ms": round(sorted(times)[len(times) // 2], 3),
+            "snapshot_ms_min_max": [round(min(times), 3), round(max(times), 3)]}
 print({"dim": dim, "levels": [level, g.depth], "leaves": nleaves, "finest_sweep_cells": nc,
        "finest_sweep_dependency_levels": nl, "tree_build_s": round(t_build, 2),
        "ms_per_step": round(ms, 2), "Mleaf_steps_per_s": round(nleaves / ms / 1e3, 3),
        "niter": [g.projection_params.niter, g.approx_projection_params.niter],
+       **snap,
        **({"nu": nu, "diffusion_niter": [g.diffusion_params(c).niter for c in range(dim)]} if nu != 0. else {})})
 g.destroy()
