@@ -193,6 +193,7 @@ int gfship_diffusion_rhs (gfship_domain * dom, gfship_field v, gfship_field rhs,
   Field * V = get_field (dom, v), * R = get_field (dom, rhs), * C = get_field (dom, rhoc);
   if (!V || !R || !C) return GFSHIP_EINVAL;
   GFSHIP_CHECK (dom->diff_ready, GFSHIP_EINVAL, "call gfship_diffusion_coefficients first");
+  { int r = before_write (dom); if (r) return r; }
   const int L = dom->depth;
   dim3 grid, block;
   cell_grid (dom->lay[L], &grid, &block);
@@ -209,6 +210,7 @@ int gfship_diffusion_residual (gfship_domain * dom, gfship_field u, gfship_field
     * S = get_field (dom, res);
   if (!U || !R || !C || !S) return GFSHIP_EINVAL;
   GFSHIP_CHECK (dom->diff_ready, GFSHIP_EINVAL, "call gfship_diffusion_coefficients first");
+  { int r = before_write (dom); if (r) return r; }
   return residual (dom, U, R, C, S);
 }
 
@@ -219,6 +221,7 @@ int gfship_diffusion_cycle (gfship_domain * dom, unsigned levelmin, unsigned dep
   GFSHIP_CHECK (dom != nullptr, GFSHIP_EINVAL, "null domain");
   GFSHIP_CHECK (dom->diff_ready, GFSHIP_EINVAL, "call gfship_diffusion_coefficients first");
   GFSHIP_CHECK (nrelax > 0, GFSHIP_EINVAL, "nrelax must be non zero");
+  { int r = before_write (dom); if (r) return r; }
   GFSHIP_CHECK (depth == (unsigned) dom->depth && levelmin <= depth, GFSHIP_EINVAL,
 		"levels %u..%u do not match the domain depth %d", levelmin, depth, dom->depth);
   if (dom->dp_cache < 0)
@@ -264,6 +267,7 @@ int gfship_diffusion (gfship_domain * dom, gfship_multilevel_params * par, gfshi
 {
   GFSHIP_CHECK (dom && par, GFSHIP_EINVAL, "null argument");
   int r;
+  if ((r = before_write (dom))) return r;
   /* res = gfs_temporary_variable (domain): kept between calls like the cycle's dp */
   if (dom->res_cache < 0)
     dom->res_cache = gfship_field_alloc (dom, -1);

@@ -301,10 +301,11 @@ static int check_level (gfship_domain * dom, int level)
 } // extern "C"
 
 namespace gfship {
-// bring the non-leaf levels of F up to date before level `level` (< depth) is read or written
-int coarse_flush (gfship_domain * dom, Field * F, int level)
+// bring the non-leaf levels of F up to date before level `level` (< depth) is read or written, or
+// before the leaves they are computed from are overwritten by the caller (leaf_write)
+int coarse_flush (gfship_domain * dom, Field * F, int level, bool leaf_write)
 {
-  if (!F->coarse_stale || level >= dom->depth) return GFSHIP_OK;
+  if (!F->coarse_stale || (level >= dom->depth && !leaf_write)) return GFSHIP_OK;
   F->coarse_stale = false;
   Field * one[1] = { F };
   return launch_coarse_init (dom, one, 1);
@@ -320,8 +321,8 @@ int gfship_field_upload (gfship_domain * dom, gfship_field f, int level, const d
   GFSHIP_CHECK (host != nullptr, GFSHIP_EINVAL, "null host pointer");
   int r = check_level (dom, level);
   if (r) return r;
-  if (dom->before_write && (r = dom->before_write (dom->before_write_ctx))) return r;
-  if ((r = coarse_flush (dom, F, level))) return r;
+  if ((r = before_write (dom))) return r;
+  if ((r = coarse_flush (dom, F, level, true))) return r;
   const Layout & L = dom->lay[level];
   size_t rows = (size_t) L.rows*(dom->dim == 3 ? L.rows : 1);
   GFSHIP_HIP (hipMemcpy2DAsync (F->lev[level] + L.xo, L.px*sizeof (double),
@@ -356,7 +357,8 @@ int gfship_field_fill (gfship_domain * dom, gfship_field f, int level, double va
   if (!F) return GFSHIP_EINVAL;
   int r = check_level (dom, level);
   if (r) return r;
-  if ((r = coarse_flush (dom, F, level))) return r;
+  if ((r = before_write (dom))) return r;
+  if ((r = coarse_flush (dom, F, level, true))) return r;
   r = launch_fill (dom, level, F->lev[level], value);
   F->zero[level] = (r == GFSHIP_OK && value == 0.);
   return r;
@@ -368,7 +370,8 @@ void * gfship_field_device_ptr (gfship_domain * dom, gfship_field f, int level, 
   if (!F || level < 0 || level > dom->depth) return nullptr;
   if (px) *px = dom->lay[level].px;
   if (xo) *xo = dom->lay[level].xo;
-  if (coarse_flush (dom, F, level) != GFSHIP_OK) return nullptr;
+  if (before_write (dom) != GFSHIP_OK) return nullptr;  /* the caller may write through the raw pointer */
+  if (coarse_flush (dom, F, level, true) != GFSHIP_OK) return nullptr;
   F->zero[level] = false; /* the caller may write through the raw pointer */
   return F->lev[level];
 }
@@ -379,6 +382,7 @@ int gfship_bc (gfship_domain * dom, gfship_field v, gfship_field v1, int level)
   if (!V || !V1) return GFSHIP_EINVAL;
   int r = check_level (dom, level);
   if (r) return r;
+  if ((r = before_write (dom))) return r;
   if ((r = coarse_flush (dom, V1, level))) return r;
   V1->zero[level] = false;
   return launch_bc (dom, V, V1, level, 0);
@@ -390,6 +394,7 @@ int gfship_homogeneous_bc (gfship_domain * dom, gfship_field ov, gfship_field v,
   if (!OV || !V) return GFSHIP_EINVAL;
   int r = check_level (dom, level);
   if (r) return r;
+  if ((r = before_write (dom))) return r;
   if ((r = coarse_flush (dom, OV, level))) return r;
   OV->zero[level] = false;
   return launch_bc (dom, V, OV, level, 1);

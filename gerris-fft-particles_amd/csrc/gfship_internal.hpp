@@ -107,8 +107,10 @@ struct gfship_domain {
   hipStream_t side_stream = nullptr;
   hipEvent_t side_fork = nullptr;
   bool no_arm_ahead = false;       // GFSHIP_NO_ARM_AHEAD=1: the granules are armed in line, before the loop
-  // called before a caller overwrites a field of the domain (upload, snapshot read): a simulation that
-  // keeps derived state unstored (its MAC velocities, simulation.hip: materialize_un) stores it first
+  // called by every entry point that writes a field of the domain on behalf of the caller (upload, fill,
+  // raw pointer, bc, snapshot read, the solvers called on their own ...: gfship::before_write): the
+  // simulation of the domain, which keeps derived state unstored (its MAC velocities, simulation.hip:
+  // materialize_un), stores it first.  One simulation per domain (gfship_sim_create refuses a second)
   int (* before_write) (void *) = nullptr;
   void * before_write_ctx = nullptr;
   double * d_scratch = nullptr;   // reduction scratch
@@ -169,6 +171,12 @@ namespace gfship {
 void set_error (const char * fmt, ...);
 int  hip_fail (hipError_t e, const char * what, const char * file, int line);
 
+// see gfship_domain.before_write
+inline int before_write (gfship_domain * dom)
+{
+  return dom->before_write ? dom->before_write (dom->before_write_ctx) : GFSHIP_OK;
+}
+
 #define GFSHIP_HIP(call) do { hipError_t e_ = (call); \
     if (e_ != hipSuccess) return gfship::hip_fail (e_, #call, __FILE__, __LINE__); } while (0)
 
@@ -186,7 +194,8 @@ inline hipError_t stream_wait_spin (hipStream_t st)
     gfship::set_error (__VA_ARGS__); return (code); } } while (0)
 
 Field * get_field (gfship_domain * dom, gfship_field f);
-int coarse_flush (gfship_domain * dom, Field * F, int level);
+// leaf_write: the caller is about to overwrite the leaves the pending non-leaf values come from
+int coarse_flush (gfship_domain * dom, Field * F, int level, bool leaf_write = false);
 inline long ncells (const Layout & L) {
   return L.dim == 3 ? (long) L.n*L.n*L.n : (long) L.n*L.n;
 }

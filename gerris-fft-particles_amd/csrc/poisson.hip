@@ -275,6 +275,7 @@ int gfship_relax (gfship_domain * dom, unsigned d, int level, double omega,
   GFSHIP_CHECK (level >= 0 && level <= dom->depth, GFSHIP_EINVAL, "level %d out of range", level);
   GFSHIP_CHECK (d == 2 || d == 3, GFSHIP_EINVAL, "dimension must be 2 or 3");
   GFSHIP_CHECK (dom->unit_weights, GFSHIP_EINVAL, "call gfship_poisson_coefficients first");
+  { int r = before_write (dom); if (r) return r; }
   for (Field * F : { U, R, D })
     if (int r = coarse_flush (dom, F, level)) return r;
   return relax_level (dom, d, level, omega, U, R, D);
@@ -289,6 +290,7 @@ int gfship_residual (gfship_domain * dom, unsigned d, int level,
   if (!U || !R || !D || !S) return GFSHIP_EINVAL;
   GFSHIP_CHECK (level >= 0 && level <= dom->depth, GFSHIP_EINVAL, "level %d out of range", level);
   GFSHIP_CHECK (dom->unit_weights, GFSHIP_EINVAL, "call gfship_poisson_coefficients first");
+  { int r = before_write (dom); if (r) return r; }
   for (Field * F : { U, R, D, S })
     if (int r = coarse_flush (dom, F, level)) return r;
   S->zero[level] = false;
@@ -450,6 +452,9 @@ extern "C" {
 int gfship_poisson_cycle (gfship_domain * dom, gfship_multilevel_params * p,
 			  gfship_field u, gfship_field rhs, gfship_field dia, gfship_field res)
 {
+  GFSHIP_CHECK (dom != nullptr, GFSHIP_EINVAL, "null domain");
+  int r = before_write (dom);
+  if (r) return r;
   return poisson_cycle (dom, p, u, rhs, dia, res, 1., nullptr);
 }
 
@@ -462,8 +467,12 @@ int gfship_poisson_solve (gfship_domain * dom, gfship_multilevel_params * par,
     * S = get_field (dom, res);
   if (!U || !R || !D || !S) return GFSHIP_EINVAL;
   GFSHIP_CHECK (dom->unit_weights, GFSHIP_EINVAL, "call gfship_poisson_coefficients first");
+  { int r = before_write (dom); if (r) return r; }
   int r;
   const int L = dom->depth;
+  /* non-leaf values of lhs still to be computed from its leaves (a gfs_cell_coarse_init put off): now,
+     before the solution overwrites the leaves */
+  if ((r = coarse_flush (dom, U, L, true))) return r;
   unsigned minlevel = par->minlevel;
   par->depth = L;
   par->niter = 0;

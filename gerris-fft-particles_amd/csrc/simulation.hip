@@ -310,6 +310,9 @@ int gfship_sim_create (gfship_sim ** out, gfship_domain * dom)
 {
   GFSHIP_CHECK (out && dom, GFSHIP_EINVAL, "null argument");
   *out = nullptr;
+  /* state of a simulation lives in its domain (the before_write hook, the sources, the CFL maxima) */
+  GFSHIP_CHECK (dom->before_write == nullptr, GFSHIP_EUNSUPPORTED,
+		"the domain already has a simulation: one gfship_sim per gfship_domain");
   gfship_sim * s = new gfship_sim;
   s->dom = dom;
   auto alloc = [&] (int comp) { return gfship_field_alloc (dom, comp); };
@@ -534,6 +537,9 @@ int gfship_centered_velocity_advection (gfship_sim * s, const gfship_field gmac[
 					const gfship_field g[3])
 {
   GFSHIP_CHECK (s && gmac, GFSHIP_EINVAL, "null argument");
+  /* the MAC velocities are an input, and the pass over the three components overwrites the scratch
+     (adv_tmp3) they would be rebuilt from */
+  TRY (materialize_un (s));
   return centered_velocity_advection (s, gmac, g, 0., nullptr, nullptr);
 }
 
@@ -601,6 +607,22 @@ static int centered_velocity_advection (gfship_sim * s, const gfship_field gmac[
 			     s->advection_params.dt, gmac, g));
   }
   TRY (bc_leaf_vector (s, s->u));
+  return GFSHIP_OK;
+}
+
+int gfship_correct_centered_velocities (gfship_sim * s, const gfship_field g[3], double dt)
+{
+  GFSHIP_CHECK (s && g, GFSHIP_EINVAL, "null argument");
+  for (int c = 0; c < s->dom->dim; c++)
+    GFSHIP_CHECK (get_field (s->dom, g[c]) != nullptr, GFSHIP_EINVAL, "g[%d] is not a field of the domain", c);
+  return correct_centered_velocities (s, g, dt);
+}
+
+int gfship_sim_advance_time (gfship_sim * s)
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
+  s->t = s->tnext;
+  s->i++;
   return GFSHIP_OK;
 }
 

@@ -564,6 +564,7 @@ int gfship_init_spectra (gfship_domain * dom, const gfship_init_spectra_params *
   GFSHIP_CHECK (dom && par && v, GFSHIP_EINVAL, "null argument");
   GFSHIP_CHECK (dom->dim == 3, GFSHIP_EUNSUPPORTED, "GfsInitSpectra only works in 3-D (turbulence.c:747)");
   GFSHIP_CHECK (par->level >= 1 && par->level <= 9, GFSHIP_EINVAL, "level of the spectral grid out of range");
+  { int r = before_write (dom); if (r) return r; }
   const int np = 1 << par->level, nh = np/2 + 1;
   const double deltak = 2.*M_PI/par->L;
   const size_t nc = (size_t) np*np*nh;
@@ -725,6 +726,7 @@ int gfship_turbulent_viscosity (gfship_domain * dom, const gfship_field u[3], do
 {
   GFSHIP_CHECK (dom && u, GFSHIP_EINVAL, "null argument");
   GFSHIP_CHECK (model == 0 || model == 1, GFSHIP_EINVAL, "model: 1 Smagorinsky, 0 sigma");
+  { int r = before_write (dom); if (r) return r; }
   const double * up[3] = { nullptr, nullptr, nullptr };
   for (int c = 0; c < dom->dim; c++) {
     Field * F = get_field (dom, u[c]);

@@ -107,6 +107,8 @@ SIGNATURES = {
     "gfship_mac_projection": (_i, [_vp, C.POINTER(MultilevelParams), _d, _i, _pi]),
     "gfship_approximate_projection": (_i, [_vp, C.POINTER(MultilevelParams), _d, _i, _pi]),
     "gfship_centered_velocity_advection": (_i, [_vp, _pi, _pi]),
+    "gfship_correct_centered_velocities": (_i, [_vp, _pi, _d]),
+    "gfship_sim_advance_time": (_i, [_vp]),
     "gfship_tracer_advection": (_i, [_vp, _i, _d]),
     "gfship_domain_cfl": (_i, [_vp, _pd]),
     "gfship_set_timestep": (_i, [_vp]),
@@ -601,6 +603,42 @@ class Simulation:
 
     def tracer_advection(self, t, dt):
         _check(lib().gfship_tracer_advection(self.ptr, t.h, dt))
+
+    @staticmethod
+    def _handles(v):
+        return (C.c_int * 3)(*([f.h for f in v] + [-1] * (3 - len(v))))
+
+    def mac_projection(self, par, dt, p, g):
+        """gfs_mac_projection on the MAC velocities as they are; par: one of the parameter structs"""
+        _check(lib().gfship_mac_projection(self.ptr, C.byref(par), dt, p.h, self._handles(g)))
+
+    def approximate_projection(self, par, dt, p, g):
+        _check(lib().gfship_approximate_projection(self.ptr, C.byref(par), dt, p.h, self._handles(g)))
+
+    def centered_velocity_advection(self, gmac, g=None):
+        _check(lib().gfship_centered_velocity_advection(self.ptr, self._handles(gmac),
+                                                        self._handles(g) if g is not None else None))
+
+    def correct_centered_velocities(self, g, dt):
+        _check(lib().gfship_correct_centered_velocities(self.ptr, self._handles(g), dt))
+
+    def set_timestep(self):
+        _check(lib().gfship_set_timestep(self.ptr))
+
+    def coarse_init(self):
+        _check(lib().gfship_coarse_init(self.ptr))
+
+    def advance_time(self):
+        """t = tnext, i++ (the end of the loop body of simulation_run)"""
+        _check(lib().gfship_sim_advance_time(self.ptr))
+
+    NEXT_EVENT_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_double, C.c_uint)
+
+    def set_next_event(self, fn):
+        """fn (t, i) -> the tnext the host's events give (None: no events)"""
+        self._next_event = None if fn is None else self.NEXT_EVENT_FN(lambda ctx, t, i: float(fn(t, i)))
+        _check(lib().gfship_sim_set_next_event(
+            self.ptr, None if fn is None else C.cast(self._next_event, C.c_void_p), None))
 
     def un(self, c):
         n = (1 << self.dom.depth) + 2

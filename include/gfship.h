@@ -102,7 +102,15 @@ int  gfship_field_upload (gfship_domain * dom, gfship_field f, int level, const 
 int  gfship_field_download (gfship_domain * dom, gfship_field f, int level, double * host);
 int  gfship_field_fill (gfship_domain * dom, gfship_field f, int level, double value);
 /* device pointer and layout of level `level`: cell (i,j,k) is at
-   ptr[xo + i + px*(j + (n+2)*k)] */
+   ptr[xo + i + px*(j + (n+2)*k)], the storage gfship_field_upload / _download of that level move
+   at the time of the call.  Work enqueued on gfship_domain_stream is ordered with the library's.
+   The pointer stays valid until the next call that advances a simulation of the domain
+   (gfship_sim_start, gfship_sim_step, gfship_sim_advection_step, or any of the pieces
+   gfship_predicted_face_velocities ... gfship_coarse_init): the library computes U, V, W and the
+   tracers out of place and swaps the storage of a variable with a scratch array, so a pointer taken
+   before such a call may address scratch after it -- ask again after every such call.  Between two of
+   them the pointer is stable, and uploads, fills and downloads go to the same storage.  The call
+   counts as a write of the field (a simulation brings the state it keeps unstored up to date first). */
 void * gfship_field_device_ptr (gfship_domain * dom, gfship_field f, int level,
 				int * px, int * xo);
 
@@ -199,7 +207,16 @@ enum { GFSHIP_VAR_P = 0, GFSHIP_VAR_PMAC = 1, GFSHIP_VAR_U = 2, GFSHIP_VAR_G = 3
 			    the first cell), GFS_STATE (cell)->f[2c].un */ };
 
 /* gfs_simulation_new + simulation_init (src/simulation.c:910-1015): allocates P, Pmac, U, V(, W),
-   the gradient vectors g[], gmac[] of simulation_run (:432-456) and the face state */
+   the gradient vectors g[], gmac[] of simulation_run (:432-456) and the face state.  One simulation
+   per domain, as one GfsSimulation is its GfsDomain: a second gfship_sim_create on a domain that has
+   one fails with GFSHIP_EUNSUPPORTED (and leaves the first untouched); after gfship_sim_destroy the
+   domain takes a new one.
+   State between calls: a gfship_sim_step may leave the MAC velocities of its approximate projection
+   unstored; every entry point that reads them (the pieces below, gfship_sim_download_un,
+   gfship_sim_variable (GFSHIP_VAR_UN)) or that lets the caller write a field of the domain
+   (gfship_field_upload, _fill, _device_ptr, gfship_bc, the snapshot reader, the solvers called on
+   their own) stores them first, from the fields as the step left them.  So the pieces and
+   gfship_sim_step can be mixed in any order, and the fields can be rewritten between two calls. */
 int  gfship_sim_create (gfship_sim ** sim, gfship_domain * dom);
 void gfship_sim_destroy (gfship_sim * sim);
 gfship_field gfship_sim_variable (gfship_sim * sim, int which, int c);
@@ -262,10 +279,17 @@ int  gfship_approximate_projection (gfship_sim * sim, gfship_multilevel_params *
 				    gfship_field p, const gfship_field g[3]); /* :560-596 */
 int  gfship_centered_velocity_advection (gfship_sim * sim, const gfship_field gmac[3],
 					 const gfship_field g[3]);           /* :976-1016 */
+/* gfs_correct_centered_velocities (src/timestep.c:498-530): U -= g dt on the leaves, then the
+   conditions of U, V(, W) -- the statement between the advection and gfs_cell_coarse_init in the
+   loop body of simulation_run (src/simulation.c:517-521, there with g or gmac and - dt) */
+int  gfship_correct_centered_velocities (gfship_sim * sim, const gfship_field g[3], double dt);
 int  gfship_tracer_advection (gfship_sim * sim, gfship_field t, double dt);  /* :1028-1055 */
 int  gfship_domain_cfl (gfship_sim * sim, double * cfl);       /* src/domain.c:2824-2923 */
 int  gfship_set_timestep (gfship_sim * sim);                   /* src/simulation.c:1569-1633 */
 int  gfship_coarse_init (gfship_sim * sim);                    /* src/adaptive.c:43-58 */
+/* `sim->time.t = sim->tnext; sim->time.i++' of the loop body (src/simulation.c:538-539), tnext being
+   the one the last gfship_set_timestep chose (it is not t + dt where an event cut the step) */
+int  gfship_sim_advance_time (gfship_sim * sim);
 /* OutputScalarNorm { v = Divergence }: gfs_divergence (src/fluid.c:2357-2376) + norm */
 int  gfship_divergence_norm (gfship_sim * sim, gfship_norm * out);
 /* MAC normal velocity on the faces orthogonal to component c, as a host array in the cell

@@ -248,6 +248,17 @@ static void diffusion_cycle (GoDomain * dom, unsigned levelmin, unsigned depth, 
   go_field_destroy (dp);
 }
 
+/* the pieces above for the tests that compare them one by one with the device's entry points */
+void go_diffusion_coefficients (GoDomain * dom, double D, double dt, double beta, GoField * rhoc)
+{ diffusion_coefficients (dom, D, dt, beta, rhoc); }
+void go_diffusion_rhs (GoDomain * dom, GoField * v, GoField * rhs, GoField * rhoc, double beta)
+{ diffusion_rhs (dom, v, rhs, rhoc, beta); }
+void go_diffusion_residual (GoDomain * dom, GoField * u, GoField * rhs, GoField * rhoc, GoField * res)
+{ diffusion_residual (dom, u, rhs, rhoc, res); }
+void go_diffusion_cycle (GoDomain * dom, unsigned levelmin, unsigned depth, unsigned nrelax,
+			 GoField * u, GoField * rhs, GoField * rhoc, GoField * res)
+{ diffusion_cycle (dom, levelmin, depth, nrelax, u, rhs, rhoc, res); }
+
 /* variable_diffusion (timestep.c:923-949) + gfs_diffusion (timestep.c:735-788) */
 void go_variable_diffusion (GoSim * s, GoField * v, GoField * rhs, double D, double dt,
 			    GoMultilevelParams * par)

@@ -6,6 +6,8 @@
 
 #define GO_MAXTRACERS 4
 
+typedef double (* GoNextEventFunc) (void * ctx, double t, unsigned i);
+
 typedef struct GoSim {
   GoDomain * dom;
   GoField * p, * pmac, * u[3], * g[3], * gmac[3];
@@ -24,6 +26,8 @@ typedef struct GoSim {
   /* GfsPhysicalParams { alpha = ... } (simulation.c:1306-1440) as gfs_function_face_value (alpha) on the
    * leaf faces: alpha[c] in the layout go_poisson_coefficients_alpha takes; NULL = alpha NULL */
   GoField * alpha[3];
+  GoNextEventFunc next_event;    /* the host's events, see go_sim_set_next_event */
+  void * next_event_ctx;
 } GoSim;
 
 GoSim * go_sim_new (int dim, int depth, const int side[6]);
@@ -44,6 +48,9 @@ void    go_approximate_projection (GoSim * s, GoMultilevelParams * par, double d
 				   GoField ** g);
 void    go_mac_projection (GoSim * s, GoMultilevelParams * par, double dt, GoField * p,
 			   GoField ** g);
+void    go_correct_centered_velocities (GoSim * s, GoField ** g, double dt);
+void    go_sim_advance_time (GoSim * s);
+void    go_sim_set_next_event (GoSim * s, GoNextEventFunc fn, void * ctx);
 void    go_predicted_face_velocities (GoSim * s);
 void    go_centered_velocity_advection (GoSim * s, GoField ** gmac, GoField ** g);
 void    go_tracer_advection (GoSim * s, GoField * t, double dt);

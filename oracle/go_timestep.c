@@ -322,6 +322,18 @@ static void correct_centered_velocities (GoSim * s, GoField ** g, double dt)
     go_bc (s->u[c], s->u[c], L);
 }
 
+void go_correct_centered_velocities (GoSim * s, GoField ** g, double dt)
+{
+  correct_centered_velocities (s, g, dt);
+}
+
+/* the caller's `time.t = tnext; time.i++' of the loop body, simulation.c:538-539 */
+void go_sim_advance_time (GoSim * s)
+{
+  s->t = s->tnext;
+  s->i++;
+}
+
 /* gfs_approximate_projection, timestep.c:560-596 */
 void go_approximate_projection (GoSim * s, GoMultilevelParams * par, double dt, GoField * p,
 				GoField ** g)
@@ -711,7 +723,15 @@ double go_domain_cfl (GoSim * s)
   return sqrt (cfl);
 }
 
-/* gfs_simulation_set_timestep, simulation.c:1569-1633; the only event time is `end` */
+/* the events of the host (gfs_event_next loop, simulation.c:1603-1610): fn returns the tnext they
+   give for time t and iteration i (G_MAXINT without events) */
+void go_sim_set_next_event (GoSim * s, GoNextEventFunc fn, void * ctx)
+{
+  s->next_event = fn;
+  s->next_event_ctx = ctx;
+}
+
+/* gfs_simulation_set_timestep, simulation.c:1569-1633; the event times are `end` and the hook's */
 void go_set_timestep (GoSim * s)
 {
   double t = s->t;
@@ -724,6 +744,8 @@ void go_set_timestep (GoSim * s)
     s->advection_params.dt = s->dtmax;
 
   double tnext = G_MAXINT;
+  if (s->next_event)
+    tnext = (* s->next_event) (s->next_event_ctx, t, s->i);
   if (s->end < tnext)
     tnext = s->end;
 

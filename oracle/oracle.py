@@ -224,6 +224,16 @@ def _sim_sigs(L):
         "go_sim_set_alpha": (None, [vp, C.POINTER(vp)]),
         "go_variable_diffusion": (None, [vp, vp, vp, d, d, C.POINTER(MultilevelParams)]),
         "go_sim_diffusion_params": (C.POINTER(MultilevelParams), [vp, i]),
+        "go_mac_projection": (None, [vp, C.POINTER(MultilevelParams), d, vp, C.POINTER(vp)]),
+        "go_approximate_projection": (None, [vp, C.POINTER(MultilevelParams), d, vp, C.POINTER(vp)]),
+        "go_centered_velocity_advection": (None, [vp, C.POINTER(vp), C.POINTER(vp)]),
+        "go_correct_centered_velocities": (None, [vp, C.POINTER(vp), d]),
+        "go_sim_advance_time": (None, [vp]),
+        "go_sim_set_next_event": (None, [vp, vp, vp]),
+        "go_diffusion_coefficients": (None, [vp, d, d, d, vp]),
+        "go_diffusion_rhs": (None, [vp, vp, vp, vp, d]),
+        "go_diffusion_residual": (None, [vp, vp, vp, vp, vp]),
+        "go_diffusion_cycle": (None, [vp, u, u, u, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -314,6 +324,50 @@ class Sim:
     def fv(self, d):
         n = (1 << self.depth) + 2
         return np.ctypeslib.as_array(lib().go_sim_fv(self.ptr, d), shape=(n,) * self.dim)
+
+    # the public pieces of the time step (go_timestep.c), one call each
+    @staticmethod
+    def _ptrs(v):
+        return (C.c_void_p * 3)(*([f.ptr for f in v] + [None] * (3 - len(v))))
+
+    def predicted_face_velocities(self):
+        lib().go_predicted_face_velocities(self.ptr)
+
+    def mac_projection(self, par, dt, p, g):
+        lib().go_mac_projection(self.ptr, C.byref(par), dt, p.ptr, self._ptrs(g))
+
+    def approximate_projection(self, par, dt, p, g):
+        lib().go_approximate_projection(self.ptr, C.byref(par), dt, p.ptr, self._ptrs(g))
+
+    def centered_velocity_advection(self, gmac, g=None):
+        lib().go_centered_velocity_advection(self.ptr, self._ptrs(gmac),
+                                             self._ptrs(g) if g is not None else None)
+
+    def correct_centered_velocities(self, g, dt):
+        lib().go_correct_centered_velocities(self.ptr, self._ptrs(g), dt)
+
+    def tracer_advection(self, t, dt):
+        lib().go_tracer_advection(self.ptr, t.ptr, dt)
+
+    def cfl(self):
+        return lib().go_domain_cfl(self.ptr)
+
+    def set_timestep(self):
+        lib().go_set_timestep(self.ptr)
+
+    def coarse_init(self):
+        lib().go_coarse_init(self.ptr)
+
+    def advance_time(self):
+        lib().go_sim_advance_time(self.ptr)
+
+    NEXT_EVENT_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_double, C.c_uint)
+
+    def set_next_event(self, fn):
+        """fn (t, i) -> the tnext the host's events give (None: no events)"""
+        self._next_event = None if fn is None else self.NEXT_EVENT_FN(lambda ctx, t, i: float(fn(t, i)))
+        lib().go_sim_set_next_event(
+            self.ptr, None if fn is None else C.cast(self._next_event, C.c_void_p), None)
 
     def set_source(self, c, g):
         """GfsSource {} U/V/W g: constant intensity (a body force per unit mass)"""
