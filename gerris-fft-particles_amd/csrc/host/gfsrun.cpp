@@ -941,24 +941,25 @@ void parse_object (Run & R, Reader & r)
 	const int N = gfship_output_spectra_side (R.dom);
 	if (N <= 0) { fprintf (stderr, "gfship: %s\n", gfship_last_error ()); exit (1); }
 	const int nh = N/2 + 1;
-	std::vector<double> F ((size_t) 2*N*nh);
+	std::vector<double> F ((size_t) 2*N*N);
 	double ks = 0.;
 	if (gfship_output_spectra_plane (R.dom, R.vars[v].dev, normal, plane_pos, F.data (), &ks) != GFSHIP_OK) {
 	  fprintf (stderr, "gfship: %s\n", gfship_last_error ());
 	  exit (1);
 	}
-	// write_spectra, modules/fft.c:1047-1085 (L = 1): the flat direction first (one point, k = 0), then
-	// the two others in coordinate order, the last one halved
+	// write_spectra, modules/fft.c:1049-1085 (L = 1): order_array sorts by descending size, so the two
+	// in-plane directions come first, in coordinate order, both with signed k; the flat direction is last
+	// (one point, k = 0): N*N rows
 	const int ca = normal == 0 ? 1 : 0, cb = normal == 2 ? 1 : 2;
 	FILE * fp = o->open ();
 	fprintf (fp, "# %i \n", N*N);
 	fputs ("# 1:kx 2:ky 3:kz 4:real 5:img\n", fp);
-	for (int j = 0; j < N; j++)
-	  for (int l = 0; l < nh; l++) {
+	for (int i = 0; i < N; i++)
+	  for (int j = 0; j < N; j++) {
 	    double k[3] = { 0., 0., 0. };
-	    k[ca] = ks*(j < nh ? j : j - N);
-	    k[cb] = ks*l;
-	    const size_t q = 2*((size_t) j*nh + l);
+	    k[ca] = ks*(i < nh ? i : i - N);
+	    k[cb] = ks*(j < nh ? j : j - N);
+	    const size_t q = 2*((size_t) i*N + j);
 	    fprintf (fp, "%g %g %g %g %g\n", k[0], k[1], k[2], F[q]*1., F[q + 1]*1.);
 	  }
 	fflush (fp);

@@ -3,13 +3,15 @@
 // reference's binning of |F|^2 by integer |k|^2.
 //
 // The FFT arithmetic of the reference lives in FFTW3 (absent here) and the reference has no test or
-// golden data for it: parity is unpinned; tests/ check this against a numpy restatement of the
-// call sites (oracle/go_spectra.py) and against Parseval / single-mode properties.
+// golden data for it.  tests/ pin the layout of every output on the reference's text through a
+// transform that shares nothing with this file: a direct extended-precision DFT read with the
+// reference's own index expressions (tests/dft_reference.py), besides the numpy restatement of the
+// call sites (oracle/go_spectra.py) and Parseval / single-mode properties.
 //   fill_cartesian_matrix (:966-1001)   v = (u - <u>)/ntot           -> spectra_fill_kernel
 //   get_fftw_plan (:1087-1098)           r2c DFT, last dimension halved -> hipfftExecD2Z
 //   output_energy_spectra_event (:1360-1474) bins, weights             -> spectra_bin_kernel
-// The dimensions are taken in the order x, y, z (z halved; the reference sorts them by size, all
-// equal on a cube).  The bins are summed with fp64 atomics: the order of the additions, hence the
+// The dimensions are taken in the order x, y, z (the last one halved; the reference sorts them by
+// descending size, order_array :795-820, all equal on a cube).  The bins are summed with fp64 atomics: the order of the additions, hence the
 // last bits of Ek, differ from run to run and from the CPU loops (<= 1e-12 relative in the tests).
 #include "gfship_internal.hpp"
 #include <hipfft/hipfft.h>
@@ -292,6 +294,25 @@ spectra_plane_center_kernel (int np, const double * __restrict__ sum, double * _
   a[q] = v;
 }
 
+// The full n x n transform of a real plane from its half h[ia][ib <= n/2] (D2Z): the entries with
+// ib > n/2 are the conjugates of h[(n - ia) % n][n - ib].  One thread per entry of the full array.
+__global__ void __launch_bounds__(256)
+spectra_plane_full_kernel (int n, const double2 * __restrict__ h, double2 * __restrict__ f)
+{
+  const int q = blockIdx.x*blockDim.x + threadIdx.x;
+  if (q >= n*n) return;
+  const int nh = n/2 + 1;
+  const int ib = q % n, ia = q / n;
+  double2 c;
+  if (ib < nh)
+    c = h[ia*nh + ib];
+  else {
+    c = h[((n - ia) % n)*nh + (n - ib)];         /* 1 <= n - ib < nh */
+    c.y = -c.y;
+  }
+  f[q] = c;
+}
+
 } // namespace gfship
 
 using namespace gfship;
@@ -494,10 +515,17 @@ int gfship_output_spectra (gfship_domain * dom, gfship_field v, double * out, do
 
 // GfsOutputSpectra of a plane of a 3-D box (realdim == 2, modules/fft.c:1101-1160): the plane normal to
 // `normal' (0 x, 1 y, 2 z) at coordinate pos, over the whole box in the other two directions at the finest
-// level.  order_array (:800-820) puts the flat direction first and keeps the other two in coordinate order:
-// out receives N*(N/2 + 1) complex numbers, index ia*(N/2 + 1) + ib with ia the first and ib the second
+// level.  order_array (:795-820) sorts the directions by DESCENDING number of points: the two in-plane ones
+// come first (coordinate order for equal sizes; the reference leaves ties to g_array_sort) and the flat one,
+// np = 1, is dirdata[2].  With d.Ndim = 3 (:1121) the halved dimension is that one, npaux = 1/2 + 1 = 1:
+// fftw_plan_dft_r2c_3d (N, N, 1) leaves the FULL N x N complex transform and write_spectra (:1049-1085)
+// prints N*N rows.  out receives N*N complex numbers, index ia*N + ib with ia the first and ib the second
 // in-plane coordinate (x, y for a z plane; x, z for a y plane; y, z for an x plane); write_spectra prints
-// k = kstep times the signed index in those directions and 0 in the normal one.
+// k = kstep times the SIGNED index in both of those directions and 0 in the normal one.
+// The cell holding the plane is taken for any pos inside the box; the reference selects cells only when pos
+// is a cell-centre coordinate (inside_domain, :348-362), and its (ix, iy, iz) indexing of the plane lands
+// where the transform reads only for a z-normal plane: the x- and y-normal planes are the coherent
+// analogue (extensions).
 int gfship_output_spectra_plane (gfship_domain * dom, gfship_field v, int normal, double pos, double * out,
 				 double * kstep)
 {
@@ -509,16 +537,20 @@ int gfship_output_spectra_plane (gfship_domain * dom, gfship_field v, int normal
   if (!F) return GFSHIP_EINVAL;
   const Layout & L = dom->lay[dom->depth];
   const int N = L.n, nh = N/2 + 1;
-  /* gfs_domain_locate: the cell whose extent holds the point */
-  int kc = (int) floor ((pos + 0.5)*N) + 1;
+  GFSHIP_CHECK (N >= 2, GFSHIP_EINVAL, "level too coarse for a spectrum");
+  /* gfs_domain_locate: the cell whose extent [-0.5 + k/N, -0.5 + (k + 1)/N) holds the point.  pos*N is
+     exact (N is a power of two) where (pos + 0.5)*N is not: just below 0.5 the sum rounds up to 1 */
+  GFSHIP_CHECK (pos >= -0.5 && pos < 0.5, GFSHIP_EINVAL, "the plane at %g lies outside the box", pos);
+  const int kc = (int) floor (pos*N) + N/2 + 1;
   GFSHIP_CHECK (kc >= 1 && kc <= N, GFSHIP_EINVAL, "the plane at %g lies outside the box", pos);
   double * a = nullptr, * sum = nullptr;
-  double2 * Fo = nullptr;
+  double2 * Fh = nullptr, * Fo = nullptr;
   hipfftHandle plan = 0;
   int r = GFSHIP_OK;
   hipError_t e = hipMalloc ((void **) &a, (size_t) N*N*sizeof (double));
   if (e == hipSuccess) e = hipMalloc ((void **) &sum, sizeof (double));
-  if (e == hipSuccess) e = hipMalloc ((void **) &Fo, (size_t) N*nh*sizeof (double2));
+  if (e == hipSuccess) e = hipMalloc ((void **) &Fh, (size_t) N*nh*sizeof (double2));
+  if (e == hipSuccess) e = hipMalloc ((void **) &Fo, (size_t) N*N*sizeof (double2));
   if (e == hipSuccess) e = hipMemsetAsync (sum, 0, sizeof (double), dom->stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL (spectra_plane_gather_kernel, dim3 ((N*N + 255)/256), dim3 (256), 0, dom->stream, L,
@@ -527,19 +559,24 @@ int gfship_output_spectra_plane (gfship_domain * dom, gfship_field v, int normal
     e = hipGetLastError ();
   }
   if (e == hipSuccess) {
-    /* fftw_plan_dft_r2c_3d (1, N, N): a 2-D transform */
+    /* fftw_plan_dft_r2c_3d (N, N, 1): the 2-D transform of a real plane, all N x N coefficients.  The
+       half a D2Z transform leaves is completed by conjugate symmetry */
     if (hipfftPlan2d (&plan, N, N, HIPFFT_D2Z) != HIPFFT_SUCCESS || hipfftSetStream (plan, dom->stream) != HIPFFT_SUCCESS ||
-	hipfftExecD2Z (plan, a, (hipfftDoubleComplex *) Fo) != HIPFFT_SUCCESS) {
+	hipfftExecD2Z (plan, a, (hipfftDoubleComplex *) Fh) != HIPFFT_SUCCESS) {
       gfship::set_error ("hipFFT error in the transform of a plane");
       r = GFSHIP_EHIP;
     }
   }
+  if (e == hipSuccess && r == GFSHIP_OK) {
+    hipLaunchKernelGGL (spectra_plane_full_kernel, dim3 ((N*N + 255)/256), dim3 (256), 0, dom->stream, N, Fh, Fo);
+    e = hipGetLastError ();
+  }
   if (e == hipSuccess && r == GFSHIP_OK)
-    e = hipMemcpyAsync (out, Fo, (size_t) N*nh*sizeof (double2), hipMemcpyDeviceToHost, dom->stream);
+    e = hipMemcpyAsync (out, Fo, (size_t) N*N*sizeof (double2), hipMemcpyDeviceToHost, dom->stream);
   if (e == hipSuccess && r == GFSHIP_OK)
     e = hipStreamSynchronize (dom->stream);
   if (plan) (void) hipfftDestroy (plan);
-  (void) hipFree (a); (void) hipFree (sum); (void) hipFree (Fo);
+  (void) hipFree (a); (void) hipFree (sum); (void) hipFree (Fh); (void) hipFree (Fo);
   if (r) return r;
   GFSHIP_HIP (e);
   if (kstep)

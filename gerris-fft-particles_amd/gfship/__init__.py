@@ -443,10 +443,11 @@ class Domain:
         return out, ks.value
 
     def output_spectra_plane(self, v, normal, pos):
-        """GfsOutputSpectra of a plane of the 3-D box (realdim == 2): (F, kstep), F[ia][ib <= N/2] the 2-D r2c
-        DFT of the cell values on the plane minus their mean over their number"""
+        """GfsOutputSpectra of a plane of the 3-D box (realdim == 2): (F, kstep), F[ia][ib] the full N x N
+        2-D DFT of the cell values on the plane minus their mean over their number, ia / ib the first /
+        second in-plane coordinate (what fftw_plan_dft_r2c_3d (N, N, 1) leaves: modules/fft.c:795-820)"""
         N = _check(lib().gfship_output_spectra_side(self.ptr))
-        out = np.empty((N, N // 2 + 1), dtype=np.complex128)
+        out = np.empty((N, N), dtype=np.complex128)
         ks = C.c_double()
         _check(lib().gfship_output_spectra_plane(self.ptr, v.h, int(normal), float(pos),
                                                  out.ctypes.data_as(_pd), C.byref(ks)))

@@ -345,10 +345,13 @@ int  gfship_energy_spectra (gfship_domain * dom, int ncomp, const gfship_field *
    and gfship_energy_spectra likewise bins the whole domain.
    gfship_output_spectra_plane: the same event with a flat box (realdim == 2, :1131-1141,
    fill_interpolated_cartesian_matrix :822-883): the cells the points of the plane normal to `normal' (0 x,
-   1 y, 2 z) at coordinate pos lie in, minus their mean, over their number; the 2-D r2c DFT; out receives
-   N*(N/2 + 1) complex numbers, index ia*(N/2 + 1) + ib, ia / ib the first / second in-plane coordinate
-   (order_array keeps them in coordinate order behind the flat one); one box.  GfsOutputSpectraInterface
-   samples the position of a VOF interface (out of scope with VOF): not provided. */
+   1 y, 2 z) at coordinate pos (-0.5 <= pos < 0.5) lie in, minus their mean, over their number.  order_array
+   (:795-820) sorts the directions by descending size, so the flat one comes LAST and is the one that is
+   "halved" (1/2 + 1 = 1): the transform is the FULL 2-D DFT.  out receives N*N complex numbers (2*N*N
+   doubles: twice what the half-spectrum layout of earlier versions took -- size the buffer accordingly),
+   index ia*N + ib, ia / ib the first / second in-plane coordinate in coordinate order; write_spectra prints
+   k = kstep times the signed index (q < N/2 + 1 ? q : q - N) along both and 0 along the normal; one box.
+   GfsOutputSpectraInterface samples the position of a VOF interface (out of scope with VOF): not provided. */
 int  gfship_output_spectra_side (gfship_domain * dom);
 int  gfship_output_spectra (gfship_domain * dom, gfship_field v, double * out, double * kstep);
 int  gfship_output_spectra_plane (gfship_domain * dom, gfship_field v, int normal, double pos, double * out,

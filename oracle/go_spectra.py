@@ -16,9 +16,11 @@ spectra: PARITY UNPINNED.  What is restated is the published algorithm of the ca
       nk = (dim + 1) (np/2 + 1)^2 bins, Etot = sum of all bins
   write_energy_spectra (:1340-1348)   lines "deltak*sqrt(i) Ek[i]" for i = 1 .. nk - 1, with
       deltak = 2 pi/(x1 - x0) and x0, x1 the first / last CELL CENTRES along x ((np - 1) dx apart).
-The order of the dimensions of the transform (the reference sorts them by size, :800-820, all equal
-for a cube) is fixed here to x, y, z with z halved; the components are summed in the order U, V, W.
-Uses numpy's pocketfft; sums in the order of the loops above."""
+The order of the dimensions of the transform (the reference sorts them by descending size, :795-820,
+all equal for a cube) is fixed here to x, y, z with the last one halved; the components are summed in
+the order U, V, W.  Uses numpy's pocketfft; sums in the order of the loops above.
+tests/test_dft_reference_cpu.py compares every function here with a direct extended-precision DFT
+read through the reference's own index expressions (tests/dft_reference.py)."""
 import numpy as np
 
 
@@ -65,11 +67,15 @@ def output_spectra_plane(u, normal, pos):
     """GfsOutputSpectra with a flat box (realdim == 2, modules/fft.c:1131-1141): the points
     pos_min + j dx of the plane normal to `normal' (0 x, 1 y, 2 z) at coordinate pos take the value of the
     cell they lie in (fill_interpolated_cartesian_matrix, :822-883: gfs_domain_locate + GFS_VALUE), the mean
-    of the np values is removed and the result divided by np; order_array (:800-820) puts the flat direction
-    first and keeps the other two in coordinate order; fftw_plan_dft_r2c_3d (1, N, N).  u: [k][j][i] of the
-    leaf level; returns F[ia][ib <= N/2] and the k step of write_spectra."""
+    of the np values is removed and the result divided by np.  order_array (:795-820) sorts the directions
+    by DESCENDING np: the two in-plane ones stay in coordinate order and the flat one (np = 1) comes LAST,
+    so the halved dimension (d.Ndim = 3, :817) is the flat one, 1/2 + 1 = 1: fftw_plan_dft_r2c_3d (N, N, 1)
+    leaves the full N x N complex transform.  u: [k][j][i] of the leaf level; returns F[ia][ib] (N x N,
+    ia / ib the first / second in-plane coordinate) and the k step of write_spectra."""
     n = u.shape[0]
-    kc = int(np.floor((pos + 0.5) * n))
+    kc = int(np.floor(pos * n)) + n // 2     # pos*n is exact (n a power of two); (pos + 0.5)*n is not
+    if not 0 <= kc < n:
+        raise ValueError("the plane at %g lies outside the box" % pos)
     a = np.transpose(u)                      # [i][j][k]
     sl = [slice(None)] * 3
     sl[normal] = kc
@@ -77,7 +83,7 @@ def output_spectra_plane(u, normal, pos):
     npnt = plane.size
     avg = plane.sum() / npnt
     plane = (plane - avg) / npnt
-    return np.fft.rfftn(plane), 2. * np.pi / ((n - 1) * (1. / n))
+    return np.fft.fft2(plane), 2. * np.pi / ((n - 1) * (1. / n))
 
 
 def turbulent_viscosity(u, Cs, model=1):

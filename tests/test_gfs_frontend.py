@@ -273,17 +273,29 @@ def test_output_spectra_and_turbulent_viscosity_case(tmp_path):
     assert len(big) == 4                                   # kz >= 0 half: (+-1, +-1, 1)
     assert np.allclose(np.abs(big[:, :3]), dk, rtol=1e-5)
     assert np.allclose(np.hypot(big[:, 3], big[:, 4]), 0.125, rtol=1e-3)
-    # the plane z = 0.1 (a flat box: realdim == 2): N x (N/2 + 1) rows, kz = 0, the mode (+-1, 1) of
-    # sin (2 pi x) cos (2 pi y) with the amplitude cos (2 pi z_cell)/4
+    # the plane z = 0.1 (a flat box: realdim == 2): N x N rows (order_array puts the flat direction last,
+    # the transform is the full one), kz = 0, the modes (+-1, +-1) of sin (2 pi x) cos (2 pi y) with the
+    # amplitude cos (2 pi z_cell)/4
     lines = open(tmp_path / "spectra-U-plane").read().splitlines()
     assert lines[0].strip() == "# %d" % n ** 2
     prow = np.array([[float(x) for x in l.split()] for l in lines[2:]])
-    assert len(prow) == n * (n // 2 + 1) and np.all(prow[:, 2] == 0.)
+    assert len(prow) == n * n and np.all(prow[:, 2] == 0.)
     pamp = np.hypot(prow[:, 3], prow[:, 4])
     pbig = prow[pamp > 0.05]
-    assert len(pbig) == 2 and np.allclose(np.abs(pbig[:, :2]), dk, rtol=1e-5)
+    assert len(pbig) == 4 and np.allclose(np.abs(pbig[:, :2]), dk, rtol=1e-5)
+    assert sorted(map(tuple, np.sign(pbig[:, :2]))) == [(-1, -1), (-1, 1), (1, -1), (1, 1)]
     zc = -0.5 + (np.floor((0.1 + 0.5) * n) + 0.5) / n
     assert np.allclose(np.hypot(pbig[:, 3], pbig[:, 4]), abs(np.cos(2 * np.pi * zc)) / 4., rtol=1e-3)
+    # every row of both files against the direct DFT read with the reference's index expressions
+    # (tests/dft_reference.py) of the initial field; %g prints six digits
+    import dft_reference as R
+    xc = (np.arange(n) + 0.5) / n - 0.5
+    Zc, Yc, Xc = np.meshgrid(xc, xc, xc, indexing="ij")
+    u0 = np.sin(2 * np.pi * Xc) * np.cos(2 * np.pi * Yc) * np.cos(2 * np.pi * Zc)
+    for got, want in ((rows, R.spectra_rows_box(u0)), (prow, R.spectra_rows_plane(u0, 2, 0.1))):
+        want = want.astype(float)
+        assert got.shape == want.shape
+        assert np.allclose(got, want, rtol=1e-5, atol=1e-13)
     # the eddy viscosity against the numpy restatement on the initial field
     from oracle.go_spectra import turbulent_viscosity
     x = (np.arange(-1, n + 1) + 0.5) / n - 0.5

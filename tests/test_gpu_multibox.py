@@ -239,6 +239,13 @@ def test_spectra_of_a_lattice_of_boxes_equal_those_of_the_whole_domain():
         assert np.abs(Ek - Ek0).max() <= 1e-12 * Etot0
         F, ks = r["sp"]
         assert ks == ks0 and np.abs(F - F0).max() <= 1e-13
+    # and against the direct extended-precision DFT read with the reference's own index expressions
+    # (tests/dft_reference.py): independent of the restatement
+    import dft_reference as R
+    bins0, rows0 = R.energy_bins(comps, n_box=n), R.spectra_rows_box(comps[0], n_box=n)
+    for r in res:
+        R.assert_bins_match(r["es"], bins0, label="lattice 2x2x2 energy_spectra")
+        R.assert_rows_match(R.rows_of_box_output(*r["sp"]), rows0, label="lattice 2x2x2 output_spectra")
 
 
 def test_lattice_flow_2d_device_boxes_equal_oracle_boxes():

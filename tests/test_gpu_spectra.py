@@ -163,8 +163,8 @@ def test_turbulent_viscosity_matches_the_restatement(dim, model):
 
 @pytest.mark.parametrize("normal,pos", [(2, 0.1), (0, -0.3), (1, 0.26)])
 def test_output_spectra_of_a_plane_matches_the_restatement(normal, pos):
-    """GfsOutputSpectra with a flat box (a plane of the 3-D box): the 2-D r2c DFT of the cell values on the
-    plane against the numpy restatement of modules/fft.c:822-883,1101-1160, and a single in-plane mode"""
+    """GfsOutputSpectra with a flat box (a plane of the 3-D box): the full N x N 2-D DFT of the cell values
+    on the plane against the numpy restatement of modules/fft.c:822-883,1101-1160"""
     from oracle import go_spectra as GS
     level = 5
     n = 1 << level
@@ -180,6 +180,7 @@ def test_output_spectra_of_a_plane_matches_the_restatement(normal, pos):
     F, ks = gd.output_spectra_plane(v, normal, pos)
     Fo, kso = GS.output_spectra_plane(a[1:-1, 1:-1, 1:-1], normal, pos)
     assert ks == kso
+    assert F.shape == Fo.shape == (n, n)
     assert np.abs(F - Fo).max() <= 1e-13 * max(1., np.abs(Fo).max())
     assert abs(F[0, 0]) <= 1e-15                   # the mean of the plane has been removed
     gd.destroy()
