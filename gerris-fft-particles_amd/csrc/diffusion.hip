@@ -129,8 +129,11 @@ static int relax_loop (gfship_domain * dom, Field * dp, Field * u, int level, Fi
   /* 3-D levels of 32^3 and more: the pipelined tile kernels with the diffusion cell update (rhoc
      travels as their dia stream); the whole loop in one launch on boxes without MPI sides */
   static const bool pipelined = getenv ("GFSHIP_DIFFUSION_HYPERPLANES") == nullptr;
-  if (pipelined && dom->dim == 3 && dom->relax_mode == GFSHIP_RELAX_EXACT && !dom->force_hyperplane &&
-      skew_supported (dom, level) && !(dom->has_external && dom->overlap && nrelax > 1))
+  const bool pipelined_applies = dom->dim == 3 && dom->relax_mode == GFSHIP_RELAX_EXACT && !dom->force_hyperplane &&
+    skew_supported (dom, level) && !(dom->has_external && dom->overlap && nrelax > 1);
+  if (pipelined_applies)
+    dom->kc[pipelined ? GFSHIP_KC_DIFFUSION_PIPELINED : GFSHIP_KC_DIFFUSION_HYPERPLANES]++;
+  if (pipelined && pipelined_applies)
     return launch_relax_loop_skew (dom, level, dp, u, res->lev[level], dia->lev[level], false, nrelax,
 				   true, nullptr, nullptr, &op);
   if ((r = launch_bc (dom, u, dp, level, 1))) return r;

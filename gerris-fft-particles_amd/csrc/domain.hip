@@ -215,6 +215,14 @@ int gfship_domain_path_counts (gfship_domain * dom, unsigned long long * lattice
   return GFSHIP_OK;
 }
 
+int gfship_domain_kernel_counts (gfship_domain * dom, unsigned long long * counts, int n)
+{
+  GFSHIP_CHECK (dom != nullptr && counts != nullptr && n >= 0, GFSHIP_EINVAL, "null argument");
+  for (int k = 0; k < n && k < GFSHIP_KC_COUNT; k++)
+    counts[k] = dom->kc[k];
+  return GFSHIP_OK;
+}
+
 int gfship_domain_synchronize (gfship_domain * dom)
 {
   GFSHIP_CHECK (dom != nullptr, GFSHIP_EINVAL, "null domain");

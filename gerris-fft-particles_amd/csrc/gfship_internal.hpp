@@ -137,6 +137,7 @@ struct gfship_domain {
   bool no_fused_prolongation = false;   // GFSHIP_NO_FUSED_PROLONGATION=1: prolongate_kernel, then the copy
   bool no_fused_mpi = false;      // GFSHIP_NO_FUSED_MPI=1: face-value arrays on boxes with MPI sides
   unsigned long long n_lattice_cycles = 0, n_fused_mpi = 0;   // gfship_domain_path_counts
+  unsigned long long kc[GFSHIP_KC_COUNT] = {};                // gfship_domain_kernel_counts
   bool lattice_attr_set = false;  // dynamic-LDS limit of lattice_cycle_kernel raised
   bool no_lattice_cycle = false;  // GFSHIP_NO_LATTICE_CYCLE=1: one exchange per sweep on every level
   void * mpi_plan[GFSHIP_MAXLEVEL + 1] = {};  // MPI-sides-first sweep order of each level (poisson_kernels.hip)
@@ -330,6 +331,7 @@ int  skew_arm_ahead (gfship_domain * dom, int level, unsigned nrelax);
 int  patch_resident_per_cu ();
 // the prolongation onto `level' can be done by the copy into the skewed layout of its relax loop
 bool prolongation_fused (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax);
+bool prolongation_fusable (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax);
 /* weighted sweeps (face weights from alpha) run on the six-wave kernel with its tile-skewed layout */
 inline bool patch_level (const gfship_domain * dom, int level) { return dom->patch && !dom->weighted && dom->lay[level].n >= dom->patch_min_n; }
 int  patch_pack (gfship_domain * dom, int level, SkewPlan * S, const double * u, const double * rhs,

@@ -13,11 +13,16 @@ namespace gfship {
 
 // weighted sweeps of this level run on the pipelined tile kernel (GFSHIP_WEIGHTED_HYPERPLANES=1: one
 // launch per hyperplane, the independent implementation)
+static bool weighted_pipelinable (gfship_domain * dom, unsigned dimension, int level)
+{
+  return dom->relax_mode == GFSHIP_RELAX_EXACT && dimension == 3 && dom->dim == 3 &&
+    skew_supported (dom, level) && !dom->force_hyperplane;
+}
+
 static bool weighted_pipelined (gfship_domain * dom, unsigned dimension, int level)
 {
   static const bool off = getenv ("GFSHIP_WEIGHTED_HYPERPLANES") != nullptr;
-  return !off && dom->relax_mode == GFSHIP_RELAX_EXACT && dimension == 3 && dom->dim == 3 &&
-    skew_supported (dom, level) && !dom->force_hyperplane;
+  return !off && weighted_pipelinable (dom, dimension, level);
 }
 
 // gfs_relax on one level (src/poisson.c:604-632)
@@ -30,9 +35,13 @@ static int relax_level (gfship_domain * dom, unsigned dimension, int level, doub
        cell streamed beside u / rhs / dia by the pipelined tile kernel (3-D levels >= 32^3), in one
        launch per sweep by rows (2-D) or in LDS (small 3-D levels) */
     RelaxOp op = weighted_op (dom, level);
-    if (weighted_pipelined (dom, dimension, level))
+    if (weighted_pipelined (dom, dimension, level)) {
+      dom->kc[GFSHIP_KC_WEIGHTED_PIPELINED]++;
       return launch_relax_loop_skew (dom, level, u, u, rhs->lev[level], dia->lev[level], false, 1, false,
 				     nullptr, nullptr, &op);
+    }
+    if (weighted_pipelinable (dom, dimension, level))
+      dom->kc[GFSHIP_KC_WEIGHTED_HYPERPLANES]++;
     return launch_relax_exact (dom, dimension, level, omega, u->lev[level], rhs->lev[level],
 			       dia->lev[level], &op);
   }
@@ -62,6 +71,7 @@ static int relax_loop (gfship_domain * dom, Field * dp, Field * u, unsigned dime
     /* the whole loop in one launch on boxes without MPI sides (the weights do not change between
        the sweeps), else sweep by sweep with the BC between */
     RelaxOp op = weighted_op (dom, level);
+    dom->kc[GFSHIP_KC_WEIGHTED_PIPELINED]++;
     return launch_relax_loop_skew (dom, level, dp, u, rhs->lev[level], dia->lev[level], false, nrelax,
 				   true, nullptr, nullptr, &op);
   }
@@ -396,8 +406,9 @@ static int poisson_cycle (gfship_domain * dom, gfship_multilevel_params * p,
 	TRY (skew_arm_ahead (dom, l + 1, nrl[l + 1]));
       /* where level l + 1 runs its relax loop on the 2 x 2 kernels the residual is copied into their
 	 layout by the same pass that restricts it (and so is the restricted one, where level l does) */
-      if (!dom->no_fused_restriction && !dom->skew[l + 1].rs_ready &&
-	  prolongation_fused (dom, p->dimension, l + 1, nrl[l + 1]))
+      const bool rp = !dom->skew[l + 1].rs_ready && prolongation_fused (dom, p->dimension, l + 1, nrl[l + 1]);
+      if (rp) dom->kc[dom->no_fused_restriction ? GFSHIP_KC_RESTRICTION_DECLINED : GFSHIP_KC_RESTRICTION_FUSED]++;
+      if (!dom->no_fused_restriction && rp)
 	TRY (launch_restrict_pack (dom, p->dimension, l + 1, S,
 				   l > (int) minlevel && prolongation_fused (dom, p->dimension, l, nrl[l])));
       else
@@ -417,12 +428,15 @@ static int poisson_cycle (gfship_domain * dom, gfship_multilevel_params * p,
       TRY (launch_fill (dom, minlevel, DP->lev[minlevel], 0.));
       TRY (relax_loop (dom, DP, U, p->dimension, minlevel, p->omega, S, D, nrl[minlevel]));
       first = minlevel + 1;
+      dom->kc[GFSHIP_KC_COARSE_END_BY_LEVEL]++;
     }
     /* relax from top to bottom */
     for (unsigned l = first; l <= p->depth; l++) {
       /* get initial guess from coarser grid -- on the levels of the 2 x 2 sweep kernels while the
 	 level is copied into their layout */
       const bool fp = prolongation_fused (dom, p->dimension, (int) l, nrl[l]);
+      if (fp) dom->kc[GFSHIP_KC_PROLONGATION_FUSED]++;
+      else if (prolongation_fusable (dom, p->dimension, (int) l, nrl[l])) dom->kc[GFSHIP_KC_PROLONGATION_DECLINED]++;
       if (!fp)
 	TRY (launch_prolongate (dom, l - 1, DP->lev[l - 1], DP->lev[l]));
       TRY (relax_loop (dom, DP, U, p->dimension, l, p->omega, S, D, nrl[l],

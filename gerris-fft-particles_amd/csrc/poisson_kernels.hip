@@ -278,7 +278,9 @@ int launch_relax_exact (gfship_domain * dom, unsigned dimension, int level, doub
   const Layout & L = dom->lay[level];
   int n = L.n;
   static const bool rows2d = getenv ("GFSHIP_NO_ROWS2D") == nullptr;
-  if (dom->dim == 2 && dimension == 2 && n >= 8 && n <= 1024 && rows2d && !dom->force_hyperplane)
+  const bool rows2d_apply = dom->dim == 2 && dimension == 2 && n >= 8 && n <= 1024 && !dom->force_hyperplane;
+  if (rows2d_apply) dom->kc[rows2d ? GFSHIP_KC_ROWS2D : GFSHIP_KC_HYPERPLANES_2D]++;
+  if (rows2d_apply && rows2d)
     return launch_relax_rows2d (dom, level, omega, u, rhs, dia, kind, w, h2, op);
   int nplanes = dom->dim == 3 ? 3*n - 2 : 2*n - 1;
   int nthreads = dom->dim == 3 ? n*n : n;
@@ -816,6 +818,8 @@ int launch_coarse_cycle (gfship_domain * dom, unsigned dimension, double omega, 
       dom->coarse_attr_set = true;
     }
     hipLaunchKernelGGL (coarse_cycle_kernel<3>, dim3 (1), dim3 (coarse_threads ()), bytes, dom->stream, A);
+    dom->kc[GFSHIP_KC_COARSE_CYCLES]++;
+    dom->kc[GFSHIP_KC_COARSE_THREADS] = coarse_threads ();
   }
   else {
     if (!dom->coarse_attr_set) {
@@ -824,6 +828,8 @@ int launch_coarse_cycle (gfship_domain * dom, unsigned dimension, double omega, 
       dom->coarse_attr_set = true;
     }
     hipLaunchKernelGGL (coarse_cycle_kernel<2>, dim3 (1), dim3 (coarse_threads ()), bytes, dom->stream, A);
+    dom->kc[GFSHIP_KC_COARSE_CYCLES]++;
+    dom->kc[GFSHIP_KC_COARSE_THREADS] = coarse_threads ();
   }
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
@@ -1334,6 +1340,7 @@ int launch_residual (gfship_domain * dom, int level, const double * u, const dou
   dim3 grid, block;
   cell_grid (L, &grid, &block);
   static const bool pairs = getenv ("GFSHIP_RN_SCALAR") == nullptr;
+  if (dom->dim == 3 && L.n >= 64) dom->kc[pairs ? GFSHIP_KC_RESIDUAL_PAIRS : GFSHIP_KC_RESIDUAL_SCALAR]++;
   if (dom->dim == 3 && L.n >= 64 && pairs) {
     /* two cells per thread, 16-byte accesses (residual_norm2_kernel without the norm) */
     const long nitems = (long) L.n*L.n*(L.n/2);
@@ -1903,6 +1910,7 @@ int launch_residual_norm (gfship_domain * dom, int level, const double * u, cons
   double * partial = dom->d_scratch;
   double * result = out ? dom->h_pinned : dom->h_pinned + 8;
   static const bool rn_pairs = getenv ("GFSHIP_RN_SCALAR") == nullptr;
+  if (dom->dim == 3 && L.n >= 64) dom->kc[rn_pairs ? GFSHIP_KC_RESIDUAL_PAIRS : GFSHIP_KC_RESIDUAL_SCALAR]++;
   if (dom->dim == 3 && L.n >= 64 && rn_pairs) {
     const long nitems = (long) L.n*L.n*(L.n/2);
     long nb = (nitems + 255)/256;
@@ -1919,6 +1927,9 @@ int launch_residual_norm (gfship_domain * dom, int level, const double * u, cons
   hipLaunchKernelGGL (norm_final_kernel, dim3 (1), dim3 (256), 0, dom->stream,
 		      partial, nblocks, result);
   GFSHIP_HIP (hipGetLastError ());
+  dom->kc[GFSHIP_KC_RN_BLOCKS_LIMIT] = rn_blocks;
+  if ((unsigned long long) nblocks > dom->kc[GFSHIP_KC_RN_BLOCKS_MAX])
+    dom->kc[GFSHIP_KC_RN_BLOCKS_MAX] = nblocks;
   if (out) {
     GFSHIP_HIP (stream_wait_spin (dom->stream));
     memcpy (out, dom->h_pinned, 5*sizeof (double));

@@ -1401,7 +1401,9 @@ int patch_pack (gfship_domain * dom, int level, SkewPlan * S, const double * u, 
   if (rhs) { A.src[A.narr] = rhs; A.dst[A.narr++] = S->rs; }     /* nullptr: already there (patch_restrict_pack) */
   if (dia) { A.src[A.narr] = dia; A.dst[A.narr++] = S->ds; }
   const int rows = A.L.n + PK_SKEW + 1;
-  if (coarse && !getenv ("GFSHIP_OLD_PROLONG_PACK")) {
+  const bool old_pack = coarse && getenv ("GFSHIP_OLD_PROLONG_PACK");
+  if (coarse) dom->kc[old_pack ? GFSHIP_KC_PROLONG_PACK_OLD : GFSHIP_KC_PROLONG_PACK_NEW]++;
+  if (coarse && !old_pack) {
     /* the prolongation straight into the layout (patch_prolong_kernel); arrays that still have to be
        copied (a dia that is not zero; the rhs when the restriction has not left it there) follow in
        the transposing copy */

@@ -543,7 +543,13 @@ static int skew_loop_trial (gfship_domain * dom, int level, SkewPlan * S, unsign
 
 bool prolongation_fused (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax)
 {
-  if (dom->no_fused_prolongation || dom->weighted || level < 1) return false;
+  return !dom->no_fused_prolongation && prolongation_fusable (dom, dimension, level, nrelax);
+}
+
+// ... where nothing but GFSHIP_NO_FUSED_PROLONGATION stands against it
+bool prolongation_fusable (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax)
+{
+  if (dom->weighted || level < 1) return false;
   if (dom->relax_mode != GFSHIP_RELAX_EXACT || dimension != 3 || dom->force_hyperplane) return false;
   if (dom->has_external && dom->overlap && nrelax > 1) return false;
   return skew_supported (dom, level) && patch_level (dom, level);

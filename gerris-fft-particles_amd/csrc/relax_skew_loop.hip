@@ -886,7 +886,7 @@ static SetGeometry skew_set_geometry (const gfship_domain * dom, int level, cons
 int skew_arm_ahead (gfship_domain * dom, int level, unsigned nrelax)
 {
   SkewPlan * S = &dom->skew[level];
-  if (dom->no_arm_ahead || !dom->side_stream || !S->hbf || S->arm_wait || nrelax < 2 || nrelax > SK_MAXF)
+  if (!dom->side_stream || !S->hbf || S->arm_wait || nrelax < 2 || nrelax > SK_MAXF)
     return GFSHIP_OK;           /* nothing allocated yet (first loop of the level): armed in line */
   if (dom->no_fused_loop || !skew_loop_supported (dom, level, nrelax, true))
     return GFSHIP_OK;
@@ -896,6 +896,11 @@ int skew_arm_ahead (gfship_domain * dom, int level, unsigned nrelax)
   const int set = S->cur_set;
   if (S->armed[set] >= G.need)
     return GFSHIP_OK;
+  if (dom->no_arm_ahead) {      /* GFSHIP_NO_ARM_AHEAD=1: left to the loop */
+    dom->kc[GFSHIP_KC_ARM_AHEAD_DECLINED]++;
+    return GFSHIP_OK;
+  }
+  dom->kc[GFSHIP_KC_ARM_AHEAD]++;
   if (!S->arm_ev)
     GFSHIP_HIP (hipEventCreateWithFlags (&S->arm_ev, hipEventDisableTiming));
   u64 * const base = (u64 *) S->hbf + (size_t) set*G.set_words;
@@ -942,9 +947,13 @@ int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat,
     GFSHIP_HIP (hipStreamWaitEvent (dom->stream, S->arm_ev, 0));
     S->arm_wait = false;
   }
-  if (S->armed[set] < need)
+  if (S->armed[set] < need) {
     GFSHIP_HIP (hipMemsetAsync (base, 0xFF, need*sizeof (u64), dom->stream));
+    dom->kc[GFSHIP_KC_ARM_INLINE]++;
+  }
   const bool arms = patch_level (dom, level) && !dom->no_kernel_arming;
+  if (patch_level (dom, level))
+    dom->kc[arms ? GFSHIP_KC_PATCH_LOOP_KERNEL_ARMS : GFSHIP_KC_PATCH_LOOP_HOST_ARMS]++;
   if (arms && !S->arm_cum) {
     /* tile (P, Q) starts about P + Q hops after the first: its share of the arming grows with that
        slack, the tiles of the first diagonals get none */
@@ -1001,12 +1010,17 @@ int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat,
       A.per_xcd = ntiles/8;
       A.xticket = (unsigned *) (base + 1);
       { const char * e = getenv ("GFSHIP_XCD_NEAR_MODE"); A.near_mode = e ? atoi (e) : 2; }
+      dom->kc[GFSHIP_KC_XCD_NEAR_MODE] = 1 + (unsigned long long) (A.near_mode < 0 ? 0 : A.near_mode);
     }
+    dom->kc[A.per_xcd ? GFSHIP_KC_XCD_SCOPE_ON : GFSHIP_KC_XCD_SCOPE_OFF]++;
   }
   else if (dom->xcd_place && S->xorder && ntiles >= 8 && skew_loop_resident (dom, level) >= ntiles) {
     A.per_xcd = ntiles/8;
     GFSHIP_HIP (hipMemsetAsync ((unsigned *) S->ctl + 6, 0, 8*sizeof (unsigned), dom->stream));
+    dom->kc[GFSHIP_KC_XCD_PLACE_ON]++;
   }
+  else if (ntiles >= 8)
+    dom->kc[GFSHIP_KC_XCD_PLACE_OFF]++;
   A.ticket = (unsigned *) base;
   A.err = (unsigned *) (dom->h_pinned + 32) + level;     /* skew_err_word, relax_skew.hip */
   A.dummy = (const u64 *) S->ctl + 2;

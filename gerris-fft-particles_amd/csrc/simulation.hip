@@ -132,8 +132,12 @@ int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, g
     s->un_lazy = false;                /* un is rewritten (or declared unstored) below */
   if (approximate)
     TRY (launch_face_interp_div (dom, u, lazy ? nullptr : un, leaf (s, s->div), dt));
-  else if (!(s->div_ready && s->div_dt == dt))       /* left there by the predictor (sweep along z) */
+  else if (!(s->div_ready && s->div_dt == dt)) {     /* left there by the predictor (sweep along z) */
     TRY (launch_divergence (dom, un, leaf (s, s->div), dt));
+    dom->kc[GFSHIP_KC_DIVERGENCE_SEPARATE]++;
+  }
+  else
+    dom->kc[GFSHIP_KC_DIVERGENCE_FUSED]++;
   s->div_ready = false;
   TRY (gfship_poisson_solve (dom, par, p, s->div, s->res, s->dia, dt));
   /* gfs_correct_normal_velocities + gfs_scale_gradients, and for the approximate projection
@@ -258,6 +262,7 @@ int variable_sources (gfship_sim * s, gfship_field v, gfship_field sv, int gradi
     std::swap (dom->fields[v].lev[L], dom->fields[s->adv_tmp].lev[L]);
     return GFSHIP_OK;
   }
+  s->dom->kc[GFSHIP_KC_ADVECT_GENERAL]++;
   TRY (face_values_set (s, v, dt, 0, gradient));
   const double * gm = velocity ? leaf (s, gmac[c]) : nullptr;
   const double * gc = (velocity && g) ? leaf (s, g[c]) : nullptr;
@@ -490,7 +495,9 @@ static int predicted_face_velocities (gfship_sim * s, double mac_dt)
     double * u[3], * un[3];
     ptrs3 (s, s->u, u);
     ptrs3 (s, s->un, un);
-    const bool want_div = mac_dt != 0. && s->dom->dim == 3 && !getenv ("GFSHIP_NO_FUSED_DIVERGENCE");
+    const bool div_applies = mac_dt != 0. && s->dom->dim == 3;
+    const bool want_div = div_applies && !getenv ("GFSHIP_NO_FUSED_DIVERGENCE");
+    if (div_applies && !want_div) s->dom->kc[GFSHIP_KC_DIVERGENCE_DECLINED]++;
     bool done = false;
     TRY (launch_predict_un_fused (s->dom, u, s->advection_params.dt,
 				  s->advection_params.gradient, s->visc, un,
@@ -502,6 +509,7 @@ static int predicted_face_velocities (gfship_sim * s, double mac_dt)
     }
     return GFSHIP_OK;
   }
+  s->dom->kc[GFSHIP_KC_PREDICT_GENERAL]++;
   for (int c = 0; c < s->dom->dim; c++) {
     /* only the faces normal to component c are read by gfs_face_advected_normal_velocity */
     TRY (face_values_set (s, s->u[c], s->advection_params.dt, 1, s->advection_params.gradient, 1 << c));
@@ -566,7 +574,9 @@ static int centered_velocity_advection (gfship_sim * s, const gfship_field gmac[
     ptrs3 (s, s->un, un);
     ptrs3 (s, gmac, gm);
     if (g) ptrs3 (s, g, gc);
-    const bool fuse = corr_dt != 0. && g && corrected && !getenv ("GFSHIP_NO_FUSED_CORRECTION");
+    const bool corr_applies = corr_dt != 0. && g && corrected;
+    const bool fuse = corr_applies && !getenv ("GFSHIP_NO_FUSED_CORRECTION");
+    if (corr_applies) dom->kc[fuse ? GFSHIP_KC_CORRECTION_FUSED : GFSHIP_KC_CORRECTION_DECLINED]++;
     double * uc[3] = { nullptr, nullptr, nullptr };
     if (fuse && u_coarse && L >= 1)
       for (int c = 0; c < 3; c++) {

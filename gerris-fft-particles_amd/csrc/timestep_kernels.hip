@@ -3088,7 +3088,9 @@ int launch_project_correct (gfship_domain * dom, const double * p, double * cons
   }
   Ptr3 none = { { nullptr, nullptr, nullptr } };
   static const bool pairs = getenv ("GFSHIP_PC_SCALAR") == nullptr;
-  if (dom->dim == 3 && !u && !pm && pairs && L.n >= 64 && L.n % 2 == 0) {
+  const bool pairs_apply = dom->dim == 3 && !u && !pm && L.n >= 64 && L.n % 2 == 0;
+  if (pairs_apply) dom->kc[pairs ? GFSHIP_KC_PROJECT_PAIRS : GFSHIP_KC_PROJECT_SCALAR]++;
+  if (pairs_apply && pairs) {
     /* the MAC projection: two cells per thread, 16-byte accesses */
     const int b = 128, half = L.n/2;
     hipLaunchKernelGGL (project_correct2_kernel, dim3 ((half + b - 1)/b, L.n + 1, L.n + 1), dim3 (b), 0, dom->stream,
@@ -3158,7 +3160,9 @@ int launch_face_interp_div (gfship_domain * dom, double * const u[3], double * c
   else {
     Ptr3 none = { { nullptr, nullptr, nullptr } };
     static const bool pairs = getenv ("GFSHIP_PC_SCALAR") == nullptr;
-    if (dom->dim == 3 && pairs && L.n >= 64 && L.n % 2 == 0) {
+    const bool pairs_apply = dom->dim == 3 && L.n >= 64 && L.n % 2 == 0;
+    if (pairs_apply) dom->kc[pairs ? GFSHIP_KC_PROJECT_PAIRS : GFSHIP_KC_PROJECT_SCALAR]++;
+    if (pairs_apply && pairs) {
       const int b = 128, half = L.n/2;
       hipLaunchKernelGGL (face_interp_div2_kernel, dim3 ((half + b - 1)/b, L.n, L.n), dim3 (b), 0, dom->stream, L, c3 (u), div, dt);
     }
@@ -3189,7 +3193,9 @@ int launch_project_correct_lazy (gfship_domain * dom, const double * p, double *
     GFSHIP_HIP (hipMemsetAsync (dom->cfl_partial, 0, nb*sizeof (double), dom->stream));
   dom->cfl_dirty = true;
   static const bool pairs = getenv ("GFSHIP_PC_SCALAR") == nullptr;
-  if (dom->dim == 3 && pairs && L.n >= 64 && L.n % 2 == 0) {
+  const bool pairs_apply = dom->dim == 3 && L.n >= 64 && L.n % 2 == 0;
+  if (pairs_apply) dom->kc[pairs ? GFSHIP_KC_PROJECT_PAIRS : GFSHIP_KC_PROJECT_SCALAR]++;
+  if (pairs_apply && pairs) {
     /* two cells per thread, 16-byte accesses */
     const int b = 128, half = L.n/2;
     hipLaunchKernelGGL (project_correct_lazy2_kernel, dim3 ((half + b - 1)/b, L.n + 1, L.n + 1), dim3 (b), 0, dom->stream,
@@ -3268,6 +3274,7 @@ int launch_predict_un_fused (gfship_domain * dom, double * const u[3], double dt
     else          { if (anyv) PS (false, true); else PS (false, false); }
 #undef PS
     GFSHIP_HIP (hipGetLastError ());
+    dom->kc[GFSHIP_KC_PREDICT_SWEEP]++;
     if (div_done) *div_done = dv;
     return GFSHIP_OK;
   }
@@ -3301,6 +3308,7 @@ int launch_predict_un_fused (gfship_domain * dom, double * const u[3], double dt
       else          { if (anyv) PSM (false, true); else PSM (false, false); }
 #undef PSM
       GFSHIP_HIP (hipGetLastError ());
+      dom->kc[GFSHIP_KC_PREDICT_SWEEP_MPI]++;
       if (div_done) *div_done = dv;
       return GFSHIP_OK;
     }
@@ -3310,6 +3318,7 @@ int launch_predict_un_fused (gfship_domain * dom, double * const u[3], double dt
   else          { if (anyv) PK (false, true); else PK (false, false); }
 #undef PK
   GFSHIP_HIP (hipGetLastError ());
+  dom->kc[mpi ? GFSHIP_KC_PREDICT_TILED_MPI : GFSHIP_KC_PREDICT_TILED]++;
   return GFSHIP_OK;
 }
 
@@ -3332,6 +3341,7 @@ int launch_advect_fused (gfship_domain * dom, bool velocity, const double * v, d
   }
 #undef AK
   GFSHIP_HIP (hipGetLastError ());
+  dom->kc[velocity ? GFSHIP_KC_ADVECT1_TILED_VELOCITY : GFSHIP_KC_ADVECT1_TILED_TRACER]++;
   return GFSHIP_OK;
 }
 
@@ -3383,6 +3393,7 @@ int launch_advect3_fused (gfship_domain * dom, double * const v[3], double * con
     else          { if (srcs0) SK3M (false, true); else SK3M (false, false); }
 #undef SK3M
     GFSHIP_HIP (hipGetLastError ());
+    dom->kc[GFSHIP_KC_ADVECT3_SWEEP2_MPI]++;
     return GFSHIP_OK;
   }
   if (!mpi && sweep_ok && L.n % SWX == 0 && L.n % SWY == 0 && L.n % SWZ == 0) {
@@ -3403,6 +3414,7 @@ int launch_advect3_fused (gfship_domain * dom, double * const v[3], double * con
     else          { if (srcs0) SK3 (false, true); else SK3 (false, false); }
 #undef SK3
     GFSHIP_HIP (hipGetLastError ());
+    dom->kc[sweep1 ? GFSHIP_KC_ADVECT3_SWEEP1 : GFSHIP_KC_ADVECT3_SWEEP2]++;
     return GFSHIP_OK;
   }
 #define AK(VL_, MPI_, SRC_) do { \
@@ -3421,6 +3433,7 @@ int launch_advect3_fused (gfship_domain * dom, double * const v[3], double * con
   else AK (false, false, false);
 #undef AK
   GFSHIP_HIP (hipGetLastError ());
+  dom->kc[mpi ? GFSHIP_KC_ADVECT3_TILED_MPI : GFSHIP_KC_ADVECT3_TILED]++;
   return GFSHIP_OK;
 }
 

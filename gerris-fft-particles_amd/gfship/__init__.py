@@ -120,6 +120,7 @@ SIGNATURES = {
     "gfship_domain_set_reduce": (_i, [_vp, _vp, _vp]),
     "gfship_domain_set_gather": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(C.c_int)]),
     "gfship_domain_path_counts": (_i, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "gfship_domain_kernel_counts": (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
     "gfship_sim_restart": (_i, [_vp, _d, _u]),
     "gfship_snapshot_tree_bytes": (C.c_size_t, [_vp, _i]),
     "gfship_snapshot_tree_write": (_i, [_vp, _i, _pi, _vp, C.c_size_t]),
@@ -192,6 +193,23 @@ SIGNATURES = {
 
 
 UNIQUE_ID_BYTES = 128
+
+# the families of gfship_domain_kernel_counts, in the order of the GFSHIP_KC_* constants of gfship.h
+KERNEL_COUNT_NAMES = (
+    "PREDICT_SWEEP", "PREDICT_SWEEP_MPI", "PREDICT_TILED", "PREDICT_TILED_MPI", "PREDICT_GENERAL",
+    "ADVECT3_SWEEP2", "ADVECT3_SWEEP2_MPI", "ADVECT3_SWEEP1", "ADVECT3_TILED", "ADVECT3_TILED_MPI",
+    "ADVECT1_TILED_VELOCITY", "ADVECT1_TILED_TRACER", "ADVECT_GENERAL", "CORRECTION_FUSED",
+    "CORRECTION_DECLINED", "DIVERGENCE_FUSED", "DIVERGENCE_DECLINED", "DIVERGENCE_SEPARATE",
+    "PROJECT_PAIRS", "PROJECT_SCALAR", "RESIDUAL_PAIRS", "RESIDUAL_SCALAR", "RN_BLOCKS_LIMIT",
+    "RN_BLOCKS_MAX", "ROWS2D", "HYPERPLANES_2D", "DIFFUSION_PIPELINED", "DIFFUSION_HYPERPLANES",
+    "WEIGHTED_PIPELINED", "WEIGHTED_HYPERPLANES", "PROLONGATION_FUSED", "PROLONGATION_DECLINED",
+    "RESTRICTION_FUSED", "RESTRICTION_DECLINED", "PROLONG_PACK_NEW", "PROLONG_PACK_OLD",
+    "ARM_AHEAD", "ARM_AHEAD_DECLINED", "ARM_INLINE", "PATCH_LOOP_KERNEL_ARMS",
+    "PATCH_LOOP_HOST_ARMS", "XCD_SCOPE_ON", "XCD_SCOPE_OFF", "XCD_NEAR_MODE", "XCD_PLACE_ON",
+    "XCD_PLACE_OFF", "COARSE_CYCLES", "COARSE_THREADS", "COARSE_END_BY_LEVEL",
+)
+# ... of which these hold a value (a limit, a thread count, a mode) instead of a tally
+KERNEL_COUNT_VALUES = ("RN_BLOCKS_LIMIT", "RN_BLOCKS_MAX", "XCD_NEAR_MODE", "COARSE_THREADS")
 
 
 def comm_available():
@@ -314,6 +332,14 @@ class Domain:
         a, b = C.c_ulonglong(), C.c_ulonglong()
         _check(lib().gfship_domain_path_counts(self.ptr, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def kernel_counts(self):
+        """{family: tally} of gfship_domain_kernel_counts: which branch of every switchable dispatch has
+        run on this domain (KERNEL_COUNT_NAMES; the families of KERNEL_COUNT_VALUES hold a value)"""
+        n = len(KERNEL_COUNT_NAMES)
+        a = (C.c_ulonglong * n)()
+        _check(lib().gfship_domain_kernel_counts(self.ptr, a, n))
+        return {name: int(a[k]) for k, name in enumerate(KERNEL_COUNT_NAMES)}
 
     def snapshot_tree(self, variables):
         """the binary cell data of a GfsBox (gfship_snapshot_tree_write) as bytes"""

@@ -503,6 +503,65 @@ int  gfship_domain_set_gather (gfship_domain * dom, gfship_gather_fn fn, void * 
    exchanged in one message per side (library communicator only, GFSHIP_NO_FUSED_MPI=1 disables). */
 int  gfship_domain_path_counts (gfship_domain * dom, unsigned long long * lattice_cycles,
 				unsigned long long * fused_mpi_launches);
+/* Which branch of every switchable dispatch has run on this domain (for tests: the variants behind the
+   GFSHIP_* environment switches are bit-identical, and a test that sets one needs proof that the other
+   branch really ran).  Plain host-side tallies made where the kernel is chosen; nothing on the device
+   knows of them.  counts[k] receives family k for k < min (n, GFSHIP_KC_COUNT).  Unless said
+   otherwise a family counts launches (or sweeps / loops, where one decision covers several launches);
+   the "declined" families count the times a switch alone kept a fused pass from being used. */
+enum {
+  GFSHIP_KC_PREDICT_SWEEP = 0,       /* predict_un_sweep_kernel, periodic box */
+  GFSHIP_KC_PREDICT_SWEEP_MPI,       /* ... with the states beyond the MPI sides from the buffers */
+  GFSHIP_KC_PREDICT_TILED,           /* predict_un_tiled_kernel, periodic box */
+  GFSHIP_KC_PREDICT_TILED_MPI,       /* ... on a box with MPI sides */
+  GFSHIP_KC_PREDICT_GENERAL,         /* face-value arrays + predict_un_kernel per component */
+  GFSHIP_KC_ADVECT3_SWEEP2,          /* advect3_sweep2_kernel, periodic box */
+  GFSHIP_KC_ADVECT3_SWEEP2_MPI,
+  GFSHIP_KC_ADVECT3_SWEEP1,          /* advect3_sweep_kernel (GFSHIP_ADVECT_SWEEP1) */
+  GFSHIP_KC_ADVECT3_TILED,           /* advect3_tiled_kernel, periodic box */
+  GFSHIP_KC_ADVECT3_TILED_MPI,
+  GFSHIP_KC_ADVECT1_TILED_VELOCITY,  /* advect_tiled_kernel on one velocity component */
+  GFSHIP_KC_ADVECT1_TILED_TRACER,    /* advect_tiled_kernel on a tracer */
+  GFSHIP_KC_ADVECT_GENERAL,          /* face-value arrays + flux kernel, one variable */
+  GFSHIP_KC_CORRECTION_FUSED,        /* centred correction + coarse fill inside the advection pass */
+  GFSHIP_KC_CORRECTION_DECLINED,     /* GFSHIP_NO_FUSED_CORRECTION alone kept it separate */
+  GFSHIP_KC_DIVERGENCE_FUSED,        /* MAC divergence left behind by the predictor sweep */
+  GFSHIP_KC_DIVERGENCE_DECLINED,     /* GFSHIP_NO_FUSED_DIVERGENCE alone kept it separate */
+  GFSHIP_KC_DIVERGENCE_SEPARATE,     /* divergence kernel of the MAC projection */
+  GFSHIP_KC_PROJECT_PAIRS,           /* projection update / face interpolation, two cells per thread */
+  GFSHIP_KC_PROJECT_SCALAR,          /* the same launches by the one-cell kernels (GFSHIP_PC_SCALAR) */
+  GFSHIP_KC_RESIDUAL_PAIRS,          /* residual (+ norm), two cells per thread */
+  GFSHIP_KC_RESIDUAL_SCALAR,         /* the same launches by the one-cell kernels (GFSHIP_RN_SCALAR) */
+  GFSHIP_KC_RN_BLOCKS_LIMIT,         /* value: the limit on workgroups of residual + norm last applied */
+  GFSHIP_KC_RN_BLOCKS_MAX,           /* value: the largest grid residual + norm was launched with */
+  GFSHIP_KC_ROWS2D,                  /* 2-D sweeps by relax_rows2d_kernel */
+  GFSHIP_KC_HYPERPLANES_2D,          /* 2-D sweeps, one launch per hyperplane */
+  GFSHIP_KC_DIFFUSION_PIPELINED,     /* diffusion relax loops on the pipelined tile kernels */
+  GFSHIP_KC_DIFFUSION_HYPERPLANES,   /* the same loops, one launch per hyperplane */
+  GFSHIP_KC_WEIGHTED_PIPELINED,      /* weighted sweeps / loops on the pipelined tile kernel */
+  GFSHIP_KC_WEIGHTED_HYPERPLANES,    /* the same sweeps, one launch per hyperplane */
+  GFSHIP_KC_PROLONGATION_FUSED,      /* prolongation while the level is packed */
+  GFSHIP_KC_PROLONGATION_DECLINED,   /* GFSHIP_NO_FUSED_PROLONGATION alone: prolongate_kernel, then the copy */
+  GFSHIP_KC_RESTRICTION_FUSED,       /* restriction while the residual is packed */
+  GFSHIP_KC_RESTRICTION_DECLINED,    /* GFSHIP_NO_FUSED_RESTRICTION alone: restrict_kernel, then the copy */
+  GFSHIP_KC_PROLONG_PACK_NEW,        /* patch_prolong_kernel */
+  GFSHIP_KC_PROLONG_PACK_OLD,        /* prolongation inside patch_pack_kernel (GFSHIP_OLD_PROLONG_PACK) */
+  GFSHIP_KC_ARM_AHEAD,               /* granule sets armed on the side stream */
+  GFSHIP_KC_ARM_AHEAD_DECLINED,      /* GFSHIP_NO_ARM_AHEAD alone left the set to the loop */
+  GFSHIP_KC_ARM_INLINE,              /* granule sets armed on the main stream, before the loop */
+  GFSHIP_KC_PATCH_LOOP_KERNEL_ARMS,  /* 2 x 2 loops that arm the other set (GFSHIP_KERNEL_ARMING) */
+  GFSHIP_KC_PATCH_LOOP_HOST_ARMS,    /* 2 x 2 loops that do not */
+  GFSHIP_KC_XCD_SCOPE_ON,            /* 2 x 2 loops with XCD blocks (GFSHIP_XCD_SCOPE) */
+  GFSHIP_KC_XCD_SCOPE_OFF,           /* 2 x 2 loops without */
+  GFSHIP_KC_XCD_NEAR_MODE,           /* value: 1 + the GFSHIP_XCD_NEAR_MODE last used, 0 = never */
+  GFSHIP_KC_XCD_PLACE_ON,            /* one-line loops of >= 8 tiles placed by XCD (GFSHIP_XCD_PLACE) */
+  GFSHIP_KC_XCD_PLACE_OFF,           /* one-line loops of >= 8 tiles in ticket order */
+  GFSHIP_KC_COARSE_CYCLES,           /* coarse ends of V-cycles in one launch */
+  GFSHIP_KC_COARSE_THREADS,          /* value: threads of the last such launch */
+  GFSHIP_KC_COARSE_END_BY_LEVEL,     /* V-cycles whose coarse end ran level by level */
+  GFSHIP_KC_COUNT
+};
+int  gfship_domain_kernel_counts (gfship_domain * dom, unsigned long long * counts, int n);
 /* The same boundary served inside the library over RCCL (xGMI on one node), no hooks: the domain
    is one GfsBox of a periodic lattice of lattice[0] x lattice[1] x lattice[2] boxes, one box per
    rank / GPU, rank r at (r % bx, (r / bx) % by, r / (bx by)) (gfs_domain_split, src/domain.c:2576-2599,

@@ -7,8 +7,9 @@ runs once and checks everything it can on the way.
             them on 8x8 tiles, the coarse end in LDS)
   config C  256^3 triply periodic: one V-cycle on random fields (16x16 tiles, the fused relax
             loops of the 256^3 .. 32^3 levels) and one full Taylor-Green time step after
-            simulation_run's start-up (the tiled Godunov kernels on 8x64x64 tiles, fused
-            projection updates, CFL)
+            simulation_run's start-up (the Godunov kernels as sweeps along z in chunks of 64
+            planes, fused projection updates, CFL; the tiled Godunov kernels with several tiles
+            along x are pinned by tests/test_gpu_switches.py)
   config D  10^5 tracers over 24 events on a 64^3 Taylor-Green box, incl. the re-sort by cell after
             16 events: positions (hence cell indices), ids and list order identical
 """
