@@ -128,7 +128,7 @@ static int relax_loop (gfship_domain * dom, Field * dp, Field * u, int level, Fi
     return GFSHIP_OK;
   /* 3-D levels of 32^3 and more: the pipelined tile kernels with the diffusion cell update (rhoc
      travels as their dia stream); the whole loop in one launch on boxes without MPI sides */
-  static const bool pipelined = getenv ("GFSHIP_DIFFUSION_HYPERPLANES") == nullptr;
+  const bool pipelined = dom->sw.diffusion_pipelined;
   const bool pipelined_applies = dom->dim == 3 && dom->relax_mode == GFSHIP_RELAX_EXACT && !dom->force_hyperplane &&
     skew_supported (dom, level) && !(dom->has_external && dom->overlap && nrelax > 1);
   if (pipelined_applies)

@@ -106,19 +106,7 @@ int gfship_domain_create (gfship_domain ** out, int dim, int depth, const int si
     gfship_domain_destroy (dom);
     return r;
   }
-  dom->skew_old = getenv ("GFSHIP_SKEW_OLD") != nullptr;
-  dom->patch = getenv ("GFSHIP_SKEW_LINES") == nullptr && !dom->skew_old;
-  { const char * w = getenv ("GFSHIP_PATCH_MIN_N"); if (w) dom->patch_min_n = atoi (w); }
-  dom->no_fused_godunov3 = getenv ("GFSHIP_NO_ADVECT3") != nullptr;
-  dom->no_lattice_cycle = getenv ("GFSHIP_NO_LATTICE_CYCLE") != nullptr;
-  dom->no_fused_mpi = getenv ("GFSHIP_NO_FUSED_MPI") != nullptr;
-  dom->no_fused_prolongation = getenv ("GFSHIP_NO_FUSED_PROLONGATION") != nullptr;
-  dom->no_kernel_arming = getenv ("GFSHIP_KERNEL_ARMING") == nullptr;
-  dom->no_xcd_scope = getenv ("GFSHIP_XCD_SCOPE") == nullptr;
-  dom->no_fused_restriction = getenv ("GFSHIP_NO_FUSED_RESTRICTION") != nullptr;
-  dom->no_arm_ahead = getenv ("GFSHIP_NO_ARM_AHEAD") != nullptr;
-  { const char * w = getenv ("GFSHIP_XCD_PLACE"); dom->xcd_place = w && w[0] == '1'; }
-  { const char * w = getenv ("GFSHIP_WAVE_LOOP"); dom->wave_loop = w && w[0] == '1'; }
+  dom->sw = read_switches ();
   *out = dom;
   return GFSHIP_OK;
 }

@@ -8,7 +8,9 @@
 #include <vector>
 #include <deque>
 #include <string>
+#include <type_traits>
 #include "gfship.h"
+#include "switches.hpp"
 
 namespace gfship {
 
@@ -97,6 +99,7 @@ struct gfship_domain {
   int dim = 3, depth = 0, device = 0;
   int side[6] = {1, 1, 1, 1, 1, 1};
   int relax_mode = GFSHIP_RELAX_EXACT;
+  gfship::Switches sw;                // the GFSHIP_* environment switches, read by gfship_domain_create
   gfship::Layout lay[GFSHIP_MAXLEVEL + 1];
   std::deque<gfship::Field> fields;   // deque: handles stay valid while fields are added
   hipStream_t stream = nullptr;
@@ -106,7 +109,6 @@ struct gfship_domain {
   // latency-bound coarse levels, forked and joined with events
   hipStream_t side_stream = nullptr;
   hipEvent_t side_fork = nullptr;
-  bool no_arm_ahead = false;       // GFSHIP_NO_ARM_AHEAD=1: the granules are armed in line, before the loop
   // called by every entry point that writes a field of the domain on behalf of the caller (upload, fill,
   // raw pointer, bc, snapshot read, the solvers called on their own ...: gfship::before_write): the
   // simulation of the domain, which keeps derived state unstored (its MAC velocities, simulation.hip:
@@ -131,26 +133,14 @@ struct gfship_domain {
   size_t lat_res_doubles = 0, lat_xch_doubles = 0;
   double * gfv_send[6] = {}, * gfv_recv[6] = {};   // states beyond the MPI sides of the tiled Godunov kernels
   double src[3] = { 0., 0., 0. };       // GfsSource {} U/V/W: constant intensities (gfship_sim_set_source)
-  bool no_xcd_scope = true;             // GFSHIP_XCD_SCOPE=1: XCD blocks of tiles + narrower-scope stores towards same-XCD consumers (measured: no gain)
-  bool no_fused_restriction = false;    // GFSHIP_NO_FUSED_RESTRICTION=1: restrict_kernel, then the copy of the rhs
-  bool no_kernel_arming = true;         // GFSHIP_KERNEL_ARMING=1: the loop kernels arm the other granule set (measured: no gain)
-  bool no_fused_prolongation = false;   // GFSHIP_NO_FUSED_PROLONGATION=1: prolongate_kernel, then the copy
-  bool no_fused_mpi = false;      // GFSHIP_NO_FUSED_MPI=1: face-value arrays on boxes with MPI sides
   unsigned long long n_lattice_cycles = 0, n_fused_mpi = 0;   // gfship_domain_path_counts
   unsigned long long kc[GFSHIP_KC_COUNT] = {};                // gfship_domain_kernel_counts
   bool lattice_attr_set = false;  // dynamic-LDS limit of lattice_cycle_kernel raised
-  bool no_lattice_cycle = false;  // GFSHIP_NO_LATTICE_CYCLE=1: one exchange per sweep on every level
   void * mpi_plan[GFSHIP_MAXLEVEL + 1] = {};  // MPI-sides-first sweep order of each level (poisson_kernels.hip)
   gfship_field dp_cache = -1;     // the `dp` temporary of gfs_poisson_cycle, kept between cycles
   int skew_resident = -1;         // workgroups of the fused relax loop that fit on the device
   int patch_resident = 0;         // the same for the kernels of relax_patch_loop.hip
-  bool wave_loop = false;         // fused relax loops by the experimental one-wave-per-tile kernel (GFSHIP_WAVE_LOOP=1)
-  bool xcd_place = false;         // XCD-aware tile placement in the loop kernel (experiment, GFSHIP_XCD_PLACE=1)
-  bool skew_old = false;          // single sweeps by the older four-wave kernel (GFSHIP_SKEW_OLD)
-  bool patch = true;              // 2 x 2 lines per lane (relax_patch_loop.hip) on the levels where it wins; GFSHIP_SKEW_LINES=1: one line per thread everywhere
-  int patch_min_n = 128;          // ... i.e. n >= 128 (GFSHIP_PATCH_MIN_N): on 64^3 and 32^3 (16 and 4 tiles) one line per thread is a few us faster
   bool no_fused_godunov = false;  // face-value arrays + separate kernels even on periodic boxes
-  bool no_fused_godunov3 = false; // one launch per velocity component instead of the three at once (GFSHIP_NO_ADVECT3)
   bool no_fused_loop = false;     // one launch per sweep even where the fused loop applies
   bool force_hyperplane = false;  // debug/bench: per-hyperplane launches instead of relax_skew
   bool unit_weights = false;      // gfship_poisson_coefficients called with alpha = NULL
@@ -189,6 +179,15 @@ inline hipError_t stream_wait_spin (hipStream_t st)
   while ((e = hipStreamQuery (st)) == hipErrorNotReady)
     ;
   return e;
+}
+
+// launches that select bool template arguments at run time: calls f with one std::true_type or
+// std::false_type per bool; f is a generic lambda that launches kernel<decltype (B)::value, ...>
+template <class F> inline void with_bools (F && f) { f (); }
+template <class F, class... B> inline void with_bools (F && f, bool b0, B... rest)
+{
+  if (b0) with_bools ([&] (auto... r) { f (std::true_type {}, r...); }, rest...);
+  else    with_bools ([&] (auto... r) { f (std::false_type {}, r...); }, rest...);
 }
 
 #define GFSHIP_CHECK(cond, code, ...) do { if (!(cond)) { \
@@ -328,12 +327,12 @@ int  skew_check_error (gfship_domain * dom);
 // arm the granules of the next relax loop of `level' on the side stream, from this point of the main stream
 int  skew_arm_ahead (gfship_domain * dom, int level, unsigned nrelax);
 // relax_patch_loop.hip
-int  patch_resident_per_cu ();
+int  patch_resident_per_cu (const gfship_domain * dom);
 // the prolongation onto `level' can be done by the copy into the skewed layout of its relax loop
 bool prolongation_fused (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax);
 bool prolongation_fusable (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax);
 /* weighted sweeps (face weights from alpha) run on the six-wave kernel with its tile-skewed layout */
-inline bool patch_level (const gfship_domain * dom, int level) { return dom->patch && !dom->weighted && dom->lay[level].n >= dom->patch_min_n; }
+inline bool patch_level (const gfship_domain * dom, int level) { return dom->sw.patch () && !dom->weighted && dom->lay[level].n >= dom->sw.patch_min_n; }
 int  patch_pack (gfship_domain * dom, int level, SkewPlan * S, const double * u, const double * rhs,
 		 const double * dia, const double * coarse = nullptr);
 int  patch_unpack (gfship_domain * dom, int level, SkewPlan * S, double * u, double * add_into);

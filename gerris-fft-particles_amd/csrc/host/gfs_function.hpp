@@ -94,7 +94,7 @@ public:
     if (!fp) throw ParseError ("cannot write " + c);
     fputs (code.c_str (), fp);
     fclose (fp);
-    const char * cc = getenv ("GFSHIP_CC");
+    const char * cc = getenv ("GFSHIP_CC");   // not in the library's table (switches.hpp): the front end has no domain
     // -ffp-contract=off: no fused multiply-add, the arithmetic of the reference's x86-64 build
     std::string cmd = std::string (cc ? cc : "cc") +
       " -O1 -fPIC -shared -ffp-contract=off -o " + so + " " + c + " -lm";

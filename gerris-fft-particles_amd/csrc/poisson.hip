@@ -21,8 +21,7 @@ static bool weighted_pipelinable (gfship_domain * dom, unsigned dimension, int l
 
 static bool weighted_pipelined (gfship_domain * dom, unsigned dimension, int level)
 {
-  static const bool off = getenv ("GFSHIP_WEIGHTED_HYPERPLANES") != nullptr;
-  return !off && weighted_pipelinable (dom, dimension, level);
+  return dom->sw.weighted_pipelined && weighted_pipelinable (dom, dimension, level);
 }
 
 // gfs_relax on one level (src/poisson.c:604-632)
@@ -407,8 +406,8 @@ static int poisson_cycle (gfship_domain * dom, gfship_multilevel_params * p,
       /* where level l + 1 runs its relax loop on the 2 x 2 kernels the residual is copied into their
 	 layout by the same pass that restricts it (and so is the restricted one, where level l does) */
       const bool rp = !dom->skew[l + 1].rs_ready && prolongation_fused (dom, p->dimension, l + 1, nrl[l + 1]);
-      if (rp) dom->kc[dom->no_fused_restriction ? GFSHIP_KC_RESTRICTION_DECLINED : GFSHIP_KC_RESTRICTION_FUSED]++;
-      if (!dom->no_fused_restriction && rp)
+      if (rp) dom->kc[dom->sw.fused_restriction ? GFSHIP_KC_RESTRICTION_FUSED : GFSHIP_KC_RESTRICTION_DECLINED]++;
+      if (dom->sw.fused_restriction && rp)
 	TRY (launch_restrict_pack (dom, p->dimension, l + 1, S,
 				   l > (int) minlevel && prolongation_fused (dom, p->dimension, l, nrl[l])));
       else
@@ -570,7 +569,7 @@ int gfship_time_relax (gfship_domain * dom, unsigned d, int level, gfship_field 
     U->zero[level] = false;
     r = skew_time_sweeps (dom, level, U, R->lev[level], D->lev[level], D->zero[level], reps,
 			  ms_per_sweep);
-    if (r == GFSHIP_OK && getenv ("GFSHIP_SKEW_STATS"))
+    if (r == GFSHIP_OK && dom->sw.skew_stats)
       skew_dump_stats (dom, level);
     return r;
   }
@@ -583,7 +582,7 @@ int gfship_time_relax (gfship_domain * dom, unsigned d, int level, gfship_field 
   float ms = 0.f;
   GFSHIP_HIP (hipEventElapsedTime (&ms, dom->ev0, dom->ev1));
   *ms_per_sweep = (double) ms/reps;
-  if (getenv ("GFSHIP_SKEW_STATS"))
+  if (dom->sw.skew_stats)
     skew_dump_stats (dom, level);
   return GFSHIP_OK;
 }

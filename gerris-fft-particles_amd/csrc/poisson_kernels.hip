@@ -277,7 +277,7 @@ int launch_relax_exact (gfship_domain * dom, unsigned dimension, int level, doub
   const double w = op ? op->w : 1., h2 = op ? op->h2 : 1.;
   const Layout & L = dom->lay[level];
   int n = L.n;
-  static const bool rows2d = getenv ("GFSHIP_NO_ROWS2D") == nullptr;
+  const bool rows2d = dom->sw.rows2d;
   const bool rows2d_apply = dom->dim == 2 && dimension == 2 && n >= 8 && n <= 1024 && !dom->force_hyperplane;
   if (rows2d_apply) dom->kc[rows2d ? GFSHIP_KC_ROWS2D : GFSHIP_KC_HYPERPLANES_2D]++;
   if (rows2d_apply && rows2d)
@@ -767,15 +767,10 @@ int coarse_cycle_top (gfship_domain * dom, int minlevel)
   return top > minlevel ? top : -1;   /* a single level: the plain LDS loop does it */
 }
 
-static int coarse_threads ()
+static int coarse_threads (const gfship_domain * dom)
 {
-  static int n = 0;
-  if (!n) {
-    const char * e = getenv ("GFSHIP_COARSE_THREADS");
-    n = e ? atoi (e) : 1024;
-    if (n < 64 || n > 1024 || (n & 63)) n = 1024;
-  }
-  return n;
+  const int n = dom->sw.coarse_threads;
+  return n < 64 || n > 1024 || (n & 63) ? 1024 : n;
 }
 
 int launch_coarse_cycle (gfship_domain * dom, unsigned dimension, double omega, int lmin, int ltop,
@@ -817,9 +812,9 @@ int launch_coarse_cycle (gfship_domain * dom, unsigned dimension, double omega, 
 				       hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024));
       dom->coarse_attr_set = true;
     }
-    hipLaunchKernelGGL (coarse_cycle_kernel<3>, dim3 (1), dim3 (coarse_threads ()), bytes, dom->stream, A);
+    hipLaunchKernelGGL (coarse_cycle_kernel<3>, dim3 (1), dim3 (coarse_threads (dom)), bytes, dom->stream, A);
     dom->kc[GFSHIP_KC_COARSE_CYCLES]++;
-    dom->kc[GFSHIP_KC_COARSE_THREADS] = coarse_threads ();
+    dom->kc[GFSHIP_KC_COARSE_THREADS] = coarse_threads (dom);
   }
   else {
     if (!dom->coarse_attr_set) {
@@ -827,9 +822,9 @@ int launch_coarse_cycle (gfship_domain * dom, unsigned dimension, double omega, 
 				       hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024));
       dom->coarse_attr_set = true;
     }
-    hipLaunchKernelGGL (coarse_cycle_kernel<2>, dim3 (1), dim3 (coarse_threads ()), bytes, dom->stream, A);
+    hipLaunchKernelGGL (coarse_cycle_kernel<2>, dim3 (1), dim3 (coarse_threads (dom)), bytes, dom->stream, A);
     dom->kc[GFSHIP_KC_COARSE_CYCLES]++;
-    dom->kc[GFSHIP_KC_COARSE_THREADS] = coarse_threads ();
+    dom->kc[GFSHIP_KC_COARSE_THREADS] = coarse_threads (dom);
   }
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
@@ -1136,7 +1131,7 @@ static int lattice_attr (gfship_domain * dom)
 // highest level of the replicated coarse end (lmin .. ltop in LDS per box); -1 when it does not apply
 int lattice_cycle_top (gfship_domain * dom, int minlevel, Field * dia)
 {
-  if (!dom->has_external || dom->no_lattice_cycle || dom->overlap || dom->weighted)
+  if (!dom->has_external || !dom->sw.lattice_cycle || dom->overlap || dom->weighted)
     return -1;
   if (!(dom->comm || dom->gather) || dom->lat_rank < 0 || dom->lat_n < 1 || dom->lat_n > LAT_MAXBOXES)
     return -1;
@@ -1176,7 +1171,7 @@ int lattice_check_error (gfship_domain * dom)
   unsigned * w = lattice_err_word (dom);
   if (*w != 0) {
     *w = 0;
-    dom->no_lattice_cycle = true;
+    dom->sw.lattice_cycle = false;
     set_error ("lattice_cycle_kernel: a barrier wait timed out (workgroups not all resident: CUs held "
 	       "by another process or stream?); this solve failed, the domain falls back to one "
 	       "exchange per sweep and level");
@@ -1339,7 +1334,7 @@ int launch_residual (gfship_domain * dom, int level, const double * u, const dou
   const Layout & L = dom->lay[level];
   dim3 grid, block;
   cell_grid (L, &grid, &block);
-  static const bool pairs = getenv ("GFSHIP_RN_SCALAR") == nullptr;
+  const bool pairs = dom->sw.residual_pairs;
   if (dom->dim == 3 && L.n >= 64) dom->kc[pairs ? GFSHIP_KC_RESIDUAL_PAIRS : GFSHIP_KC_RESIDUAL_SCALAR]++;
   if (dom->dim == 3 && L.n >= 64 && pairs) {
     /* two cells per thread, 16-byte accesses (residual_norm2_kernel without the norm) */
@@ -1900,16 +1895,12 @@ int launch_residual_norm (gfship_domain * dom, int level, const double * u, cons
   int block = L.n >= 256 ? 256 : L.n >= 128 ? 128 : 64;
   /* d_scratch holds 5*8192 partials; GFSHIP_RN_BLOCKS: tuning knob (4096 = 16 workgroups per CU:
      the 7-point reads of a row keep more rows in flight than the norm alone needs) */
-  static int rn_blocks = 0;
-  if (!rn_blocks) {
-    const char * e = getenv ("GFSHIP_RN_BLOCKS");
-    rn_blocks = e ? atoi (e) : 4096;
-    if (rn_blocks < 64 || rn_blocks > 8192) rn_blocks = 4096;
-  }
+  int rn_blocks = dom->sw.rn_blocks;
+  if (rn_blocks < 64 || rn_blocks > 8192) rn_blocks = 4096;
   int nblocks = (int) (nrows > rn_blocks ? rn_blocks : nrows);
   double * partial = dom->d_scratch;
   double * result = out ? dom->h_pinned : dom->h_pinned + 8;
-  static const bool rn_pairs = getenv ("GFSHIP_RN_SCALAR") == nullptr;
+  const bool rn_pairs = dom->sw.residual_pairs;
   if (dom->dim == 3 && L.n >= 64) dom->kc[rn_pairs ? GFSHIP_KC_RESIDUAL_PAIRS : GFSHIP_KC_RESIDUAL_SCALAR]++;
   if (dom->dim == 3 && L.n >= 64 && rn_pairs) {
     const long nitems = (long) L.n*L.n*(L.n/2);

@@ -1369,15 +1369,10 @@ patch_unpack_kernel (PatchPackArgs A)
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static bool patch_regs ()
-{
-  return getenv ("GFSHIP_PATCH_REGS") != nullptr;
-}
-
-int patch_resident_per_cu ()
+int patch_resident_per_cu (const gfship_domain * dom)
 {
   int per_cu = 0;
-  hipError_t e = patch_regs () ?
+  hipError_t e = dom->sw.patch_regs ?
     hipOccupancyMaxActiveBlocksPerMultiprocessor (&per_cu, relax_patch_loop_kernel<true>, PK_NTHREADS, 0) :
     hipOccupancyMaxActiveBlocksPerMultiprocessor (&per_cu, relax_ring_loop_kernel<true, 0>, RK_NTHREADS, 0);
   int per_cu1 = 0;
@@ -1401,7 +1396,7 @@ int patch_pack (gfship_domain * dom, int level, SkewPlan * S, const double * u, 
   if (rhs) { A.src[A.narr] = rhs; A.dst[A.narr++] = S->rs; }     /* nullptr: already there (patch_restrict_pack) */
   if (dia) { A.src[A.narr] = dia; A.dst[A.narr++] = S->ds; }
   const int rows = A.L.n + PK_SKEW + 1;
-  const bool old_pack = coarse && getenv ("GFSHIP_OLD_PROLONG_PACK");
+  const bool old_pack = coarse && dom->sw.old_prolong_pack;
   if (coarse) dom->kc[old_pack ? GFSHIP_KC_PROLONG_PACK_OLD : GFSHIP_KC_PROLONG_PACK_NEW]++;
   if (coarse && !old_pack) {
     /* the prolongation straight into the layout (patch_prolong_kernel); arrays that still have to be
@@ -1464,7 +1459,7 @@ int patch_loop_launch (gfship_domain * dom, const SkewLoopArgs & A, int ntiles, 
   if (ms) GFSHIP_HIP (hipEventRecord (dom->ev0, dom->stream));
   if (A.op == 1)            /* diffusion_relax: the ring kernel (rhoc travels as the dia stream) */
     hipLaunchKernelGGL ((relax_ring_loop_kernel<true, 1>), dim3 (ntiles), dim3 (RK_NTHREADS), 0, dom->stream, A);
-  else if (patch_regs ()) {      /* the variant that streams through registers (GFSHIP_PATCH_REGS=1) */
+  else if (dom->sw.patch_regs) {      /* the variant that streams through registers (GFSHIP_PATCH_REGS=1) */
     if (has_dia)
       hipLaunchKernelGGL (relax_patch_loop_kernel<true>, dim3 (ntiles), dim3 (PK_NTHREADS), 0, dom->stream, A);
     else

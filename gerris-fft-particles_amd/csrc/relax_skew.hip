@@ -363,7 +363,7 @@ static int skew_plan (gfship_domain * dom, int level, SkewPlan ** out)
     GFSHIP_HIP (hipMalloc ((void **) &S.ds, doubles*sizeof (double)));
     GFSHIP_HIP (hipMalloc ((void **) &S.hb, 2*S.hb_words*sizeof (u64)));
     GFSHIP_HIP (hipMalloc ((void **) &S.ctl, 64));
-    if (getenv ("GFSHIP_SKEW_STATS"))
+    if (dom->sw.skew_stats)
       GFSHIP_HIP (hipMalloc ((void **) &S.stats, (size_t) ntiles*4*sizeof (u64)));
     // ticket -> tile, anti-diagonal major: a tile only depends on tiles of earlier diagonals
     std::vector<unsigned short> order;
@@ -501,7 +501,7 @@ static int skew_sweep (gfship_domain * dom, int level, SkewPlan * S, double * u_
 {
   /* the six-wave kernel of relax_skew_loop.hip also runs a single sweep (any sides); the
      four-wave kernel below is kept as an independent implementation (GFSHIP_SKEW_OLD=1) */
-  if (!dom->skew_old || (op && op->kind))
+  if (!dom->sw.skew_old || (op && op->kind))
     return skew_loop_run (dom, level, S, u_nat, has_dia, 1, nullptr, nullptr, op);
   // ticket = 0 (err is sticky), hand-off granules = sentinel
   GFSHIP_HIP (hipMemsetAsync (S->ctl, 0, sizeof (unsigned), dom->stream));
@@ -543,7 +543,7 @@ static int skew_loop_trial (gfship_domain * dom, int level, SkewPlan * S, unsign
 
 bool prolongation_fused (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax)
 {
-  return !dom->no_fused_prolongation && prolongation_fusable (dom, dimension, level, nrelax);
+  return dom->sw.fused_prolongation && prolongation_fusable (dom, dimension, level, nrelax);
 }
 
 // ... where nothing but GFSHIP_NO_FUSED_PROLONGATION stands against it
@@ -642,7 +642,7 @@ int skew_time_sweeps (gfship_domain * dom, int level, Field * u, const double * 
   float total = 0.f;
   for (int q = 0; q < reps; q++) {
     float ms = 0.f;
-    if (!dom->skew_old) {
+    if (!dom->sw.skew_old) {
       if ((r = skew_loop_run (dom, level, S, u->lev[level], !dia_zero, 1, &ms))) return r;
     }
     else {
@@ -721,7 +721,7 @@ int skew_time_loop (gfship_domain * dom, int level, Field * u, const double * rh
       else
 	for (unsigned w = 0; w < nrelax; w++) {
 	  float m1 = 0.f;
-	  if (!dom->skew_old) {
+	  if (!dom->sw.skew_old) {
 	    if ((r = skew_loop_run (dom, level, S, un, !dia_zero, 1, &m1))) return r;
 	  }
 	  else {

@@ -839,7 +839,7 @@ static int skew_loop_resident (gfship_domain * dom, int level)
     else {
       if (per_cu_2 < per_cu) per_cu = per_cu_2;
       dom->skew_resident = (per_cu < per_cu_w ? per_cu : per_cu_w)*prop.multiProcessorCount;
-      dom->patch_resident = patch_resident_per_cu ()*prop.multiProcessorCount;
+      dom->patch_resident = patch_resident_per_cu (dom)*prop.multiProcessorCount;
     }
   }
   return patch_level (dom, level) ? dom->patch_resident : dom->skew_resident;
@@ -890,13 +890,13 @@ int skew_arm_ahead (gfship_domain * dom, int level, unsigned nrelax)
     return GFSHIP_OK;           /* nothing allocated yet (first loop of the level): armed in line */
   if (dom->no_fused_loop || !skew_loop_supported (dom, level, nrelax, true))
     return GFSHIP_OK;
-  if (patch_level (dom, level) && !dom->no_kernel_arming)
+  if (patch_level (dom, level) && dom->sw.kernel_arming)
     return GFSHIP_OK;           /* the loop kernels arm the other set themselves (opt-in) */
   const SetGeometry G = skew_set_geometry (dom, level, S, nrelax);
   const int set = S->cur_set;
   if (S->armed[set] >= G.need)
     return GFSHIP_OK;
-  if (dom->no_arm_ahead) {      /* GFSHIP_NO_ARM_AHEAD=1: left to the loop */
+  if (!dom->sw.arm_ahead) {      /* GFSHIP_NO_ARM_AHEAD=1: left to the loop */
     dom->kc[GFSHIP_KC_ARM_AHEAD_DECLINED]++;
     return GFSHIP_OK;
   }
@@ -951,7 +951,7 @@ int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat,
     GFSHIP_HIP (hipMemsetAsync (base, 0xFF, need*sizeof (u64), dom->stream));
     dom->kc[GFSHIP_KC_ARM_INLINE]++;
   }
-  const bool arms = patch_level (dom, level) && !dom->no_kernel_arming;
+  const bool arms = patch_level (dom, level) && dom->sw.kernel_arming;
   if (patch_level (dom, level))
     dom->kc[arms ? GFSHIP_KC_PATCH_LOOP_KERNEL_ARMS : GFSHIP_KC_PATCH_LOOP_HOST_ARMS]++;
   if (arms && !S->arm_cum) {
@@ -998,6 +998,7 @@ int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat,
   A.w = op ? op->w : 1.;
   A.h2 = op ? op->h2 : 1.;
   for (int d = 0; d < 6; d++) A.ws[d] = S->ws[d];
+  /* not in the table (switches.hpp): fault injection that a test toggles on a live domain, read at every launch */
   { const char * e = getenv ("GFSHIP_FAULT_DROP_HANDOFF"); A.fault_tile = e ? atoi (e) : -1; }
   if (patch_level (dom, level)) {
     /* the 2 x 2 kernels, GFSHIP_XCD_SCOPE=1: XCD blocks + narrower-scope stores towards consumers on
@@ -1005,16 +1006,16 @@ int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat,
        ms per loop against 0.505 without; + workgroup-scope stores (GFSHIP_XCD_NEAR_MODE=2) 0.485-0.52;
        + plain stores (=1) 1.04 (they linger in the L1's write path): the hand-off latency is not
        the store's way to memory.  Off by default. */
-    if (!dom->no_xcd_scope && S->xorder && ntiles >= 8 && ntiles % 8 == 0 &&
+    if (dom->sw.xcd_scope && S->xorder && ntiles >= 8 && ntiles % 8 == 0 &&
 	skew_loop_resident (dom, level) >= ntiles) {
       A.per_xcd = ntiles/8;
       A.xticket = (unsigned *) (base + 1);
-      { const char * e = getenv ("GFSHIP_XCD_NEAR_MODE"); A.near_mode = e ? atoi (e) : 2; }
+      A.near_mode = dom->sw.xcd_near_mode;
       dom->kc[GFSHIP_KC_XCD_NEAR_MODE] = 1 + (unsigned long long) (A.near_mode < 0 ? 0 : A.near_mode);
     }
     dom->kc[A.per_xcd ? GFSHIP_KC_XCD_SCOPE_ON : GFSHIP_KC_XCD_SCOPE_OFF]++;
   }
-  else if (dom->xcd_place && S->xorder && ntiles >= 8 && skew_loop_resident (dom, level) >= ntiles) {
+  else if (dom->sw.xcd_place && S->xorder && ntiles >= 8 && skew_loop_resident (dom, level) >= ntiles) {
     A.per_xcd = ntiles/8;
     GFSHIP_HIP (hipMemsetAsync ((unsigned *) S->ctl + 6, 0, 8*sizeof (unsigned), dom->stream));
     dom->kc[GFSHIP_KC_XCD_PLACE_ON]++;
@@ -1025,7 +1026,7 @@ int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat,
   A.err = (unsigned *) (dom->h_pinned + 32) + level;     /* skew_err_word, relax_skew.hip */
   A.dummy = (const u64 *) S->ctl + 2;
   A.stats = nullptr;
-  if (getenv ("GFSHIP_SKEW_STATS")) {
+  if (dom->sw.skew_stats) {
     if (!S->stats_loop)
       GFSHIP_HIP (hipMalloc ((void **) &S->stats_loop, (size_t) ntiles*SK_MAXF*2*sizeof (u64)));
     A.stats = (u64 *) S->stats_loop;
@@ -1050,7 +1051,7 @@ int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat,
     hipLaunchKernelGGL ((relax_skew_loop_kernel<true, 2>), dim3 (ntiles), dim3 (SK_NTHREADS + 64), SK_WBYTES,
 			dom->stream, A);
   }
-  else if (dom->wave_loop && nrelax >= 2 && !has_dia)     /* one compute wave per tile */
+  else if (dom->sw.wave_loop && nrelax >= 2 && !has_dia)     /* one compute wave per tile */
     hipLaunchKernelGGL (relax_wave_loop_kernel, dim3 (ntiles), dim3 (WV_NTHREADS), 0, dom->stream, A);
   else if (has_dia)
     hipLaunchKernelGGL ((relax_skew_loop_kernel<true, 0>), dim3 (ntiles), dim3 (SK_NTHREADS), 0, dom->stream, A);

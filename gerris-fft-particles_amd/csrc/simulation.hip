@@ -124,7 +124,7 @@ int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, g
      interpolated from the centred ones, gfs_approximate_projection src/timestep.c:572-580) */
   for (int c = 0; c < dom->dim; c++)
     if (s->visc[c] != 0. || dom->src[c] != 0.) lazy = false;   /* the CFL needs the full kernel then */
-  if (!approximate || !s->tracers.empty () || s->un_handle_given || p != s->p || getenv ("GFSHIP_NO_LAZY_UN"))
+  if (!approximate || !s->tracers.empty () || s->un_handle_given || p != s->p || !dom->sw.lazy_un)
     lazy = false;
   if (!approximate)
     TRY (materialize_un (s));          /* un is an input of the MAC projection */
@@ -496,7 +496,7 @@ static int predicted_face_velocities (gfship_sim * s, double mac_dt)
     ptrs3 (s, s->u, u);
     ptrs3 (s, s->un, un);
     const bool div_applies = mac_dt != 0. && s->dom->dim == 3;
-    const bool want_div = div_applies && !getenv ("GFSHIP_NO_FUSED_DIVERGENCE");
+    const bool want_div = div_applies && s->dom->sw.fused_divergence;
     if (div_applies && !want_div) s->dom->kc[GFSHIP_KC_DIVERGENCE_DECLINED]++;
     bool done = false;
     TRY (launch_predict_un_fused (s->dom, u, s->advection_params.dt,
@@ -557,7 +557,7 @@ static int centered_velocity_advection (gfship_sim * s, const gfship_field gmac[
   if (corrected) *corrected = false;
   if (u_coarse) *u_coarse = false;
   if (s->dom->dim == 3 && (godunov_fused_supported (s->dom) || godunov_fused_mpi_supported (s->dom)) &&
-      !s->dom->no_fused_godunov3 && s->advection_params.gradient <= 1 &&
+      s->dom->sw.advect3 && s->advection_params.gradient <= 1 &&
       s->visc[0] == 0. && s->visc[1] == 0. && s->visc[2] == 0.) {
     /* the three components in one pass over the box (same MAC velocities, nothing of one component
        feeds another): into scratch leaf levels, then the storage is swapped */
@@ -575,7 +575,7 @@ static int centered_velocity_advection (gfship_sim * s, const gfship_field gmac[
     ptrs3 (s, gmac, gm);
     if (g) ptrs3 (s, g, gc);
     const bool corr_applies = corr_dt != 0. && g && corrected;
-    const bool fuse = corr_applies && !getenv ("GFSHIP_NO_FUSED_CORRECTION");
+    const bool fuse = corr_applies && dom->sw.fused_correction;
     if (corr_applies) dom->kc[fuse ? GFSHIP_KC_CORRECTION_FUSED : GFSHIP_KC_CORRECTION_DECLINED]++;
     double * uc[3] = { nullptr, nullptr, nullptr };
     if (fuse && u_coarse && L >= 1)

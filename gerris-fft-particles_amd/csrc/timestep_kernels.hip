@@ -3087,7 +3087,7 @@ int launch_project_correct (gfship_domain * dom, const double * p, double * cons
     pm = dom->cfl_partial;
   }
   Ptr3 none = { { nullptr, nullptr, nullptr } };
-  static const bool pairs = getenv ("GFSHIP_PC_SCALAR") == nullptr;
+  const bool pairs = dom->sw.project_pairs;
   const bool pairs_apply = dom->dim == 3 && !u && !pm && L.n >= 64 && L.n % 2 == 0;
   if (pairs_apply) dom->kc[pairs ? GFSHIP_KC_PROJECT_PAIRS : GFSHIP_KC_PROJECT_SCALAR]++;
   if (pairs_apply && pairs) {
@@ -3098,14 +3098,10 @@ int launch_project_correct (gfship_domain * dom, const double * p, double * cons
     GFSHIP_HIP (hipGetLastError ());
     return GFSHIP_OK;
   }
-  if (dom->dim == 3) {
-    if (u) hipLaunchKernelGGL ((project_correct_kernel<3, true>), grid, block, 0, dom->stream, L, p, m3 (un), m3 (g), m3 (u), dt, pm);
-    else   hipLaunchKernelGGL ((project_correct_kernel<3, false>), grid, block, 0, dom->stream, L, p, m3 (un), m3 (g), none, dt, pm);
-  }
-  else {
-    if (u) hipLaunchKernelGGL ((project_correct_kernel<2, true>), grid, block, 0, dom->stream, L, p, m3 (un), m3 (g), m3 (u), dt, pm);
-    else   hipLaunchKernelGGL ((project_correct_kernel<2, false>), grid, block, 0, dom->stream, L, p, m3 (un), m3 (g), none, dt, pm);
-  }
+  with_bools ([&] (auto D3, auto U) {
+    hipLaunchKernelGGL ((project_correct_kernel<decltype (D3)::value ? 3 : 2, decltype (U)::value>), grid, block, 0, dom->stream,
+			L, p, m3 (un), m3 (g), u ? m3 (u) : none, dt, pm);
+  }, dom->dim == 3, u != nullptr);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
@@ -3153,22 +3149,19 @@ int launch_face_interp_div (gfship_domain * dom, double * const u[3], double * c
   const Layout & L = dom->lay[dom->depth];
   dim3 grid, block;
   ext1_grid (L, &grid, &block);
-  if (un) {
-    if (dom->dim == 3) hipLaunchKernelGGL ((face_interp_div_kernel<3, true>), grid, block, 0, dom->stream, L, c3 (u), m3 (un), div, dt);
-    else hipLaunchKernelGGL ((face_interp_div_kernel<2, true>), grid, block, 0, dom->stream, L, c3 (u), m3 (un), div, dt);
+  Ptr3 none = { { nullptr, nullptr, nullptr } };
+  const bool pairs = dom->sw.project_pairs;
+  const bool pairs_apply = !un && dom->dim == 3 && L.n >= 64 && L.n % 2 == 0;
+  if (pairs_apply) dom->kc[pairs ? GFSHIP_KC_PROJECT_PAIRS : GFSHIP_KC_PROJECT_SCALAR]++;
+  if (pairs_apply && pairs) {
+    const int b = 128, half = L.n/2;
+    hipLaunchKernelGGL (face_interp_div2_kernel, dim3 ((half + b - 1)/b, L.n, L.n), dim3 (b), 0, dom->stream, L, c3 (u), div, dt);
   }
-  else {
-    Ptr3 none = { { nullptr, nullptr, nullptr } };
-    static const bool pairs = getenv ("GFSHIP_PC_SCALAR") == nullptr;
-    const bool pairs_apply = dom->dim == 3 && L.n >= 64 && L.n % 2 == 0;
-    if (pairs_apply) dom->kc[pairs ? GFSHIP_KC_PROJECT_PAIRS : GFSHIP_KC_PROJECT_SCALAR]++;
-    if (pairs_apply && pairs) {
-      const int b = 128, half = L.n/2;
-      hipLaunchKernelGGL (face_interp_div2_kernel, dim3 ((half + b - 1)/b, L.n, L.n), dim3 (b), 0, dom->stream, L, c3 (u), div, dt);
-    }
-    else if (dom->dim == 3) hipLaunchKernelGGL ((face_interp_div_kernel<3, false>), grid, block, 0, dom->stream, L, c3 (u), none, div, dt);
-    else hipLaunchKernelGGL ((face_interp_div_kernel<2, false>), grid, block, 0, dom->stream, L, c3 (u), none, div, dt);
-  }
+  else
+    with_bools ([&] (auto D3, auto UN) {
+      hipLaunchKernelGGL ((face_interp_div_kernel<decltype (D3)::value ? 3 : 2, decltype (UN)::value>), grid, block, 0, dom->stream,
+			  L, c3 (u), un ? m3 (un) : none, div, dt);
+    }, dom->dim == 3, un != nullptr);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
@@ -3192,7 +3185,7 @@ int launch_project_correct_lazy (gfship_domain * dom, const double * p, double *
   if (dom->cfl_dirty)
     GFSHIP_HIP (hipMemsetAsync (dom->cfl_partial, 0, nb*sizeof (double), dom->stream));
   dom->cfl_dirty = true;
-  static const bool pairs = getenv ("GFSHIP_PC_SCALAR") == nullptr;
+  const bool pairs = dom->sw.project_pairs;
   const bool pairs_apply = dom->dim == 3 && L.n >= 64 && L.n % 2 == 0;
   if (pairs_apply) dom->kc[pairs ? GFSHIP_KC_PROJECT_PAIRS : GFSHIP_KC_PROJECT_SCALAR]++;
   if (pairs_apply && pairs) {
@@ -3223,7 +3216,7 @@ bool godunov_fused_supported (const gfship_domain * dom)
 // the tiled kernels with the states beyond the MPI sides exchanged in one message per side
 bool godunov_fused_mpi_supported (const gfship_domain * dom)
 {
-  if (dom->dim != 3 || dom->no_fused_godunov || dom->no_fused_mpi || !dom->comm) return false;
+  if (dom->dim != 3 || dom->no_fused_godunov || !dom->sw.fused_mpi || !dom->comm) return false;
   const int n = dom->lay[dom->depth].n;
   if (n % GX) return false;
   bool ext = false;
@@ -3258,27 +3251,6 @@ int launch_predict_un_fused (gfship_domain * dom, double * const u[3], double dt
   const bool anyv = visc[0] != 0. || visc[1] != 0. || visc[2] != 0. ||
     dom->src[0] != 0. || dom->src[1] != 0. || dom->src[2] != 0.;
   if (div_done) *div_done = false;
-  static const bool sweep_ok = getenv ("GFSHIP_NO_ADVECT_SWEEP") == nullptr;
-  if (!dom->has_external && sweep_ok && L.n % SWX == 0 && L.n % SWY == 0 && L.n % SWZ == 0) {
-    /* periodic box: the sweep along z, with the divergence of the MAC projection that follows */
-    const dim3 sgrid (L.n/SWX, L.n/SWY, L.n/SWZ);
-    const bool dv = div != nullptr && div_dt != 0.;
-    GhostFv G0;
-    for (int d = 0; d < 6; d++) { G0.r[d] = nullptr; G0.s[d] = nullptr; }
-#define PS(VL_, VS_) do { \
-      if (dv) hipLaunchKernelGGL ((predict_un_sweep_kernel<VL_, VS_, true, false>), sgrid, dim3 (SWN + SW_RING), 0, \
-				  dom->stream, L, c3 (u), m3 (un), dt, vs, div, div_dt, G0); \
-      else hipLaunchKernelGGL ((predict_un_sweep_kernel<VL_, VS_, false, false>), sgrid, dim3 (SWN + SW_RING), 0, \
-			       dom->stream, L, c3 (u), m3 (un), dt, vs, div, div_dt, G0); } while (0)
-    if (gradient) { if (anyv) PS (true, true); else PS (true, false); }
-    else          { if (anyv) PS (false, true); else PS (false, false); }
-#undef PS
-    GFSHIP_HIP (hipGetLastError ());
-    dom->kc[GFSHIP_KC_PREDICT_SWEEP]++;
-    if (div_done) *div_done = dv;
-    return GFSHIP_OK;
-  }
-  const dim3 grid (L.n/GX, L.n/GY, L.n/GZ);
   GhostFv G;
   for (int d = 0; d < 6; d++) { G.r[d] = nullptr; G.s[d] = nullptr; }
   const bool mpi = dom->has_external;
@@ -3287,36 +3259,34 @@ int launch_predict_un_fused (gfship_domain * dom, double * const u[3], double dt
     if (r) return r;
     const dim3 bgrid ((L.n*L.n + 255)/256, 6);
     CPtr3 none = { { nullptr, nullptr, nullptr } };
-#define BK(VL_, VS_) hipLaunchKernelGGL ((boundary_face_values_kernel<true, VL_, VS_>), bgrid, dim3 (256), 0, 					 dom->stream, L, c3 (u), none, dt, vs, G)
-    if (gradient) { if (anyv) BK (true, true); else BK (true, false); }
-    else          { if (anyv) BK (false, true); else BK (false, false); }
-#undef BK
+    with_bools ([&] (auto VL, auto VS) {
+      hipLaunchKernelGGL ((boundary_face_values_kernel<true, decltype (VL)::value, decltype (VS)::value>), bgrid, dim3 (256), 0,
+			  dom->stream, L, c3 (u), none, dt, vs, G);
+    }, gradient != 0, anyv);
     GFSHIP_HIP (hipGetLastError ());
     if ((r = comm_exchange_raw (dom, dom->gfv_send, dom->gfv_recv, (size_t) L.n*L.n))) return r;
     dom->n_fused_mpi++;
-    static const bool mpi_sweep_ok = getenv ("GFSHIP_NO_MPI_SWEEP") == nullptr;
-    if (sweep_ok && mpi_sweep_ok && L.n % SWX == 0 && L.n % SWY == 0 && L.n % SWZ == 0) {
-      /* the sweep along z with the states beyond the MPI sides from the received buffers, and the divergence */
-      const dim3 sgrid (L.n/SWX, L.n/SWY, L.n/SWZ);
-      const bool dv = div != nullptr && div_dt != 0.;
-#define PSM(VL_, VS_) do { \
-	if (dv) hipLaunchKernelGGL ((predict_un_sweep_kernel<VL_, VS_, true, true>), sgrid, dim3 (SWN + SW_RING), 0, \
-				    dom->stream, L, c3 (u), m3 (un), dt, vs, div, div_dt, G); \
-	else hipLaunchKernelGGL ((predict_un_sweep_kernel<VL_, VS_, false, true>), sgrid, dim3 (SWN + SW_RING), 0, \
-				 dom->stream, L, c3 (u), m3 (un), dt, vs, div, div_dt, G); } while (0)
-      if (gradient) { if (anyv) PSM (true, true); else PSM (true, false); }
-      else          { if (anyv) PSM (false, true); else PSM (false, false); }
-#undef PSM
-      GFSHIP_HIP (hipGetLastError ());
-      dom->kc[GFSHIP_KC_PREDICT_SWEEP_MPI]++;
-      if (div_done) *div_done = dv;
-      return GFSHIP_OK;
-    }
   }
-#define PK(VL_, VS_) do { if (mpi) hipLaunchKernelGGL ((predict_un_tiled_kernel<VL_, VS_, true>), grid, dim3 (GN), 0, 							dom->stream, L, c3 (u), m3 (un), dt, vs, G);     else hipLaunchKernelGGL ((predict_un_tiled_kernel<VL_, VS_, false>), grid, dim3 (GN), 0, 			     dom->stream, L, c3 (u), m3 (un), dt, vs, G); } while (0)
-  if (gradient) { if (anyv) PK (true, true); else PK (true, false); }
-  else          { if (anyv) PK (false, true); else PK (false, false); }
-#undef PK
+  const bool sweep_fits = dom->sw.advect_sweep && L.n % SWX == 0 && L.n % SWY == 0 && L.n % SWZ == 0;
+  if (sweep_fits && (!mpi || dom->sw.mpi_sweep)) {
+    /* the sweep along z, with the divergence of the MAC projection that follows; on a box with MPI sides
+       the states beyond those sides come from the received buffers */
+    const dim3 sgrid (L.n/SWX, L.n/SWY, L.n/SWZ);
+    const bool dv = div != nullptr && div_dt != 0.;
+    with_bools ([&] (auto VL, auto VS, auto DV, auto MPI) {
+      hipLaunchKernelGGL ((predict_un_sweep_kernel<decltype (VL)::value, decltype (VS)::value, decltype (DV)::value, decltype (MPI)::value>),
+			  sgrid, dim3 (SWN + SW_RING), 0, dom->stream, L, c3 (u), m3 (un), dt, vs, div, div_dt, G);
+    }, gradient != 0, anyv, dv, mpi);
+    GFSHIP_HIP (hipGetLastError ());
+    dom->kc[mpi ? GFSHIP_KC_PREDICT_SWEEP_MPI : GFSHIP_KC_PREDICT_SWEEP]++;
+    if (div_done) *div_done = dv;
+    return GFSHIP_OK;
+  }
+  const dim3 grid (L.n/GX, L.n/GY, L.n/GZ);
+  with_bools ([&] (auto VL, auto VS, auto MPI) {
+    hipLaunchKernelGGL ((predict_un_tiled_kernel<decltype (VL)::value, decltype (VS)::value, decltype (MPI)::value>), grid, dim3 (GN), 0,
+			dom->stream, L, c3 (u), m3 (un), dt, vs, G);
+  }, gradient != 0, anyv, mpi);
   GFSHIP_HIP (hipGetLastError ());
   dom->kc[mpi ? GFSHIP_KC_PREDICT_TILED_MPI : GFSHIP_KC_PREDICT_TILED]++;
   return GFSHIP_OK;
@@ -3328,18 +3298,10 @@ int launch_advect_fused (gfship_domain * dom, bool velocity, const double * v, d
 {
   const Layout & L = dom->lay[dom->depth];
   dim3 grid (L.n/GX, L.n/GY, L.n/GZ);
-#define AK(VE_, VL_, VS_) hipLaunchKernelGGL ((advect_tiled_kernel<VE_, VL_, VS_>), grid, dim3 (GN), 0, \
-					      dom->stream, L, v, out, c3 (un), gm, gc, dt, visc, gsrc)
-  const bool vs = visc != 0. || gsrc != 0.;
-  if (velocity) {
-    if (gradient) { if (vs) AK (true, true, true); else AK (true, true, false); }
-    else          { if (vs) AK (true, false, true); else AK (true, false, false); }
-  }
-  else {
-    if (gradient) { if (vs) AK (false, true, true); else AK (false, true, false); }
-    else          { if (vs) AK (false, false, true); else AK (false, false, false); }
-  }
-#undef AK
+  with_bools ([&] (auto VE, auto VL, auto VS) {
+    hipLaunchKernelGGL ((advect_tiled_kernel<decltype (VE)::value, decltype (VL)::value, decltype (VS)::value>), grid, dim3 (GN), 0,
+			dom->stream, L, v, out, c3 (un), gm, gc, dt, visc, gsrc);
+  }, velocity, gradient != 0, visc != 0. || gsrc != 0.);
   GFSHIP_HIP (hipGetLastError ());
   dom->kc[velocity ? GFSHIP_KC_ADVECT1_TILED_VELOCITY : GFSHIP_KC_ADVECT1_TILED_TRACER]++;
   return GFSHIP_OK;
@@ -3363,75 +3325,43 @@ int launch_advect3_fused (gfship_domain * dom, double * const v[3], double * con
   K.Lc = dom->lay[dom->depth > 0 ? dom->depth - 1 : 0];
   const bool corr = corr_dt != 0.;
   GFSHIP_CHECK (!corr || gc, GFSHIP_EINVAL, "the fused correction needs the centred gradient");
+  const bool srcs = dom->src[0] != 0. || dom->src[1] != 0. || dom->src[2] != 0.;
   const bool mpi = dom->has_external;
   if (mpi) {
     int r = ghost_fv (dom, &G);
     if (r) return r;
     const dim3 bgrid ((L.n*L.n + 255)/256, 6);
-    const bool bsrc = dom->src[0] != 0. || dom->src[1] != 0. || dom->src[2] != 0.;
-#define BK3(VL_, VS_) hipLaunchKernelGGL ((boundary_face_values_kernel<false, VL_, VS_>), bgrid, dim3 (256), 0, \
-					  dom->stream, L, c3 (v), c3 (un), dt, vs, G)
-    if (gradient) { if (bsrc) BK3 (true, true); else BK3 (true, false); }
-    else          { if (bsrc) BK3 (false, true); else BK3 (false, false); }
-#undef BK3
+    with_bools ([&] (auto VL, auto VS) {
+      hipLaunchKernelGGL ((boundary_face_values_kernel<false, decltype (VL)::value, decltype (VS)::value>), bgrid, dim3 (256), 0,
+			  dom->stream, L, c3 (v), c3 (un), dt, vs, G);
+    }, gradient != 0, srcs);
     GFSHIP_HIP (hipGetLastError ());
     if ((r = comm_exchange_raw (dom, dom->gfv_send, dom->gfv_recv, (size_t) 3*L.n*L.n))) return r;
     dom->n_fused_mpi++;
   }
-  const bool srcs0 = dom->src[0] != 0. || dom->src[1] != 0. || dom->src[2] != 0.;
-  static const bool sweep_ok = getenv ("GFSHIP_NO_ADVECT_SWEEP") == nullptr;
-  static const bool mpi_sweep_ok = getenv ("GFSHIP_NO_MPI_SWEEP") == nullptr;
-  if (mpi && sweep_ok && mpi_sweep_ok && L.n % SWX == 0 && L.n % SWY == 0 && L.n % SWZ == 0) {
-    /* a box with MPI sides: the same sweep with the states beyond those sides from the received buffers */
+  const bool sweep_fits = dom->sw.advect_sweep && L.n % SWX == 0 && L.n % SWY == 0 && L.n % SWZ == 0;
+  if (sweep_fits && (!mpi || dom->sw.mpi_sweep)) {
+    /* the sweep along z; on a box with MPI sides the states beyond those sides come from the received buffers */
     const dim3 sgrid (L.n/SWX, L.n/SWY, L.n/SWZ);
-#define SK3M(VL_, SRC_) do { \
-      if (corr) hipLaunchKernelGGL ((advect3_sweep2_kernel<VL_, SRC_, true, true>), sgrid, dim3 (SWN + SW_RING), 0, dom->stream, \
-				    L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K, G); \
-      else hipLaunchKernelGGL ((advect3_sweep2_kernel<VL_, SRC_, false, true>), sgrid, dim3 (SWN + SW_RING), 0, dom->stream, \
-			       L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K, G); } while (0)
-    if (gradient) { if (srcs0) SK3M (true, true); else SK3M (true, false); }
-    else          { if (srcs0) SK3M (false, true); else SK3M (false, false); }
-#undef SK3M
+    const bool sweep1 = !mpi && dom->sw.advect_sweep1;     /* advect3_sweep_kernel has no MPI flavour */
+    if (sweep1)
+      with_bools ([&] (auto VL, auto SRC, auto CORR) {
+	hipLaunchKernelGGL ((advect3_sweep_kernel<decltype (VL)::value, decltype (SRC)::value, decltype (CORR)::value>),
+			    sgrid, dim3 (SWN + SW_RING), 0, dom->stream, L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K);
+      }, gradient != 0, srcs, corr);
+    else
+      with_bools ([&] (auto VL, auto SRC, auto CORR, auto MPI) {
+	hipLaunchKernelGGL ((advect3_sweep2_kernel<decltype (VL)::value, decltype (SRC)::value, decltype (CORR)::value, decltype (MPI)::value>),
+			    sgrid, dim3 (SWN + SW_RING), 0, dom->stream, L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K, G);
+      }, gradient != 0, srcs, corr, mpi);
     GFSHIP_HIP (hipGetLastError ());
-    dom->kc[GFSHIP_KC_ADVECT3_SWEEP2_MPI]++;
+    dom->kc[mpi ? GFSHIP_KC_ADVECT3_SWEEP2_MPI : sweep1 ? GFSHIP_KC_ADVECT3_SWEEP1 : GFSHIP_KC_ADVECT3_SWEEP2]++;
     return GFSHIP_OK;
   }
-  if (!mpi && sweep_ok && L.n % SWX == 0 && L.n % SWY == 0 && L.n % SWZ == 0) {
-    /* periodic box: the sweep along z (advect3_sweep_kernel) */
-    const dim3 sgrid (L.n/SWX, L.n/SWY, L.n/SWZ);
-    static const bool sweep1 = getenv ("GFSHIP_ADVECT_SWEEP1") != nullptr;
-#define SK3(VL_, SRC_) do { \
-      if (sweep1) { \
-	if (corr) hipLaunchKernelGGL ((advect3_sweep_kernel<VL_, SRC_, true>), sgrid, dim3 (SWN + SW_RING), 0, dom->stream, \
-				      L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K); \
-	else hipLaunchKernelGGL ((advect3_sweep_kernel<VL_, SRC_, false>), sgrid, dim3 (SWN + SW_RING), 0, dom->stream, \
-				 L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K); } \
-      else if (corr) hipLaunchKernelGGL ((advect3_sweep2_kernel<VL_, SRC_, true, false>), sgrid, dim3 (SWN + SW_RING), 0, dom->stream, \
-					 L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K, G); \
-      else hipLaunchKernelGGL ((advect3_sweep2_kernel<VL_, SRC_, false, false>), sgrid, dim3 (SWN + SW_RING), 0, dom->stream, \
-			       L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K, G); } while (0)
-    if (gradient) { if (srcs0) SK3 (true, true); else SK3 (true, false); }
-    else          { if (srcs0) SK3 (false, true); else SK3 (false, false); }
-#undef SK3
-    GFSHIP_HIP (hipGetLastError ());
-    dom->kc[sweep1 ? GFSHIP_KC_ADVECT3_SWEEP1 : GFSHIP_KC_ADVECT3_SWEEP2]++;
-    return GFSHIP_OK;
-  }
-#define AK(VL_, MPI_, SRC_) do { \
-    if (corr) hipLaunchKernelGGL ((advect3_tiled_kernel<VL_, MPI_, SRC_, ADV3_WPE, true>), grid, dim3 (GN), 0, \
-				  dom->stream, L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, G, vs, K); \
-    else hipLaunchKernelGGL ((advect3_tiled_kernel<VL_, MPI_, SRC_, ADV3_WPE, false>), grid, dim3 (GN), 0, \
-			     dom->stream, L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, G, vs, K); } while (0)
-  const bool srcs = dom->src[0] != 0. || dom->src[1] != 0. || dom->src[2] != 0.;
-  if (srcs) {
-    if (mpi) { if (gradient) AK (true, true, true); else AK (false, true, true); }
-    else if (gradient) AK (true, false, true);
-    else AK (false, false, true);
-  }
-  else if (mpi) { if (gradient) AK (true, true, false); else AK (false, true, false); }
-  else if (gradient) AK (true, false, false);
-  else AK (false, false, false);
-#undef AK
+  with_bools ([&] (auto VL, auto MPI, auto SRC, auto CORR) {
+    hipLaunchKernelGGL ((advect3_tiled_kernel<decltype (VL)::value, decltype (MPI)::value, decltype (SRC)::value, ADV3_WPE, decltype (CORR)::value>),
+			grid, dim3 (GN), 0, dom->stream, L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, G, vs, K);
+  }, gradient != 0, mpi, srcs, corr);
   GFSHIP_HIP (hipGetLastError ());
   dom->kc[mpi ? GFSHIP_KC_ADVECT3_TILED_MPI : GFSHIP_KC_ADVECT3_TILED]++;
   return GFSHIP_OK;

@@ -41,7 +41,7 @@ static int rccl_load ()
   if (g_rccl.handle) return GFSHIP_OK;
   /* GFSHIP_RCCL_LIBRARY: the RCCL to open (a site's own build; the test suite's in-process stand-in,
      tests/mock_rccl, which runs N ranks of this transport as N threads on one GPU): no fallback to the
-     system's library when it is set and cannot be opened */
+     system's library when it is set and cannot be opened.  Not in the table (switches.hpp): a path, not a switch */
   const char * named = getenv ("GFSHIP_RCCL_LIBRARY");
   const char * names[] = { "librccl.so.1", "/opt/rocm/lib/librccl.so.1", "librccl.so" };
   void * h = nullptr;

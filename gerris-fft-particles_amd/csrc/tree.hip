@@ -121,6 +121,7 @@ struct Recorder {           // host: which cells does the stencil read?
 
 struct gfship_tree {
   int device = 0;
+  gfship::Switches sw;                            // the GFSHIP_* environment switches, read by gfship_tree_create
   hipStream_t stream = nullptr;
   Topo H, D;
   std::vector<unsigned char> hflag;
@@ -1446,7 +1447,7 @@ int sweep_plan (gfship_tree * tr, int m, Sweep * S)
     }
     nlev = std::max (nlev, L + 1);
   }
-  if (getenv ("GFSHIP_TREE_DEBUG")) {
+  if (tr->sw.tree_debug) {
     // what pipelining the nrelax sweeps of a loop would give: the sequential program [copies of the
     // ghosts][sweep 0][copies][sweep 1]... scheduled into levels that keep its RAW / WAR / WAW order
     const int nrelax = 4;
@@ -1898,22 +1899,18 @@ int loop_plan (gfship_tree * tr, int m, unsigned nrelax, Sweep * S, Sweep::Loop 
     for (int l = 0; l <= tr->H.depth; l++)
       for (int g = tr->H.off[l]; g < tr->H.off[l + 1]; g++) level_of[g] = l;
     P.flow = new FlowPlan;
-    static int flow_width = -1;
-    if (flow_width < 0) {
-      const char * e = getenv ("GFSHIP_FLOW_WIDTH");      /* lab: operations per level (a multiple of 64 up to 512) */
-      flow_width = e ? std::min (FLOW_WIDTH, std::max (64, atoi (e)/64*64)) : 0;
-    }
+    const int flow_width = std::min (FLOW_WIDTH, tr->sw.flow_width);      /* lab: operations per level (a multiple of 64 up to 512) */
     /* a level costs about the same whatever its width: the widest plan wins on octrees; the levels of a quadtree
        are narrow, 256 operations per level are as few levels and fewer idle wavefronts (measured: 11.5 against
        12.5 ms per step on the quadtree bench) */
     const int width = flow_width ? flow_width : tr->H.dim == 2 ? 256 : FLOW_WIDTH;
-    if (!flow_plan (tr->ncell, tr->H.dim, S, nrelax, sg, level_of.data (), tr->H.dim == 2, P.flow, g_host_only, width)) {
+    if (!flow_plan (tr->ncell, tr->H.dim, S, nrelax, sg, level_of.data (), tr->H.dim == 2, P.flow, g_host_only, tr->sw.tree_debug, width)) {
       flow_free (*P.flow);
       delete P.flow;
       P.flow = nullptr;
     }
   }
-  if (getenv ("GFSHIP_TREE_DEBUG"))
+  if (tr->sw.tree_debug)
     fprintf (stderr, "gfship_tree: relax loop of level %d: %u sweeps, %d nodes in %d levels, %d chunks; flow plan: %d operations in %d levels, %d constants\n",
 	     m, nrelax, P.nnodes, P.nlev, P.nchunks, P.flow ? P.flow->nops : -1, P.flow ? P.flow->nlev : -1,
 	     P.flow ? P.flow->nct : -1);
@@ -2072,13 +2069,8 @@ int residual_norm (gfship_tree * tr, const double * u, const double * rhs, doubl
 {
   GFSHIP_HIP (hipMemsetAsync (tr->d_red, 0, 4*sizeof (double), tr->stream));
   {
-    static int no_tape = -1;
-    if (no_tape < 0) {
-      const char * e = getenv ("GFSHIP_TREE_NO_RESIDUAL_TAPE");      /* 1: the residual by the code that walks the tree */
-      no_tape = e ? atoi (e) : 0;
-    }
     const Sweep & S = tr->sweep[tr->H.depth];
-    if (!no_tape && S.taped && S.ncells == tr->nleaves)
+    if (tr->sw.tree_residual_tape && S.taped && S.ncells == tr->nleaves)
       t_residual_tape<<<blocks (S.ncells), 256, 0, tr->stream>>> (tr->D, S.cells, S.cell_off, S.ncells, S.ti, S.td, S.tv,
 								   u, rhs, res, tr->d_red);
     else
@@ -2104,23 +2096,14 @@ int relax_loop (gfship_tree * tr, int m, unsigned nrelax, double omega, int op =
 		const Sgn6 * sgp = nullptr)
 {
   Sweep & S = tr->sweep[m];
-  static int use_template = -1;
-  if (use_template < 0) {
-    const char * e = getenv ("GFSHIP_TREE_TEMPLATE_RELAX");   /* 1: the stencil code walks the tree in every sweep */
-    use_template = e ? atoi (e) : 0;
-  }
+  const bool use_template = tr->sw.tree_template_relax;
   if (!tr->tape_attr_set) {       /* more than 64 KB of dynamic LDS needs the attribute */
     GFSHIP_HIP (hipFuncSetAttribute ((const void *) t_relax_tape, hipFuncAttributeMaxDynamicSharedMemorySize,
 				     TAPE_LDS_BYTES));
     tr->tape_attr_set = true;
   }
-  static int no_pipeline = -1;
-  if (no_pipeline < 0) {
-    const char * e = getenv ("GFSHIP_TREE_NO_PIPELINE");      /* 1: sweep after sweep (t_relax_tape) */
-    no_pipeline = e ? atoi (e) : 0;
-  }
   const Sgn6 sg = sgp ? *sgp : homogeneous_signs (tr);
-  if (S.taped && !use_template && (!no_pipeline || op == 1)) {
+  if (S.taped && !use_template && (tr->sw.tree_pipeline || op == 1)) {
     Sweep::Loop * P = &S.loop;
     if (op == 1) {
       /* the plan with these conditions and this number of sweeps, kept from an earlier solve */
@@ -2138,12 +2121,7 @@ int relax_loop (gfship_tree * tr, int m, unsigned nrelax, double omega, int op =
       int e = loop_plan (tr, m, nrelax, &S);
       if (e) return e;
     }
-    static int no_flow = -1;
-    if (no_flow < 0) {
-      const char * e = getenv ("GFSHIP_TREE_NO_FLOW");          /* 1: the tape kernels (t_relax_nodes_pf) */
-      no_flow = e ? atoi (e) : 0;
-    }
-    if (P->flow && !no_flow) {
+    if (P->flow && tr->sw.tree_flow) {
       const FlowPlan & F = *P->flow;
       t_flow_pack<<<blocks (F.npos), 256, 0, tr->stream>>> (F.gidx, F.npos, tr->var[V_DP], tr->var[V_RES], F.up, F.rp);
       if (tr->H.dim == 3)
@@ -2154,12 +2132,7 @@ int relax_loop (gfship_tree * tr, int m, unsigned nrelax, double omega, int op =
       KCHECK ();
       return 0;
     }
-    static int old_nodes = -1;
-    if (old_nodes < 0) {
-      const char * e = getenv ("GFSHIP_TREE_NO_PREFETCH");      /* 1: t_relax_nodes (every load in place) */
-      old_nodes = e ? atoi (e) : 0;
-    }
-    if (old_nodes) {
+    if (!tr->sw.tree_prefetch) {
       GFSHIP_HIP (hipFuncSetAttribute ((const void *) t_relax_nodes, hipFuncAttributeMaxDynamicSharedMemorySize,
 				       TAPE_LDS_BYTES));
       t_relax_nodes<<<1, 1024, TAPE_LDS_BYTES, tr->stream>>> (tr->D, P->node_g, P->node_off, P->chunk,
@@ -2805,6 +2778,7 @@ static int tree_create_sides (gfship_tree ** out, int dim, gfship_refine_fn refi
   GFSHIP_CHECK (e == 0, e, "gfship_tree_create: more than %d levels", GFSHIP_MAXLEVEL);
   gfship_tree * tr = new gfship_tree;
   tr->device = device;
+  tr->sw = read_switches ();
   for (int d = 0; d < 2*dim; d++) {
     tr->side[d] = side ? side[d] : GFSHIP_SIDE_PERIODIC;
     if (tr->side[d] != GFSHIP_SIDE_PERIODIC && tr->side[d] != GFSHIP_SIDE_BOUNDARY) {
@@ -3194,7 +3168,7 @@ int gfship_tree_host_check (int dim, gfship_refine_fn refine, void * ctx, const 
     if (S.loop.flow) {
       const long long hz = flow_emulate (*S.loop.flow, T.dim, c4, rhs, omega, 0, 1.);
       stats[3] += hz;
-      if (getenv ("GFSHIP_TREE_DEBUG")) {
+      if (tr->sw.tree_debug) {
 	long long nd4 = 0;
 	for (int g = 0; g < tr->ncell; g++) nd4 += memcmp (&a[g], &c4[g], sizeof (double)) != 0;
 	fprintf (stderr, "gfship_tree: flow plan of level %d: %lld hazards, %lld values differ\n", m, hz, nd4);

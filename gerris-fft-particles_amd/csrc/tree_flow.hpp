@@ -752,7 +752,7 @@ struct FlowBuilder {
 // the copies of the ghosts between the sweeps, as a flow plan; returns false when the loop does not fit
 // the format (the caller keeps the tape kernels)
 inline bool flow_plan (int ncell, int dim, const Sweep * S, unsigned nrelax, const Sgn6 & sg, const int * cell_level_of,
-		       bool reads_self, FlowPlan * out, bool host_only, int width = FLOW_WIDTH)
+		       bool reads_self, FlowPlan * out, bool host_only, bool debug, int width = FLOW_WIDTH)
 {
   flow_free (*out);
   FlowBuilder B;
@@ -831,7 +831,7 @@ inline bool flow_plan (int ncell, int dim, const Sweep * S, unsigned nrelax, con
   }
   FlowPlan & F = *out;
   F.width = width;
-  if (getenv ("GFSHIP_TREE_DEBUG")) fprintf (stderr, "gfship_tree: flow plan: %d of %zu levels have a wavefront with two kinds\n", nmixed_out, B.lev.size ());
+  if (debug) fprintf (stderr, "gfship_tree: flow plan: %d of %zu levels have a wavefront with two kinds\n", nmixed_out, B.lev.size ());
   {
     // places in the order of the plan
     std::vector<int> pos (ncell, -1);

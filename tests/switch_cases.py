@@ -1,10 +1,11 @@
 """Registry of the GFSHIP_* environment switches and the cases that pin them on the oracle
 (tests/test_gpu_switches.py, tests/switch_worker.py, tests/test_switch_registry_cpu.py).
 
-Most kernel-selecting switches are read once per process into a `static const', so each setting
-runs in a process of its own (switch_worker.py) and the parent compares what it wrote with the
-oracle.  A case is one function that drives either side the same way -- run_case (name, "oracle")
-on the CPU, run_case (name, "device") in the worker -- and returns a flat {key: array or scalar}:
+Every switch is looked up when a Domain or a Tree is created (csrc/switches.hpp).  Each setting
+still runs in a process of its own (switch_worker.py), so that a fault under one switch cannot take
+the others with it, and the parent compares what it wrote with the oracle.  A case is one function
+that drives either side the same way -- run_case (name, "oracle") on the CPU, run_case (name,
+"device") in the worker -- and returns a flat {key: array or scalar}:
 the state after the last step in full, the state after every earlier step as SHA-256 digests of
 the same arrays (so the files stay small and every step is still compared bit for bit).
 
@@ -566,7 +567,7 @@ NOT_KERNEL_SELECTING = {
 # of these, the loader's own settings stay in the environment of a worker (it must load the library
 # the parent tests); every other GFSHIP_* variable the caller's shell may hold is stripped
 KEEP_IN_CHILD = ("GFSHIP_LIB", "GFSHIP_NO_TORCH")
-# kernel-selecting, read when a Domain / Tree is created or on every call, pinned elsewhere: name -> file
+# kernel-selecting, pinned elsewhere: name -> file
 PINNED_ELSEWHERE = {
     "GFSHIP_SKEW_OLD": "tests/test_gpu_poisson.py",
     "GFSHIP_SKEW_LINES": "tests/test_gpu_poisson.py",
@@ -581,11 +582,6 @@ PINNED_ELSEWHERE = {
     "GFSHIP_TREE_NO_FLOW": "tests/test_gpu_tree.py",
     "GFSHIP_TREE_NO_PREFETCH": "tests/test_gpu_tree.py",
 }
-# read once per process into a static: must be set before the first call into the library
-READ_ONCE = ("GFSHIP_NO_ADVECT_SWEEP", "GFSHIP_NO_MPI_SWEEP", "GFSHIP_ADVECT_SWEEP1", "GFSHIP_PC_SCALAR",
-             "GFSHIP_RN_SCALAR", "GFSHIP_RN_BLOCKS", "GFSHIP_NO_ROWS2D", "GFSHIP_COARSE_THREADS",
-             "GFSHIP_DIFFUSION_HYPERPLANES", "GFSHIP_WEIGHTED_HYPERPLANES")
-
 
 def child_timeout(switch):
     """time limit of the worker of a switch [s]: start-up plus a generous allowance per case (uploads

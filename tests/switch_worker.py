@@ -1,6 +1,5 @@
 """Worker of tests/test_gpu_switches.py: one setting of the GFSHIP_* switches in a process of its own
-(most of them are read once per process into a static, so they must be in the environment before the
-library is loaded).  Runs the device half of every case tests/switch_cases.py lists for the switch,
+(a domain looks them up when it is created; here they are in the environment from the start).  Runs the device half of every case tests/switch_cases.py lists for the switch,
 writes OUTDIR/<case>.npz (fields, scalars) and OUTDIR/<case>.json (the tallies of
 gfship_domain_kernel_counts and what else the case reports) and prints one JSON line.  It computes
 no oracle and asserts nothing about bits: the parent does.

@@ -1,7 +1,8 @@
 """Every kernel-selecting GFSHIP_* switch against the oracle, one process per setting.
 
-Most of the switches are read once per process into a static, so monkeypatch.setenv inside pytest
-would test the default path twice.  Per setting of tests/switch_cases.py:SWITCHES this file starts
+A domain looks its switches up when it is created (csrc/switches.hpp;
+test_three_domains_of_one_process_each_follow_their_own_environment).  A process per setting keeps a
+fault under one switch from the others: per setting of tests/switch_cases.py:SWITCHES this file starts
 ONE child (tests/switch_worker.py, a fresh interpreter with the setting in its environment before the
 library is loaded; one child at a time), then compares every case the child ran with the oracle --
 np.array_equal on every field of the last step, the SHA-256 of every field of the earlier steps, ==
@@ -172,3 +173,36 @@ def test_control_run_takes_the_default_branches(tmp_path_factory):
     for case in S.VC128 + ("tg128",):
         assert c[case]["PROLONGATION_FUSED"] > 0 and c[case]["RESTRICTION_FUSED"] > 0, (case, c[case])
         assert c[case]["PATCH_LOOP_HOST_ARMS"] > 0 and c[case]["COARSE_CYCLES"] > 0, (case, c[case])
+
+
+def test_three_domains_of_one_process_each_follow_their_own_environment(monkeypatch):
+    """A domain looks its switches up when it is created, none is read once per process: three domains
+    created one after another in this process -- empty environment, three of the switches that used to
+    be read into a static, empty environment again -- each show the kernel families of their own
+    environment, and each equal the oracle (Taylor-Green 64^3 with a mean flow, van Leer + GfsSource,
+    two steps: 64^3 is the smallest size the sweeps along z and the pair kernels run at)"""
+    case = S._case_tg(6, 1, -0.7, False, 2)
+    oracle = case("oracle", None)
+    default = ("PREDICT_SWEEP", "ADVECT3_SWEEP2", "RESIDUAL_PAIRS", "PROJECT_PAIRS")
+    switched = ("PREDICT_TILED", "ADVECT3_TILED", "RESIDUAL_SCALAR", "PROJECT_SCALAR")
+    for k in [k for k in os.environ if k.startswith("GFSHIP_") and k not in S.KEEP_IN_CHILD]:
+        monkeypatch.delenv(k)
+    bad = []
+    for which, env in enumerate(({}, {"GFSHIP_NO_ADVECT_SWEEP": "1", "GFSHIP_RN_SCALAR": "1", "GFSHIP_PC_SCALAR": "1"}, {})):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        dev = S._Device()
+        rec = case("device", dev)           # creates the domain: the environment counts from here on
+        for k in env:
+            monkeypatch.delenv(k)
+        counts = S._counts(dev.domains)
+        for gs in dev.sims:
+            gs.destroy()
+        for gd in dev.domains:
+            gd.destroy()
+        print("domain %d: %s" % (which + 1, {k: v for k, v in counts.items() if v}))
+        on, off = (switched, default) if env else (default, switched)
+        bad += ["domain %d: %s == %d, expected > 0" % (which + 1, f, counts[f]) for f in on if not counts[f] > 0]
+        bad += ["domain %d: %s == %d, expected 0" % (which + 1, f, counts[f]) for f in off if counts[f] != 0]
+        bad += ["domain %d: %s" % (which + 1, d) for d in _differences(oracle, rec)]
+    assert not bad, "\n".join(bad)

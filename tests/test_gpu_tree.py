@@ -282,7 +282,8 @@ def test_other_relax_kernels_give_the_same_bits(switch):
     interpreted from the tapes (t_relax_nodes_pf; with GFSHIP_TREE_NO_PREFETCH=1 t_relax_nodes);
     GFSHIP_FLOW_WIDTH: fewer operations per level of the flow plan; GFSHIP_TREE_NO_RESIDUAL_TAPE=1: the residual
     by the code that walks the tree instead of the compiled stencils: the same comparison with the oracle, in a
-    process of its own (the switches are read once)"""
+    process of its own (a tree looks its switches up when it is created; it keeps no tallies that could tell an
+    in-process test which branch ran)"""
     import subprocess
     import sys
     code = ("import sys; sys.path.insert(0, %r); import test_gpu_tree as t; "

@@ -24,12 +24,42 @@ def _read(path):
         return f.read()
 
 
-def _names_read_by_the_sources():
-    names = {}
+TABLE = os.path.join(PKG, "csrc", "switches.hpp")
+# read outside the table, each for a reason the source states beside the read: name -> file
+OUTSIDE_THE_TABLE = {
+    "GFSHIP_FAULT_DROP_HANDOFF": "csrc/relax_skew_loop.hip",
+    "GFSHIP_RCCL_LIBRARY": "csrc/transport.hip",
+    "GFSHIP_CC": "csrc/host/gfs_function.hpp",
+}
+README_RULE = "Every switch of the library is looked up when a domain or a tree is created"
+
+
+def _table_lines():
+    """the lines of read_switches (): [(member, [names])], one per environment variable"""
+    body = _read(TABLE)
+    body = body[body.index("inline Switches read_switches ()"):]
+    body = body[body.index("Switches s;") + len("Switches s;"):body.index("return s;")]
+    return [(line.split("=")[0].strip(), re.findall(r'"(GFSHIP_[A-Z0-9_]+)"', line))
+            for line in body.splitlines() if line.strip()]
+
+
+def _getenv_calls():
+    """every getenv under csrc/: [(path relative to the package, its argument as written)]"""
+    calls = []
     for path in glob.glob(os.path.join(PKG, "csrc", "**", "*"), recursive=True):
         if os.path.splitext(path)[1] in (".hip", ".hpp", ".cpp", ".h"):
-            for m in re.finditer(r'getenv\s*\(\s*"(GFSHIP_[A-Z0-9_]+)"', _read(path)):
-                names.setdefault(m.group(1), set()).add(os.path.relpath(path, ROOT))
+            for m in re.finditer(r'\bgetenv\s*\(\s*([^)]*?)\s*\)', _read(path)):
+                calls.append((os.path.relpath(path, PKG), m.group(1)))
+    return calls
+
+
+def _names_read_by_the_sources():
+    names = {}
+    for member, found in _table_lines():
+        for name in found:
+            names.setdefault(name, set()).add(os.path.relpath(TABLE, ROOT))
+    for name, path in OUTSIDE_THE_TABLE.items():
+        names.setdefault(name, set()).add(os.path.join("gerris-fft-particles_amd", path))
     for path in glob.glob(os.path.join(PKG, "gfship", "**", "*.py"), recursive=True) + [os.path.join(ROOT, "bench.py")]:
         for m in re.finditer(r'environ(?:\.get\s*\(|\s*\[)\s*"(GFSHIP_[A-Z0-9_]+)"', _read(path)):
             names.setdefault(m.group(1), set()).add(os.path.relpath(path, ROOT))
@@ -47,7 +77,7 @@ def test_every_variable_the_sources_read_is_accounted_for():
     # one home per name
     assert not set(S.REGISTRY_NAMES) & set(S.NOT_KERNEL_SELECTING)
     assert not set(S.NOT_KERNEL_SELECTING) & set(S.PINNED_ELSEWHERE)
-    assert set(S.READ_ONCE) <= set(S.REGISTRY_NAMES)
+    assert not set(S.REGISTRY_NAMES) & set(S.PINNED_ELSEWHERE)
 
 
 def test_variables_pinned_elsewhere_are_set_by_the_file_named():
@@ -56,15 +86,25 @@ def test_variables_pinned_elsewhere_are_set_by_the_file_named():
 
 
 def test_read_once_list_matches_the_sources():
-    """a variable read into a function-level static must be set before the library is loaded"""
-    static = set()
-    for path in glob.glob(os.path.join(PKG, "csrc", "*.hip")):
-        text = _read(path)
-        static |= set(re.findall(r'static const bool \w+ = getenv \("(GFSHIP_[A-Z0-9_]+)"\)', text))
-        # static int n = 0; if (!n) { e = getenv (...) }
-        for m in re.finditer(r'static int (\w+) = 0;\s*if \(!\1\) \{\s*const char \* e = getenv \("(GFSHIP_[A-Z0-9_]+)"\)', text):
-            static.add(m.group(2))
-    assert static == set(S.READ_ONCE), static ^ set(S.READ_ONCE)
+    """nothing is read once per process or per call any more: the table of csrc/switches.hpp, with one
+    line, one member and one variable per line, and the three reads allowed outside it are every getenv
+    under csrc/"""
+    lines = _table_lines()
+    assert len(lines) >= 35
+    for member, found in lines:
+        assert re.fullmatch(r"s\.\w+", member) and len(set(found)) == 1, (member, found)
+    members = [m for m, _ in lines]
+    names = [f[0] for _, f in lines]
+    assert len(set(members)) == len(members) and len(set(names)) == len(names)
+    # every member of the struct is filled by a line of the table
+    struct = _read(TABLE)
+    struct = struct[struct.index("struct Switches {"):struct.index("bool patch () const")]
+    declared = re.findall(r"^\s*(?:bool|int) (\w+) = ", struct, flags=re.M)
+    assert sorted("s." + d for d in declared) == sorted(members)
+    outside = [(path, arg) for path, arg in _getenv_calls() if path != "csrc/switches.hpp"]
+    assert sorted(outside) == sorted((path, '"%s"' % name) for name, path in OUTSIDE_THE_TABLE.items()), outside
+    # the table itself calls getenv in its three helpers only, on their argument
+    assert [arg for path, arg in _getenv_calls() if path == "csrc/switches.hpp"] == ["name"] * 3
 
 
 def test_every_variable_is_documented():
@@ -74,9 +114,8 @@ def test_every_variable_is_documented():
         assert name in docs, "%s is documented neither in README.md nor in DESIGN.md" % name
     for name in S.REGISTRY_NAMES:
         assert name in readme, "%s is missing from README.md's list of switches" % name
-    for name in S.READ_ONCE:
-        assert re.search(r"read once[^\n]*(\n[^\n]+)*%s\b" % name, readme), \
-            "README.md does not say that %s is read once per process" % name
+    assert README_RULE in " ".join(readme.split()), "README.md does not state when the switches are looked up"
+    assert "read once per process, at the first call" not in " ".join(readme.split())
 
 
 def test_design_table_matches_the_registry():

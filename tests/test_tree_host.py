@@ -47,7 +47,7 @@ def test_refinement_that_differs_across_a_periodic_side_is_refused():
 
 @pytest.mark.parametrize("width", [64, 192])
 def test_flow_plans_with_fewer_operations_per_level(width):
-    """GFSHIP_FLOW_WIDTH (read once per process): the flow plans of a quadtree and of an octree with levels
+    """GFSHIP_FLOW_WIDTH (looked up when a tree is created): the flow plans of a quadtree and of an octree with levels
     of 64 / 192 operations at most: more levels, chains of CHILD -> SUM -> CELL squeezed by the capacity"""
     import os
     import subprocess
