@@ -1,14 +1,19 @@
 // diffusion.hip -- implicit diffusion (GfsSourceDiffusion / viscosity): kernels and host control
 // behind gfs_diffusion_coefficients, gfs_diffusion_rhs, gfs_diffusion_residual,
-// gfs_diffusion_cycle (src/poisson.c:1271-1690) and gfs_diffusion (src/timestep.c:735-788), for a
-// constant diffusion coefficient, constant density and no solid boundaries.
+// gfs_diffusion_cycle (src/poisson.c:1271-1690) and gfs_diffusion (src/timestep.c:735-788), without
+// solid boundaries.
 //
-// Under these conditions every leaf face carries the same weight w = lambda2*beta*dt*D
-// (diffusion_coef, src/poisson.c:1280-1303) and every cell the same rhoc = 1.
-// (diffusion_mixed_coef :1305-1348), so a level is described by one scalar instead of 2*dim
-// arrays; the coarse weights are computed on the host with face_coeff_from_below's arithmetic
-// (:826-853), one scalar per level.  The in-place sweeps reuse the exact-order kernels of
-// poisson_kernels.hip with the diffusion cell update (RelaxOp kind 1).
+// With a constant diffusion coefficient and a constant density (gfship_diffusion_coefficients) every
+// leaf face carries the same weight w = lambda2*beta*dt*D (diffusion_coef, src/poisson.c:1280-1303)
+// and every cell the same rhoc = 1. (diffusion_mixed_coef :1305-1348), so a level is described by one
+// scalar instead of 2*dim arrays; the coarse weights are computed on the host with
+// face_coeff_from_below's arithmetic (:826-853), one scalar per level.  The in-place sweeps reuse the
+// exact-order kernels of poisson_kernels.hip with the diffusion cell update (RelaxOp kind 1).
+//
+// With a coefficient given at the leaf faces and a density given at the cells of every level
+// (gfship_diffusion_coefficients_faces) the weights are the arrays f[d].v the weighted Poisson solver
+// uses (dom->wf), computed on the device, and the sweeps run the same cell update with the six weights
+// of the cell (RelaxOp kind 3).  The domain remembers which of the two was set last (diff_kind).
 #include "gfship_internal.hpp"
 #include <cmath>
 #include <cstdlib>
@@ -51,7 +56,7 @@ diffusion_rhs_kernel (Layout L, double w, double pbeta, const double * __restric
   rhs[c] += pbeta*f/(h*h*rhoc[c]);
 }
 
-// diffusion_residual, src/poisson.c:1519-1556
+// diffusion_residual, src/poisson.c:1534-1569
 template <int DIM>
 __global__ void __launch_bounds__(256)
 diffusion_residual_kernel (Layout L, double w, const double * __restrict__ u,
@@ -95,6 +100,74 @@ restrict_intensive_kernel (Layout Lc, Layout Lf, double * __restrict__ vc,
   vc[c] = val/sa;
 }
 
+// the same two with the six face weights of the cell (gfs_face_cm_weighted_gradient's same-level branch,
+// src/fluid.c:1361-1366: g.a = w, g.b = w*v_nb), d = 0 .. 2 DIM - 1
+struct DW6 { const double * p[6]; };
+
+template <int DIM>
+__global__ void __launch_bounds__(256)
+diffusion_rhs_faces_kernel (Layout L, DW6 wf, double pbeta, const double * __restrict__ v,
+			    const double * __restrict__ rhoc, double * __restrict__ rhs)
+{
+  CELL_LOOP_PROLOGUE (L);
+  const double h = 1./L.n;
+  const long off[3] = { 1, L.sy, L.sz };
+  const double val = v[c];
+  double f = 0.;
+#pragma unroll
+  for (int cc = 0; cc < DIM; cc++) {
+    { const double g = wf.p[2*cc][c]; f += g*v[c + off[cc]] - g*val; }
+    { const double g = wf.p[2*cc + 1][c]; f += g*v[c - off[cc]] - g*val; }
+  }
+  rhs[c] += pbeta*f/(h*h*rhoc[c]);
+}
+
+template <int DIM>
+__global__ void __launch_bounds__(256)
+diffusion_residual_faces_kernel (Layout L, DW6 wf, const double * __restrict__ u,
+				 const double * __restrict__ rhs, const double * __restrict__ rhoc,
+				 double * __restrict__ res)
+{
+  CELL_LOOP_PROLOGUE (L);
+  const double h = 1./L.n;
+  const long off[3] = { 1, L.sy, L.sz };
+  double a = rhoc[c];
+  double ga = 0., gb = 0.;
+#pragma unroll
+  for (int cc = 0; cc < DIM; cc++) {
+    { const double g = wf.p[2*cc][c]; ga += g; gb += g*u[c + off[cc]]; }
+    { const double g = wf.p[2*cc + 1][c]; ga += g; gb += g*u[c - off[cc]]; }
+  }
+  a *= h*h;
+  ga = 1. + ga/a;
+  gb = rhs[c] + gb/a;
+  res[c] = gb - ga*u[c];
+}
+
+// diffusion_mixed_coeff, src/poisson.c:1321-1332, on the cells of one level: rho = 1./alpha (the cell
+// fraction is 1.); *bad is set where the reference stops with "density is negative", and for an alpha
+// that is zero or not a number
+template <int DIM>
+__global__ void __launch_bounds__(256)
+diffusion_rhoc_kernel (Layout L, const double * __restrict__ alpha, double * __restrict__ rhoc,
+		       unsigned * __restrict__ bad)
+{
+  CELL_LOOP_PROLOGUE (L);
+  const double al = alpha[c];
+  const double rho = 1./al;
+  if (!(al > 0.) || !(rho > 0.))
+    *bad = 1u;
+  rhoc[c] = rho*1.;
+}
+
+static DW6 level_weights (gfship_domain * dom, int level)
+{
+  DW6 w;
+  for (int d = 0; d < 6; d++)
+    w.p[d] = d < 2*dom->dim ? dom->fields[dom->wf[d]].lev[level] : nullptr;
+  return w;
+}
+
 #define DLAUNCH(dom, kern, grid, block, ...) do {				\
     if ((dom)->dim == 3)						\
       hipLaunchKernelGGL (kern<3>, grid, block, 0, (dom)->stream, __VA_ARGS__); \
@@ -103,15 +176,29 @@ restrict_intensive_kernel (Layout Lc, Layout Lf, double * __restrict__ vc,
     GFSHIP_HIP (hipGetLastError ());					\
   } while (0)
 
-static RelaxOp level_op (const gfship_domain * dom, int level)
+static RelaxOp level_op (gfship_domain * dom, int level)
 {
   RelaxOp op;
-  op.kind = 1;
-  op.w = dom->diff_w[level];
+  if (dom->diff_kind == 3) {
+    op = weighted_op (dom, level);      /* the six arrays of the level */
+    op.kind = 3;
+  }
+  else {
+    op.kind = 1;
+    op.w = dom->diff_w[level];
+  }
   double h = 1./dom->lay[level].n;
   op.h2 = h*h;
   return op;
 }
+
+// the 2 x 2 ring kernels know the uniform weight only: whether a level may run on them is decided by
+// the coefficients of THIS call, whatever the last Poisson call left in dom->weighted
+struct PatchCall {
+  gfship_domain * dom;
+  PatchCall (gfship_domain * d, int kind) : dom (d) { dom->patch_call = kind == 1; }
+  ~PatchCall () { dom->patch_call = -1; }
+};
 
 // relax_loop, src/poisson.c:1070-1089, with diffusion_relax as the cell update
 static int relax_loop (gfship_domain * dom, Field * dp, Field * u, int level, Field * res,
@@ -119,6 +206,8 @@ static int relax_loop (gfship_domain * dom, Field * dp, Field * u, int level, Fi
 {
   int r;
   RelaxOp op = level_op (dom, level);
+  PatchCall scope (dom, op.kind);
+  const bool faces = op.kind == 3;
   dp->zero[level] = false;
   bool done = false;
   if ((r = launch_relax_loop_small (dom, dom->dim, level, 1., dp, u, res->lev[level],
@@ -128,10 +217,12 @@ static int relax_loop (gfship_domain * dom, Field * dp, Field * u, int level, Fi
     return GFSHIP_OK;
   /* 3-D levels of 32^3 and more: the pipelined tile kernels with the diffusion cell update (rhoc
      travels as their dia stream); the whole loop in one launch on boxes without MPI sides */
-  const bool pipelined = dom->sw.diffusion_pipelined;
+  const bool pipelined = faces ? dom->sw.weighted_pipelined : dom->sw.diffusion_pipelined;
   const bool pipelined_applies = dom->dim == 3 && dom->relax_mode == GFSHIP_RELAX_EXACT && !dom->force_hyperplane &&
     skew_supported (dom, level) && !(dom->has_external && dom->overlap && nrelax > 1);
-  if (pipelined_applies)
+  if (pipelined_applies && faces)
+    dom->kc[pipelined ? GFSHIP_KC_DIFFUSION_FACES_PIPELINED : GFSHIP_KC_DIFFUSION_FACES_HYPERPLANES]++;
+  else if (pipelined_applies)
     dom->kc[pipelined ? GFSHIP_KC_DIFFUSION_PIPELINED : GFSHIP_KC_DIFFUSION_HYPERPLANES]++;
   if (pipelined && pipelined_applies)
     return launch_relax_loop_skew (dom, level, dp, u, res->lev[level], dia->lev[level], false, nrelax,
@@ -153,8 +244,12 @@ static int residual (gfship_domain * dom, Field * U, Field * R, Field * C, Field
   dim3 grid, block;
   cell_grid (dom->lay[L], &grid, &block);
   S->zero[L] = false;
-  DLAUNCH (dom, diffusion_residual_kernel, grid, block, dom->lay[L], dom->diff_w[L],
-	   U->lev[L], R->lev[L], C->lev[L], S->lev[L]);
+  if (dom->diff_kind == 3)
+    DLAUNCH (dom, diffusion_residual_faces_kernel, grid, block, dom->lay[L], level_weights (dom, L),
+	     U->lev[L], R->lev[L], C->lev[L], S->lev[L]);
+  else
+    DLAUNCH (dom, diffusion_residual_kernel, grid, block, dom->lay[L], dom->diff_w[L],
+	     U->lev[L], R->lev[L], C->lev[L], S->lev[L]);
   return GFSHIP_OK;
 }
 
@@ -187,6 +282,57 @@ int gfship_diffusion_coefficients (gfship_domain * dom, double D, double dt, gfs
     if (r) return r;
   }
   dom->diff_ready = true;
+  dom->diff_kind = 1;
+  return GFSHIP_OK;
+}
+
+int gfship_diffusion_coefficients_faces (gfship_domain * dom, const gfship_field D[3], double dt,
+					 gfship_field rhoc, gfship_field alpha_cell, double beta)
+{
+  GFSHIP_CHECK (dom != nullptr, GFSHIP_EINVAL, "null domain");
+  GFSHIP_CHECK (D != nullptr, GFSHIP_EINVAL, "null diffusion coefficient");
+  GFSHIP_CHECK (beta >= 0.5 && beta <= 1., GFSHIP_EINVAL, "beta must be in [0.5,1]");
+  GFSHIP_CHECK (!dom->has_external, GFSHIP_EUNSUPPORTED,
+		"per-face diffusion coefficients on a box with MPI sides are not supported");
+  Field * C = get_field (dom, rhoc);
+  if (!C) return GFSHIP_EINVAL;
+  Field * A = nullptr;
+  if (alpha_cell != -1 && !(A = get_field (dom, alpha_cell))) return GFSHIP_EINVAL;
+  double * d[3] = { nullptr, nullptr, nullptr };
+  for (int c = 0; c < dom->dim; c++) {
+    Field * F = get_field (dom, D[c]);
+    if (!F) return GFSHIP_EINVAL;
+    d[c] = F->lev[dom->depth];
+  }
+  int r;
+  if ((r = before_write (dom))) return r;
+  const int L = dom->depth;
+  /* diffusion_mixed_coeff on every cell of every level (FTT_TRAVERSE_ALL) */
+  if (A) {
+    unsigned * bad = (unsigned *) (dom->d_scratch + dom->scratch_doubles - 1), hbad = 0;
+    GFSHIP_HIP (hipMemsetAsync (bad, 0, sizeof (unsigned), dom->stream));
+    for (int l = 0; l <= L; l++) {
+      dim3 grid, block;
+      cell_grid (dom->lay[l], &grid, &block);
+      C->zero[l] = false;
+      DLAUNCH (dom, diffusion_rhoc_kernel, grid, block, dom->lay[l], A->lev[l], C->lev[l], bad);
+    }
+    GFSHIP_HIP (hipMemcpyAsync (&hbad, bad, sizeof (unsigned), hipMemcpyDeviceToHost, dom->stream));
+    GFSHIP_HIP (hipStreamSynchronize (dom->stream));
+    if (hbad)
+      dom->diff_ready = false;      /* rhoc has been overwritten: no solve before the next successful call */
+    GFSHIP_CHECK (!hbad, GFSHIP_EINVAL, "density is negative or zero: check the definition of alpha");
+  }
+  else
+    for (int l = 0; l <= L; l++)
+      if ((r = gfship_field_fill (dom, rhoc, l, 1.*1.))) return r;
+  /* diffusion_coef with dt <- beta*dt, then face_coeff_from_below: into f[d].v, which the Poisson
+     solver shares (the skewed copies of either are stale from here) */
+  if ((r = alloc_weights (dom))) return r;
+  if ((r = launch_diffusion_weights (dom, d, beta*dt))) return r;
+  dom->weights_stamp++;
+  dom->diff_ready = true;
+  dom->diff_kind = 3;
   return GFSHIP_OK;
 }
 
@@ -201,8 +347,12 @@ int gfship_diffusion_rhs (gfship_domain * dom, gfship_field v, gfship_field rhs,
   dim3 grid, block;
   cell_grid (dom->lay[L], &grid, &block);
   R->zero[L] = false;
-  DLAUNCH (dom, diffusion_rhs_kernel, grid, block, dom->lay[L], dom->diff_w[L],
-	   (1. - beta)/beta, V->lev[L], C->lev[L], R->lev[L]);
+  if (dom->diff_kind == 3)
+    DLAUNCH (dom, diffusion_rhs_faces_kernel, grid, block, dom->lay[L], level_weights (dom, L),
+	     (1. - beta)/beta, V->lev[L], C->lev[L], R->lev[L]);
+  else
+    DLAUNCH (dom, diffusion_rhs_kernel, grid, block, dom->lay[L], dom->diff_w[L],
+	     (1. - beta)/beta, V->lev[L], C->lev[L], R->lev[L]);
   return GFSHIP_OK;
 }
 

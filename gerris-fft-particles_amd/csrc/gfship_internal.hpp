@@ -80,6 +80,7 @@ struct SkewPlan {
 // diffusion_relax with the level's uniform face weight w and h2 = h*h
 struct RelaxOp {
   int kind = 0;                  // 2: Poisson relax with the face weights f[d].v of the level (wf)
+                                 // 3: diffusion_relax with the same six weights per cell and h2
   double w = 1., h2 = 1.;
   const double * wf[6] = {};
 };
@@ -154,7 +155,13 @@ struct gfship_domain {
   bool cfl_dirty = false;
   bool coarse_attr_set = false;   // dynamic-LDS limit of coarse_cycle_kernel raised
   gfship_field res_cache = -1;    // the `res` temporary of gfs_diffusion
-  bool diff_ready = false;        // gfship_diffusion_coefficients called
+  bool diff_ready = false;        // gfship_diffusion_coefficients[_faces] called
+  // the diffusion coefficients last set: 1 = one weight per level (diff_w), 3 = the six weights of every
+  // cell in wf[] (gfship_diffusion_coefficients_faces): the RelaxOp kind of the diffusion entry points
+  int diff_kind = 1;
+  // the relax loop being launched decides whether its level may run on the 2 x 2 ring kernels (which
+  // know no per-cell weights): -1 outside such a call (the Poisson path: by `weighted'), else 0 / 1
+  int patch_call = -1;
 };
 
 namespace gfship {
@@ -245,6 +252,10 @@ int launch_residual (gfship_domain * dom, int level, const double * u, const dou
 int launch_residual_weighted (gfship_domain * dom, int level, const double * u, const double * rhs,
 			      const double * dia, double * res);
 int launch_poisson_weights (gfship_domain * dom, double * const alpha[3]);
+// diffusion_coef (src/poisson.c:1280-1301) on the leaves, f[d].v = lambda2*cdt*D_face, then
+// face_coeff_from_below on every coarser level, into wf[]
+int launch_diffusion_weights (gfship_domain * dom, double * const D[3], double cdt);
+int alloc_weights (gfship_domain * dom);
 RelaxOp weighted_op (gfship_domain * dom, int level);
 int launch_restrict (gfship_domain * dom, unsigned dimension, int level_coarse, double * v_coarse,
 		     const double * v_fine);
@@ -271,7 +282,11 @@ int launch_coarse_init_from (gfship_domain * dom, Field * const * v, int nf, int
 int launch_coarse_init_levels (gfship_domain * dom, Field * const * v, int nf, int top, int bottom);
 int launch_advected_face_values (gfship_domain * dom, const double * v, double * const u[3],
 				 double * const un[3], double dt, int use_centered, int gradient,
-				 double * const fv[6], int cmask, double visc = 0., double gsrc = 0.);
+				 double * const fv[6], int cmask, double visc = 0., double gsrc = 0.,
+				 const double * msrc = nullptr /* per-cell MAC source of the diffusion instead of visc */);
+// source_diffusion_value (src/source.c:1105-1144) of every leaf cell: D at the faces, alpha at the cells or nullptr
+int launch_variable_mac_source (gfship_domain * dom, const double * v, double * const D[3],
+				const double * alpha, double * out);
 int launch_face_bc (gfship_domain * dom, Field * v, double * const fv[6], int cmask);
 int launch_predict_un (gfship_domain * dom, int cc, const double * uc, double * const fv[6],
 		       double * unc);
@@ -279,7 +294,8 @@ int launch_flux_update (gfship_domain * dom, bool velocity, double * v, double *
 			double * const fv[6], const double * gm, const double * gc, double dt,
 			double gsrc = 0.);
 int launch_cfl (gfship_domain * dom, double * const u[3], double * const un[3],
-		const double visc[3], double * cfl2);
+		const double visc[3], double * cfl2,
+		double * const msrc[3] = nullptr /* per-cell MAC sources of U, V, W (entries may be null) */);
 int launch_coarse_init (gfship_domain * dom, Field * const * v, int nf);
 int launch_velocity_divergence (gfship_domain * dom, double * const u[3], double * out);
 bool godunov_fused_supported (const gfship_domain * dom);
@@ -332,7 +348,11 @@ int  patch_resident_per_cu (const gfship_domain * dom);
 bool prolongation_fused (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax);
 bool prolongation_fusable (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax);
 /* weighted sweeps (face weights from alpha) run on the six-wave kernel with its tile-skewed layout */
-inline bool patch_level (const gfship_domain * dom, int level) { return dom->sw.patch () && !dom->weighted && dom->lay[level].n >= dom->sw.patch_min_n; }
+inline bool patch_level (const gfship_domain * dom, int level)
+{
+  const bool per_cell_weights = dom->patch_call < 0 ? dom->weighted : dom->patch_call == 0;
+  return dom->sw.patch () && !per_cell_weights && dom->lay[level].n >= dom->sw.patch_min_n;
+}
 int  patch_pack (gfship_domain * dom, int level, SkewPlan * S, const double * u, const double * rhs,
 		 const double * dia, const double * coarse = nullptr);
 int  patch_unpack (gfship_domain * dom, int level, SkewPlan * S, double * u, double * add_into);

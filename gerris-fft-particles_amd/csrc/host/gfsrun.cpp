@@ -9,8 +9,8 @@
 // test/reynolds, test/periodic ...), printed in the reference's formats so that the awk/python
 // checks of test/*/*.sh read them unchanged.  Supported: one GfsBox (periodic through self
 // edges `1 1 right`), uniform `Refine <int>`, Boundary { BcDirichlet | BcNeumann }, Time,
-// ProjectionParams, ApproxProjectionParams, AdvectionParams, Init, SourceDiffusion (constant
-// coefficient on U, V, W), VariableTracer, EventStop, EventScript, GModule (ignored: the device
+// ProjectionParams, ApproxProjectionParams, AdvectionParams, Init, SourceDiffusion / SourceViscosity (a
+// constant or a function of x, y, z, t on U, V, W), VariableTracer, EventStop, EventScript, GModule (ignored: the device
 // solver replaces hypre/agmg), OutputTime, OutputProjectionStats, OutputDiffusionStats,
 // OutputScalarNorm, OutputScalarSum, OutputScalarStats, OutputErrorNorm, OutputLocation,
 // GfsAdvection with a VariableStreamFunction, OutputSimulation (text format), OutputEnergySpectra (`GModule fft`), InitSpectra (`GModule
@@ -174,6 +174,13 @@ struct Run {
   unsigned i = 0, iend = INT_MAX;
   std::map<std::string, std::string> proj_set, approx_set, adv_set;
   double visc[3] = { 0., 0., 0. };
+  // GfsSourceDiffusion / GfsSourceViscosity with a GfsFunction of x, y, z, t: evaluated at the face centres
+  // (diffusion_face, src/source.c:933-939) before every step unless it does not depend on t
+  Function * visc_fn[3] = { nullptr, nullptr, nullptr };
+  int visc_line[3] = { 0, 0, 0 };
+  gfship_field visc_dev[3][3] = { { -1, -1, -1 }, { -1, -1, -1 }, { -1, -1, -1 } };
+  gfship_field alpha_cell_dev = -1;      // alpha at the cell centres of every level (with a viscosity)
+  bool has_viscosity (int c) const { return visc[c] != 0. || visc_fn[c] != nullptr; }
   std::map<std::string, std::string> diff_set[3];
   std::vector<std::string> tracers;
   std::vector<int> tracer_gradient;              // 0 gfs_center_gradient, 1 van Leer (default)
@@ -703,15 +710,19 @@ void parse_object (Run & R, Reader & r)
     std::vector<std::string> comps;
     if (cls == "SourceDiffusion") comps.push_back (r.word (false));
     else { comps = { "U", "V" }; if (R.dim == 3) comps.push_back ("W"); }
+    const int fline = r.line ();
     FunctionText t = r.function ();
-    if (t.block || !Reader::is_number (t.text))
-      r.fail ("only a constant diffusion coefficient is supported");
+    /* a number keeps the constant-coefficient path; anything else is a GfsFunction of x, y, z, t */
+    const bool constant = !t.block && Reader::is_number (t.text);
+    Function * fn = constant ? nullptr : R.functions.add (t, fline);
     std::map<std::string, std::string> par;
     if (r.peek (false) == '{') read_multilevel (r, par);
     for (const std::string & v : comps) {
       int c = v == "U" ? 0 : v == "V" ? 1 : (v == "W" && R.dim == 3) ? 2 : -1;
       if (c < 0) r.fail ("diffusion is supported on the velocity components only (got `" + v + "')");
-      R.visc[c] = atof (t.text.c_str ());
+      R.visc[c] = constant ? atof (t.text.c_str ()) : 0.;
+      R.visc_fn[c] = fn;
+      R.visc_line[c] = fline;
       R.diff_set[c] = par;
     }
   }
@@ -1091,7 +1102,7 @@ void parse_object (Run & R, Reader & r)
 	// gfs_output_diffusion_stats_event, src/output.c:560-600
 	const char * names[3] = { "U", "V", "W" };
 	for (int c = 0; c < R.dim; c++)
-	  if (R.visc[c] != 0.) {
+	  if (R.has_viscosity (c)) {
 	    fprintf (fp, "%s diffusion\n", names[c]);
 	    stats_write (gfship_sim_diffusion_params (R.sim, c), fp);
 	  }
@@ -2133,6 +2144,93 @@ int refresh_alpha (Run & R)
   return 0;
 }
 
+// a GfsFunction of x, y, z, t at the centre of the + face along c of every leaf cell (the ghost entry in
+// front of the first cell: its - face): the layout of gfship_poisson_coefficients_alpha
+static void face_function_values (const Run & R, const Function * f, int c, std::vector<double> & a)
+{
+  const int n = R.n ();
+  const double h = 1./n;
+  std::fill (a.begin (), a.end (), 0.);
+  int lo[3] = { 1, 1, R.dim == 3 ? 1 : 0 }, hi[3] = { n, n, R.dim == 3 ? n : 0 };
+  lo[c] = 0;
+  for (int k = lo[2]; k <= hi[2]; k++)
+    for (int j = lo[1]; j <= hi[1]; j++)
+      for (int i = lo[0]; i <= hi[0]; i++) {
+	double p[3];
+	cell_pos (R, i, j, k, p);
+	p[c] += h/2.;
+	a[R.idx (i, j, k)] = f->kind == Function::CONSTANT ? f->val : f->fn (p[0], p[1], p[2], R.t, nullptr);
+      }
+}
+
+// GfsSourceDiffusion / GfsSourceViscosity with a function: gfs_function_face_value at every leaf face
+// (diffusion_face, src/source.c:933-939), evaluated the way refresh_alpha evaluates alpha; components that
+// share the function (GfsSourceViscosity) share the fields
+int refresh_viscosity (Run & R)
+{
+  std::vector<double> a;
+  for (int c = 0; c < R.dim; c++) {
+    const Function * f = R.visc_fn[c];
+    if (!f) continue;
+    const bool first = R.visc_dev[c][0] < 0;
+    if (!first && !(f->kind == Function::COMPILED && f->uses_t))
+      continue;                 /* static */
+    int shared = -1;
+    for (int q = 0; q < c; q++)
+      if (R.visc_fn[q] == f) shared = q;
+    if (shared < 0) {
+      a.resize (R.total ());
+      for (int q = 0; q < R.dim; q++) {
+	face_function_values (R, f, q, a);
+	if (first) {
+	  R.visc_dev[c][q] = gfship_field_alloc (R.dom, -1);
+	  CHECK (R.visc_dev[c][q]);
+	}
+	CHECK (gfship_field_upload (R.dom, R.visc_dev[c][q], R.level, a.data ()));
+      }
+    }
+    else if (first)
+      for (int q = 0; q < R.dim; q++) R.visc_dev[c][q] = R.visc_dev[shared][q];
+    if (first)
+      CHECK (gfship_sim_set_viscosity_faces (R.sim, c, R.visc_dev[c]));
+  }
+  return 0;
+}
+
+// alpha at the cell centres of EVERY level (gfs_function_value (alpha, cell) under FTT_TRAVERSE_ALL,
+// diffusion_mixed_coeff src/poisson.c:1321-1332): the density of the implicit diffusion
+int refresh_alpha_cell (Run & R)
+{
+  bool visc = false;
+  for (int c = 0; c < R.dim; c++) visc = visc || R.has_viscosity (c);
+  if (!R.alpha || !visc || (R.alpha_static && R.alpha_cell_dev >= 0))
+    return 0;
+  const Function * f = R.alpha;
+  const bool first = R.alpha_cell_dev < 0;
+  if (first) {
+    R.alpha_cell_dev = gfship_field_alloc (R.dom, -1);
+    CHECK (R.alpha_cell_dev);
+  }
+  for (int l = 0; l <= R.level; l++) {
+    const int n = 1 << l;
+    const size_t r = n + 2;
+    const double h = 1./n;
+    std::vector<double> a (R.dim == 3 ? r*r*r : r*r, 0.);
+    for (int k = R.dim == 3 ? 1 : 0; k <= (R.dim == 3 ? n : 0); k++)
+      for (int j = 1; j <= n; j++)
+	for (int i = 1; i <= n; i++) {
+	  /* ftt_cell_pos on the unit box centred on the origin */
+	  const double x = -0.5 + (i - 0.5)*h, y = -0.5 + (j - 0.5)*h, z = R.dim == 3 ? -0.5 + (k - 0.5)*h : 0.;
+	  a[i + r*(j + (R.dim == 3 ? r*(size_t) k : 0))] =
+	    f->kind == Function::CONSTANT ? f->val : f->fn (x, y, z, R.t, nullptr);
+	}
+    CHECK (gfship_field_upload (R.dom, R.alpha_cell_dev, l, a.data ()));
+  }
+  if (first)
+    CHECK (gfship_sim_set_alpha_cell (R.sim, R.alpha_cell_dev));
+  return 0;
+}
+
 int run (Run & R)
 {
   R.clock0 = std::chrono::steady_clock::now ();
@@ -2157,6 +2255,38 @@ int run (Run & R)
 	return 1;
       }
     R.alpha_static = used.empty () && !(R.alpha->kind == Function::COMPILED && R.alpha->uses_t);
+  }
+  bool any_visc = false;
+  for (int c = 0; c < R.dim; c++) {
+    any_visc = any_visc || R.has_viscosity (c);
+    const Function * f = R.visc_fn[c];
+    if (!f) continue;
+    if (R.tree_mode || R.sim_class != "Simulation") {
+      fprintf (stderr, "gfship: line %d: a diffusion coefficient given as a function is supported for a GfsSimulation "
+	       "on a uniform box\n", R.visc_line[c]);
+      return 1;
+    }
+    std::vector<int> used;
+    if (f->kind == Function::VARIABLE) used.push_back (f->var);
+    else if (f->kind == Function::COMPILED) used = f->args;
+    if (!used.empty ()) {
+      /* a coefficient that follows a tracer needs its coarse-cell values (gfs_cell_coarse_init) */
+      fprintf (stderr, "gfship: line %d: the diffusion coefficient may depend on x, y, z and t (got `%s')\n",
+	       R.visc_line[c], R.vars[used[0]].name.c_str ());
+      return 1;
+    }
+  }
+  if (R.alpha && any_visc && !R.tree_mode) {
+    std::vector<int> used;
+    if (R.alpha->kind == Function::VARIABLE) used.push_back (R.alpha->var);
+    else if (R.alpha->kind == Function::COMPILED) used = R.alpha->args;
+    if (!used.empty ()) {
+      /* the density of the diffusion equation is alpha on the cells of every level: a tracer's coarse-cell
+	 values would have to follow gfs_cell_coarse_init */
+      fprintf (stderr, "gfship: line %d: together with a SourceDiffusion alpha may depend on x, y, z and t (got `%s')\n",
+	       R.alpha_line, R.vars[used[0]].name.c_str ());
+      return 1;
+    }
   }
   if (R.tree_mode)
     return run_tree (R);
@@ -2198,11 +2328,16 @@ int run (Run & R)
   for (int c = 0; c < R.dim; c++)
     if (R.source[c] != 0.)
       CHECK (gfship_sim_set_source (R.sim, c, R.source[c]));
+  /* alpha at the cell centres first: with it a viscosity and alpha go together */
+  if (refresh_alpha_cell (R)) return 1;
   for (int c = 0; c < R.dim; c++)
     if (R.visc[c] != 0.) {
       CHECK (gfship_sim_set_viscosity (R.sim, c, R.visc[c]));
       apply_multilevel (gfship_sim_diffusion_params (R.sim, c), R.diff_set[c]);
     }
+    else if (R.visc_fn[c])
+      apply_multilevel (gfship_sim_diffusion_params (R.sim, c), R.diff_set[c]);
+  if (refresh_viscosity (R)) return 1;
   // the particle lists: created (and the previous velocity of the GfsForceCoeff objects stored)
   // while the fields still hold the zeros of a fresh simulation, like the reference, which reads
   // the list before any GfsInit event runs (gfs_force_coeff_read, :181-187)
@@ -2359,6 +2494,7 @@ int run (Run & R)
     CHECK (gfship_sim_set_time (R.sim, R.end, R.dtmax));
     CHECK (gfship_sim_set_next_event (R.sim, next_event_hook, &R));
     if (refresh_alpha (R)) return 1;
+    if (refresh_alpha_cell (R) || refresh_viscosity (R)) return 1;
     CHECK (gfship_sim_start (R.sim));
     if (R.alpha && !R.alpha_static) invalidate_device_copies (R);   /* the half step of the tracers */
     while (R.t < R.end && R.i < R.iend) {
@@ -2367,6 +2503,7 @@ int run (Run & R)
 	 iteration of the loop and stops at the next test of its condition */
       CHECK (gfship_sim_set_time (R.sim, R.end, R.dtmax));
       if (refresh_alpha (R)) return 1;
+      if (refresh_alpha_cell (R) || refresh_viscosity (R)) return 1;
       CHECK (gfship_sim_step (R.sim));
       R.t = gfship_sim_time (R.sim);
       R.i = gfship_sim_iter (R.sim);
@@ -2439,6 +2576,7 @@ int check (Run & R)
 	      eval (R, kv.second.val, p, -1));
   for (int c = 0; c < R.dim; c++)
     if (R.visc[c] != 0.) printf ("viscosity %d %g\n", c, R.visc[c]);
+    else if (R.visc_fn[c]) printf ("viscosity %d function\n", c);
   for (auto & e : R.events)
     printf ("event %s line %d start %g step %g istep %u end_event %d\n", e->cls.c_str (), e->line,
 	    e->start, e->step == DBL_MAX ? -1. : e->step, e->istep == INT_MAX ? 0 : e->istep,

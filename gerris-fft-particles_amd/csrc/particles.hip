@@ -683,7 +683,7 @@ using namespace gfship;
 
 extern "C" {
 
-struct gfship_sim_view { gfship_domain * dom; const gfship_field * u; double dt; double visc; };
+struct gfship_sim_view { gfship_domain * dom; const gfship_field * u; double dt; double visc; int visc_faces; };
 gfship_sim_view gfship_sim_view_get (gfship_sim * s);   /* simulation.hip */
 
 int gfship_particles_create (gfship_particles ** out, gfship_sim * sim, int np,
@@ -1156,6 +1156,9 @@ int gfship_particles_set_forces (gfship_particles * pl, int nforces, const int *
   GFSHIP_CHECK (pl && (nforces == 0 || kinds), GFSHIP_EINVAL, "null argument");
   GFSHIP_CHECK (pl->particulate, GFSHIP_EINVAL, "forces act on particulates (gfship_particles_set_particulate)");
   GFSHIP_CHECK (nforces >= 0 && nforces <= 8, GFSHIP_EINVAL, "at most 8 forces");
+  /* the drag laws take one viscosity (gfship_sim_set_viscosity of U) */
+  GFSHIP_CHECK (nforces == 0 || !gfship_sim_view_get (pl->sim).visc_faces, GFSHIP_EUNSUPPORTED,
+		"particle forces together with a viscosity that varies in space are not supported");
   bool coeff = false;
   for (int f = 0; f < nforces; f++)
     GFSHIP_CHECK (kinds[f] >= GFSHIP_FORCE_INERTIAL && kinds[f] <= GFSHIP_FORCE_BUOY, GFSHIP_EINVAL,
@@ -1266,6 +1269,8 @@ int gfship_particle_list_event (gfship_particles * pl)
   A.migrate = migrates;
   int block = 256, grid = (pl->n + block - 1)/block;
   if (pl->n > 0 && pl->particulate && pl->nforces > 0) {
+    GFSHIP_CHECK (!v.visc_faces, GFSHIP_EUNSUPPORTED,
+		  "particle forces together with a viscosity that varies in space are not supported");
     int r = particulate_event (pl, A, v.visc);
     if (r) return r;
     return migrates ? particles_migrate (pl) : GFSHIP_OK;

@@ -239,16 +239,9 @@ int gfship_poisson_coefficients_alpha (gfship_domain * dom, const gfship_field a
     if (!F) return GFSHIP_EINVAL;
     a[c] = F->lev[dom->depth];
   }
-  for (int d = 0; d < 2*dom->dim; d++)
-    if (dom->wf[d] < 0) {
-      dom->wf[d] = gfship_field_alloc (dom, -1);
-      if (dom->wf[d] < 0) return dom->wf[d];
-    }
-  for (int d = 0; d < 2*dom->dim; d++)
-    for (int l = 0; l <= dom->depth; l++)
-      dom->fields[dom->wf[d]].zero[l] = false;
-  int r = launch_poisson_weights (dom, a);
+  int r = alloc_weights (dom);
   if (r) return r;
+  if ((r = launch_poisson_weights (dom, a))) return r;
   dom->weighted = true;
   dom->weights_stamp++;         /* the skewed copies of the pipelined sweeps are stale */
   dom->unit_weights = true;     /* "coefficients have been set" for the checks of the entry points */
@@ -259,7 +252,8 @@ int gfship_poisson_weights (gfship_domain * dom, int d, gfship_field * w)
 {
   GFSHIP_CHECK (dom && w, GFSHIP_EINVAL, "null argument");
   GFSHIP_CHECK (d >= 0 && d < 2*dom->dim, GFSHIP_EINVAL, "direction %d out of range", d);
-  GFSHIP_CHECK (dom->weighted, GFSHIP_EINVAL, "call gfship_poisson_coefficients_alpha first");
+  GFSHIP_CHECK (dom->wf[d] >= 0 && (dom->weighted || (dom->diff_ready && dom->diff_kind == 3)), GFSHIP_EINVAL,
+		"call gfship_poisson_coefficients_alpha or gfship_diffusion_coefficients_faces first");
   *w = dom->wf[d];
   return GFSHIP_OK;
 }

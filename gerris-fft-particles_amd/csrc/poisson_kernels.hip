@@ -15,9 +15,10 @@ namespace gfship {
 // K1: relax / relax2D, src/poisson.c:507-557, with face_weighted_gradient's same-level branch
 // (src/fluid.c:858-864: g->a = w; g->b = w*u_nb) for w == 1.
 //
-// OP == 1 is diffusion_relax, src/poisson.c:1455-1484, with gfs_face_cm_weighted_gradient's
+// OP == 1 is diffusion_relax, src/poisson.c:1471-1498, with gfs_face_cm_weighted_gradient's
 // same-level branch (src/fluid.c:1361-1366: g->a = w; g->b = w*u_nb) for the uniform face
 // weight w of the level and h2 = h*h:  a = dia*h*h ; g.a = 1. + g.a/a ; u = (g.b/a + res)/g.a.
+// OP == 3 is the same cell update with the six face weights of the cell (OP == 2's arrays).
 // ---------------------------------------------------------------------------------------------
 struct W6 { const double * p[6]; };   // the six face weights f[d].v of a level (OP == 2)
 
@@ -41,6 +42,22 @@ __device__ __forceinline__ double relax_value (const double * __restrict__ u, lo
     if (dimension == 2)
       return a != 0. ? (1. - omega)*u[c] + omega*(b - rhs)/a : 0.;
     return a != 0. ? (b - rhs)/a : 0.;
+  }
+  if (OP == 3) {
+    // diffusion_relax (src/poisson.c:1471-1498) with the face weights of the cell
+    // (gfs_face_cm_weighted_gradient's same-level branch src/fluid.c:1361-1366: g.a = w, g.b = w*u_nb)
+    double ga = 0., gb = 0.;
+    { const double g = wf->p[0][c]; ga += g; gb += g*u[c + 1]; }
+    { const double g = wf->p[1][c]; ga += g; gb += g*u[c - 1]; }
+    { const double g = wf->p[2][c]; ga += g; gb += g*u[c + sy]; }
+    { const double g = wf->p[3][c]; ga += g; gb += g*u[c - sy]; }
+    if (DIM == 3) {
+      { const double g = wf->p[4][c]; ga += g; gb += g*u[c + sz]; }
+      { const double g = wf->p[5][c]; ga += g; gb += g*u[c - sz]; }
+    }
+    double a = dia*h2;
+    ga = 1. + ga/a;
+    return (gb/a + rhs)/ga;
   }
   if (OP == 1) {
     double ga = 0., gb = 0.;
@@ -154,12 +171,12 @@ relax_rows2d_kernel (Layout L, double omega, double w, double h2,
   auto clampi = [n] (int i) { return i < 0 ? 0 : i > n + 1 ? n + 1 : i; };
   // at step t: I = t - J; right = u (I + 2, j) = row[I + 3]; rhs, dia, ghost row at i = I + 1
   double pR[RX_D], pH[RX_D], pD[RX_D], pE[RX_D];
-  // OP == 2: the four face weights of the cell (rows of the natural arrays f[d].v)
+  // OP == 2, 3: the four face weights of the cell (rows of the natural arrays f[d].v)
   double pW[4][RX_D];
   const double * wrow[4];
 #pragma unroll
   for (int d = 0; d < 4; d++)
-    wrow[d] = OP == 2 ? wf.p[d] + L.idx (0, j, 0) - 1 : nullptr;
+    wrow[d] = OP >= 2 ? wf.p[d] + L.idx (0, j, 0) - 1 : nullptr;
 #pragma unroll
   for (int q = 0; q < RX_D; q++) {
     const int i = q - J + 1;
@@ -167,7 +184,7 @@ relax_rows2d_kernel (Layout L, double omega, double w, double h2,
     pH[q] = rrow[clampi (i) + 1];
     pD[q] = drow[clampi (i) + 1];
     pE[q] = erow ? erow[clampi (i) + 1] : 0.;
-    if (OP == 2) {
+    if (OP >= 2) {
 #pragma unroll
       for (int d = 0; d < 4; d++)
 	pW[d][q] = wrow[d][clampi (i) + 1];
@@ -189,7 +206,7 @@ relax_rows2d_kernel (Layout L, double omega, double w, double h2,
       const int rd = t & 1, wr = rd ^ 1;
       const double right = pR[q], rh = pH[q], di = pD[q], ex = pE[q];
       double w0 = 0., w1 = 0., w2 = 0., w3 = 0.;
-      if (OP == 2) { w0 = pW[0][q]; w1 = pW[1][q]; w2 = pW[2][q]; w3 = pW[3][q]; }
+      if (OP >= 2) { w0 = pW[0][q]; w1 = pW[1][q]; w2 = pW[2][q]; w3 = pW[3][q]; }
       // the loads of step t + RX_D
       {
 	const int i = I + RX_D + 1;
@@ -197,7 +214,7 @@ relax_rows2d_kernel (Layout L, double omega, double w, double h2,
 	pH[q] = rrow[clampi (i) + 1];
 	pD[q] = drow[clampi (i) + 1];
 	if (erow) pE[q] = erow[clampi (i) + 1];
-	if (OP == 2) {
+	if (OP >= 2) {
 #pragma unroll
 	  for (int d = 0; d < 4; d++)
 	    pW[d][q] = wrow[d][clampi (i) + 1];
@@ -218,14 +235,20 @@ relax_rows2d_kernel (Layout L, double omega, double w, double h2,
 	  ga = 1. + ga/a;
 	  v = (gb/a + rh)/ga;
 	}
-	else if (OP == 2) {
-	  // relax2D with the face weights of the cell (src/poisson.c:532-557, src/fluid.c:858-864)
-	  double a = di, b = 0.;
+	else if (OP >= 2) {
+	  // the face weights of the cell: relax2D (src/poisson.c:532-557, src/fluid.c:858-864) sums from dia,
+	  // diffusion_relax (OP == 3, src/poisson.c:1471-1498, src/fluid.c:1361-1366) from 0.
+	  double a = OP == 2 ? di : 0., b = 0.;
 	  a += w0; b += w0*right;
 	  a += w1; b += w1*left;
 	  a += w2; b += w2*top;
 	  a += w3; b += w3*bottom;
-	  v = a != 0. ? (1. - omega)*cur + omega*(b - rh)/a : 0.;
+	  if (OP == 3) {
+	    const double ar = di*h2;
+	    v = (b/ar + rh)/(1. + a/ar);
+	  }
+	  else
+	    v = a != 0. ? (1. - omega)*cur + omega*(b - rh)/a : 0.;
 	}
 	else {
 	  double a = di, b = 0.;
@@ -257,7 +280,10 @@ static int launch_relax_rows2d (gfship_domain * dom, int level, double omega, do
   const int block = L.n <= 64 ? 64 : L.n <= 128 ? 128 : L.n <= 256 ? 256 : L.n <= 512 ? 512 : 1024;
   W6 wf;
   for (int d = 0; d < 6; d++) wf.p[d] = op ? op->wf[d] : nullptr;
-  if (kind == 2)
+  if (kind == 3)
+    hipLaunchKernelGGL (relax_rows2d_kernel<3>, dim3 (1), dim3 (block), 0, dom->stream, L, omega, w, h2,
+			u, rhs, dia, wf);
+  else if (kind == 2)
     hipLaunchKernelGGL (relax_rows2d_kernel<2>, dim3 (1), dim3 (block), 0, dom->stream, L, omega, w, h2,
 			u, rhs, dia, wf);
   else if (kind)
@@ -291,8 +317,8 @@ int launch_relax_exact (gfship_domain * dom, unsigned dimension, int level, doub
   for (int p = 0; p < nplanes; p++) {
 #define HP_LAUNCH(D, O) hipLaunchKernelGGL ((relax_hyperplane_kernel<D, O>), dim3 (grid), dim3 (block), \
 					    0, dom->stream, L, p, dimension, omega, w, h2, u, rhs, dia, wf)
-    if (dom->dim == 3) { if (kind == 2) HP_LAUNCH (3, 2); else if (kind) HP_LAUNCH (3, 1); else HP_LAUNCH (3, 0); }
-    else               { if (kind == 2) HP_LAUNCH (2, 2); else if (kind) HP_LAUNCH (2, 1); else HP_LAUNCH (2, 0); }
+    if (dom->dim == 3) { if (kind == 3) HP_LAUNCH (3, 3); else if (kind == 2) HP_LAUNCH (3, 2); else if (kind) HP_LAUNCH (3, 1); else HP_LAUNCH (3, 0); }
+    else               { if (kind == 3) HP_LAUNCH (2, 3); else if (kind == 2) HP_LAUNCH (2, 2); else if (kind) HP_LAUNCH (2, 1); else HP_LAUNCH (2, 0); }
 #undef HP_LAUNCH
   }
   GFSHIP_HIP (hipGetLastError ());
@@ -384,9 +410,10 @@ relax_loop_lds_kernel (Layout L, BcDesc bc, unsigned dimension, double omega, do
 	  int i = I + 1, j = n - J, k = DIM == 3 ? n - K : 0;
 	  long c = i + ssy*j + ssz*k;
 	  long g = L.idx (i, j, k);
-	  if (OP == 2) {
-	    // the face weights of the cell live in the natural arrays (index g), u in LDS (index c)
-	    double a = dia[g], b = 0.;
+	  if (OP >= 2) {
+	    // the face weights of the cell live in the natural arrays (index g), u in LDS (index c): relax sums
+	    // from dia, diffusion_relax (OP == 3: the expressions of relax_value<DIM, 3>) from 0.
+	    double a = OP == 2 ? dia[g] : 0., b = 0.;
 	    { const double q = wf.p[0][g]; a += q; b += q*s[c + 1]; }
 	    { const double q = wf.p[1][g]; a += q; b += q*s[c - 1]; }
 	    { const double q = wf.p[2][g]; a += q; b += q*s[c + ssy]; }
@@ -395,8 +422,13 @@ relax_loop_lds_kernel (Layout L, BcDesc bc, unsigned dimension, double omega, do
 	      { const double q = wf.p[4][g]; a += q; b += q*s[c + ssz]; }
 	      { const double q = wf.p[5][g]; a += q; b += q*s[c - ssz]; }
 	    }
-	    s[c] = dimension == 2 ? (a != 0. ? (1. - omega)*s[c] + omega*(b - rhs[g])/a : 0.) :
-	      (a != 0. ? (b - rhs[g])/a : 0.);
+	    if (OP == 3) {
+	      const double ar = dia[g]*h2;
+	      s[c] = (b/ar + rhs[g])/(1. + a/ar);
+	    }
+	    else
+	      s[c] = dimension == 2 ? (a != 0. ? (1. - omega)*s[c] + omega*(b - rhs[g])/a : 0.) :
+		(a != 0. ? (b - rhs[g])/a : 0.);
 	  }
 	  else
 	    s[c] = relax_value<DIM, OP> (s, c, ssy, ssz, rhs[g], dia[g], dimension, omega, w, h2);
@@ -452,8 +484,8 @@ int launch_relax_loop_small (gfship_domain * dom, unsigned dimension, int level,
 #define LDS_LAUNCH(D, O) hipLaunchKernelGGL ((relax_loop_lds_kernel<D, O>), dim3 (1), dim3 (block), bytes, \
 					     dom->stream, L, bc, dimension, omega, w, h2, nrelax, \
 					     dp->lev[level], rhs, dia, wf)
-  if (dom->dim == 3) { if (kind == 2) LDS_LAUNCH (3, 2); else if (kind) LDS_LAUNCH (3, 1); else LDS_LAUNCH (3, 0); }
-  else               { if (kind == 2) LDS_LAUNCH (2, 2); else if (kind) LDS_LAUNCH (2, 1); else LDS_LAUNCH (2, 0); }
+  if (dom->dim == 3) { if (kind == 3) LDS_LAUNCH (3, 3); else if (kind == 2) LDS_LAUNCH (3, 2); else if (kind) LDS_LAUNCH (3, 1); else LDS_LAUNCH (3, 0); }
+  else               { if (kind == 3) LDS_LAUNCH (2, 3); else if (kind == 2) LDS_LAUNCH (2, 2); else if (kind) LDS_LAUNCH (2, 1); else LDS_LAUNCH (2, 0); }
 #undef LDS_LAUNCH
   GFSHIP_HIP (hipGetLastError ());
   *done = true;
@@ -1463,6 +1495,52 @@ weights_coarse_kernel (Layout Lc, Layout Lf, M6 wc, W6 wfine)
     wc.p[d][c] = neighbors == 1 ? 0. : s6[d];
 }
 
+// diffusion_coef (src/poisson.c:1280-1301): v = lambda2*dt*gfs_source_diffusion_face*face_fraction/
+// metric = 1.*cdt*D*1./1. ASSIGNED to f[d].v of the cells on both sides of the face; D[c] in the
+// layout of weights_leaf_kernel's alpha
+template <int DIM>
+__global__ void __launch_bounds__(256)
+diffusion_weights_leaf_kernel (Layout L, A3 D, double cdt, M6 w)
+{
+  CELL_LOOP_PROLOGUE (L);
+  const long off[3] = { 1, L.sy, L.sz };
+#pragma unroll
+  for (int cc = 0; cc < DIM; cc++) {
+    w.p[2*cc][c] = 1.*cdt*D.p[cc][c]*1./1.;
+    w.p[2*cc + 1][c] = 1.*cdt*D.p[cc][c - off[cc]]*1./1.;
+  }
+}
+
+static int launch_weights_coarse (gfship_domain * dom);
+
+int alloc_weights (gfship_domain * dom)
+{
+  for (int d = 0; d < 2*dom->dim; d++)
+    if (dom->wf[d] < 0) {
+      dom->wf[d] = gfship_field_alloc (dom, -1);
+      if (dom->wf[d] < 0) return dom->wf[d];
+    }
+  for (int d = 0; d < 2*dom->dim; d++)
+    for (int l = 0; l <= dom->depth; l++)
+      dom->fields[dom->wf[d]].zero[l] = false;
+  return GFSHIP_OK;
+}
+
+int launch_diffusion_weights (gfship_domain * dom, double * const D[3], double cdt)
+{
+  const int Ld = dom->depth;
+  const Layout & L = dom->lay[Ld];
+  dim3 grid, block;
+  cell_grid (L, &grid, &block);
+  A3 a;
+  M6 w;
+  for (int c = 0; c < 3; c++) a.p[c] = c < dom->dim ? D[c] : nullptr;
+  for (int d = 0; d < 6; d++) w.p[d] = d < 2*dom->dim ? dom->fields[dom->wf[d]].lev[Ld] : nullptr;
+  if (dom->dim == 3) hipLaunchKernelGGL (diffusion_weights_leaf_kernel<3>, grid, block, 0, dom->stream, L, a, cdt, w);
+  else               hipLaunchKernelGGL (diffusion_weights_leaf_kernel<2>, grid, block, 0, dom->stream, L, a, cdt, w);
+  return launch_weights_coarse (dom);
+}
+
 int launch_poisson_weights (gfship_domain * dom, double * const alpha[3])
 {
   const int Ld = dom->depth;
@@ -1477,6 +1555,13 @@ int launch_poisson_weights (gfship_domain * dom, double * const alpha[3])
     if (dom->dim == 3) hipLaunchKernelGGL (weights_leaf_kernel<3>, grid, block, 0, dom->stream, L, a, w);
     else               hipLaunchKernelGGL (weights_leaf_kernel<2>, grid, block, 0, dom->stream, L, a, w);
   }
+  return launch_weights_coarse (dom);
+}
+
+// face_coeff_from_below (src/poisson.c:826-853) on every non-leaf level, finest first
+static int launch_weights_coarse (gfship_domain * dom)
+{
+  const int Ld = dom->depth;
   for (int l = Ld - 1; l >= 0; l--) {
     const Layout & Lc = dom->lay[l], & Lf = dom->lay[l + 1];
     dim3 grid, block;

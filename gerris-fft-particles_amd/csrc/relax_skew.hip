@@ -565,7 +565,7 @@ int launch_relax_loop_skew (gfship_domain * dom, int level, Field * dp, Field * 
   if ((r = skew_plan (dom, level, &S))) return r;
   double * u = dp->lev[level];
   if ((r = skew_loop_trial (dom, level, S, nrelax, bc))) return r;
-  if (op && op->kind == 2) {
+  if (op && op->kind >= 2) {
     if ((r = skew_pack_weights (dom, level, S, op))) return r;
     dia_zero = false;           /* the weighted cell update always reads dia */
   }

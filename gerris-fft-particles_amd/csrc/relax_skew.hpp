@@ -93,9 +93,10 @@ struct SkewLoopArgs {
   int fault_tile;          // test of the error path (GFSHIP_FAULT_DROP_HANDOFF=tile): that tile publishes nothing in sweep 0
   int near_mode;           // stores towards a consumer on the same XCD: 0 agent scope like the others, 1 plain, 2 workgroup scope
   // cell update (RelaxOp): 0 = relax (src/poisson.c:507-530, unit weights), 1 = diffusion_relax
-  // (:1455-1484) with the uniform face weight w of the level and h2 = h*h; dia is then rhoc
+  // (:1471-1498) with the uniform face weight w of the level and h2 = h*h; dia is then rhoc
   // 2 = relax with the six face weights f[d].v of every cell (gfs_poisson_coefficients with a
   // GfsFunction alpha): ws[d] are skewed copies of the weights, streamed beside u / rhs / dia
+  // 3 = diffusion_relax with those six weights per cell (gfship_diffusion_coefficients_faces) and h2
   int op;
   double w, h2;
   const double * ws[6];
@@ -141,7 +142,7 @@ __device__ __forceinline__ double divide_by_6 (double x)
 int patch_loop_launch (gfship_domain * dom, const SkewLoopArgs & A, int ntiles, bool has_dia,
 		       unsigned nrelax, float * ms);
 
-// diffusion_relax of one cell, src/poisson.c:1455-1484 with gfs_face_cm_weighted_gradient's
+// diffusion_relax of one cell, src/poisson.c:1471-1498 with gfs_face_cm_weighted_gradient's
 // same-level branch (relax_value<3, 1> of poisson_kernels.hip): d = 0..5 = right, left, top, bottom,
 // front, back
 __device__ __forceinline__ double diffusion_cell (double right, double left, double top, double bottom,
@@ -158,6 +159,14 @@ __device__ __forceinline__ double diffusion_cell (double right, double left, dou
   const double a = dia*h2;
   ga = 1. + ga/a;
   return (gb/a + rhs)/ga;
+}
+
+// the same with the six face weights of the cell already summed in the order d = 0..5:
+// ga = sum g_d, gb = sum g_d*u_d
+__device__ __forceinline__ double diffusion_cell_faces (double ga, double gb, double rhs, double dia, double h2)
+{
+  const double a = dia*h2;
+  return (gb/a + rhs)/(1. + ga/a);
 }
 
 } // namespace gfship

@@ -80,18 +80,21 @@ __device__ __forceinline__ unsigned skew_claim_tile (const SkewLoopArgs & A)
 // dependent chain of a step; as register streams they cost the compute waves 290 spilled VGPRs)
 #define SK_WR 6              /* ring slots: divides the unroll factor SK_D of the step loop */
 #define SK_WD 5              /* rows ahead (<= SK_WR - 1; 12*(SK_WD - 1) < 64: the vmcnt counter) */
+// OP == 3 (diffusion_relax with the same six weights per cell, gfs_diffusion_coefficients with a
+// GfsSourceDiffusion that varies in space): the weights wave and the ring of OP == 2 unchanged, only the
+// cell update of the compute waves differs
 #define SK_WBYTES (SK_WR*6*SK_NL*sizeof (double))
 static_assert (SK_D % SK_WR == 0, "slot numbers of the weight ring must be compile-time constants");
 
 template <bool HAS_DIA, int OP>
-__global__ void __launch_bounds__(OP == 2 ? SK_NTHREADS + 64 : SK_NTHREADS)
+__global__ void __launch_bounds__(OP >= 2 ? SK_NTHREADS + 64 : SK_NTHREADS)
 relax_skew_loop_kernel (SkewLoopArgs A)
 {
   constexpr int XS = SK_T + 1;
   __shared__ double X[2][XS*XS];
   __shared__ double Y[2][XS*XS];
   __shared__ unsigned s_tile;
-  extern __shared__ double wring[];      // OP == 2: [SK_WR][6][SK_NL] face weights of the rows t .. t + SK_WD
+  extern __shared__ double wring[];      // OP >= 2: [SK_WR][6][SK_NL] face weights of the rows t .. t + SK_WD
 
   const int tid0 = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane (tid0 >> 6);                   // wave-uniform
@@ -116,7 +119,7 @@ relax_skew_loop_kernel (SkewLoopArgs A)
 
   double * const ut = A.us + tile*tstride + SK_FP*SK_NL;
   const bool loader = wave == SK_NL/64, storer = wave == SK_NL/64 + 1;
-  const bool weigher = OP == 2 && wave == SK_NL/64 + 2;
+  const bool weigher = OP >= 2 && wave == SK_NL/64 + 2;
 #if SK_EXP & 4
   if (compute) __builtin_amdgcn_s_setprio (3);     /* experiment: compute waves first on their SIMD */
 #endif
@@ -394,10 +397,12 @@ relax_skew_loop_kernel (SkewLoopArgs A)
 	  aa += 1.; bb += 1.*Bo;
 	  aa += 1.; bb += 1.*Fn;
 	  aa += 1.; bb += 1.*Bk;
-	  if (OP == 2) {
-	    // relax with the face weights of the cell (src/poisson.c:507-530, face_weighted_gradient's
-	    // same-level branch src/fluid.c:858-864: g.a = w, g.b = w*u_nb), d = 0..5
-	    aa = pDia[q]; bb = 0.;
+	  if (OP >= 2) {
+	    // the face weights of the cell, d = 0..5 (g.a = w, g.b = w*u_nb): relax (src/poisson.c:507-530,
+	    // face_weighted_gradient's same-level branch src/fluid.c:858-864) starts its sum from dia;
+	    // diffusion_relax (OP == 3, src/poisson.c:1471-1498, gfs_face_cm_weighted_gradient's same-level
+	    // branch src/fluid.c:1361-1366) from 0. and takes its quotients in diffusion_cell_faces
+	    aa = OP == 2 ? pDia[q] : 0.; bb = 0.;
 	    const double * const wl = wring + (q % SK_WR)*(6*SK_NL) + tid;      // slot of row t
 	    { const double g = wl[0*SK_NL]; aa += g; bb += g*Rv; }
 	    { const double g = wl[1*SK_NL]; aa += g; bb += g*prev; }
@@ -406,7 +411,8 @@ relax_skew_loop_kernel (SkewLoopArgs A)
 	    { const double g = wl[4*SK_NL]; aa += g; bb += g*Fn; }
 	    { const double g = wl[5*SK_NL]; aa += g; bb += g*Bk; }
 	  }
-	  const double v = OP == 1 ? diffusion_cell (Rv, prev, Tn, Bo, Fn, Bk, pRhs[q], pDia[q], A.w, A.h2) :
+	  const double v = OP == 3 ? diffusion_cell_faces (aa, bb, pRhs[q], pDia[q], A.h2) :
+	    OP == 1 ? diffusion_cell (Rv, prev, Tn, Bo, Fn, Bk, pRhs[q], pDia[q], A.w, A.h2) :
 	    HAS_DIA ? (aa != 0. ? (bb - pRhs[q])/aa : 0.) : divide_by_6 (bb - pRhs[q]);
 	  prev = act ? v : prev;
 	  first = I == 0 ? v : first;
@@ -837,6 +843,13 @@ static int skew_loop_resident (gfship_domain * dom, int level)
       dom->patch_resident = 0;
     }
     else {
+      int per_cu_3 = 0;
+      if (hipFuncSetAttribute ((const void *) relax_skew_loop_kernel<true, 3>,
+			       hipFuncAttributeMaxDynamicSharedMemorySize, SK_WBYTES) != hipSuccess ||
+	  hipOccupancyMaxActiveBlocksPerMultiprocessor (&per_cu_3, relax_skew_loop_kernel<true, 3>,
+							SK_NTHREADS + 64, SK_WBYTES) != hipSuccess)
+	per_cu_3 = 0;
+      if (per_cu_3 < per_cu_2) per_cu_2 = per_cu_3;
       if (per_cu_2 < per_cu) per_cu = per_cu_2;
       dom->skew_resident = (per_cu < per_cu_w ? per_cu : per_cu_w)*prop.multiProcessorCount;
       dom->patch_resident = patch_resident_per_cu (dom)*prop.multiProcessorCount;
@@ -921,9 +934,9 @@ int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat,
 {
   const Layout & L = dom->lay[level];
   int ntiles = S->ntj*S->ntj;
-  GFSHIP_CHECK (!op || op->kind == 0 || ((op->kind == 1 || op->kind == 2) && has_dia), GFSHIP_EUNSUPPORTED,
+  GFSHIP_CHECK (!op || op->kind == 0 || (op->kind >= 1 && op->kind <= 3 && has_dia), GFSHIP_EUNSUPPORTED,
 		"the pipelined sweep knows the Poisson (unit or per-face weights) and the diffusion cell updates");
-  GFSHIP_CHECK (!op || op->kind != 2 || (S->ws[0] && !patch_level (dom, level)), GFSHIP_EINVAL,
+  GFSHIP_CHECK (!op || op->kind < 2 || (S->ws[0] && !patch_level (dom, level)), GFSHIP_EINVAL,
 		"weighted sweep without the skewed copies of the face weights");
   /* 8 words in front of the granules: the ticket counter, armed with them (it then counts from all
      ones: the claims add one).  Two sets of granules used in turn.  With GFSHIP_KERNEL_ARMING=1 the
@@ -1049,6 +1062,16 @@ int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat,
       attr = true;
     }
     hipLaunchKernelGGL ((relax_skew_loop_kernel<true, 2>), dim3 (ntiles), dim3 (SK_NTHREADS + 64), SK_WBYTES,
+			dom->stream, A);
+  }
+  else if (A.op == 3) {                              /* diffusion_relax with the face weights of every cell */
+    static bool attr3 = false;
+    if (!attr3) {
+      GFSHIP_HIP (hipFuncSetAttribute ((const void *) relax_skew_loop_kernel<true, 3>,
+				       hipFuncAttributeMaxDynamicSharedMemorySize, SK_WBYTES));
+      attr3 = true;
+    }
+    hipLaunchKernelGGL ((relax_skew_loop_kernel<true, 3>), dim3 (ntiles), dim3 (SK_NTHREADS + 64), SK_WBYTES,
 			dom->stream, A);
   }
   else if (dom->sw.wave_loop && nrelax >= 2 && !has_dia)     /* one compute wave per tile */

@@ -27,6 +27,16 @@ struct gfship_sim {
   // layout gfship_poisson_coefficients_alpha takes (gfship_sim_set_alpha); has_alpha = false: alpha = NULL
   gfship_field alpha[3] = {-1, -1, -1};
   bool has_alpha = false;
+  // GfsSourceDiffusion with a coefficient that varies in space: gfs_source_diffusion_face on the faces
+  // normal to each direction, by handle like alpha (gfship_sim_set_viscosity_faces)
+  gfship_field viscf[3][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};
+  bool has_viscf[3] = {false, false, false};
+  // alpha at the cell centres of every level (gfship_sim_set_alpha_cell): the density of the implicit
+  // diffusion (rhoc = 1./alpha) and the factor of its MAC source
+  gfship_field alpha_cell = -1;
+  bool has_alpha_cell = false;
+  gfship_field dconst[3] = {-1, -1, -1};   // a constant coefficient as face fields, where alpha_cell asks for the per-face path
+  gfship_field msrc[3] = {-1, -1, -1};     // per-cell MAC source of the implicit diffusion of U, V, W
   gfship_multilevel_params diffusion_params[3];
   gfship_field drhs = -1, rhoc = -1;   // temporaries of variable_diffusion
   bool cfl_ready = false;              // maxima for the CFL condition left by the last projection
@@ -64,6 +74,69 @@ void ptrs6 (gfship_sim * s, double * out[6])
 }
 
 #define TRY(x) do { int r_ = (x); if (r_ != GFSHIP_OK) return r_; } while (0)
+
+// the implicit diffusion runs with per-face coefficients and the density of alpha_cell: the advection then
+// takes the general path (face-value arrays + flux kernel) with the MAC source read from an array
+inline bool diffusion_faces (const gfship_sim * s)
+{
+  return s->has_alpha_cell || s->has_viscf[0] || s->has_viscf[1] || s->has_viscf[2];
+}
+
+inline bool has_viscosity (const gfship_sim * s, int c)
+{
+  return s->visc[c] != 0. || s->has_viscf[c];
+}
+
+// the coefficient of component c at the faces: the caller's fields, or a constant one written into fields
+int diffusion_face_fields (gfship_sim * s, int c, gfship_field D[3])
+{
+  gfship_domain * dom = s->dom;
+  for (int q = 0; q < 3; q++) D[q] = -1;
+  if (s->has_viscf[c]) {
+    for (int q = 0; q < dom->dim; q++) D[q] = s->viscf[c][q];
+    return GFSHIP_OK;
+  }
+  for (int q = 0; q < dom->dim; q++) {
+    if (s->dconst[q] < 0)
+      s->dconst[q] = gfship_field_alloc (dom, -1);
+    if (s->dconst[q] < 0) return s->dconst[q];
+    int r = gfship_field_fill (dom, s->dconst[q], dom->depth, s->visc[c]);
+    if (r) return r;
+    D[q] = s->dconst[q];
+  }
+  return GFSHIP_OK;
+}
+
+// gfs_variable_mac_source of velocity component c (source_diffusion_value, src/source.c:1105-1144) into out
+int variable_mac_source (gfship_sim * s, int c, gfship_field out)
+{
+  gfship_domain * dom = s->dom;
+  gfship_field D[3];
+  int r = diffusion_face_fields (s, c, D);
+  if (r) return r;
+  double * d[3] = { nullptr, nullptr, nullptr };
+  for (int q = 0; q < dom->dim; q++) d[q] = dom->fields[D[q]].lev[dom->depth];
+  dom->fields[out].zero[dom->depth] = false;
+  return launch_variable_mac_source (dom, dom->fields[s->u[c]].lev[dom->depth], d,
+				     s->has_alpha_cell ? dom->fields[s->alpha_cell].lev[dom->depth] : nullptr,
+				     dom->fields[out].lev[dom->depth]);
+}
+
+// the array the general advection path reads the MAC source of component c from (nullptr: none, or the
+// constant-coefficient expression inside the kernels)
+int mac_source_array (gfship_sim * s, int c, const double ** out)
+{
+  *out = nullptr;
+  if (!diffusion_faces (s) || !has_viscosity (s, c))
+    return GFSHIP_OK;
+  if (s->msrc[c] < 0)
+    s->msrc[c] = gfship_field_alloc (s->dom, -1);
+  if (s->msrc[c] < 0) return s->msrc[c];
+  int r = variable_mac_source (s, c, s->msrc[c]);
+  if (r) return r;
+  *out = s->dom->fields[s->msrc[c]].lev[s->dom->depth];
+  return GFSHIP_OK;
+}
 
 int bc_leaf (gfship_sim * s, gfship_field v)
 {
@@ -123,7 +196,7 @@ int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, g
   /* MAC divergence, scaled by 1/dt (approximate projection: together with the MAC velocities
      interpolated from the centred ones, gfs_approximate_projection src/timestep.c:572-580) */
   for (int c = 0; c < dom->dim; c++)
-    if (s->visc[c] != 0. || dom->src[c] != 0.) lazy = false;   /* the CFL needs the full kernel then */
+    if (has_viscosity (s, c) || dom->src[c] != 0.) lazy = false;   /* the CFL needs the full kernel then */
   if (!approximate || !s->tracers.empty () || s->un_handle_given || p != s->p || !dom->sw.lazy_un)
     lazy = false;
   if (!approximate)
@@ -146,7 +219,7 @@ int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, g
   s->cfl_ready = false;
   bool want_max = approximate;
   for (int c = 0; c < dom->dim; c++)
-    if (s->visc[c] != 0. || dom->src[c] != 0.) want_max = false;   /* the acceleration term needs the full kernel */
+    if (has_viscosity (s, c) || dom->src[c] != 0.) want_max = false;   /* the acceleration term needs the full kernel */
   if (s->has_alpha) {
     /* the same pass with gfs_face_weighted_gradient's weights (the CFL maxima come from their own pass) */
     want_max = false;
@@ -217,13 +290,15 @@ int face_values_set (gfship_sim * s, gfship_field v, double dt, int use_centered
   ptrs6 (s, fv);
   /* v->sources: the implicit diffusion of a velocity component acts as MAC source */
   double visc = 0., gsrc = 0.;
+  const double * msrc = nullptr;
   for (int c = 0; c < s->dom->dim; c++)
     if (v == s->u[c]) {
       visc = s->visc[c];
       gsrc = s->dom->src[c];     /* ... and the intensity of a GfsSource on it */
+      TRY (mac_source_array (s, c, &msrc));   /* coefficient at the faces, alpha: from an array */
     }
   TRY (launch_advected_face_values (s->dom, leaf (s, v), u, un, dt, use_centered, gradient, fv, cmask,
-				    visc, gsrc));
+				    visc, gsrc, msrc));
   TRY (launch_face_bc (s->dom, get_field (s->dom, v), fv, cmask));
   return GFSHIP_OK;
 }
@@ -236,7 +311,8 @@ int variable_sources (gfship_sim * s, gfship_field v, gfship_field sv, int gradi
   ptrs3 (s, s->un, un);
   ptrs6 (s, fv);
   int c = s->dom->fields[v].component;
-  if (godunov_fused_supported (s->dom) && gradient <= 1) {      /* limiters 2 .. 4: the general path */
+  if (godunov_fused_supported (s->dom) && gradient <= 1 &&      /* limiters 2 .. 4: the general path */
+      !(velocity && diffusion_faces (s))) {                     /* ... and the MAC source from an array */
     /* periodic box: face values recomputed inside the flux kernel, no face-value arrays */
     gfship_domain * dom = s->dom;
     const int L = dom->depth;
@@ -284,7 +360,14 @@ int variable_diffusion (gfship_sim * s, int c, gfship_field rhs)
   if (s->rhoc < 0)
     s->rhoc = gfship_field_alloc (dom, -1);
   if (s->rhoc < 0) return s->rhoc;
-  TRY (gfship_diffusion_coefficients (dom, s->visc[c], dt, s->rhoc, par->beta));
+  if (diffusion_faces (s)) {
+    gfship_field D[3];
+    TRY (diffusion_face_fields (s, c, D));
+    TRY (gfship_diffusion_coefficients_faces (dom, D, dt, s->rhoc, s->has_alpha_cell ? s->alpha_cell : -1,
+					      par->beta));
+  }
+  else
+    TRY (gfship_diffusion_coefficients (dom, s->visc[c], dt, s->rhoc, par->beta));
   TRY (gfship_diffusion_rhs (dom, s->u[c], rhs, s->rhoc, par->beta));
   TRY (gfship_diffusion (dom, par, s->u[c], rhs, s->rhoc));
   return GFSHIP_OK;
@@ -304,10 +387,11 @@ int advance_tracers (gfship_sim * s, double dt)
 extern "C" {
 
 /* internal view of a simulation for particles.hip */
-struct gfship_sim_view { gfship_domain * dom; const gfship_field * u; double dt; double visc; };
+struct gfship_sim_view { gfship_domain * dom; const gfship_field * u; double dt; double visc; int visc_faces; };
 gfship_sim_view gfship_sim_view_get (gfship_sim * s)
 {
-  gfship_sim_view v = { s->dom, s->u, s->advection_params.dt, s->visc[0] };
+  gfship_sim_view v = { s->dom, s->u, s->advection_params.dt, s->visc[0],
+			s->has_viscf[0] || s->has_viscf[1] || s->has_viscf[2] };
   return v;
 }
 
@@ -366,7 +450,7 @@ void gfship_sim_destroy (gfship_sim * s)
   for (int c = 0; c < 3; c++) { fr (s->u[c]); fr (s->g[c]); fr (s->gmac[c]); fr (s->un[c]); }
   for (int d = 0; d < 6; d++) fr (s->fv[d]);
   fr (s->dia); fr (s->div); fr (s->res); fr (s->drhs); fr (s->rhoc); fr (s->adv_tmp);
-  for (int c = 0; c < 3; c++) fr (s->adv_tmp3[c]);
+  for (int c = 0; c < 3; c++) { fr (s->adv_tmp3[c]); fr (s->dconst[c]); fr (s->msrc[c]); }
   for (gfship_field t : s->tracers) fr (t);
   delete s;
 }
@@ -433,9 +517,10 @@ int gfship_sim_set_alpha (gfship_sim * s, const gfship_field alpha[3])
     s->alpha[c] = alpha[c];
   }
   for (int c = 0; c < s->dom->dim; c++)
-    GFSHIP_CHECK (s->visc[c] == 0., GFSHIP_EUNSUPPORTED,
+    GFSHIP_CHECK (!has_viscosity (s, c) || s->has_alpha_cell, GFSHIP_EUNSUPPORTED,
 		  "GfsSourceDiffusion together with GfsPhysicalParams { alpha } (gfs_diffusion_coefficients "
-		  "with a variable density, src/poisson.c:1280-1348) is not supported");
+		  "with a variable density, src/poisson.c:1280-1348) needs alpha at the cell centres of every "
+		  "level: call gfship_sim_set_alpha_cell first");
   s->has_alpha = true;
   s->cfl_ready = false;
   return GFSHIP_OK;
@@ -446,10 +531,68 @@ int gfship_sim_set_viscosity (gfship_sim * s, int c, double nu)
   GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
   GFSHIP_CHECK (c >= 0 && c < s->dom->dim, GFSHIP_EINVAL, "component %d out of range", c);
   GFSHIP_CHECK (nu >= 0., GFSHIP_EINVAL, "the diffusion coefficient must be positive");
-  GFSHIP_CHECK (nu == 0. || !s->has_alpha, GFSHIP_EUNSUPPORTED,
-		"GfsSourceDiffusion together with GfsPhysicalParams { alpha } is not supported");
+  GFSHIP_CHECK (nu == 0. || !s->has_alpha || s->has_alpha_cell, GFSHIP_EUNSUPPORTED,
+		"GfsSourceDiffusion together with GfsPhysicalParams { alpha } needs alpha at the cell centres "
+		"of every level: call gfship_sim_set_alpha_cell first");
   s->visc[c] = nu;
+  if (nu != 0.)
+    s->has_viscf[c] = false;      /* one GfsSourceDiffusion per component: the last call holds */
   return GFSHIP_OK;
+}
+
+int gfship_sim_set_viscosity_faces (gfship_sim * s, int c, const gfship_field D[3])
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
+  GFSHIP_CHECK (c >= 0 && c < s->dom->dim, GFSHIP_EINVAL, "component %d out of range", c);
+  if (!D) {
+    s->has_viscf[c] = false;
+    s->cfl_ready = false;
+    return GFSHIP_OK;
+  }
+  GFSHIP_CHECK (!s->dom->has_external, GFSHIP_EUNSUPPORTED,
+		"a diffusion coefficient that varies in space on a box with MPI sides is not supported");
+  GFSHIP_CHECK (!s->has_alpha || s->has_alpha_cell, GFSHIP_EUNSUPPORTED,
+		"GfsSourceDiffusion together with GfsPhysicalParams { alpha } needs alpha at the cell centres "
+		"of every level: call gfship_sim_set_alpha_cell first");
+  for (int q = 0; q < s->dom->dim; q++)
+    GFSHIP_CHECK (get_field (s->dom, D[q]) != nullptr, GFSHIP_EINVAL, "D[%d] is not a field of the domain", q);
+  for (int q = 0; q < s->dom->dim; q++)
+    s->viscf[c][q] = D[q];
+  s->has_viscf[c] = true;
+  s->visc[c] = 0.;                /* ... and replaces a constant coefficient of the component */
+  s->cfl_ready = false;
+  return GFSHIP_OK;
+}
+
+int gfship_sim_set_alpha_cell (gfship_sim * s, gfship_field alpha_cell)
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
+  if (alpha_cell == -1) {
+    bool visc = false;
+    for (int c = 0; c < s->dom->dim; c++) visc = visc || has_viscosity (s, c);
+    GFSHIP_CHECK (!(s->has_alpha && visc), GFSHIP_EUNSUPPORTED,
+		  "GfsSourceDiffusion together with GfsPhysicalParams { alpha } needs alpha at the cell centres");
+    s->has_alpha_cell = false;
+    s->cfl_ready = false;
+    return GFSHIP_OK;
+  }
+  GFSHIP_CHECK (!s->dom->has_external, GFSHIP_EUNSUPPORTED,
+		"a variable density in the implicit diffusion on a box with MPI sides is not supported");
+  GFSHIP_CHECK (get_field (s->dom, alpha_cell) != nullptr, GFSHIP_EINVAL, "alpha_cell is not a field of the domain");
+  s->alpha_cell = alpha_cell;
+  s->has_alpha_cell = true;
+  s->cfl_ready = false;
+  return GFSHIP_OK;
+}
+
+int gfship_variable_mac_source (gfship_sim * s, int c, gfship_field out)
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
+  GFSHIP_CHECK (c >= 0 && c < s->dom->dim, GFSHIP_EINVAL, "component %d out of range", c);
+  GFSHIP_CHECK (get_field (s->dom, out) != nullptr, GFSHIP_EINVAL, "out is not a field of the domain");
+  GFSHIP_CHECK (has_viscosity (s, c), GFSHIP_EINVAL, "component %d has no GfsSourceDiffusion", c);
+  TRY (before_write (s->dom));
+  return variable_mac_source (s, c, out);
 }
 
 gfship_multilevel_params * gfship_sim_diffusion_params (gfship_sim * s, int c)
@@ -491,7 +634,7 @@ static int predicted_face_velocities (gfship_sim * s, double mac_dt)
   /* the reset of every face (gfs_face_reset_normal_velocity) is implied: each component's
      faces are all overwritten below */
   if ((godunov_fused_supported (s->dom) || godunov_fused_mpi_supported (s->dom)) &&
-      s->advection_params.gradient <= 1) {
+      s->advection_params.gradient <= 1 && !diffusion_faces (s)) {
     double * u[3], * un[3];
     ptrs3 (s, s->u, u);
     ptrs3 (s, s->un, un);
@@ -557,7 +700,7 @@ static int centered_velocity_advection (gfship_sim * s, const gfship_field gmac[
   if (corrected) *corrected = false;
   if (u_coarse) *u_coarse = false;
   if (s->dom->dim == 3 && (godunov_fused_supported (s->dom) || godunov_fused_mpi_supported (s->dom)) &&
-      s->dom->sw.advect3 && s->advection_params.gradient <= 1 &&
+      s->dom->sw.advect3 && s->advection_params.gradient <= 1 && !diffusion_faces (s) &&
       s->visc[0] == 0. && s->visc[1] == 0. && s->visc[2] == 0.) {
     /* the three components in one pass over the box (same MAC velocities, nothing of one component
        feeds another): into scratch leaf levels, then the storage is swapped */
@@ -598,7 +741,7 @@ static int centered_velocity_advection (gfship_sim * s, const gfship_field gmac[
     return GFSHIP_OK;
   }
   for (int c = 0; c < s->dom->dim; c++) {
-    if (s->visc[c] != 0.) {
+    if (has_viscosity (s, c)) {
       /* source_diffusion (v[c]): rhs = copy of v on the leaves, sources into rhs, implicit
 	 solve (src/timestep.c:996-1007) */
       gfship_domain * dom = s->dom;
@@ -651,6 +794,18 @@ int gfship_tracer_advection (gfship_sim * s, gfship_field t, double dt)
   return GFSHIP_OK;
 }
 
+// gfs_domain_cfl with the acceleration time scale of the sources of U, V, W (src/domain.c:2893-2901)
+static int cfl_full (gfship_sim * s, double * const u[3], double * const un[3], double * c2)
+{
+  double * msrc[3] = { nullptr, nullptr, nullptr };
+  for (int c = 0; c < s->dom->dim; c++) {
+    const double * m;
+    TRY (mac_source_array (s, c, &m));
+    msrc[c] = const_cast<double *> (m);
+  }
+  return launch_cfl (s->dom, u, un, s->visc, c2, msrc);
+}
+
 static int domain_cfl (gfship_sim * s, double * cfl, bool cached)
 {
   double * u[3], * un[3];
@@ -661,7 +816,7 @@ static int domain_cfl (gfship_sim * s, double * cfl, bool cached)
     TRY (launch_cfl_from_max (s->dom, &c2));
   else {
     TRY (materialize_un (s));
-    TRY (launch_cfl (s->dom, u, un, s->visc, &c2));
+    TRY (cfl_full (s, u, un, &c2));
   }
   s->cfl_ready = false;
   *cfl = sqrt (c2);
@@ -677,7 +832,7 @@ int gfship_domain_cfl (gfship_sim * s, double * cfl)
   double c2;
   s->cfl_ready = false;
   TRY (materialize_un (s));
-  TRY (launch_cfl (s->dom, u, un, s->visc, &c2));
+  TRY (cfl_full (s, u, un, &c2));
   *cfl = sqrt (c2);
   return GFSHIP_OK;
 }

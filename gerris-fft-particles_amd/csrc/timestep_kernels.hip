@@ -771,11 +771,36 @@ __device__ __forceinline__ double source_diffusion_value (const double * __restr
   return 1.*(gb - ga*v0)*rh2;
 }
 
+// source_diffusion_value, src/source.c:1105-1144, of every leaf cell with a diffusion coefficient given
+// at the faces (gfs_source_diffusion_face, :933-939: D[cc] holds the + face of a cell along cc, the entry
+// in front of it its - face) and GfsPhysicalParams { alpha } at the cell centres (nullptr: 1.):
+//   g.a += D*e.a ; g.b += D*e.b over d = 0 .. 2 DIM - 1 ; alpha*(g.b - g.a*v0)/(h*h)
+template <int DIM>
+__global__ void __launch_bounds__(256)
+variable_mac_source_kernel (Layout L, const double * __restrict__ v, CPtr3 D,
+			    const double * __restrict__ alpha, double * __restrict__ out)
+{
+  CELL_PROLOGUE (L);
+  const long off[3] = { 1, L.sy, L.sz };
+  /* h = 1/n is a power of two: the division by h*h is an exact scaling by n*n */
+  const double rh2 = (double) L.n*(double) L.n;
+  double ga = 0., gb = 0.;
+  const double v0 = v[c];
+#pragma unroll
+  for (int cc = 0; cc < DIM; cc++) {
+    { const double Df = D.p[cc][c]; ga += Df*1.; gb += Df*v[c + off[cc]]; }
+    { const double Df = D.p[cc][c - off[cc]]; ga += Df*1.; gb += Df*v[c - off[cc]]; }
+  }
+  out[c] = (alpha ? alpha[c] : 1.)*(gb - ga*v0)*rh2;
+}
+
+// msrc_cell != nullptr: the MAC source of the implicit diffusion comes from this array
+// (variable_mac_source_kernel) instead of the constant coefficient visc
 template <int DIM>
 __global__ void __launch_bounds__(256)
 advected_face_values_kernel (Layout L, const double * __restrict__ v, CPtr3 u, CPtr3 un,
 			     double dt, int use_centered_velocity, int gradient, Ptr6 fv, int cmask,
-			     double visc, double gsrc)
+			     double visc, double gsrc, const double * __restrict__ msrc_cell)
 {
   CELL_PROLOGUE (L);
   const long off[3] = { 1, L.sy, L.sz };
@@ -807,7 +832,9 @@ advected_face_values_kernel (Layout L, const double * __restrict__ v, CPtr3 u, C
     double vr = v0 + GMAX ((- 1. - unorm)/2., -0.5)*g;
     /* gfs_variable_mac_source, src/source.c:38-59 */
     double msrc = 0.;
-    if (visc != 0.)
+    if (msrc_cell)
+      msrc = 0. + msrc_cell[c];
+    else if (visc != 0.)
       msrc = 0. + source_diffusion_value<DIM> (v, c, off, visc, L.n);
     msrc += gsrc;               /* the intensity of a GfsSource (source_value, src/source.c:398-403) */
     double src = dt*msrc/2.;
@@ -2799,7 +2826,7 @@ __device__ __forceinline__ double wave_min (double v)
 
 template <int DIM>
 __global__ void __launch_bounds__(256)
-cfl_partial_kernel (Layout L, CPtr3 u, CPtr3 un, Visc3 visc, double * __restrict__ partial)
+cfl_partial_kernel (Layout L, CPtr3 u, CPtr3 un, Visc3 visc, CPtr3 msrc, double * __restrict__ partial)
 {
   const int n = L.n;
   const double length = 1./n;
@@ -2828,11 +2855,12 @@ cfl_partial_kernel (Layout L, CPtr3 u, CPtr3 un, Visc3 visc, double * __restrict
 	  double cflu = length/fabs (1.*uv);
 	  m = fmin (m, cflu*cflu);
 	}
-	if ((visc.d[cc] != 0. || visc.g[cc] != 0.) && i <= n && j <= n && (DIM == 2 || k <= n)) {
+	if ((visc.d[cc] != 0. || visc.g[cc] != 0. || msrc.p[cc]) && i <= n && j <= n && (DIM == 2 || k <= n)) {
 	  /* p->v[c]->sources: acceleration time scale, src/domain.c:2893-2901 (gfs_variable_mac_source:
 	     the explicit diffusion term, then the intensity of a GfsSource) */
 	  double g = 0.;
-	  if (visc.d[cc] != 0.) g += source_diffusion_value<DIM> (u.p[cc], c, off, visc.d[cc], n);
+	  if (msrc.p[cc]) g += msrc.p[cc][c];      /* variable_mac_source_kernel: coefficient at the faces, alpha */
+	  else if (visc.d[cc] != 0.) g += source_diffusion_value<DIM> (u.p[cc], c, off, visc.d[cc], n);
 	  if (visc.g[cc] != 0.) g += visc.g[cc];
 	  if (g != 0.) {
 	    double cflg = 2.*length/fabs (1.*g);
@@ -2983,13 +3011,23 @@ int launch_correct_centered_coarse (gfship_domain * dom, double * const u[3], do
 
 int launch_advected_face_values (gfship_domain * dom, const double * v, double * const u[3],
 				 double * const un[3], double dt, int use_centered, int gradient,
-				 double * const fv[6], int cmask, double visc, double gsrc)
+				 double * const fv[6], int cmask, double visc, double gsrc, const double * msrc)
 {
   const Layout & L = dom->lay[dom->depth];
   dim3 grid, block;
   cell_grid (L, &grid, &block);
   DISPATCH (dom, advected_face_values_kernel, grid, block, L, v, c3 (u), c3 (un), dt,
-	    use_centered, gradient, m6 (fv), cmask, visc, gsrc);
+	    use_centered, gradient, m6 (fv), cmask, visc, gsrc, msrc);
+  return GFSHIP_OK;
+}
+
+int launch_variable_mac_source (gfship_domain * dom, const double * v, double * const D[3],
+				const double * alpha, double * out)
+{
+  const Layout & L = dom->lay[dom->depth];
+  dim3 grid, block;
+  cell_grid (L, &grid, &block);
+  DISPATCH (dom, variable_mac_source_kernel, grid, block, L, v, c3 (D), alpha, out);
   return GFSHIP_OK;
 }
 
@@ -3368,8 +3406,9 @@ int launch_advect3_fused (gfship_domain * dom, double * const v[3], double * con
 }
 
 int launch_cfl (gfship_domain * dom, double * const u[3], double * const un[3],
-		const double visc[3], double * cfl2)
+		const double visc[3], double * cfl2, double * const msrc[3])
 {
+  double * const none[3] = { nullptr, nullptr, nullptr };
   Visc3 vs;
   for (int c = 0; c < 3; c++) { vs.d[c] = visc ? visc[c] : 0.; vs.g[c] = dom->src[c]; }
   const Layout & L = dom->lay[dom->depth];
@@ -3380,7 +3419,8 @@ int launch_cfl (gfship_domain * dom, double * const u[3], double * const un[3],
   if (nblocks > 1024) nblocks = 1024;
   double * partial = dom->d_scratch;
   double * result = dom->h_pinned;      /* host memory mapped on the device: no copy kernel */
-  DISPATCH (dom, cfl_partial_kernel, dim3 (nblocks), dim3 (block), L, c3 (u), c3 (un), vs, partial);
+  DISPATCH (dom, cfl_partial_kernel, dim3 (nblocks), dim3 (block), L, c3 (u), c3 (un), vs, c3 (msrc ? msrc : none),
+	    partial);
   hipLaunchKernelGGL (min_final_kernel, dim3 (1), dim3 (256), 0, dom->stream, partial, nblocks, result);
   GFSHIP_HIP (hipGetLastError ());
   GFSHIP_HIP (stream_wait_spin (dom->stream));

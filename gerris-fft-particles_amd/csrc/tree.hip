@@ -508,7 +508,7 @@ t_relax_nodes (Topo T, const int * node_g, const int * node_off, const int * chu
 	  x = dim == 2 ? (1. - omega)*self + omega*(gb - rhs[g])/ga : (gb - rhs[g])/ga;
 	u[g] = x;
       }
-      else {      /* diffusion_relax, src/poisson.c:1455-1484 (rhoc = 1): diffusion_relax_cell of tree.hpp */
+      else {      /* diffusion_relax, src/poisson.c:1471-1498 (rhoc = 1): diffusion_relax_cell of tree.hpp */
 	cur.tv++;
 	double ga, gb;
 	tape_cell (cur, nd, dim, ncd, ga, gb, w);
@@ -602,7 +602,7 @@ t_relax_nodes_pf (Topo T, const int * rec_g, const int * desc_g, int nchunks,
 	  x = dim == 2 ? (1. - omega)*self + omega*(gb - rh)/ga : (gb - rh)/ga;
 	u[g] = x;
       }
-      else {      /* diffusion_relax, src/poisson.c:1455-1484 (rhoc = 1) */
+      else {      /* diffusion_relax, src/poisson.c:1471-1498 (rhoc = 1) */
 	cur.tv++;
 	double ga, gb;
 	tape_cell (cur, nd, dim, ncd, ga, gb, w);
@@ -730,7 +730,7 @@ __global__ void t_diffusion_rhs (Topo T, const Cell * cells, int n, const double
   rhs[T.gi (c)] += diffusion_rhs_cell (T, c, R, WConst { w }, pbeta);
 }
 
-// gfs_diffusion_residual (src/poisson.c:1519-1556) on the leaves + gfs_domain_norm_variable
+// gfs_diffusion_residual (src/poisson.c:1534-1569) on the leaves + gfs_domain_norm_variable
 // (src/domain.c:2197-2232: weights = cell volumes): the maximum is exact, the sums in no particular order
 __global__ void t_diffusion_residual (Topo T, const Cell * cells, int n, const double * u, const double * rhs,
 				      double * res, double w, double * red)

@@ -412,7 +412,7 @@ __host__ __device__ inline Grad2 face_gradient_w (const Topo & T, const Face & f
   return g;
 }
 
-// diffusion_relax, src/poisson.c:1455-1484 (rhoc = 1): the new value of u at `cell'
+// diffusion_relax, src/poisson.c:1471-1498 (rhoc = 1): the new value of u at `cell'
 template <class V, class W>
 __host__ __device__ inline double diffusion_relax_cell (const Topo & T, Cell cell, V & u, double res, const W & w,
 							int max_level)
@@ -432,7 +432,7 @@ __host__ __device__ inline double diffusion_relax_cell (const Topo & T, Cell cel
   return (g.b/a + res)/g.a;
 }
 
-// diffusion_residual, src/poisson.c:1519-1556 (rhoc = 1)
+// diffusion_residual, src/poisson.c:1534-1569 (rhoc = 1)
 template <class V, class W>
 __host__ __device__ inline double diffusion_residual_cell (const Topo & T, Cell cell, V & u, double rhs, const W & w)
 {

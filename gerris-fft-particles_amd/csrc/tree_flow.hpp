@@ -13,7 +13,7 @@
 //          leaf (src/fluid.c:795-829): the pair of one child;
 //   SUM    the sum over the children of that face, in child order (:812-826);
 //   CELL   the sums over the faces in direction order and the new value (relax, src/poisson.c:507-557;
-//          diffusion_relax, :1455-1484);
+//          diffusion_relax, :1471-1498);
 //   GHOST  the copy of a ghost cell between two sweeps (homogeneous condition or periodic image).
 // Every operation has at most nine inputs at fixed places of a 48-byte record, all independent
 // loads, and is scheduled as a node of its own: CHILD one level before its SUM, FC / SUM one level
@@ -120,7 +120,7 @@ __host__ __device__ inline FlowPair flow_eval (unsigned w0, const double * x, co
       }
       o.x = r;
     }
-    else {      /* diffusion_relax, src/poisson.c:1455-1484 (rhoc = 1) */
+    else {      /* diffusion_relax, src/poisson.c:1471-1498 (rhoc = 1) */
       const int l = (w0 >> 15) & 31;
       const double h = 1./(1 << l);
       const double a = 1.*h*h;

@@ -77,6 +77,7 @@ SIGNATURES = {
     "gfship_poisson_cycle": (_i, [_vp, C.POINTER(MultilevelParams), _i, _i, _i, _i]),
     "gfship_poisson_solve": (_i, [_vp, C.POINTER(MultilevelParams), _i, _i, _i, _i, _d]),
     "gfship_diffusion_coefficients": (_i, [_vp, _d, _d, _i, _d]),
+    "gfship_diffusion_coefficients_faces": (_i, [_vp, _pi, _d, _i, _i, _d]),
     "gfship_diffusion_rhs": (_i, [_vp, _i, _i, _i, _d]),
     "gfship_diffusion_residual": (_i, [_vp, _i, _i, _i, _i]),
     "gfship_diffusion_cycle": (_i, [_vp, _u, _u, _u, _i, _i, _i, _i]),
@@ -96,6 +97,9 @@ SIGNATURES = {
     "gfship_sim_iter": (_u, [_vp]),
     "gfship_sim_add_tracer": (_i, [_vp]),
     "gfship_sim_set_viscosity": (_i, [_vp, _i, _d]),
+    "gfship_sim_set_viscosity_faces": (_i, [_vp, _i, _pi]),
+    "gfship_sim_set_alpha_cell": (_i, [_vp, _i]),
+    "gfship_variable_mac_source": (_i, [_vp, _i, _i]),
     "gfship_sim_set_alpha": (_i, [_vp, _pi]),
     "gfship_sim_set_source": (_i, [_vp, _i, _d]),
     "gfship_sim_diffusion_params": (C.POINTER(MultilevelParams), [_vp, _i]),
@@ -207,6 +211,7 @@ KERNEL_COUNT_NAMES = (
     "ARM_AHEAD", "ARM_AHEAD_DECLINED", "ARM_INLINE", "PATCH_LOOP_KERNEL_ARMS",
     "PATCH_LOOP_HOST_ARMS", "XCD_SCOPE_ON", "XCD_SCOPE_OFF", "XCD_NEAR_MODE", "XCD_PLACE_ON",
     "XCD_PLACE_OFF", "COARSE_CYCLES", "COARSE_THREADS", "COARSE_END_BY_LEVEL",
+    "DIFFUSION_FACES_PIPELINED", "DIFFUSION_FACES_HYPERPLANES",
 )
 # ... of which these hold a value (a limit, a thread count, a mode) instead of a tally
 KERNEL_COUNT_VALUES = ("RN_BLOCKS_LIMIT", "RN_BLOCKS_MAX", "XCD_NEAR_MODE", "COARSE_THREADS")
@@ -418,6 +423,13 @@ class Domain:
     def diffusion_coefficients(self, D, dt, rhoc, beta=1.):
         _check(lib().gfship_diffusion_coefficients(self.ptr, D, dt, rhoc.h, beta))
 
+    def diffusion_coefficients_faces(self, D, dt, rhoc, alpha_cell=None, beta=1.):
+        """D: dim Variables holding the diffusion coefficient at the leaf faces (the layout of
+        poisson_coefficients_alpha); alpha_cell: a Variable holding alpha on every level, or None"""
+        h = (C.c_int * 3)(*([v.h for v in D] + [-1] * (3 - len(D))))
+        _check(lib().gfship_diffusion_coefficients_faces(self.ptr, h, dt, rhoc.h,
+                                                         -1 if alpha_cell is None else alpha_cell.h, beta))
+
     def diffusion_rhs(self, v, rhs, rhoc, beta=1.):
         _check(lib().gfship_diffusion_rhs(self.ptr, v.h, rhs.h, rhoc.h, beta))
 
@@ -571,6 +583,22 @@ class Simulation:
     def set_viscosity(self, c, nu):
         """SourceDiffusion {} U|V|W nu"""
         _check(lib().gfship_sim_set_viscosity(self.ptr, c, nu))
+
+    def set_viscosity_faces(self, c, D):
+        """SourceDiffusion {} U|V|W f(x,y,z,t): dim Variables of face values (None removes it)"""
+        if D is None:
+            _check(lib().gfship_sim_set_viscosity_faces(self.ptr, c, None))
+            return
+        h = (C.c_int * 3)(*([v.h for v in D] + [-1] * (3 - len(D))))
+        _check(lib().gfship_sim_set_viscosity_faces(self.ptr, c, h))
+
+    def set_alpha_cell(self, alpha_cell):
+        """alpha at the cell centres of every level: a Variable (None removes it)"""
+        _check(lib().gfship_sim_set_alpha_cell(self.ptr, -1 if alpha_cell is None else alpha_cell.h))
+
+    def variable_mac_source(self, c, out):
+        """gfs_variable_mac_source of velocity component c into the Variable out"""
+        _check(lib().gfship_variable_mac_source(self.ptr, c, out.h))
 
     def diffusion_params(self, c):
         return lib().gfship_sim_diffusion_params(self.ptr, c).contents

@@ -168,16 +168,34 @@ int  gfship_poisson_solve (gfship_domain * dom, gfship_multilevel_params * par,
 			   gfship_field lhs, gfship_field rhs, gfship_field res,
 			   gfship_field dia, double dt);
 
-/* ---- implicit diffusion (GfsSourceDiffusion with a constant coefficient, no solids) ---------- */
+/* ---- implicit diffusion (GfsSourceDiffusion, no solids) -------------------------------------- */
 
 /* gfs_diffusion_coefficients, src/poisson.c:1357-1390: face weights lambda2*beta*dt*D on every
    level (one scalar per level on a uniform box) and rhoc = 1. on every cell */
 int  gfship_diffusion_coefficients (gfship_domain * dom, double D, double dt, gfship_field rhoc,
 				    double beta);
+/* gfs_diffusion_coefficients, src/poisson.c:1357-1399, with a coefficient that varies in space and a
+   variable density (diffusion_coef :1280-1301, diffusion_mixed_coeff :1303-1333, face_coeff_from_below
+   :826-853): D[c] holds gfs_source_diffusion_face (src/source.c:933-939) of the leaf faces normal to c
+   in the layout of gfship_poisson_coefficients_alpha (the entry of a cell is its + face, the ghost
+   entry in front of the first cell its - face).  Sets f[d].v = lambda2*(beta*dt)*D_face on the leaves
+   (assignment) and every coarser level from below, on the device, into the variables
+   gfship_poisson_weights returns: as in the reference the Poisson and the diffusion coefficients share
+   f[d].v, so whoever solves a Poisson problem afterwards calls gfship_poisson_coefficients[_alpha]
+   again.  alpha_cell: a variable the caller has filled with gfs_function_value (alpha, cell) on EVERY
+   level (FTT_TRAVERSE_ALL, :1384-1386), rhoc = 1./alpha_cell on every level; alpha_cell = -1:
+   rhoc = 1.  GFSHIP_EINVAL if a density is <= 0 (the reference's "density is negative", :1323-1330):
+   rhoc and the coefficients are then undefined until the next successful call.
+   gfship_diffusion_rhs, _residual, _cycle and gfship_diffusion then run with the six weights of every
+   cell (diffusion_rhs :1401-1430, diffusion_relax :1471-1498, diffusion_residual :1534-1569) until
+   gfship_diffusion_coefficients is called again.  Uniform boxes without MPI sides
+   (GFSHIP_EUNSUPPORTED otherwise). */
+int  gfship_diffusion_coefficients_faces (gfship_domain * dom, const gfship_field D[3], double dt,
+					  gfship_field rhoc, gfship_field alpha_cell, double beta);
 /* gfs_diffusion_rhs, src/poisson.c:1447-1453 (diffusion_rhs :1392-1436) */
 int  gfship_diffusion_rhs (gfship_domain * dom, gfship_field v, gfship_field rhs,
 			   gfship_field rhoc, double beta);
-/* gfs_diffusion_residual, src/poisson.c:1587-1612 (diffusion_residual :1519-1556) */
+/* gfs_diffusion_residual, src/poisson.c:1587-1612 (diffusion_residual :1534-1569) */
 int  gfship_diffusion_residual (gfship_domain * dom, gfship_field u, gfship_field rhs,
 				gfship_field rhoc, gfship_field res);
 /* gfs_diffusion_cycle, src/poisson.c:1633-1690 */
@@ -241,13 +259,34 @@ int      gfship_sim_set_tracer_gradient (gfship_sim * sim, int tracer, int gradi
    velocity component c (0. removes it), and the GfsMultilevelParams of its solver
    (tolerance 1e-6, beta 1: diffusion_init, src/source.c:966-974) */
 int      gfship_sim_set_viscosity (gfship_sim * sim, int c, double nu);
+/* GfsSourceDiffusion {} U|V|W f(x,y,z,t) / GfsSourceViscosity f: D[q] holds gfs_source_diffusion_face
+   (diffusion_face, src/source.c:933-939) of the leaf faces normal to q, in the layout of
+   gfship_diffusion_coefficients_faces, kept by handle like alpha (the caller may rewrite the fields
+   between steps); NULL removes it.  variable_diffusion (src/timestep.c:923-949) then runs
+   gfship_diffusion_coefficients_faces, and the step takes the general advection path (face-value arrays
+   + flux kernel) with the MAC source of gfship_variable_mac_source.  A component has one
+   GfsSourceDiffusion: this call replaces a constant set by gfship_sim_set_viscosity, and
+   gfship_sim_set_viscosity with nu != 0 replaces the fields.  Not on boxes with MPI sides, and not
+   together with particle forces (GFSHIP_EUNSUPPORTED). */
+int      gfship_sim_set_viscosity_faces (gfship_sim * sim, int c, const gfship_field D[3]);
+/* gfs_function_value (alpha, cell) of GfsPhysicalParams { alpha } on the cells of EVERY level, by
+   handle (-1 removes it): the density of the implicit diffusion, rhoc = 1./alpha (diffusion_mixed_coeff,
+   src/poisson.c:1321-1332, FTT_TRAVERSE_ALL), and the factor of its MAC source
+   (source_diffusion_value, src/source.c:1141-1143).  With it gfship_sim_set_alpha and a viscosity go
+   together. */
+int      gfship_sim_set_alpha_cell (gfship_sim * sim, gfship_field alpha_cell);
+/* gfs_variable_mac_source (src/source.c:38-59) of velocity component c for its GfsSourceDiffusion:
+   source_diffusion_value (src/source.c:1105-1144) of every leaf cell,
+   alpha(cell)*(sum_d D_f*e.b - (sum_d D_f)*v0)/(h*h), into the leaves of out */
+int      gfship_variable_mac_source (gfship_sim * sim, int c, gfship_field out);
 /* GfsPhysicalParams { alpha = ... } (src/simulation.c:1306-1440): the inverse of the density as
    gfs_function_face_value (alpha, face) on the leaf faces, alpha[c] in the layout of
    gfship_poisson_coefficients_alpha (kept by handle: the caller may rewrite the fields between steps
    when alpha depends on time or on a tracer).  Both projections then run gfs_poisson_coefficients
    with it (src/timestep.c:376), the multigrid with the face weights, and gfs_correct_normal_velocities
    / gfs_update_gradients with gfs_face_weighted_gradient's weights (:118-144,306-322).  NULL: alpha =
-   NULL again.  Not together with GfsSourceDiffusion (variable-density diffusion coefficients). */
+   NULL again.  Together with GfsSourceDiffusion once gfship_sim_set_alpha_cell has given alpha at the
+   cell centres (the density of the diffusion equation); GFSHIP_EUNSUPPORTED before that. */
 int      gfship_sim_set_alpha (gfship_sim * sim, const gfship_field alpha[3]);
 /* GfsSource {} U|V|W g (src/source.c:362-500) with a constant intensity g on velocity component c
    (0. removes it): a body force per unit mass -- the MAC source of gfs_cell_advected_face_values
@@ -559,6 +598,8 @@ enum {
   GFSHIP_KC_COARSE_CYCLES,           /* coarse ends of V-cycles in one launch */
   GFSHIP_KC_COARSE_THREADS,          /* value: threads of the last such launch */
   GFSHIP_KC_COARSE_END_BY_LEVEL,     /* V-cycles whose coarse end ran level by level */
+  GFSHIP_KC_DIFFUSION_FACES_PIPELINED,   /* per-face diffusion relax loops on the pipelined tile kernel */
+  GFSHIP_KC_DIFFUSION_FACES_HYPERPLANES, /* the same loops, one launch per hyperplane */
   GFSHIP_KC_COUNT
 };
 int  gfship_domain_kernel_counts (gfship_domain * dom, unsigned long long * counts, int n);
@@ -720,7 +761,7 @@ int  gfship_tree_divergence (gfship_tree * tree);
    loop plans, [3] = number of values that differ between (a), (b), (c): 0 for valid plans */
 int  gfship_tree_host_check (int dim, gfship_refine_fn refine, void * ctx, const int * side,
 			     unsigned nrelax, long long stats[4]);
-/* the same for the diffusion relax (diffusion_relax, src/poisson.c:1455-1484) with the coefficients of
+/* the same for the diffusion relax (diffusion_relax, src/poisson.c:1471-1498) with the coefficients of
    gfs_diffusion_coefficients for the face weight w > 0 (the homogeneous conditions of U): for every level
    (a) the reference's program with the coefficients computed in the reference's order for this w, (b) the
    plan of the whole loop, (c) its flow plan with the kernel's timing, both with w on every face as the
