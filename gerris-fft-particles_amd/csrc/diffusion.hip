@@ -7,34 +7,20 @@
 // leaf face carries the same weight w = lambda2*beta*dt*D (diffusion_coef, src/poisson.c:1280-1303)
 // and every cell the same rhoc = 1. (diffusion_mixed_coef :1305-1348), so a level is described by one
 // scalar instead of 2*dim arrays; the coarse weights are computed on the host with
-// face_coeff_from_below's arithmetic (:826-853), one scalar per level.  The in-place sweeps reuse the
-// exact-order kernels of poisson_kernels.hip with the diffusion cell update (RelaxOp kind 1).
+// face_coeff_from_below's arithmetic (:826-853), one scalar per level: RelaxOp kind 1 of cell_update.hpp.
 //
 // With a coefficient given at the leaf faces and a density given at the cells of every level
 // (gfship_diffusion_coefficients_faces) the weights are the arrays f[d].v the weighted Poisson solver
-// uses (dom->wf), computed on the device, and the sweeps run the same cell update with the six weights
-// of the cell (RelaxOp kind 3).  The domain remembers which of the two was set last (diff_kind).
+// uses (dom->wf), computed on the device: kind 3.  The domain remembers which of the two was set last
+// (diff_kind).  The in-place sweeps are the exact-order kernels of poisson_kernels.hip with that kind.
 #include "gfship_internal.hpp"
+#include "cell_loop.hpp"
 #include <cmath>
 #include <cstdlib>
 
 using namespace gfship;
 
 namespace gfship {
-
-#define CELL_LOOP_PROLOGUE(L)						\
-  int i = blockIdx.x*blockDim.x + threadIdx.x + 1;			\
-  int j = blockIdx.y + 1;						\
-  int k = (L).dim == 3 ? blockIdx.z + 1 : 0;				\
-  if (i > (L).n) return;						\
-  long c = (L).idx (i, j, k)
-
-static inline void cell_grid (const Layout & L, dim3 * grid, dim3 * block)
-{
-  int b = L.n >= 256 ? 256 : L.n >= 128 ? 128 : 64;
-  *block = dim3 (b);
-  *grid = dim3 ((L.n + b - 1)/b, L.n, L.dim == 3 ? L.n : 1);
-}
 
 // gfs_diffusion_rhs / diffusion_rhs, src/poisson.c:1392-1451:
 //   f = sum_d (g.b - g.a*v) with g.a = w, g.b = w*v_nb ; rhs += (1 - beta)/beta*f/(h*h*rhoc)
@@ -45,14 +31,7 @@ diffusion_rhs_kernel (Layout L, double w, double pbeta, const double * __restric
 {
   CELL_LOOP_PROLOGUE (L);
   const double h = 1./L.n;
-  const long off[3] = { 1, L.sy, L.sz };
-  const double val = v[c];
-  double f = 0.;
-#pragma unroll
-  for (int cc = 0; cc < DIM; cc++) {
-    f += w*v[c + off[cc]] - w*val;
-    f += w*v[c - off[cc]] - w*val;
-  }
+  const double f = flux_sum<DIM> (UniformW { w }, ArrayU { v, c, L.sy, L.sz }, v[c]);
   rhs[c] += pbeta*f/(h*h*rhoc[c]);
 }
 
@@ -65,18 +44,9 @@ diffusion_residual_kernel (Layout L, double w, const double * __restrict__ u,
 {
   CELL_LOOP_PROLOGUE (L);
   const double h = 1./L.n;
-  const long off[3] = { 1, L.sy, L.sz };
-  double a = rhoc[c];
-  double ga = 0., gb = 0.;
-#pragma unroll
-  for (int cc = 0; cc < DIM; cc++) {
-    ga += w; gb += w*u[c + off[cc]];
-    ga += w; gb += w*u[c - off[cc]];
-  }
-  a *= h*h;
-  ga = 1. + ga/a;
-  gb = rhs[c] + gb/a;
-  res[c] = gb - ga*u[c];
+  const double a = rhoc[c];
+  const FaceSums s = face_sums<DIM> (UniformW { w }, ArrayU { u, c, L.sy, L.sz }, 0.);
+  res[c] = diffusion_residual_close (s.a, s.b, rhs[c], a, h*h, u[c]);
 }
 
 // gfs_get_from_below_intensive, src/fluid.c:1843-1864 (unit cell fractions): children in
@@ -100,13 +70,13 @@ restrict_intensive_kernel (Layout Lc, Layout Lf, double * __restrict__ vc,
   vc[c] = val/sa;
 }
 
-// the same two with the six face weights of the cell (gfs_face_cm_weighted_gradient's same-level branch,
-// src/fluid.c:1361-1366: g.a = w, g.b = w*v_nb), d = 0 .. 2 DIM - 1
-struct DW6 { const double * p[6]; };
+// the same two with the six face weights of the cell: flux_sum, and face_sums with diffusion_residual_close,
+// of ArrayW { &wf, c }, as written before the shared header (through it three of the four kernels come out an
+// instruction longer or shorter)
 
 template <int DIM>
 __global__ void __launch_bounds__(256)
-diffusion_rhs_faces_kernel (Layout L, DW6 wf, double pbeta, const double * __restrict__ v,
+diffusion_rhs_faces_kernel (Layout L, W6 wf, double pbeta, const double * __restrict__ v,
 			    const double * __restrict__ rhoc, double * __restrict__ rhs)
 {
   CELL_LOOP_PROLOGUE (L);
@@ -124,7 +94,7 @@ diffusion_rhs_faces_kernel (Layout L, DW6 wf, double pbeta, const double * __res
 
 template <int DIM>
 __global__ void __launch_bounds__(256)
-diffusion_residual_faces_kernel (Layout L, DW6 wf, const double * __restrict__ u,
+diffusion_residual_faces_kernel (Layout L, W6 wf, const double * __restrict__ u,
 				 const double * __restrict__ rhs, const double * __restrict__ rhoc,
 				 double * __restrict__ res)
 {
@@ -160,21 +130,13 @@ diffusion_rhoc_kernel (Layout L, const double * __restrict__ alpha, double * __r
   rhoc[c] = rho*1.;
 }
 
-static DW6 level_weights (gfship_domain * dom, int level)
+static W6 level_weights (gfship_domain * dom, int level)
 {
-  DW6 w;
+  W6 w;
   for (int d = 0; d < 6; d++)
     w.p[d] = d < 2*dom->dim ? dom->fields[dom->wf[d]].lev[level] : nullptr;
   return w;
 }
-
-#define DLAUNCH(dom, kern, grid, block, ...) do {				\
-    if ((dom)->dim == 3)						\
-      hipLaunchKernelGGL (kern<3>, grid, block, 0, (dom)->stream, __VA_ARGS__); \
-    else								\
-      hipLaunchKernelGGL (kern<2>, grid, block, 0, (dom)->stream, __VA_ARGS__); \
-    GFSHIP_HIP (hipGetLastError ());					\
-  } while (0)
 
 static RelaxOp level_op (gfship_domain * dom, int level)
 {
@@ -244,12 +206,16 @@ static int residual (gfship_domain * dom, Field * U, Field * R, Field * C, Field
   dim3 grid, block;
   cell_grid (dom->lay[L], &grid, &block);
   S->zero[L] = false;
-  if (dom->diff_kind == 3)
-    DLAUNCH (dom, diffusion_residual_faces_kernel, grid, block, dom->lay[L], level_weights (dom, L),
-	     U->lev[L], R->lev[L], C->lev[L], S->lev[L]);
-  else
-    DLAUNCH (dom, diffusion_residual_kernel, grid, block, dom->lay[L], dom->diff_w[L],
-	     U->lev[L], R->lev[L], C->lev[L], S->lev[L]);
+  with_bools ([&] (auto D3) {
+    constexpr int DIM = decltype (D3)::value ? 3 : 2;
+    if (dom->diff_kind == 3)
+      hipLaunchKernelGGL (diffusion_residual_faces_kernel<DIM>, grid, block, 0, dom->stream, dom->lay[L],
+			  level_weights (dom, L), U->lev[L], R->lev[L], C->lev[L], S->lev[L]);
+    else
+      hipLaunchKernelGGL (diffusion_residual_kernel<DIM>, grid, block, 0, dom->stream, dom->lay[L],
+			  dom->diff_w[L], U->lev[L], R->lev[L], C->lev[L], S->lev[L]);
+  }, dom->dim == 3);
+  GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
 
@@ -315,7 +281,11 @@ int gfship_diffusion_coefficients_faces (gfship_domain * dom, const gfship_field
       dim3 grid, block;
       cell_grid (dom->lay[l], &grid, &block);
       C->zero[l] = false;
-      DLAUNCH (dom, diffusion_rhoc_kernel, grid, block, dom->lay[l], A->lev[l], C->lev[l], bad);
+      with_bools ([&] (auto D3) {
+	hipLaunchKernelGGL (diffusion_rhoc_kernel<decltype (D3)::value ? 3 : 2>, grid, block, 0, dom->stream,
+			    dom->lay[l], A->lev[l], C->lev[l], bad);
+      }, dom->dim == 3);
+      GFSHIP_HIP (hipGetLastError ());
     }
     GFSHIP_HIP (hipMemcpyAsync (&hbad, bad, sizeof (unsigned), hipMemcpyDeviceToHost, dom->stream));
     GFSHIP_HIP (hipStreamSynchronize (dom->stream));
@@ -347,12 +317,16 @@ int gfship_diffusion_rhs (gfship_domain * dom, gfship_field v, gfship_field rhs,
   dim3 grid, block;
   cell_grid (dom->lay[L], &grid, &block);
   R->zero[L] = false;
-  if (dom->diff_kind == 3)
-    DLAUNCH (dom, diffusion_rhs_faces_kernel, grid, block, dom->lay[L], level_weights (dom, L),
-	     (1. - beta)/beta, V->lev[L], C->lev[L], R->lev[L]);
-  else
-    DLAUNCH (dom, diffusion_rhs_kernel, grid, block, dom->lay[L], dom->diff_w[L],
-	     (1. - beta)/beta, V->lev[L], C->lev[L], R->lev[L]);
+  with_bools ([&] (auto D3) {
+    constexpr int DIM = decltype (D3)::value ? 3 : 2;
+    if (dom->diff_kind == 3)
+      hipLaunchKernelGGL (diffusion_rhs_faces_kernel<DIM>, grid, block, 0, dom->stream, dom->lay[L],
+			  level_weights (dom, L), (1. - beta)/beta, V->lev[L], C->lev[L], R->lev[L]);
+    else
+      hipLaunchKernelGGL (diffusion_rhs_kernel<DIM>, grid, block, 0, dom->stream, dom->lay[L],
+			  dom->diff_w[L], (1. - beta)/beta, V->lev[L], C->lev[L], R->lev[L]);
+  }, dom->dim == 3);
+  GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
 
@@ -391,8 +365,11 @@ int gfship_diffusion_cycle (gfship_domain * dom, unsigned levelmin, unsigned dep
     dim3 grid, block;
     cell_grid (dom->lay[l], &grid, &block);
     S->zero[l] = false;
-    DLAUNCH (dom, restrict_intensive_kernel, grid, block, dom->lay[l], dom->lay[l + 1],
-	     S->lev[l], S->lev[l + 1]);
+    with_bools ([&] (auto D3) {
+      hipLaunchKernelGGL (restrict_intensive_kernel<decltype (D3)::value ? 3 : 2>, grid, block, 0, dom->stream,
+			  dom->lay[l], dom->lay[l + 1], S->lev[l], S->lev[l + 1]);
+    }, dom->dim == 3);
+    GFSHIP_HIP (hipGetLastError ());
   }
   /* relax top level */
   for (int l = 0; l <= L; l++)

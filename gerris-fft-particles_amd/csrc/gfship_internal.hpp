@@ -11,6 +11,7 @@
 #include <type_traits>
 #include "gfship.h"
 #include "switches.hpp"
+#include "cell_update.hpp"
 
 namespace gfship {
 
@@ -76,14 +77,20 @@ struct SkewPlan {
   unsigned short * xorder = nullptr;   // tiles by XCD block (relax_skew_loop.hip)
 };
 
-// cell update of the exact-order sweeps: kind 0 = Poisson relax (unit weights), kind 1 =
-// diffusion_relax with the level's uniform face weight w and h2 = h*h
+// cell update of the exact-order sweeps: the kinds 0 .. 3 of cell_update.hpp
 struct RelaxOp {
-  int kind = 0;                  // 2: Poisson relax with the face weights f[d].v of the level (wf)
-                                 // 3: diffusion_relax with the same six weights per cell and h2
-  double w = 1., h2 = 1.;
-  const double * wf[6] = {};
+  int kind = 0;
+  double w = 1., h2 = 1.;        // kind 1: the face weight of the level; kinds 1 and 3: h*h
+  const double * wf[6] = {};     // kinds 2 and 3: the face weights f[d].v of the level
 };
+
+// the weight arrays of an operator as the kernels take them (null pointers where it has none)
+inline W6 op_weights (const RelaxOp * op)
+{
+  W6 wf;
+  for (int d = 0; d < 6; d++) wf.p[d] = op ? op->wf[d] : nullptr;
+  return wf;
+}
 
 // device-side description of the six sides for the BC kernel
 struct BcDesc {
@@ -195,6 +202,17 @@ template <class F, class... B> inline void with_bools (F && f, bool b0, B... res
 {
   if (b0) with_bools ([&] (auto... r) { f (std::true_type {}, r...); }, rest...);
   else    with_bools ([&] (auto... r) { f (std::false_type {}, r...); }, rest...);
+}
+
+// the same for a RelaxOp kind, followed by any bools: f gets std::integral_constant<int, K>, K = 0 .. 3 (any
+// other value runs kind 1), then one std::true_type or std::false_type per bool
+template <class F, class... B> inline void with_kind (F && f, int kind, B... bools)
+{
+  auto k = [&] (auto K) { with_bools ([&] (auto... r) { f (K, r...); }, bools...); };
+  if (kind == 3)      k (std::integral_constant<int, 3> {});
+  else if (kind == 2) k (std::integral_constant<int, 2> {});
+  else if (kind)      k (std::integral_constant<int, 1> {});
+  else                k (std::integral_constant<int, 0> {});
 }
 
 #define GFSHIP_CHECK(cond, code, ...) do { if (!(cond)) { \

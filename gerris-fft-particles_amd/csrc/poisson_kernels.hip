@@ -2,9 +2,9 @@
 //
 // All arithmetic is IEEE fp64, compiled with -ffp-contract=off, and written operation by
 // operation in the operand order of the reference (src/poisson.c, src/fluid.c) so that the
-// exact-mode results are bit-identical to the CPU algorithm.  Unit face weights
-// (gfs_poisson_coefficients with alpha = NULL on a uniform single box: every f[d].v == 1.).
+// exact-mode results are bit-identical to the CPU algorithm.
 #include "gfship_internal.hpp"
+#include "cell_loop.hpp"
 #include "relax_skew.hpp"
 #include <algorithm>
 #include <cstdlib>
@@ -12,95 +12,24 @@
 namespace gfship {
 
 // ---------------------------------------------------------------------------------------------
-// K1: relax / relax2D, src/poisson.c:507-557, with face_weighted_gradient's same-level branch
-// (src/fluid.c:858-864: g->a = w; g->b = w*u_nb) for w == 1.
-//
-// OP == 1 is diffusion_relax, src/poisson.c:1471-1498, with gfs_face_cm_weighted_gradient's
-// same-level branch (src/fluid.c:1361-1366: g->a = w; g->b = w*u_nb) for the uniform face
-// weight w of the level and h2 = h*h:  a = dia*h*h ; g.a = 1. + g.a/a ; u = (g.b/a + res)/g.a.
-// OP == 3 is the same cell update with the six face weights of the cell (OP == 2's arrays).
+// K1: the in-place sweeps.  The cell update of the four operator kinds OP (RelaxOp::kind) is
+// cell_update<DIM, OP> of cell_update.hpp; relax_value is that update of the cell c of an array u of the level's
+// layout (that of the face weights).
 // ---------------------------------------------------------------------------------------------
-struct W6 { const double * p[6]; };   // the six face weights f[d].v of a level (OP == 2)
-
 template <int DIM, int OP>
 __device__ __forceinline__ double relax_value (const double * __restrict__ u, long c, long sy, long sz,
 					       double rhs, double dia, unsigned dimension,
 					       double omega, double w, double h2, const W6 * wf = nullptr)
 {
-  if (OP == 2) {
-    // relax / relax2D with the face weights of the cell (src/poisson.c:507-557, gfs_face_weighted_
-    // gradient's same-level branch src/fluid.c:858-864: g.a = w, g.b = w*u_nb)
-    double a = dia, b = 0.;
-    { const double g = wf->p[0][c]; a += g; b += g*u[c + 1]; }
-    { const double g = wf->p[1][c]; a += g; b += g*u[c - 1]; }
-    { const double g = wf->p[2][c]; a += g; b += g*u[c + sy]; }
-    { const double g = wf->p[3][c]; a += g; b += g*u[c - sy]; }
-    if (DIM == 3) {
-      { const double g = wf->p[4][c]; a += g; b += g*u[c + sz]; }
-      { const double g = wf->p[5][c]; a += g; b += g*u[c - sz]; }
-    }
-    if (dimension == 2)
-      return a != 0. ? (1. - omega)*u[c] + omega*(b - rhs)/a : 0.;
-    return a != 0. ? (b - rhs)/a : 0.;
-  }
-  if (OP == 3) {
-    // diffusion_relax (src/poisson.c:1471-1498) with the face weights of the cell
-    // (gfs_face_cm_weighted_gradient's same-level branch src/fluid.c:1361-1366: g.a = w, g.b = w*u_nb)
-    double ga = 0., gb = 0.;
-    { const double g = wf->p[0][c]; ga += g; gb += g*u[c + 1]; }
-    { const double g = wf->p[1][c]; ga += g; gb += g*u[c - 1]; }
-    { const double g = wf->p[2][c]; ga += g; gb += g*u[c + sy]; }
-    { const double g = wf->p[3][c]; ga += g; gb += g*u[c - sy]; }
-    if (DIM == 3) {
-      { const double g = wf->p[4][c]; ga += g; gb += g*u[c + sz]; }
-      { const double g = wf->p[5][c]; ga += g; gb += g*u[c - sz]; }
-    }
-    double a = dia*h2;
-    ga = 1. + ga/a;
-    return (gb/a + rhs)/ga;
-  }
-  if (OP == 1) {
-    double ga = 0., gb = 0.;
-    ga += w; gb += w*u[c + 1];
-    ga += w; gb += w*u[c - 1];
-    ga += w; gb += w*u[c + sy];
-    ga += w; gb += w*u[c - sy];
-    if (DIM == 3) {
-      ga += w; gb += w*u[c + sz];
-      ga += w; gb += w*u[c - sz];
-    }
-    double a = dia*h2;
-    ga = 1. + ga/a;
-    return (gb/a + rhs)/ga;
-  }
-  double a = dia, b = 0.;
-  a += 1.; b += 1.*u[c + 1];
-  a += 1.; b += 1.*u[c - 1];
-  a += 1.; b += 1.*u[c + sy];
-  a += 1.; b += 1.*u[c - sy];
-  if (DIM == 3) {
-    a += 1.; b += 1.*u[c + sz];
-    a += 1.; b += 1.*u[c - sz];
-  }
-  if (dimension == 2)
-    return a != 0. ? (1. - omega)*u[c] + omega*(b - rhs)/a : 0.;
-  return a != 0. ? (b - rhs)/a : 0.;
+  return cell_update<DIM, OP> (kind_weights<OP> (w, ArrayW { wf, c }), ArrayU { u, c, sy, sz }, rhs, dia, u + c,
+			       dimension, omega, h2);
 }
 
-// the same for unit weights, dia == 0 and dimension == 3: a = 0. + 1. + ... + 1. = 6. exactly and the
-// correctly rounded quotient comes from divide_by_6's reciprocal sequence (relax_skew.hpp) instead of
-// the division
+// the same for unit weights, dia == 0 and dimension == 3
 __device__ __forceinline__ double relax_value_six (const double * __restrict__ u, long c, long sy, long sz,
 						    double rhs)
 {
-  double b = 0.;
-  b += 1.*u[c + 1];
-  b += 1.*u[c - 1];
-  b += 1.*u[c + sy];
-  b += 1.*u[c - sy];
-  b += 1.*u[c + sz];
-  b += 1.*u[c - sz];
-  return divide_by_6 (b - rhs);
+  return cell_update_six (ArrayU { u, c, sy, sz }, rhs);
 }
 
 // Exact-order sweep, one launch per hyperplane I + J + K = plane of the oriented coordinates
@@ -147,7 +76,7 @@ relax_hyperplane_kernel (Layout L, int plane, unsigned dimension, double omega, 
 // thread reads its own row ahead of its stores (RX_D steps: a register ring, the step loop unrolled
 // by RX_D) and nobody else's, so no global-memory ordering between threads is involved; the ghost
 // rows j = n + 1 and j = 0 (written by the BC application before the sweep, not by the sweep) are
-// streamed by the threads of the first and the last row.  Same expressions as relax_value<2, OP>.
+// streamed by the threads of the first and the last row.  The cell update is cell_update<2, OP>.
 // ---------------------------------------------------------------------------------------------
 #define RX_D 8
 
@@ -225,39 +154,14 @@ relax_rows2d_kernel (Layout L, double omega, double w, double h2,
       if (active) {
 	const double top = J == 0 ? ex : N[rd][J];              // new value of (I, J - 1): row j + 1
 	const double bottom = J == n - 1 ? ex : O[rd][J + 2];     // old value of (I, J + 1): row j - 1
-	if (OP == 1) {
-	  double ga = 0., gb = 0.;
-	  ga += w; gb += w*right;
-	  ga += w; gb += w*left;
-	  ga += w; gb += w*top;
-	  ga += w; gb += w*bottom;
-	  double a = di*h2;
-	  ga = 1. + ga/a;
-	  v = (gb/a + rh)/ga;
+	if (OP == 3) {
+	  // cell_update<2, 3> with the one-statement closing (with the other one the kernel is an instruction shorter)
+	  const FaceSums f = face_sums<2> (CellW {{ w0, w1, w2, w3 }}, CellU {{ right, left, top, bottom }}, 0.);
+	  v = diffusion_close_1 (f.a, f.b, rh, di, h2);
 	}
-	else if (OP >= 2) {
-	  // the face weights of the cell: relax2D (src/poisson.c:532-557, src/fluid.c:858-864) sums from dia,
-	  // diffusion_relax (OP == 3, src/poisson.c:1471-1498, src/fluid.c:1361-1366) from 0.
-	  double a = OP == 2 ? di : 0., b = 0.;
-	  a += w0; b += w0*right;
-	  a += w1; b += w1*left;
-	  a += w2; b += w2*top;
-	  a += w3; b += w3*bottom;
-	  if (OP == 3) {
-	    const double ar = di*h2;
-	    v = (b/ar + rh)/(1. + a/ar);
-	  }
-	  else
-	    v = a != 0. ? (1. - omega)*cur + omega*(b - rh)/a : 0.;
-	}
-	else {
-	  double a = di, b = 0.;
-	  a += 1.; b += 1.*right;
-	  a += 1.; b += 1.*left;
-	  a += 1.; b += 1.*top;
-	  a += 1.; b += 1.*bottom;
-	  v = a != 0. ? (1. - omega)*cur + omega*(b - rh)/a : 0.;
-	}
+	else
+	  v = cell_update<2, OP> (kind_weights<OP> (w, CellW {{ w0, w1, w2, w3 }}), CellU {{ right, left, top, bottom }},
+				  rh, di, &cur, 2, omega, h2);
 	row[I + 1 + 1] = v;
 	left = v;
 	cur = right;
@@ -278,20 +182,10 @@ static int launch_relax_rows2d (gfship_domain * dom, int level, double omega, do
 {
   const Layout & L = dom->lay[level];
   const int block = L.n <= 64 ? 64 : L.n <= 128 ? 128 : L.n <= 256 ? 256 : L.n <= 512 ? 512 : 1024;
-  W6 wf;
-  for (int d = 0; d < 6; d++) wf.p[d] = op ? op->wf[d] : nullptr;
-  if (kind == 3)
-    hipLaunchKernelGGL (relax_rows2d_kernel<3>, dim3 (1), dim3 (block), 0, dom->stream, L, omega, w, h2,
-			u, rhs, dia, wf);
-  else if (kind == 2)
-    hipLaunchKernelGGL (relax_rows2d_kernel<2>, dim3 (1), dim3 (block), 0, dom->stream, L, omega, w, h2,
-			u, rhs, dia, wf);
-  else if (kind)
-    hipLaunchKernelGGL (relax_rows2d_kernel<1>, dim3 (1), dim3 (block), 0, dom->stream, L, omega, w, h2,
-			u, rhs, dia, wf);
-  else
-    hipLaunchKernelGGL (relax_rows2d_kernel<0>, dim3 (1), dim3 (block), 0, dom->stream, L, omega, w, h2,
-			u, rhs, dia, wf);
+  with_kind ([&] (auto K) {
+    hipLaunchKernelGGL (relax_rows2d_kernel<decltype (K)::value>, dim3 (1), dim3 (block), 0, dom->stream, L, omega,
+			w, h2, u, rhs, dia, op_weights (op));
+  }, kind);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
@@ -312,15 +206,11 @@ int launch_relax_exact (gfship_domain * dom, unsigned dimension, int level, doub
   int nthreads = dom->dim == 3 ? n*n : n;
   int block = 256;
   int grid = (nthreads + block - 1)/block;
-  W6 wf;
-  for (int d = 0; d < 6; d++) wf.p[d] = op ? op->wf[d] : nullptr;
-  for (int p = 0; p < nplanes; p++) {
-#define HP_LAUNCH(D, O) hipLaunchKernelGGL ((relax_hyperplane_kernel<D, O>), dim3 (grid), dim3 (block), \
-					    0, dom->stream, L, p, dimension, omega, w, h2, u, rhs, dia, wf)
-    if (dom->dim == 3) { if (kind == 3) HP_LAUNCH (3, 3); else if (kind == 2) HP_LAUNCH (3, 2); else if (kind) HP_LAUNCH (3, 1); else HP_LAUNCH (3, 0); }
-    else               { if (kind == 3) HP_LAUNCH (2, 3); else if (kind == 2) HP_LAUNCH (2, 2); else if (kind) HP_LAUNCH (2, 1); else HP_LAUNCH (2, 0); }
-#undef HP_LAUNCH
-  }
+  for (int p = 0; p < nplanes; p++)
+    with_kind ([&] (auto K, auto D3) {
+      hipLaunchKernelGGL ((relax_hyperplane_kernel<decltype (D3)::value ? 3 : 2, decltype (K)::value>), dim3 (grid),
+			  dim3 (block), 0, dom->stream, L, p, dimension, omega, w, h2, u, rhs, dia, op_weights (op));
+    }, kind, dom->dim == 3);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
@@ -410,9 +300,10 @@ relax_loop_lds_kernel (Layout L, BcDesc bc, unsigned dimension, double omega, do
 	  int i = I + 1, j = n - J, k = DIM == 3 ? n - K : 0;
 	  long c = i + ssy*j + ssz*k;
 	  long g = L.idx (i, j, k);
+	  // u in LDS (index c); rhs, dia and the face weights of the cell in the natural arrays (index g)
 	  if (OP >= 2) {
-	    // the face weights of the cell live in the natural arrays (index g), u in LDS (index c): relax sums
-	    // from dia, diffusion_relax (OP == 3: the expressions of relax_value<DIM, 3>) from 0.
+	    // cell_update<DIM, OP> as written before the shared header: with the sources (ArrayW at g, ArrayU in LDS)
+	    // the 3-D kernels come out two and three instructions longer
 	    double a = OP == 2 ? dia[g] : 0., b = 0.;
 	    { const double q = wf.p[0][g]; a += q; b += q*s[c + 1]; }
 	    { const double q = wf.p[1][g]; a += q; b += q*s[c - 1]; }
@@ -422,10 +313,8 @@ relax_loop_lds_kernel (Layout L, BcDesc bc, unsigned dimension, double omega, do
 	      { const double q = wf.p[4][g]; a += q; b += q*s[c + ssz]; }
 	      { const double q = wf.p[5][g]; a += q; b += q*s[c - ssz]; }
 	    }
-	    if (OP == 3) {
-	      const double ar = dia[g]*h2;
-	      s[c] = (b/ar + rhs[g])/(1. + a/ar);
-	    }
+	    if (OP == 3)
+	      s[c] = diffusion_close_1 (a, b, rhs[g], dia[g], h2);
 	    else
 	      s[c] = dimension == 2 ? (a != 0. ? (1. - omega)*s[c] + omega*(b - rhs[g])/a : 0.) :
 		(a != 0. ? (b - rhs[g])/a : 0.);
@@ -479,14 +368,11 @@ int launch_relax_loop_small (gfship_domain * dom, unsigned dimension, int level,
   bc.homogeneous = 1;
   int nface = dom->dim == 3 ? L.n*L.n : L.n;
   int block = nface <= 64 ? 64 : nface <= 256 ? 256 : 1024;
-  W6 wf;
-  for (int d = 0; d < 6; d++) wf.p[d] = op ? op->wf[d] : nullptr;
-#define LDS_LAUNCH(D, O) hipLaunchKernelGGL ((relax_loop_lds_kernel<D, O>), dim3 (1), dim3 (block), bytes, \
-					     dom->stream, L, bc, dimension, omega, w, h2, nrelax, \
-					     dp->lev[level], rhs, dia, wf)
-  if (dom->dim == 3) { if (kind == 3) LDS_LAUNCH (3, 3); else if (kind == 2) LDS_LAUNCH (3, 2); else if (kind) LDS_LAUNCH (3, 1); else LDS_LAUNCH (3, 0); }
-  else               { if (kind == 3) LDS_LAUNCH (2, 3); else if (kind == 2) LDS_LAUNCH (2, 2); else if (kind) LDS_LAUNCH (2, 1); else LDS_LAUNCH (2, 0); }
-#undef LDS_LAUNCH
+  with_kind ([&] (auto K, auto D3) {
+    hipLaunchKernelGGL ((relax_loop_lds_kernel<decltype (D3)::value ? 3 : 2, decltype (K)::value>), dim3 (1),
+			dim3 (block), bytes, dom->stream, L, bc, dimension, omega, w, h2, nrelax, dp->lev[level],
+			rhs, dia, op_weights (op));
+  }, kind, dom->dim == 3);
   GFSHIP_HIP (hipGetLastError ());
   *done = true;
   return GFSHIP_OK;
@@ -705,6 +591,7 @@ coarse_cycle_kernel (CoarseCycleArgs A)
 	  const int I = q - (sw << lg) - J - K;
 	  if (mine && sw >= 0 && (unsigned) I < (unsigned) n) {
 	    const int i = I + 1;
+	    // cell_update_six, as written before the shared header: through it this kernel's code comes out different
 	    double b = 0.;
 	    b += 1.*srow[i + 1];
 	    b += 1.*srow[i - 1];
@@ -1100,6 +987,7 @@ lattice_cycle_kernel (LatticeCycleArgs A)
 	  const int I = plane - J - K;
 	  if (mine && (unsigned) I < (unsigned) n) {
 	    const int i = I + 1;
+	    // cell_update_six, as written before the shared header: through it this kernel's code comes out different
 	    double b = 0.;
 	    b += 1.*srow[i + 1];
 	    b += 1.*srow[i - 1];
@@ -1308,34 +1196,19 @@ int launch_relax_redblack (gfship_domain * dom, unsigned dimension, int level, d
   int block = half >= 128 ? 128 : 64;
   dim3 grid ((half + block - 1)/block, L.n, dom->dim == 3 ? L.n : 1);
   for (int colour = 0; colour < 2; colour++) {
-    if (dom->dim == 3)
-      hipLaunchKernelGGL (relax_redblack_kernel<3>, grid, dim3 (block), 0, dom->stream,
+    with_bools ([&] (auto D3) {
+      hipLaunchKernelGGL (relax_redblack_kernel<decltype (D3)::value ? 3 : 2>, grid, dim3 (block), 0, dom->stream,
 			  L, colour, dimension, omega, u, rhs, dia);
-    else
-      hipLaunchKernelGGL (relax_redblack_kernel<2>, grid, dim3 (block), 0, dom->stream,
-			  L, colour, dimension, omega, u, rhs, dia);
+    }, dom->dim == 3);
   }
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
-// Cell-parallel kernels: one thread per interior cell, x fastest.
+// Cell-parallel kernels: one thread per interior cell, x fastest (CELL_LOOP_PROLOGUE and cell_grid of
+// cell_loop.hpp).
 // ---------------------------------------------------------------------------------------------
-#define CELL_LOOP_PROLOGUE(L)						\
-  int i = blockIdx.x*blockDim.x + threadIdx.x + 1;			\
-  int j = blockIdx.y + 1;						\
-  int k = (L).dim == 3 ? blockIdx.z + 1 : 0;				\
-  if (i > (L).n) return;						\
-  long c = (L).idx (i, j, k)
-
-static inline void cell_grid (const Layout & L, dim3 * grid, dim3 * block)
-{
-  int b = L.n >= 256 ? 256 : L.n >= 128 ? 128 : 64;
-  *block = dim3 (b);
-  *grid = dim3 ((L.n + b - 1)/b, L.n, L.dim == 3 ? L.n : 1);
-}
-
 // K2: residual_set / residual_set2D, src/poisson.c:634-678
 template <int DIM>
 __global__ void __launch_bounds__(256)
@@ -1343,16 +1216,8 @@ residual_kernel (Layout L, const double * __restrict__ u, const double * __restr
 		 const double * __restrict__ dia, double * __restrict__ res)
 {
   CELL_LOOP_PROLOGUE (L);
-  double a = dia[c], b = 0.;
-  a += 1.; b += 1.*u[c + 1];
-  a += 1.; b += 1.*u[c - 1];
-  a += 1.; b += 1.*u[c + L.sy];
-  a += 1.; b += 1.*u[c - L.sy];
-  if (DIM == 3) {
-    a += 1.; b += 1.*u[c + L.sz];
-    a += 1.; b += 1.*u[c - L.sz];
-  }
-  res[c] = rhs[c] - (b - u[c]*a);
+  const FaceSums s = face_sums<DIM> (UnitW {}, ArrayU { u, c, L.sy, L.sz }, dia[c]);
+  res[c] = residual_close (s.a, s.b, rhs[c], u[c]);
 }
 
 template <bool NORM>
@@ -1378,10 +1243,9 @@ int launch_residual (gfship_domain * dom, int level, const double * u, const dou
     GFSHIP_HIP (hipGetLastError ());
     return GFSHIP_OK;
   }
-  if (dom->dim == 3)
-    hipLaunchKernelGGL (residual_kernel<3>, grid, block, 0, dom->stream, L, u, rhs, dia, res);
-  else
-    hipLaunchKernelGGL (residual_kernel<2>, grid, block, 0, dom->stream, L, u, rhs, dia, res);
+  with_bools ([&] (auto D3) {
+    hipLaunchKernelGGL (residual_kernel<decltype (D3)::value ? 3 : 2>, grid, block, 0, dom->stream, L, u, rhs, dia, res);
+  }, dom->dim == 3);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
@@ -1393,16 +1257,8 @@ residual_weighted_kernel (Layout L, const double * __restrict__ u, const double 
 			  const double * __restrict__ dia, double * __restrict__ res, W6 wf)
 {
   CELL_LOOP_PROLOGUE (L);
-  double a = dia[c], b = 0.;
-  { const double g = wf.p[0][c]; a += g; b += g*u[c + 1]; }
-  { const double g = wf.p[1][c]; a += g; b += g*u[c - 1]; }
-  { const double g = wf.p[2][c]; a += g; b += g*u[c + L.sy]; }
-  { const double g = wf.p[3][c]; a += g; b += g*u[c - L.sy]; }
-  if (DIM == 3) {
-    { const double g = wf.p[4][c]; a += g; b += g*u[c + L.sz]; }
-    { const double g = wf.p[5][c]; a += g; b += g*u[c - L.sz]; }
-  }
-  res[c] = rhs[c] - (b - u[c]*a);
+  const FaceSums s = face_sums<DIM> (ArrayW { &wf, c }, ArrayU { u, c, L.sy, L.sz }, dia[c]);
+  res[c] = residual_close (s.a, s.b, rhs[c], u[c]);
 }
 
 RelaxOp weighted_op (gfship_domain * dom, int level)
@@ -1421,12 +1277,11 @@ int launch_residual_weighted (gfship_domain * dom, int level, const double * u, 
   dim3 grid, block;
   cell_grid (L, &grid, &block);
   RelaxOp op = weighted_op (dom, level);
-  W6 wf;
-  for (int d = 0; d < 6; d++) wf.p[d] = op.wf[d];
-  if (dom->dim == 3)
-    hipLaunchKernelGGL (residual_weighted_kernel<3>, grid, block, 0, dom->stream, L, u, rhs, dia, res, wf);
-  else
-    hipLaunchKernelGGL (residual_weighted_kernel<2>, grid, block, 0, dom->stream, L, u, rhs, dia, res, wf);
+  W6 wf = op_weights (&op);
+  with_bools ([&] (auto D3) {
+    hipLaunchKernelGGL (residual_weighted_kernel<decltype (D3)::value ? 3 : 2>, grid, block, 0, dom->stream, L, u, rhs,
+			dia, res, wf);
+  }, dom->dim == 3);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
@@ -1698,23 +1553,8 @@ int launch_fill (gfship_domain * dom, int level, double * a, double value)
 // K7: norms.  gfs_norm_add (src/fluid.c:2139-2154) per cell on val = a[c]/scale with weight w;
 // the sums are tree-reduced (deterministic, but not the reference's sequential order: they
 // agree to rounding); infty = max |val| is exact.  out = { sum w*val, sum w*|val|,
-// sum w*|val|*|val|, max |val|, sum a[c] }.
+// sum w*|val|*|val|, max |val|, sum a[c] }: block_norm_sums of cell_loop.hpp.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum (double v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    v += __shfl_down (v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max (double v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    v = fmax (v, __shfl_down (v, o, 64));
-  return v;
-}
-
 // rows of cells per workgroup (grid-stride), lanes along x: no per-cell index arithmetic.  EXACT_INV:
 // scale is a power of two (h*h), the division raw/scale is the exact multiplication by 1/scale.
 template <bool EXACT_INV>
@@ -1740,20 +1580,7 @@ norm_partial_kernel (Layout L, const double * __restrict__ a, double scale, doub
       s4 += raw;
     }
   }
-  __shared__ double sh[5][4];
-  s0 = wave_sum (s0); s1 = wave_sum (s1); s2 = wave_sum (s2); s3 = wave_max (s3); s4 = wave_sum (s4);
-  int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) { sh[0][w] = s0; sh[1][w] = s1; sh[2][w] = s2; sh[3][w] = s3; sh[4][w] = s4; }
-  __syncthreads ();
-  if (threadIdx.x == 0) {
-    int nw = blockDim.x >> 6;
-    double r0 = 0., r1 = 0., r2 = 0., r3 = 0., r4 = 0.;
-    for (int q = 0; q < nw; q++) {
-      r0 += sh[0][q]; r1 += sh[1][q]; r2 += sh[2][q]; r3 = fmax (r3, sh[3][q]); r4 += sh[4][q];
-    }
-    double * p = partial + 5*(size_t) blockIdx.x;
-    p[0] = r0; p[1] = r1; p[2] = r2; p[3] = r3; p[4] = r4;
-  }
+  block_norm_sums (s0, s1, s2, s3, s4, partial, blockIdx.x);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1764,6 +1591,8 @@ norm_final_kernel (const double * __restrict__ partial, int nblocks, double * __
     const double * p = partial + 5*(size_t) q;
     s0 += p[0]; s1 += p[1]; s2 += p[2]; s3 = fmax (s3, p[3]); s4 += p[4];
   }
+  // block_norm_sums of the 4 wavefronts, as written before the shared header: through it the compiler orders
+  // the kernel's first instructions differently
   __shared__ double sh[5][4];
   s0 = wave_sum (s0); s1 = wave_sum (s1); s2 = wave_sum (s2); s3 = wave_max (s3); s4 = wave_sum (s4);
   int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1847,16 +1676,9 @@ residual_norm_kernel (Layout L, const double * __restrict__ u, const double * __
     const long row = L.idx (1, j, k);
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
       const long c = row + i;
-      double a = dia ? dia[c] : 0., b = 0.;     /* dia == nullptr: the level holds zeros (not read) */
-      a += 1.; b += 1.*u[c + 1];
-      a += 1.; b += 1.*u[c - 1];
-      a += 1.; b += 1.*u[c + L.sy];
-      a += 1.; b += 1.*u[c - L.sy];
-      if (DIM == 3) {
-	a += 1.; b += 1.*u[c + L.sz];
-	a += 1.; b += 1.*u[c - L.sz];
-      }
-      const double raw = rhs[c] - (b - u[c]*a);
+      /* dia == nullptr: the level holds zeros (not read) */
+      const FaceSums f = face_sums<DIM> (UnitW {}, ArrayU { u, c, L.sy, L.sz }, dia ? dia[c] : 0.);
+      const double raw = residual_close (f.a, f.b, rhs[c], u[c]);
       res[c] = raw;
       double val = raw*inv;
       s0 += weight*val;
@@ -1867,20 +1689,7 @@ residual_norm_kernel (Layout L, const double * __restrict__ u, const double * __
       s4 += raw;
     }
   }
-  __shared__ double sh[5][4];
-  s0 = wave_sum (s0); s1 = wave_sum (s1); s2 = wave_sum (s2); s3 = wave_max (s3); s4 = wave_sum (s4);
-  int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) { sh[0][w] = s0; sh[1][w] = s1; sh[2][w] = s2; sh[3][w] = s3; sh[4][w] = s4; }
-  __syncthreads ();
-  if (threadIdx.x == 0) {
-    int nw = blockDim.x >> 6;
-    double r0 = 0., r1 = 0., r2 = 0., r3 = 0., r4 = 0.;
-    for (int q = 0; q < nw; q++) {
-      r0 += sh[0][q]; r1 += sh[1][q]; r2 += sh[2][q]; r3 = fmax (r3, sh[3][q]); r4 += sh[4][q];
-    }
-    double * p = partial + 5*(size_t) blockIdx.x;
-    p[0] = r0; p[1] = r1; p[2] = r2; p[3] = r3; p[4] = r4;
-  }
+  block_norm_sums (s0, s1, s2, s3, s4, partial, blockIdx.x);
 }
 
 // The same for 3-D levels with n >= 4, two cells of a row per thread: the rows of a level start 16-byte
@@ -1912,6 +1721,8 @@ residual_norm2_kernel (Layout L, const double * __restrict__ u, const double * _
     d2 di = { 0., 0. };
     if (dia) di = *(const d2 *) (dia + c);
     d2 out;
+    // face_sums<3> (UnitW) and residual_close of the two cells, as written before the shared header: through
+    // them the compiler schedules this kernel differently
     {
       double a = di.x, b = 0.;
       a += 1.; b += 1.*uc.y;
@@ -1947,6 +1758,7 @@ residual_norm2_kernel (Layout L, const double * __restrict__ u, const double * _
     }
   }
   if (!NORM) return;
+  // block_norm_sums, as written before the shared header (two instructions come out swapped through it)
   __shared__ double sh[5][4];
   s0 = wave_sum (s0); s1 = wave_sum (s1); s2 = wave_sum (s2); s3 = wave_max (s3); s4 = wave_sum (s4);
   int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1994,12 +1806,11 @@ int launch_residual_norm (gfship_domain * dom, int level, const double * u, cons
     hipLaunchKernelGGL (residual_norm2_kernel<true>, dim3 (nblocks), dim3 (256), 0, dom->stream, L, u,
 			rhs, dia_zero ? nullptr : dia, res, 1./scale, weight, partial);
   }
-  else if (dom->dim == 3)
-    hipLaunchKernelGGL (residual_norm_kernel<3>, dim3 (nblocks), dim3 (block), 0, dom->stream, L, u,
-			rhs, dia_zero ? nullptr : dia, res, 1./scale, weight, partial);
   else
-    hipLaunchKernelGGL (residual_norm_kernel<2>, dim3 (nblocks), dim3 (block), 0, dom->stream, L, u,
-			rhs, dia_zero ? nullptr : dia, res, 1./scale, weight, partial);
+    with_bools ([&] (auto D3) {
+      hipLaunchKernelGGL (residual_norm_kernel<decltype (D3)::value ? 3 : 2>, dim3 (nblocks), dim3 (block), 0,
+			  dom->stream, L, u, rhs, dia_zero ? nullptr : dia, res, 1./scale, weight, partial);
+    }, dom->dim == 3);
   hipLaunchKernelGGL (norm_final_kernel, dim3 (1), dim3 (256), 0, dom->stream,
 		      partial, nblocks, result);
   GFSHIP_HIP (hipGetLastError ());
@@ -2180,12 +1991,10 @@ int launch_relax_mpi_first (gfship_domain * dom, unsigned dimension, int level, 
     const int count = P->first[s + 1] - P->first[s];
     const int * cells = P->cells + P->first[s];
     const int block = 256, grid = (count + block - 1)/block;
-#define LS_LAUNCH(D, O) hipLaunchKernelGGL ((relax_listed_kernel<D, O>), dim3 (grid), dim3 (block), 0, \
-					    dom->stream, cells, count, L.sy, L.sz, dimension, omega, \
-					    w, h2, u, rhs, dia)
-    if (dom->dim == 3) { if (kind) LS_LAUNCH (3, 1); else LS_LAUNCH (3, 0); }
-    else               { if (kind) LS_LAUNCH (2, 1); else LS_LAUNCH (2, 0); }
-#undef LS_LAUNCH
+    with_bools ([&] (auto D3, auto K1) {      /* kinds 0 and 1: the kernel takes no per-cell weights (the weighted relax loop does not come here) */
+      hipLaunchKernelGGL ((relax_listed_kernel<decltype (D3)::value ? 3 : 2, decltype (K1)::value ? 1 : 0>), dim3 (grid),
+			  dim3 (block), 0, dom->stream, cells, count, L.sy, L.sz, dimension, omega, w, h2, u, rhs, dia);
+    }, dom->dim == 3, kind != 0);
     if (s + 1 == P->shell_steps && after_shell && (r = (* after_shell) (ctx)))
       return r;
   }

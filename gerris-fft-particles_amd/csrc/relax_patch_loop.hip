@@ -108,7 +108,7 @@ __device__ __forceinline__ bool patch_same_xcd (const SkewLoopArgs & A, int t)
 }
 
 // one cell: relax, src/poisson.c:507-530, unit weights, d = 0..5 = right, left, top, bottom, front, back.
-// Without dia the quotient by 6 comes from divide_by_6's reciprocal sequence (relax_skew.hpp), whose
+// Without dia the quotient by 6 comes from divide_by_6's reciprocal sequence (cell_update.hpp), whose
 // guard -- operands so small that the sequence could meet subnormals -- is only recorded here: the
 // four cells of a step form one dependent chain, a branch per cell would cut it into basic blocks
 // that the scheduler cannot interleave.  The step tests the four flags once and, in the (never
@@ -118,17 +118,10 @@ __device__ __forceinline__ double patch_cell (double right, double left, double 
 					      double front, double back, double rhs, double dia,
 					      bool & tiny, bool exact, double w = 1., double h2 = 1.)
 {
-  if (OP == 1)
-    return diffusion_cell (right, left, top, bottom, front, back, rhs, dia, w, h2);
-  double aa = HAS_DIA ? dia : 0., bb = 0.;
-  aa += 1.; bb += 1.*right;
-  aa += 1.; bb += 1.*left;
-  aa += 1.; bb += 1.*top;
-  aa += 1.; bb += 1.*bottom;
-  aa += 1.; bb += 1.*front;
-  aa += 1.; bb += 1.*back;
-  if (HAS_DIA)
-    return aa != 0. ? (bb - rhs)/aa : 0.;
+  if (OP == 1 || HAS_DIA)
+    return cell_update<3, OP> (kind_weights<OP> (w, UnitW {}), CellU {{ right, left, top, bottom, front, back }}, rhs,
+			       dia, nullptr, 3, 1., h2);
+  const double bb = face_sums<3> (UnitW {}, CellU {{ right, left, top, bottom, front, back }}, 0.).b;
   const double x = bb - rhs;
   if (exact)
     return x/6.;

@@ -209,14 +209,11 @@ relax_skew_kernel (SkewArgs A)
       const double Tn = X[B][iT], Fn = X[B][iF], Bo = Y[B][iBo], Bk = Y[B][iBk];
       // relax, src/poisson.c:507-530, unit weights, d = 0..5 = right,left,top,bottom,front,back
       const double Rv = (I + 1 < n) ? pR[q] : ghostR;
-      double aa = HAS_DIA ? pDia[q] : 0., bb = 0.;
-      aa += 1.; bb += 1.*Rv;        // right  (+x, old)
-      aa += 1.; bb += 1.*prev;      // left   (-x, new)
-      aa += 1.; bb += 1.*Tn;        // top    (+y = J-1, new)
-      aa += 1.; bb += 1.*Bo;        // bottom (-y = J+1, old)
-      aa += 1.; bb += 1.*Fn;        // front  (+z = K-1, new)
-      aa += 1.; bb += 1.*Bk;        // back   (-z = K+1, old)
-      const double v = HAS_DIA ? (aa != 0. ? (bb - pRhs[q])/aa : 0.) : divide_by_6 (bb - pRhs[q]);
+      // right (+x, old), left (-x, new), top (+y = J-1, new), bottom (-y = J+1, old), front (+z = K-1, new),
+      // back (-z = K+1, old)
+      const double v = HAS_DIA ?
+	cell_update<3, 0> (UnitW {}, CellU {{ Rv, prev, Tn, Bo, Fn, Bk }}, pRhs[q], pDia[q], nullptr, 3, 1., 1.) :
+	cell_update_six (CellU {{ Rv, prev, Tn, Bo, Fn, Bk }}, pRhs[q]);
       prev = act ? v : prev;
       // publish for step t + 1
       X[B ^ 1][iOwnX] = v;

@@ -92,11 +92,8 @@ struct SkewLoopArgs {
   unsigned * tile_xcd;
   int fault_tile;          // test of the error path (GFSHIP_FAULT_DROP_HANDOFF=tile): that tile publishes nothing in sweep 0
   int near_mode;           // stores towards a consumer on the same XCD: 0 agent scope like the others, 1 plain, 2 workgroup scope
-  // cell update (RelaxOp): 0 = relax (src/poisson.c:507-530, unit weights), 1 = diffusion_relax
-  // (:1471-1498) with the uniform face weight w of the level and h2 = h*h; dia is then rhoc
-  // 2 = relax with the six face weights f[d].v of every cell (gfs_poisson_coefficients with a
-  // GfsFunction alpha): ws[d] are skewed copies of the weights, streamed beside u / rhs / dia
-  // 3 = diffusion_relax with those six weights per cell (gfship_diffusion_coefficients_faces) and h2
+  // cell update: the RelaxOp kind (cell_update.hpp); dia is rhoc for kinds 1 and 3, ws[d] are skewed copies
+  // of the face weights of kinds 2 and 3, streamed beside u / rhs / dia
   int op;
   double w, h2;
   const double * ws[6];
@@ -114,59 +111,7 @@ __device__ __forceinline__ void store_sc1 (u64 * p, u64 v)
   __hip_atomic_store ((gu64 *) p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// (bb - rhs)/aa of relax (src/poisson.c:527) when dia == 0: aa = 0. + 1. + ... + 1. = 6. exactly,
-// and the correctly rounded quotient x/6 is obtained without the 14-instruction IEEE division
-// sequence: q = x*r, rem = fma (-q, 6, x) (exact), q' = fma (rem, r, q) with r = RN (1/6)
-// (Markstein's correction step).  x/6 = (x/2)/3 is never closer than 1/6 ulp to a rounding
-// boundary while q + rem*r differs from x/6 by less than 2^-52 ulp, so q' = RN (x/6) whenever
-// nothing underflows: for x = +0 the sequence gives +0 (x is never -0 here: it is a difference
-// whose minuend is a sum started from +0.), large x does not overflow (q <= x/6, the product in
-// the fma is exact), infinities and NaNs give NaN where the division gives inf/NaN (the solve has
-// diverged either way); only for 0 < |x| < 2^-1000, where q or the remainder may be subnormal,
-// the true division is used.  The guard is one exponent extraction and one integer compare, off
-// the dependent chain (tools/lab/step_lab.hip: the earlier two-sided floating-point range test
-// cost more than the division it replaced).  Checked against x/6. on 1.5e9 operands.
-__device__ __forceinline__ double divide_by_6 (double x)
-{
-  const double r = 0x1.5555555555555p-3;
-  const double q = x*r;
-  const double rem = __builtin_fma (- q, 6., x);
-  double q2 = __builtin_fma (rem, r, q);
-  // frexp exponent: 0 for zeros, infinities and NaNs; below -999 only for tiny non-zero x
-  const bool tiny = __builtin_amdgcn_frexp_exp (x) < -999;
-  if (__builtin_expect (__builtin_amdgcn_ballot_w64 (tiny) != 0, 0))
-    q2 = x/6.;
-  return q2;
-}
-
 int patch_loop_launch (gfship_domain * dom, const SkewLoopArgs & A, int ntiles, bool has_dia,
 		       unsigned nrelax, float * ms);
-
-// diffusion_relax of one cell, src/poisson.c:1471-1498 with gfs_face_cm_weighted_gradient's
-// same-level branch (relax_value<3, 1> of poisson_kernels.hip): d = 0..5 = right, left, top, bottom,
-// front, back
-__device__ __forceinline__ double diffusion_cell (double right, double left, double top, double bottom,
-						  double front, double back, double rhs, double dia,
-						  double w, double h2)
-{
-  double ga = 0., gb = 0.;
-  ga += w; gb += w*right;
-  ga += w; gb += w*left;
-  ga += w; gb += w*top;
-  ga += w; gb += w*bottom;
-  ga += w; gb += w*front;
-  ga += w; gb += w*back;
-  const double a = dia*h2;
-  ga = 1. + ga/a;
-  return (gb/a + rhs)/ga;
-}
-
-// the same with the six face weights of the cell already summed in the order d = 0..5:
-// ga = sum g_d, gb = sum g_d*u_d
-__device__ __forceinline__ double diffusion_cell_faces (double ga, double gb, double rhs, double dia, double h2)
-{
-  const double a = dia*h2;
-  return (gb/a + rhs)/(1. + ga/a);
-}
 
 } // namespace gfship

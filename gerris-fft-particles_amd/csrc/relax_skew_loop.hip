@@ -388,7 +388,8 @@ relax_skew_loop_kernel (SkewLoopArgs A)
 	  const bool act = I >= 0 && I < n;
 	  const int B = t & 1;
 	  const double Tn = X[B][iT], Fn = X[B][iF], Bo = Y[B][iBo], Bk = Y[B][iBk];
-	  // relax, src/poisson.c:507-530, unit weights, d = 0..5 = right,left,top,bottom,front,back
+	  // cell_update<3, OP> (cell_update_six without dia), kept as written before the shared header: through
+	  // the call the compiler allocates the registers of this kernel differently
 	  const double Rv = (I + 1 < n) ? pR[q] : ghostR;
 	  double aa = HAS_DIA ? pDia[q] : 0., bb = 0.;
 	  aa += 1.; bb += 1.*Rv;
@@ -398,10 +399,7 @@ relax_skew_loop_kernel (SkewLoopArgs A)
 	  aa += 1.; bb += 1.*Fn;
 	  aa += 1.; bb += 1.*Bk;
 	  if (OP >= 2) {
-	    // the face weights of the cell, d = 0..5 (g.a = w, g.b = w*u_nb): relax (src/poisson.c:507-530,
-	    // face_weighted_gradient's same-level branch src/fluid.c:858-864) starts its sum from dia;
-	    // diffusion_relax (OP == 3, src/poisson.c:1471-1498, gfs_face_cm_weighted_gradient's same-level
-	    // branch src/fluid.c:1361-1366) from 0. and takes its quotients in diffusion_cell_faces
+	    // the face weights of the cell, d = 0..5: relax starts its sum from dia, diffusion_relax (OP == 3) from 0.
 	    aa = OP == 2 ? pDia[q] : 0.; bb = 0.;
 	    const double * const wl = wring + (q % SK_WR)*(6*SK_NL) + tid;      // slot of row t
 	    { const double g = wl[0*SK_NL]; aa += g; bb += g*Rv; }
@@ -411,9 +409,12 @@ relax_skew_loop_kernel (SkewLoopArgs A)
 	    { const double g = wl[4*SK_NL]; aa += g; bb += g*Fn; }
 	    { const double g = wl[5*SK_NL]; aa += g; bb += g*Bk; }
 	  }
-	  const double v = OP == 3 ? diffusion_cell_faces (aa, bb, pRhs[q], pDia[q], A.h2) :
-	    OP == 1 ? diffusion_cell (Rv, prev, Tn, Bo, Fn, Bk, pRhs[q], pDia[q], A.w, A.h2) :
-	    HAS_DIA ? (aa != 0. ? (bb - pRhs[q])/aa : 0.) : divide_by_6 (bb - pRhs[q]);
+	  double v;
+	  if (OP == 3)
+	    v = diffusion_close_1 (aa, bb, pRhs[q], pDia[q], A.h2);
+	  else
+	    v = OP == 1 ? cell_update<3, 1> (UniformW { A.w }, CellU {{ Rv, prev, Tn, Bo, Fn, Bk }}, pRhs[q], pDia[q], nullptr, 3, 1., A.h2) :
+	      HAS_DIA ? (aa != 0. ? (bb - pRhs[q])/aa : 0.) : divide_by_6 (bb - pRhs[q]);
 	  prev = act ? v : prev;
 	  first = I == 0 ? v : first;
 	  X[B ^ 1][iOwnX] = v;
@@ -604,14 +605,7 @@ relax_wave_loop_kernel (SkewLoopArgs A)
 	  const double back = lastB ? hKp : pB[q];
 	  // relax, src/poisson.c:507-530, unit weights, d = 0..5 = right,left,top,bottom,front,back
 	  const double Rv = (I + 1 < n) ? Rn : ghostR;
-	  double bb = 0.;
-	  bb += 1.*Rv;
-	  bb += 1.*prev;
-	  bb += 1.*top;
-	  bb += 1.*bot;
-	  bb += 1.*front;
-	  bb += 1.*back;
-	  const double v = divide_by_6 (bb - pRhs[q]);
+	  const double v = cell_update_six (CellU {{ Rv, prev, top, bot, front, back }}, pRhs[q]);
 	  prev = act ? v : prev;
 	  first = I == 0 ? v : first;
 	  N = v;

@@ -13,16 +13,10 @@
 // reference scatters (+=) into both cells of a face in traversal order, the kernels gather per
 // cell in that same order (see flux_update_kernel).
 #include "gfship_internal.hpp"
+#include "cell_loop.hpp"
 #include <cfloat>
 
 namespace gfship {
-
-#define CELL_PROLOGUE(L)						\
-  int i = blockIdx.x*blockDim.x + threadIdx.x + 1;			\
-  int j = blockIdx.y + 1;						\
-  int k = (L).dim == 3 ? blockIdx.z + 1 : 0;				\
-  if (i > (L).n) return;						\
-  long c = (L).idx (i, j, k)
 
 // cells 0..n in every direction (faces on the + side of the low ghost layer included)
 #define EXT_PROLOGUE(L)							\
@@ -31,13 +25,6 @@ namespace gfship {
   int k = (L).dim == 3 ? blockIdx.z : 0;				\
   if (i > (L).n) return;						\
   long c = (L).idx (i, j, k)
-
-static inline void cell_grid (const Layout & L, dim3 * grid, dim3 * block)
-{
-  int b = L.n >= 256 ? 256 : L.n >= 128 ? 128 : 64;
-  *block = dim3 (b);
-  *grid = dim3 ((L.n + b - 1)/b, L.n, L.dim == 3 ? L.n : 1);
-}
 
 static inline void ext_grid (const Layout & L, dim3 * grid, dim3 * block)
 {
@@ -89,7 +76,7 @@ template <int DIM>
 __global__ void __launch_bounds__(256)
 divergence_kernel (Layout L, CPtr3 un, double * __restrict__ div, double dt)
 {
-  CELL_PROLOGUE (L);
+  CELL_LOOP_PROLOGUE (L);
   const long off[3] = { 1, L.sy, L.sz };
   double h = 1./L.n;
   double d_ = 0.;
@@ -127,7 +114,7 @@ template <int DIM>
 __global__ void __launch_bounds__(256)
 centered_gradient_kernel (Layout L, const double * __restrict__ p, Ptr3 g)
 {
-  CELL_PROLOGUE (L);
+  CELL_LOOP_PROLOGUE (L);
   const long off[3] = { 1, L.sy, L.sz };
   double h = 1./L.n;
 #pragma unroll
@@ -148,7 +135,7 @@ template <int DIM>
 __global__ void __launch_bounds__(256)
 correct_centered_kernel (Layout L, Ptr3 u, CPtr3 g, double dt)
 {
-  CELL_PROLOGUE (L);
+  CELL_LOOP_PROLOGUE (L);
 #pragma unroll
   for (int cc = 0; cc < DIM; cc++)
     u.p[cc][c] -= g.p[cc][c]*dt;
@@ -196,14 +183,6 @@ correct_centered_coarse_kernel (Layout L, Layout Lc, Ptr3 u, CPtr3 g, double dt,
 // monotonically non-increasing in |x|, roundings included, so the minimum of minimum_mac_cfl /
 // minimum_cfl (src/domain.c:2824-2890) is that expression of the maximum.
 // h = 1/n is a power of two: /h is written as an exact scaling by n.
-__device__ __forceinline__ double wave_max_d (double v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    v = fmax (v, __shfl_down (v, o, 64));
-  return v;
-}
-
 // Index space: one thread per (i,j,k) with i in 1..n, j and k in 0..n; the thread of i = 1 also
 // takes the column i = 0 (faces on the low x side), so that rows map to whole 256-thread blocks.
 template <int DIM, bool FUSE_U>
@@ -258,7 +237,7 @@ project_correct_kernel (Layout L, const double * __restrict__ p, Ptr3 un, Ptr3 g
   }
   if (partial_max) {
     __shared__ double sh[4];
-    mx = wave_max_d (mx);
+    mx = wave_max (mx);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
     __syncthreads ();
     if (threadIdx.x == 0) {
@@ -477,7 +456,7 @@ project_correct_lazy2_kernel (Layout L, const double * __restrict__ p, CPtr3 u, 
   }
   if (partial_max) {
     __shared__ double sh[4];
-    mx = wave_max_d (mx);
+    mx = wave_max (mx);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
     __syncthreads ();
     if (threadIdx.x == 0) {
@@ -613,7 +592,7 @@ project_correct_lazy_kernel (Layout L, const double * __restrict__ p, CPtr3 u, P
   }
   if (partial_max) {
     __shared__ double sh[4];
-    mx = wave_max_d (mx);
+    mx = wave_max (mx);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
     __syncthreads ();
     if (threadIdx.x == 0) {
@@ -638,7 +617,7 @@ cfl_from_max_kernel (double * __restrict__ partial_max, int nblocks, double leng
     partial_max[q] = 0.;
   }
   __shared__ double sh[4];
-  m = wave_max_d (m);
+  m = wave_max (m);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
   __syncthreads ();
   if (threadIdx.x == 0) {
@@ -780,7 +759,7 @@ __global__ void __launch_bounds__(256)
 variable_mac_source_kernel (Layout L, const double * __restrict__ v, CPtr3 D,
 			    const double * __restrict__ alpha, double * __restrict__ out)
 {
-  CELL_PROLOGUE (L);
+  CELL_LOOP_PROLOGUE (L);
   const long off[3] = { 1, L.sy, L.sz };
   /* h = 1/n is a power of two: the division by h*h is an exact scaling by n*n */
   const double rh2 = (double) L.n*(double) L.n;
@@ -802,7 +781,7 @@ advected_face_values_kernel (Layout L, const double * __restrict__ v, CPtr3 u, C
 			     double dt, int use_centered_velocity, int gradient, Ptr6 fv, int cmask,
 			     double visc, double gsrc, const double * __restrict__ msrc_cell)
 {
-  CELL_PROLOGUE (L);
+  CELL_LOOP_PROLOGUE (L);
   const long off[3] = { 1, L.sy, L.sz };
   const double size = 1./L.n;
   const double v0 = v[c];
@@ -960,7 +939,7 @@ __global__ void __launch_bounds__(256)
 flux_update_kernel (Layout L, double * __restrict__ v, CPtr3 un, CPtr6 fv,
 		    const double * __restrict__ gm, const double * __restrict__ gc, double dt, double gsrc)
 {
-  CELL_PROLOGUE (L);
+  CELL_LOOP_PROLOGUE (L);
   const int n = L.n;
   const double h = 1./n;
   double acc = 0.;
@@ -2816,14 +2795,6 @@ predict_un_sweep_kernel (Layout L, CPtr3 u, Ptr3 un, double dt, Visc3 visc, doub
 // ---------------------------------------------------------------------------------------------
 // K19: minimum_mac_cfl / minimum_cfl, src/domain.c:2824-2923: min of (h/|un|)^2 and (h/|u|)^2
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_min (double v)
-{
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    v = fmin (v, __shfl_down (v, o, 64));
-  return v;
-}
-
 template <int DIM>
 __global__ void __launch_bounds__(256)
 cfl_partial_kernel (Layout L, CPtr3 u, CPtr3 un, Visc3 visc, CPtr3 msrc, double * __restrict__ partial)
@@ -2902,7 +2873,7 @@ template <int DIM>
 __global__ void __launch_bounds__(256)
 coarse_init_kernel (Layout Lc, Layout Lf, CoarseArgs A)
 {
-  CELL_PROLOGUE (Lc);
+  CELL_LOOP_PROLOGUE (Lc);
   for (int f = 0; f < A.nf; f++) {        // every variable of the domain (src/adaptive.c:43-58)
     double val = 0., sa = 0.;
 #pragma unroll
@@ -2923,7 +2894,7 @@ template <int DIM>
 __global__ void __launch_bounds__(256)
 velocity_divergence_kernel (Layout L, CPtr3 u, double * __restrict__ out)
 {
-  CELL_PROLOGUE (L);
+  CELL_LOOP_PROLOGUE (L);
   const long off[3] = { 1, L.sy, L.sz };
   double h = 1./L.n;
   double div = 0.;

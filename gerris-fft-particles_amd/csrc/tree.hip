@@ -25,6 +25,7 @@
 // src/fluid.c:1843-1864,2310-2324, src/domain.c:2239-2288,2824-2923, src/simulation.c:432-557,
 // 1569-1633, src/ftt.c:45-83,169-192,2013-2074 (refinement with the neighbour and corner rules).
 #include "gfship_internal.hpp"
+#include "cell_loop.hpp"
 #include "tree.hpp"
 #include <algorithm>
 #include <array>
@@ -636,12 +637,8 @@ __device__ inline void atomic_min_pos (double * addr, double v)
 // the sum / maximum / minimum of a wavefront in lane 0 (every lane of the wavefront calls these): one atomic
 // per wavefront and number instead of one per cell -- 40 000 atomics on four addresses were the time of
 // t_residual (80 us)
-__device__ inline double wave_sum (double v)
-{
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down (v, o);
-  return v;
-}
-__device__ inline double wave_max (double v)
+// (wave_sum and wave_min: cell_loop.hpp; its wave_max is fmax, which drops a NaN)
+__device__ inline double wave_max_nan (double v)
 {
   for (int o = 32; o > 0; o >>= 1) {      /* a NaN wins, as it does in atomic_max_pos (its bits are the largest) */
     const double b = __shfl_down (v, o);
@@ -649,12 +646,6 @@ __device__ inline double wave_max (double v)
   }
   return v;
 }
-__device__ inline double wave_min (double v)
-{
-  for (int o = 32; o > 0; o >>= 1) v = fmin (v, __shfl_down (v, o));
-  return v;
-}
-
 // gfs_residual on the leaves + add_norm_residual (src/domain.c:2239-2246): the maximum is exact, the
 // sums are accumulated in no particular order (reported, never branched on)
 __global__ void t_residual (Topo T, const Cell * cells, int n, const double * u, const double * rhs,
@@ -673,7 +664,7 @@ __global__ void t_residual (Topo T, const Cell * cells, int n, const double * u,
     const double size = T.size (c);
     val = r/(1.*size*size);
   }
-  const double m = wave_max (fabs (val)), s1 = wave_sum (r), s2 = wave_sum (fabs (val)), s3 = wave_sum (val*val);
+  const double m = wave_max_nan (fabs (val)), s1 = wave_sum (r), s2 = wave_sum (fabs (val)), s3 = wave_sum (val*val);
   if ((threadIdx.x & 63) == 0) {
     atomic_max_pos (&red[0], m);
     atomicAdd (&red[1], s1);
@@ -702,7 +693,7 @@ __global__ void t_residual_tape (Topo T, const Cell * cells, const int * cell_of
     const double size = T.size (cells[t]);
     val = r/(1.*size*size);
   }
-  const double m = wave_max (fabs (val)), s1 = wave_sum (r), s2 = wave_sum (fabs (val)), s3 = wave_sum (val*val);
+  const double m = wave_max_nan (fabs (val)), s1 = wave_sum (r), s2 = wave_sum (fabs (val)), s3 = wave_sum (val*val);
   if ((threadIdx.x & 63) == 0) {
     atomic_max_pos (&red[0], m);
     atomicAdd (&red[1], s1);
@@ -746,7 +737,7 @@ __global__ void t_diffusion_residual (Topo T, const Cell * cells, int n, const d
     const double size = T.size (c);
     vol = T.dim == 3 ? size*size*size : size*size;
   }
-  const double m = wave_max (fabs (r)), s1 = wave_sum (vol*r), s2 = wave_sum (vol*fabs (r)), s3 = wave_sum (vol*r*r),
+  const double m = wave_max_nan (fabs (r)), s1 = wave_sum (vol*r), s2 = wave_sum (vol*fabs (r)), s3 = wave_sum (vol*r*r),
     s4 = wave_sum (vol);
   if ((threadIdx.x & 63) == 0) {
     atomic_max_pos (&red[0], m);

@@ -255,6 +255,8 @@ void go_diffusion_rhs (GoDomain * dom, GoField * v, GoField * rhs, GoField * rho
 { diffusion_rhs (dom, v, rhs, rhoc, beta); }
 void go_diffusion_residual (GoDomain * dom, GoField * u, GoField * rhs, GoField * rhoc, GoField * res)
 { diffusion_residual (dom, u, rhs, rhoc, res); }
+void go_diffusion_relax (GoDomain * dom, int level, GoField * u, GoField * res, GoField * dia)
+{ diffusion_relax (dom, level, u, res, dia); }
 void go_diffusion_cycle (GoDomain * dom, unsigned levelmin, unsigned depth, unsigned nrelax,
 			 GoField * u, GoField * rhs, GoField * rhoc, GoField * res)
 { diffusion_cycle (dom, levelmin, depth, nrelax, u, rhs, rhoc, res); }

@@ -65,6 +65,7 @@ def lib():
             "go_relax": (None, [vp, u, i, d, vp, vp, vp]),
             "go_relax_lexicographic": (None, [vp, u, i, d, vp, vp, vp]),
             "go_residual": (None, [vp, u, i, vp, vp, vp, vp]),
+            "go_diffusion_relax": (None, [vp, i, vp, vp, vp]),
             "go_norm_residual": (Norm, [vp, d, vp]),
             "go_norm_variable": (Norm, [vp, vp]),
             "go_poisson_cycle": (None, [vp, C.POINTER(MultilevelParams), vp, vp, vp, vp]),

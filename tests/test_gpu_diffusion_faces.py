@@ -9,9 +9,9 @@ given fields holding (beta*dt)*D_face, the product the device forms, and rhoc le
 
 Everything is compared with array_equal; the tree-reduced norm sums of the solve with the project's 1e-12.
 
-Shapes: the smallest at which each kernel family is the one that runs -- 8^2 the one-workgroup LDS loop,
-64^2 relax_rows2d_kernel, 16^3 the LDS loop and the coarse end, 32^3 the first level of the pipelined tile
-kernel, 128^3 (one case) the level the uniform coefficient sends to the 2 x 2 ring kernels.
+Shapes: the smallest at which each kernel family is the one that runs -- 8^2 and 64^2 the one-workgroup LDS
+loop, 128^2 (one case) relax_rows2d_kernel, 16^3 the LDS loop and the coarse end, 32^3 the first level of the
+pipelined tile kernel, 128^3 (one case) the level the uniform coefficient sends to the 2 x 2 ring kernels.
 """
 import ctypes as C
 
@@ -183,6 +183,25 @@ def test_cycle_by_hyperplanes(monkeypatch):
         p.same("cycle")
         kc = p.gd.kernel_counts()
         assert kc["DIFFUSION_FACES_HYPERPLANES"] > 0 and kc["DIFFUSION_FACES_PIPELINED"] == 0
+    finally:
+        p.destroy()
+
+
+@pytest.mark.parametrize("rows", [True, False])
+def test_cycle_at_128_squared_by_rows_and_by_hyperplanes(monkeypatch, rows):
+    """kind 3 in 2-D on a level that does not fit the one-workgroup LDS loop (64^2 and less do): one launch
+    per sweep by relax_rows2d_kernel<3>, and with GFSHIP_NO_ROWS2D relax_hyperplane_kernel<2, 3>"""
+    if not rows:
+        monkeypatch.setenv("GFSHIP_NO_ROWS2D", "1")
+    p = Pair(2, 7, 0.5)
+    try:
+        p.coefficients()
+        p.rhs()
+        p.residual()
+        p.cycle()
+        p.same("cycle")
+        kc = p.gd.kernel_counts()
+        assert kc["ROWS2D" if rows else "HYPERPLANES_2D"] > 0 and kc["HYPERPLANES_2D" if rows else "ROWS2D"] == 0
     finally:
         p.destroy()
 

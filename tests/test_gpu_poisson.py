@@ -598,6 +598,35 @@ def test_poisson_coefficients_with_alpha_bit_exact(dim, level, kind):
     assert np.array_equal(f["u"][0].leaf()[inner], f["u"][1].download()[inner])
 
 
+def test_weighted_sweeps_in_2d_by_hyperplanes(monkeypatch):
+    """relax_hyperplane_kernel<2, 2>: the sweeps of the test above at 8^2 with GFSHIP_NO_ROWS2D, one launch per
+    hyperplane instead of relax_rows2d_kernel<2>"""
+    monkeypatch.setenv("GFSHIP_NO_ROWS2D", "1")
+    L = O.lib()
+    dim, level, kind = 2, 3, "dirichlet"
+    side, bck = SIDES[kind]
+    rng = np.random.default_rng(177)
+    od, gd = _pair(dim, level, side)
+    oa, ga = _alpha_pair(od, gd, rng, kind)
+    od.poisson_coefficients_alpha(oa)
+    gd.poisson_coefficients_alpha(ga)
+    inner = (slice(1, -1),) * dim
+    f = _rand_fields(od, gd, ["u", "rhs", "dia"], rng)
+    n = 1 << level
+    for d in range(2 * dim):
+        val = rng.standard_normal(n ** (dim - 1))
+        f["u"][0].set_bc(d, bck, val)
+        f["u"][1].set_bc(d, bck, val)
+    L.go_bc(f["u"][0].ptr, f["u"][0].ptr, level)
+    gd.bc(f["u"][1])
+    for _ in range(2):
+        L.go_relax(od.ptr, dim, level, 1., f["u"][0].ptr, f["rhs"][0].ptr, f["dia"][0].ptr)
+        gd.relax(f["u"][1], f["rhs"][1], f["dia"][1])
+        assert np.array_equal(f["u"][0].leaf()[inner], f["u"][1].download()[inner])
+    kc = gd.kernel_counts()
+    assert kc["HYPERPLANES_2D"] == 2 and kc["ROWS2D"] == 0
+
+
 # ---------------------------------------------------------------------------------------------
 # the three implementations of the pipelined sweep (one line per thread; 2 x 2 lines per lane with
 # the rows streamed through registers, or through an LDS ring by a fourth wave) on every size and

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two builds of libgfship's objects, byte for byte.
 
-    tools/device_code_diff.py OBJDIR_A OBJDIR_B
+    tools/device_code_diff.py [--rename OLD=NEW]... OBJDIR_A OBJDIR_B
 
 For every *.o of OBJDIR_A: the .hip_fatbin section is taken out of both objects, the gfx950 code
 object unbundled, and its .text and .rodata compared.  Where a section differs (a changed order of
 template instantiations permutes .text) the kernels and functions are compared one by one instead:
 names, sizes and bytes of every defined symbol of the section; of a kernel descriptor (NAME.kd in
 .rodata) all but bytes 16-23, the offset from the descriptor to the kernel's code, which moves with
-the kernel.  Prints one line per file; exit status 1 if any file differs."""
+the kernel.  --rename OLD=NEW (mangled names, repeatable) compares the kernel OLD of OBJDIR_A with the kernel
+NEW of OBJDIR_B, for a kernel whose name changed with the type of an argument.  Prints one line per file; exit
+status 1 if any file differs."""
 import glob
 import os
 import subprocess
@@ -45,6 +47,9 @@ def section(co, name, tmp, tag):
         return f.read()
 
 
+RENAME = {}
+
+
 def symbols(co, sec, data):
     """{name: bytes} of the defined symbols of section `sec' (llvm-readobj --symbols)"""
     out, cur = {}, {}
@@ -64,7 +69,8 @@ def symbols(co, sec, data):
                 out[cur["Name"]] = (int(cur["Value"], 16), int(cur["Size"]))
             cur = {}
     code = {n: data[a - base:a - base + s] for n, (a, s) in out.items()}
-    return {n: c[:16] + c[24:] if n.endswith(".kd") else c for n, c in code.items()}
+    code = {n: c[:16] + c[24:] if n.endswith(".kd") else c for n, c in code.items()}
+    return {RENAME.get(n[:-3], n[:-3]) + ".kd" if n.endswith(".kd") else RENAME.get(n, n): c for n, c in code.items()}
 
 
 def main(a, b):
@@ -94,6 +100,11 @@ def main(a, b):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    args = sys.argv[1:]
+    while len(args) > 1 and args[0] == "--rename":
+        old, new = args[1].split("=")
+        RENAME[old] = new
+        args = args[2:]
+    if len(args) != 2:
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(args[0], args[1]))
