@@ -179,7 +179,9 @@ struct Run {
   Function * visc_fn[3] = { nullptr, nullptr, nullptr };
   int visc_line[3] = { 0, 0, 0 };
   gfship_field visc_dev[3][3] = { { -1, -1, -1 }, { -1, -1, -1 }, { -1, -1, -1 } };
-  gfship_field alpha_cell_dev = -1;      // alpha at the cell centres of every level (with a viscosity)
+  gfship_field alpha_cell_dev = -1;      // alpha at the cell centres of every level (with a viscosity or particle forces)
+  double alpha_cell_t = 0., mu_cell_t = 0.;   // the time alpha_cell_dev and mu_cell_dev were last evaluated at
+  gfship_field mu_cell_dev = -1;         // the viscosity function of U at the leaf centres (with particle forces)
   bool has_viscosity (int c) const { return visc[c] != 0. || visc_fn[c] != nullptr; }
   std::map<std::string, std::string> diff_set[3];
   std::vector<std::string> tracers;
@@ -198,6 +200,11 @@ struct Run {
   std::vector<std::unique_ptr<Event>> events;
   std::vector<std::unique_ptr<Output>> outputs;
   std::vector<std::unique_ptr<ParticleSpec>> plists;
+  bool particulate_forces () const        // a list of GfsParticulate with GfsParticleForce objects
+  {
+    for (auto & ps : plists) if (!ps->forces.empty ()) return true;
+    return false;
+  }
   std::vector<std::pair<gfship_init_spectra_params, std::vector<std::string>>> init_spectra;
   std::string particles_out;                     // --particles FILE: the lists at the end of the run
   Function * refine_fn = nullptr;                // GfsRefine given as a function
@@ -295,6 +302,9 @@ std::vector<double> & host_of (Run & R, int v)
     V.host.assign (R.total (), 0.);
   return V.host;
 }
+
+int refresh_alpha_cell (Run & R);        /* the fields of the fluid an event of a list with forces reads */
+int refresh_viscosity_cell (Run & R);
 
 void invalidate_device_copies (Run & R)
 {
@@ -879,7 +889,11 @@ void parse_object (Run & R, Reader & r)
       if (ps->forces.size () > 8) r.fail ("at most 8 forces");
     }
     if (numeric (r.peek (false))) r.number ();           /* idlast */
-    e->action = [ps] () {
+    Run * pr = &R;
+    e->action = [ps, pr] () {
+      /* the forces read the density and the viscosity of the fluid at the time of the event */
+      if (ps->pl && !ps->forces.empty () && (refresh_alpha_cell (*pr) || refresh_viscosity_cell (*pr)))
+	exit (1);
       if (ps->pl && gfship_particle_list_event (ps->pl) != GFSHIP_OK) {
 	fprintf (stderr, "gfship: %s\n", gfship_last_error ());
 	exit (1);
@@ -2203,8 +2217,11 @@ int refresh_alpha_cell (Run & R)
 {
   bool visc = false;
   for (int c = 0; c < R.dim; c++) visc = visc || R.has_viscosity (c);
-  if (!R.alpha || !visc || (R.alpha_static && R.alpha_cell_dev >= 0))
+  if (!R.alpha || !(visc || R.particulate_forces ()) || (R.alpha_static && R.alpha_cell_dev >= 0))
     return 0;
+  if (R.alpha_cell_dev >= 0 && R.alpha_cell_t == R.t)
+    return 0;                   /* already evaluated at this time */
+  R.alpha_cell_t = R.t;
   const Function * f = R.alpha;
   const bool first = R.alpha_cell_dev < 0;
   if (first) {
@@ -2228,6 +2245,39 @@ int refresh_alpha_cell (Run & R)
   }
   if (first)
     CHECK (gfship_sim_set_alpha_cell (R.sim, R.alpha_cell_dev));
+  return 0;
+}
+
+// the `mu' of the GfsDiffusion of U (update_mu / gfs_diffusion_cell, src/source.c:906-946): the function of
+// its GfsSourceDiffusion / GfsSourceViscosity at the centres of the leaf cells, evaluated the way
+// refresh_alpha_cell evaluates alpha -- what the GfsParticleForce objects take for the viscosity at the cell
+// of a particle (modules/particulatecommon.c:277-279).  Once for a function of x, y, z; before every event
+// of a list with forces, at the time of the event, for a function of t
+int refresh_viscosity_cell (Run & R)
+{
+  const Function * f = R.visc_fn[0];
+  if (!f || !R.particulate_forces ())
+    return 0;
+  const bool first = R.mu_cell_dev < 0;
+  if (!first && (!(f->kind == Function::COMPILED && f->uses_t) || R.mu_cell_t == R.t))
+    return 0;
+  R.mu_cell_t = R.t;
+  if (first) {
+    R.mu_cell_dev = gfship_field_alloc (R.dom, -1);
+    CHECK (R.mu_cell_dev);
+  }
+  const int n = R.n ();
+  std::vector<double> a (R.total (), 0.);
+  for (int k = R.dim == 3 ? 1 : 0; k <= (R.dim == 3 ? n : 0); k++)
+    for (int j = 1; j <= n; j++)
+      for (int i = 1; i <= n; i++) {
+	double p[3];
+	cell_pos (R, i, j, k, p);
+	a[R.idx (i, j, k)] = f->kind == Function::CONSTANT ? f->val : f->fn (p[0], p[1], p[2], R.t, nullptr);
+      }
+  CHECK (gfship_field_upload (R.dom, R.mu_cell_dev, R.level, a.data ()));
+  if (first)
+    CHECK (gfship_sim_set_viscosity_cell (R.sim, R.mu_cell_dev));
   return 0;
 }
 
@@ -2288,6 +2338,17 @@ int run (Run & R)
       return 1;
     }
   }
+  if (R.alpha && R.particulate_forces () && !R.tree_mode) {
+    std::vector<int> used;
+    if (R.alpha->kind == Function::VARIABLE) used.push_back (R.alpha->var);
+    else if (R.alpha->kind == Function::COMPILED) used = R.alpha->args;
+    if (!used.empty ()) {
+      /* the density of the fluid at a particle is alpha at the centre of its cell, evaluated on the host */
+      fprintf (stderr, "gfship: line %d: together with GfsParticulate forces alpha may depend on x, y, z and t (got `%s')\n",
+	       R.alpha_line, R.vars[used[0]].name.c_str ());
+      return 1;
+    }
+  }
   if (R.tree_mode)
     return run_tree (R);
   open_pipes (R);
@@ -2337,7 +2398,7 @@ int run (Run & R)
     }
     else if (R.visc_fn[c])
       apply_multilevel (gfship_sim_diffusion_params (R.sim, c), R.diff_set[c]);
-  if (refresh_viscosity (R)) return 1;
+  if (refresh_viscosity (R) || refresh_viscosity_cell (R)) return 1;
   // the particle lists: created (and the previous velocity of the GfsForceCoeff objects stored)
   // while the fields still hold the zeros of a fresh simulation, like the reference, which reads
   // the list before any GfsInit event runs (gfs_force_coeff_read, :181-187)

@@ -331,10 +331,14 @@ particle_list_event_kernel (PartArgs A, int depth)
 }
 
 // ---------------------------------------------------------------------------------------------
-// GfsParticulate with forces (modules/particulatecommon.c:91-842): uniform box, alpha = NULL
-// (fluid_rho = 1.), constant viscosity (GfsSourceDiffusion on U), no user coefficient functions
-// (cm = cl = 0.5, the default drag law).  Same operand order as the reference; pow (Re, 0.5) of
-// the drag law is evaluated as sqrt (Re) (correctly rounded; glibc's pow is within 0.52 ulp of it).
+// GfsParticulate with forces (modules/particulatecommon.c:91-842): uniform box.  Same operand order
+// as the reference; pow (Re, 0.5) of the drag law is evaluated as sqrt (Re) (correctly rounded;
+// glibc's pow is within 0.52 ulp of it).  The density and the viscosity of the fluid are those of the
+// cell that holds the particle (:273-279, 349-359, 439-445, 534-541, 631-632): the kernels are
+// instantiated on RHO (fluid_rho = 1./alpha_cell[idx]; false: alpha = NULL, fluid_rho = 1.) and on MU
+// (viscosity = mu_cell[idx], gfs_diffusion_cell; false: the constant of the launch).  <false, false>
+// takes ParticulateArgs itself: the kernel arguments, and with them the device code, of a build
+// without the two fields.
 // ---------------------------------------------------------------------------------------------
 enum { FORCE_INERTIAL = GFSHIP_FORCE_INERTIAL, FORCE_ADDEDMASS = GFSHIP_FORCE_ADDEDMASS,
        FORCE_LIFT = GFSHIP_FORCE_LIFT, FORCE_DRAG = GFSHIP_FORCE_DRAG, FORCE_BUOY = GFSHIP_FORCE_BUOY };
@@ -352,6 +356,31 @@ struct ParticulateArgs {
                                // GfsForceDrag in 2-D (two-component norm, particulatecommon.c:549-556)
 };
 
+// the arguments of an instantiation that reads a field of the fluid at the particle's cell
+struct ParticulateFieldArgs : ParticulateArgs {
+  const double * alpha_cell, * mu_cell;      // leaf level, layout of P.u; nullptr where not read
+};
+template <bool RHO, bool MU>
+using ParticulateArgsOf = std::conditional_t<RHO || MU, ParticulateFieldArgs, ParticulateArgs>;
+
+// fluid_rho (1./gfs_function_value (alpha, cell), :273-274) and the viscosity (gfs_diffusion_cell
+// (d->D, cell), :277-279) of cell idx
+template <bool RHO, class Args>
+__device__ __forceinline__ double cell_fluid_rho (const Args & A, long idx)
+{
+  if constexpr (RHO) return 1./A.alpha_cell[idx];
+  else return 1.;
+}
+
+// (MU = false: 0., never read -- the constant of the launch is read where it is used, as in a build
+// without the fields)
+template <bool MU, class Args>
+__device__ __forceinline__ double cell_viscosity (const Args & A, long idx)
+{
+  if constexpr (MU) return A.mu_cell[idx];
+  else return 0.;
+}
+
 // gfs_center_gradient, src/fluid.c:434-475, both neighbours at the same level (x1 = x2 = 1.)
 __device__ __forceinline__ double center_gradient (const double * __restrict__ v, long idx, long off)
 {
@@ -362,14 +391,14 @@ __device__ __forceinline__ double center_gradient (const double * __restrict__ v
 // compute_inertial_force, :285-336
 // (fvel: the fluid velocity interpolated at the particle, computed once per particle and shared with
 // the lift and drag forces: the same gfs_interpolate of the same fields)
-template <int DIM>
-__device__ void inertial_force (const ParticulateArgs & A, const int cell[3], const double p[3],
+template <int DIM, bool RHO, class Args>
+__device__ void inertial_force (const Args & A, const int cell[3], const double p[3],
 				long idx, const double fvel[3], double force[3])
 {
   const Layout & L = A.P.L;
   const long off[3] = { 1, (long) L.sy, (long) L.sz };
   const double size = 1./L.n;
-  const double fluid_rho = 1.;
+  const double fluid_rho = cell_fluid_rho<RHO> (A, idx);
   force[0] = force[1] = force[2] = 0.;
   if (!(A.P.dt > 0.))
     return;
@@ -390,9 +419,9 @@ __device__ void inertial_force (const ParticulateArgs & A, const int cell[3], co
 // Reynolds number from the relative velocity (all three components of the FttVectors), the sphere
 // diameter and the viscosity (0.001 where the reference substitutes it for a zero viscosity in the
 // added-mass and lift coefficients; the drag is then zero whatever its coefficient)
-template <int DIM>
+template <int DIM, bool RHO, bool MU>
 __global__ void __launch_bounds__(256)
-particulate_coeff_inputs_kernel (ParticulateArgs A, int depth)
+particulate_coeff_inputs_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
 {
   const PartArgs & P = A.P;
   int q = blockIdx.x*blockDim.x + threadIdx.x;
@@ -403,14 +432,17 @@ particulate_coeff_inputs_kernel (ParticulateArgs A, int depth)
   int cell[3];
   if (!locate<DIM> (depth, p, cell)) return;
   const unsigned o = A.orig[q];
-  const double fluid_rho = 1.;
+  const long idx = RHO || MU ? L.idx (cell[0], cell[1], DIM == 3 ? cell[2] : 0) : 0;
+  const double fluid_rho = cell_fluid_rho<RHO> (A, idx);
+  const double mu = cell_viscosity<MU> (A, idx);
   double rel[3] = { 0. - A.vel[0][o], 0. - A.vel[1][o], 0. - A.vel[2][o] };
 #pragma unroll
   for (int c = 0; c < DIM; c++)
     rel[c] = interpolate<DIM> (L, P.u[c], cell, p) - A.vel[c][o];
   const double norm = sqrt (rel[0]*rel[0] + rel[1]*rel[1] + rel[2]*rel[2]);
   const double dia = A.dia[o];
-  const double viscosity = A.viscosity == 0 ? 0.001 : A.viscosity;
+  const double cell_visc = MU ? mu : A.viscosity;
+  const double viscosity = cell_visc == 0 ? 0.001 : cell_visc;      /* :372-375, 461-464 */
   A.cin[0][q] = norm*dia*fluid_rho/viscosity;
   A.cin[1][q] = rel[0]; A.cin[2][q] = rel[1]; A.cin[3][q] = rel[2];
   A.cin[4][q] = dia;
@@ -419,9 +451,9 @@ particulate_coeff_inputs_kernel (ParticulateArgs A, int depth)
 }
 
 // gfs_particulate_event (:768-842) in a gfs_particle_list_event (:980-1015)
-template <int DIM>
+template <int DIM, bool RHO, bool MU>
 __global__ void __launch_bounds__(256)
-particulate_list_event_kernel (ParticulateArgs A, int depth)
+particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
 {
   const PartArgs & P = A.P;
   int q = blockIdx.x*blockDim.x + threadIdx.x;
@@ -439,7 +471,10 @@ particulate_list_event_kernel (ParticulateArgs A, int depth)
   const long idx = L.idx (cell[0], cell[1], DIM == 3 ? cell[2] : 0);
   const long off[3] = { 1, (long) L.sy, (long) L.sz };
   const double size = 1./L.n;
-  const double fluid_rho = 1.;
+  // the two fields of the fluid at the particle's cell: loads that depend on idx alone, issued here with
+  // the first gathers of the interpolation, not behind its chain
+  const double fluid_rho = cell_fluid_rho<RHO> (A, idx);
+  const double mu = cell_viscosity<MU> (A, idx);
   const double dt = P.dt;
   double po[3] = { p[0], p[1], p[2] };
   double vel[3] = { A.vel[0][o], A.vel[1][o], A.vel[2][o] };
@@ -461,7 +496,7 @@ particulate_list_event_kernel (ParticulateArgs A, int depth)
       fvel[c] = interpolate<DIM> (L, P.u[c], cell, p);
   }
   if (need_dudt)
-    inertial_force<DIM> (A, cell, p, idx, fvel, dudt);
+    inertial_force<DIM, RHO> (A, cell, p, idx, fvel, dudt);
   for (int f = 0; f < A.nforces; f++) {
     double force[3] = { 0., 0., 0. };
     switch (A.forces[f]) {
@@ -511,9 +546,17 @@ particulate_list_event_kernel (ParticulateArgs A, int depth)
       const double dia = A.dia[o];
       const double norm = DIM == 3 ? sqrt (rel[0]*rel[0] + rel[1]*rel[1] + rel[2]*rel[2]) :
 	sqrt (rel[0]*rel[0] + rel[1]*rel[1]);
-      if (A.viscosity == 0)
-	break;
-      const double Re = norm*dia*fluid_rho/A.viscosity;
+      double Re;
+      if constexpr (MU) {
+	if (mu == 0)              /* :561-562: no drag in a cell without viscosity */
+	  break;
+	Re = norm*dia*fluid_rho/mu;
+      }
+      else {
+	if (A.viscosity == 0)
+	  break;
+	Re = norm*dia*fluid_rho/A.viscosity;
+      }
       double cd;
       if (A.coef[f])
 	cd = A.coef[f][q];
@@ -554,6 +597,12 @@ particulate_list_event_kernel (ParticulateArgs A, int depth)
   A.mass[o] = mass;
   particle_bc_and_store<DIM> (P, q, depth, cell, p, po);
 }
+
+// the instantiations without fields come first, in the order of a build without the two fields
+template __global__ void particulate_coeff_inputs_kernel<3, false, false> (ParticulateArgs, int);
+template __global__ void particulate_coeff_inputs_kernel<2, false, false> (ParticulateArgs, int);
+template __global__ void particulate_list_event_kernel<3, false, false> (ParticulateArgs, int);
+template __global__ void particulate_list_event_kernel<2, false, false> (ParticulateArgs, int);
 
 
 // mpi_send_particle (modules/particulatecommon.c:3218-3222): the particles marked 2 + d go into the
@@ -683,7 +732,11 @@ using namespace gfship;
 
 extern "C" {
 
-struct gfship_sim_view { gfship_domain * dom; const gfship_field * u; double dt; double visc; int visc_faces; };
+struct gfship_sim_view {
+  gfship_domain * dom; const gfship_field * u; double dt; double visc; int visc_faces;
+  int has_alpha;                    /* gfship_sim_set_alpha */
+  gfship_field alpha_cell, mu;      /* gfship_sim_set_alpha_cell, gfship_sim_set_viscosity_cell; -1: not set */
+};
 gfship_sim_view gfship_sim_view_get (gfship_sim * s);   /* simulation.hip */
 
 int gfship_particles_create (gfship_particles ** out, gfship_sim * sim, int np,
@@ -1045,10 +1098,27 @@ static int store_previous_vel (gfship_particles * pl)
   return GFSHIP_OK;
 }
 
-static int particulate_event (gfship_particles * pl, const PartArgs & P, double viscosity)
+// the fields of the fluid the forces of a list read (fluid_rho and viscosity of compute_*_force): alpha
+// at the cell centres whenever the simulation has it, the viscosity of U at the leaf centres where U
+// has one -- which it must where the viscosity of U is given on the faces
+static int particulate_fluid_check (const gfship_sim_view & v)
+{
+  GFSHIP_CHECK (!v.visc_faces || v.mu >= 0, GFSHIP_EUNSUPPORTED,
+		"particle forces together with a viscosity that varies in space need the viscosity at the "
+		"centres of the leaf cells (gfs_diffusion_cell): call gfship_sim_set_viscosity_cell first");
+  GFSHIP_CHECK (!v.has_alpha || v.alpha_cell >= 0, GFSHIP_EUNSUPPORTED,
+		"particle forces together with GfsPhysicalParams { alpha } need alpha at the cell centres "
+		"(fluid_rho = 1./alpha): call gfship_sim_set_alpha_cell first");
+  return GFSHIP_OK;
+}
+
+static int particulate_event (gfship_particles * pl, const PartArgs & P, const gfship_sim_view & v)
 {
   gfship_domain * dom = pl->dom;
-  ParticulateArgs A;
+  ParticulateFieldArgs A;
+  const bool rho = v.alpha_cell >= 0, mu = v.mu >= 0;
+  A.alpha_cell = rho ? dom->fields[v.alpha_cell].lev[dom->depth] : nullptr;
+  A.mu_cell = mu ? dom->fields[v.mu].lev[dom->depth] : nullptr;
   A.P = P;
   A.orig = pl->orig;
   for (int c = 0; c < 3; c++) {
@@ -1060,7 +1130,7 @@ static int particulate_event (gfship_particles * pl, const PartArgs & P, double 
   A.mass = pl->mass; A.volume = pl->volume; A.dia = pl->dia;
   A.nforces = pl->nforces;
   for (int f = 0; f < 8; f++) A.forces[f] = pl->forces[f];
-  A.viscosity = viscosity;
+  A.viscosity = v.visc;
   int block = 256, grid = (pl->n + block - 1)/block;
   bool any = false;
   for (int f = 0; f < 8; f++) {
@@ -1085,12 +1155,12 @@ static int particulate_event (gfship_particles * pl, const PartArgs & P, double 
       pl->coef_cap = pl->cap;
     }
     for (int q = 0; q < 6; q++) A.cin[q] = pl->cin[q];
-    if (dom->dim == 3)
-      hipLaunchKernelGGL (particulate_coeff_inputs_kernel<3>, dim3 (grid), dim3 (block), 0, dom->stream,
-			  A, dom->depth);
-    else
-      hipLaunchKernelGGL (particulate_coeff_inputs_kernel<2>, dim3 (grid), dim3 (block), 0, dom->stream,
-			  A, dom->depth);
+    with_bools ([&] (auto D3, auto RHO, auto MU) {
+      constexpr int DIM = decltype (D3)::value ? 3 : 2;
+      constexpr bool R = decltype (RHO)::value, M = decltype (MU)::value;
+      hipLaunchKernelGGL ((particulate_coeff_inputs_kernel<DIM, R, M>), dim3 (grid), dim3 (block), 0, dom->stream,
+			  static_cast<const ParticulateArgsOf<R, M> &> (A), dom->depth);
+    }, dom->dim == 3, rho, mu);
     GFSHIP_HIP (hipGetLastError ());
     const double * rel[3] = { pl->cin[1], pl->cin[2], pl->cin[3] };
     for (int f = 0; f < pl->nforces; f++)
@@ -1104,12 +1174,12 @@ static int particulate_event (gfship_particles * pl, const PartArgs & P, double 
 	A.coef[f] = pl->coef[f];
       }
   }
-  if (dom->dim == 3)
-    hipLaunchKernelGGL (particulate_list_event_kernel<3>, dim3 (grid), dim3 (block), 0, dom->stream,
-			A, dom->depth);
-  else
-    hipLaunchKernelGGL (particulate_list_event_kernel<2>, dim3 (grid), dim3 (block), 0, dom->stream,
-			A, dom->depth);
+  with_bools ([&] (auto D3, auto RHO, auto MU) {
+    constexpr int DIM = decltype (D3)::value ? 3 : 2;
+    constexpr bool R = decltype (RHO)::value, M = decltype (MU)::value;
+    hipLaunchKernelGGL ((particulate_list_event_kernel<DIM, R, M>), dim3 (grid), dim3 (block), 0, dom->stream,
+			static_cast<const ParticulateArgsOf<R, M> &> (A), dom->depth);
+  }, dom->dim == 3, rho, mu);
   GFSHIP_HIP (hipGetLastError ());
   // the velocity of this step for the inertial force of the next one (:1003-1012: only for
   // GfsForceInertial objects)
@@ -1156,9 +1226,10 @@ int gfship_particles_set_forces (gfship_particles * pl, int nforces, const int *
   GFSHIP_CHECK (pl && (nforces == 0 || kinds), GFSHIP_EINVAL, "null argument");
   GFSHIP_CHECK (pl->particulate, GFSHIP_EINVAL, "forces act on particulates (gfship_particles_set_particulate)");
   GFSHIP_CHECK (nforces >= 0 && nforces <= 8, GFSHIP_EINVAL, "at most 8 forces");
-  /* the drag laws take one viscosity (gfship_sim_set_viscosity of U) */
-  GFSHIP_CHECK (nforces == 0 || !gfship_sim_view_get (pl->sim).visc_faces, GFSHIP_EUNSUPPORTED,
-		"particle forces together with a viscosity that varies in space are not supported");
+  if (nforces > 0) {
+    int r = particulate_fluid_check (gfship_sim_view_get (pl->sim));
+    if (r) return r;
+  }
   bool coeff = false;
   for (int f = 0; f < nforces; f++)
     GFSHIP_CHECK (kinds[f] >= GFSHIP_FORCE_INERTIAL && kinds[f] <= GFSHIP_FORCE_BUOY, GFSHIP_EINVAL,
@@ -1269,9 +1340,9 @@ int gfship_particle_list_event (gfship_particles * pl)
   A.migrate = migrates;
   int block = 256, grid = (pl->n + block - 1)/block;
   if (pl->n > 0 && pl->particulate && pl->nforces > 0) {
-    GFSHIP_CHECK (!v.visc_faces, GFSHIP_EUNSUPPORTED,
-		  "particle forces together with a viscosity that varies in space are not supported");
-    int r = particulate_event (pl, A, v.visc);
+    int r = particulate_fluid_check (v);
+    if (r) return r;
+    r = particulate_event (pl, A, v);
     if (r) return r;
     return migrates ? particles_migrate (pl) : GFSHIP_OK;
   }

@@ -35,6 +35,10 @@ struct gfship_sim {
   // diffusion (rhoc = 1./alpha) and the factor of its MAC source
   gfship_field alpha_cell = -1;
   bool has_alpha_cell = false;
+  // the viscosity of U at the centres of the leaf cells (gfship_sim_set_viscosity_cell): what the particle
+  // forces read at the cell of a particle
+  gfship_field mu = -1;
+  bool has_mu = false;
   gfship_field dconst[3] = {-1, -1, -1};   // a constant coefficient as face fields, where alpha_cell asks for the per-face path
   gfship_field msrc[3] = {-1, -1, -1};     // per-cell MAC source of the implicit diffusion of U, V, W
   gfship_multilevel_params diffusion_params[3];
@@ -387,11 +391,16 @@ int advance_tracers (gfship_sim * s, double dt)
 extern "C" {
 
 /* internal view of a simulation for particles.hip */
-struct gfship_sim_view { gfship_domain * dom; const gfship_field * u; double dt; double visc; int visc_faces; };
+struct gfship_sim_view {
+  gfship_domain * dom; const gfship_field * u; double dt; double visc; int visc_faces;
+  int has_alpha;                    /* gfship_sim_set_alpha */
+  gfship_field alpha_cell, mu;      /* gfship_sim_set_alpha_cell, gfship_sim_set_viscosity_cell; -1: not set */
+};
 gfship_sim_view gfship_sim_view_get (gfship_sim * s)
 {
   gfship_sim_view v = { s->dom, s->u, s->advection_params.dt, s->visc[0],
-			s->has_viscf[0] || s->has_viscf[1] || s->has_viscf[2] };
+			s->has_viscf[0] || s->has_viscf[1] || s->has_viscf[2],
+			s->has_alpha, s->has_alpha_cell ? s->alpha_cell : -1, s->has_mu ? s->mu : -1 };
   return v;
 }
 
@@ -582,6 +591,19 @@ int gfship_sim_set_alpha_cell (gfship_sim * s, gfship_field alpha_cell)
   s->alpha_cell = alpha_cell;
   s->has_alpha_cell = true;
   s->cfl_ready = false;
+  return GFSHIP_OK;
+}
+
+int gfship_sim_set_viscosity_cell (gfship_sim * s, gfship_field mu)
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
+  if (mu == -1) {
+    s->has_mu = false;
+    return GFSHIP_OK;
+  }
+  GFSHIP_CHECK (get_field (s->dom, mu) != nullptr, GFSHIP_EINVAL, "mu is not a field of the domain");
+  s->mu = mu;
+  s->has_mu = true;
   return GFSHIP_OK;
 }
 

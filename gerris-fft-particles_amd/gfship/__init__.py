@@ -99,6 +99,7 @@ SIGNATURES = {
     "gfship_sim_set_viscosity": (_i, [_vp, _i, _d]),
     "gfship_sim_set_viscosity_faces": (_i, [_vp, _i, _pi]),
     "gfship_sim_set_alpha_cell": (_i, [_vp, _i]),
+    "gfship_sim_set_viscosity_cell": (_i, [_vp, _i]),
     "gfship_variable_mac_source": (_i, [_vp, _i, _i]),
     "gfship_sim_set_alpha": (_i, [_vp, _pi]),
     "gfship_sim_set_source": (_i, [_vp, _i, _d]),
@@ -595,6 +596,11 @@ class Simulation:
     def set_alpha_cell(self, alpha_cell):
         """alpha at the cell centres of every level: a Variable (None removes it)"""
         _check(lib().gfship_sim_set_alpha_cell(self.ptr, -1 if alpha_cell is None else alpha_cell.h))
+
+    def set_viscosity_cell(self, mu):
+        """the viscosity of U at the centres of the leaf cells, read by particle forces: a Variable (None
+        removes it)"""
+        _check(lib().gfship_sim_set_viscosity_cell(self.ptr, -1 if mu is None else mu.h))
 
     def variable_mac_source(self, c, out):
         """gfs_variable_mac_source of velocity component c into the Variable out"""

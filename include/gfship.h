@@ -266,8 +266,8 @@ int      gfship_sim_set_viscosity (gfship_sim * sim, int c, double nu);
    gfship_diffusion_coefficients_faces, and the step takes the general advection path (face-value arrays
    + flux kernel) with the MAC source of gfship_variable_mac_source.  A component has one
    GfsSourceDiffusion: this call replaces a constant set by gfship_sim_set_viscosity, and
-   gfship_sim_set_viscosity with nu != 0 replaces the fields.  Not on boxes with MPI sides, and not
-   together with particle forces (GFSHIP_EUNSUPPORTED). */
+   gfship_sim_set_viscosity with nu != 0 replaces the fields.  Not on boxes with MPI sides
+   (GFSHIP_EUNSUPPORTED). */
 int      gfship_sim_set_viscosity_faces (gfship_sim * sim, int c, const gfship_field D[3]);
 /* gfs_function_value (alpha, cell) of GfsPhysicalParams { alpha } on the cells of EVERY level, by
    handle (-1 removes it): the density of the implicit diffusion, rhoc = 1./alpha (diffusion_mixed_coeff,
@@ -275,6 +275,12 @@ int      gfship_sim_set_viscosity_faces (gfship_sim * sim, int c, const gfship_f
    (source_diffusion_value, src/source.c:1141-1143).  With it gfship_sim_set_alpha and a viscosity go
    together. */
 int      gfship_sim_set_alpha_cell (gfship_sim * sim, gfship_field alpha_cell);
+/* the `mu' of the GfsDiffusion of U (update_mu / gfs_diffusion_cell, src/source.c:906-946): the
+   GfsFunction of the GfsSourceDiffusion / GfsSourceViscosity of U at the centres of the leaf cells, by
+   handle like alpha_cell (the caller may rewrite the field between events; -1 removes it).  Only the
+   interior cells of the leaf level are read.  It is the viscosity the forces of a list of
+   GfsParticulate take at the cell of each particle; nothing else reads it. */
+int      gfship_sim_set_viscosity_cell (gfship_sim * sim, gfship_field mu);
 /* gfs_variable_mac_source (src/source.c:38-59) of velocity component c for its GfsSourceDiffusion:
    source_diffusion_value (src/source.c:1105-1144) of every leaf cell,
    alpha(cell)*(sum_d D_f*e.b - (sum_d D_f)*v0)/(h*h), into the leaves of out */
@@ -467,8 +473,15 @@ int  gfship_particles_download (gfship_particles * pl, double * pos, unsigned * 
    reference), GfsForceLift (:455-524, cl = 0.5), GfsForceDrag (:527-588, default law
    cd = 16 (1 + 0.15 Re^0.5)/Re below Re = 50, 48 (1 - 2.21/Re^0.5)/Re above; no force without
    viscosity), GfsForceBuoy (:619-653, gravity = the sum of the GfsSource intensities on U, V, W) --
-   then pos += vel*dt/2, vel += force*dt/mass, pos += vel*dt/2 and gfs_particle_bc.  fluid density 1
-   (alpha = NULL), viscosity = gfship_sim_set_viscosity of U.  Particulates migrate between boxes like
+   then pos += vel*dt/2, vel += force*dt/mass, pos += vel*dt/2 and gfs_particle_bc.  The density and
+   the viscosity of the fluid are those of the cell that holds the particle (fluid_rho = 1./alpha and
+   gfs_diffusion_cell of the GfsSourceDiffusion of U, :273-279): 1./alpha_cell wherever
+   gfship_sim_set_alpha_cell is set (1. otherwise), the field of gfship_sim_set_viscosity_cell where it
+   is set and the constant gfship_sim_set_viscosity of U otherwise.  A cell without viscosity gives no
+   drag, and 0.001 in the Rep of the coefficient functions.  GFSHIP_EUNSUPPORTED from
+   gfship_particles_set_forces and gfship_particle_list_event while U has gfship_sim_set_viscosity_faces
+   and no gfship_sim_set_viscosity_cell, or the simulation gfship_sim_set_alpha and no
+   gfship_sim_set_alpha_cell.  Particulates migrate between boxes like
    tracers, with 15-double records.
    gfship_particles_set_force_coefficient: the GfsFunction a GfsForceAddedMass / GfsForceLift /
    GfsForceDrag object of the list may carry (gfs_force_coeff_read, :166-210) -- C text as in the
