@@ -51,6 +51,14 @@ bc_kernel (Layout L, BcDesc bc, double * __restrict__ a)
 
 static int launch_bc_kernel (gfship_domain * dom, Field * v, Field * v1, int level, int homogeneous);
 
+bool all_sides_periodic (const gfship_domain * dom)
+{
+  if (dom->dim != 3) return false;
+  for (int d = 0; d < 6; d++)
+    if (dom->side[d] != GFSHIP_SIDE_PERIODIC) return false;
+  return true;
+}
+
 int launch_bc (gfship_domain * dom, Field * v, Field * v1, int level, int homogeneous)
 {
   int r = launch_bc_kernel (dom, v, v1, level, homogeneous);

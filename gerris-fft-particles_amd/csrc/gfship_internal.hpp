@@ -227,6 +227,23 @@ inline long ncells (const Layout & L) {
 
 // kernels launchers (poisson_kernels.hip, bc.hip)
 int launch_bc (gfship_domain * dom, Field * v, Field * v1, int level, int homogeneous);
+// a 3-D box whose six sides are GFSHIP_SIDE_PERIODIC: the ghost layers are copies of interior layers of the
+// same box, which the kernel that computes those layers can store itself
+bool all_sides_periodic (const gfship_domain * dom);
+
+// the face ghosts of interior cell (i, j, k) of such a box: what bc_kernel copies there (face ghosts only, no
+// edges or corners), stored by the kernel that has just computed v = a[idx (i, j, k)]
+__device__ __forceinline__ void periodic_images (const Layout & L, double * __restrict__ a, int i, int j, int k,
+						  double v)
+{
+  const int n = L.n;
+  if (i == 1) a[L.idx (n + 1, j, k)] = v;
+  if (i == n) a[L.idx (0, j, k)] = v;
+  if (j == 1) a[L.idx (i, n + 1, k)] = v;
+  if (j == n) a[L.idx (i, 0, k)] = v;
+  if (k == 1) a[L.idx (i, j, n + 1)] = v;
+  if (k == n) a[L.idx (i, j, 0)] = v;
+}
 int call_exchange (gfship_domain * dom, double * ptr, int level, int kind);
 int bc_mpi_begin (gfship_domain * dom, Field * v1, int level);
 int bc_mpi_end (gfship_domain * dom, Field * v, Field * v1, int level, int homogeneous);
@@ -318,15 +335,19 @@ int launch_coarse_init (gfship_domain * dom, Field * const * v, int nf);
 int launch_velocity_divergence (gfship_domain * dom, double * const u[3], double * out);
 bool godunov_fused_supported (const gfship_domain * dom);
 bool godunov_fused_mpi_supported (const gfship_domain * dom);
+// ghosts_done (here and in launch_project_correct_lazy): the caller accepts that the kernel writes the face ghosts
+// of g (and of uo) itself where it can (3-D, all six sides periodic, the pair kernels); set when it has done so
 int launch_project_correct (gfship_domain * dom, const double * p, double * const un[3],
-			    double * const g[3], double * const u[3], double dt, bool want_max);
+			    double * const g[3], double * const u[3], double dt, bool want_max,
+			    bool * ghosts_done = nullptr);
 int launch_cfl_from_max (gfship_domain * dom, double * cfl2);
 int launch_face_interp_div (gfship_domain * dom, double * const u[3], double * const un[3] /* or nullptr */,
 			    double * div, double dt);
 int launch_project_correct_weighted (gfship_domain * dom, const double * p, double * const un[3],
 				     double * const g[3], double * const u[3], double dt);
 int launch_project_correct_lazy (gfship_domain * dom, const double * p, double * const u[3],
-				 double * const g[3], double * const uo[3], double dt);
+				 double * const g[3], double * const uo[3], double dt,
+				 bool * ghosts_done = nullptr);
 // div != nullptr: the caller's next operation is the MAC projection with time step div_dt; where the
 // predictor runs as the sweep along z it also leaves the scaled divergence of the new face velocities
 // in div (*div_done set): mac_projection then skips its divergence pass
@@ -351,9 +372,11 @@ int  launch_relax_loop_skew (gfship_domain * dom, int level, Field * dp, Field *
 			     const double * prolong_from = nullptr, const RelaxOp * op = nullptr);
 void skew_free (gfship_domain * dom);
 bool skew_loop_supported (gfship_domain * dom, int level, unsigned nrelax, bool bc);
+struct LoopGhosts;     // relax_skew.hpp
+// ghosts != nullptr: the ghost planes of a loop of nrelax >= 2 sweeps are left to the caller (*ghosts)
 int  skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat, bool has_dia,
 		    unsigned nrelax, float * ms = nullptr, const Field * ubc = nullptr,
-		    const RelaxOp * op = nullptr);
+		    const RelaxOp * op = nullptr, LoopGhosts * ghosts = nullptr);
 int  skew_time_loop (gfship_domain * dom, int level, Field * u, const double * rhs,
 		     const double * dia, bool dia_zero, unsigned nrelax, int reps,
 		     double * ms_per_loop, int * fused, double * ms_inclusive = nullptr);
@@ -365,6 +388,9 @@ int  patch_resident_per_cu (const gfship_domain * dom);
 // the prolongation onto `level' can be done by the copy into the skewed layout of its relax loop
 bool prolongation_fused (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax);
 bool prolongation_fusable (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax);
+// the same on the levels of the one-line kernels of a box with six periodic sides
+bool line_prolongation_fused (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax);
+bool line_prolongation_fusable (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax);
 /* weighted sweeps (face weights from alpha) run on the six-wave kernel with its tile-skewed layout */
 inline bool patch_level (const gfship_domain * dom, int level)
 {
@@ -373,7 +399,8 @@ inline bool patch_level (const gfship_domain * dom, int level)
 }
 int  patch_pack (gfship_domain * dom, int level, SkewPlan * S, const double * u, const double * rhs,
 		 const double * dia, const double * coarse = nullptr);
-int  patch_unpack (gfship_domain * dom, int level, SkewPlan * S, double * u, double * add_into);
+int  patch_unpack (gfship_domain * dom, int level, SkewPlan * S, double * u, double * add_into,
+		   const LoopGhosts * ghosts = nullptr);
 int  patch_restrict_pack (gfship_domain * dom, int level, SkewPlan * S, const double * res,
 			  double * res_coarse, SkewPlan * Sc, unsigned dimension);
 // restriction of the residual of `level' onto level - 1 together with the copy of the residual into

@@ -427,9 +427,12 @@ static int poisson_cycle (gfship_domain * dom, gfship_multilevel_params * p,
     for (unsigned l = first; l <= p->depth; l++) {
       /* get initial guess from coarser grid -- on the levels of the 2 x 2 sweep kernels while the
 	 level is copied into their layout */
-      const bool fp = prolongation_fused (dom, p->dimension, (int) l, nrl[l]);
+      const bool fp = prolongation_fused (dom, p->dimension, (int) l, nrl[l]) ||
+	line_prolongation_fused (dom, p->dimension, (int) l, nrl[l]);
       if (fp) dom->kc[GFSHIP_KC_PROLONGATION_FUSED]++;
-      else if (prolongation_fusable (dom, p->dimension, (int) l, nrl[l])) dom->kc[GFSHIP_KC_PROLONGATION_DECLINED]++;
+      else if (prolongation_fusable (dom, p->dimension, (int) l, nrl[l]) ||
+	       line_prolongation_fusable (dom, p->dimension, (int) l, nrl[l]))
+	dom->kc[GFSHIP_KC_PROLONGATION_DECLINED]++;
       if (!fp)
 	TRY (launch_prolongate (dom, l - 1, DP->lev[l - 1], DP->lev[l]));
       TRY (relax_loop (dom, DP, U, p->dimension, l, p->omega, S, D, nrl[l],
@@ -439,7 +442,10 @@ static int poisson_cycle (gfship_domain * dom, gfship_multilevel_params * p,
   /* correct on leaf cells, then BC on u (gfs_traverse_and_bc ... correct, u, u) */
   if (!corrected)
     TRY (launch_correct (dom, L, U->lev[L], DP->lev[L]));
-  TRY (launch_bc (dom, U, U, L, 0));
+  /* (where the correction was added by the copy out of the loop's layout on a box with six periodic sides, that
+     copy has stored the images) */
+  if (!(corrected && all_sides_periodic (dom)))
+    TRY (launch_bc (dom, U, U, L, 0));
   /* compute new residual on leaf cells */
   if (norm)
     TRY (residual_and_norm (dom, dt, U, R, D, S, norm));

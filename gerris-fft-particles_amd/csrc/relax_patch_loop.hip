@@ -970,38 +970,13 @@ relax_ring_loop_kernel (SkewLoopArgs A)
 }
 
 // y and z ghost planes left by the last BC application of the loop, from the granules of sweep
-// nsweeps - 2 (see skew_loop_ghosts_kernel); rows in this file's convention
+// nsweeps - 2 (loop_ghost_cell, relax_skew.hpp); rows in this file's convention
 __global__ void __launch_bounds__(256)
 patch_loop_ghosts_kernel (SkewLoopArgs A)
 {
-  const int n = A.L.n, ntj = A.ntj;
-  const long hstride = (long) SK_HROWS (n)*SK_T;
-  const int sw = A.nsweeps - 2;
-  const u64 * hbJ = A.hb + sw*A.hb_sweep, * hbK = hbJ + A.hb_words;
-  const u64 * snJ = hbK + A.hb_words, * snK = snJ + A.hb_words;
   const int I = blockIdx.x*blockDim.x + threadIdx.x;     // 0 .. n-1
-  const int c = blockIdx.y;                               // the other tangential index, 0 .. n-1
-  const int plane = blockIdx.z;
-  if (I >= n) return;
-  const int T_ = c / SK_T, l = c % SK_T, lh = l >> 1;
-  const long lastJ = (long) ((ntj - 1) + ntj*T_)*hstride, firstJ = (long) (0 + ntj*T_)*hstride;
-  const long lastK = (long) (T_ + ntj*(ntj - 1))*hstride, firstK = (long) (T_ + ntj*0)*hstride;
-  const long rowHb = (long) (I + lh)*SK_T + l, rowSn = (long) (I + lh + 7)*SK_T + l;
-  u64 bits;
-  long dst;
-  double sg;
-  switch (plane) {
-  case 0: sg = A.sgn[2]; bits = sg == 0. ? hbJ[lastJ + rowHb] : snJ[firstJ + rowSn];     // ghost j = n + 1
-    dst = A.L.idx (I + 1, n + 1, n - c); break;
-  case 1: sg = A.sgn[3]; bits = sg == 0. ? snJ[firstJ + rowSn] : hbJ[lastJ + rowHb];     // ghost j = 0
-    dst = A.L.idx (I + 1, 0, n - c); break;
-  case 2: sg = A.sgn[4]; bits = sg == 0. ? hbK[lastK + rowHb] : snK[firstK + rowSn];     // ghost k = n + 1
-    dst = A.L.idx (I + 1, n - c, n + 1); break;
-  default: sg = A.sgn[5]; bits = sg == 0. ? snK[firstK + rowSn] : hbK[lastK + rowHb];    // ghost k = 0
-    dst = A.L.idx (I + 1, n - c, 0);
-  }
-  const double v = __longlong_as_double ((long long) bits);
-  A.un[dst] = sg == 0. ? v : sg*v;
+  if (I >= A.L.n) return;
+  loop_ghost_cell (loop_ghosts_of (A, true), I, blockIdx.y, blockIdx.z);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1022,30 +997,10 @@ struct PatchPackArgs {
   const double * coarse;
   double * nat;
   Layout Lc;
+  // all six sides are periodic: the kernel also writes the face ghosts of what it writes into a natural array
+  // (prolongation: nat; unpack with add: the corrected array), the BC application that followed is not launched
+  bool periodic;
 };
-
-// get_from_above of fine cell (i, j, k): prolongate_kernel's expression (poisson_kernels.hip)
-__device__ __forceinline__ double patch_prolong (const Layout & Lc, const double * __restrict__ vc,
-						 int i, int j, int k)
-{
-  const int pi = (i + 1)/2, pj = (j + 1)/2, pk = (k + 1)/2;
-  const long p = Lc.idx (pi, pj, pk);
-  const double pv = vc[p];
-  double h[3];
-  const long off[3] = { 1, Lc.sy, Lc.sz };
-#pragma unroll
-  for (int cc = 0; cc < 3; cc++) {
-    double g1 = vc[p + off[cc]] - 1.*pv;
-    double g2 = vc[p - off[cc]] - 1.*pv;
-    h[cc] = (g1 - g2)/2.;
-  }
-  const double rel[3] = { ((i & 1) ? -1. : 1.)/4., ((j & 1) ? -1. : 1.)/4., ((k & 1) ? -1. : 1.)/4. };
-  double val = pv;
-#pragma unroll
-  for (int cc = 0; cc < 3; cc++)
-    val += rel[cc]*h[cc];
-  return val;
-}
 
 // get_from_above (src/poisson.c:1005-1042) of a whole level STRAIGHT INTO the patch-skewed layout of
 // its relax loop: the initial guess of the loop is produced where the loop reads it, the natural
@@ -1177,8 +1132,10 @@ patch_prolong_kernel (PatchPackArgs A)
       const double vv[4] = { o01.x, o01.y, o23.x, o23.y };
 #pragma unroll
       for (int q = 0; q < 4; q++)
-	if (ends || side_j[q & 1] || side_k[q >> 1])
+	if (ends || side_j[q & 1] || side_k[q >> 1]) {
 	  A.nat[A.L.idx (I + 1, j0 - (q & 1), k0 - (q >> 1))] = vv[q];
+	  if (A.periodic) periodic_images (A.L, A.nat, I + 1, j0 - (q & 1), k0 - (q >> 1), vv[q]);
+	}
     }
   }
 }
@@ -1320,9 +1277,14 @@ patch_restrict_pack_kernel (PatchRestrictArgs A)
   }
 }
 
+// G: the ghost planes the loop has left to this launch, taken by the blocks behind those of the tiles
 __global__ void __launch_bounds__(256)
-patch_unpack_kernel (PatchPackArgs A)
+patch_unpack_kernel (PatchPackArgs A, LoopGhosts G)
 {
+  if ((int) blockIdx.z >= A.ntj*A.ntj) {
+    loop_ghost_blocks (G, A.ntj*A.ntj);
+    return;
+  }
   __shared__ double buf[32][PPU_SPAN + 1];
   const int tid = threadIdx.x;
   const int tile = blockIdx.z, PB = blockIdx.y, r0 = blockIdx.x*PPU_ROWS;
@@ -1351,8 +1313,12 @@ patch_unpack_kernel (PatchPackArgs A)
     if (I >= 0 && I < n && rho >= r0 && rho < r0 + PPU_ROWS) {
       const int j = n - (SK_T*P + a), k = n - (SK_T*Q + 2*PB + db);
       const long c = A.L.idx (I + 1, j, k);
-      if (A.add)
-	A.add[c] += buf[line][di];     /* correct (src/poisson.c:998-1003) fused into the unpack */
+      if (A.add) {
+	const double v = A.add[c] + buf[line][di];     /* correct (src/poisson.c:998-1003) fused into the unpack */
+	A.add[c] = v;
+	if (A.periodic && (I == 0 || I == n - 1 || j == 1 || j == n || k == 1 || k == n))
+	  periodic_images (A.L, A.add, I + 1, j, k, v);
+      }
       else
 	A.dst[0][c] = buf[line][di];
     }
@@ -1381,6 +1347,7 @@ int patch_pack (gfship_domain * dom, int level, SkewPlan * S, const double * u, 
   PatchPackArgs A;
   A.add = nullptr;
   A.coarse = coarse;
+  A.periodic = all_sides_periodic (dom);
   A.nat = const_cast<double *> (u);
   A.Lc = dom->lay[level > 0 ? level - 1 : 0];
   A.L = dom->lay[level]; A.ntj = S->ntj; A.RT = S->RT;
@@ -1430,16 +1397,20 @@ int patch_restrict_pack (gfship_domain * dom, int level, SkewPlan * S, const dou
   return GFSHIP_OK;
 }
 
-int patch_unpack (gfship_domain * dom, int level, SkewPlan * S, double * u, double * add_into)
+int patch_unpack (gfship_domain * dom, int level, SkewPlan * S, double * u, double * add_into,
+		  const LoopGhosts * ghosts)
 {
   PatchPackArgs A;
   A.coarse = nullptr; A.nat = nullptr; A.Lc = dom->lay[level];
+  A.periodic = all_sides_periodic (dom);
   A.L = dom->lay[level]; A.ntj = S->ntj; A.RT = S->RT;
   A.narr = 1;
   A.src[0] = S->us; A.dst[0] = u; A.add = add_into;
   const int rows = A.L.n + PK_SKEW + 1;
   dim3 grid ((rows + PPU_ROWS - 1)/PPU_ROWS, 8, S->ntj*S->ntj);
-  hipLaunchKernelGGL (patch_unpack_kernel, grid, dim3 (256), 0, dom->stream, A);
+  const LoopGhosts G = ghosts ? *ghosts : LoopGhosts ();
+  grid.z += loop_ghost_planes (G, grid.x, grid.y);
+  hipLaunchKernelGGL (patch_unpack_kernel, grid, dim3 (256), 0, dom->stream, A, G);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
@@ -1447,7 +1418,7 @@ int patch_unpack (gfship_domain * dom, int level, SkewPlan * S, double * u, doub
 // launches the loop kernel (and the ghost planes for nrelax >= 2) with the arguments the caller has
 // prepared (skew_loop_run, relax_skew_loop.hip: granules armed, ticket zeroed)
 int patch_loop_launch (gfship_domain * dom, const SkewLoopArgs & A, int ntiles, bool has_dia,
-		       unsigned nrelax, float * ms)
+		       unsigned nrelax, float * ms, LoopGhosts * ghosts)
 {
   if (ms) GFSHIP_HIP (hipEventRecord (dom->ev0, dom->stream));
   if (A.op == 1)            /* diffusion_relax: the ring kernel (rhoc travels as the dia stream) */
@@ -1468,7 +1439,9 @@ int patch_loop_launch (gfship_domain * dom, const SkewLoopArgs & A, int ntiles, 
     GFSHIP_HIP (hipEventSynchronize (dom->ev1));
     GFSHIP_HIP (hipEventElapsedTime (ms, dom->ev0, dom->ev1));
   }
-  if (nrelax >= 2) {
+  if (nrelax >= 2 && ghosts)
+    *ghosts = loop_ghosts_of (A, true);
+  else if (nrelax >= 2) {
     const Layout & L = A.L;
     int block = L.n >= 256 ? 256 : L.n >= 128 ? 128 : 64;
     hipLaunchKernelGGL (patch_loop_ghosts_kernel, dim3 ((L.n + block - 1)/block, L.n, 4), dim3 (block),

@@ -260,6 +260,11 @@ struct PackArgs {
   double * dst[3];
   int narr;
   double * add;            // unpack: add the values to this natural array instead of storing them
+  bool periodic;           // ... and store its face ghosts, the images of a box with six periodic sides
+  // skew_prolong_pack_kernel: array 0 is not read but prolongated from the next coarser level
+  const double * coarse;
+  Layout Lc;
+  double * nat;            // the natural array of the level: gets the cells along the box sides and their images
 };
 
 __global__ void __launch_bounds__(SK_NL)
@@ -296,9 +301,58 @@ skew_pack_kernel (PackArgs A)
   }
 }
 
+// skew_pack_kernel on a box with six periodic sides, with get_from_above (src/poisson.c:1005-1042) for array 0:
+// the initial guess of the relax loop of a one-line level is computed where the copy into the layout would have
+// read it (prolongate_kernel's expression and operand order: patch_prolong), the natural array gets what the loop
+// reads there, the periodic images of the cells along the six sides (and those cells), and the other arrays
+// are copied as before: prolongate_kernel, bc_kernel and skew_pack_kernel in one launch, as patch_prolong_kernel
+// does it for the levels of the 2 x 2 kernels
 __global__ void __launch_bounds__(SK_NL)
-skew_unpack_kernel (PackArgs A)
+skew_prolong_pack_kernel (PackArgs A)
 {
+  __shared__ double tile_[3][SK_T][SK_T + 1];
+  const int tid = threadIdx.x;
+  const int lo = tid & (SK_T - 1), hi = tid >> 4;
+  const int tile = blockIdx.z;
+  const int b = blockIdx.y;
+  const int I0 = blockIdx.x*SK_T;
+  const int P = tile % A.ntj, Q = tile / A.ntj;
+  const int n = A.L.n;
+  const int k = n - (SK_T*Q + b);
+  const long tbase = (long) tile*(A.RT + 2*SK_FP)*SK_NL + SK_FP*SK_NL;
+  {
+    const int i = I0 + lo + 1, j = n - (SK_T*P + hi);
+    const long nidx = A.L.idx (i, j, k);
+    const double v = patch_prolong (A.Lc, A.coarse, i, j, k);
+    tile_[0][hi][lo] = v;
+    if (i == 1 || i == n || j == 1 || j == n || k == 1 || k == n) {
+      A.nat[nidx] = v;
+      periodic_images (A.L, A.nat, i, j, k, v);
+    }
+    for (int q = 1; q < A.narr; q++)
+      tile_[q][hi][lo] = A.src[q][nidx];
+  }
+  __syncthreads ();
+#pragma unroll
+  for (int pass = 0; pass < 2; pass++) {
+    const int m = hi + SK_T*pass;            // 0 .. 30
+    const int di = m - lo;                   // I - I0
+    if (m <= 2*SK_T - 2 && di >= 0 && di < SK_T) {
+      long sidx = tbase + (long) (I0 + m + b)*SK_NL + lo + SK_T*b;
+      for (int q = 0; q < A.narr; q++)
+	A.dst[q][sidx] = tile_[q][lo][di];
+    }
+  }
+}
+
+// G: the ghost planes the loop has left to this launch, taken by the blocks behind those of the tiles
+__global__ void __launch_bounds__(SK_NL)
+skew_unpack_kernel (PackArgs A, LoopGhosts G)
+{
+  if ((int) blockIdx.z >= A.ntj*A.ntj) {
+    loop_ghost_blocks (G, A.ntj*A.ntj);
+    return;
+  }
   __shared__ double tile_[SK_T][SK_T + 1];
   const int tid = threadIdx.x;
   const int lo = tid & (SK_T - 1), hi = tid >> 4;
@@ -319,8 +373,11 @@ skew_unpack_kernel (PackArgs A)
   __syncthreads ();
   const int j = n - (SK_T*P + hi);
   const long c = A.L.idx (I0 + lo + 1, j, k);
-  if (A.add)
-    A.add[c] += tile_[hi][lo];     /* correct (src/poisson.c:998-1003) fused into the unpack */
+  if (A.add) {
+    const double v = A.add[c] + tile_[hi][lo];     /* correct (src/poisson.c:998-1003) fused into the unpack */
+    A.add[c] = v;
+    if (A.periodic) periodic_images (A.L, A.add, I0 + lo + 1, j, k, v);
+  }
   else
     A.dst[0][c] = tile_[hi][lo];
 }
@@ -419,14 +476,19 @@ static int skew_pack (gfship_domain * dom, int level, SkewPlan * S, const double
   if (patch_level (dom, level))
     return patch_pack (dom, level, S, u, rhs, dia, coarse);
   PackArgs A;
-  A.add = nullptr;
+  A.add = nullptr; A.periodic = false;
+  A.coarse = coarse; A.nat = const_cast<double *> (u);
+  A.Lc = dom->lay[level > 0 ? level - 1 : 0];
   A.L = dom->lay[level]; A.ntj = S->ntj; A.RT = S->RT;
   A.narr = 0;
   A.src[A.narr] = u;   A.dst[A.narr++] = S->us;
   A.src[A.narr] = rhs; A.dst[A.narr++] = S->rs;
   if (dia) { A.src[A.narr] = dia; A.dst[A.narr++] = S->ds; }
   dim3 grid (A.L.n/SK_T, SK_T, S->ntj*S->ntj);
-  hipLaunchKernelGGL (skew_pack_kernel, grid, dim3 (SK_NL), 0, dom->stream, A);
+  if (coarse)       /* six periodic sides (line_prolongation_fusable) */
+    hipLaunchKernelGGL (skew_prolong_pack_kernel, grid, dim3 (SK_NL), 0, dom->stream, A);
+  else
+    hipLaunchKernelGGL (skew_pack_kernel, grid, dim3 (SK_NL), 0, dom->stream, A);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
@@ -445,7 +507,8 @@ static int skew_pack_weights (gfship_domain * dom, int level, SkewPlan * S, cons
     }
   for (int h = 0; h < 2; h++) {
     PackArgs A;
-    A.add = nullptr;
+    A.add = nullptr; A.periodic = false;
+    A.coarse = nullptr; A.nat = nullptr; A.Lc = dom->lay[level];
     A.L = dom->lay[level]; A.ntj = S->ntj; A.RT = S->RT;
     A.narr = 3;
     for (int q = 0; q < 3; q++) { A.src[q] = op->wf[3*h + q]; A.dst[q] = S->ws[3*h + q]; }
@@ -458,16 +521,20 @@ static int skew_pack_weights (gfship_domain * dom, int level, SkewPlan * S, cons
 }
 
 static int skew_unpack (gfship_domain * dom, int level, SkewPlan * S, double * u,
-			double * add_into = nullptr)
+			double * add_into = nullptr, const LoopGhosts * ghosts = nullptr)
 {
   if (patch_level (dom, level))
-    return patch_unpack (dom, level, S, u, add_into);
+    return patch_unpack (dom, level, S, u, add_into, ghosts);
   PackArgs A;
   A.L = dom->lay[level]; A.ntj = S->ntj; A.RT = S->RT;
   A.narr = 1;
   A.src[0] = S->us; A.dst[0] = u; A.add = add_into;
+  A.coarse = nullptr; A.nat = nullptr; A.Lc = dom->lay[level];
+  A.periodic = all_sides_periodic (dom);
   dim3 grid (A.L.n/SK_T, SK_T, S->ntj*S->ntj);
-  hipLaunchKernelGGL (skew_unpack_kernel, grid, dim3 (SK_NL), 0, dom->stream, A);
+  const LoopGhosts G = ghosts ? *ghosts : LoopGhosts ();
+  grid.z += loop_ghost_planes (G, grid.x, grid.y);
+  hipLaunchKernelGGL (skew_unpack_kernel, grid, dim3 (SK_NL), 0, dom->stream, A, G);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
@@ -552,6 +619,28 @@ bool prolongation_fusable (gfship_domain * dom, unsigned dimension, int level, u
   return skew_supported (dom, level) && patch_level (dom, level);
 }
 
+// the same on the levels of the one-line kernels (skew_prolong_pack_kernel), on boxes with six periodic sides
+bool line_prolongation_fusable (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax)
+{
+  (void) nrelax;
+  if (dom->weighted || level < 1) return false;
+  if (dom->relax_mode != GFSHIP_RELAX_EXACT || dimension != 3 || dom->force_hyperplane) return false;
+  return all_sides_periodic (dom) && skew_supported (dom, level) && !patch_level (dom, level);
+}
+
+bool line_prolongation_fused (gfship_domain * dom, unsigned dimension, int level, unsigned nrelax)
+{
+  return dom->sw.fused_prolongation && line_prolongation_fusable (dom, dimension, level, nrelax);
+}
+
+// the prolongation in the copy into the layout of `level' writes the periodic images of the side cells: always
+// on the one-line levels; patch_prolong_kernel does (not the older prolongation in the transposing copy,
+// GFSHIP_OLD_PROLONG_PACK)
+static bool prolong_images (gfship_domain * dom, int level)
+{
+  return all_sides_periodic (dom) && (!patch_level (dom, level) || !dom->sw.old_prolong_pack);
+}
+
 int launch_relax_loop_skew (gfship_domain * dom, int level, Field * dp, Field * ubc,
 			    const double * rhs, const double * dia, bool dia_zero,
 			    unsigned nrelax, bool bc, double * correct_into, const double * prolong_from,
@@ -568,19 +657,26 @@ int launch_relax_loop_skew (gfship_domain * dom, int level, Field * dp, Field * 
   }
   /* get_from_above fused into the copy into the skewed layout: the natural array gets the cells
      along the box sides only (what the BC application reads), then the BC, then the loop */
-  const bool fusedp = prolong_from != nullptr && bc && patch_level (dom, level);
+  const bool fusedp = prolong_from != nullptr && bc && (patch_level (dom, level) || all_sides_periodic (dom));
   /* the residual was copied into the skewed layout when it was restricted (launch_restrict_pack) */
   const double * rhs_pack = S->rs_ready && patch_level (dom, level) ? nullptr : rhs;
   S->rs_ready = false;
   if (prolong_from && !fusedp)
     if ((r = launch_prolongate (dom, level - 1, prolong_from, u))) return r;
   if (fusedp && (r = skew_pack (dom, level, S, u, rhs_pack, dia_zero ? nullptr : dia, prolong_from))) return r;
-  if (bc && (r = launch_bc (dom, ubc, dp, level, 1))) return r;
+  /* ... on a box with six periodic sides the prolongation has written the images as well */
+  if (bc &&!(fusedp && prolong_images (dom, level)) && (r = launch_bc (dom, ubc, dp, level, 1))) return r;
   if (!fusedp && (r = skew_pack (dom, level, S, u, rhs_pack, dia_zero ? nullptr : dia))) return r;
   if (!dom->no_fused_loop && skew_loop_supported (dom, level, nrelax, bc)) {
-    /* the sweeps of the loop pipelined in one launch (relax_skew_loop.hip) */
-    if ((r = skew_loop_run (dom, level, S, u, !dia_zero, nrelax, nullptr, ubc, op))) return r;
-    return skew_unpack (dom, level, S, u, correct_into);
+    /* the sweeps of the loop pipelined in one launch (relax_skew_loop.hip).  On a box with six periodic sides
+       the ghost planes of the natural array it leaves behind are written by the launch that copies the level
+       out of the layout -- or not at all where that copy adds the level to correct_into: dp's natural
+       array is then not read again (the next cycle prolongates into it and applies the BC first) */
+    LoopGhosts G;
+    const bool defer = all_sides_periodic (dom) && !op;    /* the diffusion and weighted loops launch what they did */
+    if ((r = skew_loop_run (dom, level, S, u, !dia_zero, nrelax, nullptr, ubc, op, defer ? &G : nullptr))) return r;
+    if (correct_into) G.active = false;
+    return skew_unpack (dom, level, S, u, correct_into, &G);
   }
   for (unsigned q = 0; q < nrelax; q++) {
     if ((r = skew_sweep (dom, level, S, u, !dia_zero, op))) return r;

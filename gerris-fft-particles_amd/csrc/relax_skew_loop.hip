@@ -773,45 +773,13 @@ relax_wave_loop_kernel (SkewLoopArgs A)
   }
 }
 
-// y and z ghost planes left by the last BC application of the loop = periodic images (or, at a
-// non-periodic side, +- the adjacent line) of the side cells after sweep nsweeps - 2, taken from
-// that sweep's granules:
-//   hand-off J of tile (ntj-1,Q): line a = 15 (j = 1)  -> ghost j = n + 1     row I + b
-//   snapshot J of tile (0,Q):     line a = 0  (j = n)  -> ghost j = 0         row I + b + 15
-//   hand-off K of tile (P,ntj-1): line b = 15 (k = 1)  -> ghost k = n + 1     row I + a
-//   snapshot K of tile (P,0):     line b = 0  (k = n)  -> ghost k = 0         row I + a + 15
+// y and z ghost planes left by the last BC application of the loop (loop_ghost_cell, relax_skew.hpp)
 __global__ void __launch_bounds__(256)
 skew_loop_ghosts_kernel (SkewLoopArgs A)
 {
-  const int n = A.L.n, ntj = A.ntj;
-  const long hstride = (long) SK_HROWS (n)*SK_T;
-  const int sw = A.nsweeps - 2;
-  const u64 * hbJ = A.hb + sw*A.hb_sweep, * hbK = hbJ + A.hb_words;
-  const u64 * snJ = hbK + A.hb_words, * snK = snJ + A.hb_words;
   const int I = blockIdx.x*blockDim.x + threadIdx.x;     // 0 .. n-1
-  const int c = blockIdx.y;                               // the other tangential index, 0 .. n-1
-  const int plane = blockIdx.z;
-  if (I >= n) return;
-  const int T_ = c / SK_T, l = c % SK_T;                  // tile and line of the tangential index
-  // periodic: the line next to the opposite side; otherwise sgn * the line next to the same side
-  const long lastJ = (long) ((ntj - 1) + ntj*T_)*hstride, firstJ = (long) (0 + ntj*T_)*hstride;
-  const long lastK = (long) (T_ + ntj*(ntj - 1))*hstride, firstK = (long) (T_ + ntj*0)*hstride;
-  const long rowHb = (long) (I + l)*SK_T + l, rowSn = (long) (I + l + SK_T - 1)*SK_T + l;
-  u64 bits;
-  long dst;
-  double sg;
-  switch (plane) {
-  case 0: sg = A.sgn[2]; bits = sg == 0. ? hbJ[lastJ + rowHb] : snJ[firstJ + rowSn];     // ghost j = n + 1
-    dst = A.L.idx (I + 1, n + 1, n - c); break;
-  case 1: sg = A.sgn[3]; bits = sg == 0. ? snJ[firstJ + rowSn] : hbJ[lastJ + rowHb];     // ghost j = 0
-    dst = A.L.idx (I + 1, 0, n - c); break;
-  case 2: sg = A.sgn[4]; bits = sg == 0. ? hbK[lastK + rowHb] : snK[firstK + rowSn];     // ghost k = n + 1
-    dst = A.L.idx (I + 1, n - c, n + 1); break;
-  default: sg = A.sgn[5]; bits = sg == 0. ? snK[firstK + rowSn] : hbK[lastK + rowHb];    // ghost k = 0
-    dst = A.L.idx (I + 1, n - c, 0);
-  }
-  const double v = __longlong_as_double ((long long) bits);
-  A.un[dst] = sg == 0. ? v : sg*v;
+  if (I >= A.L.n) return;
+  loop_ghost_cell (loop_ghosts_of (A, false), I, blockIdx.y, blockIdx.z);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -924,7 +892,7 @@ int skew_arm_ahead (gfship_domain * dom, int level, unsigned nrelax)
 // pipelined sweep runs on (any sides; the BC kernel is applied around it by the caller, so the
 // cells next to the box sides are mirrored into the natural array).
 int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat, bool has_dia,
-		   unsigned nrelax, float * ms, const Field * ubc, const RelaxOp * op)
+		   unsigned nrelax, float * ms, const Field * ubc, const RelaxOp * op, LoopGhosts * ghosts)
 {
   const Layout & L = dom->lay[level];
   int ntiles = S->ntj*S->ntj;
@@ -1039,7 +1007,7 @@ int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat,
     A.stats = (u64 *) S->stats_loop;
   }
   if (patch_level (dom, level)) {
-    int r = patch_loop_launch (dom, A, ntiles, has_dia, nrelax, ms);
+    int r = patch_loop_launch (dom, A, ntiles, has_dia, nrelax, ms, ghosts);
     if (r) return r;
     if (nrelax >= 2 && A.stats && ms)
       goto dump_stats;
@@ -1080,7 +1048,9 @@ int skew_loop_run (gfship_domain * dom, int level, SkewPlan * S, double * u_nat,
     GFSHIP_HIP (hipEventSynchronize (dom->ev1));
     GFSHIP_HIP (hipEventElapsedTime (ms, dom->ev0, dom->ev1));
   }
-  if (nrelax >= 2) {
+  if (nrelax >= 2 && ghosts)
+    *ghosts = loop_ghosts_of (A, false);
+  else if (nrelax >= 2) {
     int block = L.n >= 256 ? 256 : L.n >= 128 ? 128 : 64;
     hipLaunchKernelGGL (skew_loop_ghosts_kernel, dim3 ((L.n + block - 1)/block, L.n, 4), dim3 (block),
 			0, dom->stream, A);

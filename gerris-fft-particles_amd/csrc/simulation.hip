@@ -221,7 +221,7 @@ int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, g
      gfs_correct_centered_velocities (src/timestep.c:486-530), in one pass over p.  The pass
      also leaves the largest |un|, |u| behind for the CFL condition of the next time step. */
   s->cfl_ready = false;
-  bool want_max = approximate;
+  bool want_max = approximate, ghosts_done = false;
   for (int c = 0; c < dom->dim; c++)
     if (has_viscosity (s, c) || dom->src[c] != 0.) want_max = false;   /* the acceleration term needs the full kernel */
   if (s->has_alpha) {
@@ -240,7 +240,7 @@ int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, g
       if (s->adv_tmp3[c] < 0) return s->adv_tmp3[c];
     }
     ptrs3 (s, s->adv_tmp3, uo);
-    TRY (launch_project_correct_lazy (dom, leaf (s, p), u, gp, uo, dt));
+    TRY (launch_project_correct_lazy (dom, leaf (s, p), u, gp, uo, dt, &ghosts_done));
     for (int c = 0; c < dom->dim; c++) {
       std::swap (dom->fields[s->u[c]].lev[L], dom->fields[s->adv_tmp3[c]].lev[L]);
       dom->fields[s->u[c]].zero[L] = false;
@@ -249,10 +249,12 @@ int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, g
     s->un_lazy_dt = dt;
   }
   else
-    TRY (launch_project_correct (dom, leaf (s, p), un, gp, approximate ? u : nullptr, dt, want_max));
+    TRY (launch_project_correct (dom, leaf (s, p), un, gp, approximate ? u : nullptr, dt, want_max, &ghosts_done));
   s->cfl_ready = want_max;
-  TRY (bc_leaf_vector (s, g));
-  if (approximate)
+  /* on a periodic box the pair kernels have written the ghost layers of what they computed */
+  if (!ghosts_done)
+    TRY (bc_leaf_vector (s, g));
+  if (approximate && !(ghosts_done && lazy))
     TRY (bc_leaf_vector (s, s->u));
   return GFSHIP_OK;
 }

@@ -289,8 +289,28 @@ face_interp_div2_kernel (Layout L, CPtr3 u, double * __restrict__ div, double dt
   *(d2 *) (div + c) = out;
 }
 
+// On a box whose six sides are periodic the ghost layer of a side holds the interior layer along the opposite
+// side (bc_kernel: a[ghost] = a[image], face ghosts only).  A kernel that has just computed the cells of a pair
+// (i1, i1 + 1) of row (j, k) stores them into those ghost cells itself: the launch of bc_kernel that followed is
+// then not needed.  c = L.idx (i1, j, k); n is even, so cell n is the second of its pair.
+__device__ __forceinline__ void periodic_images_pair (const Layout & L, double * __restrict__ a, long c,
+						       int i1, int j, int k, double vx, double vy)
+{
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  const int n = L.n;
+  const d2 V = { vx, vy };
+  if (i1 == 1) a[c + n] = vx;
+  if (i1 + 1 == n) a[c + 1 - n] = vy;
+  if (j == 1) *(d2 *) (a + c + n*L.sy) = V;
+  if (j == n) *(d2 *) (a + c - n*L.sy) = V;
+  if (k == 1) *(d2 *) (a + c + n*L.sz) = V;
+  if (k == n) *(d2 *) (a + c - n*L.sz) = V;
+}
+
 // project_correct_kernel<3, false> (the MAC projection: correct_normal_velocity + the centred gradient) with two
-// cells of a row per thread and 16-byte accesses, as project_correct_lazy2_kernel below
+// cells of a row per thread and 16-byte accesses, as project_correct_lazy2_kernel below.  PER: all six sides
+// are periodic and the face ghosts of g are written here (periodic_images_pair)
+template <bool PER>
 __global__ void __launch_bounds__(128)
 project_correct2_kernel (Layout L, const double * __restrict__ p, Ptr3 un, Ptr3 g, double dt)
 {
@@ -351,6 +371,7 @@ project_correct2_kernel (Layout L, const double * __restrict__ p, Ptr3 un, Ptr3 
       }
       *(d2 *) (un.p[cc] + c) = W;
       *(d2 *) (g.p[cc] + c) = G;
+      if (PER) periodic_images_pair (L, g.p[cc], c, i1, j, k, G.x, G.y);
     }
   }
   else {
@@ -365,7 +386,9 @@ project_correct2_kernel (Layout L, const double * __restrict__ p, Ptr3 un, Ptr3 
 // at i = 1 (Layout), so p, its four neighbour rows, the three velocity components, their + neighbours along y
 // and z and the six results move as 16-byte accesses (19 memory instructions per two cells instead of 38: the
 // 8-byte version is bound by the number of requests, not by bytes).  Same expressions per cell.  Rows of the
-// ghost planes (j = 0 or k = 0) and the column i = 0 keep the one-cell body.
+// ghost planes (j = 0 or k = 0) and the column i = 0 keep the one-cell body.  PER: all six sides are periodic and
+// the face ghosts of g and of uo are written here (periodic_images_pair)
+template <bool PER>
 __global__ void __launch_bounds__(128)
 project_correct_lazy2_kernel (Layout L, const double * __restrict__ p, CPtr3 u, Ptr3 g, Ptr3 uo,
 			      double dt, double * __restrict__ partial_max)
@@ -445,6 +468,10 @@ project_correct_lazy2_kernel (Layout L, const double * __restrict__ p, CPtr3 u, 
 	}
 	*(d2 *) (g.p[cc] + c) = G;
 	*(d2 *) (uo.p[cc] + c) = W;
+	if (PER) {
+	  periodic_images_pair (L, g.p[cc], c, i1, j, k, G.x, G.y);
+	  periodic_images_pair (L, uo.p[cc], c, i1, j, k, W.x, W.y);
+	}
       }
     }
     else {
@@ -3076,8 +3103,9 @@ static inline void ext1_grid (const Layout & L, dim3 * grid, dim3 * block)
 
 int launch_project_correct (gfship_domain * dom, const double * p, double * const un[3],
 			    double * const g[3], double * const u[3] /* or nullptr */, double dt,
-			    bool want_max)
+			    bool want_max, bool * ghosts_done)
 {
+  if (ghosts_done) *ghosts_done = false;
   const Layout & L = dom->lay[dom->depth];
   dim3 grid, block;
   ext1_grid (L, &grid, &block);
@@ -3102,9 +3130,13 @@ int launch_project_correct (gfship_domain * dom, const double * p, double * cons
   if (pairs_apply && pairs) {
     /* the MAC projection: two cells per thread, 16-byte accesses */
     const int b = 128, half = L.n/2;
-    hipLaunchKernelGGL (project_correct2_kernel, dim3 ((half + b - 1)/b, L.n + 1, L.n + 1), dim3 (b), 0, dom->stream,
-			L, p, m3 (un), m3 (g), dt);
+    const bool per = ghosts_done && all_sides_periodic (dom);
+    with_bools ([&] (auto PER) {
+      hipLaunchKernelGGL (project_correct2_kernel<decltype (PER)::value>, dim3 ((half + b - 1)/b, L.n + 1, L.n + 1), dim3 (b), 0,
+			  dom->stream, L, p, m3 (un), m3 (g), dt);
+    }, per);
     GFSHIP_HIP (hipGetLastError ());
+    if (per) *ghosts_done = true;
     return GFSHIP_OK;
   }
   with_bools ([&] (auto D3, auto U) {
@@ -3179,8 +3211,9 @@ int launch_face_interp_div (gfship_domain * dom, double * const u[3], double * c
 // g and the corrected centred velocities uo from p and the uncorrected u; the maxima for the CFL
 // condition are always left behind
 int launch_project_correct_lazy (gfship_domain * dom, const double * p, double * const u[3],
-				 double * const g[3], double * const uo[3], double dt)
+				 double * const g[3], double * const uo[3], double dt, bool * ghosts_done)
 {
+  if (ghosts_done) *ghosts_done = false;
   const Layout & L = dom->lay[dom->depth];
   dim3 grid, block;
   ext1_grid (L, &grid, &block);
@@ -3200,8 +3233,12 @@ int launch_project_correct_lazy (gfship_domain * dom, const double * p, double *
   if (pairs_apply && pairs) {
     /* two cells per thread, 16-byte accesses */
     const int b = 128, half = L.n/2;
-    hipLaunchKernelGGL (project_correct_lazy2_kernel, dim3 ((half + b - 1)/b, L.n + 1, L.n + 1), dim3 (b), 0, dom->stream,
-			L, p, c3 (u), m3 (g), m3 (uo), dt, dom->cfl_partial);
+    const bool per = ghosts_done && all_sides_periodic (dom);
+    with_bools ([&] (auto PER) {
+      hipLaunchKernelGGL (project_correct_lazy2_kernel<decltype (PER)::value>, dim3 ((half + b - 1)/b, L.n + 1, L.n + 1), dim3 (b), 0,
+			  dom->stream, L, p, c3 (u), m3 (g), m3 (uo), dt, dom->cfl_partial);
+    }, per);
+    if (per) *ghosts_done = true;
   }
   else if (dom->dim == 3)
     hipLaunchKernelGGL ((project_correct_lazy_kernel<3>), grid, block, 0, dom->stream, L, p, c3 (u), m3 (g), m3 (uo), dt, dom->cfl_partial);
