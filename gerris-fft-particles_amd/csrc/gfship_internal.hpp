@@ -322,6 +322,11 @@ int launch_advected_face_values (gfship_domain * dom, const double * v, double *
 // source_diffusion_value (src/source.c:1105-1144) of every leaf cell: D at the faces, alpha at the cells or nullptr
 int launch_variable_mac_source (gfship_domain * dom, const double * v, double * const D[3],
 				const double * alpha, double * out);
+// coupling.hip: velocity sources given as fields (GfsSourceParticulate).  out = 0. + the value of F
+// interpolated on the positive face of component c (source_particulate_value) [+ out, the MAC source of the
+// diffusion]; v += dt*(0. + F [+ gsrc]) (add_sources)
+int launch_mac_source_fields (gfship_domain * dom, int c, const double * F, bool add_out, double * out);
+int launch_centered_source_fields (gfship_domain * dom, double * v, const double * F, double gsrc, double dt);
 int launch_face_bc (gfship_domain * dom, Field * v, double * const fv[6], int cmask);
 int launch_predict_un (gfship_domain * dom, int cc, const double * uc, double * const fv[6],
 		       double * unc);

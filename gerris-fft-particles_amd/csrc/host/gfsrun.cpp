@@ -16,8 +16,8 @@
 // GfsAdvection with a VariableStreamFunction, OutputSimulation (text format), OutputEnergySpectra (`GModule fft`), InitSpectra (`GModule
 // turbulence`), GfsParticleList of GfsParticle / GfsParticulate objects with
 // GfsForce{Inertial,AddedMass,Lift,Drag,Buoy} (`GModule particulates`; --particles FILE writes the
-// lists at the end of the run the way the reference prints them).  Anything else fails loudly with
-// the line number.
+// lists at the end of the run the way the reference prints them), GfsParticulateField and
+// GfsSourceParticulate on a list named `*NAME'.  Anything else fails loudly with the line number.
 //
 //   gfship2D [-D NAME=VALUE ...] [--device N] [--particles FILE] file.gfs     (gfship3D for three dimensions)
 #include <algorithm>
@@ -160,7 +160,17 @@ struct ParticleSpec {
   std::vector<double> pos, vel, mass, volume;    // 3 per particle for pos / vel
   std::vector<int> forces;                       // GFSHIP_FORCE_* in file order
   std::vector<std::string> force_functions;      // the GfsFunction of a GfsForceCoeff ("" = none)
+  std::string name;                              // the optional `*name' of the event (gfs_event_read, src/event.c:198-203)
   gfship_particles * pl = nullptr;
+};
+
+// GfsSourceParticulate (modules/particulatecommon.c:2230-2350): the list, rkernel, the text of kernel and
+// the variables <list>_Fx, _Fy[, _Fz]
+struct SourceParticulateSpec {
+  ParticleSpec * ps = nullptr;
+  double rkernel = 0.;
+  std::string kernel;                            // "" = the constant 0 of source_particulate_init
+  int fvar[3] = { -1, -1, -1 };
 };
 
 struct Run {
@@ -200,6 +210,11 @@ struct Run {
   std::vector<std::unique_ptr<Event>> events;
   std::vector<std::unique_ptr<Output>> outputs;
   std::vector<std::unique_ptr<ParticleSpec>> plists;
+  std::vector<std::unique_ptr<SourceParticulateSpec>> source_particulates;
+  ParticleSpec * plist_by_name (const std::string & name) const {
+    for (auto & ps : plists) if (!ps->name.empty () && ps->name == name) return ps.get ();
+    return nullptr;
+  }
   bool particulate_forces () const        // a list of GfsParticulate with GfsParticleForce objects
   {
     for (auto & ps : plists) if (!ps->forces.empty ()) return true;
@@ -827,9 +842,12 @@ void parse_object (Run & R, Reader & r)
     // (modules/particulatecommon.c:1022-1093):
     //   GfsParticleList { event } [GfsParticle|GfsParticulate] { objects } [{ forces }] [idlast]
     Event * e = new Event;
+    std::string ename;
+    if (r.peek (false) == '*') ename = r.word (false).substr (1);     /* optional name, src/event.c:198-203 */
     read_event_params (r, *e);
     R.plists.emplace_back (new ParticleSpec);
     ParticleSpec * ps = R.plists.back ().get ();
+    ps->name = ename;
     auto strip = [] (std::string w) { return w.compare (0, 3, "Gfs") == 0 ? w.substr (3) : w; };
     std::string item;
     if (r.peek (false) != '{') item = strip (r.word (false));
@@ -899,6 +917,84 @@ void parse_object (Run & R, Reader & r)
 	exit (1);
       }
     };
+    add_event (R, e, cls, line);
+  }
+  else if (cls == "ParticulateField" || cls == "SourceParticulate") {
+    // particulate_field_read (modules/particulatecommon.c:1959-1984):  GfsParticulateField [{ event }] NAME LIST
+    // source_particulate_read (:2230-2318):  GfsSourceParticulate [{ event }] LIST { rkernel = R kernel = FUNCTION }
+    // LIST is the `*name' of a GfsParticleList read above (gfs_object_from_name)
+    const bool field = cls == "ParticulateField";
+    Event * e = new Event;
+    if (!field) e->istep = 1;                     /* source_particulate_init, :2342-2350 */
+    if (r.peek (false) == '{') read_event_params (r, *e);
+    std::string vname;
+    if (field) vname = r.word (false);            /* gfs_variable_read: the name of the variable */
+    if (r.at_end_of_object () || r.peek (false) == '{')
+      r.fail ("expecting a string (object name)");
+    const std::string lname = r.word (false);
+    ParticleSpec * ps = R.plist_by_name (lname);
+    if (!ps) {
+      if (R.var_index (lname) >= 0)
+	r.fail ("object '" + lname + "' is not a GfsParticleList");
+      r.fail ("unknown object '" + lname + "'");
+    }
+    if (!ps->particulate)
+      r.fail ("the list `" + lname + "' holds GfsParticle objects: Gfs" + cls + " needs GfsParticulate objects");
+    Run * pr = &R;
+    if (field) {
+      const int v = R.get_or_add_variable (vname);
+      R.device_vars.push_back (vname);
+      e->action = [pr, ps, v] () {
+        Run & R = *pr;
+	if (gfship_particulate_field (ps->pl, R.vars[v].dev) != GFSHIP_OK) {
+	  fprintf (stderr, "gfship: %s\n", gfship_last_error ());
+	  exit (1);
+	}
+	R.vars[v].host_time = -1.;
+      };
+    }
+    else {
+      if (!R.source_particulates.empty ())
+	r.fail ("one GfsSourceParticulate per simulation (the velocity takes one set of source fields)");
+      R.source_particulates.emplace_back (new SourceParticulateSpec);
+      SourceParticulateSpec * sp = R.source_particulates.back ().get ();
+      sp->ps = ps;
+      if (r.peek (false) != '{') r.fail ("expecting an opening brace");
+      {
+	int l0 = r.line ();
+	Reader b (r.braces (), "simulation file", l0);
+	while (!b.eof ()) {
+	  if (b.peek () == '{' || b.peek () == '=') b.fail ("expecting a keyword");
+	  const std::string k = b.word ();
+	  if (k != "rkernel" && k != "kernel") b.fail ("unknown keyword `" + k + "'");
+	  if (b.peek (false) != '=') b.fail ("expecting '='");
+	  b.expect ('=');
+	  if (k == "rkernel") sp->rkernel = atof (b.word ().c_str ());
+	  else sp->kernel = b.function ().text;
+	}
+      }
+      static const char * comp[3] = { "_Fx", "_Fy", "_Fz" };
+      for (int c = 0; c < R.dim; c++) {
+	const std::string fname = ps->name + comp[c];
+	if (R.var_index (fname) < 0) R.device_vars.push_back (fname);
+	sp->fvar[c] = R.get_or_add_variable (fname);
+      }
+      e->action = [pr, sp] () {
+	Run & R = *pr;
+	/* the forces read the density and the viscosity of the fluid at the time of the event */
+	if (refresh_alpha_cell (R) || refresh_viscosity_cell (R))
+	  exit (1);
+	gfship_field F[3] = { -1, -1, -1 };
+	for (int c = 0; c < R.dim; c++) {
+	  F[c] = R.vars[sp->fvar[c]].dev;
+	  R.vars[sp->fvar[c]].host_time = -1.;
+	}
+	if (gfship_source_particulate_event (sp->ps->pl, F) != GFSHIP_OK) {
+	  fprintf (stderr, "gfship: %s\n", gfship_last_error ());
+	  exit (1);
+	}
+      };
+    }
     add_event (R, e, cls, line);
   }
   else if (cls == "OutputEnergySpectra") {
@@ -2413,6 +2509,14 @@ int run (Run & R)
 	if (!ps->force_functions[f].empty ())
 	  CHECK (gfship_particles_set_force_coefficient (ps->pl, (int) f, ps->force_functions[f].c_str ()));
     }
+  }
+  // GfsSourceParticulate: the kernel of its list, and <list>_Fx/_Fy/_Fz as velocity source (mac_value and
+  // centered_value of the object, modules/particulatecommon.c:2029-2079)
+  for (auto & sp : R.source_particulates) {
+    CHECK (gfship_particles_set_kernel (sp->ps->pl, sp->rkernel, sp->kernel.empty () ? nullptr : sp->kernel.c_str ()));
+    gfship_field F[3] = { -1, -1, -1 };
+    for (int c = 0; c < R.dim; c++) F[c] = R.vars[sp->fvar[c]].dev;
+    CHECK (gfship_sim_set_source_fields (R.sim, F));
   }
   set_boundary_conditions (R);
   apply_init (R);

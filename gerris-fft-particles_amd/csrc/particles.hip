@@ -20,57 +20,11 @@
 // and gfship_particles_download returns the survivors in that order (the reference's list
 // order).  Tracers move less than one cell per step (CFL < 1), so the order stays good between
 // sorts.
-#include "gfship_internal.hpp"
+#include "particles.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <numeric>
 
-namespace gfship {
-struct RtcKernel;
-int  rtc_compile_coefficient (gfship_domain * dom, const char * text, RtcKernel ** out);
-int  rtc_launch_coefficient (RtcKernel * k, hipStream_t stream, int n, const unsigned char * alive,
-			     const double * rep, const double * const rel[3], const double * pdia,
-			     double t, double * out);
-void rtc_free (RtcKernel * k);
-}
-
-struct gfship_particles {
-  gfship_sim * sim = nullptr;
-  gfship_domain * dom = nullptr;
-  int n = 0;                   // slots in use (alive or not)
-  int cap = 0;                 // slots allocated
-  double * pos[3] = {}, * old[3] = {};
-  unsigned * id = nullptr;
-  unsigned char * alive = nullptr;
-  unsigned * d_count = nullptr;
-  // sort by cell
-  unsigned * orig = nullptr;          // creation slot of the particle stored in each slot
-  double * pos2[3] = {}, * old2[3] = {};   // gather targets (swapped with pos/old after a sort)
-  unsigned * id2 = nullptr, * orig2 = nullptr;
-  unsigned char * alive2 = nullptr;
-  unsigned * key = nullptr, * key2 = nullptr, * slot = nullptr, * slot2 = nullptr;
-  void * sort_tmp = nullptr;
-  size_t sort_tmp_bytes = 0;
-  int sort_every = 16, events_since_sort = -1;   // -1: never sorted yet
-  // migration through GfsBoundaryMpi sides
-  gfship_particle_migrate_fn migrate = nullptr; void * migrate_ctx = nullptr;
-  double * outbox = nullptr;          // device, 6 x out_cap records of 7 doubles
-  unsigned * out_count = nullptr;     // device, 6 counters
-  int out_cap = 0;
-  // GfsParticulate (modules/particulatecommon.h:35-48), indexed by the creation slot (`orig`):
-  // velocity, force, mass, volume, diameter; the list's forces in application order
-  bool particulate = false;
-  int np0 = 0;                        // particles at creation
-  double * vel[3] = {}, * force[3] = {}, * mass = nullptr, * volume = nullptr, * dia = nullptr;
-  int nforces = 0, forces[8] = {};
-  double gravity[3] = {};
-  gfship_field uold[3] = { -1, -1, -1 };   // Un, Vn, Wn of GfsForceCoeff
-  // GfsFunction coefficients of the GfsForceCoeff objects, compiled for the device (rtc.hip): the
-  // variables Rep, Urelp, Vrelp, Wrelp, Pdia of every particle (slot order), and the values
-  gfship::RtcKernel * coef_fn[8] = {};
-  double * coef[8] = {}, * cin[6] = {};
-  int coef_cap = 0;
-};
 
 namespace gfship {
 
@@ -86,30 +40,6 @@ struct PartArgs {
   unsigned * count;
   int migrate;                 // particles leaving through an external side are kept for the hook
 };
-
-// ftt_cell_locate on the unit box centred on the origin, leaf level
-template <int DIM>
-__device__ __forceinline__ bool locate (int depth, const double target[3], int ijk[3])
-{
-  double pos[3] = { 0., 0., 0. };
-  double size = 1./2.;
-#pragma unroll
-  for (int c = 0; c < DIM; c++)
-    if (target[c] > pos[c] + size || target[c] < pos[c] - size)
-      return false;
-  int q[3] = { 0, 0, 0 };
-  for (int l = 0; l < depth; l++) {
-    size /= 2.;
-#pragma unroll
-    for (int c = 0; c < DIM; c++) {
-      bool up = target[c] > pos[c];
-      q[c] = 2*q[c] + (up ? 1 : 0);
-      pos[c] += (up ? 1. : -1.)*size;
-    }
-  }
-  ijk[0] = q[0] + 1; ijk[1] = q[1] + 1; ijk[2] = DIM == 3 ? q[2] + 1 : 0;
-  return true;
-}
 
 // gfs_interpolate (src/fluid.c:2697-2710) of one variable at p inside cell (i,j,k)
 template <int DIM>
@@ -451,7 +381,12 @@ particulate_coeff_inputs_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
 }
 
 // gfs_particulate_event (:768-842) in a gfs_particle_list_event (:980-1015)
-template <int DIM, bool RHO, bool MU>
+// ONFLUID: the forces of the fluid on the particle that a GfsSourceParticulate gives back to the fluid
+// (compute_forces_onfluid, :753-765, in source_particulate_event, :2199-2206): force = 0, then every force
+// of the list but GfsForceBuoy, force[c] = new_force[c]*volume + force[c]; only `force' is written -- the
+// particle does not move, keeps its mass (what compute_addedmass_force adds belongs to the event) and
+// stays on the list; a particle without a cell gets the zero force every compute_*_force returns there
+template <int DIM, bool RHO, bool MU, bool ONFLUID = false>
 __global__ void __launch_bounds__(256)
 particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
 {
@@ -464,7 +399,14 @@ particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
   int cell[3];
   // remove_particles_not_in_domain, :955-969
   if (!locate<DIM> (depth, p, cell)) {
-    P.alive[q] = 0;
+    if constexpr (ONFLUID) {
+      const unsigned o = A.orig[q];
+#pragma unroll
+      for (int c = 0; c < 3; c++)
+	A.force[c][o] = 0.;
+    }
+    else
+      P.alive[q] = 0;
     return;
   }
   const unsigned o = A.orig[q];
@@ -486,6 +428,8 @@ particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
   // same expressions per force: same bits)
   bool need_fvel = false, need_dudt = false;
   for (int f = 0; f < A.nforces; f++) {
+    if (ONFLUID && A.forces[f] == FORCE_BUOY)
+      continue;
     need_fvel = need_fvel || A.forces[f] != FORCE_BUOY;
     need_dudt = need_dudt || A.forces[f] == FORCE_INERTIAL || A.forces[f] == FORCE_ADDEDMASS;
   }
@@ -499,6 +443,8 @@ particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
     inertial_force<DIM, RHO> (A, cell, p, idx, fvel, dudt);
   for (int f = 0; f < A.nforces; f++) {
     double force[3] = { 0., 0., 0. };
+    if (ONFLUID && A.forces[f] == FORCE_BUOY)      /* :756 */
+      continue;
     switch (A.forces[f]) {
     case FORCE_INERTIAL:
       force[0] = dudt[0]; force[1] = dudt[1]; force[2] = dudt[2];
@@ -509,7 +455,8 @@ particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
 #pragma unroll
       for (int c = 0; c < DIM; c++)
 	force[c] *= cm;
-      mass += fluid_rho*volume*cm;
+      if (!ONFLUID)
+	mass += fluid_rho*volume*cm;
       break;
     }
     case FORCE_LIFT: {          // compute_lift_force, :455-524; vorticity_vector, :146-168
@@ -582,6 +529,12 @@ particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
     for (int c = 0; c < DIM; c++)
       pf[c] = force[c]*volume + pf[c];
     if (DIM == 2) pf[2] = 0.;
+  }
+  if constexpr (ONFLUID) {
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+      A.force[c][o] = pf[c];
+    return;
   }
 #pragma unroll
   for (int c = 0; c < DIM; c++) {
@@ -732,13 +685,6 @@ using namespace gfship;
 
 extern "C" {
 
-struct gfship_sim_view {
-  gfship_domain * dom; const gfship_field * u; double dt; double visc; int visc_faces;
-  int has_alpha;                    /* gfship_sim_set_alpha */
-  gfship_field alpha_cell, mu;      /* gfship_sim_set_alpha_cell, gfship_sim_set_viscosity_cell; -1: not set */
-};
-gfship_sim_view gfship_sim_view_get (gfship_sim * s);   /* simulation.hip */
-
 int gfship_particles_create (gfship_particles ** out, gfship_sim * sim, int np,
 			     const double * pos, const unsigned * id)
 {
@@ -808,6 +754,8 @@ void gfship_particles_destroy (gfship_particles * pl)
   if (pl->mass) (void) hipFree (pl->mass);
   if (pl->volume) (void) hipFree (pl->volume);
   if (pl->dia) (void) hipFree (pl->dia);
+  if (pl->rb) (void) hipFree (pl->rb);
+  gfship::coupling_free (pl);
   for (int f = 0; f < 8; f++) {
     if (pl->coef[f]) (void) hipFree (pl->coef[f]);
     gfship::rtc_free (pl->coef_fn[f]);
@@ -952,6 +900,9 @@ static int particles_reserve (gfship_particles * pl, int need)
     GFSHIP_HIP (grow ((void **) &pl->mass, sizeof (double), true));
     GFSHIP_HIP (grow ((void **) &pl->volume, sizeof (double), true));
     GFSHIP_HIP (grow ((void **) &pl->dia, sizeof (double), true));
+    /* (rb is not kept for newcomers: particles arrive through GfsBoundaryMpi sides only, and every reader
+       of rb refuses a box with such sides, coupling.hip) */
+    GFSHIP_HIP (grow ((void **) &pl->rb, sizeof (double), true));
   }
   pl->cap = (int) m;
   return GFSHIP_OK;
@@ -1101,7 +1052,9 @@ static int store_previous_vel (gfship_particles * pl)
 // the fields of the fluid the forces of a list read (fluid_rho and viscosity of compute_*_force): alpha
 // at the cell centres whenever the simulation has it, the viscosity of U at the leaf centres where U
 // has one -- which it must where the viscosity of U is given on the faces
-static int particulate_fluid_check (const gfship_sim_view & v)
+} // extern "C"
+
+int gfship::particulate_fluid_check (const gfship_sim_view & v)
 {
   GFSHIP_CHECK (!v.visc_faces || v.mu >= 0, GFSHIP_EUNSUPPORTED,
 		"particle forces together with a viscosity that varies in space need the viscosity at the "
@@ -1112,7 +1065,11 @@ static int particulate_fluid_check (const gfship_sim_view & v)
   return GFSHIP_OK;
 }
 
-static int particulate_event (gfship_particles * pl, const PartArgs & P, const gfship_sim_view & v)
+extern "C" {
+
+// onfluid: the forces on the fluid alone (particulate_list_event_kernel <ONFLUID>): nothing but `force' changes
+static int particulate_event (gfship_particles * pl, const PartArgs & P, const gfship_sim_view & v,
+			      bool onfluid = false)
 {
   gfship_domain * dom = pl->dom;
   ParticulateFieldArgs A;
@@ -1174,6 +1131,16 @@ static int particulate_event (gfship_particles * pl, const PartArgs & P, const g
 	A.coef[f] = pl->coef[f];
       }
   }
+  if (onfluid) {
+    with_bools ([&] (auto D3, auto RHO, auto MU) {
+      constexpr int DIM = decltype (D3)::value ? 3 : 2;
+      constexpr bool R = decltype (RHO)::value, M = decltype (MU)::value;
+      hipLaunchKernelGGL ((particulate_list_event_kernel<DIM, R, M, true>), dim3 (grid), dim3 (block), 0,
+			  dom->stream, static_cast<const ParticulateArgsOf<R, M> &> (A), dom->depth);
+    }, dom->dim == 3, rho, mu);
+    GFSHIP_HIP (hipGetLastError ());
+    return GFSHIP_OK;
+  }
   with_bools ([&] (auto D3, auto RHO, auto MU) {
     constexpr int DIM = decltype (D3)::value ? 3 : 2;
     constexpr bool R = decltype (RHO)::value, M = decltype (MU)::value;
@@ -1215,6 +1182,13 @@ int gfship_particles_set_particulate (gfship_particles * pl, const double * vel,
     for (size_t q = 0; q < np; q++)
       tmp[q] = 2.*pow (3.0*volume[q]/4.0/M_PI, 1./3.);
     GFSHIP_HIP (hipMemcpy (pl->dia, tmp.data (), np*sizeof (double), hipMemcpyHostToDevice));
+  }
+  /* rb of distance_normalization (:2091), the host's pow like the diameter */
+  GFSHIP_HIP (hipMalloc ((void **) &pl->rb, m*sizeof (double)));
+  if (np) {
+    for (size_t q = 0; q < np; q++)
+      tmp[q] = pow (3.*volume[q]/(4.*M_PI), 1./3.);
+    GFSHIP_HIP (hipMemcpy (pl->rb, tmp.data (), np*sizeof (double), hipMemcpyHostToDevice));
   }
   pl->particulate = true;
   return GFSHIP_OK;
@@ -1358,6 +1332,35 @@ int gfship_particle_list_event (gfship_particles * pl)
   if (migrates)
     return particles_migrate (pl);
   return GFSHIP_OK;
+}
+
+// the forces of source_particulate_event (modules/particulatecommon.c:2199-2206)
+int gfship_particles_forces_on_fluid (gfship_particles * pl)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_CHECK (pl->particulate, GFSHIP_EUNSUPPORTED,
+		"the forces on the fluid are those of particulates (gfship_particles_set_particulate)");
+  gfship_sim_view v = gfship_sim_view_get (pl->sim);
+  gfship_domain * dom = pl->dom;
+  GFSHIP_CHECK (!dom->has_external, GFSHIP_EUNSUPPORTED,
+		"GfsSourceParticulate on a box with GfsBoundaryMpi sides is not supported");
+  int r = particulate_fluid_check (v);
+  if (r) return r;
+  if (pl->n == 0) return GFSHIP_OK;
+  PartArgs A;
+  A.L = dom->lay[dom->depth];
+  for (int d = 0; d < 6; d++) A.side[d] = dom->side[d];
+  A.n = pl->n;
+  for (int c = 0; c < 3; c++) {
+    A.pos[c] = pl->pos[c];
+    A.old[c] = pl->old[c];
+    A.u[c] = c < dom->dim ? dom->fields[v.u[c]].lev[dom->depth] : nullptr;
+  }
+  A.alive = pl->alive;
+  A.dt = v.dt;
+  A.count = pl->d_count;
+  A.migrate = 0;
+  return particulate_event (pl, A, v, true);
 }
 
 int gfship_particles_count (gfship_particles * pl)

@@ -1,0 +1,112 @@
+// particles.hpp -- the particle list and the cell search shared by particles.hip and coupling.hip.
+#pragma once
+#include "gfship_internal.hpp"
+
+namespace gfship {
+struct RtcKernel;
+int  rtc_compile_coefficient (gfship_domain * dom, const char * text, RtcKernel ** out);
+int  rtc_launch_coefficient (RtcKernel * k, hipStream_t stream, int n, const unsigned char * alive,
+			     const double * rep, const double * const rel[3], const double * pdia,
+			     double t, double * out);
+void rtc_free (RtcKernel * k);
+// the kernel function of a GfsSourceParticulate: a GfsFunction (spatial) of x, y, z, t, evaluated for the
+// first cnt[r/stride] records of every block of `stride' records
+int  rtc_compile_spatial (gfship_domain * dom, const char * text, RtcKernel ** out);
+int  rtc_launch_spatial (RtcKernel * k, hipStream_t stream, long nrec, int stride, const int * cnt,
+			 const double * x, const double * y, const double * z, double t, double * out);
+}
+
+struct gfship_particles {
+  gfship_sim * sim = nullptr;
+  gfship_domain * dom = nullptr;
+  int n = 0;                   // slots in use (alive or not)
+  int cap = 0;                 // slots allocated
+  double * pos[3] = {}, * old[3] = {};
+  unsigned * id = nullptr;
+  unsigned char * alive = nullptr;
+  unsigned * d_count = nullptr;
+  // sort by cell
+  unsigned * orig = nullptr;          // creation slot of the particle stored in each slot
+  double * pos2[3] = {}, * old2[3] = {};   // gather targets (swapped with pos/old after a sort)
+  unsigned * id2 = nullptr, * orig2 = nullptr;
+  unsigned char * alive2 = nullptr;
+  unsigned * key = nullptr, * key2 = nullptr, * slot = nullptr, * slot2 = nullptr;
+  void * sort_tmp = nullptr;
+  size_t sort_tmp_bytes = 0;
+  int sort_every = 16, events_since_sort = -1;   // -1: never sorted yet
+  // migration through GfsBoundaryMpi sides
+  gfship_particle_migrate_fn migrate = nullptr; void * migrate_ctx = nullptr;
+  double * outbox = nullptr;          // device, 6 x out_cap records of 7 doubles
+  unsigned * out_count = nullptr;     // device, 6 counters
+  int out_cap = 0;
+  // GfsParticulate (modules/particulatecommon.h:35-48), indexed by the creation slot (`orig`):
+  // velocity, force, mass, volume, diameter; the list's forces in application order
+  bool particulate = false;
+  int np0 = 0;                        // particles at creation
+  double * vel[3] = {}, * force[3] = {}, * mass = nullptr, * volume = nullptr, * dia = nullptr;
+  int nforces = 0, forces[8] = {};
+  double gravity[3] = {};
+  gfship_field uold[3] = { -1, -1, -1 };   // Un, Vn, Wn of GfsForceCoeff
+  // GfsFunction coefficients of the GfsForceCoeff objects, compiled for the device (rtc.hip): the
+  // variables Rep, Urelp, Vrelp, Wrelp, Pdia of every particle (slot order), and the values
+  gfship::RtcKernel * coef_fn[8] = {};
+  double * coef[8] = {}, * cin[6] = {};
+  int coef_cap = 0;
+  // two-way coupling (coupling.hip): rb of distance_normalization per creation slot, the kernel of the
+  // GfsSourceParticulate (its radius; a constant or a compiled GfsFunction) and the work arrays of the
+  // void fraction and of the spreading
+  double * rb = nullptr;
+  double rkernel = 0., kernel_value = 0.;
+  gfship::RtcKernel * kernel_fn = nullptr;
+  unsigned * where = nullptr;         // slot of each creation slot
+  int where_cap = 0;
+  unsigned long long * ckey = nullptr, * ckey2 = nullptr;   // (cell, creation slot) keys
+  double * cq[3] = {}, * cval = nullptr, * cval2 = nullptr; // per record: q of the cell, K (q)
+  double * ccorr = nullptr;           // per particle of the chunk: correction
+  int * ccnt = nullptr;               // per particle of the chunk: leaves its kernel reaches
+  int * cflag = nullptr;
+  size_t ckey_cap = 0, crec_cap = 0, cpart_cap = 0;
+};
+
+extern "C" {
+struct gfship_sim_view {
+  gfship_domain * dom; const gfship_field * u; double dt; double visc; int visc_faces;
+  int has_alpha;                    /* gfship_sim_set_alpha */
+  gfship_field alpha_cell, mu;      /* gfship_sim_set_alpha_cell, gfship_sim_set_viscosity_cell; -1: not set */
+};
+gfship_sim_view gfship_sim_view_get (gfship_sim * s);   /* simulation.hip */
+}
+
+namespace gfship {
+// the refusals of every entry that evaluates the forces of a list (particles.hip)
+int particulate_fluid_check (const gfship_sim_view & v);
+void coupling_free (gfship_particles * pl);   // coupling.hip
+}
+
+namespace gfship {
+
+// ftt_cell_locate on the unit box centred on the origin, leaf level
+template <int DIM>
+__device__ __forceinline__ bool locate (int depth, const double target[3], int ijk[3])
+{
+  double pos[3] = { 0., 0., 0. };
+  double size = 1./2.;
+#pragma unroll
+  for (int c = 0; c < DIM; c++)
+    if (target[c] > pos[c] + size || target[c] < pos[c] - size)
+      return false;
+  int q[3] = { 0, 0, 0 };
+  for (int l = 0; l < depth; l++) {
+    size /= 2.;
+#pragma unroll
+    for (int c = 0; c < DIM; c++) {
+      bool up = target[c] > pos[c];
+      q[c] = 2*q[c] + (up ? 1 : 0);
+      pos[c] += (up ? 1. : -1.)*size;
+    }
+  }
+  ijk[0] = q[0] + 1; ijk[1] = q[1] + 1; ijk[2] = DIM == 3 ? q[2] + 1 : 0;
+  return true;
+}
+
+} // namespace gfship

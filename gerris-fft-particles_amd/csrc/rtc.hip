@@ -70,8 +70,11 @@ void rtc_free (RtcKernel * k)
   delete k;
 }
 
-// the kernel around a GfsFunction of the variables of gfs_force_coeff_read (:189-207) and the time
-int rtc_compile_coefficient (gfship_domain * dom, const char * text, RtcKernel ** out)
+// the text of a GfsFunction -- an expression or a { block } with a return -- as the body of the device
+// function whose head is `signature', followed by the kernel `kernel_src' that calls it; compiled for the
+// GPU of the domain, `entry' is the kernel's name
+static int rtc_compile (gfship_domain * dom, const char * text, const char * signature,
+			const char * kernel_src, const char * entry, RtcKernel ** out)
 {
   GFSHIP_CHECK (dom && text && out, GFSHIP_EINVAL, "null argument");
   *out = nullptr;
@@ -82,23 +85,13 @@ int rtc_compile_coefficient (gfship_domain * dom, const char * text, RtcKernel *
   GFSHIP_CHECK (a != std::string::npos, GFSHIP_EINVAL, "empty function");
   t = t.substr (a, b - a + 1);
   const bool block = t[0] == '{';
-  std::string src =
-    "#ifndef M_PI\n#define M_PI 3.14159265358979323846\n#endif\n"
-    "static __device__ double gfship_f (double Rep, double Urelp, double Vrelp, double Wrelp,\n"
-    "                                   double Pdia, double t)\n";
+  std::string src = "#ifndef M_PI\n#define M_PI 3.14159265358979323846\n#endif\n";
+  src += signature;
   if (block)
     src += t + "\n";
   else
     src += "{ return (" + t + "); }\n";
-  src +=
-    "extern \"C\" __global__ void gfship_coeff (int n, const unsigned char * alive,\n"
-    "    const double * rep, const double * urel, const double * vrel, const double * wrel,\n"
-    "    const double * pdia, double t, double * out)\n"
-    "{\n"
-    "  int q = blockIdx.x*blockDim.x + threadIdx.x;\n"
-    "  if (q >= n || alive[q] != 1) return;\n"
-    "  out[q] = gfship_f (rep[q], urel[q], vrel[q], wrel[q], pdia[q], t);\n"
-    "}\n";
+  src += kernel_src;
   hipDeviceProp_t prop;
   GFSHIP_HIP (hipGetDeviceProperties (&prop, dom->device));
   const std::string arch = std::string ("--offload-arch=") + prop.gcnArchName;
@@ -126,12 +119,55 @@ int rtc_compile_coefficient (gfship_domain * dom, const char * text, RtcKernel *
   GFSHIP_CHECK (e == HIPRTC_SUCCESS, GFSHIP_EHIP, "hiprtcGetCode: %s", g_rtc.GetErrorString (e));
   RtcKernel * k = new RtcKernel;
   hipError_t he = hipModuleLoadData (&k->mod, code.data ());
-  if (he == hipSuccess) he = hipModuleGetFunction (&k->fn, k->mod, "gfship_coeff");
+  if (he == hipSuccess) he = hipModuleGetFunction (&k->fn, k->mod, entry);
   if (he != hipSuccess) {
     rtc_free (k);
     return hip_fail (he, "loading the compiled function", __FILE__, __LINE__);
   }
   *out = k;
+  return GFSHIP_OK;
+}
+
+// the kernel around a GfsFunction of the variables of gfs_force_coeff_read (:189-207) and the time
+int rtc_compile_coefficient (gfship_domain * dom, const char * text, RtcKernel ** out)
+{
+  return rtc_compile (dom, text,
+    "static __device__ double gfship_f (double Rep, double Urelp, double Vrelp, double Wrelp,\n"
+    "                                   double Pdia, double t)\n",
+    "extern \"C\" __global__ void gfship_coeff (int n, const unsigned char * alive,\n"
+    "    const double * rep, const double * urel, const double * vrel, const double * wrel,\n"
+    "    const double * pdia, double t, double * out)\n"
+    "{\n"
+    "  int q = blockIdx.x*blockDim.x + threadIdx.x;\n"
+    "  if (q >= n || alive[q] != 1) return;\n"
+    "  out[q] = gfship_f (rep[q], urel[q], vrel[q], wrel[q], pdia[q], t);\n"
+    "}\n", "gfship_coeff", out);
+}
+
+// the kernel function of a GfsSourceParticulate (modules/particulatecommon.c:2271-2289): a GfsFunction
+// (spatial) of x, y, z and t (gfs_function_spatial_value, src/utils.c:1476-1494), evaluated at the
+// normalised distances of the records of the spreading (coupling.hip): record r belongs to particle
+// r/stride of the chunk and is in use if r%stride < cnt[r/stride]
+int rtc_compile_spatial (gfship_domain * dom, const char * text, RtcKernel ** out)
+{
+  return rtc_compile (dom, text,
+    "static __device__ double gfship_f (double x, double y, double z, double t)\n",
+    "extern \"C\" __global__ void gfship_spatial (long nrec, int stride, const int * cnt,\n"
+    "    const double * qx, const double * qy, const double * qz, double t, double * out)\n"
+    "{\n"
+    "  long r = (long) blockIdx.x*blockDim.x + threadIdx.x;\n"
+    "  if (r >= nrec || (int) (r%stride) >= cnt[r/stride]) return;\n"
+    "  out[r] = gfship_f (qx[r], qy[r], qz[r], t);\n"
+    "}\n", "gfship_spatial", out);
+}
+
+int rtc_launch_spatial (RtcKernel * k, hipStream_t stream, long nrec, int stride, const int * cnt,
+			const double * x, const double * y, const double * z, double t, double * out)
+{
+  if (nrec <= 0) return GFSHIP_OK;
+  void * args[] = { &nrec, &stride, &cnt, &x, &y, &z, &t, &out };
+  GFSHIP_HIP (hipModuleLaunchKernel (k->fn, (unsigned) ((nrec + 255)/256), 1, 1, 256, 1, 1, 0, stream, args,
+				     nullptr));
   return GFSHIP_OK;
 }
 

@@ -41,6 +41,9 @@ struct gfship_sim {
   bool has_mu = false;
   gfship_field dconst[3] = {-1, -1, -1};   // a constant coefficient as face fields, where alpha_cell asks for the per-face path
   gfship_field msrc[3] = {-1, -1, -1};     // per-cell MAC source of the implicit diffusion of U, V, W
+  // velocity sources given as fields (gfship_sim_set_source_fields): what GfsSourceParticulate adds to U, V, W
+  gfship_field srcf[3] = {-1, -1, -1};
+  bool has_srcf = false;
   gfship_multilevel_params diffusion_params[3];
   gfship_field drhs = -1, rhoc = -1;   // temporaries of variable_diffusion
   bool cfl_ready = false;              // maxima for the CFL condition left by the last projection
@@ -128,17 +131,35 @@ int variable_mac_source (gfship_sim * s, int c, gfship_field out)
 
 // the array the general advection path reads the MAC source of component c from (nullptr: none, or the
 // constant-coefficient expression inside the kernels)
+//
+// With source fields the array holds the whole sum of gfs_variable_mac_source (src/source.c:38-59) but the
+// constant of a GfsSource, which the kernels add last.  The sum runs over v->sources, and gts_container_add
+// puts a new source at the HEAD of that list (the reference itself reverses a list it has filled that way
+// to get back the order of the file, src/event.c:2499-2504): the sources are visited last-read first.  A
+// GfsSourceParticulate names a particle list, so it stands below that list in the file, after the
+// GfsSourceDiffusion and GfsSource objects of a usual file; it derives from GfsSourceVelocity and joins the
+// sources of every component.  The order of the additions is therefore
+//   sum = 0. + mac_value (GfsSourceParticulate) + mac_value (GfsSourceDiffusion) + intensity (GfsSource)
+// -- the last two in the order this library had already.
 int mac_source_array (gfship_sim * s, int c, const double ** out)
 {
   *out = nullptr;
-  if (!diffusion_faces (s) || !has_viscosity (s, c))
+  const bool fields = s->has_srcf;
+  if (!fields && (!diffusion_faces (s) || !has_viscosity (s, c)))
     return GFSHIP_OK;
   if (s->msrc[c] < 0)
     s->msrc[c] = gfship_field_alloc (s->dom, -1);
   if (s->msrc[c] < 0) return s->msrc[c];
-  int r = variable_mac_source (s, c, s->msrc[c]);
-  if (r) return r;
+  const bool diffusion = has_viscosity (s, c);
+  if (diffusion) {
+    int r = variable_mac_source (s, c, s->msrc[c]);
+    if (r) return r;
+  }
   *out = s->dom->fields[s->msrc[c]].lev[s->dom->depth];
+  if (fields) {
+    s->dom->fields[s->msrc[c]].zero[s->dom->depth] = false;
+    return launch_mac_source_fields (s->dom, c, leaf (s, s->srcf[c]), diffusion, leaf (s, s->msrc[c]));
+  }
   return GFSHIP_OK;
 }
 
@@ -200,7 +221,7 @@ int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, g
   /* MAC divergence, scaled by 1/dt (approximate projection: together with the MAC velocities
      interpolated from the centred ones, gfs_approximate_projection src/timestep.c:572-580) */
   for (int c = 0; c < dom->dim; c++)
-    if (has_viscosity (s, c) || dom->src[c] != 0.) lazy = false;   /* the CFL needs the full kernel then */
+    if (has_viscosity (s, c) || dom->src[c] != 0. || s->has_srcf) lazy = false;   /* the CFL needs the full kernel then */
   if (!approximate || !s->tracers.empty () || s->un_handle_given || p != s->p || !dom->sw.lazy_un)
     lazy = false;
   if (!approximate)
@@ -223,7 +244,7 @@ int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, g
   s->cfl_ready = false;
   bool want_max = approximate, ghosts_done = false;
   for (int c = 0; c < dom->dim; c++)
-    if (has_viscosity (s, c) || dom->src[c] != 0.) want_max = false;   /* the acceleration term needs the full kernel */
+    if (has_viscosity (s, c) || dom->src[c] != 0. || s->has_srcf) want_max = false;   /* the acceleration term needs the full kernel */
   if (s->has_alpha) {
     /* the same pass with gfs_face_weighted_gradient's weights (the CFL maxima come from their own pass) */
     want_max = false;
@@ -318,7 +339,7 @@ int variable_sources (gfship_sim * s, gfship_field v, gfship_field sv, int gradi
   ptrs6 (s, fv);
   int c = s->dom->fields[v].component;
   if (godunov_fused_supported (s->dom) && gradient <= 1 &&      /* limiters 2 .. 4: the general path */
-      !(velocity && diffusion_faces (s))) {                     /* ... and the MAC source from an array */
+      !(velocity && (diffusion_faces (s) || s->has_srcf))) {    /* ... and the MAC source from an array */
     /* periodic box: face values recomputed inside the flux kernel, no face-value arrays */
     gfship_domain * dom = s->dom;
     const int L = dom->depth;
@@ -353,6 +374,13 @@ int variable_sources (gfship_sim * s, gfship_field v, gfship_field sv, int gradi
   for (int q = 0; q < s->dom->dim; q++)
     if (v == s->u[q])
       gsrc = s->dom->src[q];
+  if (velocity && s->has_srcf && c >= 0 && c < s->dom->dim && v == s->u[c]) {
+    /* add_sources (src/source.c:66-79) with the centred value of the source fields first (the order of
+       mac_source_array), in a pass of its own after the fluxes: the flux kernel and its instantiations stay
+       what they are, and val += dt*sum on a value that has been stored and loaded again is the same addition */
+    TRY (launch_flux_update (s->dom, velocity, leaf (s, sv), un, fv, gm, gc, dt, 0.));
+    return launch_centered_source_fields (s->dom, leaf (s, sv), leaf (s, s->srcf[c]), gsrc, dt);
+  }
   TRY (launch_flux_update (s->dom, velocity, leaf (s, sv), un, fv, gm, gc, dt, gsrc));
   return GFSHIP_OK;
 }
@@ -516,6 +544,24 @@ int gfship_sim_set_source (gfship_sim * s, int c, double intensity)
   return GFSHIP_OK;
 }
 
+int gfship_sim_set_source_fields (gfship_sim * s, const gfship_field F[3])
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
+  s->cfl_ready = false;
+  if (!F) {
+    s->has_srcf = false;
+    return GFSHIP_OK;
+  }
+  GFSHIP_CHECK (!s->dom->has_external, GFSHIP_EUNSUPPORTED,
+		"velocity sources from fields on a box with GfsBoundaryMpi sides are not supported");
+  for (int c = 0; c < s->dom->dim; c++)
+    GFSHIP_CHECK (get_field (s->dom, F[c]) != nullptr, GFSHIP_EINVAL, "F[%d] is not a field of the domain", c);
+  for (int c = 0; c < s->dom->dim; c++)
+    s->srcf[c] = F[c];
+  s->has_srcf = true;
+  return GFSHIP_OK;
+}
+
 int gfship_sim_set_alpha (gfship_sim * s, const gfship_field alpha[3])
 {
   GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
@@ -614,8 +660,19 @@ int gfship_variable_mac_source (gfship_sim * s, int c, gfship_field out)
   GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
   GFSHIP_CHECK (c >= 0 && c < s->dom->dim, GFSHIP_EINVAL, "component %d out of range", c);
   GFSHIP_CHECK (get_field (s->dom, out) != nullptr, GFSHIP_EINVAL, "out is not a field of the domain");
-  GFSHIP_CHECK (has_viscosity (s, c), GFSHIP_EINVAL, "component %d has no GfsSourceDiffusion", c);
+  GFSHIP_CHECK (has_viscosity (s, c) || s->has_srcf, GFSHIP_EINVAL,
+		"component %d has no GfsSourceDiffusion and no source field", c);
   TRY (before_write (s->dom));
+  if (s->has_srcf) {
+    /* the sum with the source fields (mac_source_array), copied out */
+    GFSHIP_CHECK (out != s->srcf[c], GFSHIP_EINVAL, "out is the source field");
+    const double * m;
+    TRY (mac_source_array (s, c, &m));
+    s->dom->fields[out].zero[s->dom->depth] = false;
+    GFSHIP_HIP (hipMemcpyAsync (leaf (s, out), m, s->dom->lay[s->dom->depth].total*sizeof (double),
+				hipMemcpyDeviceToDevice, s->dom->stream));
+    return GFSHIP_OK;
+  }
   return variable_mac_source (s, c, out);
 }
 
@@ -658,7 +715,7 @@ static int predicted_face_velocities (gfship_sim * s, double mac_dt)
   /* the reset of every face (gfs_face_reset_normal_velocity) is implied: each component's
      faces are all overwritten below */
   if ((godunov_fused_supported (s->dom) || godunov_fused_mpi_supported (s->dom)) &&
-      s->advection_params.gradient <= 1 && !diffusion_faces (s)) {
+      s->advection_params.gradient <= 1 && !diffusion_faces (s) && !s->has_srcf) {
     double * u[3], * un[3];
     ptrs3 (s, s->u, u);
     ptrs3 (s, s->un, un);
@@ -724,7 +781,7 @@ static int centered_velocity_advection (gfship_sim * s, const gfship_field gmac[
   if (corrected) *corrected = false;
   if (u_coarse) *u_coarse = false;
   if (s->dom->dim == 3 && (godunov_fused_supported (s->dom) || godunov_fused_mpi_supported (s->dom)) &&
-      s->dom->sw.advect3 && s->advection_params.gradient <= 1 && !diffusion_faces (s) &&
+      s->dom->sw.advect3 && s->advection_params.gradient <= 1 && !diffusion_faces (s) && !s->has_srcf &&
       s->visc[0] == 0. && s->visc[1] == 0. && s->visc[2] == 0.) {
     /* the three components in one pass over the box (same MAC velocities, nothing of one component
        feeds another): into scratch leaf levels, then the storage is swapped */

@@ -163,6 +163,13 @@ SIGNATURES = {
     "gfship_particles_set_forces": (_i, [_vp, _i, C.POINTER(_i), _pd]),
     "gfship_particles_set_force_coefficient": (_i, [_vp, _i, C.c_char_p]),
     "gfship_particles_download_particulate": (_i, [_vp, _pd, _pd, _pd]),
+    "gfship_particulate_field": (_i, [_vp, _i]),
+    "gfship_particles_forces_on_fluid": (_i, [_vp]),
+    "gfship_particles_set_kernel": (_i, [_vp, C.c_double, C.c_char_p]),
+    "gfship_source_particulate_event": (_i, [_vp, C.POINTER(_i)]),
+    "gfship_particles_spread_forces": (_i, [_vp, C.POINTER(_i)]),
+    "gfship_sim_set_source_fields": (_i, [_vp, C.POINTER(_i)]),
+    "gfship_particles_time_spreading": (_i, [_vp, C.POINTER(_i), _pd]),
     "gfship_tree_create": (_i, [C.POINTER(_vp), _i, C.c_void_p, _vp, _i]),
     "gfship_tree_create_sides": (_i, [C.POINTER(_vp), _i, C.c_void_p, _vp, _pi, _i]),
     "gfship_tree_set_bc": (_i, [_vp, _i, _i]),
@@ -593,6 +600,15 @@ class Simulation:
         h = (C.c_int * 3)(*([v.h for v in D] + [-1] * (3 - len(D))))
         _check(lib().gfship_sim_set_viscosity_faces(self.ptr, c, h))
 
+    def set_source_fields(self, F):
+        """the velocity source of GfsSourceParticulate: dim Variables read as centred and MAC source of
+        U, V, W (None removes it)"""
+        if F is None:
+            _check(lib().gfship_sim_set_source_fields(self.ptr, None))
+            return
+        h = (C.c_int * 3)(*([v.h for v in F] + [-1] * (3 - len(F))))
+        _check(lib().gfship_sim_set_source_fields(self.ptr, h))
+
     def set_alpha_cell(self, alpha_cell):
         """alpha at the cell centres of every level: a Variable (None removes it)"""
         _check(lib().gfship_sim_set_alpha_cell(self.ptr, -1 if alpha_cell is None else alpha_cell.h))
@@ -787,6 +803,39 @@ class ParticleList:
         k = _check(lib().gfship_particles_download_particulate(
             self.ptr, vel.ctypes.data_as(_pd), mass.ctypes.data_as(_pd), force.ctypes.data_as(_pd)))
         return vel[:k].copy(), mass[:k].copy(), force[:k].copy()
+
+    # two-way coupling: GfsParticulateField and the event of GfsSourceParticulate
+    def particulate_field(self, v):
+        """v = the volume fraction of the particles of the list (GfsParticulateField)"""
+        _check(lib().gfship_particulate_field(self.ptr, v.h))
+
+    def forces_on_fluid(self):
+        """the stored force of every particle = its forces but buoyancy, times its volume"""
+        _check(lib().gfship_particles_forces_on_fluid(self.ptr))
+
+    def set_kernel(self, rkernel, function=None):
+        """rkernel (a length) and kernel (C text of x, y, z, t; a number; None = 0) of GfsSourceParticulate"""
+        _check(lib().gfship_particles_set_kernel(
+            self.ptr, float(rkernel), None if function is None else str(function).encode()))
+
+    def _fields3(self, F):
+        h = [f.h for f in F] + [-1] * (3 - len(F))
+        return (_i * 3)(*h)
+
+    def spread_forces(self, F):
+        """F[c] = minus the stored forces spread around the particles with the kernel"""
+        _check(lib().gfship_particles_spread_forces(self.ptr, self._fields3(F)))
+
+    def time_spreading(self, F):
+        """spread_forces, measured: (ms of pass 1, ms of pass 2, record slots per particle, particles per
+        chunk, bytes of the record arrays)"""
+        info = (C.c_double * 5)()
+        _check(lib().gfship_particles_time_spreading(self.ptr, self._fields3(F), info))
+        return float(info[0]), float(info[1]), int(info[2]), int(info[3]), int(info[4])
+
+    def source_particulate_event(self, F):
+        """forces_on_fluid, then spread_forces"""
+        _check(lib().gfship_source_particulate_event(self.ptr, self._fields3(F)))
 
     def destroy(self):
         if self.ptr:

@@ -503,6 +503,63 @@ int  gfship_particles_set_force_coefficient (gfship_particles * pl, int force, c
 int  gfship_particles_download_particulate (gfship_particles * pl, double * vel, double * mass,
 					    double * force);
 
+/* Two-way coupling: the particles act on the fluid (modules/particulatecommon.c:1927-2228).  Uniform
+   boxes without GfsBoundaryMpi sides, lists of particulates; GFSHIP_EUNSUPPORTED otherwise, and where
+   gfship_particles_set_forces refuses.  Every result is the reference's sum in the order of its particle
+   list (the order of gfship_particles_download), bit for bit, whatever the storage order of the particles
+   (gfship_particles_sort) and from run to run: contributions are sorted by (cell, list position) and
+   added serially per cell, never with atomics.
+   gfship_particulate_field: GfsParticulateField (particulate_field_event, :1934-1957).  v is reset on the
+   leaves, then v[cell] += volume/ftt_cell_volume (cell) for every particle that gfs_domain_locate finds a
+   cell for (L = 1).
+   gfship_particles_forces_on_fluid: for every particle force = 0, then force[c] = new_force[c]*volume +
+   force[c] over the forces of the list in order except GfsForceBuoy (compute_forces_onfluid, :753-765, in
+   source_particulate_event, :2199-2206).  Only the stored force changes (read it with
+   gfship_particles_download_particulate): no particle moves or leaves, the mass and Un, Vn, Wn stay.
+   gfship_particles_set_kernel: rkernel and kernel of GfsSourceParticulate (source_particulate_read,
+   :2271-2289): rkernel is an absolute length (cond_kernel, :2143; the `influencerad' of :2210 is never
+   used); function is a GfsFunction (spatial) of x, y, z, t -- C text, an expression or a { block },
+   compiled for the device with hipRTC like the force coefficients (GFSHIP_EINVAL with the compiler's
+   messages where it does not compile); a number is a constant and compiles nothing; NULL is the constant 0
+   of source_particulate_init (:2342-2350), which deposits nothing.
+   gfship_particles_spread_forces: F[c] (c < dim) are reset on the leaves, then for every particle in list
+   order the two pruned traversals of :2208-2222: a leaf is reached if it and its ancestors pass cond_kernel
+   (:2126-2156: |centre - pos| - (size/2) sqrt (dim) <= rkernel, or the particle inside the cell; no
+   periodic wrap), correction = sum K (q) cellvol / sum cellvol in traversal order with q =
+   distance_normalization (:2089-2099: (centre - pos)/rb for x and y, rb = pow (3 volume/(4 pi), 1./3.); z is
+   0 in 2-D and (0. - pos.z)/rb in 3-D, as written there), and where correction > 1.e-10
+   F[c][cell] -= force[c]/liq_rho/cellvol*K (q)/correction with liq_rho = 1./alpha_cell where
+   gfship_sim_set_alpha_cell is set and 1. otherwise (diffuse_force, :2158-2175).
+   gfship_source_particulate_event: source_particulate_event (:2177-2228), the two calls above in turn. */
+int  gfship_particulate_field (gfship_particles * pl, gfship_field v);
+int  gfship_particles_forces_on_fluid (gfship_particles * pl);
+int  gfship_particles_set_kernel (gfship_particles * pl, double rkernel, const char * function);
+int  gfship_source_particulate_event (gfship_particles * pl, const gfship_field F[3]);
+int  gfship_particles_spread_forces (gfship_particles * pl, const gfship_field F[3]);
+/* gfship_particles_spread_forces, measured (no reference counterpart): info[0], info[1] = the milliseconds
+   the device spent in pass 1 (the descent of every particle, the kernel function, volume and correction:
+   kernel_volume, :2108-2119) and in pass 2 (the sort of the records and the sums per cell: diffuse_force,
+   :2158-2175), summed over the chunks from events on the domain's stream; info[2] = the record slots of a
+   particle, info[3] = the particles of a chunk, info[4] = the bytes of the record arrays (56 per slot, at
+   most 2^22 slots).  A kernel whose slots per particle exceed a chunk is refused (GFSHIP_EUNSUPPORTED, by
+   gfship_particles_set_kernel already), and so is a box of 2^32 cells or more. */
+int  gfship_particles_time_spreading (gfship_particles * pl, const gfship_field F[3], double info[5]);
+/* GfsSourceParticulate in the time step: U, V, W (c < dim) get the velocity source whose centred value is
+   F[c] of the cell (source_particulate_centered_value, :2067-2079) and whose MAC value is F[c] interpolated
+   on the positive face of component c, gfs_face_interpolated_value_generic (source_particulate_value,
+   :2029-2065; beyond a side of the box it reads the ghost cells of F as the caller left them: the
+   reference's event applies no boundary condition to them).  The MAC value enters gfs_variable_mac_source
+   (src/source.c:38-59) -- the face values of the advection (src/advection.c:82,124), hence the predicted
+   face velocities, and the acceleration scale of gfs_domain_cfl (src/domain.c:2882-2883) -- and the centred
+   value add_sources (src/source.c:66-79).  v->sources is visited last-read first (gts_container_add puts a
+   source at the head; a GfsSourceParticulate stands below its particle list, after the other sources of a
+   usual file): sum = 0. + F-term + GfsSourceDiffusion + GfsSource.  The fields are read at every use: the
+   event may rewrite them between steps.  With source fields the time step takes the general advection path
+   (face-value arrays), not the fused periodic one; gfship_variable_mac_source then gives the sum without the
+   constant of gfship_sim_set_source.  NULL removes the source.  GFSHIP_EUNSUPPORTED on a box with
+   GfsBoundaryMpi sides. */
+int  gfship_sim_set_source_fields (gfship_sim * sim, const gfship_field F[3]);
+
 /* ---- one box per GPU: GfsBoundaryMpi sides (src/mpi_boundary.c:78-246) ----------------------- */
 
 /* Either the in-library RCCL transport below (gfship_domain_comm_init: what bench.py uses), or two
