@@ -9,8 +9,13 @@
 // interpolate = gfs_interpolate: corner values are inverse-distance weighted means of the cells
 // sharing the corner (src/fluid.c:2983-3101), then the reference's 8-corner polynomial
 // (:2640-2683).  All in the reference's operand order: cell indices and positions are
-// bit-identical to the CPU algorithm.  The reference has no test for this path (parity pinned
-// on the oracle and on analytic properties only).
+// bit-identical to the CPU algorithm.  The reference has no test for this path.  It is pinned on a
+// restatement of the reference on an explicit cell graph (tests/sampler_reference.py: the box tree
+// and the flattened boundary tree of every side, neighbours found as ftt_cell_neighbor finds them):
+// sample_kernel and particle_list_event_kernel against it in tests/test_gpu_sampler_reference.py,
+// the oracle against it in tests/test_sampler_reference_cpu.py, all by array_equal.  On a uniform
+// box the walk of do_path reaches exactly the cells of the 2^DIM block that have at most one
+// coordinate in the ghost layer: `out <= 1' below is that statement.
 //
 // Sort by cell: the gather of a particle reads the 27 cells around it for three components and
 // two RK stages, so particles of one wavefront should sit in neighbouring cells.  Every
@@ -1378,9 +1383,10 @@ int gfship_particles_count (gfship_particles * pl)
   return (int) c;
 }
 
-int gfship_particles_download (gfship_particles * pl, double * pos, unsigned * id)
+// the survivors in creation order (the reference's list order), whatever the storage order: their
+// positions (src = pl->pos) or old positions (src = pl->old), and their ids where id is given
+static int particles_download (gfship_particles * pl, double * const src[3], double * pos, unsigned * id)
 {
-  GFSHIP_CHECK (pl && pos && id, GFSHIP_EINVAL, "null argument");
   if (pl->n == 0) return 0;
   gfship_domain * dom = pl->dom;
   GFSHIP_HIP (hipStreamSynchronize (dom->stream));
@@ -1389,12 +1395,11 @@ int gfship_particles_download (gfship_particles * pl, double * pos, unsigned * i
   std::vector<unsigned> ids (m), orig (m), where (m);
   std::vector<unsigned char> al (m);
   GFSHIP_HIP (hipMemcpy (orig.data (), pl->orig, m*sizeof (unsigned), hipMemcpyDeviceToHost));
-  GFSHIP_HIP (hipMemcpy (x.data (), pl->pos[0], m*sizeof (double), hipMemcpyDeviceToHost));
-  GFSHIP_HIP (hipMemcpy (y.data (), pl->pos[1], m*sizeof (double), hipMemcpyDeviceToHost));
-  GFSHIP_HIP (hipMemcpy (z.data (), pl->pos[2], m*sizeof (double), hipMemcpyDeviceToHost));
+  GFSHIP_HIP (hipMemcpy (x.data (), src[0], m*sizeof (double), hipMemcpyDeviceToHost));
+  GFSHIP_HIP (hipMemcpy (y.data (), src[1], m*sizeof (double), hipMemcpyDeviceToHost));
+  GFSHIP_HIP (hipMemcpy (z.data (), src[2], m*sizeof (double), hipMemcpyDeviceToHost));
   GFSHIP_HIP (hipMemcpy (ids.data (), pl->id, m*sizeof (unsigned), hipMemcpyDeviceToHost));
   GFSHIP_HIP (hipMemcpy (al.data (), pl->alive, m, hipMemcpyDeviceToHost));
-  /* survivors in creation order (the reference's list order), whatever the storage order */
   for (size_t q = 0; q < m; q++)
     where[orig[q]] = (unsigned) q;
   int k = 0;
@@ -1403,11 +1408,23 @@ int gfship_particles_download (gfship_particles * pl, double * pos, unsigned * i
     if (al[q] == 1) {
       pos[3*(size_t) k] = x[q]; pos[3*(size_t) k + 1] = y[q];
       pos[3*(size_t) k + 2] = dom->dim == 3 ? z[q] : 0.;
-      id[k] = ids[q];
+      if (id) id[k] = ids[q];
       k++;
     }
   }
   return k;
+}
+
+int gfship_particles_download (gfship_particles * pl, double * pos, unsigned * id)
+{
+  GFSHIP_CHECK (pl && pos && id, GFSHIP_EINVAL, "null argument");
+  return particles_download (pl, pl->pos, pos, id);
+}
+
+int gfship_particles_download_old (gfship_particles * pl, double * old)
+{
+  GFSHIP_CHECK (pl && old, GFSHIP_EINVAL, "null argument");
+  return particles_download (pl, pl->old, old, nullptr);
 }
 
 } // extern "C"

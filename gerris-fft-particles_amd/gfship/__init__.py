@@ -151,6 +151,7 @@ SIGNATURES = {
     "gfship_particles_sort": (_i, [_vp]),
     "gfship_particles_set_sort_interval": (_i, [_vp, _i]),
     "gfship_particles_download": (_i, [_vp, _pd, C.POINTER(C.c_uint)]),
+    "gfship_particles_download_old": (_i, [_vp, _pd]),
     "gfship_energy_spectra_bins": (_i, [_vp]),
     "gfship_energy_spectra": (_i, [_vp, _i, C.POINTER(_i), _pd, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)]),
@@ -776,6 +777,13 @@ class ParticleList:
         k = _check(lib().gfship_particles_download(self.ptr, pos.ctypes.data_as(_pd),
                                                    ids.ctypes.data_as(C.POINTER(C.c_uint))))
         return pos[:k].copy(), ids[:k].copy()
+
+    def download_old(self):
+        """pos_old of the particles on the list, in the order of download()"""
+        m = max(_check(lib().gfship_particles_slots(self.ptr)), 1)
+        old = np.empty((m, 3))
+        k = _check(lib().gfship_particles_download_old(self.ptr, old.ctypes.data_as(_pd)))
+        return old[:k].copy()
 
     # GfsParticulate: velocity, mass, volume and the list's forces (FORCE_* in application order)
     def set_particulate(self, vel, mass, volume):

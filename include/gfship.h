@@ -343,7 +343,12 @@ int  gfship_sim_download_un (gfship_sim * sim, int c, double * host);
 
 /* GfsOutputLocation's sampling (src/output.c:1182-1199): gfs_domain_locate + gfs_interpolate
    (src/fluid.c:2983-3101) of variable v at np points (pos = 3*np doubles); inside[q] = 0 where
-   the point is outside the domain (out[q] is then 0) */
+   the point is outside the domain (out[q] is then 0).
+   GFS_NODATA (DBL_MAX) is not supported: nothing in this library produces it (no solid boundaries, no
+   masked variables), so neither `return GFS_NODATA' of gfs_interpolate (:2704-2705) nor the fall-back
+   to the cell's value in gfs_cell_corner_value (:3096-3097) exists here; a field that holds DBL_MAX is
+   sampled as the number it is (tests/test_gpu_sampler_reference.py pins that).  The same holds for the
+   particle events, which share the sampler. */
 int  gfship_field_interpolate (gfship_domain * dom, gfship_field v, int np, const double * pos,
 			       double * out, unsigned char * inside);
 
@@ -463,6 +468,8 @@ int  gfship_particles_slots (gfship_particles * pl);
 int  gfship_particles_count (gfship_particles * pl);
 /* positions and ids of the particles still on the list, in list order; returns their number */
 int  gfship_particles_download (gfship_particles * pl, double * pos, unsigned * id);
+/* pos_old (GfsParticle, src/particle.h) of the same particles in the same order; returns their number */
+int  gfship_particles_download_old (gfship_particles * pl, double * old);
 
 /* GfsParticulate with forces (modules/particulatecommon.h:35-61, particulatecommon.c:91-842): the
    particles of the list get a velocity (3*np), a mass and a volume (np each), and the list a set of

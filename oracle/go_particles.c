@@ -5,8 +5,10 @@
  * (gfs_domain_locate, gfs_domain_advect_point), src/ftt.c:1535-1574 (ftt_cell_locate),
  * src/fluid.c:2596-2710,2938-3101 (corner interpolation) and
  * modules/particulatecommon.c:955-1015,3058-3395 (list event, ray march to the exit face,
- * periodic wrap).  The reference holds no test or golden data for any of this: parity of this
- * file is UNPINNED by the reference; it is pinned only by analytic properties (tests/). */
+ * periodic wrap).  The reference holds no test or golden data for any of this; locate, interpolate
+ * and the tracer event of this file are pinned on the restatement of the reference on an explicit
+ * cell graph, tests/sampler_reference.py (tests/test_sampler_reference_cpu.py, array_equal), the
+ * rest on analytic properties (tests/). */
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
@@ -290,6 +292,7 @@ void go_particles_append (GoParticles * pl, int n, const double * rec)
 
 int go_particles_count (const GoParticles * pl) { return pl->n; }
 double * go_particles_pos (GoParticles * pl) { return pl->pos; }
+double * go_particles_pos_old (GoParticles * pl) { return pl->pos_old; }
 unsigned * go_particles_id (GoParticles * pl) { return pl->id; }
 
 static void move_particle (GoParticles * pl, int m, int q)

@@ -39,6 +39,7 @@ int    go_particles_outbox (GoParticles * pl, int d, double ** rec);
 void   go_particles_clear_outbox (GoParticles * pl);
 void   go_particles_append (GoParticles * pl, int n, const double * rec);
 double * go_particles_pos (GoParticles * pl);
+double * go_particles_pos_old (GoParticles * pl);
 unsigned * go_particles_id (GoParticles * pl);
 void   go_particle_list_event (GoSim * s, GoParticles * pl);
 void   go_particles_set_particulate (GoParticles * pl, const double * vel, const double * mass,

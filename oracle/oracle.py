@@ -483,6 +483,7 @@ class Particles:
                 "go_particles_destroy": (None, [vp]),
                 "go_particles_count": (i, [vp]),
                 "go_particles_pos": (pd, [vp]),
+                "go_particles_pos_old": (pd, [vp]),
                 "go_particles_id": (pu, [vp]),
                 "go_particle_list_event": (None, [vp, vp]),
                 "go_locate": (i, [vp, pd, C.POINTER(C.c_int)]),
@@ -569,6 +570,10 @@ class Particles:
         pos = np.ctypeslib.as_array(lib().go_particles_pos(self.ptr), shape=(max(n, 1), 3))[:n].copy()
         ids = np.ctypeslib.as_array(lib().go_particles_id(self.ptr), shape=(max(n, 1),))[:n].copy()
         return pos, ids
+
+    def pos_old_ptr(self):
+        """pos_old of the particles on the list (3 doubles each), in list order"""
+        return lib().go_particles_pos_old(self.ptr)
 
     def locate(self, p):
         p = np.ascontiguousarray(p, dtype=np.float64)

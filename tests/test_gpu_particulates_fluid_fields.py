@@ -13,7 +13,8 @@ The oracle's particle code has fluid_rho = 1. and one viscosity, so the path is 
   (2) for general values, against a restatement of the five forces and of gfs_particulate_event in plain
       Python floats, one particle at a time, in the reference's operand order (:273-336, 349-427, 439-524,
       534-588, 631-653, 828-837), fed with the library's own sampler (Domain.interpolate, pinned on the
-      oracle by the tracer tests) and the downloaded fields.  The build has no contraction, division and
+      cell-graph restatement of the reference by tests/test_gpu_sampler_reference.py) and the
+      downloaded fields.  The build has no contraction, division and
       square root are correctly rounded on both sides: force, vel and mass must be equal bit for bit;
   (3) the refusals.
 """

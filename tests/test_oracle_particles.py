@@ -1,6 +1,9 @@
-"""The reference holds no test, example or golden file for its particle module:
-parity of the tracer path is UNPINNED by the reference.  The oracle's restatement of
-locate / interpolate / RK2 / periodic wrap is checked here on analytic properties."""
+"""The reference holds no test, example or golden file for its particle module.
+The oracle's restatement of locate / interpolate / RK2 / periodic wrap is checked here on analytic
+properties; what pins it cell by cell and bit by bit, box sides, edges and corners included, is the
+restatement of the reference on an explicit cell graph (tests/sampler_reference.py), against which
+tests/test_sampler_reference_cpu.py compares the oracle and tests/test_gpu_sampler_reference.py the
+device."""
 import numpy as np
 import pytest
 
