@@ -367,7 +367,10 @@ int launch_advect3_fused (gfship_domain * dom, double * const v[3], double * con
 int launch_advect_fused (gfship_domain * dom, bool velocity, const double * v, double * out,
 			 double * const un[3], const double * gm, const double * gc, double dt,
 			 int gradient, double visc, double gsrc = 0.);
-
+// out = v + fluxes + (1 - beta)/beta*diffusion_rhs (v) with the weight w of the leaf faces: the right-hand side
+// of the implicit diffusion of a tracer with coefficient D (the MAC source of its face values)
+int launch_advect_diffuse_fused (gfship_domain * dom, const double * v, double * out, double * const un[3],
+				 double dt, int gradient, double D, double w, double beta);
 
 // relax_skew.hip
 bool skew_supported (const gfship_domain * dom, int level);

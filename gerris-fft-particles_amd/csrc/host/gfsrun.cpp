@@ -10,10 +10,11 @@
 // checks of test/*/*.sh read them unchanged.  Supported: one GfsBox (periodic through self
 // edges `1 1 right`), uniform `Refine <int>`, Boundary { BcDirichlet | BcNeumann }, Time,
 // ProjectionParams, ApproxProjectionParams, AdvectionParams, Init, SourceDiffusion / SourceViscosity (a
-// constant or a function of x, y, z, t on U, V, W), VariableTracer, EventStop, EventScript, GModule (ignored: the device
+// constant or a function of x, y, z, t on U, V, W; SourceDiffusion with a constant on a declared tracer),
+// VariableTracer { gradient = .. scheme = godunov | none }, EventStop, EventScript, GModule (ignored: the device
 // solver replaces hypre/agmg), OutputTime, OutputProjectionStats, OutputDiffusionStats,
 // OutputScalarNorm, OutputScalarSum, OutputScalarStats, OutputErrorNorm, OutputLocation,
-// GfsAdvection with a VariableStreamFunction, OutputSimulation (text format), OutputEnergySpectra (`GModule fft`), InitSpectra (`GModule
+// GfsAdvection with a VariableStreamFunction (or without one when no tracer is advected), OutputSimulation (text format), OutputEnergySpectra (`GModule fft`), InitSpectra (`GModule
 // turbulence`), GfsParticleList of GfsParticle / GfsParticulate objects with
 // GfsForce{Inertial,AddedMass,Lift,Drag,Buoy} (`GModule particulates`; --particles FILE writes the
 // lists at the end of the run the way the reference prints them), GfsParticulateField and
@@ -196,6 +197,11 @@ struct Run {
   std::map<std::string, std::string> diff_set[3];
   std::vector<std::string> tracers;
   std::vector<int> tracer_gradient;              // 0 gfs_center_gradient, 1 van Leer (default)
+  std::vector<int> tracer_scheme;                // GfsVariableTracer { scheme = godunov | none }
+  // GfsSourceDiffusion on a tracer: the constant, the line it stands on (0: none), its GfsMultilevelParams
+  std::vector<double> tracer_D;
+  std::vector<int> tracer_D_line;
+  std::vector<std::map<std::string, std::string>> tracer_diff_set;
   Function * stream_function = nullptr;          // GfsVariableStreamFunction (2-D, GfsAdvection)
   std::vector<std::pair<std::string, Function *>> init;   // Init {} { var = f }
   double source[3] = { 0., 0., 0. };    // GfsSource intensities on U, V, W
@@ -744,6 +750,26 @@ void parse_object (Run & R, Reader & r)
     if (r.peek (false) == '{') read_multilevel (r, par);
     for (const std::string & v : comps) {
       int c = v == "U" ? 0 : v == "V" ? 1 : (v == "W" && R.dim == 3) ? 2 : -1;
+      const auto tr = std::find (R.tracers.begin (), R.tracers.end (), v);
+      if (c < 0 && cls == "SourceDiffusion" && tr != R.tracers.end ()) {
+	// GfsSourceDiffusion on a declared tracer (gfs_tracer_advection_diffusion, src/timestep.c:1039-1048):
+	// a constant coefficient
+	const size_t k = tr - R.tracers.begin ();
+	if (R.tracer_D_line[k]) {
+	  fprintf (stderr, "gfship: line %d: only one diffusion source can be specified for a given variable "
+		   "(`%s' has one on line %d)\n", fline, v.c_str (), R.tracer_D_line[k]);     /* src/source.c:1047 */
+	  exit (1);
+	}
+	if (!constant) {
+	  fprintf (stderr, "gfship: line %d: the diffusion coefficient of a tracer must be a constant (got `%s' "
+		   "for `%s')\n", fline, t.text.c_str (), v.c_str ());
+	  exit (1);
+	}
+	R.tracer_D[k] = atof (t.text.c_str ());
+	R.tracer_D_line[k] = fline;
+	R.tracer_diff_set[k] = par;
+	continue;
+      }
       if (c < 0) r.fail ("diffusion is supported on the velocity components only (got `" + v + "')");
       R.visc[c] = constant ? atof (t.text.c_str ()) : 0.;
       R.visc_fn[c] = fn;
@@ -786,16 +812,22 @@ void parse_object (Run & R, Reader & r)
   }
   else if (cls == "VariableTracer") {
     std::string name = r.word (false);
-    int gradient = 1;
+    int gradient = 1, scheme = GFSHIP_SCHEME_GODUNOV;
     if (r.peek (false) == '{') {
       auto m = r.assignments ();
       for (auto & kv : m)
 	if (kv.first == "gradient" && gradient_kind (kv.second) >= 0) gradient = gradient_kind (kv.second);
+	else if (kv.first == "scheme" && (kv.second == "godunov" || kv.second == "none"))
+	  scheme = kv.second == "none" ? GFSHIP_SCHEME_NONE : GFSHIP_SCHEME_GODUNOV;    /* src/advection.c:1009-1018 */
 	else
 	  r.fail ("unsupported GfsVariableTracer parameter " + kv.first + " = " + kv.second);
     }
     R.tracers.push_back (name);
     R.tracer_gradient.push_back (gradient);
+    R.tracer_scheme.push_back (scheme);
+    R.tracer_D.push_back (0.);
+    R.tracer_D_line.push_back (0);
+    R.tracer_diff_set.emplace_back ();
     R.get_or_add_variable (name);
   }
   else if (cls == "VariableStreamFunction") {
@@ -1215,6 +1247,12 @@ void parse_object (Run & R, Reader & r)
 	  if (R.has_viscosity (c)) {
 	    fprintf (fp, "%s diffusion\n", names[c]);
 	    stats_write (gfship_sim_diffusion_params (R.sim, c), fp);
+	  }
+	// ... then the tracers, in the order of domain->variables, once their solver has run (:551)
+	for (size_t k = 0; k < R.tracers.size (); k++)
+	  if (R.tracer_D[k] != 0. && gfship_sim_tracer_diffusion_params (R.sim, (int) k)->niter > 0) {
+	    fprintf (fp, "%s diffusion\n", R.tracers[k].c_str ());
+	    stats_write (gfship_sim_tracer_diffusion_params (R.sim, (int) k), fp);
 	  }
       }
       else {
@@ -2019,6 +2057,8 @@ int run_tree (Run & R)
   if (R.tracers.size () > 2) return refuse ("more than two tracers");
   for (int g : R.tracer_gradient)
     if (g > 1) return refuse ("this gradient of a GfsVariableTracer");
+  for (int sc : R.tracer_scheme)
+    if (sc != GFSHIP_SCHEME_GODUNOV) return refuse ("GfsVariableTracer { scheme = none }");
   if (!R.plists.empty ()) return refuse ("a particle list");
   if (!R.init_spectra.empty ()) return refuse ("GfsInitSpectra");
   if (!R.device_vars.empty ()) return refuse ("a turbulent-viscosity variable");
@@ -2385,6 +2425,13 @@ int run (Run & R)
   add_derived (R);
   R.functions.resolve (R.var_names ());
   resolve_refine (R);
+  if (R.tree_mode)
+    for (size_t k = 0; k < R.tracers.size (); k++)
+      if (R.tracer_D_line[k]) {
+	fprintf (stderr, "gfship: line %d: GfsSourceDiffusion on a tracer (`%s') is not supported on a refined tree\n",
+		 R.tracer_D_line[k], R.tracers[k].c_str ());
+	return 1;
+      }
   if (R.alpha) {
     if (R.tree_mode || R.sim_class != "Simulation") {
       fprintf (stderr, "gfship: line %d: GfsPhysicalParams { alpha } is supported for a GfsSimulation on a uniform box\n", R.alpha_line);
@@ -2460,6 +2507,11 @@ int run (Run & R)
     CHECK (k);
     R.vars[R.var_index (t)].dev = gfship_sim_variable (R.sim, GFSHIP_VAR_TRACER, k);
     CHECK (gfship_sim_set_tracer_gradient (R.sim, k, R.tracer_gradient[(size_t) k]));
+    CHECK (gfship_sim_set_tracer_scheme (R.sim, k, R.tracer_scheme[(size_t) k]));
+    if (R.tracer_D[(size_t) k] != 0.) {
+      CHECK (gfship_sim_set_tracer_diffusion (R.sim, k, R.tracer_D[(size_t) k]));
+      apply_multilevel (gfship_sim_tracer_diffusion_params (R.sim, k), R.tracer_diff_set[(size_t) k]);
+    }
   }
   for (const std::string & dv : R.device_vars) {
     gfship_field f = gfship_field_alloc (R.dom, -1);
@@ -2603,11 +2655,19 @@ int run (Run & R)
     // advection_run, src/simulation.c:2061-2116, with the velocity of a GfsVariableStreamFunction
     // (variable_stream_function_event, src/variable.c:1041-1086: psi at the four corners of every
     // leaf -> MAC velocities, centred velocities = means of the two faces, BC)
-    if (!R.stream_function) {
+    // Without one the velocity stays the zeros of a fresh simulation; that is accepted where no tracer
+    // reads it (every GfsVariableTracer has scheme = none: test/diffusion).  advection_run ignores the
+    // default scheme (:2078), so min_cfl (:1537-1554) is then G_MAXDOUBLE and the step is G_MAXINT, cut by
+    // dtmax and the events.
+    bool advected = false;
+    for (int sc : R.tracer_scheme) advected = advected || sc == GFSHIP_SCHEME_GODUNOV;
+    if (!R.stream_function && advected) {
       fprintf (stderr, "gfship: GfsAdvection needs a GfsVariableStreamFunction (prescribed velocity)\n");
       return 1;
     }
-    {
+    if (!advected)
+      gfship_sim_advection_params (R.sim)->cfl = DBL_MAX;
+    if (R.stream_function) {
       const int n = R.n ();
       std::vector<double> un[2], uc[2];
       for (int c = 0; c < 2; c++) { un[c].assign (R.total (), 0.); uc[c].assign (R.total (), 0.); }

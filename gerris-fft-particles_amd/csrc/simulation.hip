@@ -15,6 +15,13 @@ struct gfship_sim {
   gfship_field p = -1, pmac = -1, u[3] = {-1, -1, -1}, g[3] = {-1, -1, -1}, gmac[3] = {-1, -1, -1};
   std::vector<gfship_field> tracers;
   std::vector<int> tracer_gradient;    // GfsVariableTracer { gradient = }: 0 centred, 1 van Leer
+  std::vector<int> tracer_scheme;      // GfsVariableTracer { scheme = }: GFSHIP_SCHEME_GODUNOV | _NONE
+  // GfsSourceDiffusion on a tracer (constant coefficient, 0.: none) and the GfsMultilevelParams of its solver
+  // (a deque: the addresses given out by gfship_sim_tracer_diffusion_params hold when a tracer is added)
+  std::vector<double> tracer_D;
+  std::deque<gfship_multilevel_params> tracer_diffusion_params;
+  bool tracer_diffusion_fused = true;  // gfship_sim_tracer_diffusion_path
+  unsigned long long tracer_diffusion_counts[2] = { 0, 0 };   // starts of the solve by the fused / composed path
   gfship_field un[3] = {-1, -1, -1};   // face normal velocities (see timestep_kernels.hip)
   gfship_field fv[6] = {-1, -1, -1, -1, -1, -1};
   gfship_field dia = -1, div = -1, res = -1, tmp = -1; // temporaries of mac_projection
@@ -308,15 +315,17 @@ int correct_centered_velocities (gfship_sim * s, const gfship_field g[3], double
 }
 
 // face_values_set, src/timestep.c:644-654
+// tracer_D: the coefficient of the GfsSourceDiffusion of a tracer v (no alpha factor: source_diffusion_value
+// takes alpha for velocity components only, src/source.c:1141-1143)
 int face_values_set (gfship_sim * s, gfship_field v, double dt, int use_centered, int gradient,
-		     int cmask = 7)
+		     int cmask = 7, double tracer_D = 0.)
 {
   double * u[3], * un[3], * fv[6];
   ptrs3 (s, s->u, u);
   ptrs3 (s, s->un, un);
   ptrs6 (s, fv);
   /* v->sources: the implicit diffusion of a velocity component acts as MAC source */
-  double visc = 0., gsrc = 0.;
+  double visc = tracer_D, gsrc = 0.;
   const double * msrc = nullptr;
   for (int c = 0; c < s->dom->dim; c++)
     if (v == s->u[c]) {
@@ -330,9 +339,10 @@ int face_values_set (gfship_sim * s, gfship_field v, double dt, int use_centered
   return GFSHIP_OK;
 }
 
-// variable_sources, src/timestep.c:872-921 (Godunov; the update goes into sv)
+// variable_sources, src/timestep.c:872-921 (Godunov; the update goes into sv).  tracer_D: the coefficient
+// of the GfsSourceDiffusion of a tracer v, the MAC source of its face values
 int variable_sources (gfship_sim * s, gfship_field v, gfship_field sv, int gradient, bool velocity,
-		      double dt, const gfship_field gmac[3], const gfship_field g[3])
+		      double dt, const gfship_field gmac[3], const gfship_field g[3], double tracer_D = 0.)
 {
   double * un[3], * fv[6];
   ptrs3 (s, s->un, un);
@@ -345,7 +355,7 @@ int variable_sources (gfship_sim * s, gfship_field v, gfship_field sv, int gradi
     const int L = dom->depth;
     const double * gm = velocity ? leaf (s, gmac[c]) : nullptr;
     const double * gc = (velocity && g) ? leaf (s, g[c]) : nullptr;
-    double visc = 0., gsrc = 0.;
+    double visc = tracer_D, gsrc = 0.;
     for (int q = 0; q < dom->dim; q++)
       if (v == s->u[q]) {
 	visc = s->visc[q];
@@ -366,7 +376,7 @@ int variable_sources (gfship_sim * s, gfship_field v, gfship_field sv, int gradi
     return GFSHIP_OK;
   }
   s->dom->kc[GFSHIP_KC_ADVECT_GENERAL]++;
-  TRY (face_values_set (s, v, dt, 0, gradient));
+  TRY (face_values_set (s, v, dt, 0, gradient, 7, tracer_D));
   const double * gm = velocity ? leaf (s, gmac[c]) : nullptr;
   const double * gc = (velocity && g) ? leaf (s, g[c]) : nullptr;
   s->dom->fields[sv].zero[s->dom->depth] = false;
@@ -694,6 +704,11 @@ int gfship_sim_add_tracer (gfship_sim * s)
   if (t < 0) return t;
   s->tracers.push_back (t);
   s->tracer_gradient.push_back (1);      /* gfs_center_van_leer_gradient, src/variable.c:429 */
+  s->tracer_scheme.push_back (GFSHIP_SCHEME_GODUNOV);
+  s->tracer_D.push_back (0.);
+  s->tracer_diffusion_params.emplace_back ();
+  gfship_multilevel_params_init (&s->tracer_diffusion_params.back (), s->dom->dim);
+  s->tracer_diffusion_params.back ().tolerance = 1e-6;      /* diffusion_init, src/source.c:966-974 */
   return (int) s->tracers.size () - 1;
 }
 
@@ -867,11 +882,92 @@ int gfship_tracer_advection (gfship_sim * s, gfship_field t, double dt)
   if (!get_field (s->dom, t)) return GFSHIP_EINVAL;
   /* tracers: van Leer gradient unless the file says otherwise + gfs_face_advection_flux
      (src/variable.c:427-431) */
-  int gradient = 1;
+  int gradient = 1, k = -1;
   for (size_t q = 0; q < s->tracers.size (); q++)
-    if (s->tracers[q] == t) gradient = s->tracer_gradient[q];
-  TRY (variable_sources (s, t, t, gradient, false, dt, nullptr, nullptr));
-  TRY (bc_leaf (s, t));
+    if (s->tracers[q] == t) { gradient = s->tracer_gradient[q]; k = (int) q; }
+  /* GfsVariableTracer { scheme = none }: the Godunov block of variable_sources is skipped
+     (src/timestep.c:878-899) */
+  const bool godunov = k < 0 || s->tracer_scheme[k] == GFSHIP_SCHEME_GODUNOV;
+  const double D = k < 0 ? 0. : s->tracer_D[k];
+  if (D == 0.) {
+    if (godunov)
+      TRY (variable_sources (s, t, t, gradient, false, dt, nullptr, nullptr));
+    TRY (bc_leaf (s, t));
+    return GFSHIP_OK;
+  }
+  /* source_diffusion (t): rhs = copy of t on the leaves, sources into rhs with D as the MAC source of the
+     face values, then variable_diffusion with alpha = NULL (src/timestep.c:1039-1048; the conditions of t
+     are those the solve applies, there is no gfs_domain_bc in this branch) */
+  gfship_domain * dom = s->dom;
+  gfship_multilevel_params * par = &s->tracer_diffusion_params[k];
+  if (s->drhs < 0)
+    s->drhs = gfship_field_alloc (dom, -1);
+  if (s->drhs < 0) return s->drhs;
+  if (s->rhoc < 0)
+    s->rhoc = gfship_field_alloc (dom, -1);
+  if (s->rhoc < 0) return s->rhoc;
+  /* gfs_diffusion_coefficients first: nothing below writes what it reads, and the fused pass takes the
+     weight of the leaf faces from it */
+  TRY (gfship_diffusion_coefficients (dom, D, dt, s->rhoc, par->beta));
+  if (s->tracer_diffusion_fused && godunov && gradient <= 1 && godunov_fused_supported (dom)) {
+    /* leaf copy, variable_sources and gfs_diffusion_rhs in one pass over t */
+    double * un[3];
+    ptrs3 (s, s->un, un);
+    dom->fields[s->drhs].zero[dom->depth] = false;
+    TRY (launch_advect_diffuse_fused (dom, leaf (s, t), leaf (s, s->drhs), un, dt, gradient, D,
+				      dom->diff_w[dom->depth], par->beta));
+    s->tracer_diffusion_counts[0]++;
+  }
+  else {
+    dom->fields[s->drhs].zero[dom->depth] = false;
+    GFSHIP_HIP (hipMemcpyAsync (leaf (s, s->drhs), leaf (s, t), dom->lay[dom->depth].total*sizeof (double),
+				hipMemcpyDeviceToDevice, dom->stream));
+    if (godunov)
+      TRY (variable_sources (s, t, s->drhs, gradient, false, dt, nullptr, nullptr, D));
+    TRY (gfship_diffusion_rhs (dom, t, s->drhs, s->rhoc, par->beta));
+    s->tracer_diffusion_counts[1]++;
+  }
+  TRY (gfship_diffusion (dom, par, t, s->drhs, s->rhoc));
+  return GFSHIP_OK;
+}
+
+int gfship_sim_set_tracer_diffusion (gfship_sim * s, int t, double D)
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
+  GFSHIP_CHECK (t >= 0 && (size_t) t < s->tracers.size (), GFSHIP_EINVAL, "no tracer %d", t);
+  GFSHIP_CHECK (D >= 0., GFSHIP_EINVAL, "the diffusion coefficient must be positive");
+  GFSHIP_CHECK (D == 0. || !s->dom->has_external, GFSHIP_EUNSUPPORTED,
+		"GfsSourceDiffusion on a tracer on a box with GfsBoundaryMpi sides is not supported");
+  s->tracer_D[t] = D;
+  return GFSHIP_OK;
+}
+
+gfship_multilevel_params * gfship_sim_tracer_diffusion_params (gfship_sim * s, int t)
+{ return (s && t >= 0 && (size_t) t < s->tracers.size ()) ? &s->tracer_diffusion_params[t] : nullptr; }
+
+int gfship_sim_set_tracer_scheme (gfship_sim * s, int t, int scheme)
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
+  GFSHIP_CHECK (t >= 0 && (size_t) t < s->tracers.size (), GFSHIP_EINVAL, "no tracer %d", t);
+  GFSHIP_CHECK (scheme == GFSHIP_SCHEME_GODUNOV || scheme == GFSHIP_SCHEME_NONE, GFSHIP_EINVAL,
+		"scheme: GFSHIP_SCHEME_GODUNOV or GFSHIP_SCHEME_NONE");
+  s->tracer_scheme[t] = scheme;
+  return GFSHIP_OK;
+}
+
+int gfship_sim_tracer_diffusion_path (gfship_sim * s, int fused)
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
+  GFSHIP_CHECK (fused == 0 || fused == 1, GFSHIP_EINVAL, "path: 1 the fused pass where it applies, 0 composed");
+  s->tracer_diffusion_fused = fused != 0;
+  return GFSHIP_OK;
+}
+
+int gfship_sim_tracer_diffusion_counts (gfship_sim * s, unsigned long long counts[2])
+{
+  GFSHIP_CHECK (s && counts, GFSHIP_EINVAL, "null argument");
+  counts[0] = s->tracer_diffusion_counts[0];
+  counts[1] = s->tracer_diffusion_counts[1];
   return GFSHIP_OK;
 }
 

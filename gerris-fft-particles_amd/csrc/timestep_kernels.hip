@@ -1314,6 +1314,113 @@ advect_tiled_kernel (Layout L, const double * __restrict__ v, double * __restric
   out[c] = val;
 }
 
+// The start of the implicit solve of a tracer with a GfsSourceDiffusion in one pass
+// (gfs_tracer_advection_diffusion, src/timestep.c:1039-1046): copy_v_rhs, variable_sources (t -> rhs) with
+// source_diffusion_value as the MAC source of the face values, and gfs_diffusion_rhs
+// (diffusion_rhs, src/poisson.c:1392-1451) with the weight w = beta*dt*D of the leaf faces and rhoc = 1.:
+//   rhs = t + fluxes + pbeta*f/(h*h*1.),  f = flux_sum of t, pbeta = (1 - beta)/beta.
+// The body up to the update is advect_tiled_kernel<false, VL, true> with gsrc = 0. and no pressure gradient,
+// kept as a kernel of its own so that the instantiations of that kernel stay what they are; the last
+// statement is diffusion_rhs_kernel<3> on the value the update would have stored: same operations in the
+// same order as the three passes, same bits.
+template <bool VL>
+__global__ void __launch_bounds__(GN)
+advect_diffuse_tiled_kernel (Layout L, const double * __restrict__ v, double * __restrict__ out, CPtr3 un,
+			     double dt, double visc, double w, double pbeta)
+{
+  __shared__ double fl[3][GN], fr[3][GN];
+  __shared__ double hm[3][GX*GZ], hp[3][GX*GZ];   // l of the cell before / r of the cell after the tile
+  const TileIdx T;
+  const int n = L.n;
+  const double rn = (double) n;
+  const int c = (int) L.idx (T.i, T.j, T.k);
+  const int off[3] = { 1, (int) L.sy, (int) L.sz };
+  CPtr3 none = { { nullptr, nullptr, nullptr } };
+  {
+    FacePair f = face_values_dir<3, 0, false, VL, true> (L, v, none, un, c, dt, visc, 0.);
+    fl[0][T.own ()] = f.l; fr[0][T.own ()] = f.r;
+    f = face_values_dir<3, 1, false, VL, true> (L, v, none, un, c, dt, visc, 0.);
+    fl[1][T.own ()] = f.l; fr[1][T.own ()] = f.r;
+    f = face_values_dir<3, 2, false, VL, true> (L, v, none, un, c, dt, visc, 0.);
+    fl[2][T.own ()] = f.l; fr[2][T.own ()] = f.r;
+  }
+  // halo cells, as in advect_tiled_kernel: waves 0-1 y minus, 2-3 y plus, 4-5 z minus, 6-7 z plus; the
+  // first 32 lanes also take the x halos
+  {
+    const int h = threadIdx.x;
+    const int grp = h / (GX*GZ), idx = h % (GX*GZ), p = idx % GX, q = idx / GX;
+    if (grp < 2) {
+      int ci = image<3> (L, blockIdx.x*GX + p + 1, blockIdx.y*GY + (grp ? GY + 1 : 0), blockIdx.z*GZ + q + 1);
+      FacePair f = face_values_dir<3, 1, false, VL, true> (L, v, none, un, ci, dt, visc, 0.);
+      if (grp) hp[1][idx] = f.r; else hm[1][idx] = f.l;
+    }
+    else {
+      int ci = image<3> (L, blockIdx.x*GX + p + 1, blockIdx.y*GY + q + 1, blockIdx.z*GZ + (grp == 3 ? GZ + 1 : 0));
+      FacePair f = face_values_dir<3, 2, false, VL, true> (L, v, none, un, ci, dt, visc, 0.);
+      if (grp == 3) hp[2][idx] = f.r; else hm[2][idx] = f.l;
+    }
+    if (h < 2*GY*GZ) {
+      const int plus = h >= GY*GZ, hh = h % (GY*GZ), py = hh % GY, qz = hh / GY;
+      int ci = image<3> (L, blockIdx.x*GX + (plus ? GX + 1 : 0), blockIdx.y*GY + py + 1, blockIdx.z*GZ + qz + 1);
+      FacePair f = face_values_dir<3, 0, false, VL, true> (L, v, none, un, ci, dt, visc, 0.);
+      if (plus) hp[0][hh] = f.r; else hm[0][hh] = f.l;
+    }
+  }
+  __syncthreads ();
+  const int t3[3] = { T.tx, T.ty, T.tz }, g3[3] = { GX, GY, GZ };
+  const int so[3] = { 1, GX, GX*GY };
+  const int hi[3] = { T.ty + GY*T.tz, T.tx + GX*T.tz, T.tx + GX*T.ty };
+  // flux through the + face (direction cf) of the own cell (minus = 0) or of the cell before it
+  auto flux = [&] (int cf, int minus) -> double {
+    int a = minus ? c - off[cf] : c;
+    double l_, r_;
+    if (!minus) {
+      l_ = fl[cf][T.own ()];
+      r_ = t3[cf] + 1 < g3[cf] ? fr[cf][T.own () + so[cf]] : hp[cf][hi[cf]];
+    }
+    else {
+      l_ = t3[cf] > 0 ? fl[cf][T.own () - so[cf]] : hm[cf][hi[cf]];
+      r_ = fr[cf][T.own ()];
+    }
+    double unf = un.p[cf][a];
+    double upw = upwinded (unf, l_, r_);
+    return 1.*unf*dt*upw*rn;            /* /h, h = 1/n a power of two: exact scaling */
+  };
+  const int i = T.i, j = T.j, k = T.k;
+  double acc = 0.;
+  if (i > 1)
+    acc += flux (0, 1);
+  acc -= flux (0, 0);
+  acc -= flux (1, 0);
+  acc -= flux (2, 0);
+  {
+    unsigned J = n - j, K = n - k;
+    bool back_first = __ffs (~J) > __ffs (~K);
+    if (back_first) {
+      if (k > 1) acc += flux (2, 1);
+      if (j > 1) acc += flux (1, 1);
+    }
+    else {
+      if (j > 1) acc += flux (1, 1);
+      if (k > 1) acc += flux (2, 1);
+    }
+  }
+  if (i == 1)
+    acc += flux (0, 1);
+  if (j == 1)
+    acc += flux (1, 1);
+  if (k == 1)
+    acc += flux (2, 1);
+  const double t0 = v[c];
+  double val = t0;
+  val += acc/1.;
+  /* diffusion_rhs on the tracer itself, not on the advected value (also when pbeta == 0.) */
+  const double h = 1./L.n;
+  const double f = flux_sum<3> (UniformW { w }, ArrayU { v, c, L.sy, L.sz }, t0);
+  val += pbeta*f/(h*h*1.);
+  out[c] = val;
+}
+
 // ---------------------------------------------------------------------------------------------
 // The three velocity components in ONE pass (gfs_centered_velocity_advection_diffusion without
 // viscosity, src/timestep.c:976-1016: variable_sources of U, V, W with the same MAC velocities).
@@ -3350,6 +3457,21 @@ int launch_advect_fused (gfship_domain * dom, bool velocity, const double * v, d
   }, velocity, gradient != 0, visc != 0. || gsrc != 0.);
   GFSHIP_HIP (hipGetLastError ());
   dom->kc[velocity ? GFSHIP_KC_ADVECT1_TILED_VELOCITY : GFSHIP_KC_ADVECT1_TILED_TRACER]++;
+  return GFSHIP_OK;
+}
+
+// a tracer with a GfsSourceDiffusion: the right-hand side of its implicit solve from the tracer in one pass
+// (where godunov_fused_supported; w: the weight of the leaf faces, gfship_diffusion_coefficients)
+int launch_advect_diffuse_fused (gfship_domain * dom, const double * v, double * out, double * const un[3],
+				 double dt, int gradient, double D, double w, double beta)
+{
+  const Layout & L = dom->lay[dom->depth];
+  dim3 grid (L.n/GX, L.n/GY, L.n/GZ);
+  with_bools ([&] (auto VL) {
+    hipLaunchKernelGGL ((advect_diffuse_tiled_kernel<decltype (VL)::value>), grid, dim3 (GN), 0,
+			dom->stream, L, v, out, c3 (un), dt, D, w, (1. - beta)/beta);
+  }, gradient != 0);
+  GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
 

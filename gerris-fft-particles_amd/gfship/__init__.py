@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("GFSHIP_LIB", os.path.join(_PKG, "lib", "libgfship.so"
 
 SIDE_PERIODIC, SIDE_BOUNDARY, SIDE_EXTERNAL = 0, 1, 2
 BC_SYMMETRY, BC_DIRICHLET, BC_NEUMANN = 0, 1, 2
+SCHEME_GODUNOV, SCHEME_NONE = 0, 1
 RELAX_EXACT, RELAX_REDBLACK, RELAX_EXACT_HYPERPLANE, RELAX_EXACT_PER_SWEEP = 0, 1, 2, 3
 
 
@@ -108,6 +109,11 @@ SIGNATURES = {
     "gfship_sim_step": (_i, [_vp]),
     "gfship_sim_advection_step": (_i, [_vp]),
     "gfship_sim_set_tracer_gradient": (_i, [_vp, _i, _i]),
+    "gfship_sim_set_tracer_scheme": (_i, [_vp, _i, _i]),
+    "gfship_sim_set_tracer_diffusion": (_i, [_vp, _i, _d]),
+    "gfship_sim_tracer_diffusion_params": (C.POINTER(MultilevelParams), [_vp, _i]),
+    "gfship_sim_tracer_diffusion_path": (_i, [_vp, _i]),
+    "gfship_sim_tracer_diffusion_counts": (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     "gfship_predicted_face_velocities": (_i, [_vp]),
     "gfship_mac_projection": (_i, [_vp, C.POINTER(MultilevelParams), _d, _i, _pi]),
     "gfship_approximate_projection": (_i, [_vp, C.POINTER(MultilevelParams), _d, _i, _pi]),
@@ -631,7 +637,39 @@ class Simulation:
         t = _check(lib().gfship_sim_add_tracer(self.ptr))
         if gradient is not None:
             _check(lib().gfship_sim_set_tracer_gradient(self.ptr, t, gradient))
-        return self._var(self.VAR_TRACER, t)
+        v = self._var(self.VAR_TRACER, t)
+        v.tracer_index = t
+        return v
+
+    @staticmethod
+    def _tracer(t):
+        """the index of a tracer: the Variable add_tracer returned, or the index itself"""
+        return t if isinstance(t, int) else t.tracer_index
+
+    def set_tracer_diffusion(self, t, D):
+        """SourceDiffusion T D on a tracer (0. removes it)"""
+        _check(lib().gfship_sim_set_tracer_diffusion(self.ptr, self._tracer(t), float(D)))
+
+    def tracer_diffusion_params(self, t):
+        """the GfsMultilevelParams of the diffusion of a tracer (tolerance 1e-6, beta 1)"""
+        p = lib().gfship_sim_tracer_diffusion_params(self.ptr, self._tracer(t))
+        if not p:
+            raise GfshipError("no tracer %r" % (t,))
+        return p.contents
+
+    def set_tracer_scheme(self, t, scheme):
+        """VariableTracer T { scheme = godunov | none }: SCHEME_GODUNOV, SCHEME_NONE"""
+        _check(lib().gfship_sim_set_tracer_scheme(self.ptr, self._tracer(t), scheme))
+
+    def tracer_diffusion_path(self, fused):
+        """1: the start of a tracer's diffusion solve in one pass where it applies (the default), 0: composed"""
+        _check(lib().gfship_sim_tracer_diffusion_path(self.ptr, int(fused)))
+
+    def tracer_diffusion_counts(self):
+        """(fused, composed): the solves each path has started"""
+        c = (C.c_ulonglong * 2)()
+        _check(lib().gfship_sim_tracer_diffusion_counts(self.ptr, c))
+        return int(c[0]), int(c[1])
 
     def mac_velocity(self, c):
         """MAC velocity of the + face of every cell along c (GFSHIP_VAR_UN)"""

@@ -255,6 +255,32 @@ int      gfship_sim_add_tracer (gfship_sim * sim);       /* GfsVariableTracer, s
    gfs_center_minmod_gradient | gfs_center_superbee_gradient | gfs_center_sweby_gradient }: 0 .. 4
    (src/fluid.c:434-690); the same numbers in gfship_advection_params.gradient */
 int      gfship_sim_set_tracer_gradient (gfship_sim * sim, int tracer, int gradient);
+/* GfsVariableTracer { scheme = godunov | none } (GfsAdvectionScheme, src/advection.h:32-35).  With none the
+   Godunov block of variable_sources (src/timestep.c:878-899) is skipped: the tracer is not advected, only
+   its sources act.  Such a tracer does not enter min_cfl (src/simulation.c:1547-1550). */
+enum { GFSHIP_SCHEME_GODUNOV = 0, GFSHIP_SCHEME_NONE = 1 };
+int      gfship_sim_set_tracer_scheme (gfship_sim * sim, int tracer, int scheme);
+/* GfsSourceDiffusion T D (src/source.c:933-1160) on a tracer: constant coefficient D (0. removes it).
+   gfship_tracer_advection then follows the diffusion branch of gfs_tracer_advection_diffusion
+   (src/timestep.c:1039-1048): rhs = a copy of T on the leaves, variable_sources (T -> rhs) with
+   source_diffusion_value (src/source.c:1105-1144, no alpha factor: :1141-1143 is for velocity components) as
+   the MAC source of the face values, then variable_diffusion (:923-949) with alpha = NULL, i.e.
+   gfship_diffusion_coefficients (D, dt, rhoc, beta), gfship_diffusion_rhs and gfship_diffusion on T with its
+   own conditions and its own parameters.  The CFL condition is untouched (the acceleration term of
+   gfs_domain_cfl reads the sources of U, V, W only, src/domain.c:2893-2901).  D < 0 or a bad index:
+   GFSHIP_EINVAL; a box with GFSHIP_SIDE_EXTERNAL sides: GFSHIP_EUNSUPPORTED. */
+int      gfship_sim_set_tracer_diffusion (gfship_sim * sim, int tracer, double D);
+/* the GfsMultilevelParams of that solve (tolerance 1e-6, beta 1: diffusion_init, src/source.c:966-974); the
+   address holds for the life of the simulation; NULL for a bad index */
+gfship_multilevel_params * gfship_sim_tracer_diffusion_params (gfship_sim * sim, int tracer);
+/* How gfship_tracer_advection starts the solve of a tracer with a GfsSourceDiffusion.  fused = 1 (the
+   default): where a tracer runs on the tiled Godunov kernel (3-D, six periodic sides, n a multiple of 32,
+   gradient 0 or 1, scheme godunov) one pass over T writes rhs = T + fluxes + (1 - beta)/beta*f/(h*h) (the leaf
+   copy, variable_sources and diffusion_rhs, src/timestep.c:1043-1045 and src/poisson.c:1392-1451); fused = 0:
+   the three passes everywhere.  Same bits either way.  counts[0], counts[1]: the solves started by the fused
+   and by the composed path since the simulation was created. */
+int      gfship_sim_tracer_diffusion_path (gfship_sim * sim, int fused);
+int      gfship_sim_tracer_diffusion_counts (gfship_sim * sim, unsigned long long counts[2]);
 /* GfsSourceDiffusion {} U|V|W nu (src/source.c:933-1160): constant implicit viscosity of
    velocity component c (0. removes it), and the GfsMultilevelParams of its solver
    (tolerance 1e-6, beta 1: diffusion_init, src/source.c:966-974) */
@@ -328,6 +354,8 @@ int  gfship_centered_velocity_advection (gfship_sim * sim, const gfship_field gm
    conditions of U, V(, W) -- the statement between the advection and gfs_cell_coarse_init in the
    loop body of simulation_run (src/simulation.c:517-521, there with g or gmac and - dt) */
 int  gfship_correct_centered_velocities (gfship_sim * sim, const gfship_field g[3], double dt);
+/* gfs_tracer_advection_diffusion: with a coefficient set by gfship_sim_set_tracer_diffusion the branch of
+   :1039-1048, otherwise variable_sources in place and the conditions of t */
 int  gfship_tracer_advection (gfship_sim * sim, gfship_field t, double dt);  /* :1028-1055 */
 int  gfship_domain_cfl (gfship_sim * sim, double * cfl);       /* src/domain.c:2824-2923 */
 int  gfship_set_timestep (gfship_sim * sim);                   /* src/simulation.c:1569-1633 */
