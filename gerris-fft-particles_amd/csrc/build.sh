@@ -28,7 +28,13 @@ echo "built $OUT/libgfship.so"
 BIN="$HERE/../bin"
 mkdir -p "$BIN"
 CXX="${CXX:-g++}"
-if [ ! -f "$BIN/gfship2D" ] || [ "$HERE/host/gfsrun.cpp" -nt "$BIN/gfship2D" ] || [ "$HERE/host/gfs_text.hpp" -nt "$BIN/gfship2D" ] || [ "$HERE/host/gfs_snapshot.hpp" -nt "$BIN/gfship2D" ] || [ "$HERE/host/gfs_function.hpp" -nt "$BIN/gfship2D" ] || [ "$HERE/../../include/gfship.h" -nt "$BIN/gfship2D" ]; then
+stale=0
+[ -f "$BIN/gfship2D" ] || stale=1
+# every source and header of host/ (gfsrun.cpp is one translation unit over its headers) and the C ABI
+for d in "$HERE"/host/*.hpp "$HERE"/host/*.cpp "$HERE/../../include/gfship.h"; do
+  [ "$d" -nt "$BIN/gfship2D" ] && stale=1
+done
+if [ $stale = 1 ]; then
   "$CXX" -O2 -std=c++17 -Wall -I"$HERE/../../include" -I"$HERE/host" "$HERE/host/gfsrun.cpp" \
     -o "$BIN/gfship2D" -L"$OUT" -lgfship -ldl -Wl,-rpath,'$ORIGIN/../lib' -Wl,-rpath,/opt/rocm/lib
   cp "$BIN/gfship2D" "$BIN/gfship3D"

@@ -27,6 +27,9 @@ struct Function {
   bool uses_t = false;
   CompiledFn fn = nullptr;
   int where = 0;                   // line of the file, for messages
+  std::vector<int> reads () const {  // the variables it reads (none: a constant, or x, y, z, t only)
+    return kind == VARIABLE ? std::vector<int> { var } : kind == COMPILED ? args : std::vector<int> ();
+  }
 };
 
 class FunctionSet {
