@@ -388,9 +388,10 @@ particulate_coeff_inputs_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
 // gfs_particulate_event (:768-842) in a gfs_particle_list_event (:980-1015)
 // ONFLUID: the forces of the fluid on the particle that a GfsSourceParticulate gives back to the fluid
 // (compute_forces_onfluid, :753-765, in source_particulate_event, :2199-2206): force = 0, then every force
-// of the list but GfsForceBuoy, force[c] = new_force[c]*volume + force[c]; only `force' is written -- the
-// particle does not move, keeps its mass (what compute_addedmass_force adds belongs to the event) and
-// stays on the list; a particle without a cell gets the zero force every compute_*_force returns there
+// of the list but GfsForceBuoy, force[c] = new_force[c]*volume + force[c]; `force' is written, and `mass':
+// compute_addedmass_force adds to particulate->mass here as in an event (:391) and nothing takes it back.
+// The particle does not move and stays on the list; a particle without a cell gets the zero force every
+// compute_*_force returns there and keeps its mass
 template <int DIM, bool RHO, bool MU, bool ONFLUID = false>
 __global__ void __launch_bounds__(256)
 particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
@@ -460,8 +461,7 @@ particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
 #pragma unroll
       for (int c = 0; c < DIM; c++)
 	force[c] *= cm;
-      if (!ONFLUID)
-	mass += fluid_rho*volume*cm;
+      mass += fluid_rho*volume*cm;      /* :391, in compute_forces_onfluid too */
       break;
     }
     case FORCE_LIFT: {          // compute_lift_force, :455-524; vorticity_vector, :146-168
@@ -539,6 +539,7 @@ particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
 #pragma unroll
     for (int c = 0; c < 3; c++)
       A.force[c][o] = pf[c];
+    A.mass[o] = mass;
     return;
   }
 #pragma unroll
@@ -1072,7 +1073,8 @@ int gfship::particulate_fluid_check (const gfship_sim_view & v)
 
 extern "C" {
 
-// onfluid: the forces on the fluid alone (particulate_list_event_kernel <ONFLUID>): nothing but `force' changes
+// onfluid: the forces on the fluid alone (particulate_list_event_kernel <ONFLUID>): `force' changes, and `mass'
+// where the list holds a GfsForceAddedMass
 static int particulate_event (gfship_particles * pl, const PartArgs & P, const gfship_sim_view & v,
 			      bool onfluid = false)
 {

@@ -549,8 +549,10 @@ int  gfship_particles_download_particulate (gfship_particles * pl, double * vel,
    cell for (L = 1).
    gfship_particles_forces_on_fluid: for every particle force = 0, then force[c] = new_force[c]*volume +
    force[c] over the forces of the list in order except GfsForceBuoy (compute_forces_onfluid, :753-765, in
-   source_particulate_event, :2199-2206).  Only the stored force changes (read it with
-   gfship_particles_download_particulate): no particle moves or leaves, the mass and Un, Vn, Wn stay.
+   source_particulate_event, :2199-2206).  The stored force changes (read it with
+   gfship_particles_download_particulate), and the mass of a particle inside the box grows by what every
+   GfsForceAddedMass of the list adds (compute_addedmass_force, :391, is called here as in an event and
+   nothing takes the addition back).  No particle moves or leaves; Un, Vn, Wn stay.
    gfship_particles_set_kernel: rkernel and kernel of GfsSourceParticulate (source_particulate_read,
    :2271-2289): rkernel is an absolute length (cond_kernel, :2143; the `influencerad' of :2210 is never
    used); function is a GfsFunction (spatial) of x, y, z, t -- C text, an expression or a { block },

@@ -306,27 +306,33 @@ def _run_particulates(osim, side, pos, ids, vel, mass, vol, forces, gravity, nst
     for f, (text, fn) in (coefficients or {}).items():
         opl.set_coefficient(f, fn)
         gpl.set_force_coefficient(f, text)
-    worst = 0.
+    worst, differing, compared = 0., 0, 0
     for k in range(nsteps):
         opl.event()
         gpl.event()
         op, oi = opl.state()
         gp, gi = gpl.download()
         # same survivors in the same order; positions, velocities, forces within 1e-12 relative
-        # L-infinity (the only operation not bit-reproducible is pow (Re, 0.5) of the drag law,
-        # sqrt on the device)
+        # L-infinity.  The only operation not bit-reproducible is pow (Re, 0.5) of the drag law, sqrt on
+        # the device: test_forces_reference_cpu.py measures the two (with glibc 2.35 the roots differ for
+        # 14 of 20 000 log-spaced Re, by 1 ulp, and the default cd for 3 of them, by at most 2 ulp), so
+        # the two sides nearly always agree to the bit.  This bound is a backstop over whole arrays; the
+        # forces are pinned bit for bit on the restatement in test_gpu_forces_reference.py.
         assert np.array_equal(oi, gi), k
         ov, om, of = opl.particulate_state()
         gv, gm, gf = gpl.particulate_state()
         for a, b, what in ((op, gp, "pos"), (ov, gv, "vel"), (of, gf, "force"), (om, gm, "mass")):
             e = _rel_err(a, b)
             worst = max(worst, e)
+            differing += int((a != b).sum())
+            compared += a.size
             assert e <= 1e-12, (k, what, e)
         # cell indices bit-identical
         for q in range(0, len(gi), 37):
             assert opl.locate(gp[q]) == opl.locate(op[q])
         osim.step()
         gs.step()
+    print("particulates, %d events: worst %.3e relative, %d of %d elements differ in bits" % (nsteps, worst, differing, compared))
     return worst, opl, gpl
 
 

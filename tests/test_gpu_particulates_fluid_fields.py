@@ -184,7 +184,10 @@ def _center_gradient(v, at, ax):
 def _restated_event(dim, forces, gravity, dt, size, fvel, fveln, grad, ucell, fluid_rho, viscosity,
                     vel, mass, volume, drag_coefficient):
     """gfs_particulate_event (:768-842) of one particle: (force, vel, mass) after the event.  grad[c][c2] is
-    gfs_center_gradient (cell, c2, u[c]), ucell[c] the value of u[c] at the cell."""
+    gfs_center_gradient (cell, c2, u[c]), ucell[c] the value of u[c] at the cell.  One list of forces in one
+    order, fed by the device's own interpolation; the restatement of every force on the cell graph, with
+    positions, wall cells and every order of the list, is tests/forces_reference.py
+    (test_gpu_forces_reference.py)."""
     vel = list(vel)
     pf = [0., 0., 0.]
     # compute_inertial_force, :285-302

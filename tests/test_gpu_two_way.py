@@ -98,7 +98,10 @@ FORCE_LISTS = {
 def test_forces_on_fluid_against_the_oracle(name, dim):
     """after one event and one time step (so that Un differs from U): the stored force after
     gfship_particles_forces_on_fluid is the oracle's force after an event of the same state with the list
-    without buoyancy; nothing else changes, and the next event is the oracle's"""
+    without buoyancy.  Positions, ids and velocities stay; the mass of a particle inside the box grows by
+    fluid_rho*volume*cm per GfsForceAddedMass of the list, as compute_addedmass_force adds it when
+    compute_forces_onfluid calls it (modules/particulatecommon.c:391, :757) -- the oracle has no such call,
+    its masses get the same addition here -- and the next event is the oracle's"""
     forces = FORCE_LISTS[name]
     without_buoy = [f for f in forces if f != O.FORCE_BUOY]
     gravity = (0., 0.5, 0.)
@@ -136,13 +139,26 @@ def test_forces_on_fluid_against_the_oracle(name, dim):
         before = gpl.download() + gpl.particulate_state()
         gpl.forces_on_fluid()
         after = gpl.download() + gpl.particulate_state()
-        for k in (0, 1, 2, 3):      # positions, ids, velocities, masses
+        for k in (0, 1, 2):      # positions, ids, velocities
             assert np.array_equal(before[k], after[k]), k
+        ref, full = lists
+        added = forces.count(O.FORCE_ADDEDMASS)
+
+        def with_added_mass(positions, masses, listed_ids):
+            inside = np.array([full.locate(p) is not None for p in positions])
+            v = vol[np.searchsorted(ids, listed_ids)]
+            m = masses.copy()
+            for _ in range(added):
+                m[inside] += 1. * v[inside] * 0.5
+            return m
+        want = with_added_mass(before[0], before[3], before[1])
+        assert np.array_equal(after[3], want)
+        if added:
+            assert (after[3] > before[3]).sum() > npart * 8 // 10
         gf = after[4]
         if dim == 2:
             assert not gf[:, 2].any()
         # the oracle: the same state, the list without buoyancy
-        ref, full = lists
         ref.set_forces(without_buoy, gravity)
         ref.event()
         oi = ref.state()[1]
@@ -154,7 +170,11 @@ def test_forces_on_fluid_against_the_oracle(name, dim):
         assert err <= 1e-12
         if O.FORCE_BUOY in forces:
             assert _rel_err(before[4][at], of) > 1e-3        # buoyancy is in the event's force, not here
-        # Un, Vn, Wn and the masses are what the event left: the next event is the oracle's
+        # Un, Vn, Wn are what the event left, the masses carry what the evaluation added: the next event is
+        # the oracle's on those masses
+        op, oi = full.state()
+        om = np.ctypeslib.as_array(O.lib().go_particles_mass(full.ptr), shape=(len(oi),))
+        om[...] = with_added_mass(op, om, oi)
         full.event()
         gpl.event()
         op, oi = full.state()
