@@ -2272,6 +2272,11 @@ advect3_sweep_kernel (Layout L, CPtr3 v, Ptr3 out, CPtr3 un, CPtr3 gm, CPtr3 gc,
 // as they exist (double-buffered by the parity of the plane), and the x / y fluxes of plane p - 1 are
 // formed BEFORE the face values of plane p (only the z flux needs them).  Same expressions, same
 // order per cell: bit-identical.
+// Where the waits sit (read them in the assembly after any change here): no wave waits for
+// a load of plane p's iteration before barrier (2) of that iteration, and none for a store.  The ring
+// waves load 13 values per plane (the in-plane neighbours but the outward one come from S_.V, gm of the
+// column's cell from S_.GM) and carry them into the next iteration after barrier (2); the compute waves
+// carry v and un from right after barrier (2), where gc is awaited anyway, ahead of the stores.
 // ---------------------------------------------------------------------------------------------
 struct Sweep2Lds {
   double V[3][SWY + 2][SWX + 2];
@@ -2293,6 +2298,14 @@ __device__ __forceinline__ int sweep2_plane (int k, int n, int sz, bool zlo, boo
   if (k < 1) k = MPI && zlo ? (k < 0 ? 0 : k) : k + n;
   else if (k > n) k = MPI && zhi ? n + 1 : k - n;
   return k*sz;
+}
+
+// x was loaded for a later iteration of a plane loop.  From here on it is another value for the compiler, so the
+// copy that carries it round the loop, and with it the wait for the load, cannot be placed before this point
+// (left alone the copies of the ring waves, two of them through scratch, sat before barrier (1): DESIGN 11.25).
+__device__ __forceinline__ void sweep2_landed (double & x)
+{
+  asm volatile ("" : "+v" (x));
 }
 
 template <bool VL, bool SRC, bool MPI>
@@ -2330,32 +2343,55 @@ __device__ __forceinline__ void sweep2_ring_path (Sweep2Lds & S_, const Layout &
   // are read from the row itself
   const int sy = MPI && recv && hd == 1 ? 0 : sy0;
   const size_t nf = (size_t) n*n;
-  const bool ring = role >= 0, ring_minus = role == 0 || role == 2;
-  // towards the column (a ring cell beyond an MPI side on the + side has nothing of its own to read there)
-  const int hoff = MPI && recv && !ring_minus ? 0 : hd == 0 ? 1 : sy0;
-  const int ry = role == 0 ? 0 : role == 1 ? SWY + 1 : hslot + 1;
-  const int rx = role == 2 ? 0 : role == 3 ? SWX + 1 : hslot + 1;
-  // everything is loaded one iteration before it is used (suffix n: for the next iteration)
+  const bool ring_minus = role == 0 || role == 2;
+  int ry = role == 0 ? 0 : role == 1 ? SWY + 1 : hslot + 1;
+  int rx = role == 2 ? 0 : role == 3 ? SWX + 1 : hslot + 1;
+  if (role < 0 && rid < 2*SWX + 2*SWY + 4) {
+    // four more lanes, one corner of S_.V each: the cell beyond the end of a ring row, which is also the cell
+    // beyond the end of a ring column; its row is that of the ring row, its column that of the ring column
+    // (periodic image or ghost, each by its own side)
+    const int e = rid - 2*SWX - 2*SWY;               /* bit 0: x +, bit 1: y + */
+    role = 4;
+    int hi_ = blockIdx.x*SWX + (e & 1 ? SWX + 1 : 0), hj = blockIdx.y*SWY + (e & 2 ? SWY + 1 : 0);
+    if (!(MPI && (hi_ < 1 || hi_ > n) && G.r[e & 1 ? 0 : 1]))
+      hi_ = hi_ < 1 ? hi_ + n : hi_ > n ? hi_ - n : hi_;
+    if (!(MPI && (hj < 1 || hj > n) && G.r[e & 2 ? 2 : 3]))
+      hj = hj < 1 ? hj + n : hj > n ? hj - n : hj;
+    hcol = (int) L.idx (hi_, hj, 0);
+    ry = e & 2 ? SWY + 1 : 0; rx = e & 1 ? SWX + 1 : 0;
+  }
+  static_assert (2*SWX + 2*SWY + 4 <= SW_RING, "the ring and the four corners are one lane each");
+  const bool ring = role >= 0 && role < 4, fills = role >= 0;
+  // Of the four in-plane neighbours of a ring cell three are in S_.V after barrier (1): the cell of the column
+  // and the two along the ring (written by the neighbouring ring lanes, at the ends by the corner lanes); only
+  // the one away from the column is loaded.  li: the slot of the cell in a plane of S_.V; ln[e]: those of its
+  // neighbours x -, x +, y -, y + (the outward one: the cell itself, never used)
+  const int hout = role == 0 ? -sy : role == 1 ? sy : role == 2 ? -1 : 1;
+  const int li = ry*(SWX + 2) + rx;
+  const int ln[4] = { role == 2 ? li : li - 1, role == 3 ? li : li + 1,
+		      role == 0 ? li : li - (SWX + 2), role == 1 ? li : li + (SWX + 2) };
+  // everything is loaded one iteration before it is used (suffix n: for the next iteration) and nothing loaded
+  // in an iteration is touched before its barrier (2): sweep2_landed
   double hvm[3], hv0[3] = { 0., 0., 0. }, hvp[3] = { 0., 0., 0. }, hvn[3] = { 0., 0., 0. };
-  double nbn[3][4];                                  // in-plane neighbours of the cell: x -, x +, y -, y +
+  double nbo[3] = { 0., 0., 0. };                    // the outward neighbour
   double huan[3] = { 0., 0., 0. }, hubn[2] = { 0., 0. };
-  double hunb = 0., hunzb = 0., hlo[3] = { 0., 0., 0. }, hgmo[3], hgmn[3] = { 0., 0., 0. };
-  double hgcn[3] = { 0., 0., 0. };                   // gm of the column's cell beside the ring cell
+  double hunb = 0., hunzb = 0., hlo[3] = { 0., 0., 0. }, hgmo[3] = { 0., 0., 0. }, hgmn[3] = { 0., 0., 0. };
+  double hrcn[3] = { 0., 0., 0. };                   // the state beyond an MPI side
+  auto recv_at = [=] (int q, int k) { return recv[q*nf + (size_t) n*(k < 1 ? 0 : k > n ? n - 1 : k - 1)]; };
+  if (fills) {
 #pragma unroll
-  for (int q = 0; q < 3; q++) {
-    hgmo[q] = 0.;
-#pragma unroll
-    for (int e = 0; e < 4; e++) nbn[q][e] = 0.;
+    for (int q = 0; q < 3; q++) {
+      hv0[q] = v.p[q][hcol + plane (kb - 1)];
+      hvp[q] = v.p[q][hcol + plane (kb)];
+      hvn[q] = v.p[q][hcol + plane (kb + 1)];
+    }
   }
   if (ring) {
     const int hc = hcol + plane (kb);
 #pragma unroll
     for (int q = 0; q < 3; q++) {
-      hv0[q] = v.p[q][hcol + plane (kb - 1)];
-      hvp[q] = v.p[q][hc];
-      hvn[q] = v.p[q][hcol + plane (kb + 1)];
-      nbn[q][0] = v.p[q][hc - 1];  nbn[q][1] = v.p[q][hc + 1];
-      nbn[q][2] = v.p[q][hc - sy]; nbn[q][3] = v.p[q][hc + sy];
+      nbo[q] = v.p[q][hc + hout];
+      if (MPI && recv) hrcn[q] = recv_at (q, kb);
     }
     huan[0] = un.p[0][hc]; hubn[0] = un.p[0][hc - 1];
     huan[1] = un.p[1][hc]; hubn[1] = un.p[1][hc - sy];
@@ -2364,37 +2400,37 @@ __device__ __forceinline__ void sweep2_ring_path (Sweep2Lds & S_, const Layout &
   }
   for (int p = kb; p <= kb + SWZ + 1; p++) {
     const int zp = plane (p);
-    Stencil7 HW[3];
-    double hua[3], hub[3];
+    double hua[3], hub[3], hno[3], hrc[3];
 #pragma unroll
     for (int q = 0; q < 3; q++) {
       hvm[q] = hv0[q]; hv0[q] = hvp[q]; hvp[q] = hvn[q];
-      HW[q].v0 = hv0[q];
-      HW[q].m[0] = nbn[q][0]; HW[q].p[0] = nbn[q][1];
-      HW[q].m[1] = nbn[q][2]; HW[q].p[1] = nbn[q][3];
-      HW[q].m[2] = hvm[q]; HW[q].p[2] = hvp[q];
+      hno[q] = nbo[q];
+      hrc[q] = hrcn[q];
       hgmo[q] = hgmn[q];                             // gm (p - 1) of the ring cell
     }
     hua[0] = huan[0]; hua[1] = huan[1]; hua[2] = huan[2];
     hub[0] = hubn[0]; hub[1] = hubn[1]; hub[2] = hunzb;
-    const double hgc[3] = { hgcn[0], hgcn[1], hgcn[2] };
-    if (ring) {
-      // the loads of the next iteration (plane p + 1; gm of plane p)
-      const int hc1 = hcol + plane (p + 1);
+    if (fills) {
+      // the loads of the next iterations (v of plane p + 2; the rest of plane p + 1; gm of plane p)
 #pragma unroll
       for (int q = 0; q < 3; q++) {
 	hvn[q] = v.p[q][hcol + plane (p + 2)];
-	nbn[q][0] = v.p[q][hc1 - 1];  nbn[q][1] = v.p[q][hc1 + 1];
-	nbn[q][2] = v.p[q][hc1 - sy]; nbn[q][3] = v.p[q][hc1 + sy];
+	S_.V[q][ry][rx] = hv0[q];
+      }
+    }
+    if (ring) {
+      const int hc1 = hcol + plane (p + 1);
+#pragma unroll
+      for (int q = 0; q < 3; q++) {
+	nbo[q] = v.p[q][hc1 + hout];
 	hgmn[q] = gm.p[q][hcol + zp];
-	hgcn[q] = gm.p[q][hcol + zp + hoff];
+	if (MPI && recv) hrcn[q] = recv_at (q, p + 1);
       }
       huan[0] = un.p[0][hc1]; hubn[0] = un.p[0][hc1 - 1];
       huan[1] = un.p[1][hc1]; hubn[1] = un.p[1][hc1 - sy];
       huan[2] = un.p[2][hc1];
 #pragma unroll
       for (int q = 0; q < 3; q++) {
-	S_.V[q][ry][rx] = hv0[q];
 	if (role == 3) S_.GM[q][hslot][SWX] = hgmo[q];
 	if (role == 1) S_.GM[q][SWY][hslot] = hgmo[q];
       }
@@ -2407,26 +2443,35 @@ __device__ __forceinline__ void sweep2_ring_path (Sweep2Lds & S_, const Layout &
       const AdvShared S = adv_shared_v (hua, hub, dt, rsize2);
 #pragma unroll
       for (int q = 0; q < 3; q++) {
-	FacePair f = hd == 0 ? adv_face_values_s<0, VL, SRC> (HW[q], S, dt, rsize2, src3.g[q]) :
-	  adv_face_values_s<1, VL, SRC> (HW[q], S, dt, rsize2, src3.g[q]);
-	if (MPI && recv) {
+	const double * Vq = &S_.V[q][0][0];
+	Stencil7 HW;
+	HW.v0 = hv0[q];
+	HW.m[0] = Vq[ln[0]]; HW.p[0] = Vq[ln[1]];
+	HW.m[1] = Vq[ln[2]]; HW.p[1] = Vq[ln[3]];
+	if (role == 2) HW.m[0] = hno[q];
+	if (role == 3) HW.p[0] = hno[q];
+	if (role == 0) HW.m[1] = hno[q];
+	if (role == 1) HW.p[1] = hno[q];
+	HW.m[2] = hvm[q]; HW.p[2] = hvp[q];
+	FacePair f = hd == 0 ? adv_face_values_s<0, VL, SRC> (HW, S, dt, rsize2, src3.g[q]) :
+	  adv_face_values_s<1, VL, SRC> (HW, S, dt, rsize2, src3.g[q]);
+	if (MPI && recv)
 	  /* beyond an MPI side: the state the neighbour box sent (planes 0 and n + 1 feed nothing that is stored) */
-	  const int zc = p < 1 ? 0 : p > n ? n - 1 : p - 1;
-	  f.l = f.r = recv[q*nf + (size_t) n*zc];
-	}
+	  f.l = f.r = hrc[q];
 	hl[q] = f.l;
 	if (role == 3) S_.FRx[p & 1][q][hslot][SWX] = f.r;
 	if (role == 1) S_.FRy[p & 1][q][SWY][hslot] = f.r;
       }
-      // the face between the cell and the column, plane p - 1
+      // the face between the cell and the column, plane p - 1 (gm of the column's cell: what it wrote to S_.GM)
       if (p > kb && ring_minus) {
 	const double ua = hunb;
 	const double fu = 1.*ua*dt*rn;
 #pragma unroll
 	for (int q = 0; q < 3; q++) {
 	  const double rs = role == 2 ? S_.FRx[(p - 1) & 1][q][hslot][0] : S_.FRy[(p - 1) & 1][q][0][hslot];
+	  const double hgc = role == 2 ? S_.GM[q][hslot][0] : S_.GM[q][0][hslot];
 	  double f = fu;
-	  f *= upwinded (ua, hlo[q], rs) - face_interp (hgmo[q], hgc[q])*dt/2.;
+	  f *= upwinded (ua, hlo[q], rs) - face_interp (hgmo[q], hgc)*dt/2.;
 	  if (role == 2) S_.FPx[q][hslot][0] = f; else S_.FPy[q][0][hslot] = f;
 	}
       }
@@ -2439,6 +2484,13 @@ __device__ __forceinline__ void sweep2_ring_path (Sweep2Lds & S_, const Layout &
       hunb = hua[hd];
       hunzb = hua[2];
     }
+    // what this iteration loaded is carried into the next one from here, not from before a barrier
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      sweep2_landed (hvn[q]); sweep2_landed (nbo[q]); sweep2_landed (hgmn[q]); sweep2_landed (huan[q]);
+      if (MPI) sweep2_landed (hrcn[q]);
+    }
+    sweep2_landed (hubn[0]); sweep2_landed (hubn[1]);
   }
 }
 
@@ -2486,21 +2538,32 @@ advect3_sweep2_kernel (Layout L, CPtr3 v, Ptr3 out, CPtr3 un, CPtr3 gm, CPtr3 gc
     unn[d] = un.p[d][col + plane (kb)];
     unb[d] = 0.;
   }
+  // gc of a component that has none is loaded from gm (same layout) and not used: the loop has no load
+  // behind a branch
+  const double * gcl[3];
+#pragma unroll
+  for (int q = 0; q < 3; q++)
+    gcl[q] = gc.p[q] ? gc.p[q] : gm.p[q];
 
   for (int p = kb; p <= kb + SWZ + 1; p++) {
     const int zp = plane (p);
     const int rp = p & 1, ro = rp ^ 1;
-    // ---- shift the column registers; the loads (none is consumed before the face values are done,
-    // un not before the next iteration)
+    // ---- shift the column registers; the loads, in the order in which they are consumed (loads return in
+    // order): gm and gc after the face values of this iteration, v and un not before the next one.  No
+    // branch around a load, so the counts of the waits are exact.
     double gcv[3];
 #pragma unroll
     for (int q = 0; q < 3; q++) {
       vm[q] = v0[q]; v0[q] = vp[q]; vp[q] = vn[q];
-      vn[q] = v.p[q][col + plane (p + 2)];
       gmo[q] = gmc[q];
       gmc[q] = gm.p[q][col + zp];
-      gcv[q] = gc.p[q] ? gc.p[q][col + plane (p - 1)] : 0.;
     }
+#pragma unroll
+    for (int q = 0; q < 3; q++)
+      gcv[q] = gcl[q][col + plane (p - 1)];
+#pragma unroll
+    for (int q = 0; q < 3; q++)
+      vn[q] = v.p[q][col + plane (p + 2)];
     const double unzb = una[2];                      // un_z (p - 1)
 #pragma unroll
     for (int d = 0; d < 3; d++) {
@@ -2572,6 +2635,13 @@ advect3_sweep2_kernel (Layout L, CPtr3 v, Ptr3 out, CPtr3 un, CPtr3 gm, CPtr3 gc
       }
     }
     __syncthreads ();                                // (2) the fluxes of plane p - 1; plane p has been read
+    // v and un for the next iteration are carried from here, where gc is awaited anyway: their copies round
+    // the loop then sit behind no wait.  Left at the bottom of the loop the copies waited for everything, the
+    // stores of the update just issued included (a store counts like a load until it is acknowledged).
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      sweep2_landed (vn[q]); sweep2_landed (unn[q]);
+    }
     if (p > kb) {
       const int o = p - 1, co = col + plane (o);
       if (p > kb + 1) {
