@@ -6,6 +6,8 @@ holding its part of a field with one period over the lattice, against oracle box
 lattice, bit for bit.  Prints one JSON line.
 
   python tests/mock_rccl_worker.py flow NBOXES LEVEL NSTEPS OVERLAP [nofast]
+  python tests/mock_rccl_worker.py flow --lattice BXxBYxBZ --level L --nsteps N [--overlap 1] [--gradient 0|1]
+         [--source U|V|W:value] [--visc nu] [--switch GFSHIP_NAME ...]
   python tests/mock_rccl_worker.py particles
 """
 import json
@@ -35,14 +37,39 @@ def mock_counters():
                 timeouts=int(L.mock_rccl_timeouts()))
 
 
-def flow(nboxes, level, nsteps, overlap, fast):
-    from test_multibox_cpu import run_lattice_flow_threads
-    if not fast:
-        os.environ["GFSHIP_NO_LATTICE_CYCLE"] = "1"
-        os.environ["GFSHIP_NO_FUSED_MPI"] = "1"
+KERNEL_FAMILIES = ("PREDICT_SWEEP_MPI", "PREDICT_TILED_MPI", "PREDICT_GENERAL", "ADVECT3_SWEEP2_MPI",
+                   "ADVECT3_TILED_MPI", "ADVECT_GENERAL", "CORRECTION_FUSED", "CORRECTION_DECLINED",
+                   "DIVERGENCE_FUSED")
+
+
+def differing(d, o):
+    """names of what differs between two states of tests/test_multibox_cpu.py::lattice_flow_state"""
+    bad = [name for name in ("u", "v", "w", "p", "pmac") if not np.array_equal(d[name], o[name])]
+    for key, tag in (("g", "g%d"), ("un", "un%d"), ("coarse", "coarse%d")):
+        bad += [tag % c for c in range(3) if not np.array_equal(d[key][c], o[key][c])]
+    bad += [name for name in ("dt", "t", "res") if d[name] != o[name]]
+    if tuple(d["niter"]) != tuple(o["niter"]):
+        bad.append("niter")
+    return bad
+
+
+def flow(grid, level, nsteps, overlap, gradient=None, source=None, visc=0., switches=()):
+    """device boxes of the lattice `grid` over the library's transport against oracle boxes of the same
+    lattice: everything lattice_flow_state holds, after the start-up (step 0) and after every step"""
+    import time
+    from test_multibox_cpu import lattice_flow_state, run_lattice_flow_threads
+    for name in switches:
+        assert name.startswith("GFSHIP_"), name
+        os.environ[name] = "1"          # a domain looks its switches up when it is created
     n = 1 << level
-    grid = D.BoxGrid(nboxes, 3)
+    nboxes = grid.n
+    t0 = time.time()
+    ora = run_lattice_flow_threads(nboxes, level, nsteps, overlap, grid=grid, gradient=gradient,
+                                   source=source, visc=visc, per_step=True)
+    t1 = time.time()
     uid = gfship.comm_unique_id()
+    bad = []
+    i3 = (slice(1, -1),) * 3
 
     def worker(rank, fabric):
         gd = gfship.Domain(3, level, grid.sides(rank))
@@ -56,39 +83,69 @@ def flow(nboxes, level, nsteps, overlap, fast):
             b = np.zeros((n + 2,) * 3)
             b[1:-1, 1:-1, 1:-1] = a
             gs.u[c].upload(b)
+        if gradient is not None:
+            gs.advection_params.gradient = gradient
+        if source is not None:
+            gs.set_source(*source)
+        if visc:
+            for c in range(3):
+                gs.set_viscosity(c, visc)
+
+        def check(step):
+            gd.synchronize()
+            st = lattice_flow_state(gs, n, level, gs.un, lambda f: f.download()[i3],
+                                    lambda f: f.download(level - 1)[i3])
+            bad.extend((rank, step, name) for name in differing(st, ora[rank][step]))
+            return st
+
         gs.start()
-        for _ in range(nsteps):
+        st = check(0)
+        for k in range(nsteps):
             gs.step()
-        gd.synchronize()
-        i3 = (slice(1, -1),) * 3
-        out = dict(u=gs.u[0].download()[i3], v=gs.u[1].download()[i3], w=gs.u[2].download()[i3],
-                   p=gs.p.download()[i3], pmac=gs.pmac.download()[i3],
-                   g=[gs.g[c].download()[i3] for c in range(3)], dt=gs.dt, t=gs.t,
-                   niter=(gs.projection_params.niter, gs.approx_projection_params.niter),
-                   res=gs.approx_projection_params.residual.infty,
-                   counts=gd.path_counts(), stats=gd.comm_stats())
+            st = check(k + 1)
+        kc = gd.kernel_counts()
+        out = dict(u=st["u"], kernels={f: kc[f] for f in KERNEL_FAMILIES}, counts=gd.path_counts(),
+                   stats=gd.comm_stats())
         fabric.barrier.wait()       # nobody destroys buffers a neighbour may still read
         gs.destroy()
         gd.destroy()
         return out
 
     dev = M.run_boxes(nboxes, worker)
-    ora = run_lattice_flow_threads(nboxes, level, nsteps, overlap)
-    bad = []
-    for rank, (d, o) in enumerate(zip(dev, ora)):
-        for name in ("u", "v", "w", "p", "pmac"):
-            if not np.array_equal(d[name], o[name]):
-                bad.append((rank, name))
-        for c in range(3):
-            if not np.array_equal(d["g"][c], o["g"][c]):
-                bad.append((rank, "g%d" % c))
-        if d["dt"] != o["dt"] or d["t"] != o["t"] or tuple(d["niter"]) != tuple(o["niter"]) or \
-                d["res"] != o["res"]:
-            bad.append((rank, "scalars"))
-    return dict(bad=bad, differ=bool(not np.array_equal(dev[0]["u"], dev[1]["u"])),
+    t2 = time.time()
+    differ = all(not np.array_equal(dev[a]["u"], dev[b]["u"]) for a in range(nboxes) for b in range(a))
+    return dict(bad=sorted(bad), differ=bool(differ), kernels=[d["kernels"] for d in dev],
                 lattice_cycles=[int(d["counts"][0]) for d in dev],
                 fused_mpi=[int(d["counts"][1]) for d in dev],
-                sent=[int(d["stats"][0]) for d in dev], **mock_counters())
+                sent=[int(d["stats"][0]) for d in dev],
+                seconds=dict(oracle=round(t1 - t0, 2), device=round(t2 - t1, 2)), **mock_counters())
+
+
+def flow_arguments(argv):
+    """flow NBOXES LEVEL NSTEPS OVERLAP [nofast], or flow --lattice BXxBYxBZ --level L --nsteps N with
+    --overlap, --gradient, --source U|V|W:value, --visc nu and --switch GFSHIP_NAME (repeatable)"""
+    if argv and not argv[0].startswith("--"):
+        nofast = len(argv) > 4 and argv[4] == "nofast"
+        return dict(grid=D.BoxGrid(int(argv[0]), 3), level=int(argv[1]), nsteps=int(argv[2]),
+                    overlap=int(argv[3]),
+                    switches=("GFSHIP_NO_LATTICE_CYCLE", "GFSHIP_NO_FUSED_MPI") if nofast else ())
+    import argparse
+    ap = argparse.ArgumentParser(prog="mock_rccl_worker.py flow")
+    ap.add_argument("--lattice", required=True)
+    ap.add_argument("--level", type=int, required=True)
+    ap.add_argument("--nsteps", type=int, required=True)
+    ap.add_argument("--overlap", type=int, default=0)
+    ap.add_argument("--gradient", type=int, default=None)
+    ap.add_argument("--source", default=None)
+    ap.add_argument("--visc", type=float, default=0.)
+    ap.add_argument("--switch", action="append", default=[])
+    a = ap.parse_args(argv)
+    source = None
+    if a.source:
+        comp, value = a.source.split(":")
+        source = ("UVW".index(comp), float(value))
+    return dict(grid=M.ShapedGrid([int(x) for x in a.lattice.split("x")]), level=a.level, nsteps=a.nsteps,
+                overlap=a.overlap, gradient=a.gradient, source=source, visc=a.visc, switches=tuple(a.switch))
 
 
 def particles():
@@ -170,8 +227,7 @@ def particles():
 
 if __name__ == "__main__":
     if sys.argv[1] == "flow":
-        out = flow(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]),
-                   len(sys.argv) < 7 or sys.argv[6] != "nofast")
+        out = flow(**flow_arguments(sys.argv[2:]))
     else:
         out = particles()
     print("MOCKRCCL " + json.dumps(out))

@@ -4,6 +4,7 @@
   * LocalFabric / LocalTransport: an in-process transport for several boxes of one process (one
     thread per box), used to run several oracle boxes, or several device boxes on a single GPU
     (RCCL refuses two ranks on one device), through the GFSHIP_SIDE_EXTERNAL path;
+  * ShapedGrid: a lattice of boxes of a given shape (1 x 1 x 2, 1 x 2 x 2 ...);
   * global fields: every box holds ITS part of a field defined on the whole lattice, so that a
     swapped peer, a wrong rank_of or a left/right mix-up changes the results;
   * run_boxes: the thread harness.
@@ -30,6 +31,21 @@ def layer_slices(dim, n, side, ghost):
     else:
         sl[axis] = 1 if side & 1 else n
     return tuple(sl)
+
+
+class ShapedGrid(D.BoxGrid):
+    """a BoxGrid whose lattice b = (bx, by, bz) is given instead of derived from the number of boxes
+    (D.lattice doubles along x first: a split along y or z alone never comes out of it).  Same rank
+    formula, so the library's transport (gfship_domain_comm_init takes any lattice) sees the same
+    neighbours"""
+
+    def __init__(self, b, dim=3):
+        b = tuple(int(x) for x in b)
+        if len(b) != 3 or min(b) < 1 or (dim == 2 and b[2] != 1):
+            raise ValueError("not a lattice of %d-D boxes: %r" % (dim, b))
+        self.dim = dim
+        self.b = b
+        self.n = b[0] * b[1] * b[2]
 
 
 class OracleHooks:

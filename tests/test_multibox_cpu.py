@@ -39,12 +39,24 @@ def _part(grid, rank, G, n):
     return G[cz * n:(cz + 1) * n, cy * n:(cy + 1) * n, cx * n:(cx + 1) * n]
 
 
-@pytest.mark.parametrize("nboxes", [2, 4, 8])
+SHAPES = [(1, 1, 2), (1, 2, 1), (1, 2, 2), (2, 1, 2)]     # lattices that doubling along x first never gives
+
+
+def _shape_id(b):
+    return "%dx%dx%d" % tuple(b)
+
+
+@pytest.mark.parametrize("nboxes", [2, 4, 8] + [pytest.param(b, id=_shape_id(b)) for b in SHAPES])
 def test_ghost_layers_come_from_the_geometric_neighbour(nboxes):
     level = 3
     n = 1 << level
-    grid = D.BoxGrid(nboxes, 3)
-    G = _global_random(grid, n, 7 + nboxes)
+    if isinstance(nboxes, tuple):
+        grid = M.ShapedGrid(nboxes)
+        nboxes = grid.n
+        G = _global_random(grid, n, 7 + 100 * grid.b[0] + 10 * grid.b[1] + grid.b[2])
+    else:
+        grid = D.BoxGrid(nboxes, 3)
+        G = _global_random(grid, n, 7 + nboxes)
     L = O.lib()
 
     def worker(rank, fabric):
@@ -72,6 +84,34 @@ def test_ghost_layers_come_from_the_geometric_neighbour(nboxes):
                 sl = [slice(1, -1)] * 3
                 sl[ax] = s
                 assert np.array_equal(a[tuple(sl)], want[tuple(sl)]), (rank, ax, s)
+
+
+@pytest.mark.parametrize("b", SHAPES + [(2, 2, 2)], ids=_shape_id)
+def test_shaped_grid_neighbours_follow_the_rank_formula_of_the_transport(b):
+    """rank r sits at (r % bx, (r / bx) % by, r / (bx by)) (struct Comm, csrc/transport.hip); the box
+    across side d is one step along axis d / 2, + for even d, on the periodic lattice"""
+    bx, by, bz = b
+    grid = M.ShapedGrid(b)
+    assert grid.n == bx * by * bz and grid.b == tuple(b)
+    assert grid.external_sides() == [d for d in range(6) if b[d // 2] > 1]
+    for r in range(grid.n):
+        c = [r % bx, (r // bx) % by, r // (bx * by)]
+        assert grid.coords(r) == tuple(c) and grid.rank_of(c) == r
+        assert grid.sides(r) == [D.SIDE_EXTERNAL if b[d // 2] > 1 else D.SIDE_PERIODIC for d in range(6)]
+        for d in range(6):
+            cc = list(c)
+            cc[d // 2] += -1 if d & 1 else 1
+            cc = [(x % m + m) % m for x, m in zip(cc, b)]
+            assert grid.neighbour(r, d) == cc[0] + bx * (cc[1] + by * cc[2]), (r, d)
+            assert grid.neighbour(grid.neighbour(r, d), d ^ 1) == r
+
+
+def test_shaped_grid_refuses_what_is_no_lattice():
+    for b in ((2, 2), (0, 1, 1), (2, 1, 1, 1)):
+        with pytest.raises(ValueError):
+            M.ShapedGrid(b)
+    with pytest.raises(ValueError):
+        M.ShapedGrid((2, 1, 2), dim=2)
 
 
 def _solve_boxes(nboxes, level, overlap, cycles, tolerance=1e-30):
@@ -144,10 +184,34 @@ def test_two_ranks_over_gloo_equal_two_threads_on_the_lattice_field(tmp_path, ov
     assert not np.array_equal(ref[0]["u"], ref[1]["u"])
 
 
-def run_lattice_flow_threads(nboxes, level, nsteps, overlap, tolerance=None):
-    """the oracle on a lattice of boxes, one thread per box: state of every box after nsteps"""
+def lattice_flow_state(sim, n, depth, un, interior, coarse):
+    """what the lattice tests compare of one box, oracle or device alike: un (c) the MAC velocities of
+    component c with ghosts, interior (f) / coarse (f) the leaf cells / level depth - 1 of a field"""
+    st = dict(u=interior(sim.u[0]), v=interior(sim.u[1]), w=interior(sim.u[2]), p=interior(sim.p),
+              dt=sim.dt, t=sim.t, g=[interior(sim.g[c]) for c in range(3)], pmac=interior(sim.pmac),
+              niter=(sim.projection_params.niter, sim.approx_projection_params.niter),
+              res=sim.approx_projection_params.residual.infty)
+    # the faces with tangential coordinates in 1..n and normal coordinate in 0..n (_assert_same_un of
+    # tests/test_gpu_timestep.py): face 0 along an MPI side is the one shared with the neighbour box
+    st["un"] = []
+    for c in range(3):
+        sl = [slice(1, n + 1)] * 3
+        sl[2 - c] = slice(0, n + 1)
+        st["un"].append(np.array(un(c)[tuple(sl)]))
+    st["coarse"] = [coarse(sim.u[c]) for c in range(3)]
+    return st
+
+
+def run_lattice_flow_threads(nboxes, level, nsteps, overlap, tolerance=None, grid=None, gradient=None,
+                             source=None, visc=0., per_step=False):
+    """the oracle on a lattice of boxes, one thread per box: state of every box after nsteps.
+    grid: the lattice (default: nboxes doubled along x, y, z in turn); gradient: of the velocity
+    advection (0 centred, 1 van Leer); source = (component, value): GfsSource; visc: SourceDiffusion on
+    U, V, W; per_step: the list of states after the start-up and after every step instead"""
     n = 1 << level
-    grid = D.BoxGrid(nboxes, 3)
+    if grid is None:
+        grid = D.BoxGrid(nboxes, 3)
+    assert grid.n == nboxes
     L = O.lib()
 
     def worker(rank, fabric):
@@ -160,19 +224,60 @@ def run_lattice_flow_threads(nboxes, level, nsteps, overlap, tolerance=None):
         if tolerance is not None:
             sim.projection_params.tolerance = tolerance
             sim.approx_projection_params.tolerance = tolerance
+        if gradient is not None:
+            sim.advection_params.gradient = gradient
+        if source is not None:
+            sim.set_source(*source)
+        if visc:
+            for c in range(3):
+                sim.set_viscosity(c, visc)
+
+        def state():
+            return lattice_flow_state(sim, n, level, lambda c: sim.un(2 * c), lambda f: f.interior().copy(),
+                                      lambda f: f.interior(level - 1).copy())
+
         sim.start()
+        states = [state()] if per_step else []
         for _ in range(nsteps):
             sim.step()
-        out = dict(u=sim.u[0].interior().copy(), v=sim.u[1].interior().copy(),
-                   w=sim.u[2].interior().copy(), p=sim.p.interior().copy(), dt=sim.dt, t=sim.t,
-                   g=[sim.g[c].interior().copy() for c in range(3)],
-                   pmac=sim.pmac.interior().copy(),
-                   niter=(sim.projection_params.niter, sim.approx_projection_params.niter),
-                   res=sim.approx_projection_params.residual.infty)
+            if per_step:
+                states.append(state())
+        out = states if per_step else state()
         del hooks
         return out
 
     return M.run_boxes(nboxes, worker)
+
+
+def test_lattice_flow_threads_options():
+    """per_step ends on the state the plain call returns; gradient, source and viscosity reach the
+    oracle (each changes the flow); a lattice split along z alone runs and differs from the one along x"""
+    level, nsteps = 3, 2
+    n = 1 << level
+    plain = run_lattice_flow_threads(2, level, nsteps, 0)
+    steps = run_lattice_flow_threads(2, level, nsteps, 0, per_step=True)
+    assert [len(s) for s in steps] == [nsteps + 1] * 2
+    for rank in range(2):
+        a, b = plain[rank], steps[rank][-1]
+        assert set(a) == set(b) >= {"u", "v", "w", "p", "pmac", "g", "dt", "t", "niter", "res", "un", "coarse"}
+        for name in ("u", "v", "w", "p", "pmac"):
+            assert np.array_equal(a[name], b[name]) and a[name].shape == (n,) * 3
+        for c in range(3):
+            assert np.array_equal(a["un"][c], b["un"][c]) and np.array_equal(a["coarse"][c], b["coarse"][c])
+            assert a["coarse"][c].shape == (n // 2,) * 3
+            sh = [n] * 3
+            sh[2 - c] = n + 1
+            assert a["un"][c].shape == tuple(sh)
+        assert a["t"] == b["t"] and steps[rank][0]["t"] == 0. and steps[rank][1]["t"] < b["t"]
+        # the MAC velocity of the face shared by the two boxes: both hold it (x: + face of box 0 is
+        # face 0 of box 1 and the other way round, the lattice being periodic)
+        assert np.array_equal(plain[rank]["un"][0][:, :, n], plain[rank ^ 1]["un"][0][:, :, 0])
+    for kw in (dict(gradient=1), dict(source=(1, -0.8)), dict(visc=2e-3)):
+        other = run_lattice_flow_threads(2, level, nsteps, 0, **kw)
+        assert not np.array_equal(other[0]["v"], plain[0]["v"]), kw
+    z = run_lattice_flow_threads(2, level, nsteps, 0, grid=M.ShapedGrid((1, 1, 2)))
+    assert not np.array_equal(z[0]["u"], plain[0]["u"])
+    assert np.array_equal(z[0]["un"][2][n], z[1]["un"][2][0])
 
 
 def test_multibox_flow_approaches_the_single_box_flow_of_the_whole_grid():
