@@ -9,6 +9,13 @@
 
 using namespace gfship;
 
+// `dimension' of gfs_relax / gfs_residual / GfsMultilevelParams: 2 on a 3-D domain selects relax2D over the
+// four FTT_NEIGHBORS_2D in the reference (src/poisson.c:604-632), 3 on a 2-D domain does not exist there.  The
+// kernels sum the 2 dim directions of the domain whatever it says: anything but the domain's own is refused.
+#define GFSHIP_CHECK_DIMENSION(dom, d) \
+  GFSHIP_CHECK ((d) == (unsigned) (dom)->dim, GFSHIP_EUNSUPPORTED, \
+		"dimension %u on a %d-D domain: only the dimension of the domain is implemented", (d), (dom)->dim)
+
 namespace gfship {
 
 // weighted sweeps of this level run on the pipelined tile kernel (GFSHIP_WEIGHTED_HYPERPLANES=1: one
@@ -277,6 +284,7 @@ int gfship_relax (gfship_domain * dom, unsigned d, int level, double omega,
   if (!U || !R || !D) return GFSHIP_EINVAL;
   GFSHIP_CHECK (level >= 0 && level <= dom->depth, GFSHIP_EINVAL, "level %d out of range", level);
   GFSHIP_CHECK (d == 2 || d == 3, GFSHIP_EINVAL, "dimension must be 2 or 3");
+  GFSHIP_CHECK_DIMENSION (dom, d);
   GFSHIP_CHECK (dom->unit_weights, GFSHIP_EINVAL, "call gfship_poisson_coefficients first");
   { int r = before_write (dom); if (r) return r; }
   for (Field * F : { U, R, D })
@@ -287,11 +295,12 @@ int gfship_relax (gfship_domain * dom, unsigned d, int level, double omega,
 int gfship_residual (gfship_domain * dom, unsigned d, int level,
 		     gfship_field u, gfship_field rhs, gfship_field dia, gfship_field res)
 {
-  (void) d;
   Field * U = get_field (dom, u), * R = get_field (dom, rhs), * D = get_field (dom, dia),
     * S = get_field (dom, res);
   if (!U || !R || !D || !S) return GFSHIP_EINVAL;
   GFSHIP_CHECK (level >= 0 && level <= dom->depth, GFSHIP_EINVAL, "level %d out of range", level);
+  GFSHIP_CHECK (d == 2 || d == 3, GFSHIP_EINVAL, "dimension must be 2 or 3");
+  GFSHIP_CHECK_DIMENSION (dom, d);
   GFSHIP_CHECK (dom->unit_weights, GFSHIP_EINVAL, "call gfship_poisson_coefficients first");
   { int r = before_write (dom); if (r) return r; }
   for (Field * F : { U, R, D, S })
@@ -351,6 +360,7 @@ static int poisson_cycle (gfship_domain * dom, gfship_multilevel_params * p,
 {
   GFSHIP_CHECK (dom && p, GFSHIP_EINVAL, "null argument");
   GFSHIP_CHECK (p->dimension == 2 || p->dimension == 3, GFSHIP_EINVAL, "dimension must be 2 or 3");
+  GFSHIP_CHECK_DIMENSION (dom, p->dimension);
   GFSHIP_CHECK (p->nrelax > 0 && p->erelax > 0, GFSHIP_EINVAL, "nrelax and erelax must be non zero");
   GFSHIP_CHECK (dom->unit_weights, GFSHIP_EINVAL, "call gfship_poisson_coefficients first");
   /* gfs_temporary_variable: the allocation is kept between cycles (a hipMalloc/hipFree pair
@@ -479,6 +489,8 @@ int gfship_poisson_solve (gfship_domain * dom, gfship_multilevel_params * par,
   Field * U = get_field (dom, lhs), * R = get_field (dom, rhs), * D = get_field (dom, dia),
     * S = get_field (dom, res);
   if (!U || !R || !D || !S) return GFSHIP_EINVAL;
+  GFSHIP_CHECK (par->dimension == 2 || par->dimension == 3, GFSHIP_EINVAL, "dimension must be 2 or 3");
+  GFSHIP_CHECK_DIMENSION (dom, par->dimension);
   GFSHIP_CHECK (dom->unit_weights, GFSHIP_EINVAL, "call gfship_poisson_coefficients first");
   { int r = before_write (dom); if (r) return r; }
   int r;

@@ -136,7 +136,9 @@ int  gfship_poisson_coefficients (gfship_domain * dom);
    d = 0 .. 2 dim - 1. */
 int  gfship_poisson_coefficients_alpha (gfship_domain * dom, const gfship_field alpha[3]);
 int  gfship_poisson_weights (gfship_domain * dom, int d, gfship_field * w);
-/* gfs_relax, src/poisson.c:604-632: one in-place sweep of level `level` */
+/* gfs_relax, src/poisson.c:604-632: one in-place sweep of level `level`.  d (and the `dimension' of the
+   parameters of gfship_poisson_cycle / _solve) must be the dimension of the domain: GFSHIP_EUNSUPPORTED
+   otherwise (the reference's d = 2 on a 3-D domain, relax2D over four neighbours, is not implemented) */
 int  gfship_relax (gfship_domain * dom, unsigned d, int level, double omega,
 		   gfship_field u, gfship_field rhs, gfship_field dia);
 /* gfs_residual, src/poisson.c:721-747 */

@@ -40,6 +40,42 @@ def test_plans_of_a_tree_reproduce_the_sequential_program(name, kw):
     assert levels_loop <= levels_sweeps + 2 * nrelax * 8
 
 
+# relax loops of many sweeps: nrelax*erelax^(depth - l) sweeps on level l of a projection with erelax = 2,
+# 10*nrelax sweeps on the coarsest level of a diffusion cycle (src/poisson.c:1129-1160, 1505-1509)
+MANY_SWEEPS_TREES = [
+    ("quadtree 4/6", dict(refine=lambda x, y: 6 if inside(x, y) else 4)),
+    ("octree 3/4", dict(refine=lambda x, y, z: 4 if inside(x, y, z) else 3, dim=3)),
+    ("quadtree with GfsBoundary sides",
+     dict(refine=lambda x, y: 6 if x * x + y * y <= 0.0625 else 4, sides=[gfship.SIDE_BOUNDARY] * 4)),
+]
+
+
+@pytest.mark.parametrize("nrelax", [8, 16, 40])
+@pytest.mark.parametrize("name,kw", MANY_SWEEPS_TREES, ids=[c[0] for c in MANY_SWEEPS_TREES])
+def test_plans_of_loops_of_many_sweeps(name, kw, nrelax):
+    updates, levels_sweeps, levels_loop, differ = gfship.tree_host_check(nrelax=nrelax, **kw)
+    assert updates > 0 and levels_loop > 0
+    assert differ == 0
+    # the Poisson check adds the hazards of the flow plans to `differ' and is silent about a level without a
+    # flow plan; the diffusion check of the same tree and sweeps reports both, one by one
+    k = dict(kw)
+    stats = gfship.tree_host_check_diffusion(k["refine"], 0.37, dim=k.get("dim", 2), sides=k.get("sides"),
+                                             nrelax=nrelax)
+    assert stats[0] == updates
+    assert stats[3] == 0, "%d values differ" % stats[3]
+    assert stats[4] == 0 and stats[5] == 0, "hazards %d, levels without a flow plan %d" % stats[4:6]
+
+
+@pytest.mark.parametrize("name,kw", MANY_SWEEPS_TREES[:2], ids=[c[0] for c in MANY_SWEEPS_TREES[:2]])
+def test_diffusion_plans_of_forty_sweeps(name, kw):
+    """gfs_diffusion_cycle with nrelax = 4 on its coarsest level"""
+    k = dict(kw)
+    updates, levels, not_w, differ, hazards, no_flow = gfship.tree_host_check_diffusion(
+        k["refine"], 1e-3 / 3, dim=k.get("dim", 2), nrelax=40)
+    assert updates > 0 and levels > 0
+    assert differ == 0 and hazards == 0 and no_flow == 0 and not_w == 0
+
+
 def test_refinement_that_differs_across_a_periodic_side_is_refused():
     with pytest.raises(gfship.GfshipError, match="periodic side"):
         gfship.tree_host_check(lambda x, y: 5 if x > 0.25 else 4)
