@@ -437,6 +437,7 @@ static int key_bits (unsigned long long ncell)
 static int coupling_check (gfship_particles * pl, const char * what)
 {
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_NO_TREE_LIST (pl, what);
   GFSHIP_CHECK (pl->particulate, GFSHIP_EUNSUPPORTED,
 		"%s needs a list of particulates (gfship_particles_set_particulate)", what);
   GFSHIP_CHECK (!pl->dom->has_external, GFSHIP_EUNSUPPORTED,

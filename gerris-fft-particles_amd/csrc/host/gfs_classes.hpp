@@ -426,6 +426,7 @@ inline void read_particle_list (Run & R, Reader & r, Object & ob)
   R.plists.emplace_back (new ParticleSpec);
   ParticleSpec * ps = R.plists.back ().get ();
   ps->name = ename;
+  ps->line = ob.line;
   std::string item;
   if (r.peek (false) != '{') item = strip_gfs (r.word (false));
   Reader objects = block (r);
@@ -827,7 +828,8 @@ inline void read_output_location (Run & R, Reader & r, Object & ob)
   if (pts->size () % 3) r.fail ("expecting x y z triplets");
   if (r.peek (false) == '{') r.braces ();     /* label, precision: defaults only */
   auto first = std::make_shared<bool> (true);
-  ob.e->action = [&R, o, pts, first] () {
+  const int line = ob.line;
+  ob.e->action = [&R, o, pts, first, line] () {
     FILE * fp = o->open ();
     int np = (int) pts->size ()/3;
     if (*first) {
@@ -843,6 +845,16 @@ inline void read_output_location (Run & R, Reader & r, Object & ob)
     for (Variable & V : R.vars) {
       if (V.derive) continue;
       std::vector<double> out (np, 0.);
+      if (R.tree) {         /* a refined tree samples the variables it keeps on the device (GFSHIP_TREE_*) */
+        if (V.dev < 0) {
+          fprintf (stderr, "gfship: line %d: GfsOutputLocation: the variable `%s' is not kept on a refined tree\n",
+                   line, V.name.c_str ());
+          exit (1);
+        }
+        CHECK (gfship_tree_interpolate (R.tree, V.dev, np, pts->data (), out.data (), inside.data ()));
+        cols.push_back (out);
+        continue;
+      }
       gfship_field f = V.dev;
       gfship_field tmp = -1;
       if (f < 0) {          /* host-only variable: sample it through a scratch device field */
@@ -961,7 +973,8 @@ inline const ClassRow class_table[] = {
   { "VariableTracer", read_variable_tracer, 0 },          // { gradient = .. scheme = godunov | none }
   { "VariableStreamFunction", read_variable_stream_function, 0 },    // GfsAdvection
   { "EventStop", read_event_stop, EVENT | PARAMS | TREE },
-  { "ParticleList", read_particle_list, EVENT },          // of GfsParticle / GfsParticulate, with GfsForce*
+  { "ParticleList", read_particle_list, EVENT | TREE },   // of GfsParticle / GfsParticulate, with GfsForce*; on a
+                                                          //   tree: GfsParticle without forces (check_tree_simulation)
   { "ParticulateField", read_particulate_field, EVENT },  // on a list named `*NAME'
   { "SourceParticulate", read_particulate_field, EVENT },
   { "OutputEnergySpectra", read_output_energy_spectra, OUT },
@@ -976,7 +989,7 @@ inline const ClassRow class_table[] = {
   { "OutputScalarSum", read_output_scalar, OUT | ON_TREES },
   { "OutputScalarStats", read_output_scalar, OUT | ON_TREES },
   { "OutputErrorNorm", read_output_error_norm, OUT | ON_TREES },
-  { "OutputLocation", read_output_location, OUT },
+  { "OutputLocation", read_output_location, OUT | TREE }, // on a tree: gfship_tree_interpolate
   { "OutputSimulation", read_output_simulation, OUT | TREE | TREE_POISSON_SKIP },    // gfs (text or binary), text
   { "OutputPPM", read_not_produced, 0 },
   { "OutputGRD", read_not_produced, 0 },

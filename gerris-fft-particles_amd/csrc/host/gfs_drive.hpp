@@ -478,7 +478,12 @@ inline int check_tree_simulation (Run & R)
     if (tr.gradient > 1) return refuse ("this gradient of a GfsVariableTracer");
   for (const TracerSpec & tr : R.tracers)
     if (tr.scheme != GFSHIP_SCHEME_GODUNOV) return refuse ("GfsVariableTracer { scheme = none }");
-  if (!R.plists.empty ()) return refuse ("a particle list");
+  for (auto & ps : R.plists)      /* tracers only: no particulates, no forces (gfship_particles_create_tree) */
+    if (ps->particulate || !ps->forces.empty ()) {
+      fprintf (stderr, "gfship: line %d: a GfsParticleList of GfsParticulate objects or with GfsForce objects is not "
+               "supported on a refined tree (GfsParticle tracers are)\n", ps->line);
+      return 1;
+    }
   if (!R.init_spectra.empty ()) return refuse ("GfsInitSpectra");
   if (!R.device_vars.empty ()) return refuse ("a turbulent-viscosity variable");
   if (R.dtmax != DBL_MAX) return refuse ("Time { dtmax }");
@@ -547,6 +552,8 @@ inline int create_tree (Run & R, TreeFlags & flag)
   return 0;
 }
 
+inline int write_particles (Run & R);
+
 // simulation_run (src/simulation.c:432-557) on a statically refined tree
 inline int run_tree (Run & R)
 {
@@ -599,6 +606,8 @@ inline int run_tree (Run & R)
     }
   apply_multilevel (gfship_tree_projection_params (R.tree, 0), R.proj_set);
   apply_multilevel (gfship_tree_projection_params (R.tree, 1), R.approx_set);
+  for (auto & ps : R.plists)      /* the lists of tracers: read before any GfsInit event runs, as on a uniform box */
+    CHECK (gfship_particles_create_tree (&ps->pl, R.tree, (int) ps->id.size (), ps->pos.data (), ps->id.data ()));
   double cfl = 0.8;        /* gfs_advection_params_init, src/advection.c:922-942 */
   for (auto & kv : R.adv_set)
     if (kv.first == "cfl") cfl = atof (kv.second.c_str ());
@@ -632,6 +641,8 @@ inline int run_tree (Run & R)
     R.i = gfship_tree_iter (R.tree);
   }
   events_do (R);
+  if (!R.particles_out.empty () && write_particles (R)) return 1;
+  for (auto & ps : R.plists) gfship_particles_destroy (ps->pl);
   for (auto & o : R.outputs) o->close ();
   gfship_tree_destroy (R.tree);
   R.tree = nullptr;

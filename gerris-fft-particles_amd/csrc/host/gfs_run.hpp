@@ -162,6 +162,7 @@ struct ParticleSpec {
   std::vector<int> forces;                       // GFSHIP_FORCE_* in file order
   std::vector<std::string> force_functions;      // the GfsFunction of a GfsForceCoeff ("" = none)
   std::string name;                              // the optional `*name' of the event (gfs_event_read, src/event.c:198-203)
+  int line = 0;                                  // of the GfsParticleList in the file
   gfship_particles * pl = nullptr;
 };
 

@@ -155,32 +155,6 @@ __device__ double interpolate (const Layout & L, const double * __restrict__ v, 
 	  c[7])/8.;
 }
 
-// check_intersetion, modules/particulatecommon.c:3058-3146
-template <int DIM>
-__device__ bool check_intersection (const double cellpos[3], const double p0[3], const double p1[3],
-				    int * dstore, double size)
-{
-  for (int d = 0; d < 2*DIM; d++) {
-    double normal = (double) (d ^ 1) - (double) d;
-    int c = d/2;
-    if ((p1[c] - p0[c]) != 0 && normal*(p1[c] - p0[c]) > 0) {
-      double t = (cellpos[c] + normal*size*0.5 - p0[c])/(p1[c] - p0[c]);
-      bool inside = true;
-      for (int a = 0; a < DIM; a++)
-	if (a != c) {
-	  double pa = p0[a] + t*(p1[a] - p0[a]);
-	  if (!((pa - cellpos[a] + size*0.5)*(pa - cellpos[a] - size*0.5) <= 0))
-	    inside = false;
-	}
-      if (inside && t*(t - 1) <= 0) {
-	*dstore = d;
-	return true;
-      }
-    }
-  }
-  return false;
-}
-
 // gfs_particle_bc, modules/particulatecommon.c:3326-3395: a particle that left the box is taken
 // off the list (or marked for the box across a GfsBoundaryMpi side) unless a periodic side puts it
 // back; stores the position
@@ -699,6 +673,18 @@ int gfship_particles_create (gfship_particles ** out, gfship_sim * sim, int np,
   gfship_particles * pl = new gfship_particles;
   pl->sim = sim;
   pl->dom = gfship_sim_view_get (sim).dom;
+  pl->stream = pl->dom->stream;
+  pl->dim = pl->dom->dim;
+  int r = gfship::particles_alloc (pl, np, pos, id);
+  if (r) return r;
+  *out = pl;
+  return GFSHIP_OK;
+}
+
+} // extern "C"
+
+int gfship::particles_alloc (gfship_particles * pl, int np, const double * pos, const unsigned * id)
+{
   pl->n = np;
   pl->np0 = np;
   pl->cap = std::max (np, 1);
@@ -729,14 +715,15 @@ int gfship_particles_create (gfship_particles ** out, gfship_sim * sim, int np,
     std::iota (iota.begin (), iota.end (), 0u);
     GFSHIP_HIP (hipMemcpy (pl->orig, iota.data (), m*sizeof (unsigned), hipMemcpyHostToDevice));
   }
-  *out = pl;
   return GFSHIP_OK;
 }
+
+extern "C" {
 
 void gfship_particles_destroy (gfship_particles * pl)
 {
   if (!pl) return;
-  (void) hipStreamSynchronize (pl->dom->stream);
+  (void) hipStreamSynchronize (pl->stream);
   for (int c = 0; c < 3; c++) {
     if (pl->pos[c]) (void) hipFree (pl->pos[c]);
     if (pl->old[c]) (void) hipFree (pl->old[c]);
@@ -755,7 +742,7 @@ void gfship_particles_destroy (gfship_particles * pl)
   for (int c = 0; c < 3; c++) {
     if (pl->vel[c]) (void) hipFree (pl->vel[c]);
     if (pl->force[c]) (void) hipFree (pl->force[c]);
-    if (pl->uold[c] >= 0) gfship_field_free (pl->dom, pl->uold[c]);
+    if (pl->uold[c] >= 0 && pl->dom) gfship_field_free (pl->dom, pl->uold[c]);
   }
   if (pl->mass) (void) hipFree (pl->mass);
   if (pl->volume) (void) hipFree (pl->volume);
@@ -821,32 +808,40 @@ int gfship_particles_sort (gfship_particles * pl)
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
   if (pl->n == 0) return GFSHIP_OK;
   gfship_domain * dom = pl->dom;
-  const Layout & L = dom->lay[dom->depth];
+  hipStream_t stream = pl->stream;
   int block = 256, grid = (pl->n + block - 1)/block;
-  if (dom->dim == 3)
-    hipLaunchKernelGGL (particle_keys_kernel<3>, dim3 (grid), dim3 (block), 0, dom->stream, L,
-			dom->depth, pl->n, pl->pos[0], pl->pos[1], pl->pos[2], pl->alive, pl->key,
-			pl->slot);
-  else
-    hipLaunchKernelGGL (particle_keys_kernel<2>, dim3 (grid), dim3 (block), 0, dom->stream, L,
-			dom->depth, pl->n, pl->pos[0], pl->pos[1], pl->pos[2], pl->alive, pl->key,
-			pl->slot);
-  GFSHIP_HIP (hipGetLastError ());
+  int bits;
+  if (pl->tree) {      /* key = the leaf in the concatenated levels of the tree */
+    int r = gfship::tree_particle_keys (pl, &bits);
+    if (r) return r;
+  }
+  else {
+    const Layout & L = dom->lay[dom->depth];
+    if (dom->dim == 3)
+      hipLaunchKernelGGL (particle_keys_kernel<3>, dim3 (grid), dim3 (block), 0, dom->stream, L,
+			  dom->depth, pl->n, pl->pos[0], pl->pos[1], pl->pos[2], pl->alive, pl->key,
+			  pl->slot);
+    else
+      hipLaunchKernelGGL (particle_keys_kernel<2>, dim3 (grid), dim3 (block), 0, dom->stream, L,
+			  dom->depth, pl->n, pl->pos[0], pl->pos[1], pl->pos[2], pl->alive, pl->key,
+			  pl->slot);
+    GFSHIP_HIP (hipGetLastError ());
+    /* the key needs dim*depth bits (+1 so that the all-ones key of the dead sorts last) */
+    bits = dom->dim*dom->depth + 1;
+  }
   size_t need = 0;
   GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (nullptr, need, pl->key, pl->key2, pl->slot,
-						  pl->slot2, pl->n, 0, 32, dom->stream));
+						  pl->slot2, pl->n, 0, 32, stream));
   if (need > pl->sort_tmp_bytes) {
     if (pl->sort_tmp) GFSHIP_HIP (hipFree (pl->sort_tmp));
     pl->sort_tmp = nullptr;
     GFSHIP_HIP (hipMalloc (&pl->sort_tmp, need));
     pl->sort_tmp_bytes = need;
   }
-  /* the key needs dim*depth bits (+1 so that the all-ones key of the dead sorts last) */
-  int bits = dom->dim*dom->depth + 1;
   if (bits > 32) bits = 32;
   size_t tmp_bytes = pl->sort_tmp_bytes;
   GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (pl->sort_tmp, tmp_bytes, pl->key, pl->key2,
-						  pl->slot, pl->slot2, pl->n, 0, bits, dom->stream));
+						  pl->slot, pl->slot2, pl->n, 0, bits, stream));
   GatherArgs G;
   G.n = pl->n;
   G.slot = pl->slot2;
@@ -856,7 +851,7 @@ int gfship_particles_sort (gfship_particles * pl)
   }
   G.id = pl->id; G.orig = pl->orig; G.alive = pl->alive;
   G.id2 = pl->id2; G.orig2 = pl->orig2; G.alive2 = pl->alive2;
-  hipLaunchKernelGGL (particle_gather_kernel, dim3 (grid), dim3 (block), 0, dom->stream, G);
+  hipLaunchKernelGGL (particle_gather_kernel, dim3 (grid), dim3 (block), 0, stream, G);
   GFSHIP_HIP (hipGetLastError ());
   for (int c = 0; c < 3; c++) {
     std::swap (pl->pos[c], pl->pos2[c]);
@@ -1021,6 +1016,7 @@ static int particles_migrate (gfship_particles * pl)
 int gfship_particles_set_migrate (gfship_particles * pl, gfship_particle_migrate_fn fn, void * ctx)
 {
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_set_migrate");
   pl->migrate = fn;
   pl->migrate_ctx = ctx;
   return GFSHIP_OK;
@@ -1029,6 +1025,7 @@ int gfship_particles_set_migrate (gfship_particles * pl, gfship_particle_migrate
 int gfship_particles_record_size (gfship_particles * pl)
 {
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_record_size");
   return pl->particulate ? 15 : 7;
 }
 
@@ -1167,6 +1164,7 @@ int gfship_particles_set_particulate (gfship_particles * pl, const double * vel,
 				      const double * volume)
 {
   GFSHIP_CHECK (pl && vel && mass && volume, GFSHIP_EINVAL, "null argument");
+  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_set_particulate");
   GFSHIP_CHECK (!pl->particulate, GFSHIP_EINVAL, "the list already holds particulates");
   size_t m = (size_t) pl->cap, np = (size_t) pl->n;
   GFSHIP_CHECK (pl->n == pl->np0, GFSHIP_EINVAL, "set the particulate state before the first migration");
@@ -1205,6 +1203,7 @@ int gfship_particles_set_forces (gfship_particles * pl, int nforces, const int *
 				 const double gravity[3])
 {
   GFSHIP_CHECK (pl && (nforces == 0 || kinds), GFSHIP_EINVAL, "null argument");
+  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_set_forces");
   GFSHIP_CHECK (pl->particulate, GFSHIP_EINVAL, "forces act on particulates (gfship_particles_set_particulate)");
   GFSHIP_CHECK (nforces >= 0 && nforces <= 8, GFSHIP_EINVAL, "at most 8 forces");
   if (nforces > 0) {
@@ -1244,6 +1243,7 @@ int gfship_particles_set_forces (gfship_particles * pl, int nforces, const int *
 int gfship_particles_set_force_coefficient (gfship_particles * pl, int force, const char * function)
 {
   GFSHIP_CHECK (pl && function, GFSHIP_EINVAL, "null argument");
+  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_set_force_coefficient");
   GFSHIP_CHECK (force >= 0 && force < pl->nforces, GFSHIP_EINVAL,
 		"force %d: the list has %d forces (gfship_particles_set_forces)", force, pl->nforces);
   GFSHIP_CHECK (pl->forces[force] == GFSHIP_FORCE_ADDEDMASS || pl->forces[force] == GFSHIP_FORCE_LIFT ||
@@ -1261,7 +1261,9 @@ int gfship_particles_set_force_coefficient (gfship_particles * pl, int force, co
 int gfship_particles_download_particulate (gfship_particles * pl, double * vel, double * mass,
 					   double * force)
 {
-  GFSHIP_CHECK (pl && pl->particulate, GFSHIP_EINVAL, "not a list of particulates");
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_download_particulate");
+  GFSHIP_CHECK (pl->particulate, GFSHIP_EINVAL, "not a list of particulates");
   if (pl->n == 0) return 0;
   gfship_domain * dom = pl->dom;
   GFSHIP_HIP (hipStreamSynchronize (dom->stream));
@@ -1295,6 +1297,17 @@ int gfship_particles_download_particulate (gfship_particles * pl, double * vel, 
 int gfship_particle_list_event (gfship_particles * pl)
 {
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  if (pl->tree) {
+    if (pl->n == 0) return GFSHIP_OK;
+    if (pl->sort_every > 0 &&
+	(pl->events_since_sort < 0 || pl->events_since_sort >= pl->sort_every)) {
+      int r = gfship_particles_sort (pl);
+      if (r) return r;
+    }
+    if (pl->events_since_sort >= 0)
+      pl->events_since_sort++;
+    return gfship::tree_particle_list_event (pl);
+  }
   const bool migrates = pl->migrate != nullptr || (pl->dom->comm && pl->dom->has_external);
   if (pl->n == 0 && !migrates) return GFSHIP_OK;
   if (pl->sort_every > 0 &&
@@ -1345,6 +1358,7 @@ int gfship_particle_list_event (gfship_particles * pl)
 int gfship_particles_forces_on_fluid (gfship_particles * pl)
 {
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_forces_on_fluid");
   GFSHIP_CHECK (pl->particulate, GFSHIP_EUNSUPPORTED,
 		"the forces on the fluid are those of particulates (gfship_particles_set_particulate)");
   gfship_sim_view v = gfship_sim_view_get (pl->sim);
@@ -1374,14 +1388,14 @@ int gfship_particles_count (gfship_particles * pl)
 {
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
   if (pl->n == 0) return 0;
-  gfship_domain * dom = pl->dom;
-  GFSHIP_HIP (hipMemsetAsync (pl->d_count, 0, sizeof (unsigned), dom->stream));
+  hipStream_t stream = pl->stream;
+  GFSHIP_HIP (hipMemsetAsync (pl->d_count, 0, sizeof (unsigned), stream));
   int block = 256, grid = (pl->n + block - 1)/block;
-  hipLaunchKernelGGL (count_alive_kernel, dim3 (grid), dim3 (block), 0, dom->stream,
+  hipLaunchKernelGGL (count_alive_kernel, dim3 (grid), dim3 (block), 0, stream,
 		      pl->alive, pl->n, pl->d_count);
   unsigned c = 0;
-  GFSHIP_HIP (hipMemcpyAsync (&c, pl->d_count, sizeof (unsigned), hipMemcpyDeviceToHost, dom->stream));
-  GFSHIP_HIP (hipStreamSynchronize (dom->stream));
+  GFSHIP_HIP (hipMemcpyAsync (&c, pl->d_count, sizeof (unsigned), hipMemcpyDeviceToHost, stream));
+  GFSHIP_HIP (hipStreamSynchronize (stream));
   return (int) c;
 }
 
@@ -1390,8 +1404,7 @@ int gfship_particles_count (gfship_particles * pl)
 static int particles_download (gfship_particles * pl, double * const src[3], double * pos, unsigned * id)
 {
   if (pl->n == 0) return 0;
-  gfship_domain * dom = pl->dom;
-  GFSHIP_HIP (hipStreamSynchronize (dom->stream));
+  GFSHIP_HIP (hipStreamSynchronize (pl->stream));
   size_t m = pl->n;
   std::vector<double> x (m), y (m), z (m);
   std::vector<unsigned> ids (m), orig (m), where (m);
@@ -1409,7 +1422,7 @@ static int particles_download (gfship_particles * pl, double * const src[3], dou
     size_t q = where[o];
     if (al[q] == 1) {
       pos[3*(size_t) k] = x[q]; pos[3*(size_t) k + 1] = y[q];
-      pos[3*(size_t) k + 2] = dom->dim == 3 ? z[q] : 0.;
+      pos[3*(size_t) k + 2] = pl->dim == 3 ? z[q] : 0.;
       if (id) id[k] = ids[q];
       k++;
     }

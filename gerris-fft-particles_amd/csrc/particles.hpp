@@ -19,6 +19,9 @@ int  rtc_launch_spatial (RtcKernel * k, hipStream_t stream, long nrec, int strid
 struct gfship_particles {
   gfship_sim * sim = nullptr;
   gfship_domain * dom = nullptr;
+  gfship_tree * tree = nullptr;       // a list of GfsParticle on a refined tree (tree_particles.hip): sim, dom = nullptr
+  hipStream_t stream = nullptr;       // the stream of dom or of tree
+  int dim = 0;
   int n = 0;                   // slots in use (alive or not)
   int cap = 0;                 // slots allocated
   double * pos[3] = {}, * old[3] = {};
@@ -81,7 +84,17 @@ namespace gfship {
 // the refusals of every entry that evaluates the forces of a list (particles.hip)
 int particulate_fluid_check (const gfship_sim_view & v);
 void coupling_free (gfship_particles * pl);   // coupling.hip
+// the per-particle arrays of a new list of np tracers (particles.hip); pl->stream is set by the caller
+int particles_alloc (gfship_particles * pl, int np, const double * pos, const unsigned * id);
+// a list on a tree (tree_particles.hip): the event of its tracers, the keys of gfship_particles_sort and their bits
+int tree_particle_list_event (gfship_particles * pl);
+int tree_particle_keys (gfship_particles * pl, int * bits);
 }
+
+// particulates, forces, coupling and migration exist on uniform boxes only
+#define GFSHIP_NO_TREE_LIST(pl, what) GFSHIP_CHECK (!(pl)->tree, GFSHIP_EUNSUPPORTED, \
+    "%s: a particle list on a refined tree holds GfsParticle tracers only (no particulates, forces, " \
+    "coupling or migration)", what)
 
 namespace gfship {
 
@@ -107,6 +120,32 @@ __device__ __forceinline__ bool locate (int depth, const double target[3], int i
   }
   ijk[0] = q[0] + 1; ijk[1] = q[1] + 1; ijk[2] = DIM == 3 ? q[2] + 1 : 0;
   return true;
+}
+
+// check_intersetion, modules/particulatecommon.c:3058-3146
+template <int DIM>
+__device__ bool check_intersection (const double cellpos[3], const double p0[3], const double p1[3],
+				    int * dstore, double size)
+{
+  for (int d = 0; d < 2*DIM; d++) {
+    double normal = (double) (d ^ 1) - (double) d;
+    int c = d/2;
+    if ((p1[c] - p0[c]) != 0 && normal*(p1[c] - p0[c]) > 0) {
+      double t = (cellpos[c] + normal*size*0.5 - p0[c])/(p1[c] - p0[c]);
+      bool inside = true;
+      for (int a = 0; a < DIM; a++)
+	if (a != c) {
+	  double pa = p0[a] + t*(p1[a] - p0[a]);
+	  if (!((pa - cellpos[a] + size*0.5)*(pa - cellpos[a] - size*0.5) <= 0))
+	    inside = false;
+	}
+      if (inside && t*(t - 1) <= 0) {
+	*dstore = d;
+	return true;
+      }
+    }
+  }
+  return false;
 }
 
 } // namespace gfship

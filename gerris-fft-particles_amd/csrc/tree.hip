@@ -27,6 +27,7 @@
 #include "gfship_internal.hpp"
 #include "cell_loop.hpp"
 #include "tree.hpp"
+#include "tree_particles.hpp"
 #include <algorithm>
 #include <array>
 #include <cfloat>
@@ -166,6 +167,9 @@ struct gfship_tree {
   unsigned long long * snap_off = nullptr;
   unsigned long long snap_records = 0;
   bool restarted = false;           // gfship_tree_restart with i > 0: gfship_tree_start takes the branch time.i > 0
+  // the corner interpolators of the point sampler and of the tracers (tree_particles.hip), built on first use
+  void * sampler = nullptr;
+  void (* sampler_free) (void *) = nullptr;
 };
 
 namespace {
@@ -2695,6 +2699,7 @@ int snapshot_vars (gfship_tree * tr, int nvars, const int * vars, SnapVars * V)
 void tree_free (gfship_tree * tr)
 {
   if (!tr) return;
+  if (tr->sampler && tr->sampler_free) tr->sampler_free (tr->sampler);
   snapshot_tables_free (tr);
   (void) hipFree (tr->dflag);
   (void) hipFree (tr->d_nbtab); (void) hipFree (tr->d_child0); (void) hipFree (tr->d_cmask); (void) hipFree (tr->d_idtab);
@@ -2717,6 +2722,25 @@ void tree_free (gfship_tree * tr)
 }
 
 } // namespace
+
+// ---- what tree_particles.hip sees of a tree --------------------------------------------------------
+
+void gfship::tree_view (gfship_tree * tr, gfship::TreeView * v)
+{
+  v->H = tr->H; v->D = tr->D;
+  v->stream = tr->stream;
+  v->device = tr->device; v->ncell = tr->ncell; v->nleaves = tr->nleaves;
+  v->hleaves = tr->hleaves.data ();
+  v->side = tr->side;
+  v->dt = tr->dt;
+  v->sampler = &tr->sampler;
+  v->sampler_free = &tr->sampler_free;
+}
+
+double * gfship::tree_variable (gfship_tree * tr, int var)
+{
+  return var >= 0 && var < abi_nvar ? tr->var[abi_var[var]] : nullptr;
+}
 
 // ---- C ABI -------------------------------------------------------------------------------------
 

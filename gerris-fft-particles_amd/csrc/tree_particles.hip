@@ -1,0 +1,778 @@
+// tree_particles.hip -- the point sampler (GfsOutputLocation) and the Lagrangian tracers (GfsParticle in a
+// GfsParticleList) on a statically refined quadtree / octree.
+//
+// One thread per point or particle.  locate = the descent of ftt_cell_locate (src/ftt.c:1535-1574) over the tables
+// of the tree (cmask, child0) to the leaf that holds the point; interpolate = gfs_interpolate (src/fluid.c:2697-2710).
+// On a refined tree the cells of a corner are found by a walk (do_path, :2925-2981) that meets coarser
+// neighbours, deeper neighbours and T-junctions (cell_corner_neighbor, :2813-2846; t_junction_interpolator,
+// :2879-2923, which calls gfs_cell_corner_interpolator of the coarse neighbour again).  The tree is static: that
+// walk is done ONCE on the host (Walker below), in the reference's order of operations, and its result is kept as
+// rows of (cell, weight) pairs, CSR, keyed by (leaf, corner).  The device sums weight * value along a row, in row
+// order (gfs_cell_corner_value, :3081-3101).
+//
+// A corner whose walk finds exactly the cells of the uniform box -- the 2^dim cells of the leaf's own level around
+// the corner, those with two or more coordinates in the ghost layer absent -- needs no row: all its weights are
+// equal and the kernel does the arithmetic of particles.hip (interpolate ()).  A byte per cell of
+// the dense levels says which corners of a leaf read the table, an int where the rows of the leaf start.
+//
+// Pinned bit for bit on tests/tree_sampler_reference.py (a restatement of the reference on explicit cell trees,
+// written from the reference) in tests/test_gpu_tree_sampler.py.
+#include "particles.hpp"
+#include "tree_particles.hpp"
+#include <vector>
+
+namespace gfship {
+
+using tree::Topo;
+using tree::Cell;
+using tree::exists;
+
+namespace {
+
+// GfsInterpolator (src/fluid.h): at most 7 cells in 2-D, 29 in 3-D (g_assert of interpolator_merge, :2861-2863)
+constexpr int INTER_MAX = 29;
+struct Inter { int n; int c[INTER_MAX + 3]; double w[INTER_MAX + 3]; };
+
+struct SamplerTables {       // device
+  unsigned char * corner_bits = nullptr;     // [cell]: bit ic = corner ic of the leaf reads its row of the table
+  int * row_base = nullptr;                  // [cell]: the first row of the leaf (its corners with a bit, in order)
+  int * row_ptr = nullptr;                   // [rows + 1]
+  int * col = nullptr;                       // [entries]: Topo::gi of the cell
+  double * w = nullptr;                      // [entries]
+  long long stats[5] = { 0, 0, 0, 0, 0 };
+};
+
+void sampler_tables_free (void * p)
+{
+  SamplerTables * S = (SamplerTables *) p;
+  (void) hipFree (S->corner_bits); (void) hipFree (S->row_base); (void) hipFree (S->row_ptr);
+  (void) hipFree (S->col); (void) hipFree (S->w);
+  delete S;
+}
+
+// corner[i], src/fluid.c:2588-2605
+const int corner2[4][3] = { {1, 3, -1}, {0, 3, -1}, {0, 2, -1}, {1, 2, -1} };
+const int corner3[8][3] = { {1, 3, 4}, {0, 3, 4}, {0, 2, 4}, {1, 2, 4}, {1, 3, 5}, {0, 3, 5}, {0, 2, 5}, {1, 2, 5} };
+// path[i][j], src/fluid.c:2938-2954
+const int path2[4][2][3] = { {{1,2,1}, {2,1,2}}, {{2,-1,3}, {-1,2,0}}, {{1,-2,3}, {-2,1,0}}, {{-1,-2,2}, {-2,-1,1}} };
+const int path3[8][3][4] = {
+  {{1,2,3,1},    {2,1,3,2},    {3,1,2,4}},
+  {{2,3,-1,3},   {3,2,-1,5},   {-1,2,3,0}},
+  {{1,-2,3,3},   {3,-2,1,6},   {-2,3,1,0}},
+  {{3,-1,-2,7},  {-2,-1,3,1},  {-1,-2,3,2}},
+  {{2,1,-3,6},   {1,2,-3,5},   {-3,1,2,0}},
+  {{2,-1,-3,7},  {-1,2,-3,4},  {-3,2,-1,1}},
+  {{1,-2,-3,7},  {-2,1,-3,4},  {-3,1,-2,2}},
+  {{-1,-2,-3,6}, {-2,-1,-3,5}, {-3,-1,-2,3}} };
+// b[FTT_CELL_ID][d] of ftt_cell_neighbor_is_brother, src/ftt.h:624-631
+const int brother2[4][4] = { {1,0,0,1}, {0,1,0,1}, {1,0,1,0}, {0,1,1,0} };
+const int brother3[8][6] = { {1,0,0,1,0,1}, {0,1,0,1,0,1}, {1,0,1,0,0,1}, {0,1,1,0,0,1},
+			     {1,0,0,1,1,0}, {0,1,0,1,1,0}, {1,0,1,0,1,0}, {0,1,1,0,1,0} };
+
+// gfs_cell_corner_interpolator (src/fluid.c:3015-3069) and what it calls, max_level = -1, centered, no solid
+struct Walker {
+  const Topo & T;
+  bool overflow = false;
+  explicit Walker (const Topo & t) : T (t) {}
+
+  // cells with two or three coordinates in the ghost layer do not exist in the reference (every side has a cell
+  // tree of its own whose root knows the box and nothing else, src/boundary.c:652-685)
+  int ghost_coordinates (Cell c) const {
+    const int n = T.n (c.l), i = T.ci (c), j = T.cj (c), k = T.ck (c);
+    return (i < 1 || i > n) + (j < 1 || j > n) + (T.dim == 3 && (k < 1 || k > n));
+  }
+  Cell absent_if_edge (Cell c) const {
+    if (exists (c) && ghost_coordinates (c) > 1) c.q = -1;
+    return c;
+  }
+  Cell neighbor (Cell c, int d) const { return absent_if_edge (T.neighbor (c, d)); }
+  Cell child_corner (Cell c, const int d[3]) const { return absent_if_edge (T.child_corner (c, d[0], d[1], d[2])); }
+  Cell parent (Cell c) const { return T.make (c.l - 1, (T.ci (c) + 1)/2, (T.cj (c) + 1)/2, T.dim == 3 ? (T.ck (c) + 1)/2 : 1); }
+  bool boundary (Cell c) const { return !T.interior (c); }          /* GFS_CELL_IS_BOUNDARY */
+  bool neighbor_is_brother (Cell c, int d) const {                  /* src/ftt.h:620-638 */
+    if (c.l == 0) return false;
+    return T.dim == 2 ? brother2[T.id (c)][d] : brother3[T.id (c)][d];
+  }
+
+  // cell_corner_neighbor, :2813-2846
+  Cell corner_neighbor (Cell cell, const int d[3], bool & t_junction) const {
+    const Cell nb = neighbor (cell, d[0]);
+    if (!exists (nb))
+      return nb;
+    if (nb.l < cell.l) {               /* neighbor is at a shallower level */
+      const Cell cc = child_corner (parent (cell), d);
+      if (!(cc.l == cell.l && cc.q == cell.q))
+	t_junction = true;
+      return nb;
+    }
+    if (T.leaf (nb))
+      return nb;
+    const int d1[3] = { d[0] ^ 1, d[1], d[2] };      /* neighbor is at a deeper level */
+    const Cell n = child_corner (nb, d1);
+    return exists (n) ? n : nb;
+  }
+
+  // interpolator_merge, :2848-2870
+  void merge (Inter & a, const Inter & b) {
+    for (int i = 0; i < b.n; i++) {
+      int j = 0;
+      while (j < a.n && b.c[i] != a.c[j]) j++;
+      if (j < a.n)
+	a.w[j] += b.w[i];
+      else {
+	if (j >= (T.dim == 2 ? 7 : INTER_MAX)) { overflow = true; return; }
+	a.c[j] = b.c[i];
+	a.w[j] = b.w[i];
+	a.n++;
+      }
+    }
+  }
+  static void scale (Inter & a, double b) { for (int i = 0; i < a.n; i++) a.w[i] *= b; }
+
+  // t_junction_interpolator, :2879-2923
+  void t_junction (Cell cell, const int d[3], Cell n, Inter & inter) {
+    int d1[3] = { d[0] ^ 1, d[1], d[2] };
+    Inter a;
+    if (T.dim == 2) {
+      corner_interpolator (n, d1, inter);
+      d1[1] = d[1] ^ 1;
+      corner_interpolator (n, d1, a);
+      merge (inter, a);
+      scale (inter, 0.5);
+      return;
+    }
+    corner_interpolator (n, d1, inter);
+    if (neighbor_is_brother (cell, d[1])) {
+      d1[1] = d[1] ^ 1;
+      corner_interpolator (n, d1, a);
+      merge (inter, a);
+      if (neighbor_is_brother (cell, d[2])) {
+	d1[2] = d[2] ^ 1;
+	corner_interpolator (n, d1, a);
+	merge (inter, a);
+	d1[1] = d[1];
+	corner_interpolator (n, d1, a);
+	merge (inter, a);
+	scale (inter, 0.25);
+      }
+      else
+	scale (inter, 0.5);
+    }
+    else {
+      d1[2] = d[2] ^ 1;
+      corner_interpolator (n, d1, a);
+      merge (inter, a);
+      scale (inter, 0.5);
+    }
+  }
+
+  // do_path, :2925-2981
+  bool do_path (Cell cell, int i, Cell n[8], const int d[3], Inter & inter) {
+    for (int j = 0; j < T.dim; j++) {
+      const int * P = T.dim == 2 ? path2[i][j] : path3[i][j];
+      const int k = P[T.dim];
+      if (!exists (n[k])) {
+	bool tj = false;
+	int d1[3] = { -1, -1, -1 };
+	for (int l = 0; l < T.dim; l++)
+	  d1[l] = P[l] < 0 ? (d[- P[l] - 1] ^ 1) : d[P[l] - 1];
+	n[k] = corner_neighbor (cell, d1, tj);
+	if (tj) {
+	  t_junction (cell, d1, n[k], inter);
+	  return true;
+	}
+	if (exists (n[k]) && do_path (n[k], k, n, d, inter))
+	  return true;
+      }
+    }
+    return false;
+  }
+
+  // gfs_cell_corner_interpolator, :3015-3069; n_out (optional): the cells of the walk when it met no T-junction
+  bool corner_interpolator (Cell cell, const int d[3], Inter & inter, Cell * n_out = nullptr) {
+    Cell n[8];
+    while (!T.leaf (cell)) {           /* :3028-3031 */
+      const Cell ch = child_corner (cell, d);
+      if (!exists (ch)) break;
+      cell = ch;
+    }
+    n[0] = cell;
+    for (int i = 1; i < T.nc (); i++) n[i].l = 0, n[i].q = -1;
+    inter.n = 0;
+    if (do_path (cell, 0, n, d, inter))
+      return true;
+    double w = 0.;
+    int boundaries = 0;
+    inter.n = 0;
+    for (int i = 0; i < T.nc (); i++)
+      if (exists (n[i])) {
+	/* distance (), :2983-2992 */
+	const double a = 1./(T.size (n[i])*(T.dim == 2 ? 0.707106781185 : 0.866025403785) + 1e-12);
+	inter.c[inter.n] = T.gi (n[i]);
+	inter.w[inter.n++] = a;
+	w += a;
+	if (boundary (n[i]))
+	  boundaries++;
+      }
+    if (inter.n == T.dim + 1 && boundaries == T.dim) {   /* corners of domain, :3057-3065 */
+      w -= inter.w[0];
+      for (int i = 0; i < inter.n - 1; i++) {
+	inter.c[i] = inter.c[i + 1];
+	inter.w[i] = inter.w[i + 1];
+      }
+      inter.n--;
+    }
+    scale (inter, 1./w);
+    if (n_out)
+      for (int i = 0; i < T.nc (); i++) n_out[i] = n[i];
+    return false;
+  }
+
+  // does the walk of this corner of a leaf give what the arithmetic of the uniform box gives?  The cells of the
+  // leaf's level at the 2^dim offsets towards the corner, present exactly where at most one coordinate is in the
+  // ghost layer.  (Then all sizes are equal and so are the weights, the sums and the domain-corner rule.)
+  bool uniform_corner (Cell leaf, const int d[3], const Cell n[8]) const {
+    const int r = T.r (leaf.l), nn = T.n (leaf.l);
+    const int ijk[3] = { T.ci (leaf), T.cj (leaf), T.dim == 3 ? T.ck (leaf) : 1 };
+    const int sg[3] = { d[0] == 0 ? 1 : -1, d[1] == 2 ? 1 : -1, d[2] == 4 ? 1 : -1 };
+    for (int m = 0; m < T.nc (); m++) {
+      int out = 0, p[3];
+      for (int a = 0; a < 3; a++) {
+	p[a] = ijk[a] + (a < T.dim && (m & (1 << a)) ? sg[a] : 0);
+	if (a < T.dim && (p[a] < 1 || p[a] > nn)) out++;
+      }
+      const int q = p[0] + r*(p[1] + (T.dim == 3 ? r*p[2] : 0));
+      if (out <= 1) {
+	if (!(exists (n[m]) && n[m].l == leaf.l && n[m].q == q)) return false;
+      }
+      else if (exists (n[m]))
+	return false;
+    }
+    return true;
+  }
+};
+
+int sampler_build (gfship_tree * tr, const TreeView & V, SamplerTables ** out)
+{
+  (void) tr;
+  const Topo & T = V.H;
+  const int nc = T.nc ();
+  std::vector<unsigned char> bits (V.ncell, 0);
+  std::vector<int> base (V.ncell, 0), ptr (1, 0), col;
+  std::vector<double> w;
+  Walker W (T);
+  int longest = 0;
+  for (int t = 0; t < V.nleaves; t++) {
+    const Cell leaf = V.hleaves[t];
+    const int g = T.gi (leaf);
+    base[g] = (int) ptr.size () - 1;
+    for (int ic = 0; ic < nc; ic++) {
+      const int * d = T.dim == 2 ? corner2[ic] : corner3[ic];
+      Inter I;
+      Cell n[8];
+      const bool tj = W.corner_interpolator (leaf, d, I, n);
+      GFSHIP_CHECK (!W.overflow && I.n <= (T.dim == 2 ? 7 : INTER_MAX), GFSHIP_EUNSUPPORTED,
+		    "a corner interpolator of this tree has more than %d cells (GfsInterpolator, src/fluid.h)",
+		    T.dim == 2 ? 7 : INTER_MAX);
+      if (!tj && W.uniform_corner (leaf, d, n))
+	continue;
+      bits[g] |= (unsigned char) (1 << ic);
+      for (int e = 0; e < I.n; e++) {
+	GFSHIP_CHECK (I.c[e] >= 0 && I.c[e] < V.ncell, GFSHIP_EINVAL, "corner interpolator: cell %d out of range", I.c[e]);
+	col.push_back (I.c[e]);
+	w.push_back (I.w[e]);
+      }
+      if (I.n > longest) longest = I.n;
+      ptr.push_back ((int) col.size ());
+    }
+  }
+  SamplerTables * S = new SamplerTables;
+  S->stats[0] = (long long) V.nleaves*nc;
+  S->stats[1] = (long long) ptr.size () - 1;
+  S->stats[2] = (long long) col.size ();
+  S->stats[3] = (long long) (bits.size () + base.size ()*sizeof (int) + ptr.size ()*sizeof (int) +
+			     col.size ()*(sizeof (int) + sizeof (double)));
+  S->stats[4] = longest;
+  if (col.empty ()) { col.push_back (0); w.push_back (0.); }      /* no empty allocation */
+  auto up = [] (void ** dst, const void * src, size_t bytes) -> hipError_t {
+    hipError_t e = hipMalloc (dst, bytes);
+    if (e == hipSuccess) e = hipMemcpy (*dst, src, bytes, hipMemcpyHostToDevice);
+    return e;
+  };
+  hipError_t e = up ((void **) &S->corner_bits, bits.data (), bits.size ());
+  if (e == hipSuccess) e = up ((void **) &S->row_base, base.data (), base.size ()*sizeof (int));
+  if (e == hipSuccess) e = up ((void **) &S->row_ptr, ptr.data (), ptr.size ()*sizeof (int));
+  if (e == hipSuccess) e = up ((void **) &S->col, col.data (), col.size ()*sizeof (int));
+  if (e == hipSuccess) e = up ((void **) &S->w, w.data (), w.size ()*sizeof (double));
+  if (e != hipSuccess) {
+    sampler_tables_free (S);
+    return hip_fail (e, "the tables of the tree sampler", __FILE__, __LINE__);
+  }
+  *out = S;
+  return GFSHIP_OK;
+}
+
+int sampler_get (gfship_tree * tr, TreeView * V, SamplerTables ** S)
+{
+  tree_view (tr, V);
+  GFSHIP_HIP (hipSetDevice (V->device));
+  if (!*V->sampler) {
+    SamplerTables * built = nullptr;
+    int r = sampler_build (tr, *V, &built);
+    if (r) return r;
+    *V->sampler = built;
+    *V->sampler_free = sampler_tables_free;
+  }
+  *S = (SamplerTables *) *V->sampler;
+  return GFSHIP_OK;
+}
+
+// ---- device ------------------------------------------------------------------------------------------
+
+struct TreeSamp {
+  Topo T;
+  const unsigned char * corner_bits;
+  const int * row_base, * row_ptr, * col;
+  const double * w;
+};
+
+struct Leaf { int l, q, g, i, j, k; };
+template <int NV> struct Vars { const double * p[NV]; };    // the arrays (all levels) of NV variables      // g = Topo::gi; i, j, k: the indices in the dense level (with ghosts)
+
+// ftt_cell_locate (root, target, -1), src/ftt.c:1535-1574, on the unit box centred on the origin
+template <int DIM>
+__device__ __forceinline__ bool tree_locate (const TreeSamp & S, const double target[3], Leaf & c)
+{
+  double pos[3] = { 0., 0., 0. };
+  double size = 1./2.;
+#pragma unroll
+  for (int a = 0; a < DIM; a++)
+    if (target[a] > pos[a] + size || target[a] < pos[a] - size)
+      return false;
+  int l = 0, i = 1, j = 1, k = DIM == 3 ? 1 : 0;
+  int q = 1 + 3*(1 + (DIM == 3 ? 3 : 0));
+  int g = S.T.off[0] + q;
+  while (l < S.T.depth && S.T.cmask[g] != 0) {
+    const bool ux = target[0] > pos[0], uy = target[1] > pos[1], uz = DIM == 3 && target[2] > pos[2];
+    const int rr = (2 << l) + 2;
+    q = S.T.child0[g] + (ux ? 1 : 0) - (uy ? 0 : rr) - (DIM == 3 && !uz ? rr*rr : 0);
+    i = 2*i - 1 + (ux ? 1 : 0);
+    j = 2*j - (uy ? 0 : 1);
+    if (DIM == 3) k = 2*k - (uz ? 0 : 1);
+    size /= 2.;
+    pos[0] += (ux ? 1. : -1.)*size;
+    pos[1] += (uy ? 1. : -1.)*size;
+    if (DIM == 3) pos[2] += (uz ? 1. : -1.)*size;
+    l++;
+    g = S.T.off[l] + q;
+  }
+  c.l = l; c.q = q; c.g = g; c.i = i; c.j = j; c.k = k;
+  return true;
+}
+
+// gfs_interpolate (src/fluid.c:2697-2710) of NV variables at p inside the leaf c; v[]: the arrays of all levels
+template <int DIM, int NV>
+__device__ void tree_interpolate (const TreeSamp & S, const Vars<NV> & v, const Leaf & c,
+				  const double p_[3], double (& out)[NV])
+{
+  constexpr int NC = 4*(DIM - 1);
+  const int n = 1 << c.l, r = n + 2;
+  const double h = 1./n;
+  const int cell[3] = { c.i, c.j, c.k };
+  bool outm[3], outp[3];    // is cell - 1 / cell + 1 a ghost along each axis?
+#pragma unroll
+  for (int a = 0; a < DIM; a++) {
+    outm[a] = cell[a] - 1 < 1;
+    outp[a] = cell[a] + 1 > n;
+  }
+  const double a_ = 1./(h*(DIM == 2 ? 0.707106781185 : 0.866025403785) + 1e-12);
+  // corner directions, src/fluid.c:2588-2605
+  const int c2[4][3] = { {-1,-1,0}, {1,-1,0}, {1,1,0}, {-1,1,0} };
+  const int c3[8][3] = { {-1,-1,1}, {1,-1,1}, {1,1,1}, {-1,1,1},
+			 {-1,-1,-1}, {1,-1,-1}, {1,1,-1}, {-1,1,-1} };
+  double f[NV][NC + 1];
+  // the corners of the uniform box: the 3^DIM cells of the leaf's level around the leaf (all of them allocated)
+#pragma unroll
+  for (int cv = 0; cv < NV; cv++) {
+    const double * __restrict__ vl = v.p[cv] + c.g;
+    double nb[DIM == 3 ? 27 : 9];
+#pragma unroll
+    for (int dz = (DIM == 3 ? -1 : 0); dz <= (DIM == 3 ? 1 : 0); dz++)
+#pragma unroll
+      for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+	for (int dx = -1; dx <= 1; dx++)
+	  nb[(dx + 1) + 3*(dy + 1) + 9*(DIM == 3 ? dz + 1 : 0)] = vl[dx + dy*r + dz*r*r];
+#pragma unroll
+    for (int ic = 0; ic < NC; ic++) {
+      int sg[3];
+#pragma unroll
+      for (int a = 0; a < 3; a++) sg[a] = DIM == 2 ? c2[ic][a] : c3[ic][a];
+      double wsum = 0., w0 = 0.;
+      int cnt = 0, boundaries = 0;
+      bool ex[1 << DIM];
+#pragma unroll
+      for (int m = 0; m < (1 << DIM); m++) {
+	int o = 0;
+#pragma unroll
+	for (int a = 0; a < DIM; a++)
+	  if (m & (1 << a))
+	    o += (sg[a] < 0 ? outm[a] : outp[a]) ? 1 : 0;
+	ex[m] = o <= 1;
+	if (ex[m]) {
+	  if (cnt == 0) w0 = a_;
+	  cnt++;
+	  wsum += a_;
+	  if (o > 0) boundaries++;
+	}
+      }
+      const bool skip0 = (cnt == DIM + 1 && boundaries == DIM);   // domain corner: drop the central cell
+      if (skip0)
+	wsum -= w0;
+      const double scale = 1./wsum;
+      double s = 0.;
+#pragma unroll
+      for (int m = 0; m < (1 << DIM); m++) {
+	const int ox = (m & 1) ? sg[0] : 0, oy = (m & 2) ? sg[1] : 0, oz = (DIM == 3 && (m & 4)) ? sg[2] : 0;
+	const double val = nb[(ox + 1) + 3*(oy + 1) + 9*(DIM == 3 ? oz + 1 : 0)];
+	if (ex[m] && !(skip0 && m == 0)) {
+	  const double wm = a_*scale;
+	  s += wm*val;
+	}
+      }
+      f[cv][ic] = s;
+    }
+    f[cv][NC] = nb[1 + 3 + (DIM == 3 ? 9 : 0)];
+  }
+  // the corners at a change of level: gfs_cell_corner_value (:3081-3101) along the row of the table, one read of
+  // (cell, weight) for all the variables
+  const unsigned bits = S.corner_bits[c.g];
+  if (bits) {
+    int row = S.row_base[c.g];
+#pragma unroll
+    for (int ic = 0; ic < NC; ic++)
+      if ((bits >> ic) & 1u) {
+	const int e0 = S.row_ptr[row], e1 = S.row_ptr[row + 1];
+	row++;
+	double s[NV];
+#pragma unroll
+	for (int cv = 0; cv < NV; cv++) s[cv] = 0.;
+	for (int e = e0; e < e1; e++) {
+	  const int g = S.col[e];
+	  const double we = S.w[e];
+#pragma unroll
+	  for (int cv = 0; cv < NV; cv++)
+	    s[cv] += we*v.p[cv][g];
+	}
+#pragma unroll
+	for (int cv = 0; cv < NV; cv++) f[cv][ic] = s[cv];
+      }
+  }
+  // gfs_interpolate_from_corners, src/fluid.c:2640-2683
+  const double o[3] = { -0.5 + (cell[0] - 0.5)*h, -0.5 + (cell[1] - 0.5)*h,
+			DIM == 3 ? -0.5 + (cell[2] - 0.5)*h : 0. };
+  const double size = h/2.;
+  double p[3];
+  p[0] = (p_[0] - o[0])/size;
+  p[1] = (p_[1] - o[1])/size;
+  p[2] = DIM == 3 ? (p_[2] - o[2])/size : 0.;
+#pragma unroll
+  for (int cv = 0; cv < NV; cv++) {
+    const double (& F)[NC + 1] = f[cv];
+    if (DIM == 2) {
+      double x = (p[0] + p[1])/2., y = (p[1] - p[0])/2., val = F[4];
+      if (x > 0.)
+	val += x*(F[2] - F[4]);
+      else
+	val -= x*(F[0] - F[4]);
+      if (y > 0.)
+	val += y*(F[3] - F[4]);
+      else
+	val -= y*(F[1] - F[4]);
+      out[cv] = val;
+    }
+    else {
+      double k[8];
+      k[0] = - F[0] + F[1] + F[2] - F[3] - F[4] + F[5] + F[6] - F[7];
+      k[1] = - F[0] - F[1] + F[2] + F[3] - F[4] - F[5] + F[6] + F[7];
+      k[2] =   F[0] + F[1] + F[2] + F[3] - F[4] - F[5] - F[6] - F[7];
+      k[3] =   F[0] - F[1] + F[2] - F[3] + F[4] - F[5] + F[6] - F[7];
+      k[4] = - F[0] + F[1] + F[2] - F[3] + F[4] - F[5] - F[6] + F[7];
+      k[5] = - F[0] - F[1] + F[2] + F[3] + F[4] + F[5] - F[6] - F[7];
+      k[6] =   F[0] - F[1] + F[2] - F[3] - F[4] + F[5] - F[6] + F[7];
+      k[7] =   F[0] + F[1] + F[2] + F[3] + F[4] + F[5] + F[6] + F[7];
+      out[cv] = (k[0]*p[0] + k[1]*p[1] + k[2]*p[2] +
+		 k[3]*p[0]*p[1] + k[4]*p[0]*p[2] + k[5]*p[1]*p[2] +
+		 k[6]*p[0]*p[1]*p[2] +
+		 k[7])/8.;
+    }
+  }
+}
+
+// GfsOutputLocation (src/output.c:1182-1199)
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_sample_kernel (TreeSamp S, int np, const double * __restrict__ pos, const double * __restrict__ v,
+		    double * __restrict__ out, unsigned char * __restrict__ inside)
+{
+  const int q = blockIdx.x*blockDim.x + threadIdx.x;
+  if (q >= np) return;
+  const double p[3] = { pos[3*(size_t) q], pos[3*(size_t) q + 1], DIM == 3 ? pos[3*(size_t) q + 2] : 0. };
+  Leaf c;
+  if (!tree_locate<DIM> (S, p, c)) {
+    inside[q] = 0;
+    out[q] = 0.;
+    return;
+  }
+  Vars<1> vv;
+  vv.p[0] = v;
+  double r[1];
+  tree_interpolate<DIM, 1> (S, vv, c, p, r);
+  inside[q] = 1;
+  out[q] = r[0];
+}
+
+struct TreePartArgs {
+  int side[6];
+  int n;
+  double * pos[3];
+  double * old[3];
+  unsigned char * alive;
+  const double * u[3];
+  double dt;
+};
+
+// gfs_particle_list_event (modules/particulatecommon.c:980-1015) of GfsParticle tracers
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_particle_list_event_kernel (TreeSamp S, TreePartArgs A)
+{
+  const int q = blockIdx.x*blockDim.x + threadIdx.x;
+  if (q >= A.n) return;
+  if (A.alive[q] != 1) return;
+  double p[3] = { A.pos[0][q], A.pos[1][q], DIM == 3 ? A.pos[2][q] : 0. };
+  Leaf c0;
+  // remove_particles_not_in_domain, :955-969
+  if (!tree_locate<DIM> (S, p, c0)) {
+    A.alive[q] = 0;
+    return;
+  }
+  Vars<DIM> uu;
+#pragma unroll
+  for (int a = 0; a < DIM; a++) uu.p[a] = A.u[a];
+  // gfs_particle_event (src/particle.c:31-44): pos_old = pos; gfs_domain_advect_point (src/domain.c:2764-2788)
+  double po[3] = { p[0], p[1], p[2] };
+  {
+    double p1[3] = { p[0], p[1], p[2] }, vel[DIM];
+    tree_interpolate<DIM, DIM> (S, uu, c0, po, vel);
+#pragma unroll
+    for (int a = 0; a < DIM; a++)
+      p1[a] += A.dt*vel[a]/2.;
+    Leaf c1;
+    if (tree_locate<DIM> (S, p1, c1)) {
+      tree_interpolate<DIM, DIM> (S, uu, c1, p1, vel);
+#pragma unroll
+      for (int a = 0; a < DIM; a++)
+	p[a] += A.dt*vel[a];
+    }
+  }
+  // gfs_particle_bc, :3326-3395
+  bool keep = true;
+  Leaf cn;
+  if (!tree_locate<DIM> (S, p, cn)) {
+    // boundarycell (:3151-3186): from the leaf of pos_old over the ftt_cell_face neighbours (same level, leaf or not,
+    // or coarser) to the cell whose neighbour is a boundary cell
+    int d = 0;
+    Cell cc = { c0.l, c0.q };
+    for (int guard = 0; guard < 4*(1 << S.T.depth); guard++) {
+      const double h = 1./(1 << cc.l);
+      const double cellpos[3] = { -0.5 + (S.T.ci (cc) - 0.5)*h, -0.5 + (S.T.cj (cc) - 0.5)*h,
+				  DIM == 3 ? -0.5 + (S.T.ck (cc) - 0.5)*h : 0. };
+      check_intersection<DIM> (cellpos, po, p, &d, h);
+      const Cell nb = S.T.neighbor (cc, d);
+      if (!exists (nb) || !S.T.interior (nb))
+	break;
+      cc = nb;
+    }
+    if (A.side[d] != GFSHIP_SIDE_PERIODIC)
+      keep = false;                 /* taken off the list, nothing puts it back */
+    else {
+      // periodic_bc_particle (:3189-3214), box of size 1 matching itself
+      const double size = 1.;
+      const double normal = (double) (d ^ 1) - (double) d;
+      double box_face = 0., box_face_nbr = 0.;
+      box_face += normal*size/2.;
+      box_face_nbr -= normal*size/2.;
+      const double tolerance = size/1.e8;
+      const double distance = (p[d/2] - box_face)*normal;
+      p[d/2] = box_face_nbr + distance + normal*tolerance;
+      po[d/2] = p[d/2];
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < DIM; a++) {
+    A.pos[a][q] = p[a];
+    A.old[a][q] = po[a];
+  }
+  if (!keep)
+    A.alive[q] = 0;
+}
+
+// key of the sort: the leaf that holds the particle (its index in the concatenated levels), dead or outside last
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_particle_keys_kernel (TreeSamp S, int n, const double * __restrict__ x, const double * __restrict__ y,
+			   const double * __restrict__ z, const unsigned char * __restrict__ alive,
+			   unsigned * __restrict__ key, unsigned * __restrict__ slot)
+{
+  const int q = blockIdx.x*blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  unsigned k = 0xFFFFFFFFu;
+  if (alive[q] == 1) {
+    const double p[3] = { x[q], y[q], DIM == 3 ? z[q] : 0. };
+    Leaf c;
+    if (tree_locate<DIM> (S, p, c))
+      k = (unsigned) c.g;
+  }
+  key[q] = k;
+  slot[q] = q;
+}
+
+TreeSamp tree_samp (const TreeView & V, const SamplerTables * S)
+{
+  TreeSamp A;
+  A.T = V.D;
+  A.corner_bits = S->corner_bits;
+  A.row_base = S->row_base; A.row_ptr = S->row_ptr; A.col = S->col;
+  A.w = S->w;
+  return A;
+}
+
+} // namespace
+
+int tree_particle_list_event (gfship_particles * pl)
+{
+  TreeView V;
+  SamplerTables * S;
+  int r = sampler_get (pl->tree, &V, &S);
+  if (r) return r;
+  TreePartArgs A;
+  for (int d = 0; d < 6; d++) A.side[d] = d < 2*V.H.dim ? V.side[d] : GFSHIP_SIDE_PERIODIC;
+  A.n = pl->n;
+  const int uvar[3] = { GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP_TREE_W };
+  for (int c = 0; c < 3; c++) {
+    A.pos[c] = pl->pos[c];
+    A.old[c] = pl->old[c];
+    A.u[c] = c < V.H.dim ? tree_variable (pl->tree, uvar[c]) : nullptr;
+  }
+  A.alive = pl->alive;
+  A.dt = V.dt;
+  const int block = 256, grid = (pl->n + block - 1)/block;
+  if (V.H.dim == 3)
+    hipLaunchKernelGGL (tree_particle_list_event_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), A);
+  else
+    hipLaunchKernelGGL (tree_particle_list_event_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), A);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
+int tree_particle_keys (gfship_particles * pl, int * bits)
+{
+  TreeView V;
+  SamplerTables * S;
+  int r = sampler_get (pl->tree, &V, &S);
+  if (r) return r;
+  const int block = 256, grid = (pl->n + block - 1)/block;
+  if (V.H.dim == 3)
+    hipLaunchKernelGGL (tree_particle_keys_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), pl->n,
+			pl->pos[0], pl->pos[1], pl->pos[2], pl->alive, pl->key, pl->slot);
+  else
+    hipLaunchKernelGGL (tree_particle_keys_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), pl->n,
+			pl->pos[0], pl->pos[1], pl->pos[2], pl->alive, pl->key, pl->slot);
+  GFSHIP_HIP (hipGetLastError ());
+  /* the bits of a cell index (+1 so that the all-ones key of the dead sorts last) */
+  int b = 0;
+  while (b < 31 && (V.ncell >> b)) b++;
+  *bits = b + 1;
+  return GFSHIP_OK;
+}
+
+} // namespace gfship
+
+using namespace gfship;
+
+extern "C" {
+
+int gfship_tree_interpolate (gfship_tree * tr, int var, int np, const double * pos, double * out,
+			     unsigned char * inside)
+{
+  GFSHIP_CHECK (tr && pos && out && inside && np >= 0, GFSHIP_EINVAL, "invalid argument");
+  const double * v = tree_variable (tr, var);
+  GFSHIP_CHECK (v != nullptr, GFSHIP_EINVAL, "gfship_tree_interpolate: %d is not a variable of a tree", var);
+  if (np == 0) return GFSHIP_OK;
+  TreeView V;
+  SamplerTables * S;
+  int r = sampler_get (tr, &V, &S);
+  if (r) return r;
+  double * dpos = nullptr, * dout = nullptr;
+  unsigned char * din = nullptr;
+  GFSHIP_HIP (hipMalloc ((void **) &dpos, 3*(size_t) np*sizeof (double)));
+  GFSHIP_HIP (hipMalloc ((void **) &dout, (size_t) np*sizeof (double)));
+  GFSHIP_HIP (hipMalloc ((void **) &din, (size_t) np));
+  hipError_t e = hipMemcpyAsync (dpos, pos, 3*(size_t) np*sizeof (double), hipMemcpyHostToDevice, V.stream);
+  if (e == hipSuccess) {
+    const int block = 256, grid = (np + block - 1)/block;
+    if (V.H.dim == 3)
+      hipLaunchKernelGGL (tree_sample_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), np, dpos, v,
+			  dout, din);
+    else
+      hipLaunchKernelGGL (tree_sample_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), np, dpos, v,
+			  dout, din);
+    e = hipGetLastError ();
+  }
+  if (e == hipSuccess)
+    e = hipMemcpyAsync (out, dout, (size_t) np*sizeof (double), hipMemcpyDeviceToHost, V.stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync (inside, din, (size_t) np, hipMemcpyDeviceToHost, V.stream);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize (V.stream);
+  if (e != hipSuccess)
+    r = hip_fail (e, "gfship_tree_interpolate", __FILE__, __LINE__);
+  (void) hipFree (dpos); (void) hipFree (dout); (void) hipFree (din);
+  return r;
+}
+
+int gfship_tree_sampler_stats (gfship_tree * tr, long long stats[5])
+{
+  GFSHIP_CHECK (tr && stats, GFSHIP_EINVAL, "invalid argument");
+  TreeView V;
+  SamplerTables * S;
+  int r = sampler_get (tr, &V, &S);
+  if (r) return r;
+  for (int k = 0; k < 5; k++) stats[k] = S->stats[k];
+  return GFSHIP_OK;
+}
+
+int gfship_particles_create_tree (gfship_particles ** out, gfship_tree * tr, int np, const double * pos,
+				  const unsigned * id)
+{
+  GFSHIP_CHECK (out && tr && (np == 0 || (pos && id)) && np >= 0, GFSHIP_EINVAL, "invalid argument");
+  *out = nullptr;
+  TreeView V;
+  SamplerTables * S;
+  int r = sampler_get (tr, &V, &S);
+  if (r) return r;
+  gfship_particles * pl = new gfship_particles;
+  pl->tree = tr;
+  pl->stream = V.stream;
+  pl->dim = V.H.dim;
+  r = particles_alloc (pl, np, pos, id);
+  if (r) {
+    gfship_particles_destroy (pl);
+    return r;
+  }
+  *out = pl;
+  return GFSHIP_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,24 @@
+// tree_particles.hpp -- what the point sampler and the tracers (tree_particles.hip) see of a gfship_tree
+// (tree.hip keeps the struct to itself).
+#pragma once
+#include "tree.hpp"
+
+namespace gfship {
+
+struct TreeView {
+  tree::Topo H, D;                  // the tables of the tree on the host and on the device
+  hipStream_t stream;
+  int device, ncell, nleaves;
+  const tree::Cell * hleaves;       // host: interior leaves in traversal order
+  const int * side;                 // GFSHIP_SIDE_* of the 2*dim sides
+  double dt;
+  // the tables of the sampler, built on first use and freed with the tree
+  void ** sampler;
+  void (** sampler_free) (void *);
+};
+
+void tree_view (gfship_tree * tr, TreeView * v);
+// the device array (all levels) of the variable GFSHIP_TREE_* `var'; nullptr: no such variable
+double * tree_variable (gfship_tree * tr, int var);
+
+}

@@ -208,6 +208,9 @@ SIGNATURES = {
     "gfship_tree_divergence": (_i, [_vp]),
     "gfship_tree_host_check": (_i, [_i, C.c_void_p, _vp, _pi, _u, C.POINTER(C.c_longlong)]),
     "gfship_tree_host_check_diffusion": (_i, [_i, C.c_void_p, _vp, _pi, _u, _d, C.POINTER(C.c_longlong)]),
+    "gfship_tree_interpolate": (_i, [_vp, _i, _i, _pd, _pd, C.POINTER(C.c_ubyte)]),
+    "gfship_tree_sampler_stats": (_i, [_vp, C.POINTER(C.c_longlong)]),
+    "gfship_particles_create_tree": (_i, [C.POINTER(_vp), _vp, _i, _pd, C.POINTER(C.c_uint)]),
 }
 
 
@@ -784,7 +787,7 @@ class InitSpectraParams(C.Structure):
 
 
 class ParticleList:
-    """GfsParticleList of GfsParticle tracers on the device."""
+    """GfsParticleList of GfsParticle tracers on the device; sim: a Simulation, or a Tree (tracers only)."""
 
     def __init__(self, sim, pos, ids):
         pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
@@ -792,8 +795,9 @@ class ParticleList:
         assert len(pos) == len(ids)
         self.sim, self.n0 = sim, len(ids)
         p = _vp()
-        _check(lib().gfship_particles_create(C.byref(p), sim.ptr, len(ids), pos.ctypes.data_as(_pd),
-                                             ids.ctypes.data_as(C.POINTER(C.c_uint))))
+        create = lib().gfship_particles_create_tree if isinstance(sim, Tree) else lib().gfship_particles_create
+        _check(create(C.byref(p), sim.ptr, len(ids), pos.ctypes.data_as(_pd),
+                      ids.ctypes.data_as(C.POINTER(C.c_uint))))
         self.ptr = p
 
     def event(self):
@@ -1034,6 +1038,27 @@ class Tree:
         a, b = C.c_int(), C.c_int()
         _check(lib().gfship_tree_sweep_levels(self.ptr, level, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def interpolate(self, var, points):
+        """GfsOutputLocation: the variable (Tree.U ...) at points (N, 3) -> (values, inside)"""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        out = np.empty(len(pts))
+        inside = np.empty(len(pts), dtype=np.uint8)
+        _check(lib().gfship_tree_interpolate(self.ptr, var, len(pts), pts.ctypes.data_as(_pd),
+                                             out.ctypes.data_as(_pd),
+                                             inside.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out, inside.astype(bool)
+
+    def particles(self, pos, ids):
+        """a GfsParticleList of GfsParticle tracers on this tree (destroy it before the tree)"""
+        return ParticleList(self, pos, ids)
+
+    def sampler_stats(self):
+        """the corner interpolators of the sampler: (corners of leaves, corners that read the table, table
+        entries, bytes on the device, cells of the longest interpolator)"""
+        stats = (C.c_longlong * 5)()
+        _check(lib().gfship_tree_sampler_stats(self.ptr, stats))
+        return tuple(stats)
 
     t = property(lambda self: lib().gfship_tree_time(self.ptr))
     dt = property(lambda self: lib().gfship_tree_dt(self.ptr))

@@ -883,6 +883,41 @@ int  gfship_tree_host_check_diffusion (int dim, gfship_refine_fn refine, void * 
    coarser leaves) and the number of dependency levels its tree order leaves on the device */
 int  gfship_tree_sweep_levels (const gfship_tree * tree, int level, int * ncells, int * nlevels);
 
+/* ---- point sampling and Lagrangian tracers on a tree ------------------------------------------ */
+
+/* GfsOutputLocation on a tree (src/output.c:1182-1199): ftt_cell_locate (src/ftt.c:1535-1574: inclusive box
+   bounds, a strict `>' in the descent) down to the leaf that holds the point, then gfs_interpolate
+   (src/fluid.c:2697-2710): the corner values of gfs_cell_corner_value (:3081-3101) through
+   gfs_cell_corner_interpolator (:3015-3069) with the coarser and deeper neighbours of cell_corner_neighbor
+   (:2813-2846) and the T-junctions of t_junction_interpolator (:2879-2923), then gfs_interpolate_from_corners
+   (:2640-2683) with the position and the size of the leaf.  The contract of gfship_field_interpolate: pos = 3*np
+   doubles, out = 0 and inside = 0 for a point outside the box, no GFS_NODATA branches.  var: any GFSHIP_TREE_*.
+   The interpolators of the corners that touch a change of level are walked once on the host, in the reference's
+   order of operations, when the first sampler call or the first list of the tree needs them; the device sums
+   weight * value in that order.
+   Ghost cells: the sampler reads the ghost cells of the leaves of every level and writes nothing.  gfship_tree_start
+   and gfship_tree_step leave them current for P, U, V, W and the tracers (the last gfs_domain_bc of the step);
+   gfship_tree_upload leaves what the caller uploaded, ghost layer included: the caller of a sampler after an
+   upload gives the ghost values it wants read. */
+int  gfship_tree_interpolate (gfship_tree * tree, int var, int np, const double * pos,
+			      double * out, unsigned char * inside);
+/* the size of those tables: stats[0] = corners of leaves (leaves * 2^dim), [1] = corners that read the table
+   (the others take the arithmetic of the uniform box), [2] = (cell, weight) entries, [3] = bytes on the device,
+   [4] = the longest interpolator (at most 7 in 2-D, 29 in 3-D: GfsInterpolator, src/fluid.h) */
+int  gfship_tree_sampler_stats (gfship_tree * tree, long long stats[5]);
+/* a GfsParticleList of GfsParticle on a tree (modules/particulatecommon.c:1022-1093).  On such a list
+   gfship_particle_list_event is gfs_particle_list_event (:980-1015): remove_particles_not_in_domain (:955-969),
+   gfs_particle_event (src/particle.c:31-44) with the RK2 of gfs_domain_advect_point (src/domain.c:2764-2788) on
+   the tree's U, V(, W) and gfship_tree_dt, then gfs_particle_bc (:3375-3395): boundarycell (:3151-3186) marches
+   over the ftt_cell_face neighbours, whatever their level, to the side the particle left through; a periodic
+   side puts it back (periodic_bc_particle, :3189-3214), a GfsBoundary side takes it off the list.  The velocity
+   is read as gfship_tree_interpolate reads it (call the event after gfship_tree_start / _step).
+   gfship_particles_count, _slots, _download, _download_old, _sort, _set_sort_interval and _destroy work on such a
+   list (destroy it before its tree); everything of particulates, forces, coupling and migration returns
+   GFSHIP_EUNSUPPORTED. */
+int  gfship_particles_create_tree (gfship_particles ** pl, gfship_tree * tree, int np,
+				   const double * pos, const unsigned * id);
+
 /* ---- instrumentation -------------------------------------------------------------------- */
 
 /* time (HIP events on the domain's stream) of `reps` back-to-back sweeps of gfship_relax on
