@@ -26,6 +26,7 @@
 // order).  Tracers move less than one cell per step (CFL < 1), so the order stays good between
 // sorts.
 #include "particles.hpp"
+#include "tree_particles.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <numeric>
@@ -1166,8 +1167,15 @@ int gfship_particles_set_particulate (gfship_particles * pl, const double * vel,
   GFSHIP_CHECK (pl && vel && mass && volume, GFSHIP_EINVAL, "null argument");
   GFSHIP_NO_TREE_LIST (pl, "gfship_particles_set_particulate");
   GFSHIP_CHECK (!pl->particulate, GFSHIP_EINVAL, "the list already holds particulates");
-  size_t m = (size_t) pl->cap, np = (size_t) pl->n;
   GFSHIP_CHECK (pl->n == pl->np0, GFSHIP_EINVAL, "set the particulate state before the first migration");
+  return gfship::particulate_alloc (pl, vel, mass, volume);
+}
+
+} // extern "C"
+
+int gfship::particulate_alloc (gfship_particles * pl, const double * vel, const double * mass, const double * volume)
+{
+  size_t m = (size_t) pl->cap, np = (size_t) pl->n;
   std::vector<double> tmp (m, 0.);
   for (int c = 0; c < 3; c++) {
     GFSHIP_HIP (hipMalloc ((void **) &pl->vel[c], m*sizeof (double)));
@@ -1199,14 +1207,16 @@ int gfship_particles_set_particulate (gfship_particles * pl, const double * vel,
   return GFSHIP_OK;
 }
 
+extern "C" {
+
 int gfship_particles_set_forces (gfship_particles * pl, int nforces, const int * kinds,
 				 const double gravity[3])
 {
   GFSHIP_CHECK (pl && (nforces == 0 || kinds), GFSHIP_EINVAL, "null argument");
-  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_set_forces");
+  GFSHIP_NO_TREE_TRACER_LIST (pl, "gfship_particles_set_forces");
   GFSHIP_CHECK (pl->particulate, GFSHIP_EINVAL, "forces act on particulates (gfship_particles_set_particulate)");
   GFSHIP_CHECK (nforces >= 0 && nforces <= 8, GFSHIP_EINVAL, "at most 8 forces");
-  if (nforces > 0) {
+  if (nforces > 0 && !pl->tree) {
     int r = particulate_fluid_check (gfship_sim_view_get (pl->sim));
     if (r) return r;
   }
@@ -1216,7 +1226,7 @@ int gfship_particles_set_forces (gfship_particles * pl, int nforces, const int *
 		  "unknown force");
   /* a new list of forces: the compiled GfsFunction of a slot belonged to the force that sat there
      (gfship_particles_set_force_coefficient comes after this call) */
-  GFSHIP_HIP (hipStreamSynchronize (pl->dom->stream));
+  GFSHIP_HIP (hipStreamSynchronize (pl->stream));
   for (int f = 0; f < 8; f++) {
     gfship::rtc_free (pl->coef_fn[f]);
     pl->coef_fn[f] = nullptr;
@@ -1230,6 +1240,8 @@ int gfship_particles_set_forces (gfship_particles * pl, int nforces, const int *
   pl->nforces = nforces;
   for (int c = 0; c < 3; c++) pl->gravity[c] = gravity ? gravity[c] : 0.;
   /* every GfsForceCoeff creates Un, Vn, Wn and stores the velocity when it is read (:181-187) */
+  if (pl->tree)      /* Un, Vn, Wn are variables of the tree (GFSHIP_TREE_UPREV ...) */
+    return coeff ? gfship::tree_previous_vel (pl->tree) : GFSHIP_OK;
   if (coeff && pl->uold[0] < 0) {
     for (int c = 0; c < pl->dom->dim; c++) {
       pl->uold[c] = gfship_field_alloc (pl->dom, -1);
@@ -1243,16 +1255,17 @@ int gfship_particles_set_forces (gfship_particles * pl, int nforces, const int *
 int gfship_particles_set_force_coefficient (gfship_particles * pl, int force, const char * function)
 {
   GFSHIP_CHECK (pl && function, GFSHIP_EINVAL, "null argument");
-  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_set_force_coefficient");
+  GFSHIP_NO_TREE_TRACER_LIST (pl, "gfship_particles_set_force_coefficient");
   GFSHIP_CHECK (force >= 0 && force < pl->nforces, GFSHIP_EINVAL,
 		"force %d: the list has %d forces (gfship_particles_set_forces)", force, pl->nforces);
   GFSHIP_CHECK (pl->forces[force] == GFSHIP_FORCE_ADDEDMASS || pl->forces[force] == GFSHIP_FORCE_LIFT ||
 		pl->forces[force] == GFSHIP_FORCE_DRAG, GFSHIP_EINVAL,
 		"only GfsForceAddedMass, GfsForceLift and GfsForceDrag read a coefficient");
   gfship::RtcKernel * k = nullptr;
-  int r = gfship::rtc_compile_coefficient (pl->dom, function, &k);
+  int r = pl->tree ? gfship::rtc_compile_coefficient_on (gfship::tree_device (pl->tree), function, &k) :
+    gfship::rtc_compile_coefficient (pl->dom, function, &k);
   if (r) return r;
-  GFSHIP_HIP (hipStreamSynchronize (pl->dom->stream));
+  GFSHIP_HIP (hipStreamSynchronize (pl->stream));
   gfship::rtc_free (pl->coef_fn[force]);
   pl->coef_fn[force] = k;
   return GFSHIP_OK;
@@ -1262,11 +1275,10 @@ int gfship_particles_download_particulate (gfship_particles * pl, double * vel, 
 					   double * force)
 {
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
-  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_download_particulate");
+  GFSHIP_NO_TREE_TRACER_LIST (pl, "gfship_particles_download_particulate");
   GFSHIP_CHECK (pl->particulate, GFSHIP_EINVAL, "not a list of particulates");
   if (pl->n == 0) return 0;
-  gfship_domain * dom = pl->dom;
-  GFSHIP_HIP (hipStreamSynchronize (dom->stream));
+  GFSHIP_HIP (hipStreamSynchronize (pl->stream));
   size_t m = pl->n, m0 = pl->n;      /* creation slots = slots in use */
   std::vector<unsigned> orig (m), where (m);
   std::vector<unsigned char> al (m);
@@ -1306,6 +1318,9 @@ int gfship_particle_list_event (gfship_particles * pl)
     }
     if (pl->events_since_sort >= 0)
       pl->events_since_sort++;
+    /* gfs_particulate_event without forces is the event of GfsParticle (:776-778) */
+    if (pl->particulate && pl->nforces > 0)
+      return gfship::tree_particulate_list_event (pl);
     return gfship::tree_particle_list_event (pl);
   }
   const bool migrates = pl->migrate != nullptr || (pl->dom->comm && pl->dom->has_external);

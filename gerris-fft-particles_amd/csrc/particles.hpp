@@ -5,6 +5,7 @@
 namespace gfship {
 struct RtcKernel;
 int  rtc_compile_coefficient (gfship_domain * dom, const char * text, RtcKernel ** out);
+int  rtc_compile_coefficient_on (int device, const char * text, RtcKernel ** out);   // a list of a tree
 int  rtc_launch_coefficient (RtcKernel * k, hipStream_t stream, int n, const unsigned char * alive,
 			     const double * rep, const double * const rel[3], const double * pdia,
 			     double t, double * out);
@@ -19,7 +20,7 @@ int  rtc_launch_spatial (RtcKernel * k, hipStream_t stream, long nrec, int strid
 struct gfship_particles {
   gfship_sim * sim = nullptr;
   gfship_domain * dom = nullptr;
-  gfship_tree * tree = nullptr;       // a list of GfsParticle on a refined tree (tree_particles.hip): sim, dom = nullptr
+  gfship_tree * tree = nullptr;       // a list of GfsParticle or GfsParticulate on a refined tree (tree_particles.hip): sim, dom = nullptr
   hipStream_t stream = nullptr;       // the stream of dom or of tree
   int dim = 0;
   int n = 0;                   // slots in use (alive or not)
@@ -89,10 +90,20 @@ int particles_alloc (gfship_particles * pl, int np, const double * pos, const un
 // a list on a tree (tree_particles.hip): the event of its tracers, the keys of gfship_particles_sort and their bits
 int tree_particle_list_event (gfship_particles * pl);
 int tree_particle_keys (gfship_particles * pl, int * bits);
+// the state of GfsParticulate of a list (velocity, mass, volume, diameter, rb; force = 0): what
+// gfship_particles_set_particulate does after its checks (particles.hip)
+int particulate_alloc (gfship_particles * pl, const double * vel, const double * mass, const double * volume);
+// a list of particulates on a tree (gfship_particulates_create_tree, tree_particles.hip): its event with forces
+int tree_particulate_list_event (gfship_particles * pl);
 }
 
-// particulates, forces, coupling and migration exist on uniform boxes only
+// coupling and migration exist on uniform boxes only, and a list of a tree is born as tracers
+// (gfship_particles_create_tree) or as particulates (gfship_particulates_create_tree)
 #define GFSHIP_NO_TREE_LIST(pl, what) GFSHIP_CHECK (!(pl)->tree, GFSHIP_EUNSUPPORTED, \
+    "%s: a particle list on a refined tree holds GfsParticle tracers only (no particulates, forces, " \
+    "coupling or migration)", what)
+// forces and the particulate state: not on a list of tracers of a tree
+#define GFSHIP_NO_TREE_TRACER_LIST(pl, what) GFSHIP_CHECK (!((pl)->tree && !(pl)->particulate), GFSHIP_EUNSUPPORTED, \
     "%s: a particle list on a refined tree holds GfsParticle tracers only (no particulates, forces, " \
     "coupling or migration)", what)
 

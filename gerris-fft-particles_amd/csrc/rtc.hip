@@ -72,11 +72,11 @@ void rtc_free (RtcKernel * k)
 
 // the text of a GfsFunction -- an expression or a { block } with a return -- as the body of the device
 // function whose head is `signature', followed by the kernel `kernel_src' that calls it; compiled for the
-// GPU of the domain, `entry' is the kernel's name
-static int rtc_compile (gfship_domain * dom, const char * text, const char * signature,
+// GPU `device' (that of the domain, or of the tree), `entry' is the kernel's name
+static int rtc_compile (int device, const char * text, const char * signature,
 			const char * kernel_src, const char * entry, RtcKernel ** out)
 {
-  GFSHIP_CHECK (dom && text && out, GFSHIP_EINVAL, "null argument");
+  GFSHIP_CHECK (text && out, GFSHIP_EINVAL, "null argument");
   *out = nullptr;
   int r = rtc_load ();
   if (r) return r;
@@ -93,7 +93,7 @@ static int rtc_compile (gfship_domain * dom, const char * text, const char * sig
     src += "{ return (" + t + "); }\n";
   src += kernel_src;
   hipDeviceProp_t prop;
-  GFSHIP_HIP (hipGetDeviceProperties (&prop, dom->device));
+  GFSHIP_HIP (hipGetDeviceProperties (&prop, device));
   const std::string arch = std::string ("--offload-arch=") + prop.gcnArchName;
   const char * opts[] = { arch.c_str (), "-ffp-contract=off", "-fno-fast-math", "-O2" };
   hiprtcProgram prog;
@@ -128,10 +128,11 @@ static int rtc_compile (gfship_domain * dom, const char * text, const char * sig
   return GFSHIP_OK;
 }
 
-// the kernel around a GfsFunction of the variables of gfs_force_coeff_read (:189-207) and the time
-int rtc_compile_coefficient (gfship_domain * dom, const char * text, RtcKernel ** out)
+// the kernel around a GfsFunction of the variables of gfs_force_coeff_read (:189-207) and the time, compiled for
+// `device' (the list of a tree has no domain: the device is all the compilation needs)
+int rtc_compile_coefficient_on (int device, const char * text, RtcKernel ** out)
 {
-  return rtc_compile (dom, text,
+  return rtc_compile (device, text,
     "static __device__ double gfship_f (double Rep, double Urelp, double Vrelp, double Wrelp,\n"
     "                                   double Pdia, double t)\n",
     "extern \"C\" __global__ void gfship_coeff (int n, const unsigned char * alive,\n"
@@ -144,13 +145,20 @@ int rtc_compile_coefficient (gfship_domain * dom, const char * text, RtcKernel *
     "}\n", "gfship_coeff", out);
 }
 
+int rtc_compile_coefficient (gfship_domain * dom, const char * text, RtcKernel ** out)
+{
+  GFSHIP_CHECK (dom != nullptr, GFSHIP_EINVAL, "null argument");
+  return rtc_compile_coefficient_on (dom->device, text, out);
+}
+
 // the kernel function of a GfsSourceParticulate (modules/particulatecommon.c:2271-2289): a GfsFunction
 // (spatial) of x, y, z and t (gfs_function_spatial_value, src/utils.c:1476-1494), evaluated at the
 // normalised distances of the records of the spreading (coupling.hip): record r belongs to particle
 // r/stride of the chunk and is in use if r%stride < cnt[r/stride]
 int rtc_compile_spatial (gfship_domain * dom, const char * text, RtcKernel ** out)
 {
-  return rtc_compile (dom, text,
+  GFSHIP_CHECK (dom != nullptr, GFSHIP_EINVAL, "null argument");
+  return rtc_compile (dom->device, text,
     "static __device__ double gfship_f (double x, double y, double z, double t)\n",
     "extern \"C\" __global__ void gfship_spatial (long nrec, int stride, const int * cnt,\n"
     "    const double * qx, const double * qy, const double * qz, double t, double * out)\n"

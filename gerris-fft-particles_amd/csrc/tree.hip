@@ -170,6 +170,9 @@ struct gfship_tree {
   // the corner interpolators of the point sampler and of the tracers (tree_particles.hip), built on first use
   void * sampler = nullptr;
   void (* sampler_free) (void *) = nullptr;
+  // Un, Vn, Wn of the GfsForceCoeff objects (GFSHIP_TREE_UPREV ...): allocated when the first list of particulates
+  // with such a force asks for them (tree_previous_vel)
+  double * uprev[3] = {};
 };
 
 namespace {
@@ -2704,6 +2707,7 @@ void tree_free (gfship_tree * tr)
   (void) hipFree (tr->dflag);
   (void) hipFree (tr->d_nbtab); (void) hipFree (tr->d_child0); (void) hipFree (tr->d_cmask); (void) hipFree (tr->d_idtab);
   for (double * p : tr->var) (void) hipFree (p);
+  for (double * p : tr->uprev) (void) hipFree (p);
   (void) hipFree (tr->leaves);
   (void) hipFree (tr->ghost_leaves);
   for (int l = 0; l <= GFSHIP_MAXLEVEL; l++) {
@@ -2733,13 +2737,38 @@ void gfship::tree_view (gfship_tree * tr, gfship::TreeView * v)
   v->hleaves = tr->hleaves.data ();
   v->side = tr->side;
   v->dt = tr->dt;
+  v->t = tr->t;
+  v->viscosity = tr->visc[0];
+  for (int c = 0; c < 3; c++) v->uprev[c] = tr->uprev[c];
   v->sampler = &tr->sampler;
   v->sampler_free = &tr->sampler_free;
 }
 
 double * gfship::tree_variable (gfship_tree * tr, int var)
 {
+  if (var >= GFSHIP_TREE_UPREV && var <= GFSHIP_TREE_WPREV)
+    return tr->uprev[var - GFSHIP_TREE_UPREV];
   return var >= 0 && var < abi_nvar ? tr->var[abi_var[var]] : nullptr;
+}
+
+int gfship::tree_device (gfship_tree * tr) { return tr->device; }
+
+// store_domain_previous_vel, modules/particulatecommon.c:99-113: the copy of U, V, W on the leaves (:108-110), then
+// gfs_domain_bc of the new variable (:111), a scalar with the default GfsBc whatever the conditions of U
+int gfship::tree_previous_vel (gfship_tree * tr)
+{
+  GFSHIP_HIP (hipSetDevice (tr->device));
+  for (int c = 0; c < tr->H.dim; c++) {
+    if (!tr->uprev[c]) {
+      GFSHIP_HIP (hipMalloc ((void **) &tr->uprev[c], tr->ncell*sizeof (double)));
+      GFSHIP_HIP (hipMemsetAsync (tr->uprev[c], 0, tr->ncell*sizeof (double), tr->stream));
+    }
+    t_copy_leaves<<<blocks (tr->nleaves), 256, 0, tr->stream>>> (tr->D, tr->leaves, tr->nleaves, tr->var[V_U + c], tr->uprev[c]);
+    GFSHIP_HIP (hipGetLastError ());
+    int e = bc_scalar (tr, tr->uprev[c]);
+    if (e) return e;
+  }
+  return GFSHIP_OK;
 }
 
 // ---- C ABI -------------------------------------------------------------------------------------
@@ -2992,9 +3021,9 @@ int gfship_tree_upload (gfship_tree * tr, int var, int level, const double * in)
 
 int gfship_tree_download (gfship_tree * tr, int var, int level, double * out)
 {
-  GFSHIP_CHECK (tr && out && var >= 0 && var < abi_nvar && level >= 0 && level <= tr->H.depth, GFSHIP_EINVAL,
+  GFSHIP_CHECK (tr && out && tree_variable (tr, var) && level >= 0 && level <= tr->H.depth, GFSHIP_EINVAL,
 		"gfship_tree_download: bad argument");
-  GFSHIP_HIP (hipMemcpyAsync (out, tr->var[abi_var[var]] + tr->H.off[level], (size_t) tr->H.lsize (level)*sizeof (double),
+  GFSHIP_HIP (hipMemcpyAsync (out, tree_variable (tr, var) + tr->H.off[level], (size_t) tr->H.lsize (level)*sizeof (double),
 			      hipMemcpyDeviceToHost, tr->stream));
   GFSHIP_HIP (hipStreamSynchronize (tr->stream));
   return GFSHIP_OK;

@@ -17,6 +17,11 @@
 //
 // Pinned bit for bit on tests/tree_sampler_reference.py (a restatement of the reference on explicit cell trees,
 // written from the reference) in tests/test_gpu_tree_sampler.py.
+//
+// GfsParticulate with forces on a tree (gfship_particulates_create_tree): the force arithmetic of
+// particles.hip on the locate / interpolate above, with gfs_center_gradient (src/fluid.c:434-475) of Du/Dt and of the
+// vorticity taken at the leaf through tree::center_gradient (tree.hpp) -- a coarser neighbour at x = 3/2, a neighbour
+// with children at x = 3/4.  Pinned on tests/tree_forces_reference.py in tests/test_gpu_tree_particulates.py.
 #include "particles.hpp"
 #include "tree_particles.hpp"
 #include <vector>
@@ -542,6 +547,47 @@ struct TreePartArgs {
   double dt;
 };
 
+// gfs_particle_bc, modules/particulatecommon.c:3326-3395, of a particle that went from po (in the leaf c0) to p:
+// false if it is taken off the list; a periodic side puts it back (p and po change)
+template <int DIM>
+__device__ __forceinline__ bool tree_particle_bc (const TreeSamp & S, const int (& side)[6], const Leaf & c0,
+						  double (& p)[3], double (& po)[3])
+{
+  bool keep = true;
+  Leaf cn;
+  if (!tree_locate<DIM> (S, p, cn)) {
+    // boundarycell (:3151-3186): from the leaf of pos_old over the ftt_cell_face neighbours (same level, leaf or not,
+    // or coarser) to the cell whose neighbour is a boundary cell
+    int d = 0;
+    Cell cc = { c0.l, c0.q };
+    for (int guard = 0; guard < 4*(1 << S.T.depth); guard++) {
+      const double h = 1./(1 << cc.l);
+      const double cellpos[3] = { -0.5 + (S.T.ci (cc) - 0.5)*h, -0.5 + (S.T.cj (cc) - 0.5)*h,
+				  DIM == 3 ? -0.5 + (S.T.ck (cc) - 0.5)*h : 0. };
+      check_intersection<DIM> (cellpos, po, p, &d, h);
+      const Cell nb = S.T.neighbor (cc, d);
+      if (!exists (nb) || !S.T.interior (nb))
+	break;
+      cc = nb;
+    }
+    if (side[d] != GFSHIP_SIDE_PERIODIC)
+      keep = false;                 /* taken off the list, nothing puts it back */
+    else {
+      // periodic_bc_particle (:3189-3214), box of size 1 matching itself
+      const double size = 1.;
+      const double normal = (double) (d ^ 1) - (double) d;
+      double box_face = 0., box_face_nbr = 0.;
+      box_face += normal*size/2.;
+      box_face_nbr -= normal*size/2.;
+      const double tolerance = size/1.e8;
+      const double distance = (p[d/2] - box_face)*normal;
+      p[d/2] = box_face_nbr + distance + normal*tolerance;
+      po[d/2] = p[d/2];
+    }
+  }
+  return keep;
+}
+
 // gfs_particle_list_event (modules/particulatecommon.c:980-1015) of GfsParticle tracers
 template <int DIM>
 __global__ void __launch_bounds__(256)
@@ -576,39 +622,7 @@ tree_particle_list_event_kernel (TreeSamp S, TreePartArgs A)
 	p[a] += A.dt*vel[a];
     }
   }
-  // gfs_particle_bc, :3326-3395
-  bool keep = true;
-  Leaf cn;
-  if (!tree_locate<DIM> (S, p, cn)) {
-    // boundarycell (:3151-3186): from the leaf of pos_old over the ftt_cell_face neighbours (same level, leaf or not,
-    // or coarser) to the cell whose neighbour is a boundary cell
-    int d = 0;
-    Cell cc = { c0.l, c0.q };
-    for (int guard = 0; guard < 4*(1 << S.T.depth); guard++) {
-      const double h = 1./(1 << cc.l);
-      const double cellpos[3] = { -0.5 + (S.T.ci (cc) - 0.5)*h, -0.5 + (S.T.cj (cc) - 0.5)*h,
-				  DIM == 3 ? -0.5 + (S.T.ck (cc) - 0.5)*h : 0. };
-      check_intersection<DIM> (cellpos, po, p, &d, h);
-      const Cell nb = S.T.neighbor (cc, d);
-      if (!exists (nb) || !S.T.interior (nb))
-	break;
-      cc = nb;
-    }
-    if (A.side[d] != GFSHIP_SIDE_PERIODIC)
-      keep = false;                 /* taken off the list, nothing puts it back */
-    else {
-      // periodic_bc_particle (:3189-3214), box of size 1 matching itself
-      const double size = 1.;
-      const double normal = (double) (d ^ 1) - (double) d;
-      double box_face = 0., box_face_nbr = 0.;
-      box_face += normal*size/2.;
-      box_face_nbr -= normal*size/2.;
-      const double tolerance = size/1.e8;
-      const double distance = (p[d/2] - box_face)*normal;
-      p[d/2] = box_face_nbr + distance + normal*tolerance;
-      po[d/2] = p[d/2];
-    }
-  }
+  const bool keep = tree_particle_bc<DIM> (S, A.side, c0, p, po);
 #pragma unroll
   for (int a = 0; a < DIM; a++) {
     A.pos[a][q] = p[a];
@@ -616,6 +630,249 @@ tree_particle_list_event_kernel (TreeSamp S, TreePartArgs A)
   }
   if (!keep)
     A.alive[q] = 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// GfsParticulate with forces on a tree (modules/particulatecommon.c:91-842): the arithmetic of
+// particulate_list_event_kernel (particles.hip) with the cell search, the interpolation and gfs_center_gradient of a
+// tree.  fluid_rho = 1. (a tree has no alpha), the viscosity is the constant of GfsSourceDiffusion {} U.
+// ---------------------------------------------------------------------------------------------
+enum { FORCE_INERTIAL = GFSHIP_FORCE_INERTIAL, FORCE_ADDEDMASS = GFSHIP_FORCE_ADDEDMASS,
+       FORCE_LIFT = GFSHIP_FORCE_LIFT, FORCE_DRAG = GFSHIP_FORCE_DRAG, FORCE_BUOY = GFSHIP_FORCE_BUOY };
+
+struct TreeParticulateArgs {
+  TreePartArgs P;
+  const unsigned * orig;
+  double * vel[3], * force[3], * mass;
+  const double * volume, * dia;
+  const double * uold[3];      // GFSHIP_TREE_UPREV ...
+  int nforces, forces[8];
+  double gravity[3], viscosity;
+  const double * coef[8];      // values of the GfsFunction of force f per slot; nullptr: the default
+  double * cin[6];             // Rep, Urelp, Vrelp, Wrelp, Pdia per slot; [5]: the Rep of GfsForceDrag in 2-D
+};
+
+struct DevValue {            // GFS_VALUEI (cell, v)
+  const double * p;
+  __device__ __forceinline__ double operator() (const Topo & T, Cell c) const { return p[T.gi (c)]; }
+};
+
+// the variables a GfsFunction of a GfsForceCoeff sees (:364-384,462-485,545-573), as particulate_coeff_inputs_kernel
+// writes them on the uniform box
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_particulate_coeff_inputs_kernel (TreeSamp S, TreeParticulateArgs A)
+{
+  const TreePartArgs & P = A.P;
+  const int q = blockIdx.x*blockDim.x + threadIdx.x;
+  if (q >= P.n) return;
+  if (P.alive[q] != 1) return;
+  const double p[3] = { P.pos[0][q], P.pos[1][q], DIM == 3 ? P.pos[2][q] : 0. };
+  Leaf c0;
+  if (!tree_locate<DIM> (S, p, c0)) return;
+  const unsigned o = A.orig[q];
+  const double fluid_rho = 1.;
+  Vars<DIM> uu;
+#pragma unroll
+  for (int a = 0; a < DIM; a++) uu.p[a] = P.u[a];
+  double fvel[DIM];
+  tree_interpolate<DIM, DIM> (S, uu, c0, p, fvel);
+  double rel[3] = { 0. - A.vel[0][o], 0. - A.vel[1][o], 0. - A.vel[2][o] };
+#pragma unroll
+  for (int c = 0; c < DIM; c++)
+    rel[c] = fvel[c] - A.vel[c][o];
+  const double norm = sqrt (rel[0]*rel[0] + rel[1]*rel[1] + rel[2]*rel[2]);
+  const double dia = A.dia[o];
+  const double viscosity = A.viscosity == 0 ? 0.001 : A.viscosity;      /* :372-375, 461-464 */
+  A.cin[0][q] = norm*dia*fluid_rho/viscosity;
+  A.cin[1][q] = rel[0]; A.cin[2][q] = rel[1]; A.cin[3][q] = rel[2];
+  A.cin[4][q] = dia;
+  if (DIM == 2)      /* compute_drag_force takes the norm of the two components in 2-D (:549-556) */
+    A.cin[5][q] = sqrt (rel[0]*rel[0] + rel[1]*rel[1])*dia*fluid_rho/viscosity;
+}
+
+// gfs_particulate_event (:768-842) in a gfs_particle_list_event (:980-1015)
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
+{
+  const TreePartArgs & P = A.P;
+  const int q = blockIdx.x*blockDim.x + threadIdx.x;
+  if (q >= P.n) return;
+  if (P.alive[q] != 1) return;
+  double p[3] = { P.pos[0][q], P.pos[1][q], DIM == 3 ? P.pos[2][q] : 0. };
+  Leaf c0;
+  // remove_particles_not_in_domain, :955-969
+  if (!tree_locate<DIM> (S, p, c0)) {
+    P.alive[q] = 0;
+    return;
+  }
+  const unsigned o = A.orig[q];
+  const Cell cell = { c0.l, c0.q };
+  const double size = 1./(1 << c0.l);      /* ftt_cell_size of the leaf */
+  const double fluid_rho = 1.;
+  const double dt = P.dt;
+  double po[3] = { p[0], p[1], p[2] };
+  double vel[3] = { A.vel[0][o], A.vel[1][o], A.vel[2][o] };
+  double mass = A.mass[o];
+  const double volume = A.volume[o];
+  double pf[3] = { 0., 0., 0. };
+  // every force is a function of the state at the start of the event: what several of them need -- the fluid
+  // velocity at the particle, Du/Dt, the gradients of the velocity at the leaf -- is evaluated once (the reference
+  // re-evaluates the same expressions per force: same bits)
+  bool need_fvel = false, need_dudt = false, need_grad = false;
+  for (int f = 0; f < A.nforces; f++) {
+    need_fvel = need_fvel || A.forces[f] != FORCE_BUOY;
+    need_dudt = need_dudt || A.forces[f] == FORCE_INERTIAL || A.forces[f] == FORCE_ADDEDMASS;
+    need_grad = need_grad || A.forces[f] == FORCE_INERTIAL || A.forces[f] == FORCE_ADDEDMASS || A.forces[f] == FORCE_LIFT;
+  }
+  double fvel[3] = { 0., 0., 0. }, fveln[3] = { 0., 0., 0. }, dudt[3] = { 0., 0., 0. };
+  if (need_dudt) {
+    // U and Un at the particle in one pass over the corner rows of the leaf
+    Vars<2*DIM> uu;
+#pragma unroll
+    for (int a = 0; a < DIM; a++) { uu.p[a] = P.u[a]; uu.p[DIM + a] = A.uold[a]; }
+    double r[2*DIM];
+    tree_interpolate<DIM, 2*DIM> (S, uu, c0, p, r);
+#pragma unroll
+    for (int a = 0; a < DIM; a++) { fvel[a] = r[a]; fveln[a] = r[DIM + a]; }
+  }
+  else if (need_fvel) {
+    Vars<DIM> uu;
+#pragma unroll
+    for (int a = 0; a < DIM; a++) uu.p[a] = P.u[a];
+    double r[DIM];
+    tree_interpolate<DIM, DIM> (S, uu, c0, p, r);
+#pragma unroll
+    for (int a = 0; a < DIM; a++) fvel[a] = r[a];
+  }
+  // grad[c][c2] = gfs_center_gradient (cell, c2, u[c]) (src/fluid.c:434-475; not yet divided by the size of the
+  // leaf: Du/Dt divides the product with u[c2], vorticity_vector the difference)
+  double grad[DIM][DIM];
+#pragma unroll
+  for (int c = 0; c < DIM; c++)
+#pragma unroll
+    for (int c2 = 0; c2 < DIM; c2++)
+      grad[c][c2] = 0.;
+  if (need_grad) {
+    // (no unroll request on the loop over the rows: the stencil code holds loops over the children of a face, the
+    // early unroll pass cannot take the loop around them and a later one does -- the build log shows no scratch,
+    // DESIGN.md 11.28; spelling the rows out by hand sends the tables of the tree to scratch)
+    for (int c = 0; c < DIM; c++) {
+      DevValue uc = { P.u[c] };
+#pragma unroll
+      for (int c2 = 0; c2 < DIM; c2++)
+	grad[c][c2] = tree::center_gradient (S.T, cell, c2, uc);
+    }
+  }
+  if (need_dudt && dt > 0.) {      // compute_inertial_force, :285-336
+#pragma unroll
+    for (int c = 0; c < DIM; c++)
+      dudt[c] = fluid_rho*(fvel[c] - fveln[c])/dt;
+#pragma unroll
+    for (int c = 0; c < DIM; c++)
+#pragma unroll
+      for (int c2 = 0; c2 < DIM; c2++)
+	dudt[c] += fluid_rho*grad[c][c2]*P.u[c2][c0.g]/size;
+  }
+  for (int f = 0; f < A.nforces; f++) {
+    double force[3] = { 0., 0., 0. };
+    switch (A.forces[f]) {
+    case FORCE_INERTIAL:
+      force[0] = dudt[0]; force[1] = dudt[1]; force[2] = dudt[2];
+      break;
+    case FORCE_ADDEDMASS: {     // compute_addedmass_force, :363-427
+      force[0] = dudt[0]; force[1] = dudt[1]; force[2] = dudt[2];
+      const double cm = A.coef[f] ? A.coef[f][q] : 0.5;
+#pragma unroll
+      for (int c = 0; c < DIM; c++)
+	force[c] *= cm;
+      mass += fluid_rho*volume*cm;      /* :391 */
+      break;
+    }
+    case FORCE_LIFT: {          // compute_lift_force, :455-524; vorticity_vector, :146-168
+      double rel[3] = { 0., 0., 0. }, vort[3];
+#pragma unroll
+      for (int c = 0; c < DIM; c++)
+	rel[c] = fvel[c] - vel[c];
+      if (DIM == 2) {
+	vort[0] = 0.; vort[1] = 0.;
+	vort[2] = (grad[1][0] - grad[0][1])/size;
+      }
+      else {
+	vort[0] = (grad[DIM - 1][1] - grad[1][DIM - 1])/size;
+	vort[1] = (grad[0][DIM - 1] - grad[DIM - 1][0])/size;
+	vort[2] = (grad[1][0] - grad[0][1])/size;
+      }
+      const double cl = A.coef[f] ? A.coef[f][q] : 0.5;
+      if (DIM == 2) {
+	force[0] = fluid_rho*cl*rel[1]*vort[2];
+	force[1] = -fluid_rho*cl*rel[0]*vort[2];
+      }
+      else {
+	force[0] = fluid_rho*cl*(rel[1]*vort[2] - rel[2]*vort[1]);
+	force[1] = fluid_rho*cl*(rel[2]*vort[0] - rel[0]*vort[2]);
+	force[2] = fluid_rho*cl*(rel[0]*vort[1] - rel[1]*vort[0]);
+      }
+      break;
+    }
+    case FORCE_DRAG: {          // compute_drag_force, :527-588
+      double rel[3] = { 0., 0., 0. };
+#pragma unroll
+      for (int c = 0; c < DIM; c++)
+	rel[c] = fvel[c] - vel[c];
+      const double dia = A.dia[o];
+      const double norm = DIM == 3 ? sqrt (rel[0]*rel[0] + rel[1]*rel[1] + rel[2]*rel[2]) :
+	sqrt (rel[0]*rel[0] + rel[1]*rel[1]);
+      if (A.viscosity == 0)       /* :561-562: no drag without viscosity */
+	break;
+      const double Re = norm*dia*fluid_rho/A.viscosity;
+      double cd;
+      if (A.coef[f])
+	cd = A.coef[f][q];
+      else if (Re < 1e-8)
+	break;
+      else if (Re < 50.0)
+	cd = 16.*(1. + 0.15*sqrt (Re))/Re;
+      else
+	cd = 48.*(1. - 2.21/sqrt (Re))/Re;
+#pragma unroll
+      for (int c = 0; c < DIM; c++)
+	force[c] += 3./(4.*dia)*cd*norm*rel[c]*fluid_rho;
+      break;
+    }
+    case FORCE_BUOY:            // compute_buoyancy_force, :619-653
+#pragma unroll
+      for (int c = 0; c < DIM; c++)
+	force[c] += (mass/volume - fluid_rho)*A.gravity[c];
+      break;
+    }
+    // compute_forces, :738-752
+#pragma unroll
+    for (int c = 0; c < DIM; c++)
+      pf[c] = force[c]*volume + pf[c];
+    if (DIM == 2) pf[2] = 0.;
+  }
+#pragma unroll
+  for (int c = 0; c < DIM; c++) {      /* :828-837 */
+    p[c] += vel[c]*dt/2.;
+    vel[c] += pf[c]*dt/mass;
+    p[c] += vel[c]*dt/2.;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    A.vel[c][o] = vel[c];
+    A.force[c][o] = pf[c];
+  }
+  A.mass[o] = mass;
+  const bool keep = tree_particle_bc<DIM> (S, P.side, c0, p, po);
+#pragma unroll
+  for (int a = 0; a < DIM; a++) {
+    P.pos[a][q] = p[a];
+    P.old[a][q] = po[a];
+  }
+  if (!keep)
+    P.alive[q] = 0;
 }
 
 // key of the sort: the leaf that holds the particle (its index in the concatenated levels), dead or outside last
@@ -673,6 +930,89 @@ int tree_particle_list_event (gfship_particles * pl)
   else
     hipLaunchKernelGGL (tree_particle_list_event_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), A);
   GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
+// gfs_particle_list_event (modules/particulatecommon.c:980-1015) of a list of GfsParticulate with forces
+int tree_particulate_list_event (gfship_particles * pl)
+{
+  TreeView V;
+  SamplerTables * S;
+  int r = sampler_get (pl->tree, &V, &S);
+  if (r) return r;
+  const int dim = V.H.dim;
+  TreeParticulateArgs A;
+  TreePartArgs & P = A.P;
+  for (int d = 0; d < 6; d++) P.side[d] = d < 2*dim ? V.side[d] : GFSHIP_SIDE_PERIODIC;
+  P.n = pl->n;
+  const int uvar[3] = { GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP_TREE_W };
+  for (int c = 0; c < 3; c++) {
+    P.pos[c] = pl->pos[c];
+    P.old[c] = pl->old[c];
+    P.u[c] = c < dim ? tree_variable (pl->tree, uvar[c]) : nullptr;
+    A.vel[c] = pl->vel[c];
+    A.force[c] = pl->force[c];
+    A.uold[c] = c < dim ? V.uprev[c] : nullptr;
+    A.gravity[c] = pl->gravity[c];
+  }
+  P.alive = pl->alive;
+  P.dt = V.dt;
+  A.orig = pl->orig;
+  A.mass = pl->mass; A.volume = pl->volume; A.dia = pl->dia;
+  A.nforces = pl->nforces;
+  bool any = false, reads_un = false;
+  for (int f = 0; f < 8; f++) {
+    A.forces[f] = pl->forces[f];
+    A.coef[f] = nullptr;
+    if (f < pl->nforces && pl->coef_fn[f]) any = true;
+    if (f < pl->nforces && (pl->forces[f] == GFSHIP_FORCE_INERTIAL || pl->forces[f] == GFSHIP_FORCE_ADDEDMASS))
+      reads_un = true;
+  }
+  GFSHIP_CHECK (!reads_un || V.uprev[0], GFSHIP_EINVAL, "the tree has no Un, Vn, Wn (gfship_particles_set_forces)");
+  A.viscosity = V.viscosity;
+  for (int q = 0; q < 6; q++) A.cin[q] = nullptr;
+  const int block = 256, grid = (pl->n + block - 1)/block;
+  const TreeSamp TS = tree_samp (V, S);
+  if (any) {
+    /* the GfsFunction coefficients: inputs of every particle, then one compiled kernel per function */
+    if (pl->coef_cap < pl->cap) {
+      for (int q = 0; q < 6; q++) {
+	if (pl->cin[q]) GFSHIP_HIP (hipFree (pl->cin[q]));
+	pl->cin[q] = nullptr;
+	GFSHIP_HIP (hipMalloc ((void **) &pl->cin[q], (size_t) pl->cap*sizeof (double)));
+      }
+      for (int f = 0; f < 8; f++) {
+	if (pl->coef[f]) GFSHIP_HIP (hipFree (pl->coef[f]));
+	pl->coef[f] = nullptr;
+      }
+      pl->coef_cap = pl->cap;
+    }
+    for (int q = 0; q < 6; q++) A.cin[q] = pl->cin[q];
+    if (dim == 3)
+      hipLaunchKernelGGL (tree_particulate_coeff_inputs_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+    else
+      hipLaunchKernelGGL (tree_particulate_coeff_inputs_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+    GFSHIP_HIP (hipGetLastError ());
+    const double * rel[3] = { pl->cin[1], pl->cin[2], pl->cin[3] };
+    for (int f = 0; f < pl->nforces; f++)
+      if (pl->coef_fn[f]) {
+	if (!pl->coef[f])
+	  GFSHIP_HIP (hipMalloc ((void **) &pl->coef[f], (size_t) pl->coef_cap*sizeof (double)));
+	const double * rep = dim == 2 && pl->forces[f] == GFSHIP_FORCE_DRAG ? pl->cin[5] : pl->cin[0];
+	r = rtc_launch_coefficient (pl->coef_fn[f], V.stream, pl->n, P.alive, rep, rel, pl->cin[4], V.t, pl->coef[f]);
+	if (r) return r;
+	A.coef[f] = pl->coef[f];
+      }
+  }
+  if (dim == 3)
+    hipLaunchKernelGGL (tree_particulate_list_event_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+  else
+    hipLaunchKernelGGL (tree_particulate_list_event_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+  GFSHIP_HIP (hipGetLastError ());
+  // the velocity of this step for the inertial force of the next one (:1003-1012: only for GfsForceInertial objects)
+  for (int f = 0; f < pl->nforces; f++)
+    if (pl->forces[f] == GFSHIP_FORCE_INERTIAL)
+      return tree_previous_vel (pl->tree);
   return GFSHIP_OK;
 }
 
@@ -767,6 +1107,27 @@ int gfship_particles_create_tree (gfship_particles ** out, gfship_tree * tr, int
   pl->stream = V.stream;
   pl->dim = V.H.dim;
   r = particles_alloc (pl, np, pos, id);
+  if (r) {
+    gfship_particles_destroy (pl);
+    return r;
+  }
+  *out = pl;
+  return GFSHIP_OK;
+}
+
+// a GfsParticleList of GfsParticulate on a tree: modules/particulatecommon.c:1022-1093 with the members of
+// GfsParticulate (modules/particulatecommon.h:35-48; gfs_particulate_read, :844-905)
+int gfship_particulates_create_tree (gfship_particles ** out, gfship_tree * tr, int np, const double * pos,
+				     const unsigned * id, const double * vel, const double * mass, const double * volume)
+{
+  GFSHIP_CHECK (out != nullptr, GFSHIP_EINVAL, "invalid argument");
+  *out = nullptr;
+  GFSHIP_CHECK (tr && np >= 0 && (np == 0 || (pos && id && vel && mass && volume)), GFSHIP_EINVAL, "invalid argument");
+  gfship_particles * pl = nullptr;
+  int r = gfship_particles_create_tree (&pl, tr, np, pos, id);
+  if (r) return r;
+  const double none[3] = { 0., 0., 0. };
+  r = particulate_alloc (pl, np ? vel : none, np ? mass : none, np ? volume : none);
   if (r) {
     gfship_particles_destroy (pl);
     return r;

@@ -11,7 +11,9 @@ struct TreeView {
   int device, ncell, nleaves;
   const tree::Cell * hleaves;       // host: interior leaves in traversal order
   const int * side;                 // GFSHIP_SIDE_* of the 2*dim sides
-  double dt;
+  double dt, t;
+  double viscosity;                 // of U (gfship_tree_set_viscosity (tree, 0, nu)); 0.: no GfsSourceDiffusion
+  double * uprev[3];                // GFSHIP_TREE_UPREV ...; nullptr until tree_previous_vel has run
   // the tables of the sampler, built on first use and freed with the tree
   void ** sampler;
   void (** sampler_free) (void *);
@@ -20,5 +22,8 @@ struct TreeView {
 void tree_view (gfship_tree * tr, TreeView * v);
 // the device array (all levels) of the variable GFSHIP_TREE_* `var'; nullptr: no such variable
 double * tree_variable (gfship_tree * tr, int var);
+// store_domain_previous_vel on the tree: GFSHIP_TREE_UPREV ... = U, V, W of this moment (allocates them the first time)
+int tree_previous_vel (gfship_tree * tr);
+int tree_device (gfship_tree * tr);
 
 }

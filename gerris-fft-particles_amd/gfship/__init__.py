@@ -211,6 +211,7 @@ SIGNATURES = {
     "gfship_tree_interpolate": (_i, [_vp, _i, _i, _pd, _pd, C.POINTER(C.c_ubyte)]),
     "gfship_tree_sampler_stats": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "gfship_particles_create_tree": (_i, [C.POINTER(_vp), _vp, _i, _pd, C.POINTER(C.c_uint)]),
+    "gfship_particulates_create_tree": (_i, [C.POINTER(_vp), _vp, _i, _pd, C.POINTER(C.c_uint), _pd, _pd, _pd]),
 }
 
 
@@ -787,14 +788,26 @@ class InitSpectraParams(C.Structure):
 
 
 class ParticleList:
-    """GfsParticleList of GfsParticle tracers on the device; sim: a Simulation, or a Tree (tracers only)."""
+    """GfsParticleList of GfsParticle tracers on the device; sim: a Simulation, or a Tree (tracers, or with
+    particulate = (vel, mass, volume) a list of GfsParticulate: Tree.particulates)."""
 
-    def __init__(self, sim, pos, ids):
+    def __init__(self, sim, pos, ids, particulate=None):
         pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         assert len(pos) == len(ids)
         self.sim, self.n0 = sim, len(ids)
         p = _vp()
+        if particulate is not None:
+            assert isinstance(sim, Tree)
+            vel = np.ascontiguousarray(particulate[0], dtype=np.float64).reshape(-1, 3)
+            mass = np.ascontiguousarray(particulate[1], dtype=np.float64)
+            volume = np.ascontiguousarray(particulate[2], dtype=np.float64)
+            assert len(vel) == len(mass) == len(volume) == len(ids)
+            _check(lib().gfship_particulates_create_tree(
+                C.byref(p), sim.ptr, len(ids), pos.ctypes.data_as(_pd), ids.ctypes.data_as(C.POINTER(C.c_uint)),
+                vel.ctypes.data_as(_pd), mass.ctypes.data_as(_pd), volume.ctypes.data_as(_pd)))
+            self.ptr = p
+            return
         create = lib().gfship_particles_create_tree if isinstance(sim, Tree) else lib().gfship_particles_create
         _check(create(C.byref(p), sim.ptr, len(ids), pos.ctypes.data_as(_pd),
                       ids.ctypes.data_as(C.POINTER(C.c_uint))))
@@ -927,6 +940,7 @@ class Tree:
     """gfship_tree: a GfsSimulation on one periodic box refined by a GfsRefine function (coarse-fine
     stencils; quadtree or octree).  refine (x, y) or refine (x, y, z) -> level wanted there."""
     P, PMAC, U, V, GX, GY, GMACX, GMACY, UN0, UN1, UN2, UN3, W, GZ, GMACZ, UN4, UN5, DIV, BCVAL, RES, T0, T1, BCU, BCV, BCW = range(25)
+    UPREV, VPREV, WPREV = 25, 26, 27      # Un, Vn, Wn: once a list of particulates has a force with a coefficient
 
     def __init__(self, refine, dim=2, device=0, sides=None):
         self.dim = dim
@@ -1052,6 +1066,11 @@ class Tree:
     def particles(self, pos, ids):
         """a GfsParticleList of GfsParticle tracers on this tree (destroy it before the tree)"""
         return ParticleList(self, pos, ids)
+
+    def particulates(self, pos, ids, vel, mass, volume):
+        """a GfsParticleList of GfsParticulate on this tree: set_forces, set_force_coefficient, particulate_state
+        and event work on it as on the uniform box (destroy it before the tree)"""
+        return ParticleList(self, pos, ids, particulate=(vel, mass, volume))
 
     def sampler_stats(self):
         """the corner interpolators of the sampler: (corners of leaves, corners that read the table, table

@@ -776,13 +776,19 @@ enum { GFSHIP_TREE_P = 0, GFSHIP_TREE_PMAC, GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP
        GFSHIP_TREE_GMACX, GFSHIP_TREE_GMACY, GFSHIP_TREE_UN0, GFSHIP_TREE_UN1, GFSHIP_TREE_UN2,
        GFSHIP_TREE_UN3, GFSHIP_TREE_W, GFSHIP_TREE_GZ, GFSHIP_TREE_GMACZ, GFSHIP_TREE_UN4,
        GFSHIP_TREE_UN5, GFSHIP_TREE_DIV, GFSHIP_TREE_BCVAL, GFSHIP_TREE_RES,
-       GFSHIP_TREE_T0, GFSHIP_TREE_T1, GFSHIP_TREE_BCU, GFSHIP_TREE_BCV, GFSHIP_TREE_BCW };
+       GFSHIP_TREE_T0, GFSHIP_TREE_T1, GFSHIP_TREE_BCU, GFSHIP_TREE_BCV, GFSHIP_TREE_BCW,
+       GFSHIP_TREE_UPREV, GFSHIP_TREE_VPREV, GFSHIP_TREE_WPREV };
 				    /* variables of a tree: P, Pmac, U, V, g, gmac, f[d].un; then the 3-D ones;
 				       DIV: the result of gfship_tree_divergence / the right-hand side of
 				       gfship_tree_poisson_solve; BCVAL: the values of the conditions of P, one per
 				       ghost cell (at the face centres); RES: the residual of the last solve;
 				       T0, T1: the tracers of gfship_tree_add_tracer; BCU, BCV, BCW: the values of the
-				       conditions of U, V, W, one per ghost cell (at the face centres) */
+				       conditions of U, V, W, one per ghost cell (at the face centres);
+				       UPREV, VPREV, WPREV: Un, Vn, Wn of the GfsForceCoeff objects
+				       (modules/particulatecommon.c:179-185), which exist once a list of
+				       particulates of the tree has a force that reads a coefficient:
+				       gfship_tree_download returns GFSHIP_EINVAL before (they are the library's to
+				       write: gfship_tree_upload does not take them) */
 int  gfship_tree_create (gfship_tree ** tree, int dim, gfship_refine_fn refine, void * ctx, int device);
 /* the same with GfsBoundary sides (side[d] = GFSHIP_SIDE_PERIODIC or GFSHIP_SIDE_BOUNDARY; the ghost
    cells of a boundary are refined like the cells they touch, gfs_domain_match): such a tree carries
@@ -914,9 +920,33 @@ int  gfship_tree_sampler_stats (gfship_tree * tree, long long stats[5]);
    is read as gfship_tree_interpolate reads it (call the event after gfship_tree_start / _step).
    gfship_particles_count, _slots, _download, _download_old, _sort, _set_sort_interval and _destroy work on such a
    list (destroy it before its tree); everything of particulates, forces, coupling and migration returns
-   GFSHIP_EUNSUPPORTED. */
+   GFSHIP_EUNSUPPORTED on a list made by this call. */
 int  gfship_particles_create_tree (gfship_particles ** pl, gfship_tree * tree, int np,
 				   const double * pos, const unsigned * id);
+/* a GfsParticleList of GfsParticulate on a tree: gfship_particles_create_tree, then what
+   gfship_particles_set_particulate does (vel = 3*np doubles, mass and volume np doubles; the diameter of
+   compute_drag_force, modules/particulatecommon.c:549, and rb of distance_normalization, :2091, from the host's
+   pow; force = 0).  On such a list gfship_particles_set_forces (gfs_force_coeff_read, :166-210),
+   gfship_particles_set_force_coefficient, gfship_particles_download_particulate and gfship_particle_list_event
+   work as on the uniform box: gfs_particle_list_event (:980-1015) with gfs_particulate_event (:768-842) and the
+   compute_*_force functions (:255-655) in the reference's order, gfs_particle_bc as for the tracers of a tree.
+   The data of the fluid are those of the tree: fluid_rho = 1. (a tree has no alpha); the viscosity is the
+   constant of gfship_tree_set_viscosity (tree, 0, nu) (0: no drag, 0.001 in Rep); dt = gfship_tree_dt; the t of
+   a coefficient function = gfship_tree_time; gravity = the argument of gfship_particles_set_forces.
+   gfs_center_gradient (src/fluid.c:434-475) of Du/Dt (:297-300) and of vorticity_vector (:142-164) is taken at
+   the leaf that holds the particle: next to a change of level through gfs_neighbor_value (:364-396) -- a coarser
+   neighbour at x = 3/2 with interpolate_1D1 / interpolate_2D1 (:171-245) in the coarse cell, a neighbour with
+   children at x = 3/4 with the mean of the children on the face (:64-93).
+   Un, Vn, Wn (store_domain_previous_vel, :99-113) are the variables GFSHIP_TREE_UPREV, _VPREV, _WPREV of the
+   tree: the copy of U, V, W on the leaves of every level, then the default GfsBc of a scalar on the ghost leaves
+   (the value of the cell a ghost of a GfsBoundary side touches, the periodic image elsewhere).  Stored by
+   gfship_particles_set_forces when any force but GfsForceBuoy is listed and after every event of a list with a
+   GfsForceInertial.
+   gfship_particles_set_particulate, the coupling calls, gfship_particles_set_kernel, _set_migrate and
+   _record_size keep returning GFSHIP_EUNSUPPORTED on every list of a tree. */
+int  gfship_particulates_create_tree (gfship_particles ** pl, gfship_tree * tree, int np,
+				      const double * pos, const unsigned * id,
+				      const double * vel, const double * mass, const double * volume);
 
 /* ---- instrumentation -------------------------------------------------------------------- */
 

@@ -2,7 +2,7 @@
 """Time steps of the refined-tree path (gfship_tree) on an octree / quadtree with BOX
 extra levels inside the central cube / square: leaves, dependency levels of the finest sweep, ms per
 step, Mleaf-steps/s.  Not the benchmarked path (that is bench.py); a measurement to quote.
-usage: tree_bench.py [dim] [level] [box] [steps] [nu] [--snapshot] [--tracers N]
+usage: tree_bench.py [dim] [level] [box] [steps] [nu] [--snapshot] [--tracers N] [--particulates N]
 nu: GfsSourceDiffusion on every velocity component (default 0: inviscid)
 --snapshot: also time the file image of the tree (gfship_tree_snapshot_write) for P, Pmac, U, V
 (, W): the first call, which builds the offset tables, and the median of 20 more (kernel + copy to the host),
@@ -11,7 +11,10 @@ memory-copy trace of the same command.
 --tracers N: after the steps, a GfsParticleList of N GfsParticle tracers (the positions of tools/particles_bench.py)
 on the tree: one event to warm up (it sorts the list by leaf), then the mean of 10 gfship_particle_list_event, ended
 by gfship_particles_count (a stream synchronise); Mparticle-steps/s of the event and the size of the corner tables
-of the sampler."""
+of the sampler.
+--particulates N: the same for a list of N GfsParticulate with the five forces and their default coefficients (the
+particles and forces of tools/particles_bench.py --particulates; the drag acts where nu is given): the event of
+tree_particulate_list_event_kernel and, after it, the copy of U, V, W into Un, Vn, Wn."""
 import os
 import sys
 import time
@@ -28,6 +31,11 @@ ntracers = 0
 if "--tracers" in sys.argv:
     k = sys.argv.index("--tracers")
     ntracers = int(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
+nparticulates = 0
+if "--particulates" in sys.argv:
+    k = sys.argv.index("--particulates")
+    nparticulates = int(sys.argv[k + 1])
     del sys.argv[k:k + 2]
 dim = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 level = int(sys.argv[2]) if len(sys.argv) > 2 else 4
@@ -106,10 +114,34 @@ if ntracers:
             "leaf_corners": st[0], "table_corners": st[1], "table_share": round(st[1] / st[0], 4),
             "table_entries": st[2], "table_bytes": st[3], "longest_interpolator": st[4]}
     pl.destroy()
+part = {}
+if nparticulates:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from particle_cases import lcg_positions_fast
+    pos, ids = lcg_positions_fast(nparticulates)
+    if dim == 2:
+        pos[:, 2] = 0.
+    rng = np.random.default_rng(1)
+    vol = 1e-6 * (0.5 + rng.random(nparticulates))
+    pl = g.particulates(pos, ids, np.zeros((nparticulates, 3)), 2. * vol, vol)
+    pl.set_forces([gfship.FORCE_INERTIAL, gfship.FORCE_ADDEDMASS, gfship.FORCE_LIFT, gfship.FORCE_DRAG,
+                   gfship.FORCE_BUOY], (0., 1., 0.))
+    pl.event()
+    pl.count()
+    events = 10
+    t0 = time.perf_counter()
+    for _ in range(events):
+        pl.event()
+    alive = pl.count()
+    dt_event = (time.perf_counter() - t0) / events
+    part = {"particulates": nparticulates, "particulates_alive": alive,
+            "particulates_ms_per_event": round(dt_event * 1e3, 3),
+            "particulates_Mparticle_steps_per_s": round(nparticulates / dt_event / 1e6, 1)}
+    pl.destroy()
 print({"dim": dim, "levels": [level, g.depth], "leaves": nleaves, "finest_sweep_cells": nc,
        "finest_sweep_dependency_levels": nl, "tree_build_s": round(t_build, 2),
        "ms_per_step": round(ms, 2), "Mleaf_steps_per_s": round(nleaves / ms / 1e3, 3),
        "niter": [g.projection_params.niter, g.approx_projection_params.niter],
-       **snap, **trac,
+       **snap, **trac, **part,
        **({"nu": nu, "diffusion_niter": [g.diffusion_params(c).niter for c in range(dim)]} if nu != 0. else {})})
 g.destroy()
