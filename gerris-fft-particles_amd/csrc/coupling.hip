@@ -32,7 +32,7 @@
 
 namespace gfship {
 
-constexpr size_t RECORD_CAP = (size_t) 1 << 22;
+constexpr size_t RECORD_CAP = COUPLING_RECORD_CAP;
 constexpr int DESCENT_MAXDEPTH = 15;
 
 // record slots per particle.  A leaf passes cond_kernel if |centre - pos| - (h/2) sqrt (dim) <= rkernel or if
@@ -59,30 +59,6 @@ static int stride_check (const gfship_domain * dom, double rkernel)
 		"GfsSourceParticulate: a kernel of rkernel = %g may reach %llu leaves of this box, more than "
 		"the %llu records of a chunk", rkernel, stride, (unsigned long long) RECORD_CAP);
   return GFSHIP_OK;
-}
-
-// cond_kernel (:2126-2156) of cell ix[] of level l (0-based indices from the low corner of the box)
-template <int DIM>
-__device__ __forceinline__ bool cond_kernel (int l, const int ix[3], const double p[3], double rkernel)
-{
-  const double cellsize = 1./(double) (1 << l);
-  double pos[3] = { 0., 0., 0. };
-#pragma unroll
-  for (int c = 0; c < DIM; c++)
-    pos[c] = -0.5 + (ix[c] + 0.5)*cellsize;      /* ftt_cell_pos: dyadic, exact */
-  const double size = cellsize/2.;
-  const double radeq = DIM == 2 ? size*sqrt (2.) : size*sqrt (3.);
-  const double dist = DIM == 2 ?
-    sqrt ((pos[0] - p[0])*(pos[0] - p[0]) + (pos[1] - p[1])*(pos[1] - p[1])) :
-    sqrt ((pos[0] - p[0])*(pos[0] - p[0]) + (pos[1] - p[1])*(pos[1] - p[1]) +
-	  (pos[2] - p[2])*(pos[2] - p[2]));
-  if (dist - radeq <= rkernel)
-    return true;
-#pragma unroll
-  for (int c = 0; c < DIM; c++)
-    if (p[c] > pos[c] + size || p[c] < pos[c] - size)
-      return false;
-  return true;
 }
 
 // gfs_domain_cell_traverse_condition (src/domain.c:1550-1574), FTT_PRE_ORDER, FTT_TRAVERSE_LEAFS: the
@@ -370,7 +346,7 @@ void coupling_free (gfship_particles * pl)
 
 // the work arrays.  The void fraction needs the two key arrays alone (spreading = false: 16 B per particle);
 // the spreading also q, K, the per-particle arrays of a chunk and the slot map of the list
-static int coupling_reserve (gfship_particles * pl, size_t nrec, size_t npart, bool spreading)
+int coupling_reserve (gfship_particles * pl, size_t nrec, size_t npart, bool spreading)
 {
   auto fresh = [] (void ** a, size_t bytes) -> hipError_t {
     if (*a) (void) hipFree (*a);
@@ -378,7 +354,7 @@ static int coupling_reserve (gfship_particles * pl, size_t nrec, size_t npart, b
     return hipMalloc (a, bytes);
   };
   if (nrec > pl->ckey_cap) {
-    GFSHIP_HIP (hipStreamSynchronize (pl->dom->stream));
+    GFSHIP_HIP (hipStreamSynchronize (pl->stream));
     pl->ckey_cap = 0;
     GFSHIP_HIP (fresh ((void **) &pl->ckey, nrec*sizeof (unsigned long long)));
     GFSHIP_HIP (fresh ((void **) &pl->ckey2, nrec*sizeof (unsigned long long)));
@@ -391,7 +367,7 @@ static int coupling_reserve (gfship_particles * pl, size_t nrec, size_t npart, b
     pl->where_cap = pl->cap;
   }
   if (nrec > pl->crec_cap) {
-    GFSHIP_HIP (hipStreamSynchronize (pl->dom->stream));
+    GFSHIP_HIP (hipStreamSynchronize (pl->stream));
     pl->crec_cap = 0;
     for (int c = 0; c < 3; c++)
       GFSHIP_HIP (fresh ((void **) &pl->cq[c], nrec*sizeof (double)));
@@ -400,7 +376,7 @@ static int coupling_reserve (gfship_particles * pl, size_t nrec, size_t npart, b
     pl->crec_cap = nrec;
   }
   if (npart > pl->cpart_cap) {
-    GFSHIP_HIP (hipStreamSynchronize (pl->dom->stream));
+    GFSHIP_HIP (hipStreamSynchronize (pl->stream));
     pl->cpart_cap = 0;
     GFSHIP_HIP (fresh ((void **) &pl->ccorr, npart*sizeof (double)));
     GFSHIP_HIP (fresh ((void **) &pl->ccnt, npart*sizeof (int)));
@@ -411,10 +387,10 @@ static int coupling_reserve (gfship_particles * pl, size_t nrec, size_t npart, b
   return GFSHIP_OK;
 }
 
-static int sort_reserve (gfship_particles * pl, size_t need)
+int coupling_sort_reserve (gfship_particles * pl, size_t need)
 {
   if (need > pl->sort_tmp_bytes) {
-    GFSHIP_HIP (hipStreamSynchronize (pl->dom->stream));
+    GFSHIP_HIP (hipStreamSynchronize (pl->stream));
     if (pl->sort_tmp) GFSHIP_HIP (hipFree (pl->sort_tmp));
     pl->sort_tmp = nullptr;
     pl->sort_tmp_bytes = 0;
@@ -426,7 +402,7 @@ static int sort_reserve (gfship_particles * pl, size_t need)
 
 // bits of the keys: 32 of the creation slot, then those of the cell numbers 0 .. ncell (ncell = pad), which
 // coupling_check keeps below 2^32
-static int key_bits (unsigned long long ncell)
+int coupling_key_bits (unsigned long long ncell)
 {
   int b = 0;
   while (b < 32 && (ncell >> b)) b++;
@@ -481,10 +457,10 @@ int gfship_particulate_field (gfship_particles * pl, gfship_field v)
   }, dom->dim == 3);
   GFSHIP_HIP (hipGetLastError ());
   size_t need = 0;
-  const int bits = key_bits (ncell);
+  const int bits = coupling_key_bits (ncell);
   GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (nullptr, need, pl->ckey, pl->ckey2, pl->n, 0, bits,
 						 dom->stream));
-  if ((r = sort_reserve (pl, need))) return r;
+  if ((r = coupling_sort_reserve (pl, need))) return r;
   size_t tmp_bytes = pl->sort_tmp_bytes;
   GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, pl->n, 0, bits,
 						 dom->stream));
@@ -567,7 +543,7 @@ static int spread_forces (gfship_particles * pl, const gfship_field F[3], double
     return hipEventRecord (e, dom->stream);
   };
   const unsigned long long ncell = (unsigned long long) ncells (L);
-  const int bits = key_bits (ncell);
+  const int bits = coupling_key_bits (ncell);
   const int block = 256;
   hipLaunchKernelGGL (where_kernel, dim3 ((pl->n + block - 1)/block), dim3 (block), 0, dom->stream, pl->n,
 		      pl->orig, pl->where);
@@ -613,7 +589,7 @@ static int spread_forces (gfship_particles * pl, const gfship_field F[3], double
     size_t need = 0;
     GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (nullptr, need, pl->ckey, pl->ckey2, pl->cval, pl->cval2,
 						    nrec, 0, bits, dom->stream));
-    if ((r = sort_reserve (pl, need))) return r;
+    if ((r = coupling_sort_reserve (pl, need))) return r;
     size_t tmp_bytes = pl->sort_tmp_bytes;
     GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, pl->cval,
 						    pl->cval2, nrec, 0, bits, dom->stream));

@@ -13,6 +13,7 @@ void rtc_free (RtcKernel * k);
 // the kernel function of a GfsSourceParticulate: a GfsFunction (spatial) of x, y, z, t, evaluated for the
 // first cnt[r/stride] records of every block of `stride' records
 int  rtc_compile_spatial (gfship_domain * dom, const char * text, RtcKernel ** out);
+int  rtc_compile_spatial_on (int device, const char * text, RtcKernel ** out);       // a list of a tree
 int  rtc_launch_spatial (RtcKernel * k, hipStream_t stream, long nrec, int stride, const int * cnt,
 			 const double * x, const double * y, const double * z, double t, double * out);
 }
@@ -85,6 +86,13 @@ namespace gfship {
 // the refusals of every entry that evaluates the forces of a list (particles.hip)
 int particulate_fluid_check (const gfship_sim_view & v);
 void coupling_free (gfship_particles * pl);   // coupling.hip
+// the work arrays of the void fraction and of the spreading (coupling.hip), shared with the lists of a tree
+// (tree_particles.hip): nrec record slots, npart particles of a chunk, on the stream of the list; a chunk holds
+// at most COUPLING_RECORD_CAP slots
+constexpr size_t COUPLING_RECORD_CAP = (size_t) 1 << 22;
+int coupling_reserve (gfship_particles * pl, size_t nrec, size_t npart, bool spreading);
+int coupling_sort_reserve (gfship_particles * pl, size_t need);
+int coupling_key_bits (unsigned long long ncell);
 // the per-particle arrays of a new list of np tracers (particles.hip); pl->stream is set by the caller
 int particles_alloc (gfship_particles * pl, int np, const double * pos, const unsigned * id);
 // a list on a tree (tree_particles.hip): the event of its tracers, the keys of gfship_particles_sort and their bits
@@ -96,6 +104,10 @@ int particulate_alloc (gfship_particles * pl, const double * vel, const double *
 // a list of particulates on a tree (gfship_particulates_create_tree, tree_particles.hip): its event with forces
 int tree_particulate_list_event (gfship_particles * pl);
 }
+
+// the coupling calls of a tree (gfship_tree_particulate_field ...): lists made by gfship_particulates_create_tree
+#define GFSHIP_TREE_PARTICULATES_ONLY(pl, what) GFSHIP_CHECK ((pl)->tree && (pl)->particulate, GFSHIP_EUNSUPPORTED, \
+    "%s needs a list of particulates of a tree (gfship_particulates_create_tree)", what)
 
 // coupling and migration exist on uniform boxes only, and a list of a tree is born as tracers
 // (gfship_particles_create_tree) or as particulates (gfship_particulates_create_tree)
@@ -130,6 +142,30 @@ __device__ __forceinline__ bool locate (int depth, const double target[3], int i
     }
   }
   ijk[0] = q[0] + 1; ijk[1] = q[1] + 1; ijk[2] = DIM == 3 ? q[2] + 1 : 0;
+  return true;
+}
+
+// cond_kernel (:2126-2156) of cell ix[] of level l (0-based indices from the low corner of the box)
+template <int DIM>
+__device__ __forceinline__ bool cond_kernel (int l, const int ix[3], const double p[3], double rkernel)
+{
+  const double cellsize = 1./(double) (1 << l);
+  double pos[3] = { 0., 0., 0. };
+#pragma unroll
+  for (int c = 0; c < DIM; c++)
+    pos[c] = -0.5 + (ix[c] + 0.5)*cellsize;      /* ftt_cell_pos: dyadic, exact */
+  const double size = cellsize/2.;
+  const double radeq = DIM == 2 ? size*sqrt (2.) : size*sqrt (3.);
+  const double dist = DIM == 2 ?
+    sqrt ((pos[0] - p[0])*(pos[0] - p[0]) + (pos[1] - p[1])*(pos[1] - p[1])) :
+    sqrt ((pos[0] - p[0])*(pos[0] - p[0]) + (pos[1] - p[1])*(pos[1] - p[1]) +
+	  (pos[2] - p[2])*(pos[2] - p[2]));
+  if (dist - radeq <= rkernel)
+    return true;
+#pragma unroll
+  for (int c = 0; c < DIM; c++)
+    if (p[c] > pos[c] + size || p[c] < pos[c] - size)
+      return false;
   return true;
 }
 

@@ -155,10 +155,9 @@ int rtc_compile_coefficient (gfship_domain * dom, const char * text, RtcKernel *
 // (spatial) of x, y, z and t (gfs_function_spatial_value, src/utils.c:1476-1494), evaluated at the
 // normalised distances of the records of the spreading (coupling.hip): record r belongs to particle
 // r/stride of the chunk and is in use if r%stride < cnt[r/stride]
-int rtc_compile_spatial (gfship_domain * dom, const char * text, RtcKernel ** out)
+int rtc_compile_spatial_on (int device, const char * text, RtcKernel ** out)
 {
-  GFSHIP_CHECK (dom != nullptr, GFSHIP_EINVAL, "null argument");
-  return rtc_compile (dom->device, text,
+  return rtc_compile (device, text,
     "static __device__ double gfship_f (double x, double y, double z, double t)\n",
     "extern \"C\" __global__ void gfship_spatial (long nrec, int stride, const int * cnt,\n"
     "    const double * qx, const double * qy, const double * qz, double t, double * out)\n"
@@ -167,6 +166,12 @@ int rtc_compile_spatial (gfship_domain * dom, const char * text, RtcKernel ** ou
     "  if (r >= nrec || (int) (r%stride) >= cnt[r/stride]) return;\n"
     "  out[r] = gfship_f (qx[r], qy[r], qz[r], t);\n"
     "}\n", "gfship_spatial", out);
+}
+
+int rtc_compile_spatial (gfship_domain * dom, const char * text, RtcKernel ** out)
+{
+  GFSHIP_CHECK (dom != nullptr, GFSHIP_EINVAL, "null argument");
+  return rtc_compile_spatial_on (dom->device, text, out);
 }
 
 int rtc_launch_spatial (RtcKernel * k, hipStream_t stream, long nrec, int stride, const int * cnt,

@@ -173,6 +173,10 @@ struct gfship_tree {
   // Un, Vn, Wn of the GfsForceCoeff objects (GFSHIP_TREE_UPREV ...): allocated when the first list of particulates
   // with such a force asks for them (tree_previous_vel)
   double * uprev[3] = {};
+  // the variable of a GfsParticulateField and <list>_Fx, _Fy, _Fz of a GfsSourceParticulate (GFSHIP_TREE_VF, _FX ...):
+  // allocated zeroed by the first call that needs them (tree_coupling_variable)
+  double * cvar[4] = {};
+  bool src_fields = false;          // gfship_tree_set_source_fields: U, V, W take the velocity source of _FX ...
 };
 
 namespace {
@@ -880,7 +884,21 @@ struct AdvArgs {
   int gradient;            // 0 gfs_center_gradient, 1 gfs_center_van_leer_gradient
   double visc;             // GfsSourceDiffusion on the variable: its explicit term is the MAC source (0: none)
   double gsrc;             // the intensity of a GfsSource on the variable (0: none)
+  const double * fsrc;     // F_c of a GfsSourceParticulate on the velocity component fcomp (nullptr: none)
+  int fcomp;
 };
+
+// source_particulate_value (modules/particulatecommon.c:2029-2065): gfs_face_interpolated_value_generic of F_c on
+// the positive face of component c of the leaf -- a leaf of the same level, a coarser leaf (gfs_neighbor_value with
+// interpolate_1D1 / interpolate_2D1), a cell with children (the mean of the children's face values) or a ghost,
+// whose F is read as it is: no boundary condition is applied to these variables.  v->sources is visited last-read
+// first: this is the first term of the sum of gfs_variable_mac_source
+__device__ inline double mac_source_fields (const Topo & T, Cell cell, int c, const double * F)
+{
+  DevReader R = { F };
+  const Face f = { cell, T.neighbor (cell, 2*c), 2*c };
+  return face_interpolated_value_generic (T, f, R);
+}
 
 // transverse_term, src/advection.c:27-47
 __device__ inline double transverse_term (const Topo & T, const AdvArgs & A, Cell cell, int g, double v0,
@@ -920,8 +938,10 @@ __global__ void t_face_values (Topo T, const Cell * cells, int n, AdvArgs A)
     const double vl = v0 + (m1 < 0.5 ? m1 : 0.5)*gr;
     const double vr = v0 + (m2 > -0.5 ? m2 : -0.5)*gr;
     double msrc = 0.;        /* gfs_variable_mac_source, src/source.c:38-59 */
-    if (A.visc != 0. || A.gsrc != 0.) {
+    if (A.visc != 0. || A.gsrc != 0. || A.fsrc) {
       double sum = 0.;
+      if (A.fsrc)
+	sum += mac_source_fields (T, cell, A.fcomp, A.fsrc);
       if (A.visc != 0.)
 	sum += source_diffusion_value (T, cell, R, A.visc);
       if (A.gsrc != 0.)
@@ -1081,7 +1101,8 @@ __global__ void t_face_flux (Topo T, const FaceRec * faces, int n, UpwindArgs A,
 // add_pressure_gradient (src/timestep.c:809-812)
 __global__ void t_gather_flux (Topo T, const Cell * cells, int n, const FaceRec * faces,
 			       const int * inc_off, const int * inc, const double * fval,
-			       double * v, const double * g, double dt, double gsrc = 0.)
+			       double * v, const double * g, double dt, double gsrc = 0.,
+			       const double * fsrc = nullptr)
 {
   int t = blockIdx.x*blockDim.x + threadIdx.x;
   if (t >= n) return;
@@ -1102,9 +1123,12 @@ __global__ void t_gather_flux (Topo T, const Cell * cells, int n, const FaceRec 
   x += f/1.;
   if (g)
     x -= g[gi]*dt;
-  if (gsrc != 0.) {     /* gfs_domain_variable_centered_sources, src/source.c:62-108: a GfsSource */
+  if (gsrc != 0. || fsrc) {     /* gfs_domain_variable_centered_sources, src/source.c:62-108 */
     double sum = 0;
-    sum += gsrc;
+    if (fsrc)             /* source_particulate_centered_value, modules/particulatecommon.c:2067-2079 */
+      sum += fsrc[gi];
+    if (gsrc != 0.)       /* a GfsSource */
+      sum += gsrc;
     x += dt*sum;
   }
   v[gi] = x;
@@ -1147,7 +1171,7 @@ __global__ void t_cfl_faces (Topo T, const FaceRec * faces, int n, P6 un, double
 }
 
 struct D3 { double d[3]; };
-__global__ void t_cfl_cells (Topo T, const Cell * cells, int n, P3 u, double * red, D3 visc, D3 src)
+__global__ void t_cfl_cells (Topo T, const Cell * cells, int n, P3 u, double * red, D3 visc, D3 src, P3 fsrc)
 {
   int t = blockIdx.x*blockDim.x + threadIdx.x;
   double best = DBL_MAX;
@@ -1161,9 +1185,11 @@ __global__ void t_cfl_cells (Topo T, const Cell * cells, int n, P3 u, double * r
       const double cflu = length/fabs (fm*u.p[c][g]);
       best = fmin (best, cflu*cflu);
     }
-    if (visc.d[c] != 0. || src.d[c] != 0.) {      /* p->v[c]->sources: the acceleration scale, src/domain.c:2882-2891 */
+    if (visc.d[c] != 0. || src.d[c] != 0. || fsrc.p[c]) {      /* p->v[c]->sources: the acceleration scale, src/domain.c:2882-2891 */
       DevReader R = { u.p[c] };
       double gs = 0.;
+      if (fsrc.p[c])
+	gs += mac_source_fields (T, cells[t], c, fsrc.p[c]);
       if (visc.d[c] != 0.)
 	gs += source_diffusion_value (T, cells[t], R, visc.d[c]);
       if (src.d[c] != 0.)
@@ -1177,6 +1203,23 @@ __global__ void t_cfl_cells (Topo T, const Cell * cells, int n, P3 u, double * r
   best = wave_min (best);
   if ((threadIdx.x & 63) == 0 && best != DBL_MAX)
     atomic_min_pos (red, best);
+}
+
+// gfs_variable_mac_source (src/source.c:38-59) of velocity component c on the leaves, without the constant of a
+// GfsSource (gfship_tree_mac_source): 0. + the F-term + the source of the diffusion
+__global__ void t_mac_source (Topo T, const Cell * cells, int n, int c, const double * u, const double * fsrc,
+			      double visc, double * out)
+{
+  int t = blockIdx.x*blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const Cell cell = cells[t];
+  DevReader R = { u };
+  double sum = 0.;
+  if (fsrc)
+    sum += mac_source_fields (T, cell, c, fsrc);
+  if (visc != 0.)
+    sum += source_diffusion_value (T, cell, R, visc);
+  out[T.gi (cell)] = sum;
 }
 
 inline int blocks (int n) { return (n + 255)/256; }
@@ -2302,7 +2345,12 @@ int face_values_set (gfship_tree * tr, const double * v, double dt, int use_cent
   AdvArgs A;
   A.v = v; A.dt = dt; A.use_centered = use_centered; A.gradient = gradient;
   A.visc = A.gsrc = 0.;
-  for (int c = 0; c < 3; c++) if (v == tr->var[V_U + c]) { A.visc = tr->visc[c]; A.gsrc = tr->src[c]; }
+  A.fsrc = nullptr; A.fcomp = 0;
+  for (int c = 0; c < 3; c++)
+    if (v == tr->var[V_U + c]) {
+      A.visc = tr->visc[c]; A.gsrc = tr->src[c];
+      if (tr->src_fields && c < tr->H.dim) { A.fsrc = tr->cvar[1 + c]; A.fcomp = c; }
+    }
   for (int c = 0; c < 3; c++) A.u[c] = tr->var[V_U + c];
   for (int d = 0; d < 6; d++) { A.un[d] = tr->var[V_UN + d]; A.fv[d] = tr->var[V_FV + d]; }
   t_face_values<<<blocks (tr->nleaves*tr->H.dim), 256, 0, tr->stream>>> (tr->D, tr->leaves, tr->nleaves, A);
@@ -2424,7 +2472,7 @@ int centered_velocity_advection (gfship_tree * tr, int gmac, int g)
       KCHECK ();
     }
     t_gather_flux<<<blocks (tr->nleaves), 256, 0, tr->stream>>> (tr->D, tr->leaves, tr->nleaves, F.faces, F.inc_off, F.inc, F.fval,
-	sv, tr->var[g + c], tr->dt, tr->src[c]);
+	sv, tr->var[g + c], tr->dt, tr->src[c], tr->src_fields ? tr->cvar[1 + c] : nullptr);
     KCHECK ();
     if (tr->visc[c] != 0. && (e = variable_diffusion (tr, c))) return e;
   }
@@ -2478,7 +2526,9 @@ int domain_cfl (gfship_tree * tr, double * cfl)   /* src/domain.c:2899-2923 */
   t_cfl_faces<<<blocks (F.nfaces), 256, 0, tr->stream>>> (tr->D, F.faces, F.nfaces, p6 (tr, V_UN), tr->d_red);
   KCHECK ();
   D3 visc = { { tr->visc[0], tr->visc[1], tr->visc[2] } }, srcs = { { tr->src[0], tr->src[1], tr->src[2] } };
-  t_cfl_cells<<<blocks (tr->nleaves), 256, 0, tr->stream>>> (tr->D, tr->leaves, tr->nleaves, p3 (tr, V_U), tr->d_red, visc, srcs);
+  P3 fsrc = { { nullptr, nullptr, nullptr } };
+  for (int c = 0; c < tr->H.dim && tr->src_fields; c++) fsrc.p[c] = tr->cvar[1 + c];
+  t_cfl_cells<<<blocks (tr->nleaves), 256, 0, tr->stream>>> (tr->D, tr->leaves, tr->nleaves, p3 (tr, V_U), tr->d_red, visc, srcs, fsrc);
   KCHECK ();
   GFSHIP_HIP (hipMemcpyAsync (tr->h_red, tr->d_red, sizeof (double), hipMemcpyDeviceToHost, tr->stream));
   GFSHIP_HIP (hipStreamSynchronize (tr->stream));
@@ -2691,6 +2741,10 @@ int snapshot_vars (gfship_tree * tr, int nvars, const int * vars, SnapVars * V)
   GFSHIP_CHECK (nvars >= 0 && nvars <= TSNAP_MAXVARS, GFSHIP_EINVAL, "at most %d variables", TSNAP_MAXVARS);
   V->nvars = nvars;
   for (int v = 0; v < nvars; v++) {
+    if (vars[v] >= GFSHIP_TREE_VF && vars[v] <= GFSHIP_TREE_FZ && tr->cvar[vars[v] - GFSHIP_TREE_VF]) {
+      V->v[v] = tr->cvar[vars[v] - GFSHIP_TREE_VF];
+      continue;
+    }
     GFSHIP_CHECK (vars[v] >= 0 && vars[v] < abi_nvar, GFSHIP_EINVAL, "gfship_tree_snapshot: variable %d", vars[v]);
     GFSHIP_CHECK (vars[v] < GFSHIP_TREE_T0 || vars[v] > GFSHIP_TREE_T1 || vars[v] - GFSHIP_TREE_T0 < tr->ntracers,
 		  GFSHIP_EINVAL, "gfship_tree_snapshot: the tree has no tracer T%d", vars[v] - GFSHIP_TREE_T0);
@@ -2708,6 +2762,7 @@ void tree_free (gfship_tree * tr)
   (void) hipFree (tr->d_nbtab); (void) hipFree (tr->d_child0); (void) hipFree (tr->d_cmask); (void) hipFree (tr->d_idtab);
   for (double * p : tr->var) (void) hipFree (p);
   for (double * p : tr->uprev) (void) hipFree (p);
+  for (double * p : tr->cvar) (void) hipFree (p);
   (void) hipFree (tr->leaves);
   (void) hipFree (tr->ghost_leaves);
   for (int l = 0; l <= GFSHIP_MAXLEVEL; l++) {
@@ -2735,6 +2790,7 @@ void gfship::tree_view (gfship_tree * tr, gfship::TreeView * v)
   v->stream = tr->stream;
   v->device = tr->device; v->ncell = tr->ncell; v->nleaves = tr->nleaves;
   v->hleaves = tr->hleaves.data ();
+  v->dleaves = tr->leaves;
   v->side = tr->side;
   v->dt = tr->dt;
   v->t = tr->t;
@@ -2748,10 +2804,27 @@ double * gfship::tree_variable (gfship_tree * tr, int var)
 {
   if (var >= GFSHIP_TREE_UPREV && var <= GFSHIP_TREE_WPREV)
     return tr->uprev[var - GFSHIP_TREE_UPREV];
+  if (var >= GFSHIP_TREE_VF && var <= GFSHIP_TREE_FZ)
+    return tr->cvar[var - GFSHIP_TREE_VF];
   return var >= 0 && var < abi_nvar ? tr->var[abi_var[var]] : nullptr;
 }
 
 int gfship::tree_device (gfship_tree * tr) { return tr->device; }
+
+int gfship::tree_coupling_variable (gfship_tree * tr, int var, double ** out)
+{
+  GFSHIP_CHECK (var >= GFSHIP_TREE_VF && var <= GFSHIP_TREE_FZ, GFSHIP_EINVAL,
+		"%d is not GFSHIP_TREE_VF, _FX, _FY or _FZ", var);
+  GFSHIP_CHECK (var != GFSHIP_TREE_FZ || tr->H.dim == 3, GFSHIP_EINVAL, "a quadtree has no GFSHIP_TREE_FZ");
+  double *& a = tr->cvar[var - GFSHIP_TREE_VF];
+  if (!a) {
+    GFSHIP_HIP (hipSetDevice (tr->device));
+    GFSHIP_HIP (hipMalloc ((void **) &a, tr->ncell*sizeof (double)));
+    GFSHIP_HIP (hipMemsetAsync (a, 0, tr->ncell*sizeof (double), tr->stream));
+  }
+  if (out) *out = a;
+  return GFSHIP_OK;
+}
 
 // store_domain_previous_vel, modules/particulatecommon.c:99-113: the copy of U, V, W on the leaves (:108-110), then
 // gfs_domain_bc of the new variable (:111), a scalar with the default GfsBc whatever the conditions of U
@@ -3011,9 +3084,17 @@ int gfship_tree_flags (const gfship_tree * tr, int level, unsigned char * out)
 
 int gfship_tree_upload (gfship_tree * tr, int var, int level, const double * in)
 {
-  GFSHIP_CHECK (tr && in && var >= 0 && var < abi_nvar && level >= 0 && level <= tr->H.depth, GFSHIP_EINVAL,
-		"gfship_tree_upload: bad argument");
-  GFSHIP_HIP (hipMemcpyAsync (tr->var[abi_var[var]] + tr->H.off[level], in, (size_t) tr->H.lsize (level)*sizeof (double),
+  GFSHIP_CHECK (tr && in && level >= 0 && level <= tr->H.depth, GFSHIP_EINVAL, "gfship_tree_upload: bad argument");
+  double * a = nullptr;
+  if (var >= GFSHIP_TREE_VF && var <= GFSHIP_TREE_FZ) {      /* an upload is a call that needs them */
+    int r = tree_coupling_variable (tr, var, &a);
+    if (r) return r;
+  }
+  else {
+    GFSHIP_CHECK (var >= 0 && var < abi_nvar, GFSHIP_EINVAL, "gfship_tree_upload: bad argument");
+    a = tr->var[abi_var[var]];
+  }
+  GFSHIP_HIP (hipMemcpyAsync (a + tr->H.off[level], in, (size_t) tr->H.lsize (level)*sizeof (double),
 			      hipMemcpyHostToDevice, tr->stream));
   GFSHIP_HIP (hipStreamSynchronize (tr->stream));
   return GFSHIP_OK;
@@ -3382,6 +3463,31 @@ int gfship_tree_set_viscosity (gfship_tree * tr, int c, double nu)
   GFSHIP_CHECK (nu == 0. || tr->H.dim == 2 || tr->diffusion_exact == 1, GFSHIP_EUNSUPPORTED,
 		"GfsSourceDiffusion on this octree: a diffusion coefficient is not the same number on every face");
   tr->visc[c] = nu;
+  return GFSHIP_OK;
+}
+
+int gfship_tree_set_source_fields (gfship_tree * tr, int on)
+{
+  GFSHIP_CHECK (tr, GFSHIP_EINVAL, "gfship_tree_set_source_fields: null tree");
+  if (on)
+    for (int c = 0; c < tr->H.dim; c++) {
+      int r = tree_coupling_variable (tr, GFSHIP_TREE_FX + c, nullptr);
+      if (r) return r;
+    }
+  tr->src_fields = on != 0;
+  return GFSHIP_OK;
+}
+
+int gfship_tree_mac_source (gfship_tree * tr, int c, int var_out)
+{
+  GFSHIP_CHECK (tr, GFSHIP_EINVAL, "gfship_tree_mac_source: null tree");
+  GFSHIP_CHECK (c >= 0 && c < tr->H.dim, GFSHIP_EINVAL, "component %d out of range", c);
+  GFSHIP_CHECK (var_out == GFSHIP_TREE_RES || var_out == GFSHIP_TREE_DIV, GFSHIP_EINVAL,
+		"gfship_tree_mac_source writes into GFSHIP_TREE_RES or GFSHIP_TREE_DIV");
+  GFSHIP_HIP (hipSetDevice (tr->device));
+  t_mac_source<<<blocks (tr->nleaves), 256, 0, tr->stream>>> (tr->D, tr->leaves, tr->nleaves, c, tr->var[V_U + c],
+      tr->src_fields ? tr->cvar[1 + c] : nullptr, tr->visc[c], tr->var[abi_var[var_out]]);
+  GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
 

@@ -24,6 +24,10 @@
 // with children at x = 3/4.  Pinned on tests/tree_forces_reference.py in tests/test_gpu_tree_particulates.py.
 #include "particles.hpp"
 #include "tree_particles.hpp"
+#include <hipcub/hipcub.hpp>
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
 #include <vector>
 
 namespace gfship {
@@ -692,7 +696,10 @@ tree_particulate_coeff_inputs_kernel (TreeSamp S, TreeParticulateArgs A)
 }
 
 // gfs_particulate_event (:768-842) in a gfs_particle_list_event (:980-1015)
-template <int DIM>
+// ONFLUID: compute_forces_onfluid (:753-765) in source_particulate_event (:2199-2206), as in particles.hip: every
+// force of the list but GfsForceBuoy; `force' is written, and `mass' (compute_addedmass_force, :391); the particle
+// does not move and stays on the list; a particle without a leaf gets the zero force and keeps its mass
+template <int DIM, bool ONFLUID = false>
 __global__ void __launch_bounds__(256)
 tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
 {
@@ -704,7 +711,14 @@ tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
   Leaf c0;
   // remove_particles_not_in_domain, :955-969
   if (!tree_locate<DIM> (S, p, c0)) {
-    P.alive[q] = 0;
+    if constexpr (ONFLUID) {
+      const unsigned o = A.orig[q];
+#pragma unroll
+      for (int c = 0; c < 3; c++)
+	A.force[c][o] = 0.;
+    }
+    else
+      P.alive[q] = 0;
     return;
   }
   const unsigned o = A.orig[q];
@@ -722,6 +736,8 @@ tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
   // re-evaluates the same expressions per force: same bits)
   bool need_fvel = false, need_dudt = false, need_grad = false;
   for (int f = 0; f < A.nforces; f++) {
+    if (ONFLUID && A.forces[f] == FORCE_BUOY)
+      continue;
     need_fvel = need_fvel || A.forces[f] != FORCE_BUOY;
     need_dudt = need_dudt || A.forces[f] == FORCE_INERTIAL || A.forces[f] == FORCE_ADDEDMASS;
     need_grad = need_grad || A.forces[f] == FORCE_INERTIAL || A.forces[f] == FORCE_ADDEDMASS || A.forces[f] == FORCE_LIFT;
@@ -777,6 +793,8 @@ tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
   }
   for (int f = 0; f < A.nforces; f++) {
     double force[3] = { 0., 0., 0. };
+    if (ONFLUID && A.forces[f] == FORCE_BUOY)      /* :756 */
+      continue;
     switch (A.forces[f]) {
     case FORCE_INERTIAL:
       force[0] = dudt[0]; force[1] = dudt[1]; force[2] = dudt[2];
@@ -787,7 +805,7 @@ tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
 #pragma unroll
       for (int c = 0; c < DIM; c++)
 	force[c] *= cm;
-      mass += fluid_rho*volume*cm;      /* :391 */
+      mass += fluid_rho*volume*cm;      /* :391, in compute_forces_onfluid too */
       break;
     }
     case FORCE_LIFT: {          // compute_lift_force, :455-524; vorticity_vector, :146-168
@@ -853,6 +871,13 @@ tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
       pf[c] = force[c]*volume + pf[c];
     if (DIM == 2) pf[2] = 0.;
   }
+  if constexpr (ONFLUID) {
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+      A.force[c][o] = pf[c];
+    A.mass[o] = mass;
+    return;
+  }
 #pragma unroll
   for (int c = 0; c < DIM; c++) {      /* :828-837 */
     p[c] += vel[c]*dt/2.;
@@ -895,6 +920,268 @@ tree_particle_keys_kernel (TreeSamp S, int n, const double * __restrict__ x, con
   slot[q] = q;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Two-way coupling on a tree (GfsParticulateField, GfsSourceParticulate): the records, the sort and
+// the serial sums of coupling.hip, with the leaf of a tree -- its index in the concatenated levels, Topo::gi -- as
+// the cell of a key, the cellvol of the leaf's own level, and the pruned descent as a walk of the tree itself.
+// ---------------------------------------------------------------------------------------------
+
+// the level of cell g of the concatenated levels
+__device__ __forceinline__ int level_of (const Topo & T, unsigned g)
+{
+  int l = 0;
+  while (l < T.depth && (int) g >= T.off[l + 1]) l++;
+  return l;
+}
+
+template <int DIM>
+__device__ __forceinline__ double level_cellvol (int l)      /* ftt_cell_volume */
+{
+  const double h = 1./(double) (1 << l);
+  return DIM == 3 ? h*h*h : h*h;
+}
+
+// gfs_cell_reset on the interior leaves of every level, for up to three variables
+__global__ void __launch_bounds__(256)
+tree_reset_leaves_kernel (Topo T, const Cell * __restrict__ cells, int n, double * a0, double * a1, double * a2)
+{
+  const int t = blockIdx.x*blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int g = T.gi (cells[t]);
+  a0[g] = 0.;
+  if (a1) a1[g] = 0.;
+  if (a2) a2[g] = 0.;
+}
+
+__global__ void __launch_bounds__(256)
+tree_where_kernel (int n, const unsigned * __restrict__ orig, unsigned * __restrict__ where)
+{
+  const int q = blockIdx.x*blockDim.x + threadIdx.x;
+  if (q < n) where[orig[q]] = (unsigned) q;
+}
+
+__global__ void __launch_bounds__(256)
+tree_spread_constant_kernel (long nrec, double value, double * __restrict__ out)
+{
+  const long r = (long) blockIdx.x*blockDim.x + threadIdx.x;
+  if (r < nrec) out[r] = value;
+}
+
+// key of the leaf that holds each particle, (leaf << 32 | creation slot); pad (leaf = number of cells of the tree)
+// for the particles that are off the list or have no leaf (:1949-1950)
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_field_keys_kernel (TreeSamp S, int n, const double * __restrict__ x, const double * __restrict__ y,
+			const double * __restrict__ z, const unsigned char * __restrict__ alive,
+			const unsigned * __restrict__ orig, unsigned long long pad, unsigned long long * __restrict__ key)
+{
+  const int q = blockIdx.x*blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  unsigned long long k = pad;
+  if (alive[q] == 1) {
+    const double p[3] = { x[q], y[q], DIM == 3 ? z[q] : 0. };
+    Leaf c;
+    if (tree_locate<DIM> (S, p, c))
+      k = (unsigned long long) c.g;
+  }
+  key[q] = k << 32 | orig[q];
+}
+
+// voidfraction_from_particles (:1929-1932) for the particles of one leaf, in list order
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_field_sum_kernel (Topo T, int n, const unsigned long long * __restrict__ key, unsigned long long ncell,
+		       const double * __restrict__ volume, double * __restrict__ v)
+{
+  const int r = blockIdx.x*blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const unsigned long long cell = key[r] >> 32;
+  if (cell >= ncell) return;
+  if (r > 0 && key[r - 1] >> 32 == cell) return;      /* not the first of its leaf */
+  const double cellvol = level_cellvol<DIM> (level_of (T, (unsigned) cell));
+  double s = v[cell];
+  for (int m = r; m < n && key[m] >> 32 == cell; m++)
+    s += volume[(unsigned) (key[m] & 0xFFFFFFFFull)]/cellvol;
+  v[cell] = s;
+}
+
+struct TreeSpreadArgs {
+  int o0, nchunk, stride;
+  double rkernel;
+  const unsigned * where;
+  const unsigned char * alive;
+  const double * pos[3];
+  const double * rb;
+  unsigned long long pad;       // key of an unused slot: leaf = number of cells of the tree
+  unsigned long long * key;
+  double * q[3];
+  int * cnt, * flag;
+};
+
+// step 1: the leaves the kernel of each particle of the chunk reaches, in traversal order.
+// ftt_cell_traverse_condition (src/ftt.c:948-986), FTT_PRE_ORDER, FTT_TRAVERSE_LEAFS, over the tree itself: the root
+// passes cond_kernel or nothing is visited; a cell that passes is visited if it is a leaf and sends the descent into
+// its children 0 .. FTT_CELLS - 1 otherwise.  The state of the walk is the cell at hand (level, integer coordinates
+// from the low corner) and the next child to try: the child id of a cell is in the low bits of its coordinates
+// (bit 0: +x, bit 1: -y, bit 2: -z), so going up continues with id + 1 -- no stack
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_spread_emit_kernel (TreeSamp S, TreeSpreadArgs A)
+{
+  const int t = blockIdx.x*blockDim.x + threadIdx.x;
+  if (t >= A.nchunk) return;
+  const Topo & T = S.T;
+  const unsigned o = (unsigned) (A.o0 + t);
+  const unsigned s = A.where[o];
+  const size_t base = (size_t) t*A.stride;
+  int cnt = 0;
+  if (A.alive[s] == 1) {
+    const double p[3] = { A.pos[0][s], A.pos[1][s], DIM == 3 ? A.pos[2][s] : 0. };
+    const double rb = A.rb[o];
+    auto index = [&] (int l, int x, int y, int z) -> int {
+      const int r = (1 << l) + 2;
+      return T.off[l] + (x + 1) + r*((y + 1) + (DIM == 3 ? r*(z + 1) : 0));
+    };
+    auto visit = [&] (int l, int x, int y, int z, int g) {
+      if (cnt < A.stride) {
+	const double cellsize = 1./(double) (1 << l);
+	A.key[base + cnt] = (unsigned long long) g << 32 | o;
+	// distance_normalization (:2089-2099).  In 3-D the line `pos1->z = 0.' comes before
+	// `pos1->z = (pos1->z - pos2->z)/rb': z is (0. - pos.z)/rb, whatever the cell
+	A.q[0][base + cnt] = (-0.5 + (x + 0.5)*cellsize - p[0])/rb;
+	A.q[1][base + cnt] = (-0.5 + (y + 0.5)*cellsize - p[1])/rb;
+	A.q[2][base + cnt] = DIM == 3 ? (0. - p[2])/rb : 0.;
+      }
+      cnt++;
+    };
+    int l = 0, x = 0, y = 0, z = 0;      /* the cell whose children are tried */
+    const int root[3] = { 0, 0, 0 };
+    if (cond_kernel<DIM> (0, root, p, A.rkernel)) {
+      const int g0 = index (0, 0, 0, 0);
+      if (T.depth == 0 || T.cmask[g0] == 0)
+	visit (0, 0, 0, 0, g0);
+      else {
+	int n = 0;                       /* the next child of (l, x, y, z) to try */
+	unsigned mask = T.cmask[g0];     /* its children */
+	for (;;) {
+	  if (n == (1 << DIM)) {         /* all children done: up, and on with the next brother */
+	    if (l == 0) break;
+	    n = ((x & 1) | ((y & 1) ? 0 : 2) | (DIM == 3 && !(z & 1) ? 4 : 0)) + 1;
+	    x >>= 1; y >>= 1; z >>= 1;
+	    l--;
+	    mask = T.cmask[index (l, x, y, z)];
+	    continue;
+	  }
+	  const int k = n++;
+	  if (!((mask >> k) & 1u))
+	    continue;
+	  const int cx[3] = { 2*x + (k & 1), 2*y + ((k & 2) ? 0 : 1), DIM == 3 ? 2*z + ((k & 4) ? 0 : 1) : 0 };
+	  if (!cond_kernel<DIM> (l + 1, cx, p, A.rkernel))
+	    continue;
+	  const int g = index (l + 1, cx[0], cx[1], cx[2]);
+	  const unsigned cm = l + 1 < T.depth ? T.cmask[g] : 0u;
+	  if (cm == 0)
+	    visit (l + 1, cx[0], cx[1], cx[2], g);
+	  else {
+	    l++;
+	    x = cx[0]; y = cx[1]; z = cx[2];
+	    n = 0;
+	    mask = cm;
+	  }
+	}
+      }
+    }
+  }
+  if (cnt > A.stride) {      /* cannot happen (tree_kernel_stride); reported, never written */
+    *A.flag = 1;
+    cnt = A.stride;
+  }
+  A.cnt[t] = cnt;
+  for (int j = cnt; j < A.stride; j++)
+    A.key[base + j] = A.pad << 32 | 0xFFFFFFFFull;
+}
+
+// step 3: kernel_volume (:2108-2119) over the leaves of each particle in traversal order, then :2216
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_spread_correction_kernel (Topo T, int nchunk, int stride, const int * __restrict__ cnt,
+			       const unsigned long long * __restrict__ key, const double * __restrict__ K,
+			       double * __restrict__ corr)
+{
+  const int t = blockIdx.x*blockDim.x + threadIdx.x;
+  if (t >= nchunk) return;
+  double volume = 0., correction = 0.;
+  const size_t base = (size_t) t*stride;
+  for (int j = 0; j < cnt[t]; j++) {
+    const double cellvol = level_cellvol<DIM> (level_of (T, (unsigned) (key[base + j] >> 32)));
+    volume += cellvol;
+    correction += K[base + j]*cellvol;
+  }
+  correction /= volume;      /* no leaf: 0./0., which is not > 1.e-10 -- and there is nothing to add to */
+  corr[t] = correction;
+}
+
+// step 4: diffuse_force (:2158-2175) for the records of one leaf, in list order; liq_rho = 1. (no alpha on a tree)
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_spread_sum_kernel (Topo T, long nrec, const unsigned long long * __restrict__ key, unsigned long long ncell,
+			const double * __restrict__ K, int o0, const double * __restrict__ corr,
+			const double * __restrict__ fx, const double * __restrict__ fy, const double * __restrict__ fz,
+			double * __restrict__ Fx, double * __restrict__ Fy, double * __restrict__ Fz)
+{
+  const long r = (long) blockIdx.x*blockDim.x + threadIdx.x;
+  if (r >= nrec) return;
+  const unsigned long long cell = key[r] >> 32;
+  if (cell >= ncell) return;
+  if (r > 0 && key[r - 1] >> 32 == cell) return;
+  const double cellvol = level_cellvol<DIM> (level_of (T, (unsigned) cell));
+  const double liq_rho = 1.;
+  double F[3] = { Fx[cell], Fy[cell], DIM == 3 ? Fz[cell] : 0. };
+  for (long m = r; m < nrec && key[m] >> 32 == cell; m++) {
+    const unsigned o = (unsigned) (key[m] & 0xFFFFFFFFull);
+    const double correction = corr[o - (unsigned) o0];
+    if (correction > 1.e-10) {
+      const double k = K[m];
+      F[0] -= fx[o]/liq_rho/cellvol*k/correction;
+      F[1] -= fy[o]/liq_rho/cellvol*k/correction;
+      if (DIM == 3) F[2] -= fz[o]/liq_rho/cellvol*k/correction;
+    }
+  }
+  Fx[cell] = F[0];
+  Fy[cell] = F[1];
+  if (DIM == 3) Fz[cell] = F[2];
+}
+
+// record slots per particle: the bound of kernel_stride (coupling.hip) per level -- the centres of the leaves of
+// level l that pass cond_kernel lie within rho_l = rkernel + (h_l/2) sqrt (dim) of the particle along every axis and
+// are h_l apart -- summed over the levels that hold interior leaves; on a uniform tree the stride of the box
+unsigned long long tree_kernel_stride (const TreeView & V, double rkernel)
+{
+  bool has[GFSHIP_MAXLEVEL + 1] = {};
+  for (int t = 0; t < V.nleaves; t++) has[V.hleaves[t].l] = true;
+  unsigned long long sum = 0;
+  for (int l = 0; l <= V.H.depth; l++)
+    if (has[l]) {
+      const double n = (double) (1 << l), h = 1./n;
+      const double rho = rkernel + h/2.*sqrt ((double) V.H.dim);
+      double m = floor (2.*rho/h) + 2.;
+      if (!(m < n)) m = n;
+      const unsigned long long s = (unsigned long long) m;
+      sum += V.H.dim == 3 ? s*s*s : s*s;
+      if (sum > COUPLING_RECORD_CAP) break;      /* refused by the callers: no need to go on (nor to overflow) */
+    }
+  return sum;
+}
+
+int tree_stride_check (const TreeView & V, double rkernel)
+{
+  const unsigned long long stride = tree_kernel_stride (V, rkernel);
+  GFSHIP_CHECK (stride <= COUPLING_RECORD_CAP, GFSHIP_EUNSUPPORTED,
+		"GfsSourceParticulate: a kernel of rkernel = %g may reach %llu leaves of this tree or more, more than "
+		"the %llu records of a chunk", rkernel, stride, (unsigned long long) COUPLING_RECORD_CAP);
+  return GFSHIP_OK;
+}
+
 TreeSamp tree_samp (const TreeView & V, const SamplerTables * S)
 {
   TreeSamp A;
@@ -933,8 +1220,9 @@ int tree_particle_list_event (gfship_particles * pl)
   return GFSHIP_OK;
 }
 
-// gfs_particle_list_event (modules/particulatecommon.c:980-1015) of a list of GfsParticulate with forces
-int tree_particulate_list_event (gfship_particles * pl)
+// gfs_particle_list_event (modules/particulatecommon.c:980-1015) of a list of GfsParticulate with forces;
+// onfluid: the forces on the fluid alone (tree_particulate_list_event_kernel <ONFLUID>), Un, Vn, Wn stay
+static int tree_particulate_event (gfship_particles * pl, bool onfluid)
 {
   TreeView V;
   SamplerTables * S;
@@ -1004,6 +1292,14 @@ int tree_particulate_list_event (gfship_particles * pl)
 	A.coef[f] = pl->coef[f];
       }
   }
+  if (onfluid) {
+    if (dim == 3)
+      hipLaunchKernelGGL ((tree_particulate_list_event_kernel<3, true>), dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+    else
+      hipLaunchKernelGGL ((tree_particulate_list_event_kernel<2, true>), dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+    GFSHIP_HIP (hipGetLastError ());
+    return GFSHIP_OK;
+  }
   if (dim == 3)
     hipLaunchKernelGGL (tree_particulate_list_event_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
   else
@@ -1015,6 +1311,8 @@ int tree_particulate_list_event (gfship_particles * pl)
       return tree_previous_vel (pl->tree);
   return GFSHIP_OK;
 }
+
+int tree_particulate_list_event (gfship_particles * pl) { return tree_particulate_event (pl, false); }
 
 int tree_particle_keys (gfship_particles * pl, int * bits)
 {
@@ -1134,6 +1432,187 @@ int gfship_particulates_create_tree (gfship_particles ** out, gfship_tree * tr, 
   }
   *out = pl;
   return GFSHIP_OK;
+}
+
+// ---- two-way coupling on a tree --------------------------------------------------------------------
+
+// GfsParticulateField: particulate_field_event, modules/particulatecommon.c:1934-1957
+int gfship_tree_particulate_field (gfship_particles * pl, int var)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_tree_particulate_field");
+  GFSHIP_CHECK (var == GFSHIP_TREE_VF, GFSHIP_EINVAL, "the variable of a GfsParticulateField is GFSHIP_TREE_VF");
+  TreeView V;
+  SamplerTables * S;
+  int r = sampler_get (pl->tree, &V, &S);
+  if (r) return r;
+  double * a = nullptr;
+  if ((r = tree_coupling_variable (pl->tree, var, &a))) return r;
+  const int block = 256;
+  /* gfs_cell_reset on the leaves (:1944-1945) */
+  hipLaunchKernelGGL (tree_reset_leaves_kernel, dim3 ((V.nleaves + block - 1)/block), dim3 (block), 0, V.stream, V.D,
+		      V.dleaves, V.nleaves, a, (double *) nullptr, (double *) nullptr);
+  GFSHIP_HIP (hipGetLastError ());
+  if (pl->n == 0) return GFSHIP_OK;
+  if ((r = coupling_reserve (pl, (size_t) pl->n, 0, false))) return r;
+  const unsigned long long ncell = (unsigned long long) V.ncell;
+  const int grid = (pl->n + block - 1)/block;
+  const TreeSamp TS = tree_samp (V, S);
+  if (V.H.dim == 3)
+    hipLaunchKernelGGL (tree_field_keys_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, TS, pl->n, pl->pos[0],
+			pl->pos[1], pl->pos[2], pl->alive, pl->orig, ncell, pl->ckey);
+  else
+    hipLaunchKernelGGL (tree_field_keys_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, TS, pl->n, pl->pos[0],
+			pl->pos[1], pl->pos[2], pl->alive, pl->orig, ncell, pl->ckey);
+  GFSHIP_HIP (hipGetLastError ());
+  size_t need = 0;
+  const int bits = coupling_key_bits (ncell);
+  GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (nullptr, need, pl->ckey, pl->ckey2, pl->n, 0, bits, V.stream));
+  if ((r = coupling_sort_reserve (pl, need))) return r;
+  size_t tmp_bytes = pl->sort_tmp_bytes;
+  GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, pl->n, 0, bits,
+						 V.stream));
+  if (V.H.dim == 3)
+    hipLaunchKernelGGL (tree_field_sum_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, V.D, pl->n, pl->ckey2, ncell,
+			pl->volume, a);
+  else
+    hipLaunchKernelGGL (tree_field_sum_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, V.D, pl->n, pl->ckey2, ncell,
+			pl->volume, a);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
+// the forces of source_particulate_event (:2199-2206)
+int gfship_tree_particles_forces_on_fluid (gfship_particles * pl)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_tree_particles_forces_on_fluid");
+  if (pl->n == 0) return GFSHIP_OK;
+  return tree_particulate_event (pl, true);
+}
+
+// rkernel and kernel of a GfsSourceParticulate (source_particulate_read, :2271-2289)
+int gfship_tree_particles_set_kernel (gfship_particles * pl, double rkernel, const char * function)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_tree_particles_set_kernel");
+  GFSHIP_CHECK (rkernel >= 0. && std::isfinite (rkernel), GFSHIP_EINVAL, "rkernel must be a length >= 0");
+  TreeView V;
+  tree_view (pl->tree, &V);
+  int r = tree_stride_check (V, rkernel);
+  if (r) return r;
+  RtcKernel * k = nullptr;
+  double value = 0.;
+  if (function) {
+    /* a constant (gfs_function_read: a number is kept as f->val) needs no compilation */
+    char * end = nullptr;
+    value = strtod (function, &end);
+    while (end != function && (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r')) end++;
+    if (end == function || *end != '\0') {
+      value = 0.;
+      GFSHIP_HIP (hipSetDevice (V.device));
+      if ((r = rtc_compile_spatial_on (V.device, function, &k))) return r;
+    }
+  }
+  GFSHIP_HIP (hipStreamSynchronize (pl->stream));
+  rtc_free (pl->kernel_fn);
+  pl->kernel_fn = k;
+  pl->kernel_value = value;
+  pl->rkernel = rkernel;
+  return GFSHIP_OK;
+}
+
+// source_particulate_event from the stored forces (:2208-2222) into GFSHIP_TREE_FX ...
+int gfship_tree_particles_spread_forces (gfship_particles * pl)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_tree_particles_spread_forces");
+  TreeView V;
+  SamplerTables * S;
+  int r = sampler_get (pl->tree, &V, &S);
+  if (r) return r;
+  const int dim = V.H.dim;
+  double * Fa[3] = { nullptr, nullptr, nullptr };
+  for (int c = 0; c < dim; c++)
+    if ((r = tree_coupling_variable (pl->tree, GFSHIP_TREE_FX + c, &Fa[c]))) return r;
+  const int block = 256;
+  /* gfs_cell_reset on the leaves (:2189-2191) */
+  hipLaunchKernelGGL (tree_reset_leaves_kernel, dim3 ((V.nleaves + block - 1)/block), dim3 (block), 0, V.stream, V.D,
+		      V.dleaves, V.nleaves, Fa[0], Fa[1], Fa[2]);
+  GFSHIP_HIP (hipGetLastError ());
+  if (pl->n == 0) return GFSHIP_OK;
+  if ((r = tree_stride_check (V, pl->rkernel))) return r;
+  const int stride = (int) tree_kernel_stride (V, pl->rkernel);
+  const int per_chunk = (int) std::min ((size_t) pl->n, COUPLING_RECORD_CAP/(size_t) stride);
+  if ((r = coupling_reserve (pl, (size_t) per_chunk*stride, (size_t) per_chunk, true))) return r;
+  const unsigned long long ncell = (unsigned long long) V.ncell;
+  const int bits = coupling_key_bits (ncell);
+  hipLaunchKernelGGL (tree_where_kernel, dim3 ((pl->n + block - 1)/block), dim3 (block), 0, V.stream, pl->n, pl->orig,
+		      pl->where);
+  GFSHIP_HIP (hipGetLastError ());
+  GFSHIP_HIP (hipMemsetAsync (pl->cflag, 0, sizeof (int), V.stream));
+  const TreeSamp TS = tree_samp (V, S);
+  TreeSpreadArgs A;
+  A.stride = stride; A.rkernel = pl->rkernel;
+  A.where = pl->where; A.alive = pl->alive; A.rb = pl->rb;
+  for (int c = 0; c < 3; c++) { A.pos[c] = pl->pos[c]; A.q[c] = pl->cq[c]; }
+  A.pad = ncell; A.key = pl->ckey; A.cnt = pl->ccnt; A.flag = pl->cflag;
+  for (int o0 = 0; o0 < pl->n; o0 += per_chunk) {
+    const int nchunk = std::min (per_chunk, pl->n - o0);
+    const long nrec = (long) nchunk*stride;
+    const int pgrid = (nchunk + block - 1)/block;
+    const unsigned rgrid = (unsigned) ((nrec + block - 1)/block);
+    A.o0 = o0; A.nchunk = nchunk;
+    if (dim == 3)
+      hipLaunchKernelGGL (tree_spread_emit_kernel<3>, dim3 (pgrid), dim3 (block), 0, V.stream, TS, A);
+    else
+      hipLaunchKernelGGL (tree_spread_emit_kernel<2>, dim3 (pgrid), dim3 (block), 0, V.stream, TS, A);
+    GFSHIP_HIP (hipGetLastError ());
+    if (pl->kernel_fn) {
+      if ((r = rtc_launch_spatial (pl->kernel_fn, V.stream, nrec, stride, pl->ccnt, pl->cq[0], pl->cq[1], pl->cq[2],
+				   V.t, pl->cval)))
+	return r;
+    }
+    else {
+      hipLaunchKernelGGL (tree_spread_constant_kernel, dim3 (rgrid), dim3 (block), 0, V.stream, nrec, pl->kernel_value,
+			  pl->cval);
+      GFSHIP_HIP (hipGetLastError ());
+    }
+    if (dim == 3)
+      hipLaunchKernelGGL (tree_spread_correction_kernel<3>, dim3 (pgrid), dim3 (block), 0, V.stream, V.D, nchunk, stride,
+			  pl->ccnt, pl->ckey, pl->cval, pl->ccorr);
+    else
+      hipLaunchKernelGGL (tree_spread_correction_kernel<2>, dim3 (pgrid), dim3 (block), 0, V.stream, V.D, nchunk, stride,
+			  pl->ccnt, pl->ckey, pl->cval, pl->ccorr);
+    GFSHIP_HIP (hipGetLastError ());
+    size_t need = 0;
+    GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (nullptr, need, pl->ckey, pl->ckey2, pl->cval, pl->cval2, nrec, 0,
+						    bits, V.stream));
+    if ((r = coupling_sort_reserve (pl, need))) return r;
+    size_t tmp_bytes = pl->sort_tmp_bytes;
+    GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, pl->cval, pl->cval2,
+						    nrec, 0, bits, V.stream));
+    if (dim == 3)
+      hipLaunchKernelGGL (tree_spread_sum_kernel<3>, dim3 (rgrid), dim3 (block), 0, V.stream, V.D, nrec, pl->ckey2, ncell,
+			  pl->cval2, o0, pl->ccorr, pl->force[0], pl->force[1], pl->force[2], Fa[0], Fa[1], Fa[2]);
+    else
+      hipLaunchKernelGGL (tree_spread_sum_kernel<2>, dim3 (rgrid), dim3 (block), 0, V.stream, V.D, nrec, pl->ckey2, ncell,
+			  pl->cval2, o0, pl->ccorr, pl->force[0], pl->force[1], pl->force[2], Fa[0], Fa[1], Fa[2]);
+    GFSHIP_HIP (hipGetLastError ());
+  }
+  int flag = 0;
+  GFSHIP_HIP (hipMemcpyAsync (&flag, pl->cflag, sizeof (int), hipMemcpyDeviceToHost, V.stream));
+  GFSHIP_HIP (hipStreamSynchronize (V.stream));
+  GFSHIP_CHECK (flag == 0, GFSHIP_EHIP, "GfsSourceParticulate: a kernel reaches more than %d leaves", stride);
+  return GFSHIP_OK;
+}
+
+// source_particulate_event, :2177-2228
+int gfship_tree_source_particulate_event (gfship_particles * pl)
+{
+  int r = gfship_tree_particles_forces_on_fluid (pl);
+  if (r) return r;
+  return gfship_tree_particles_spread_forces (pl);
 }
 
 } // extern "C"

@@ -10,6 +10,7 @@ struct TreeView {
   hipStream_t stream;
   int device, ncell, nleaves;
   const tree::Cell * hleaves;       // host: interior leaves in traversal order
+  const tree::Cell * dleaves;       // device: the same
   const int * side;                 // GFSHIP_SIDE_* of the 2*dim sides
   double dt, t;
   double viscosity;                 // of U (gfship_tree_set_viscosity (tree, 0, nu)); 0.: no GfsSourceDiffusion
@@ -25,5 +26,8 @@ double * tree_variable (gfship_tree * tr, int var);
 // store_domain_previous_vel on the tree: GFSHIP_TREE_UPREV ... = U, V, W of this moment (allocates them the first time)
 int tree_previous_vel (gfship_tree * tr);
 int tree_device (gfship_tree * tr);
+// the device array of GFSHIP_TREE_VF, _FX, _FY, _FZ, allocated zeroed (every level, ghost cells included) by the
+// first call that needs it; GFSHIP_EINVAL for another variable and for _FZ on a quadtree
+int tree_coupling_variable (gfship_tree * tr, int var, double ** out);
 
 }

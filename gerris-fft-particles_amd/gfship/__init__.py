@@ -212,6 +212,13 @@ SIGNATURES = {
     "gfship_tree_sampler_stats": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "gfship_particles_create_tree": (_i, [C.POINTER(_vp), _vp, _i, _pd, C.POINTER(C.c_uint)]),
     "gfship_particulates_create_tree": (_i, [C.POINTER(_vp), _vp, _i, _pd, C.POINTER(C.c_uint), _pd, _pd, _pd]),
+    "gfship_tree_particulate_field": (_i, [_vp, _i]),
+    "gfship_tree_particles_forces_on_fluid": (_i, [_vp]),
+    "gfship_tree_particles_set_kernel": (_i, [_vp, C.c_double, C.c_char_p]),
+    "gfship_tree_particles_spread_forces": (_i, [_vp]),
+    "gfship_tree_source_particulate_event": (_i, [_vp]),
+    "gfship_tree_set_source_fields": (_i, [_vp, _i]),
+    "gfship_tree_mac_source": (_i, [_vp, _i, _i]),
 }
 
 
@@ -941,6 +948,7 @@ class Tree:
     stencils; quadtree or octree).  refine (x, y) or refine (x, y, z) -> level wanted there."""
     P, PMAC, U, V, GX, GY, GMACX, GMACY, UN0, UN1, UN2, UN3, W, GZ, GMACZ, UN4, UN5, DIV, BCVAL, RES, T0, T1, BCU, BCV, BCW = range(25)
     UPREV, VPREV, WPREV = 25, 26, 27      # Un, Vn, Wn: once a list of particulates has a force with a coefficient
+    VF, FX, FY, FZ = 28, 29, 30, 31       # GfsParticulateField, GfsSourceParticulate: once a call has needed them
 
     def __init__(self, refine, dim=2, device=0, sides=None):
         self.dim = dim
@@ -1071,6 +1079,37 @@ class Tree:
         """a GfsParticleList of GfsParticulate on this tree: set_forces, set_force_coefficient, particulate_state
         and event work on it as on the uniform box (destroy it before the tree)"""
         return ParticleList(self, pos, ids, particulate=(vel, mass, volume))
+
+    # two-way coupling: GfsParticulateField and GfsSourceParticulate on a list of Tree.particulates
+    def particulate_field(self, pl):
+        """Tree.VF = the volume fraction of the particles of the list (GfsParticulateField)"""
+        _check(lib().gfship_tree_particulate_field(pl.ptr, Tree.VF))
+
+    def forces_on_fluid(self, pl):
+        """the stored force of every particle = its forces but buoyancy, times its volume"""
+        _check(lib().gfship_tree_particles_forces_on_fluid(pl.ptr))
+
+    def set_kernel(self, pl, rkernel, function=None):
+        """rkernel (a length) and kernel (C text of x, y, z, t; a number; None = 0) of GfsSourceParticulate"""
+        _check(lib().gfship_tree_particles_set_kernel(
+            pl.ptr, float(rkernel), None if function is None else str(function).encode()))
+
+    def spread_forces(self, pl):
+        """Tree.FX ... = minus the stored forces spread around the particles with the kernel"""
+        _check(lib().gfship_tree_particles_spread_forces(pl.ptr))
+
+    def source_particulate_event(self, pl):
+        """forces_on_fluid, then spread_forces"""
+        _check(lib().gfship_tree_source_particulate_event(pl.ptr))
+
+    def set_source_fields(self, on=True):
+        """U, V(, W) take the velocity source of Tree.FX ... (GfsSourceParticulate in the time step)"""
+        _check(lib().gfship_tree_set_source_fields(self.ptr, 1 if on else 0))
+
+    def mac_source(self, c, var_out):
+        """gfs_variable_mac_source of component c on the leaves, without the constant of set_source, into
+        Tree.RES or Tree.DIV"""
+        _check(lib().gfship_tree_mac_source(self.ptr, int(c), int(var_out)))
 
     def sampler_stats(self):
         """the corner interpolators of the sampler: (corners of leaves, corners that read the table, table

@@ -778,6 +778,8 @@ enum { GFSHIP_TREE_P = 0, GFSHIP_TREE_PMAC, GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP
        GFSHIP_TREE_UN5, GFSHIP_TREE_DIV, GFSHIP_TREE_BCVAL, GFSHIP_TREE_RES,
        GFSHIP_TREE_T0, GFSHIP_TREE_T1, GFSHIP_TREE_BCU, GFSHIP_TREE_BCV, GFSHIP_TREE_BCW,
        GFSHIP_TREE_UPREV, GFSHIP_TREE_VPREV, GFSHIP_TREE_WPREV };
+/* the numbers go on: the variables of the two-way coupling on a tree (28 .. 31, see gfship_tree_particulate_field) */
+enum { GFSHIP_TREE_VF = GFSHIP_TREE_WPREV + 1, GFSHIP_TREE_FX, GFSHIP_TREE_FY, GFSHIP_TREE_FZ };
 				    /* variables of a tree: P, Pmac, U, V, g, gmac, f[d].un; then the 3-D ones;
 				       DIV: the result of gfship_tree_divergence / the right-hand side of
 				       gfship_tree_poisson_solve; BCVAL: the values of the conditions of P, one per
@@ -943,10 +945,62 @@ int  gfship_particles_create_tree (gfship_particles ** pl, gfship_tree * tree, i
    gfship_particles_set_forces when any force but GfsForceBuoy is listed and after every event of a list with a
    GfsForceInertial.
    gfship_particles_set_particulate, the coupling calls, gfship_particles_set_kernel, _set_migrate and
-   _record_size keep returning GFSHIP_EUNSUPPORTED on every list of a tree. */
+   _record_size keep returning GFSHIP_EUNSUPPORTED on every list of a tree (the coupling of a tree has calls of its
+   own: gfship_tree_particulate_field ... below). */
 int  gfship_particulates_create_tree (gfship_particles ** pl, gfship_tree * tree, int np,
 				      const double * pos, const unsigned * id,
 				      const double * vel, const double * mass, const double * volume);
+
+/* ---- two-way coupling on a tree (modules/particulatecommon.c:1927-2228) ------------------------ */
+
+/* GfsParticulateField and GfsSourceParticulate on a refined quadtree / octree, on a list made by
+   gfship_particulates_create_tree (GFSHIP_EUNSUPPORTED on a list of tracers and on a list of a box; the calls of the
+   uniform box, gfship_particulate_field ..., keep refusing a list of a tree).  One GfsParticulateField and one
+   GfsSourceParticulate per tree: their variables are GFSHIP_TREE_VF and GFSHIP_TREE_FX, _FY, _FZ (<list>_Fx ...,
+   :2300-2312; no _FZ on a quadtree), allocated zeroed -- every level, ghost cells included -- by the first call
+   that needs them, gfship_tree_upload among them; before that gfship_tree_download returns GFSHIP_EINVAL, after it
+   download, gfship_tree_interpolate and the snapshot calls take them like any variable.  As on the box every sum is
+   the reference's in list order, bit for bit, whatever the storage order (gfship_particles_sort): the contributions
+   are records keyed (leaf << 32 | list position), leaf = the index of the leaf in the concatenated levels,
+   radix-sorted and added serially per leaf, never with atomics.
+   gfship_tree_particulate_field: particulate_field_event (:1934-1957).  var = GFSHIP_TREE_VF, reset on the interior
+   leaves of every level, then v[leaf] += volume/ftt_cell_volume (leaf) for every particle on the list that
+   ftt_cell_locate finds a leaf for, cellvol = h*h[*h], h = 1/(1 << level of the leaf).
+   gfship_tree_particles_forces_on_fluid: compute_forces_onfluid (:753-765, :2199-2206); the contract of
+   gfship_particles_forces_on_fluid with the fluid data of gfship_particulates_create_tree (the gradients at a
+   change of level included).
+   gfship_tree_particles_set_kernel: as gfship_particles_set_kernel; the function is compiled for the tree's device.
+   A kernel whose record slots exceed a chunk (2^22) is refused, GFSHIP_EUNSUPPORTED.  The slots of a particle:
+   the sum, over the levels l that hold interior leaves, of min (floor (2 rho_l/h_l) + 2, 2^l)^dim with h_l = 2^-l,
+   rho_l = rkernel + (h_l/2) sqrt (dim): the stride of the box on a uniform tree.
+   gfship_tree_particles_spread_forces: :2208-2222 into GFSHIP_TREE_FX ...: reset on the interior leaves of every level
+   (ghost cells keep what they hold: 0 unless uploaded), then per particle in list order the two pruned traversals
+   of ftt_cell_traverse_condition (src/ftt.c:948-986) over the tree itself: the root passes cond_kernel (:2126-2156,
+   with the centre and the half size of the cell at hand, whatever its level) or nothing is visited; a cell that
+   passes is visited if it is a leaf, and sends the descent into its children 0 .. FTT_CELLS - 1 otherwise.
+   correction = sum K (q) cellvol (leaf)/sum cellvol (leaf) in traversal order, and where correction > 1.e-10
+   F_c[leaf] -= force_c/liq_rho/cellvol (leaf)*K (q)/correction with liq_rho = 1. (a tree has no alpha).
+   gfship_tree_source_particulate_event: source_particulate_event (:2177-2228), the two calls above in turn. */
+int  gfship_tree_particulate_field (gfship_particles * pl, int var);
+int  gfship_tree_particles_forces_on_fluid (gfship_particles * pl);
+int  gfship_tree_particles_set_kernel (gfship_particles * pl, double rkernel, const char * function);
+int  gfship_tree_particles_spread_forces (gfship_particles * pl);
+int  gfship_tree_source_particulate_event (gfship_particles * pl);
+/* GfsSourceParticulate in the time step of a tree (as gfship_sim_set_source_fields).  on != 0: U, V(, W) take the
+   velocity source of GFSHIP_TREE_FX ... (allocated here if need be): the centred value is F_c of the leaf
+   (source_particulate_centered_value, :2067-2079), the MAC value gfs_face_interpolated_value_generic
+   (src/fluid.c:2232-2253) of F_c on the positive face of component c (source_particulate_value, :2029-2065) -- the
+   neighbour a leaf of the same level, a coarser leaf (gfs_neighbor_value, :364-396), a cell with children (the mean
+   of the children's face values) or a ghost cell, whose F is read as it is: neither the reference's event nor this
+   library applies a boundary condition to these variables.  First term of every sum, 0. + F-term +
+   GfsSourceDiffusion + GfsSource (v->sources is visited last-read first), in the face values of the advection, the
+   centred update and the acceleration scale of gfs_domain_cfl.  Read at every use; 0 removes it.  Before or after
+   gfship_tree_start.
+   gfship_tree_mac_source: the sum gfs_variable_mac_source (src/source.c:38-59) gives on the leaves for component c,
+   without the constant of gfship_tree_set_source (the counterpart of gfship_variable_mac_source), into var_out =
+   GFSHIP_TREE_RES or GFSHIP_TREE_DIV (GFSHIP_EINVAL otherwise). */
+int  gfship_tree_set_source_fields (gfship_tree * tree, int on);
+int  gfship_tree_mac_source (gfship_tree * tree, int c, int var_out);
 
 /* ---- instrumentation -------------------------------------------------------------------- */
 

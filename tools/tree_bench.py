@@ -2,7 +2,7 @@
 """Time steps of the refined-tree path (gfship_tree) on an octree / quadtree with BOX
 extra levels inside the central cube / square: leaves, dependency levels of the finest sweep, ms per
 step, Mleaf-steps/s.  Not the benchmarked path (that is bench.py); a measurement to quote.
-usage: tree_bench.py [dim] [level] [box] [steps] [nu] [--snapshot] [--tracers N] [--particulates N]
+usage: tree_bench.py [dim] [level] [box] [steps] [nu] [--snapshot] [--tracers N] [--particulates N] [--two-way N]
 nu: GfsSourceDiffusion on every velocity component (default 0: inviscid)
 --snapshot: also time the file image of the tree (gfship_tree_snapshot_write) for P, Pmac, U, V
 (, W): the first call, which builds the offset tables, and the median of 20 more (kernel + copy to the host),
@@ -14,7 +14,11 @@ by gfship_particles_count (a stream synchronise); Mparticle-steps/s of the event
 of the sampler.
 --particulates N: the same for a list of N GfsParticulate with the five forces and their default coefficients (the
 particles and forces of tools/particles_bench.py --particulates; the drag acts where nu is given): the event of
-tree_particulate_list_event_kernel and, after it, the copy of U, V, W into Un, Vn, Wn."""
+tree_particulate_list_event_kernel and, after it, the copy of U, V, W into Un, Vn, Wn.
+--two-way N: the two-way coupling of a tree for the list of --particulates N, rkernel = 1.5 h of the
+finest leaves, the polynomial kernel: one call to warm up, then the mean of 10 and the least and the largest of them,
+each ended by a stream synchronise, of Tree.particulate_field, Tree.forces_on_fluid, Tree.spread_forces and, last (it
+moves the particles), of the event of the same list: the yardstick of forces_on_fluid."""
 import os
 import sys
 import time
@@ -36,6 +40,11 @@ nparticulates = 0
 if "--particulates" in sys.argv:
     k = sys.argv.index("--particulates")
     nparticulates = int(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
+ntwoway = 0
+if "--two-way" in sys.argv:
+    k = sys.argv.index("--two-way")
+    ntwoway = int(sys.argv[k + 1])
     del sys.argv[k:k + 2]
 dim = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 level = int(sys.argv[2]) if len(sys.argv) > 2 else 4
@@ -138,10 +147,44 @@ if nparticulates:
             "particulates_ms_per_event": round(dt_event * 1e3, 3),
             "particulates_Mparticle_steps_per_s": round(nparticulates / dt_event / 1e6, 1)}
     pl.destroy()
+two = {}
+if ntwoway:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from particle_cases import lcg_positions_fast
+    pos, ids = lcg_positions_fast(ntwoway)
+    if dim == 2:
+        pos[:, 2] = 0.
+    rng = np.random.default_rng(1)
+    vol = 1e-6 * (0.5 + rng.random(ntwoway))
+    pl = g.particulates(pos, ids, np.zeros((ntwoway, 3)), 2. * vol, vol)
+    pl.set_forces([gfship.FORCE_INERTIAL, gfship.FORCE_ADDEDMASS, gfship.FORCE_LIFT, gfship.FORCE_DRAG,
+                   gfship.FORCE_BUOY], (0., 1., 0.))
+    g.set_kernel(pl, 1.5 / (1 << g.depth), "(1. - 0.04*(x*x + y*y + z*z))")
+    pl.sort()
+
+    def mean_ms(call):
+        call()
+        pl.count()
+        t = []
+        for _ in range(10):
+            t0 = time.perf_counter()
+            call()
+            pl.count()
+            t.append((time.perf_counter() - t0) * 1e3)
+        return {"mean": round(float(np.mean(t)), 3), "min": round(min(t), 3), "max": round(max(t), 3)}
+
+    two = {"two_way_particulates": ntwoway, "rkernel_h_fine": 1.5}
+    for name, call in (("particulate_field_ms", lambda: g.particulate_field(pl)),
+                       ("forces_on_fluid_ms", lambda: g.forces_on_fluid(pl)),
+                       ("spread_forces_ms", lambda: g.spread_forces(pl)),
+                       ("event_ms", pl.event)):
+        two[name] = mean_ms(call)
+    two["leaves_with_a_deposit"] = int(sum(np.count_nonzero(g.download(g.FX, l)) for l in range(g.depth + 1)))
+    pl.destroy()
 print({"dim": dim, "levels": [level, g.depth], "leaves": nleaves, "finest_sweep_cells": nc,
        "finest_sweep_dependency_levels": nl, "tree_build_s": round(t_build, 2),
        "ms_per_step": round(ms, 2), "Mleaf_steps_per_s": round(nleaves / ms / 1e3, 3),
        "niter": [g.projection_params.niter, g.approx_projection_params.niter],
-       **snap, **trac, **part,
+       **snap, **trac, **part, **two,
        **({"nu": nu, "diffusion_niter": [g.diffusion_params(c).niter for c in range(dim)]} if nu != 0. else {})})
 g.destroy()
