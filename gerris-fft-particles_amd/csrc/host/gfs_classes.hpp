@@ -513,6 +513,77 @@ inline void read_particulate_field (Run & R, Reader & r, Object & ob)
   };
 }
 
+inline void read_source_particulate_change (Run & R, Reader & r, Object & ob)
+{
+  // source_particulatevol_read (modules/particulatecommon.c:2752-2804), source_particulatemass_read (:2908-2962):
+  //   GfsSourceParticulateVol | GfsSourceParticulateMass [{ event }] LIST FUNCTION [VARIABLE]
+  // the parent class is gfs_source_generic: no variable comes before the list; LIST is the `*name' of a
+  // GfsParticleList read above.  The function runs on the device (gfship_particulate_source_create): the
+  // variables it names are bound from the device variables of the run
+  const bool vol = ob.cls == "SourceParticulateVol";
+  ob.e->istep = 1;                              /* source_generic_init, src/source.c:149-152 */
+  read_event_params (r, *ob.e);
+  if (r.at_end_of_object () || r.peek (false) == '{')
+    r.fail ("expecting a string (object name)");
+  const std::string lname = r.word (false);
+  ParticleSpec * ps = R.plist_by_name (lname);
+  if (!ps) {
+    if (R.var_index (lname) >= 0)
+      r.fail ("object '" + lname + "' is not a GfsParticleList");
+    r.fail ("unknown object '" + lname + "'");
+  }
+  if (!ps->particulate)
+    r.fail ("the list `" + lname + "' holds GfsParticle objects: Gfs" + ob.cls + " needs GfsParticulate objects");
+  R.particulate_sources.emplace_back (new ParticulateSourceSpec);
+  ParticulateSourceSpec * sp = R.particulate_sources.back ().get ();
+  sp->ps = ps;
+  sp->kind = vol ? GFSHIP_PARTICULATE_SOURCE_VOLUME : GFSHIP_PARTICULATE_SOURCE_MASS;
+  sp->line = ob.line;
+  // a variable of the object: made where it is missing (gfs_domain_get_or_add_variable) and kept on the device
+  auto device_variable = [&R] (const std::string & name) {
+    const int v = R.get_or_add_variable (name);
+    if (!R.on_device (name)) R.device_vars.push_back (name);
+    return v;
+  };
+  sp->rad = device_variable ("Rad");             /* :2785-2793 */
+  sp->urel[0] = device_variable ("Urelp");
+  sp->urel[1] = device_variable ("Vrelp");
+  if (R.dim == 3) sp->urel[2] = device_variable ("Wrelp");
+  if (r.at_end_of_object ())
+    r.fail ("expecting an expression");          /* gfs_function_read */
+  const FunctionText t = r.function ();
+  if (t.block || !Reader::is_number (t.text) || atof (t.text.c_str ()) != 0.)
+    sp->function = t.text;
+  std::string dname;
+  if (!r.at_end_of_object ()) {
+    dname = r.word (false);
+    /* volsource must exist (gfs_variable_from_name, :2798); dmdtvariable is made (:2955) */
+    if (vol && R.var_index (dname) < 0)
+      r.fail ("unknown variable `" + dname + "'");
+    sp->deposit = device_variable (dname);
+  }
+  for (const std::string & id : FunctionSet::identifiers (t.text)) {
+    if (id == "Wrelp" && R.dim == 2)
+      r.fail ("Wrelp is not a variable in 2-D");
+    if (id == "Rad" || id == "Urelp" || id == "Vrelp" || id == "Wrelp" || id == "x" || id == "y" || id == "z" ||
+        id == "t" || R.var_index (id) < 0)
+      continue;                                  /* anything else is left to the compiler of the device */
+    if (id == dname)
+      r.fail ("the function of Gfs" + ob.cls + " names `" + dname + "', the variable its sources are deposited "
+              "into: it would read a sum that depends on the order of the particles");
+    if (!R.on_device (id))
+      r.fail ("the function of Gfs" + ob.cls + " reads `" + id +
+              "', which is not kept on the device (the variables of the simulation, tracers and the variables "
+              "of GfsParticulateField, GfsSourceParticulate and these classes are)");
+    sp->reads.push_back (id);
+  }
+  ob.e->action = [&R, sp] () {
+    must (gfship_particulate_source_event (sp->src));
+    for (int v : { sp->rad, sp->urel[0], sp->urel[1], sp->urel[2], sp->deposit })
+      if (v >= 0) R.vars[v].host_time = -1.;
+  };
+}
+
 // the optional level that ends the outputs of modules/fft.c
 inline void skip_level (Reader & r)
 {
@@ -977,6 +1048,8 @@ inline const ClassRow class_table[] = {
                                                           //   tree: GfsParticle without forces (check_tree_simulation)
   { "ParticulateField", read_particulate_field, EVENT },  // on a list named `*NAME'
   { "SourceParticulate", read_particulate_field, EVENT },
+  { "SourceParticulateVol", read_source_particulate_change, EVENT },     // LIST FUNCTION [VARIABLE]: the volumes and
+  { "SourceParticulateMass", read_source_particulate_change, EVENT },    //   the masses of a list change (uniform boxes)
   { "OutputEnergySpectra", read_output_energy_spectra, OUT },
   { "OutputSpectra", read_output_spectra, OUT },
   { "VariableTurbulentViscosity", read_variable_turbulent_viscosity, EVENT },

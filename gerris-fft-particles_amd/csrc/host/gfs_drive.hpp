@@ -642,6 +642,7 @@ inline int run_tree (Run & R)
   }
   events_do (R);
   if (!R.particles_out.empty () && write_particles (R)) return 1;
+  for (auto & sp : R.particulate_sources) gfship_particulate_source_destroy (sp->src);
   for (auto & ps : R.plists) gfship_particles_destroy (ps->pl);
   for (auto & o : R.outputs) o->close ();
   gfship_tree_destroy (R.tree);
@@ -920,6 +921,24 @@ inline int create_simulation (Run & R, gfship_field & div)
     for (int c = 0; c < R.dim; c++) F[c] = R.vars[sp->fvar[c]].dev;
     CHECK (gfship_sim_set_source_fields (R.sim, F));
   }
+  // GfsSourceParticulateVol / ...Mass: the function compiled for the device, with the device variables it names
+  for (auto & sp : R.particulate_sources) {
+    std::vector<const char *> names;
+    std::vector<gfship_field> fields;
+    for (const std::string & nm : sp->reads) {
+      names.push_back (nm.c_str ());
+      fields.push_back (R.vars[R.var_index (nm)].dev);
+    }
+    if (gfship_particulate_source_create (&sp->src, sp->ps->pl, sp->kind, sp->function.empty () ? nullptr : sp->function.c_str (),
+                                          (int) names.size (), names.data (), fields.data ()) < 0) {
+      fprintf (stderr, "gfship: line %d: %s\n", sp->line, gfship_last_error ());
+      return 1;
+    }
+    gfship_field urel[3] = { -1, -1, -1 };
+    for (int c = 0; c < R.dim; c++) urel[c] = R.vars[sp->urel[c]].dev;
+    CHECK (gfship_particulate_source_set_fields (sp->src, R.vars[sp->rad].dev, urel,
+                                                 sp->deposit >= 0 ? R.vars[sp->deposit].dev : -1));
+  }
   set_boundary_conditions (R);
   apply_init (R);
   for (auto & is : R.init_spectra) {
@@ -1110,20 +1129,21 @@ inline int write_particles (Run & R)
   for (auto & ps : R.plists) {
     int m = gfship_particles_slots (ps->pl);
     CHECK (m);
-    std::vector<double> pos (3*(size_t) std::max (m, 1)), vel (pos.size ()), force (pos.size ()), mass (std::max (m, 1));
+    std::vector<double> pos (3*(size_t) std::max (m, 1)), vel (pos.size ()), force (pos.size ()), mass (std::max (m, 1)),
+      volume (std::max (m, 1));
     std::vector<unsigned> id (std::max (m, 1));
     int k = gfship_particles_download (ps->pl, pos.data (), id.data ());
     CHECK (k);
-    if (ps->particulate)
+    if (ps->particulate) {
       CHECK (gfship_particles_download_particulate (ps->pl, vel.data (), mass.data (), force.data ()));
-    std::map<unsigned, double> volume;
-    for (size_t q = 0; q < ps->id.size () && ps->particulate; q++) volume[ps->id[q]] = ps->volume[q];
+      CHECK (gfship_particles_download_volume (ps->pl, volume.data ()));      /* a GfsSourceParticulateVol changes them */
+    }
     fprintf (fp, "GfsParticleList %s {\n", ps->particulate ? "GfsParticulate" : "GfsParticle");
     for (int q = 0; q < k; q++) {
       fprintf (fp, "    %s %d %g %g %g", ps->particulate ? "GfsParticulate" : "GfsParticle", (int) id[q],
                pos[3*q], pos[3*q + 1], pos[3*q + 2]);
       if (ps->particulate) {
-        fprintf (fp, " %g %g %g %g %g", mass[q], volume[id[q]], vel[3*q], vel[3*q + 1], vel[3*q + 2]);
+        fprintf (fp, " %g %g %g %g %g", mass[q], volume[q], vel[3*q], vel[3*q + 1], vel[3*q + 2]);
         fprintf (fp, " %g %g %g", force[3*q], force[3*q + 1], force[3*q + 2]);
       }
       fputc ('\n', fp);
@@ -1156,6 +1176,7 @@ inline int run (Run & R)
       R.sim_class == "Advection" ? run_advection (R) : run_simulation (R))
     return 1;
   if (!R.particles_out.empty () && write_particles (R)) return 1;
+  for (auto & sp : R.particulate_sources) gfship_particulate_source_destroy (sp->src);
   for (auto & ps : R.plists) gfship_particles_destroy (ps->pl);
   for (auto & o : R.outputs) o->close ();
   gfship_sim_destroy (R.sim);

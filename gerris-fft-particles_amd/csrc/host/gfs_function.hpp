@@ -112,12 +112,6 @@ public:
       }
   }
 
-private:
-  static int index_of (const std::vector<std::string> & names, const std::string & n) {
-    for (size_t q = 0; q < names.size (); q++)
-      if (names[q] == n) return (int) q;
-    return -1;
-  }
   // identifiers of a C expression, each once, in order of appearance
   static std::vector<std::string> identifiers (const std::string & e) {
     std::vector<std::string> ids;
@@ -142,6 +136,12 @@ private:
     return ids;
   }
 
+private:
+  static int index_of (const std::vector<std::string> & names, const std::string & n) {
+    for (size_t q = 0; q < names.size (); q++)
+      if (names[q] == n) return (int) q;
+    return -1;
+  }
   std::vector<std::unique_ptr<Function>> fns_;
   void * handle_ = nullptr;
   std::string dir_;

@@ -175,6 +175,19 @@ struct SourceParticulateSpec {
   int fvar[3] = { -1, -1, -1 };
 };
 
+// GfsSourceParticulateVol / GfsSourceParticulateMass (modules/particulatecommon.c:2734-3047): the list, the text
+// of the function with the variables of the run it names, and the variables Rad, Urelp, Vrelp[, Wrelp] and the
+// optional deposit variable (-1: none), all kept on the device
+struct ParticulateSourceSpec {
+  ParticleSpec * ps = nullptr;
+  int kind = GFSHIP_PARTICULATE_SOURCE_VOLUME;
+  int line = 0;
+  std::string function;                          // "" = the constant 0 of source_particulatevol_init
+  std::vector<std::string> reads;
+  int rad = -1, urel[3] = { -1, -1, -1 }, deposit = -1;
+  gfship_particulate_source * src = nullptr;
+};
+
 // a cell: its indices on its level (1..2^l inside the box; k = 0 in 2-D)
 struct Cell { int i, j, k, l; };
 
@@ -219,6 +232,13 @@ struct Run {
   std::vector<std::unique_ptr<Output>> outputs;
   std::vector<std::unique_ptr<ParticleSpec>> plists;
   std::vector<std::unique_ptr<SourceParticulateSpec>> source_particulates;
+  std::vector<std::unique_ptr<ParticulateSourceSpec>> particulate_sources;
+  // a variable of the file that is kept on the device: those of the simulation, the tracers and device_vars
+  bool on_device (const std::string & name) const {
+    if (name == "P" || name == "Pmac" || velocity_component (name) >= 0) return true;
+    for (const TracerSpec & tr : tracers) if (tr.name == name) return true;
+    return std::find (device_vars.begin (), device_vars.end (), name) != device_vars.end ();
+  }
   ParticleSpec * plist_by_name (const std::string & name) const {
     for (auto & ps : plists) if (!ps->name.empty () && ps->name == name) return ps.get ();
     return nullptr;

@@ -26,6 +26,8 @@ int check (Run & R)
   resolve_refine (R);
   printf ("class Gfs%s dim %d level %d%s\n", R.sim_class.c_str (), R.dim, R.level,
 	  R.tree_mode ? " (coarsest leaves of a refined tree)" : "");
+  if (R.tree_mode && R.sim_class == "Simulation" && check_tree_events (R))
+    return 1;               /* an event that is refused on a refined tree, with its line */
   if (R.tree_mode)        /* no host copies of fields without the tree, which needs the device */
     R.init.clear ();
   printf ("sides");

@@ -660,6 +660,41 @@ count_alive_kernel (const unsigned char * alive, int n, unsigned * count)
     atomicAdd (count, (unsigned) __popcll (m));
 }
 
+// update_vol / update_mass (modules/particulatecommon.c:2806-2824, 2964-2982) up to the call of the function:
+// gfs_domain_locate, the radius, gfs_interpolate of the velocity and the relative velocity of one particle,
+// stored at its creation slot (what the function and the ordered pass of particulate_sources.hip read)
+struct SourceGatherArgs {
+  Layout L;
+  int depth, n;
+  const double * pos[3];
+  const unsigned char * alive;
+  const unsigned * orig;
+  const double * u[3], * vel[3], * volume;
+  unsigned * cell;
+  double * rad, * urel[3];
+};
+
+template <int DIM>
+__global__ void __launch_bounds__(256)
+particulate_source_gather_kernel (SourceGatherArgs A)
+{
+  int q = blockIdx.x*blockDim.x + threadIdx.x;
+  if (q >= A.n) return;
+  const unsigned o = A.orig[q];
+  double p[3] = { A.pos[0][q], A.pos[1][q], DIM == 3 ? A.pos[2][q] : 0. };
+  int c[3];
+  if (A.alive[q] != 1 || !locate<DIM> (A.depth, p, c)) {
+    A.cell[o] = PSOURCE_NO_CELL;
+    return;
+  }
+  const unsigned n = (unsigned) A.L.n;
+  A.cell[o] = (unsigned) (c[0] - 1) + n*((unsigned) (c[1] - 1) + (DIM == 3 ? n*(unsigned) (c[2] - 1) : 0u));
+  A.rad[o] = pow (3.0*A.volume[o]/4.0/M_PI, 1./3.);      /* :2812, the device's pow */
+#pragma unroll
+  for (int a = 0; a < DIM; a++)
+    A.urel[a][o] = interpolate<DIM> (A.L, A.u[a], c, p) - A.vel[a][o];
+}
+
 } // namespace gfship
 
 using namespace gfship;
@@ -1306,6 +1341,29 @@ int gfship_particles_download_particulate (gfship_particles * pl, double * vel, 
   return k;
 }
 
+int gfship_particles_download_volume (gfship_particles * pl, double * volume)
+{
+  GFSHIP_CHECK (pl && volume, GFSHIP_EINVAL, "null argument");
+  GFSHIP_NO_TREE_TRACER_LIST (pl, "gfship_particles_download_volume");
+  GFSHIP_CHECK (pl->particulate, GFSHIP_EINVAL, "not a list of particulates");
+  if (pl->n == 0) return 0;
+  GFSHIP_HIP (hipStreamSynchronize (pl->stream));
+  size_t m = pl->n;
+  std::vector<unsigned> orig (m), where (m);
+  std::vector<unsigned char> al (m);
+  std::vector<double> vol (m);
+  GFSHIP_HIP (hipMemcpy (orig.data (), pl->orig, m*sizeof (unsigned), hipMemcpyDeviceToHost));
+  GFSHIP_HIP (hipMemcpy (al.data (), pl->alive, m, hipMemcpyDeviceToHost));
+  GFSHIP_HIP (hipMemcpy (vol.data (), pl->volume, m*sizeof (double), hipMemcpyDeviceToHost));
+  for (size_t q = 0; q < m; q++)
+    where[orig[q]] = (unsigned) q;
+  int k = 0;
+  for (size_t o = 0; o < m; o++)
+    if (al[where[o]] == 1)
+      volume[k++] = vol[o];
+  return k;
+}
+
 int gfship_particle_list_event (gfship_particles * pl)
 {
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
@@ -1458,3 +1516,29 @@ int gfship_particles_download_old (gfship_particles * pl, double * old)
 }
 
 } // extern "C"
+
+int gfship::launch_particulate_source_gather (gfship_particles * pl, unsigned * cell, double * rad,
+					      double * const urel[3])
+{
+  gfship_domain * dom = pl->dom;
+  const gfship_sim_view v = gfship_sim_view_get (pl->sim);
+  SourceGatherArgs A;
+  A.L = dom->lay[dom->depth];
+  A.depth = dom->depth;
+  A.n = pl->n;
+  for (int c = 0; c < 3; c++) {
+    A.pos[c] = pl->pos[c];
+    A.u[c] = c < dom->dim ? dom->fields[v.u[c]].lev[dom->depth] : nullptr;
+    A.vel[c] = pl->vel[c];
+    A.urel[c] = urel[c];
+  }
+  A.alive = pl->alive; A.orig = pl->orig; A.volume = pl->volume;
+  A.cell = cell; A.rad = rad;
+  const int block = 256, grid = (pl->n + block - 1)/block;
+  with_bools ([&] (auto D3) {
+    constexpr int DIM = decltype (D3)::value ? 3 : 2;
+    hipLaunchKernelGGL (particulate_source_gather_kernel<DIM>, dim3 (grid), dim3 (block), 0, dom->stream, A);
+  }, dom->dim == 3);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}

@@ -16,6 +16,15 @@ int  rtc_compile_spatial (gfship_domain * dom, const char * text, RtcKernel ** o
 int  rtc_compile_spatial_on (int device, const char * text, RtcKernel ** out);       // a list of a tree
 int  rtc_launch_spatial (RtcKernel * k, hipStream_t stream, long nrec, int stride, const int * cnt,
 			 const double * x, const double * y, const double * z, double t, double * out);
+// the function of a GfsSourceParticulateVol / ...Mass: a GfsFunction of Rad, Urelp, Vrelp(, Wrelp: dim == 3), of
+// x, y, z (the centre of the particle's cell), t and of the nf variables `names', evaluated for every creation
+// slot o < n whose cell[o] is a cell of the box (its linear number; PSOURCE_NO_CELL: none)
+constexpr unsigned PSOURCE_NO_CELL = 0xFFFFFFFFu;
+int  rtc_compile_source (gfship_domain * dom, const char * text, int nf, const char * const * names,
+			 RtcKernel ** out);
+int  rtc_launch_source (RtcKernel * k, hipStream_t stream, int n, const Layout & L, const unsigned * cell,
+			const double * rad, const double * const urel[3], double t, int nf,
+			const double * const * fields, double * out);
 }
 
 struct gfship_particles {
@@ -103,6 +112,10 @@ int tree_particle_keys (gfship_particles * pl, int * bits);
 int particulate_alloc (gfship_particles * pl, const double * vel, const double * mass, const double * volume);
 // a list of particulates on a tree (gfship_particulates_create_tree, tree_particles.hip): its event with forces
 int tree_particulate_list_event (gfship_particles * pl);
+// the first pass of a GfsSourceParticulateVol / ...Mass (particulate_sources.hip) with the locate and the
+// interpolate of the event kernels (particles.hip): per creation slot the linear number of the particle's cell
+// (PSOURCE_NO_CELL off the list or without a cell), pow (3.0*volume/4.0/M_PI, 1./3.) and fluid velocity - vel
+int launch_particulate_source_gather (gfship_particles * pl, unsigned * cell, double * rad, double * const urel[3]);
 }
 
 // the coupling calls of a tree (gfship_tree_particulate_field ...): lists made by gfship_particulates_create_tree

@@ -1,0 +1,387 @@
+// particulate_sources.hip -- the particles themselves change: GfsSourceParticulateVol and
+// GfsSourceParticulateMass (modules/particulatecommon.c:2734-3047) on a uniform box.
+//
+// The event of the reference resets the deposit variable and walks the list in its order (update_vol,
+// :2806-2832; update_mass, :2964-2991): locate the cell, write Rad and Urelp, Vrelp(, Wrelp) of the particle
+// into it, evaluate the GfsFunction at the cell, volume (mass) += source*dt, deposit[cell] += source.  The
+// function is evaluated right after the particle wrote its own four values, so what it sees depends on the
+// particle alone and on fields nobody writes during the walk: the work per particle is independent.  What
+// does depend on the order is what a cell is left with: the sum of the sources of its particles, added from 0
+// in list order, and the four values of its LAST particle in list order.  Here:
+//   1. one thread per particle: locate, radius, relative velocity (particulate_source_gather_kernel,
+//      particles.hip: the locate and the interpolate of the event kernels), stored per creation slot;
+//   2. the function of every particle: a constant, or the kernel hipRTC compiled around its text (rtc.hip);
+//   3. one thread per creation slot: volume or mass += source*dt, for a volume also the diameter (:552) and rb
+//      (:2091) of the particle, and the key (cell << 32 | creation slot);
+//   4. where a field is to be written: radix sort of the keys (the arrays and the key bits of coupling.hip),
+//      then one thread per run of equal cells adds the sources serially and copies the values of the last
+//      record.  No atomics: the result does not depend on where a particle is stored nor on the scheduling.
+// The event has no chunks: one record of 8 bytes per particle (the spreading needs chunks because one particle
+// owns many records).
+//
+// pow: Rad, and the diameter and rb of a particle whose volume an event has changed, are values of the
+// device's pow (the reference's expression, glibc's pow there); everything else is the reference's arithmetic,
+// operation by operation.  A list no volume event has run on keeps the diameter and rb computed on the host
+// (particulate_alloc).
+#include "particles.hpp"
+#include <hipcub/hipcub.hpp>
+#include <cmath>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+struct gfship_particulate_source {
+  gfship_particles * pl = nullptr;
+  int kind = GFSHIP_PARTICULATE_SOURCE_VOLUME;
+  gfship::RtcKernel * fn = nullptr;      // nullptr: the constant `value'
+  double value = 0.;
+  std::vector<gfship_field> read;        // the fields the function names, in the order of its arguments
+  gfship_field rad = -1, urel[3] = { -1, -1, -1 }, deposit = -1;
+  // per creation slot: the cell, Rad, Urelp ..., the source
+  unsigned * cell = nullptr;
+  double * prad = nullptr, * purel[3] = {}, * src = nullptr;
+  int cap = 0;
+};
+
+namespace gfship {
+
+// step 3: :2828 / :2986, then the diameter of compute_drag_force (:552) and rb of distance_normalization (:2091)
+template <bool VOLUME>
+__global__ void __launch_bounds__(256)
+particulate_source_update_kernel (int n, const unsigned * __restrict__ cell, const double * __restrict__ src,
+				  double dt, double * __restrict__ state, double * __restrict__ dia,
+				  double * __restrict__ rb, unsigned long long pad, unsigned long long * __restrict__ key)
+{
+  int o = blockIdx.x*blockDim.x + threadIdx.x;
+  if (o >= n) return;
+  const unsigned c = cell[o];
+  if (c == PSOURCE_NO_CELL) {      /* not on the list, or no cell: nothing changes */
+    if (key) key[o] = pad << 32 | (unsigned) o;
+    return;
+  }
+  const double s = state[o] + src[o]*dt;
+  state[o] = s;
+  if constexpr (VOLUME) {
+    dia[o] = 2.*pow (3.0*s/4.0/M_PI, 1./3.);
+    rb[o] = pow (3.*s/(4.*M_PI), 1./3.);
+  }
+  if (key) key[o] = (unsigned long long) c << 32 | (unsigned) o;
+}
+
+__global__ void __launch_bounds__(256)
+particulate_source_constant_kernel (int n, double value, double * __restrict__ out)
+{
+  int o = blockIdx.x*blockDim.x + threadIdx.x;
+  if (o < n) out[o] = value;
+}
+
+struct SourceCellArgs {
+  Layout L;
+  int n;
+  const unsigned long long * key;
+  unsigned long long ncell;
+  const double * src, * prad, * purel[3];
+  double * deposit, * rad, * urel[3];      // nullptr: not written
+};
+
+// step 4: the records of one cell in list order: deposit += source from the 0. of the reset (:2830, :2989),
+// Rad, Urelp ... of the last one (:2812-2824: every particle overwrites what the one before left)
+template <int DIM>
+__global__ void __launch_bounds__(256)
+particulate_source_cell_kernel (SourceCellArgs A)
+{
+  int r = blockIdx.x*blockDim.x + threadIdx.x;
+  if (r >= A.n) return;
+  const unsigned long long cell = A.key[r] >> 32;
+  if (cell >= A.ncell) return;
+  if (r > 0 && A.key[r - 1] >> 32 == cell) return;      /* not the first of its cell */
+  const unsigned nside = (unsigned) A.L.n;
+  const int i = (int) (cell % nside) + 1, j = (int) ((cell/nside) % nside) + 1;
+  const int k = DIM == 3 ? (int) (cell/((unsigned long long) nside*nside)) + 1 : 0;
+  const long idx = A.L.idx (i, j, k);
+  double s = 0.;
+  int m = r;
+  for (; m < A.n && A.key[m] >> 32 == cell; m++)
+    s += A.src[(unsigned) (A.key[m] & 0xFFFFFFFFull)];
+  const unsigned last = (unsigned) (A.key[m - 1] & 0xFFFFFFFFull);
+  if (A.deposit) A.deposit[idx] = s;
+  if (A.rad) A.rad[idx] = A.prad[last];
+#pragma unroll
+  for (int c = 0; c < DIM; c++)
+    if (A.urel[c]) A.urel[c][idx] = A.purel[c][last];
+}
+
+static bool c_identifier (const char * s)
+{
+  if (!s || !(isalpha ((unsigned char) *s) || *s == '_')) return false;
+  for (; *s; s++)
+    if (!(isalnum ((unsigned char) *s) || *s == '_')) return false;
+  return true;
+}
+
+// does the C text name `id' (a whole identifier, not a member and not inside a string)?
+static bool names_identifier (const std::string & e, const std::string & id)
+{
+  size_t p = 0;
+  while (p < e.size ()) {
+    if (isalpha ((unsigned char) e[p]) || e[p] == '_') {
+      size_t b = p;
+      while (p < e.size () && (isalnum ((unsigned char) e[p]) || e[p] == '_')) p++;
+      const bool member = b > 0 && (e[b - 1] == '.' || isdigit ((unsigned char) e[b - 1]));
+      if (!member && e.compare (b, p - b, id) == 0) return true;
+    }
+    else if (e[p] == '"') {
+      p++;
+      while (p < e.size () && e[p] != '"') p++;
+      p++;
+    }
+    else
+      p++;
+  }
+  return false;
+}
+
+// what gfship_particulate_source_create and the event refuse: coupling_check of coupling.hip, word for word
+static int source_check (gfship_particles * pl, const char * what)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_NO_TREE_LIST (pl, what);
+  GFSHIP_CHECK (pl->particulate, GFSHIP_EUNSUPPORTED,
+		"%s needs a list of particulates (gfship_particles_set_particulate)", what);
+  GFSHIP_CHECK (!pl->dom->has_external, GFSHIP_EUNSUPPORTED,
+		"%s on a box with GfsBoundaryMpi sides is not supported: particles would arrive and leave "
+		"between the events of the list", what);
+  /* the keys hold the cell number and the pad (= the number of cells) in 32 bits */
+  GFSHIP_CHECK (pl->dom->dim*pl->dom->depth < 32, GFSHIP_EUNSUPPORTED,
+		"%s: the %d-D box of level %d has 2^32 cells or more", what, pl->dom->dim, pl->dom->depth);
+  return GFSHIP_OK;
+}
+
+static const char * kind_name (int kind)
+{
+  return kind == GFSHIP_PARTICULATE_SOURCE_VOLUME ? "GfsSourceParticulateVol" : "GfsSourceParticulateMass";
+}
+
+static int source_reserve (gfship_particulate_source * s)
+{
+  gfship_particles * pl = s->pl;
+  if (s->cap >= pl->n) return GFSHIP_OK;
+  GFSHIP_HIP (hipStreamSynchronize (pl->stream));
+  void ** a[] = { (void **) &s->cell, (void **) &s->prad, (void **) &s->purel[0], (void **) &s->purel[1],
+		  (void **) &s->purel[2], (void **) &s->src };
+  s->cap = 0;
+  for (void ** p : a) {
+    if (*p) (void) hipFree (*p);
+    *p = nullptr;
+    GFSHIP_HIP (hipMalloc (p, (size_t) pl->cap*(p == (void **) &s->cell ? sizeof (unsigned) : sizeof (double))));
+  }
+  s->cap = pl->cap;
+  return GFSHIP_OK;
+}
+
+// info != nullptr: the milliseconds of the per-particle passes (steps 1 to 3) and of the sort with the pass per
+// cell (step 4), from events on the stream
+static int source_event (gfship_particulate_source * s, double * info)
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null particulate source");
+  gfship_particles * pl = s->pl;
+  const char * what = kind_name (s->kind);
+  int r = source_check (pl, what);
+  if (r) return r;
+  gfship_domain * dom = pl->dom;
+  const bool volume = s->kind == GFSHIP_PARTICULATE_SOURCE_VOLUME;
+  const Layout & L = dom->lay[dom->depth];
+  Field * D = nullptr, * R = nullptr, * U[3] = { nullptr, nullptr, nullptr };
+  if (s->deposit >= 0 && !(D = get_field (dom, s->deposit))) return GFSHIP_EINVAL;
+  if (s->rad >= 0 && !(R = get_field (dom, s->rad))) return GFSHIP_EINVAL;
+  for (int c = 0; c < dom->dim; c++)
+    if (s->urel[c] >= 0 && !(U[c] = get_field (dom, s->urel[c]))) return GFSHIP_EINVAL;
+  std::vector<const double *> read;
+  for (gfship_field f : s->read) {
+    Field * F = get_field (dom, f);
+    if (!F) return GFSHIP_EINVAL;
+    read.push_back (F->lev[dom->depth]);
+  }
+  const bool fields = D || R || U[0] || U[1] || U[2];
+  if (fields && (r = before_write (dom))) return r;
+  if (D) {
+    /* gfs_cell_reset of the deposit: on every cell for a volume (FTT_TRAVERSE_ALL, :2844), on the leaves for a
+       mass (:3004) */
+    for (int l = volume ? 0 : dom->depth; l <= dom->depth; l++) {
+      GFSHIP_HIP (hipMemsetAsync (D->lev[l], 0, dom->lay[l].total*sizeof (double), dom->stream));
+      D->zero[l] = l < dom->depth;
+    }
+  }
+  if (R) R->zero[dom->depth] = false;
+  for (int c = 0; c < dom->dim; c++)
+    if (U[c]) U[c]->zero[dom->depth] = false;
+  if (info) info[0] = info[1] = 0.;
+  if (pl->n == 0) return GFSHIP_OK;
+  if ((r = source_reserve (s))) return r;
+  hipEvent_t ev[3] = { nullptr, nullptr, nullptr };
+  auto mark = [&] (int q) -> hipError_t {
+    if (!info) return hipSuccess;
+    hipError_t e = hipEventCreate (&ev[q]);
+    return e != hipSuccess ? e : hipEventRecord (ev[q], dom->stream);
+  };
+  GFSHIP_HIP (mark (0));
+  if ((r = launch_particulate_source_gather (pl, s->cell, s->prad, s->purel))) return r;
+  const int n = pl->n, block = 256, grid = (n + block - 1)/block;
+  if (s->fn) {
+    if ((r = rtc_launch_source (s->fn, dom->stream, n, L, s->cell, s->prad, s->purel, gfship_sim_time (pl->sim),
+				(int) read.size (), read.data (), s->src)))
+      return r;
+  }
+  else {
+    hipLaunchKernelGGL (particulate_source_constant_kernel, dim3 (grid), dim3 (block), 0, dom->stream, n,
+			s->value, s->src);
+    GFSHIP_HIP (hipGetLastError ());
+  }
+  const unsigned long long ncell = (unsigned long long) ncells (L);
+  if (fields && (r = coupling_reserve (pl, (size_t) n, 0, false))) return r;
+  unsigned long long * key = fields ? pl->ckey : nullptr;
+  const double dt = gfship_sim_view_get (pl->sim).dt;      /* sim->advection_params.dt */
+  if (volume)
+    hipLaunchKernelGGL (particulate_source_update_kernel<true>, dim3 (grid), dim3 (block), 0, dom->stream, n,
+			s->cell, s->src, dt, pl->volume, pl->dia, pl->rb, ncell, key);
+  else
+    hipLaunchKernelGGL (particulate_source_update_kernel<false>, dim3 (grid), dim3 (block), 0, dom->stream, n,
+			s->cell, s->src, dt, pl->mass, nullptr, nullptr, ncell, key);
+  GFSHIP_HIP (hipGetLastError ());
+  GFSHIP_HIP (mark (1));
+  if (fields) {
+    size_t need = 0;
+    const int bits = coupling_key_bits (ncell);
+    GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (nullptr, need, pl->ckey, pl->ckey2, n, 0, bits, dom->stream));
+    if ((r = coupling_sort_reserve (pl, need))) return r;
+    size_t tmp_bytes = pl->sort_tmp_bytes;
+    GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, n, 0, bits,
+						   dom->stream));
+    SourceCellArgs A;
+    A.L = L; A.n = n; A.key = pl->ckey2; A.ncell = ncell;
+    A.src = s->src; A.prad = s->prad;
+    A.deposit = D ? D->lev[dom->depth] : nullptr;
+    A.rad = R ? R->lev[dom->depth] : nullptr;
+    for (int c = 0; c < 3; c++) {
+      A.purel[c] = s->purel[c];
+      A.urel[c] = c < dom->dim && U[c] ? U[c]->lev[dom->depth] : nullptr;
+    }
+    with_bools ([&] (auto D3) {
+      constexpr int DIM = decltype (D3)::value ? 3 : 2;
+      hipLaunchKernelGGL (particulate_source_cell_kernel<DIM>, dim3 (grid), dim3 (block), 0, dom->stream, A);
+    }, dom->dim == 3);
+    GFSHIP_HIP (hipGetLastError ());
+  }
+  if (info) {
+    GFSHIP_HIP (mark (2));
+    GFSHIP_HIP (hipStreamSynchronize (dom->stream));
+    float a = 0.f, b = 0.f;
+    (void) hipEventElapsedTime (&a, ev[0], ev[1]);
+    (void) hipEventElapsedTime (&b, ev[1], ev[2]);
+    info[0] = a; info[1] = b;
+    for (hipEvent_t e : ev) (void) hipEventDestroy (e);
+  }
+  return GFSHIP_OK;
+}
+
+} // namespace gfship
+
+using namespace gfship;
+
+extern "C" {
+
+int gfship_particulate_source_create (gfship_particulate_source ** out, gfship_particles * pl, int kind,
+				      const char * function, int nvars, const char * const * names,
+				      const gfship_field * fields)
+{
+  GFSHIP_CHECK (out != nullptr, GFSHIP_EINVAL, "null output pointer");
+  *out = nullptr;
+  GFSHIP_CHECK (kind == GFSHIP_PARTICULATE_SOURCE_VOLUME || kind == GFSHIP_PARTICULATE_SOURCE_MASS, GFSHIP_EINVAL,
+		"kind must be GFSHIP_PARTICULATE_SOURCE_VOLUME or GFSHIP_PARTICULATE_SOURCE_MASS");
+  int r = source_check (pl, kind_name (kind));
+  if (r) return r;
+  GFSHIP_CHECK (nvars >= 0 && (nvars == 0 || (names && fields)), GFSHIP_EINVAL, "invalid table of variables");
+  gfship_domain * dom = pl->dom;
+  static const char * builtin[] = { "Rad", "Urelp", "Vrelp", "Wrelp", "x", "y", "z", "t" };
+  for (int q = 0; q < nvars; q++) {
+    GFSHIP_CHECK (c_identifier (names[q]), GFSHIP_EINVAL, "variable %d of the table has no C name", q);
+    for (const char * b : builtin)
+      GFSHIP_CHECK (strcmp (names[q], b) != 0, GFSHIP_EINVAL,
+		    "`%s' is a variable of the function itself: it cannot name a field", b);
+    for (int p = 0; p < q; p++)
+      GFSHIP_CHECK (strcmp (names[q], names[p]) != 0, GFSHIP_EINVAL, "`%s' is in the table twice", names[q]);
+    if (!get_field (dom, fields[q])) return GFSHIP_EINVAL;
+  }
+  RtcKernel * k = nullptr;
+  double value = 0.;
+  std::vector<gfship_field> read;
+  if (function) {
+    /* a constant (gfs_function_read: a number is kept as f->val) needs no compilation */
+    char * end = nullptr;
+    value = strtod (function, &end);
+    while (end != function && (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r')) end++;
+    if (end == function || *end != '\0') {
+      value = 0.;
+      std::vector<const char *> named;
+      for (int q = 0; q < nvars; q++)
+	if (names_identifier (function, names[q])) {
+	  named.push_back (names[q]);
+	  read.push_back (fields[q]);
+	}
+      if ((r = rtc_compile_source (dom, function, (int) named.size (), named.data (), &k))) return r;
+    }
+  }
+  gfship_particulate_source * s = new gfship_particulate_source;
+  s->pl = pl; s->kind = kind; s->fn = k; s->value = value; s->read = read;
+  *out = s;
+  return GFSHIP_OK;
+}
+
+int gfship_particulate_source_set_fields (gfship_particulate_source * s, gfship_field rad,
+					  const gfship_field urel[3], gfship_field deposit)
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null particulate source");
+  gfship_domain * dom = s->pl->dom;
+  gfship_field w[5] = { rad, urel ? urel[0] : -1, urel ? urel[1] : -1, urel && dom->dim == 3 ? urel[2] : -1,
+			deposit };
+  for (int q = 0; q < 5; q++) {
+    if (w[q] < 0) { w[q] = -1; continue; }
+    if (!get_field (dom, w[q])) return GFSHIP_EINVAL;
+    for (int p = 0; p < q; p++)
+      GFSHIP_CHECK (w[p] != w[q], GFSHIP_EINVAL, "one field is given for two of Rad, Urelp, Vrelp, Wrelp and the deposit");
+    for (gfship_field f : s->read) {
+      /* the function would read a running sum that depends on the walk (:2830) */
+      GFSHIP_CHECK (!(q == 4 && f == w[q]), GFSHIP_EUNSUPPORTED,
+		    "%s: the function names the variable its sources are deposited into", kind_name (s->kind));
+      GFSHIP_CHECK (f != w[q], GFSHIP_EINVAL,
+		    "%s: the function reads a field under a name of its own that is also written as Rad, Urelp, "
+		    "Vrelp or Wrelp", kind_name (s->kind));
+    }
+  }
+  s->rad = w[0]; s->urel[0] = w[1]; s->urel[1] = w[2]; s->urel[2] = w[3]; s->deposit = w[4];
+  return GFSHIP_OK;
+}
+
+int gfship_particulate_source_event (gfship_particulate_source * s)
+{
+  return source_event (s, nullptr);
+}
+
+int gfship_particulate_source_time_event (gfship_particulate_source * s, double info[2])
+{
+  GFSHIP_CHECK (info != nullptr, GFSHIP_EINVAL, "null argument");
+  return source_event (s, info);
+}
+
+void gfship_particulate_source_destroy (gfship_particulate_source * s)
+{
+  if (!s) return;
+  (void) hipStreamSynchronize (s->pl->stream);
+  void * a[] = { s->cell, s->prad, s->purel[0], s->purel[1], s->purel[2], s->src };
+  for (void * p : a)
+    if (p) (void) hipFree (p);
+  rtc_free (s->fn);
+  delete s;
+}
+
+} // extern "C"

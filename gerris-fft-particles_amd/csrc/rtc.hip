@@ -184,6 +184,69 @@ int rtc_launch_spatial (RtcKernel * k, hipStream_t stream, long nrec, int stride
   return GFSHIP_OK;
 }
 
+// the function of a GfsSourceParticulateVol / ...Mass (modules/particulatecommon.c:2826, 2984:
+// gfs_function_value (source, cell) right after the particle wrote Rad, Urelp ... into its cell): the values
+// of the particle for those four, the centre of the cell for x, y, z, and the value at the cell of every other
+// variable it names.  One thread per creation slot; cell[o] is the linear number of the cell, i fastest
+int rtc_compile_source (gfship_domain * dom, const char * text, int nf, const char * const * names,
+			RtcKernel ** out)
+{
+  GFSHIP_CHECK (dom != nullptr, GFSHIP_EINVAL, "null argument");
+  const bool d3 = dom->dim == 3;
+  std::string sig = "static __device__ double gfship_f (double Rad, double Urelp, double Vrelp, ";
+  if (d3) sig += "double Wrelp, ";
+  sig += "double x, double y, double z, double t";
+  std::string params, values;
+  for (int q = 0; q < nf; q++) {
+    sig += std::string (", double ") + names[q];
+    params += "    const double * f" + std::to_string (q) + ",\n";
+    values += ", f" + std::to_string (q) + "[idx]";
+  }
+  sig += ")\n";
+  std::string kern =
+    "extern \"C\" __global__ void gfship_psource (int n, unsigned nside, int xo, long sy, long sz,\n"
+    "    const unsigned * cell, const double * rad, const double * urel, const double * vrel,\n";
+  if (d3) kern += "    const double * wrel,\n";
+  kern += "    double t,\n" + params + "    double * out)\n"
+    "{\n"
+    "  int o = blockIdx.x*blockDim.x + threadIdx.x;\n"
+    "  if (o >= n) return;\n"
+    "  const unsigned c = cell[o];\n"
+    "  if (c == 0xFFFFFFFFu) return;\n"
+    "  const int i = (int) (c % nside) + 1, j = (int) ((c/nside) % nside) + 1;\n";
+  kern += d3 ? "  const int k = (int) (c/(nside*nside)) + 1;\n" : "  const int k = 0;\n";
+  kern +=
+    "  const long idx = xo + i + sy*j + sz*k;\n"
+    "  (void) idx;\n"
+    "  const double h = 1./nside;\n"      /* ftt_cell_pos: dyadic, exact */
+    "  out[o] = gfship_f (rad[o], urel[o], vrel[o], ";
+  if (d3) kern += "wrel[o], ";
+  kern += "-0.5 + (i - 0.5)*h, -0.5 + (j - 0.5)*h, ";
+  kern += d3 ? "-0.5 + (k - 0.5)*h" : "0.";
+  kern += ", t" + values + ");\n}\n";
+  return rtc_compile (dom->device, text, sig.c_str (), kern.c_str (), "gfship_psource", out);
+}
+
+int rtc_launch_source (RtcKernel * k, hipStream_t stream, int n, const Layout & L, const unsigned * cell,
+		       const double * rad, const double * const urel[3], double t, int nf,
+		       const double * const * fields, double * out)
+{
+  if (n <= 0) return GFSHIP_OK;
+  unsigned nside = (unsigned) L.n;
+  int xo = L.xo;
+  long sy = L.sy, sz = L.sz;
+  const double * u = urel[0], * v = urel[1], * w = urel[2];
+  std::vector<const double *> f (fields, fields + nf);
+  std::vector<void *> args = { &n, &nside, &xo, &sy, &sz, &cell, &rad, &u, &v };
+  if (L.dim == 3) args.push_back (&w);
+  args.push_back (&t);
+  for (int q = 0; q < nf; q++) args.push_back (&f[q]);
+  args.push_back (&out);
+  GFSHIP_HIP (hipModuleLaunchKernel (k->fn, (unsigned) ((n + 255)/256), 1, 1, 256, 1, 1, 0, stream, args.data (),
+				     nullptr));
+  return GFSHIP_OK;
+}
+
 int rtc_launch_coefficient (RtcKernel * k, hipStream_t stream, int n, const unsigned char * alive,
 			    const double * rep, const double * const rel[3], const double * pdia,
 			    double t, double * out)

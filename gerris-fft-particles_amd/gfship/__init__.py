@@ -177,6 +177,13 @@ SIGNATURES = {
     "gfship_particles_spread_forces": (_i, [_vp, C.POINTER(_i)]),
     "gfship_sim_set_source_fields": (_i, [_vp, C.POINTER(_i)]),
     "gfship_particles_time_spreading": (_i, [_vp, C.POINTER(_i), _pd]),
+    "gfship_particulate_source_create": (_i, [C.POINTER(_vp), _vp, _i, C.c_char_p, _i, C.POINTER(C.c_char_p),
+                                              C.POINTER(_i)]),
+    "gfship_particulate_source_set_fields": (_i, [_vp, _i, C.POINTER(_i), _i]),
+    "gfship_particulate_source_event": (_i, [_vp]),
+    "gfship_particulate_source_time_event": (_i, [_vp, _pd]),
+    "gfship_particulate_source_destroy": (None, [_vp]),
+    "gfship_particles_download_volume": (_i, [_vp, _pd]),
     "gfship_tree_create": (_i, [C.POINTER(_vp), _i, C.c_void_p, _vp, _i]),
     "gfship_tree_create_sides": (_i, [C.POINTER(_vp), _i, C.c_void_p, _vp, _pi, _i]),
     "gfship_tree_set_bc": (_i, [_vp, _i, _i]),
@@ -907,9 +914,55 @@ class ParticleList:
         """forces_on_fluid, then spread_forces"""
         _check(lib().gfship_source_particulate_event(self.ptr, self._fields3(F)))
 
+    def volumes(self):
+        """the volume of the particles on the list, in list order"""
+        m = max(_check(lib().gfship_particles_slots(self.ptr)), 1)
+        vol = np.empty(m)
+        k = _check(lib().gfship_particles_download_volume(self.ptr, vol.ctypes.data_as(_pd)))
+        return vol[:k].copy()
+
     def destroy(self):
         if self.ptr:
             lib().gfship_particles_destroy(self.ptr)
+            self.ptr = None
+
+
+SOURCE_VOLUME, SOURCE_MASS = 0, 1
+
+
+class ParticulateSource:
+    """GfsSourceParticulateVol (kind = SOURCE_VOLUME) or GfsSourceParticulateMass (SOURCE_MASS) on a list of
+    particulates of a uniform box.  function: C text of Rad, Urelp, Vrelp, Wrelp (3-D), x, y, z, t and of the
+    names of `variables' (a dict name -> Variable), a number, or None (the constant 0)."""
+
+    def __init__(self, plist, kind, function=None, variables=None):
+        variables = dict(variables or {})
+        names = (C.c_char_p * max(len(variables), 1))(*[k.encode() for k in variables])
+        fields = (_i * max(len(variables), 1))(*[v.h for v in variables.values()])
+        p = _vp()
+        _check(lib().gfship_particulate_source_create(
+            C.byref(p), plist.ptr, int(kind), None if function is None else str(function).encode(),
+            len(variables), names, fields))
+        self.ptr, self.plist = p, plist
+
+    def set_fields(self, rad=None, urel=(), deposit=None):
+        """the Variables Rad, (Urelp, Vrelp[, Wrelp]) and the deposit variable; None: not written"""
+        u = [v.h if v is not None else -1 for v in urel] + [-1] * (3 - len(urel))
+        _check(lib().gfship_particulate_source_set_fields(
+            self.ptr, -1 if rad is None else rad.h, (_i * 3)(*u), -1 if deposit is None else deposit.h))
+
+    def event(self):
+        _check(lib().gfship_particulate_source_event(self.ptr))
+
+    def time_event(self):
+        """event, measured: (ms of the passes per particle, ms of the sort and the pass per cell)"""
+        info = (C.c_double * 2)()
+        _check(lib().gfship_particulate_source_time_event(self.ptr, info))
+        return float(info[0]), float(info[1])
+
+    def destroy(self):
+        if self.ptr:
+            lib().gfship_particulate_source_destroy(self.ptr)
             self.ptr = None
 
 

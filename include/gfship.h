@@ -599,6 +599,57 @@ int  gfship_particles_time_spreading (gfship_particles * pl, const gfship_field 
    GfsBoundaryMpi sides. */
 int  gfship_sim_set_source_fields (gfship_sim * sim, const gfship_field F[3]);
 
+/* The particles themselves change: GfsSourceParticulateVol (modules/particulatecommon.c:2734-2887) and
+   GfsSourceParticulateMass (:2889-3047), objects on a list of particulates of a uniform box.
+   GFSHIP_EUNSUPPORTED on a list of a tree, on a list of tracers, on a box with GFSHIP_SIDE_EXTERNAL sides and
+   on a box of 2^32 cells or more (what the two-way coupling refuses).
+   gfship_particulate_source_create (source_particulatevol_read, :2752-2804; ..mass_read, :2908-2962): kind is
+   the class; function is its GfsFunction -- C text as in the simulation file, an expression or a { block }
+   with a return -- compiled for the device of the domain with hipRTC exactly as the force coefficients are
+   (-ffp-contract=off, the device's libm; GFSHIP_EINVAL with the compiler's messages in gfship_last_error ()
+   where it does not compile).  A number is a constant and compiles nothing; NULL is the constant 0 of
+   source_particulatevol_init / ..mass_init (:2861-2864, :3021-3024).  The function may name Rad, Urelp, Vrelp,
+   Wrelp (3-D only), x, y, z, t, and the nvars variables of the table (names[q], fields[q]); a name of the
+   table that is one of those eight, or no C identifier, is GFSHIP_EINVAL.  Destroy the object before its list.
+   gfship_particulate_source_set_fields: the variables Rad, Urelp, Vrelp, Wrelp (gfs_domain_get_or_add_variable,
+   :2785-2793) and the optional volsource / dmdtvariable (:2797-2803, :2954-2960); each may be -1: nothing is
+   written there (urel[2] is ignored in 2-D; with all five at -1 the event sorts nothing).  A function that
+   names the deposit variable would read a running sum that depends on the walk: GFSHIP_EUNSUPPORTED.
+   gfship_particulate_source_event (source_particulatevol_event, :2834-2852; ..mass_event, :2993-3012), on the
+   stream of the list: the deposit is reset (on every level for a volume, FTT_TRAVERSE_ALL :2844; on the leaves
+   for a mass, :3004), then for every particle in list order (update_vol, :2806-2832; update_mass, :2964-2991)
+   cell = gfs_domain_locate (pos); Rad[cell] = pow (3.0*volume/4.0/M_PI, 1./3.); Urelp ...[cell] =
+   gfs_interpolate (cell, pos, U ...) - vel; source = the function at the cell; volume (mass) += source*dt with
+   the dt of gfship_particle_list_event; deposit[cell] += source.  The function sees the particle's own Rad and
+   relative velocity however many particles share the cell, the cell's value of every variable of the table,
+   the centre of the cell for x, y, z and gfship_sim_time for t.  After the event Rad, Urelp ... of a cell hold
+   the values of its last particle in list order (cells without a particle keep what they held: nothing resets
+   these four), and the deposit of a cell is the left-to-right sum of its sources in list order from 0, bit for
+   bit, whatever the storage order (gfship_particles_sort) and from run to run: records sorted by (cell, list
+   position), added serially, no atomics.  A particle for which gfs_domain_locate finds no cell makes the
+   reference dereference NULL; here it is skipped: nothing is written for it and nothing of it changes.
+   After a volume event the diameter (compute_drag_force, :552) and rb (distance_normalization, :2091) of every
+   particle with a cell are recomputed from the new volume.  pow: Rad, and the diameter and rb of a particle
+   whose volume an event has changed, are values of the device's pow in the reference's expression (glibc's
+   and the device's need not round alike); everything else is the reference's arithmetic.  A list no volume
+   event has run on keeps its host-computed diameter and rb: its events give the bits they gave before.
+   gfship_particulate_source_time_event: the event, measured (no reference counterpart): info[0], info[1] = the
+   milliseconds the device spent in the passes per particle (locate and interpolation, the function, the
+   update) and in the sort with the pass per cell.
+   gfship_particles_download_volume: the volume of the particles still on the list, in list order; returns
+   their number (lists of particulates, of a box or of a tree). */
+typedef struct gfship_particulate_source gfship_particulate_source;
+enum { GFSHIP_PARTICULATE_SOURCE_VOLUME = 0, GFSHIP_PARTICULATE_SOURCE_MASS = 1 };
+int  gfship_particulate_source_create (gfship_particulate_source ** src, gfship_particles * pl, int kind,
+				       const char * function, int nvars, const char * const * names,
+				       const gfship_field * fields);
+int  gfship_particulate_source_set_fields (gfship_particulate_source * src, gfship_field rad,
+					   const gfship_field urel[3], gfship_field deposit);
+int  gfship_particulate_source_event (gfship_particulate_source * src);
+int  gfship_particulate_source_time_event (gfship_particulate_source * src, double info[2]);
+void gfship_particulate_source_destroy (gfship_particulate_source * src);
+int  gfship_particles_download_volume (gfship_particles * pl, double * volume);
+
 /* ---- one box per GPU: GfsBoundaryMpi sides (src/mpi_boundary.c:78-246) ----------------------- */
 
 /* Either the in-library RCCL transport below (gfship_domain_comm_init: what bench.py uses), or two
