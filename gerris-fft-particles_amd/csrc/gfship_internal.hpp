@@ -300,8 +300,14 @@ int launch_correct (gfship_domain * dom, int level, double * u, const double * d
 int launch_fill (gfship_domain * dom, int level, double * a, double value);
 int launch_residual_norm (gfship_domain * dom, int level, const double * u, const double * rhs,
 			  const double * dia, double * res, double scale, double weight,
-			  double * out /* 5 values, or nullptr: left in h_pinned[8..12], not waited for */, bool dia_zero = false);
+			  double * out /* 5 values, or nullptr: left in h_pinned[8..12], not waited for */, bool dia_zero = false,
+			  bool * store = nullptr /* in: false asks for the norm alone; out: whether res was stored */);
 int launch_norm_async (gfship_domain * dom, int level, const double * a, double scale, double weight);
+
+// poisson.hip: gfship_poisson_solve for a caller whose res is a temporary that nobody reads after the
+// solve (res_unread): the residual after the cycle expected to be the last is then not stored
+int poisson_solve (gfship_domain * dom, gfship_multilevel_params * par, gfship_field lhs, gfship_field rhs,
+		   gfship_field res, gfship_field dia, double dt, bool res_unread);
 int launch_norm (gfship_domain * dom, int level, const double * a, double scale, double weight,
 		 double out[5] /* bias(sum of scaled), first, second, infty, raw sum */);
 

@@ -168,9 +168,11 @@ static int norm_residual (gfship_domain * dom, double dt, Field * res, gfship_no
 // the leaf residual and its norm in one pass over the cells (rows of cells per workgroup, 1024
 // workgroups; round 1's first attempt at this, one partial record per row, was slower than the two
 // kernels)
+// store: see launch_residual_norm (nullptr: the residual is stored)
 static int residual_and_norm (gfship_domain * dom, double dt, Field * U, Field * R, Field * D,
-			      Field * S, gfship_norm * out)
+			      Field * S, gfship_norm * out, bool * store = nullptr)
 {
+  if (store && dom->weighted) *store = true;
   const int L = dom->depth;
   S->zero[L] = false;
   if (dom->weighted) {
@@ -181,7 +183,7 @@ static int residual_and_norm (gfship_domain * dom, double dt, Field * U, Field *
   const double size = 1./dom->lay[L].n;
   double s[5];
   int r = launch_residual_norm (dom, L, U->lev[L], R->lev[L], D->lev[L], S->lev[L], 1.*size*size, 1., s,
-				D->zero[L]);
+				D->zero[L], store);
   if (r) return r;
   return norm_residual_finish (dom, dt, s, out);
 }
@@ -353,10 +355,12 @@ int gfship_norm_variable (gfship_domain * dom, gfship_field v, gfship_norm * out
 } // extern "C"
 
 // gfs_poisson_cycle; with norm != nullptr the norm of the new residual (scaled by dt) comes out of
-// the same pass that computes it (the solve loop asks for it right after the cycle)
+// the same pass that computes it (the solve loop asks for it right after the cycle); store_res: in,
+// false asks for that norm alone where the kernel can leave the store out; out, whether res holds
+// the new residual
 static int poisson_cycle (gfship_domain * dom, gfship_multilevel_params * p,
 			  gfship_field u, gfship_field rhs, gfship_field dia, gfship_field res,
-			  double dt, gfship_norm * norm)
+			  double dt, gfship_norm * norm, bool * store_res = nullptr)
 {
   GFSHIP_CHECK (dom && p, GFSHIP_EINVAL, "null argument");
   GFSHIP_CHECK (p->dimension == 2 || p->dimension == 3, GFSHIP_EINVAL, "dimension must be 2 or 3");
@@ -458,7 +462,7 @@ static int poisson_cycle (gfship_domain * dom, gfship_multilevel_params * p,
     TRY (launch_bc (dom, U, U, L, 0));
   /* compute new residual on leaf cells */
   if (norm)
-    TRY (residual_and_norm (dom, dt, U, R, D, S, norm));
+    TRY (residual_and_norm (dom, dt, U, R, D, S, norm, store_res));
   else if (dom->weighted)
     TRY (launch_residual_weighted (dom, L, U->lev[L], R->lev[L], D->lev[L], S->lev[L]));
   else
@@ -485,6 +489,22 @@ int gfship_poisson_solve (gfship_domain * dom, gfship_multilevel_params * par,
 			  gfship_field lhs, gfship_field rhs, gfship_field res,
 			  gfship_field dia, double dt)
 {
+  return poisson_solve (dom, par, lhs, rhs, res, dia, dt, false);
+}
+
+} // extern "C"
+
+// gfs_poisson_solve.  res_unread: res is a temporary of the caller that nobody reads after the solve
+// (the next solve overwrites it before reading it).  The residual pass after the cycle that is
+// expected to be the last -- the cycle count this parameter set ended its previous solve with --
+// then computes the norm alone.  Where the loop goes on after such a pass the residual is stored
+// by a pass of its own before the next cycle restricts it; where it ends earlier nothing is lost.
+namespace gfship {
+
+int poisson_solve (gfship_domain * dom, gfship_multilevel_params * par,
+		   gfship_field lhs, gfship_field rhs, gfship_field res,
+		   gfship_field dia, double dt, bool res_unread)
+{
   GFSHIP_CHECK (dom && par, GFSHIP_EINVAL, "null argument");
   Field * U = get_field (dom, lhs), * R = get_field (dom, rhs), * D = get_field (dom, dia),
     * S = get_field (dom, res);
@@ -500,6 +520,8 @@ int gfship_poisson_solve (gfship_domain * dom, gfship_multilevel_params * par,
   if ((r = coarse_flush (dom, U, L, true))) return r;
   unsigned minlevel = par->minlevel;
   par->depth = L;
+  const unsigned predicted = res_unread ? par->niter : 0;   /* 0: no prediction */
+  bool res_stored = true;
   par->niter = 0;
 
   /* calculates the initial residual and its norm.  With nitermin >= 1 the first cycle runs whatever
@@ -527,7 +549,15 @@ int gfship_poisson_solve (gfship_domain * dom, gfship_multilevel_params * par,
 
   while (par->niter < par->nitermin ||
 	 (par->residual.infty > par->tolerance && par->niter < par->nitermax)) {
-    if ((r = poisson_cycle (dom, par, lhs, rhs, dia, res, dt, &par->residual))) {
+    if (!res_stored) {
+      /* the pass after the last cycle left the store out and the loop goes on: the cycle restricts res */
+      if ((r = launch_residual (dom, L, U->lev[L], R->lev[L], D->lev[L], S->lev[L]))) break;
+      res_stored = true;
+    }
+    bool store = !(predicted > 0 && par->niter + 1 == predicted);
+    r = poisson_cycle (dom, par, lhs, rhs, dia, res, dt, &par->residual, &store);
+    res_stored = store;
+    if (r) {
       if (deferred) {
 	/* the cycle failed after the first norm was enqueued: callers that print the statistics
 	   still get residual_before (and no stale residual) */
@@ -567,6 +597,10 @@ int gfship_poisson_solve (gfship_domain * dom, gfship_multilevel_params * par,
     r = lattice_check_error (dom);
   return r;
 }
+
+} // namespace gfship
+
+extern "C" {
 
 int gfship_time_relax (gfship_domain * dom, unsigned d, int level, gfship_field u,
 		       gfship_field rhs, gfship_field dia, int reps, double * ms_per_sweep)

@@ -402,6 +402,82 @@ struct CoarseCycleArgs {
   double omega;
 };
 
+// The plane loop of a 3-D level with n = 2^LG >= 4 cells per side on the usual path of
+// coarse_cycle_kernel (dia == 0, one (sweep slot, line of x) per thread; the comment on the sweep
+// lag there describes the loop): the same cells at the same iterations with the same reads and
+// writes, written for the fewest instructions per iteration -- a wave issues one instruction every
+// few cycles whatever the instruction is, and an iteration lasts as long as the instruction stream
+// of the busiest wave.
+//  - n is a compile-time constant: every LDS access is one address register plus an immediate offset
+//    (the right-hand side follows the solution of the level in LDS);
+//  - a thread keeps its lines to their end: slot g runs the sweeps g, g + nconc, ..., and all a thread
+//    carries from iteration to iteration is q0, the iteration at which its current line starts (the
+//    line of sweep sw starts at sw*n + J + K; the next one of the slot nconc*n iterations later, after
+//    the end of this one);
+//  - every value an iteration needs is loaded in one batch after the barrier, the values the refresh
+//    copies included (threads that refresh nothing load a cell of their own row instead);
+//  - PER: all six sides periodic, the refresh is two copies per direction.
+template <int LG, bool PER>
+__device__ __forceinline__ void coarse_plane_loop (double * s, const BcDesc & bc, const int S, const int tid)
+{
+  constexpr int n = 1 << LG, r = n + 2, ssy = r, ssz = r*r, nface = n*n;
+  constexpr int nplanes = 3*n - 2, nconc = (nplanes + n - 1)/n;
+  const int niter = nplanes + (S - 1)*n;
+  const bool per0 = PER || bc.side[0] == GFSHIP_SIDE_PERIODIC, per1 = PER || bc.side[1] == GFSHIP_SIDE_PERIODIC;
+  const bool per2 = PER || bc.side[2] == GFSHIP_SIDE_PERIODIC, per3 = PER || bc.side[3] == GFSHIP_SIDE_PERIODIC;
+  const bool per4 = PER || bc.side[4] == GFSHIP_SIDE_PERIODIC, per5 = PER || bc.side[5] == GFSHIP_SIDE_PERIODIC;
+  const int g = tid >> (2*LG), t = tid & (nface - 1);
+  const int J = t & (n - 1), K = t >> LG;
+  const int j = n - J, k = n - K;
+  double * srow = s + (ssy*j + ssz*k);
+  const double * rrow = srow + r*r*r;
+  const bool jl = j == 1, kl = k == 1;
+  // the first cells of the lines along y and z through this row, for the rows that have the last ones
+  const double * fyrow = srow + (jl ? (n - 1)*ssy : 0), * fzrow = srow + (kl ? (n - 1)*ssz : 0);
+  const int none = 1 << 30;
+  int q0 = g < nconc && g < S ? g*n + J + K : none;
+  const int qlim = S*n + J + K;          // the line in the sweep after the last
+  const int rlim = (S - 1)*n + J + K;    // the line in the last sweep: nothing is refreshed
+  for (int q = 0; q < niter; q++) {
+    const int I = q - q0;
+    if ((unsigned) I < (unsigned) n) {
+      const int i = I + 1;
+      const double right = srow[i + 1], left = srow[i - 1], up = srow[i + ssy], down = srow[i - ssy];
+      const double front = srow[i + ssz], back = srow[i - ssz], rh = rrow[i];
+      const double fx = srow[1], fy = fyrow[i], fz = fzrow[i];
+      // cell_update_six, as written before the shared header: through it this kernel's code comes out different
+      double b = 0.;
+      b += 1.*right;
+      b += 1.*left;
+      b += 1.*up;
+      b += 1.*down;
+      b += 1.*front;
+      b += 1.*back;
+      const double v = divide_by_6 (b - rh);
+      srow[i] = v;
+      if (q0 < rlim) {
+	if (i == n) {
+	  srow[0] = per1 ? v : ghost_value (bc.type[1], bc.component, 0, fx, 1, 0., 0.);
+	  srow[n + 1] = per0 ? fx : ghost_value (bc.type[0], bc.component, 0, v, 1, 0., 0.);
+	}
+	if (jl) {
+	  srow[i + n*ssy] = per2 ? v : ghost_value (bc.type[2], bc.component, 1, fy, 1, 0., 0.);
+	  srow[i - ssy] = per3 ? fy : ghost_value (bc.type[3], bc.component, 1, v, 1, 0., 0.);
+	}
+	if (kl) {
+	  srow[i + n*ssz] = per4 ? v : ghost_value (bc.type[4], bc.component, 2, fz, 1, 0., 0.);
+	  srow[i - ssz] = per5 ? fz : ghost_value (bc.type[5], bc.component, 2, v, 1, 0., 0.);
+	}
+      }
+      if (i == n) {
+	q0 += nconc*n;
+	if (q0 >= qlim) q0 = none;
+      }
+    }
+    __syncthreads ();
+  }
+}
+
 template <int DIM>
 __global__ void __launch_bounds__(1024)
 coarse_cycle_kernel (CoarseCycleArgs A)
@@ -446,6 +522,45 @@ coarse_cycle_kernel (CoarseCycleArgs A)
     const double * gf = A.res[l + 1];
     const double * sf = lds + (top ? 0 : lds_off (l + 1, 1));
     double * sc = lds + lds_off (l, 1);
+    if (DIM == 3 && top) {
+      // from device memory: the children 2i - 1, 2i of a coarse cell are one 16-byte pair (the rows
+      // of interior cells start 16-byte aligned, Layout), and the loads of up to four cells of a thread
+      // are issued before the first is waited for.  Same order of the eight additions.
+      typedef double d2 __attribute__((ext_vector_type(2)));
+      const int lgc = __ffs (n) - 1;
+      for (int q0 = tid; q0 < ncell; q0 += 4*nt) {
+	d2 ch[4][4];
+#pragma unroll
+	for (int e = 0; e < 4; e++) {
+	  const int q = q0 + e*nt;
+	  if (q < ncell) {
+	    const int i = (q & (n - 1)) + 1, j = ((q >> lgc) & (n - 1)) + 1, k = (q >> 2*lgc) + 1;
+	    const double * p = gf + Lf.idx (2*i - 1, 2*j, 2*k);
+	    ch[e][0] = *(const d2 *) p;
+	    ch[e][1] = *(const d2 *) (p - Lf.sy);
+	    ch[e][2] = *(const d2 *) (p - Lf.sz);
+	    ch[e][3] = *(const d2 *) (p - Lf.sy - Lf.sz);
+	  }
+	}
+#pragma unroll
+	for (int e = 0; e < 4; e++) {
+	  const int q = q0 + e*nt;
+	  if (q < ncell) {
+	    const int i = (q & (n - 1)) + 1, j = ((q >> lgc) & (n - 1)) + 1, k = (q >> 2*lgc) + 1;
+	    double val = 0.;
+#pragma unroll
+	    for (int m = 0; m < 4; m++) {
+	      val += ch[e][m].x;
+	      val += ch[e][m].y;
+	    }
+	    double v = A.dimension == 2 ? val : val/2.;
+	    sc[i + r*(j + r*k)] = v;
+	    A.res[l][Lc.idx (i, j, k)] = v;
+	  }
+	}
+      }
+    }
+    else
     for (int q = tid; q < ncell; q += nt) {
       int i = q % n + 1, j = (q / n) % n + 1, k = DIM == 3 ? q / (n*n) + 1 : 0;
       double val = 0.;
@@ -511,14 +626,15 @@ coarse_cycle_kernel (CoarseCycleArgs A)
 	int d = q / nface, f = q % nface;
 	int c = d/2;
 	int t1 = f % n + 1, t2 = DIM == 3 ? f / n + 1 : 0;
-	int ijk[3] = { 0, 0, 0 };
-	int ta = c == 0 ? 1 : 0, tb = c == 2 ? 1 : 2;
-	ijk[c] = (d & 1) ? 1 : n;
-	ijk[ta] = t1;
-	if (DIM == 3) ijk[tb] = t2;
+	// the cell beside the face: c is the normal direction, t1 and t2 run along the two others
+	// (selects, not an array indexed by c: that lives in scratch)
+	const int fixed = (d & 1) ? 1 : n;
+	const int ci = c == 0 ? fixed : t1;
+	const int cj = c == 1 ? fixed : c == 0 ? t1 : t2;
+	const int ck = DIM == 3 ? (c == 2 ? fixed : t2) : 0;
 	long o = c == 0 ? 1 : c == 1 ? ssy : ssz;
 	if (d & 1) o = - o;
-	long nb = ijk[0] + ssy*ijk[1] + ssz*ijk[2];
+	long nb = ci + ssy*cj + ssz*ck;
 	double v;
 	if (A.bc.side[d] == GFSHIP_SIDE_PERIODIC)
 	  v = s[nb - (long) (n - 1)*o];
@@ -527,6 +643,7 @@ coarse_cycle_kernel (CoarseCycleArgs A)
 	s[nb + o] = v;
       }
       __syncthreads ();
+      LAB_STAMP ();
       // The sweeps of the loop follow each other n planes apart instead of one after the other:
       // sweep s is on plane q - s*n at iteration q.  A cell of sweep s+1 on plane p needs its
       // later neighbours (plane p + 1) from sweep s -- two planes would do -- and the ghosts of its
@@ -576,9 +693,29 @@ coarse_cycle_kernel (CoarseCycleArgs A)
 	  }
 	}
       };
-      if (DIM == 3 && !dia && A.dimension == 3 && nconc*nface <= nt) {
-	// the usual case, one (sweep slot, line of x) per thread for the whole loop: what does not
-	// change from plane to plane is computed once, an iteration is the stencil and a barrier
+      bool looped = false;
+      if constexpr (DIM == 3)
+	if (!dia && A.dimension == 3 && nconc*nface <= nt && lg >= 2 && lg <= 4) {
+	  // the usual case on the levels 4^3, 8^3 and 16^3 (a larger one does not fit in LDS)
+	  const bool per = per0 && per1 && per2 && per3 && per4 && per5;
+	  if (per)
+	    switch (lg) {
+	    case 2: coarse_plane_loop<2, true> (s, A.bc, S, tid); break;
+	    case 3: coarse_plane_loop<3, true> (s, A.bc, S, tid); break;
+	    default: coarse_plane_loop<4, true> (s, A.bc, S, tid); break;
+	    }
+	  else
+	    switch (lg) {
+	    case 2: coarse_plane_loop<2, false> (s, A.bc, S, tid); break;
+	    case 3: coarse_plane_loop<3, false> (s, A.bc, S, tid); break;
+	    default: coarse_plane_loop<4, false> (s, A.bc, S, tid); break;
+	    }
+	  looped = true;
+	}
+      if (looped)
+	;
+      else if (DIM == 3 && !dia && A.dimension == 3 && nconc*nface <= nt) {
+	// the same on the levels 1^3 and 2^3, with n not known at compile time
 	const int g = tid >> lgf, t = tid & (nface - 1);
 	const int J = t & (n - 1), K = t >> lg;
 	const int j = n - J, k = n - K;
@@ -1220,7 +1357,7 @@ residual_kernel (Layout L, const double * __restrict__ u, const double * __restr
   res[c] = residual_close (s.a, s.b, rhs[c], u[c]);
 }
 
-template <bool NORM>
+template <bool NORM, bool STORE = true>
 __global__ void residual_norm2_kernel (Layout L, const double * __restrict__ u, const double * __restrict__ rhs,
 				       const double * __restrict__ dia, double * __restrict__ res, double inv,
 				       double weight, double * __restrict__ partial);
@@ -1698,7 +1835,9 @@ residual_norm_kernel (Layout L, const double * __restrict__ u, const double * __
 // two cells instead of 16 and 2 (the 8-byte version moved 3.1 TB/s of its 24 B per cell at 256^3: bound
 // by the number of requests, not by bytes).  Same arithmetic per cell; the sums are accumulated in
 // another order (they are tree-reduced anyway: 1e-12), the maximum is exact.
-template <bool NORM>
+// STORE = false: the norm alone, for a residual that nobody reads (res is not touched); the same
+// loads, the same expressions and the same order of the sums, so the norm has the same bits.
+template <bool NORM, bool STORE>
 __global__ void __launch_bounds__(256)
 residual_norm2_kernel (Layout L, const double * __restrict__ u, const double * __restrict__ rhs,
 		       const double * __restrict__ dia, double * __restrict__ res, double inv,
@@ -1743,7 +1882,8 @@ residual_norm2_kernel (Layout L, const double * __restrict__ u, const double * _
       a += 1.; b += 1.*uk.y;
       out.y = rh.y - (b - uc.y*a);
     }
-    *(d2 *) (res + c) = out;
+    if (STORE)
+      *(d2 *) (res + c) = out;
     if (NORM)
 #pragma unroll
     for (int e = 0; e < 2; e++) {
@@ -1779,9 +1919,14 @@ residual_norm2_kernel (Layout L, const double * __restrict__ u, const double * _
 // the caller synchronises later, launch_norm_async's convention)
 int launch_residual_norm (gfship_domain * dom, int level, const double * u, const double * rhs,
 			  const double * dia, double * res, double scale, double weight,
-			  double * out, bool dia_zero)
+			  double * out, bool dia_zero, bool * store)
 {
   const Layout & L = dom->lay[level];
+  /* the norm alone only where the pairs kernel runs; everywhere else res is stored, and the caller
+     is told so */
+  const bool no_store = store && !*store && power_of_two (scale) && dom->dim == 3 && L.n >= 64 &&
+    dom->sw.residual_pairs;
+  if (store) *store = !no_store;
   if (!power_of_two (scale)) {
     int r = launch_residual (dom, level, u, rhs, dia, res);
     if (r) return r;
@@ -1803,8 +1948,10 @@ int launch_residual_norm (gfship_domain * dom, int level, const double * u, cons
     const long nitems = (long) L.n*L.n*(L.n/2);
     long nb = (nitems + 255)/256;
     nblocks = (int) (nb > rn_blocks ? rn_blocks : nb);
-    hipLaunchKernelGGL (residual_norm2_kernel<true>, dim3 (nblocks), dim3 (256), 0, dom->stream, L, u,
-			rhs, dia_zero ? nullptr : dia, res, 1./scale, weight, partial);
+    with_bools ([&] (auto ST) {
+      hipLaunchKernelGGL ((residual_norm2_kernel<true, decltype (ST)::value>), dim3 (nblocks), dim3 (256), 0,
+			  dom->stream, L, u, rhs, dia_zero ? nullptr : dia, res, 1./scale, weight, partial);
+    }, !no_store);
   }
   else
     with_bools ([&] (auto D3) {

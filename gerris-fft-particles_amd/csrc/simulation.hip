@@ -244,7 +244,8 @@ int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, g
   else
     dom->kc[GFSHIP_KC_DIVERGENCE_FUSED]++;
   s->div_ready = false;
-  TRY (gfship_poisson_solve (dom, par, p, s->div, s->res, s->dia, dt));
+  /* s->res is a temporary of the simulation, never handed out: the next solve overwrites it before reading it */
+  TRY (poisson_solve (dom, par, p, s->div, s->res, s->dia, dt, true));
   /* gfs_correct_normal_velocities + gfs_scale_gradients, and for the approximate projection
      gfs_correct_centered_velocities (src/timestep.c:486-530), in one pass over p.  The pass
      also leaves the largest |un|, |u| behind for the CFL condition of the next time step. */
