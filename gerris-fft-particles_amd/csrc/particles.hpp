@@ -1,6 +1,7 @@
 // particles.hpp -- the particle list and the cell search shared by particles.hip and coupling.hip.
 #pragma once
 #include "gfship_internal.hpp"
+#include <vector>
 
 namespace gfship {
 struct RtcKernel;
@@ -25,7 +26,31 @@ int  rtc_compile_source (gfship_domain * dom, const char * text, int nf, const c
 int  rtc_launch_source (RtcKernel * k, hipStream_t stream, int n, const Layout & L, const unsigned * cell,
 			const double * rad, const double * const urel[3], double t, int nf,
 			const double * const * fields, double * out);
+// the same function on a list of a tree: cell[o] is the index of the leaf in the concatenated levels (Topo::gi);
+// the kernel finds the level of the leaf from the level offsets off[0 .. depth + 1] and its integer coordinates
+// from its index in the dense level, x, y, z = ftt_cell_pos of the leaf, and reads the variables (arrays of all
+// levels) at the leaf
+int  rtc_compile_tree_source (int device, int dim, const char * text, int nf, const char * const * names,
+			      RtcKernel ** out);
+int  rtc_launch_tree_source (RtcKernel * k, hipStream_t stream, int n, int dim, int depth, const int * off,
+			     const unsigned * cell, const double * rad, const double * const urel[3], double t,
+			     int nf, const double * const * fields, double * out);
 }
+
+// a GfsSourceParticulateVol / ...Mass (particulate_sources.hip) on a list of a box, or of a tree (pl->tree: the
+// variables are GFSHIP_TREE_* numbers and the event is tree_particulate_source_event, tree_particles.hip)
+struct gfship_particulate_source {
+  gfship_particles * pl = nullptr;
+  int kind = GFSHIP_PARTICULATE_SOURCE_VOLUME;
+  gfship::RtcKernel * fn = nullptr;      // nullptr: the constant `value'
+  double value = 0.;
+  std::vector<gfship_field> read;        // the fields the function names, in the order of its arguments
+  gfship_field rad = -1, urel[3] = { -1, -1, -1 }, deposit = -1;
+  // per creation slot: the cell, Rad, Urelp ..., the source
+  unsigned * cell = nullptr;
+  double * prad = nullptr, * purel[3] = {}, * src = nullptr;
+  int cap = 0;
+};
 
 struct gfship_particles {
   gfship_sim * sim = nullptr;
@@ -116,6 +141,14 @@ int tree_particulate_list_event (gfship_particles * pl);
 // interpolate of the event kernels (particles.hip): per creation slot the linear number of the particle's cell
 // (PSOURCE_NO_CELL off the list or without a cell), pow (3.0*volume/4.0/M_PI, 1./3.) and fluid velocity - vel
 int launch_particulate_source_gather (gfship_particles * pl, unsigned * cell, double * rad, double * const urel[3]);
+// the passes of particulate_sources.hip that the event of a tree shares: the per-slot arrays of the object, the
+// constant function, and step 3 (volume or mass += source*dt, diameter and rb, the key cell << 32 | slot)
+int particulate_source_reserve (gfship_particulate_source * s);
+int launch_particulate_source_constant (hipStream_t stream, int n, double value, double * out);
+int launch_particulate_source_update (gfship_particulate_source * s, hipStream_t stream, double dt,
+				      unsigned long long pad, unsigned long long * key);
+// the event of a source on a list of a tree (tree_particles.hip); info as in source_event
+int tree_particulate_source_event (gfship_particulate_source * s, double * info);
 }
 
 // the coupling calls of a tree (gfship_tree_particulate_field ...): lists made by gfship_particulates_create_tree

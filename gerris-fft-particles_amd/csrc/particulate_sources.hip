@@ -24,24 +24,12 @@
 // operation by operation.  A list no volume event has run on keeps the diameter and rb computed on the host
 // (particulate_alloc).
 #include "particles.hpp"
+#include "tree_particles.hpp"
 #include <hipcub/hipcub.hpp>
 #include <cmath>
 #include <cstdlib>
 #include <string>
 #include <vector>
-
-struct gfship_particulate_source {
-  gfship_particles * pl = nullptr;
-  int kind = GFSHIP_PARTICULATE_SOURCE_VOLUME;
-  gfship::RtcKernel * fn = nullptr;      // nullptr: the constant `value'
-  double value = 0.;
-  std::vector<gfship_field> read;        // the fields the function names, in the order of its arguments
-  gfship_field rad = -1, urel[3] = { -1, -1, -1 }, deposit = -1;
-  // per creation slot: the cell, Rad, Urelp ..., the source
-  unsigned * cell = nullptr;
-  double * prad = nullptr, * purel[3] = {}, * src = nullptr;
-  int cap = 0;
-};
 
 namespace gfship {
 
@@ -162,7 +150,7 @@ static const char * kind_name (int kind)
   return kind == GFSHIP_PARTICULATE_SOURCE_VOLUME ? "GfsSourceParticulateVol" : "GfsSourceParticulateMass";
 }
 
-static int source_reserve (gfship_particulate_source * s)
+int particulate_source_reserve (gfship_particulate_source * s)
 {
   gfship_particles * pl = s->pl;
   if (s->cap >= pl->n) return GFSHIP_OK;
@@ -179,12 +167,37 @@ static int source_reserve (gfship_particulate_source * s)
   return GFSHIP_OK;
 }
 
+int launch_particulate_source_constant (hipStream_t stream, int n, double value, double * out)
+{
+  const int block = 256, grid = (n + block - 1)/block;
+  hipLaunchKernelGGL (particulate_source_constant_kernel, dim3 (grid), dim3 (block), 0, stream, n, value, out);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
+int launch_particulate_source_update (gfship_particulate_source * s, hipStream_t stream, double dt,
+				      unsigned long long pad, unsigned long long * key)
+{
+  gfship_particles * pl = s->pl;
+  const int n = pl->n, block = 256, grid = (n + block - 1)/block;
+  if (s->kind == GFSHIP_PARTICULATE_SOURCE_VOLUME)
+    hipLaunchKernelGGL (particulate_source_update_kernel<true>, dim3 (grid), dim3 (block), 0, stream, n,
+			s->cell, s->src, dt, pl->volume, pl->dia, pl->rb, pad, key);
+  else
+    hipLaunchKernelGGL (particulate_source_update_kernel<false>, dim3 (grid), dim3 (block), 0, stream, n,
+			s->cell, s->src, dt, pl->mass, nullptr, nullptr, pad, key);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
 // info != nullptr: the milliseconds of the per-particle passes (steps 1 to 3) and of the sort with the pass per
 // cell (step 4), from events on the stream
 static int source_event (gfship_particulate_source * s, double * info)
 {
   GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null particulate source");
   gfship_particles * pl = s->pl;
+  if (pl->tree)      /* the handle knows what made it */
+    return tree_particulate_source_event (s, info);
   const char * what = kind_name (s->kind);
   int r = source_check (pl, what);
   if (r) return r;
@@ -217,7 +230,7 @@ static int source_event (gfship_particulate_source * s, double * info)
     if (U[c]) U[c]->zero[dom->depth] = false;
   if (info) info[0] = info[1] = 0.;
   if (pl->n == 0) return GFSHIP_OK;
-  if ((r = source_reserve (s))) return r;
+  if ((r = particulate_source_reserve (s))) return r;
   hipEvent_t ev[3] = { nullptr, nullptr, nullptr };
   auto mark = [&] (int q) -> hipError_t {
     if (!info) return hipSuccess;
@@ -232,22 +245,13 @@ static int source_event (gfship_particulate_source * s, double * info)
 				(int) read.size (), read.data (), s->src)))
       return r;
   }
-  else {
-    hipLaunchKernelGGL (particulate_source_constant_kernel, dim3 (grid), dim3 (block), 0, dom->stream, n,
-			s->value, s->src);
-    GFSHIP_HIP (hipGetLastError ());
-  }
+  else if ((r = launch_particulate_source_constant (dom->stream, n, s->value, s->src)))
+    return r;
   const unsigned long long ncell = (unsigned long long) ncells (L);
   if (fields && (r = coupling_reserve (pl, (size_t) n, 0, false))) return r;
   unsigned long long * key = fields ? pl->ckey : nullptr;
   const double dt = gfship_sim_view_get (pl->sim).dt;      /* sim->advection_params.dt */
-  if (volume)
-    hipLaunchKernelGGL (particulate_source_update_kernel<true>, dim3 (grid), dim3 (block), 0, dom->stream, n,
-			s->cell, s->src, dt, pl->volume, pl->dia, pl->rb, ncell, key);
-  else
-    hipLaunchKernelGGL (particulate_source_update_kernel<false>, dim3 (grid), dim3 (block), 0, dom->stream, n,
-			s->cell, s->src, dt, pl->mass, nullptr, nullptr, ncell, key);
-  GFSHIP_HIP (hipGetLastError ());
+  if ((r = launch_particulate_source_update (s, dom->stream, dt, ncell, key))) return r;
   GFSHIP_HIP (mark (1));
   if (fields) {
     size_t need = 0;
@@ -337,10 +341,93 @@ int gfship_particulate_source_create (gfship_particulate_source ** out, gfship_p
   return GFSHIP_OK;
 }
 
+int gfship_tree_particulate_source_create (gfship_particulate_source ** out, gfship_particles * pl, int kind,
+					   const char * function, int nvars, const char * const * names,
+					   const int * vars)
+{
+  GFSHIP_CHECK (out != nullptr, GFSHIP_EINVAL, "null output pointer");
+  *out = nullptr;
+  GFSHIP_CHECK (kind == GFSHIP_PARTICULATE_SOURCE_VOLUME || kind == GFSHIP_PARTICULATE_SOURCE_MASS, GFSHIP_EINVAL,
+		"kind must be GFSHIP_PARTICULATE_SOURCE_VOLUME or GFSHIP_PARTICULATE_SOURCE_MASS");
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_tree_particulate_source_create");
+  GFSHIP_CHECK (nvars >= 0 && (nvars == 0 || (names && vars)), GFSHIP_EINVAL, "invalid table of variables");
+  static const char * builtin[] = { "Rad", "Urelp", "Vrelp", "Wrelp", "x", "y", "z", "t" };
+  for (int q = 0; q < nvars; q++) {
+    GFSHIP_CHECK (c_identifier (names[q]), GFSHIP_EINVAL, "variable %d of the table has no C name", q);
+    for (const char * b : builtin)
+      GFSHIP_CHECK (strcmp (names[q], b) != 0, GFSHIP_EINVAL,
+		    "`%s' is a variable of the function itself: it cannot name a variable of the tree", b);
+    for (int p = 0; p < q; p++)
+      GFSHIP_CHECK (strcmp (names[q], names[p]) != 0, GFSHIP_EINVAL, "`%s' is in the table twice", names[q]);
+    GFSHIP_CHECK (!(vars[q] >= GFSHIP_TREE_RAD && vars[q] <= GFSHIP_TREE_DMDT), GFSHIP_EUNSUPPORTED,
+		  "%s: `%s' names a variable the walk of the list writes (Rad, Urelp, Vrelp, Wrelp or a deposit)",
+		  kind_name (kind), names[q]);
+    GFSHIP_CHECK (tree_has_variable (pl->tree, vars[q]), GFSHIP_EINVAL,
+		  "`%s': the tree has no variable %d", names[q], vars[q]);
+  }
+  RtcKernel * k = nullptr;
+  double value = 0.;
+  std::vector<gfship_field> read;
+  if (function) {
+    /* a constant (gfs_function_read: a number is kept as f->val) needs no compilation */
+    char * end = nullptr;
+    value = strtod (function, &end);
+    while (end != function && (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r')) end++;
+    if (end == function || *end != '\0') {
+      value = 0.;
+      std::vector<const char *> named;
+      for (int q = 0; q < nvars; q++)
+	if (names_identifier (function, names[q])) {
+	  named.push_back (names[q]);
+	  read.push_back (vars[q]);
+	}
+      const int device = tree_device (pl->tree);
+      GFSHIP_HIP (hipSetDevice (device));
+      int r = rtc_compile_tree_source (device, pl->dim, function, (int) named.size (), named.data (), &k);
+      if (r) return r;
+    }
+  }
+  gfship_particulate_source * s = new gfship_particulate_source;
+  s->pl = pl; s->kind = kind; s->fn = k; s->value = value; s->read = read;
+  *out = s;
+  return GFSHIP_OK;
+}
+
+int gfship_tree_particulate_source_set_fields (gfship_particulate_source * s, int rad, const int urel[3], int deposit)
+{
+  GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null particulate source");
+  GFSHIP_CHECK (s->pl->tree != nullptr, GFSHIP_EUNSUPPORTED,
+		"gfship_tree_particulate_source_set_fields: the source of a list of a box "
+		"(gfship_particulate_source_set_fields)");
+  const int dim = s->pl->dim;
+  const int w[5] = { rad, urel ? urel[0] : -1, urel ? urel[1] : -1, urel ? urel[2] : -1, deposit };
+  const int designated[5] = { GFSHIP_TREE_RAD, GFSHIP_TREE_URELP, GFSHIP_TREE_VRELP, GFSHIP_TREE_WRELP,
+			      s->kind == GFSHIP_PARTICULATE_SOURCE_VOLUME ? GFSHIP_TREE_VOLSRC : GFSHIP_TREE_DMDT };
+  static const char * name[5] = { "rad", "urel[0]", "urel[1]", "urel[2]", "deposit" };
+  for (int q = 0; q < 5; q++)
+    GFSHIP_CHECK (w[q] < 0 || w[q] == designated[q], GFSHIP_EINVAL,
+		  "%s: %s is variable %d of a tree, or -1", kind_name (s->kind), name[q], designated[q]);
+  GFSHIP_CHECK (dim == 3 || w[3] < 0, GFSHIP_EINVAL, "a quadtree has no GFSHIP_TREE_WRELP");
+  /* an argument is allocated here, zeroed: the event finds it */
+  for (int q = 0; q < 5; q++)
+    if (w[q] >= 0) {
+      int r = tree_source_variable (s->pl->tree, w[q], nullptr);
+      if (r) return r;
+    }
+  s->rad = w[0] < 0 ? -1 : w[0];
+  for (int c = 0; c < 3; c++) s->urel[c] = w[1 + c] < 0 ? -1 : w[1 + c];
+  s->deposit = w[4] < 0 ? -1 : w[4];
+  return GFSHIP_OK;
+}
+
 int gfship_particulate_source_set_fields (gfship_particulate_source * s, gfship_field rad,
 					  const gfship_field urel[3], gfship_field deposit)
 {
   GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null particulate source");
+  GFSHIP_CHECK (s->pl->tree == nullptr, GFSHIP_EUNSUPPORTED,
+		"gfship_particulate_source_set_fields: the source of a list of a tree takes the variables of the tree "
+		"(gfship_tree_particulate_source_set_fields)");
   gfship_domain * dom = s->pl->dom;
   gfship_field w[5] = { rad, urel ? urel[0] : -1, urel ? urel[1] : -1, urel && dom->dim == 3 ? urel[2] : -1,
 			deposit };

@@ -247,6 +247,76 @@ int rtc_launch_source (RtcKernel * k, hipStream_t stream, int n, const Layout & 
   return GFSHIP_OK;
 }
 
+// the same function on a list of a tree (update_vol / update_mass with cell = the leaf of gfs_domain_locate
+// (pos, -1)): cell[o] is the index of the leaf in the concatenated levels.  Its level is the last one whose offset
+// is not beyond it (level_of, tree_particles.hip; the loop has constant bounds, so the offsets are read from the
+// kernel arguments with constant indices), its integer coordinates come from its index in the dense (2^l + 2)^dim
+// level, and ftt_cell_pos is -0.5 + (i - 0.5)*2^-l, dyadic and exact.  The variables are arrays of all levels
+struct TreeSourceOffsets { int v[GFSHIP_MAXLEVEL + 2]; };
+
+int rtc_compile_tree_source (int device, int dim, const char * text, int nf, const char * const * names,
+			     RtcKernel ** out)
+{
+  const bool d3 = dim == 3;
+  std::string sig = "static __device__ double gfship_f (double Rad, double Urelp, double Vrelp, ";
+  if (d3) sig += "double Wrelp, ";
+  sig += "double x, double y, double z, double t";
+  std::string params, values;
+  for (int q = 0; q < nf; q++) {
+    sig += std::string (", double ") + names[q];
+    params += "    const double * f" + std::to_string (q) + ",\n";
+    values += ", f" + std::to_string (q) + "[g]";
+  }
+  sig += ")\n";
+  const std::string maxlevel = std::to_string (GFSHIP_MAXLEVEL);
+  std::string kern =
+    "struct gfship_offsets { int v[" + maxlevel + " + 2]; };\n"
+    "extern \"C\" __global__ void gfship_tree_psource (int n, int depth, gfship_offsets off,\n"
+    "    const unsigned * cell, const double * rad, const double * urel, const double * vrel,\n";
+  if (d3) kern += "    const double * wrel,\n";
+  kern += "    double t,\n" + params + "    double * out)\n"
+    "{\n"
+    "  int o = blockIdx.x*blockDim.x + threadIdx.x;\n"
+    "  if (o >= n) return;\n"
+    "  const unsigned g = cell[o];\n"
+    "  if (g == 0xFFFFFFFFu) return;\n"
+    "  int l = 0, base = off.v[0];\n"
+    "#pragma unroll\n"
+    "  for (int m = 1; m <= " + maxlevel + "; m++)\n"
+    "    if (m <= depth && (int) g >= off.v[m]) { l = m; base = off.v[m]; }\n"
+    "  const unsigned q = g - (unsigned) base, r = (1u << l) + 2u;\n"
+    "  const int i = (int) (q % r), j = (int) ((q/r) % r);\n";
+  kern += d3 ? "  const int k = (int) (q/(r*r));\n" : "  const int k = 0;\n";
+  kern +=
+    "  (void) k;\n"
+    "  const double h = 1./(double) (1u << l);\n"      /* ftt_cell_pos: dyadic, exact */
+    "  out[o] = gfship_f (rad[o], urel[o], vrel[o], ";
+  if (d3) kern += "wrel[o], ";
+  kern += "-0.5 + (i - 0.5)*h, -0.5 + (j - 0.5)*h, ";
+  kern += d3 ? "-0.5 + (k - 0.5)*h" : "0.";
+  kern += ", t" + values + ");\n}\n";
+  return rtc_compile (device, text, sig.c_str (), kern.c_str (), "gfship_tree_psource", out);
+}
+
+int rtc_launch_tree_source (RtcKernel * k, hipStream_t stream, int n, int dim, int depth, const int * off,
+			    const unsigned * cell, const double * rad, const double * const urel[3], double t,
+			    int nf, const double * const * fields, double * out)
+{
+  if (n <= 0) return GFSHIP_OK;
+  TreeSourceOffsets O;
+  for (int l = 0; l < GFSHIP_MAXLEVEL + 2; l++) O.v[l] = off[l];
+  const double * u = urel[0], * v = urel[1], * w = urel[2];
+  std::vector<const double *> f (fields, fields + nf);
+  std::vector<void *> args = { &n, &depth, &O, &cell, &rad, &u, &v };
+  if (dim == 3) args.push_back (&w);
+  args.push_back (&t);
+  for (int q = 0; q < nf; q++) args.push_back (&f[q]);
+  args.push_back (&out);
+  GFSHIP_HIP (hipModuleLaunchKernel (k->fn, (unsigned) ((n + 255)/256), 1, 1, 256, 1, 1, 0, stream, args.data (),
+				     nullptr));
+  return GFSHIP_OK;
+}
+
 int rtc_launch_coefficient (RtcKernel * k, hipStream_t stream, int n, const unsigned char * alive,
 			    const double * rep, const double * const rel[3], const double * pdia,
 			    double t, double * out)

@@ -176,6 +176,9 @@ struct gfship_tree {
   // the variable of a GfsParticulateField and <list>_Fx, _Fy, _Fz of a GfsSourceParticulate (GFSHIP_TREE_VF, _FX ...):
   // allocated zeroed by the first call that needs them (tree_coupling_variable)
   double * cvar[4] = {};
+  // Rad, Urelp, Vrelp, Wrelp and the deposits of GfsSourceParticulateVol / ...Mass (GFSHIP_TREE_RAD ... _DMDT), in the
+  // same way (tree_source_variable)
+  double * svar[6] = {};
   bool src_fields = false;          // gfship_tree_set_source_fields: U, V, W take the velocity source of _FX ...
 };
 
@@ -2745,6 +2748,10 @@ int snapshot_vars (gfship_tree * tr, int nvars, const int * vars, SnapVars * V)
       V->v[v] = tr->cvar[vars[v] - GFSHIP_TREE_VF];
       continue;
     }
+    if (vars[v] >= GFSHIP_TREE_RAD && vars[v] <= GFSHIP_TREE_DMDT && tr->svar[vars[v] - GFSHIP_TREE_RAD]) {
+      V->v[v] = tr->svar[vars[v] - GFSHIP_TREE_RAD];
+      continue;
+    }
     GFSHIP_CHECK (vars[v] >= 0 && vars[v] < abi_nvar, GFSHIP_EINVAL, "gfship_tree_snapshot: variable %d", vars[v]);
     GFSHIP_CHECK (vars[v] < GFSHIP_TREE_T0 || vars[v] > GFSHIP_TREE_T1 || vars[v] - GFSHIP_TREE_T0 < tr->ntracers,
 		  GFSHIP_EINVAL, "gfship_tree_snapshot: the tree has no tracer T%d", vars[v] - GFSHIP_TREE_T0);
@@ -2763,6 +2770,7 @@ void tree_free (gfship_tree * tr)
   for (double * p : tr->var) (void) hipFree (p);
   for (double * p : tr->uprev) (void) hipFree (p);
   for (double * p : tr->cvar) (void) hipFree (p);
+  for (double * p : tr->svar) (void) hipFree (p);
   (void) hipFree (tr->leaves);
   (void) hipFree (tr->ghost_leaves);
   for (int l = 0; l <= GFSHIP_MAXLEVEL; l++) {
@@ -2806,17 +2814,16 @@ double * gfship::tree_variable (gfship_tree * tr, int var)
     return tr->uprev[var - GFSHIP_TREE_UPREV];
   if (var >= GFSHIP_TREE_VF && var <= GFSHIP_TREE_FZ)
     return tr->cvar[var - GFSHIP_TREE_VF];
+  if (var >= GFSHIP_TREE_RAD && var <= GFSHIP_TREE_DMDT)
+    return tr->svar[var - GFSHIP_TREE_RAD];
   return var >= 0 && var < abi_nvar ? tr->var[abi_var[var]] : nullptr;
 }
 
 int gfship::tree_device (gfship_tree * tr) { return tr->device; }
 
-int gfship::tree_coupling_variable (gfship_tree * tr, int var, double ** out)
+// a variable that the first call that needs it allocates zeroed, every level and ghost cells included
+static int lazy_variable (gfship_tree * tr, double *& a, double ** out)
 {
-  GFSHIP_CHECK (var >= GFSHIP_TREE_VF && var <= GFSHIP_TREE_FZ, GFSHIP_EINVAL,
-		"%d is not GFSHIP_TREE_VF, _FX, _FY or _FZ", var);
-  GFSHIP_CHECK (var != GFSHIP_TREE_FZ || tr->H.dim == 3, GFSHIP_EINVAL, "a quadtree has no GFSHIP_TREE_FZ");
-  double *& a = tr->cvar[var - GFSHIP_TREE_VF];
   if (!a) {
     GFSHIP_HIP (hipSetDevice (tr->device));
     GFSHIP_HIP (hipMalloc ((void **) &a, tr->ncell*sizeof (double)));
@@ -2824,6 +2831,29 @@ int gfship::tree_coupling_variable (gfship_tree * tr, int var, double ** out)
   }
   if (out) *out = a;
   return GFSHIP_OK;
+}
+
+int gfship::tree_coupling_variable (gfship_tree * tr, int var, double ** out)
+{
+  GFSHIP_CHECK (var >= GFSHIP_TREE_VF && var <= GFSHIP_TREE_FZ, GFSHIP_EINVAL,
+		"%d is not GFSHIP_TREE_VF, _FX, _FY or _FZ", var);
+  GFSHIP_CHECK (var != GFSHIP_TREE_FZ || tr->H.dim == 3, GFSHIP_EINVAL, "a quadtree has no GFSHIP_TREE_FZ");
+  return lazy_variable (tr, tr->cvar[var - GFSHIP_TREE_VF], out);
+}
+
+int gfship::tree_source_variable (gfship_tree * tr, int var, double ** out)
+{
+  GFSHIP_CHECK (var >= GFSHIP_TREE_RAD && var <= GFSHIP_TREE_DMDT, GFSHIP_EINVAL,
+		"%d is not GFSHIP_TREE_RAD, _URELP, _VRELP, _WRELP, _VOLSRC or _DMDT", var);
+  GFSHIP_CHECK (var != GFSHIP_TREE_WRELP || tr->H.dim == 3, GFSHIP_EINVAL, "a quadtree has no GFSHIP_TREE_WRELP");
+  return lazy_variable (tr, tr->svar[var - GFSHIP_TREE_RAD], out);
+}
+
+bool gfship::tree_has_variable (gfship_tree * tr, int var)
+{
+  if (var >= GFSHIP_TREE_T0 && var <= GFSHIP_TREE_T1 && var - GFSHIP_TREE_T0 >= tr->ntracers)
+    return false;      /* as snapshot_vars: the arrays exist, the tracer does not */
+  return tree_variable (tr, var) != nullptr;
 }
 
 // store_domain_previous_vel, modules/particulatecommon.c:99-113: the copy of U, V, W on the leaves (:108-110), then
@@ -3088,6 +3118,10 @@ int gfship_tree_upload (gfship_tree * tr, int var, int level, const double * in)
   double * a = nullptr;
   if (var >= GFSHIP_TREE_VF && var <= GFSHIP_TREE_FZ) {      /* an upload is a call that needs them */
     int r = tree_coupling_variable (tr, var, &a);
+    if (r) return r;
+  }
+  else if (var >= GFSHIP_TREE_RAD && var <= GFSHIP_TREE_DMDT) {
+    int r = tree_source_variable (tr, var, &a);
     if (r) return r;
   }
   else {

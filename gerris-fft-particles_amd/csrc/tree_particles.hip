@@ -1005,6 +1005,90 @@ tree_field_sum_kernel (Topo T, int n, const unsigned long long * __restrict__ ke
   v[cell] = s;
 }
 
+// ---------------------------------------------------------------------------------------------
+// GfsSourceParticulateVol / GfsSourceParticulateMass on a tree (modules/particulatecommon.c:2734-3047; DESIGN.md
+// 11.32): the passes of particulate_sources.hip with the leaf of a tree as the cell.
+// ---------------------------------------------------------------------------------------------
+
+struct TreeSourceGatherArgs {
+  int n;
+  const double * pos[3];
+  const unsigned char * alive;
+  const unsigned * orig;
+  const double * u[3], * vel[3], * volume;
+  unsigned * cell;
+  double * rad, * urel[3];
+};
+
+// update_vol / update_mass (:2806-2824, :2964-2982) up to the call of the function: gfs_domain_locate (pos, -1), the
+// radius, gfs_interpolate of the velocity and the relative velocity of one particle, stored at its creation slot
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_particulate_source_gather_kernel (TreeSamp S, TreeSourceGatherArgs A)
+{
+  const int q = blockIdx.x*blockDim.x + threadIdx.x;
+  if (q >= A.n) return;
+  const unsigned o = A.orig[q];
+  const double p[3] = { A.pos[0][q], A.pos[1][q], DIM == 3 ? A.pos[2][q] : 0. };
+  Leaf c;
+  if (A.alive[q] != 1 || !tree_locate<DIM> (S, p, c)) {
+    A.cell[o] = PSOURCE_NO_CELL;
+    return;
+  }
+  A.cell[o] = (unsigned) c.g;
+  A.rad[o] = pow (3.0*A.volume[o]/4.0/M_PI, 1./3.);      /* :2812, :2970, the device's pow */
+  Vars<DIM> uu;
+#pragma unroll
+  for (int a = 0; a < DIM; a++) uu.p[a] = A.u[a];
+  double fvel[DIM];
+  tree_interpolate<DIM, DIM> (S, uu, c, p, fvel);
+#pragma unroll
+  for (int a = 0; a < DIM; a++)
+    A.urel[a][o] = fvel[a] - A.vel[a][o];
+}
+
+// gfs_cell_reset with max_depth = 1 (:2844, :3004): the few interior cells of levels 0 and 1 the traversal reaches
+struct TreeSourceResetCells { int n, g[9]; };
+
+__global__ void __launch_bounds__(64)
+tree_particulate_source_reset_kernel (TreeSourceResetCells C, double * __restrict__ a)
+{
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int m = 0; m < 9; m++)
+    if (t == m && m < C.n) a[C.g[m]] = 0.;
+}
+
+struct TreeSourceCellArgs {
+  int n;
+  const unsigned long long * key;
+  unsigned long long ncell;
+  const double * src, * prad, * purel[3];
+  double * deposit, * rad, * urel[3];      // nullptr: not written
+};
+
+// the records of one leaf in list order: deposit += source onto what the leaf HOLDS (:2830, :2989: nothing has reset
+// it below level 1), Rad, Urelp ... of the last one (:2812-2824)
+__global__ void __launch_bounds__(256)
+tree_particulate_source_cell_kernel (TreeSourceCellArgs A)
+{
+  const int r = blockIdx.x*blockDim.x + threadIdx.x;
+  if (r >= A.n) return;
+  const unsigned long long cell = A.key[r] >> 32;
+  if (cell >= A.ncell) return;
+  if (r > 0 && A.key[r - 1] >> 32 == cell) return;      /* not the first of its leaf */
+  double s = A.deposit ? A.deposit[cell] : 0.;
+  int m = r;
+  for (; m < A.n && A.key[m] >> 32 == cell; m++)
+    s += A.src[(unsigned) (A.key[m] & 0xFFFFFFFFull)];
+  const unsigned last = (unsigned) (A.key[m - 1] & 0xFFFFFFFFull);
+  if (A.deposit) A.deposit[cell] = s;
+  if (A.rad) A.rad[cell] = A.prad[last];
+  if (A.urel[0]) A.urel[0][cell] = A.purel[0][last];
+  if (A.urel[1]) A.urel[1][cell] = A.purel[1][last];
+  if (A.urel[2]) A.urel[2][cell] = A.purel[2][last];
+}
+
 struct TreeSpreadArgs {
   int o0, nchunk, stride;
   double rkernel;
@@ -1332,6 +1416,117 @@ int tree_particle_keys (gfship_particles * pl, int * bits)
   int b = 0;
   while (b < 31 && (V.ncell >> b)) b++;
   *bits = b + 1;
+  return GFSHIP_OK;
+}
+
+// source_particulatevol_event (:2834-2852) / source_particulatemass_event (:2993-3012) on a list of a tree.
+// info != nullptr: the milliseconds of the per-particle passes and of the sort with the pass per leaf
+int tree_particulate_source_event (gfship_particulate_source * s, double * info)
+{
+  gfship_particles * pl = s->pl;
+  GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_particulate_source_event");
+  TreeView V;
+  SamplerTables * S;
+  int r = sampler_get (pl->tree, &V, &S);
+  if (r) return r;
+  const int dim = V.H.dim;
+  const bool volume = s->kind == GFSHIP_PARTICULATE_SOURCE_VOLUME;
+  double * D = nullptr, * R = nullptr, * U[3] = { nullptr, nullptr, nullptr };
+  if (s->deposit >= 0 && (r = tree_source_variable (pl->tree, s->deposit, &D))) return r;
+  if (s->rad >= 0 && (r = tree_source_variable (pl->tree, s->rad, &R))) return r;
+  for (int c = 0; c < dim; c++)
+    if (s->urel[c] >= 0 && (r = tree_source_variable (pl->tree, s->urel[c], &U[c]))) return r;
+  std::vector<const double *> read;
+  for (int var : s->read) {
+    const double * a = tree_variable (pl->tree, var);
+    GFSHIP_CHECK (a != nullptr, GFSHIP_EINVAL, "the tree has no variable %d", var);
+    read.push_back (a);
+  }
+  const bool fields = D || R || U[0] || U[1] || U[2];
+  if (D) {
+    /* gfs_domain_cell_traverse (..., FTT_TRAVERSE_ALL | FTT_TRAVERSE_LEAFS, 1, gfs_cell_reset): the interior cells of
+       levels 0 and 1 for a volume, the leaves among them for a mass; every deeper cell keeps what it holds */
+    TreeSourceResetCells C;
+    C.n = 0;
+    for (int l = 0; l <= 1 && l <= V.H.depth; l++)
+      for (int k = 1; k <= (dim == 3 ? V.H.n (l) : 1); k++)
+	for (int j = 1; j <= V.H.n (l); j++)
+	  for (int i = 1; i <= V.H.n (l); i++) {
+	    const Cell c = V.H.make (l, i, j, k);
+	    if (exists (c) && (volume || V.H.leaf (c)))
+	      C.g[C.n++] = V.H.gi (c);
+	  }
+    if (C.n > 0) {
+      hipLaunchKernelGGL (tree_particulate_source_reset_kernel, dim3 (1), dim3 (64), 0, V.stream, C, D);
+      GFSHIP_HIP (hipGetLastError ());
+    }
+  }
+  if (info) info[0] = info[1] = 0.;
+  if (pl->n == 0) return GFSHIP_OK;
+  if ((r = particulate_source_reserve (s))) return r;
+  hipEvent_t ev[3] = { nullptr, nullptr, nullptr };
+  auto mark = [&] (int q) -> hipError_t {
+    if (!info) return hipSuccess;
+    hipError_t e = hipEventCreate (&ev[q]);
+    return e != hipSuccess ? e : hipEventRecord (ev[q], V.stream);
+  };
+  GFSHIP_HIP (mark (0));
+  const int n = pl->n, block = 256, grid = (n + block - 1)/block;
+  const TreeSamp TS = tree_samp (V, S);
+  TreeSourceGatherArgs G;
+  G.n = n;
+  const int uvar[3] = { GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP_TREE_W };
+  for (int c = 0; c < 3; c++) {
+    G.pos[c] = pl->pos[c];
+    G.u[c] = c < dim ? tree_variable (pl->tree, uvar[c]) : nullptr;
+    G.vel[c] = pl->vel[c];
+    G.urel[c] = s->purel[c];
+  }
+  G.alive = pl->alive; G.orig = pl->orig; G.volume = pl->volume;
+  G.cell = s->cell; G.rad = s->prad;
+  if (dim == 3)
+    hipLaunchKernelGGL (tree_particulate_source_gather_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, TS, G);
+  else
+    hipLaunchKernelGGL (tree_particulate_source_gather_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, TS, G);
+  GFSHIP_HIP (hipGetLastError ());
+  if (s->fn) {
+    if ((r = rtc_launch_tree_source (s->fn, V.stream, n, dim, V.H.depth, V.H.off, s->cell, s->prad, s->purel, V.t,
+				     (int) read.size (), read.data (), s->src)))
+      return r;
+  }
+  else if ((r = launch_particulate_source_constant (V.stream, n, s->value, s->src)))
+    return r;
+  const unsigned long long ncell = (unsigned long long) V.ncell;
+  if (fields && (r = coupling_reserve (pl, (size_t) n, 0, false))) return r;
+  if ((r = launch_particulate_source_update (s, V.stream, V.dt, ncell, fields ? pl->ckey : nullptr))) return r;
+  GFSHIP_HIP (mark (1));
+  if (fields) {
+    size_t need = 0;
+    const int bits = coupling_key_bits (ncell);
+    GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (nullptr, need, pl->ckey, pl->ckey2, n, 0, bits, V.stream));
+    if ((r = coupling_sort_reserve (pl, need))) return r;
+    size_t tmp_bytes = pl->sort_tmp_bytes;
+    GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, n, 0, bits, V.stream));
+    TreeSourceCellArgs A;
+    A.n = n; A.key = pl->ckey2; A.ncell = ncell;
+    A.src = s->src; A.prad = s->prad;
+    A.deposit = D; A.rad = R;
+    for (int c = 0; c < 3; c++) {
+      A.purel[c] = s->purel[c];
+      A.urel[c] = c < dim ? U[c] : nullptr;
+    }
+    hipLaunchKernelGGL (tree_particulate_source_cell_kernel, dim3 (grid), dim3 (block), 0, V.stream, A);
+    GFSHIP_HIP (hipGetLastError ());
+  }
+  if (info) {
+    GFSHIP_HIP (mark (2));
+    GFSHIP_HIP (hipStreamSynchronize (V.stream));
+    float a = 0.f, b = 0.f;
+    (void) hipEventElapsedTime (&a, ev[0], ev[1]);
+    (void) hipEventElapsedTime (&b, ev[1], ev[2]);
+    info[0] = a; info[1] = b;
+    for (hipEvent_t e : ev) (void) hipEventDestroy (e);
+  }
   return GFSHIP_OK;
 }
 

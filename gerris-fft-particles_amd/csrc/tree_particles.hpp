@@ -29,5 +29,11 @@ int tree_device (gfship_tree * tr);
 // the device array of GFSHIP_TREE_VF, _FX, _FY, _FZ, allocated zeroed (every level, ghost cells included) by the
 // first call that needs it; GFSHIP_EINVAL for another variable and for _FZ on a quadtree
 int tree_coupling_variable (gfship_tree * tr, int var, double ** out);
+// the same for GFSHIP_TREE_RAD, _URELP, _VRELP, _WRELP, _VOLSRC, _DMDT; GFSHIP_EINVAL for another variable and for
+// _WRELP on a quadtree
+int tree_source_variable (gfship_tree * tr, int var, double ** out);
+// does the tree have the variable `var' now?  tree_variable () != nullptr, and for GFSHIP_TREE_T0, _T1 a tracer of
+// gfship_tree_add_tracer behind it
+bool tree_has_variable (gfship_tree * tr, int var);
 
 }

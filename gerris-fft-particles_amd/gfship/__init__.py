@@ -226,6 +226,9 @@ SIGNATURES = {
     "gfship_tree_source_particulate_event": (_i, [_vp]),
     "gfship_tree_set_source_fields": (_i, [_vp, _i]),
     "gfship_tree_mac_source": (_i, [_vp, _i, _i]),
+    "gfship_tree_particulate_source_create": (_i, [C.POINTER(_vp), _vp, _i, C.c_char_p, _i, C.POINTER(C.c_char_p),
+                                                   C.POINTER(_i)]),
+    "gfship_tree_particulate_source_set_fields": (_i, [_vp, _i, C.POINTER(_i), _i]),
 }
 
 
@@ -966,6 +969,29 @@ class ParticulateSource:
             self.ptr = None
 
 
+class TreeParticulateSource(ParticulateSource):
+    """GfsSourceParticulateVol (kind = SOURCE_VOLUME) or GfsSourceParticulateMass (SOURCE_MASS) on a list of
+    Tree.particulates.  function: as for ParticulateSource; variables: a dict name -> Tree.* number, read at the leaf
+    of the particle.  event, time_event and destroy are those of ParticulateSource.  Destroy it before its list."""
+
+    def __init__(self, tree, plist, kind, function=None, variables=None):
+        variables = dict(variables or {})
+        names = (C.c_char_p * max(len(variables), 1))(*[k.encode() for k in variables])
+        numbers = (_i * max(len(variables), 1))(*[int(v) for v in variables.values()])
+        p = _vp()
+        _check(lib().gfship_tree_particulate_source_create(
+            C.byref(p), plist.ptr, int(kind), None if function is None else str(function).encode(),
+            len(variables), names, numbers))
+        self.ptr, self.plist, self.tree, self.kind = p, plist, tree, int(kind)
+
+    def set_fields(self, rad=None, urel=(), deposit=None):
+        """Tree.RAD, (Tree.URELP, Tree.VRELP[, Tree.WRELP]) and Tree.VOLSRC (a volume source) or Tree.DMDT (a mass
+        source); None: not written"""
+        u = [-1 if v is None else int(v) for v in urel] + [-1] * (3 - len(urel))
+        _check(lib().gfship_tree_particulate_source_set_fields(
+            self.ptr, -1 if rad is None else int(rad), (_i * 3)(*u), -1 if deposit is None else int(deposit)))
+
+
 REFINE_FN = C.CFUNCTYPE(C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p)
 
 
@@ -1002,6 +1028,8 @@ class Tree:
     P, PMAC, U, V, GX, GY, GMACX, GMACY, UN0, UN1, UN2, UN3, W, GZ, GMACZ, UN4, UN5, DIV, BCVAL, RES, T0, T1, BCU, BCV, BCW = range(25)
     UPREV, VPREV, WPREV = 25, 26, 27      # Un, Vn, Wn: once a list of particulates has a force with a coefficient
     VF, FX, FY, FZ = 28, 29, 30, 31       # GfsParticulateField, GfsSourceParticulate: once a call has needed them
+    # Rad, Urelp, Vrelp, Wrelp, volsource, dmdtvariable of GfsSourceParticulateVol / ...Mass: in the same way
+    RAD, URELP, VRELP, WRELP, VOLSRC, DMDT = 32, 33, 34, 35, 36, 37
 
     def __init__(self, refine, dim=2, device=0, sides=None):
         self.dim = dim

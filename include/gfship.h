@@ -831,6 +831,10 @@ enum { GFSHIP_TREE_P = 0, GFSHIP_TREE_PMAC, GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP
        GFSHIP_TREE_UPREV, GFSHIP_TREE_VPREV, GFSHIP_TREE_WPREV };
 /* the numbers go on: the variables of the two-way coupling on a tree (28 .. 31, see gfship_tree_particulate_field) */
 enum { GFSHIP_TREE_VF = GFSHIP_TREE_WPREV + 1, GFSHIP_TREE_FX, GFSHIP_TREE_FY, GFSHIP_TREE_FZ };
+/* ... and on: the variables of GfsSourceParticulateVol / ...Mass on a tree (32 .. 37, see
+   gfship_tree_particulate_source_create) */
+enum { GFSHIP_TREE_RAD = GFSHIP_TREE_FZ + 1, GFSHIP_TREE_URELP, GFSHIP_TREE_VRELP, GFSHIP_TREE_WRELP,
+       GFSHIP_TREE_VOLSRC, GFSHIP_TREE_DMDT };
 				    /* variables of a tree: P, Pmac, U, V, g, gmac, f[d].un; then the 3-D ones;
 				       DIV: the result of gfship_tree_divergence / the right-hand side of
 				       gfship_tree_poisson_solve; BCVAL: the values of the conditions of P, one per
@@ -1052,6 +1056,51 @@ int  gfship_tree_source_particulate_event (gfship_particles * pl);
    GFSHIP_TREE_RES or GFSHIP_TREE_DIV (GFSHIP_EINVAL otherwise). */
 int  gfship_tree_set_source_fields (gfship_tree * tree, int on);
 int  gfship_tree_mac_source (gfship_tree * tree, int c, int var_out);
+
+/* ---- the particles themselves change, on a tree (modules/particulatecommon.c:2734-3047) -------- */
+
+/* GfsSourceParticulateVol and GfsSourceParticulateMass on a refined quadtree / octree, on a list made by
+   gfship_particulates_create_tree (GFSHIP_EUNSUPPORTED on a list of tracers and on a list of a box;
+   gfship_particulate_source_create keeps refusing a list of a tree and gfship_particulate_source_set_fields a
+   handle made here).  The variables of the two classes are GFSHIP_TREE_RAD, _URELP, _VRELP, _WRELP (Rad, Urelp ...,
+   :2785-2793; no _WRELP on a quadtree: GFSHIP_EINVAL), GFSHIP_TREE_VOLSRC (volsource, :2797-2803) and GFSHIP_TREE_DMDT
+   (dmdtvariable, :2954-2960), allocated zeroed -- every level, ghost cells included -- by the first call that needs
+   them, gfship_tree_upload among them; before that gfship_tree_download returns GFSHIP_EINVAL, after it download,
+   gfship_tree_interpolate and the snapshot calls take them like any variable.
+   gfship_tree_particulate_source_create: kind, function and NULL as for gfship_particulate_source_create; the
+   function is compiled for the device of the tree (-ffp-contract=off).  vars[q] is the GFSHIP_TREE_* variable the
+   name names[q] reads at the leaf.  A name that is one of Rad, Urelp, Vrelp, Wrelp, x, y, z, t or no C identifier, and
+   a variable the tree does not have, are GFSHIP_EINVAL; an entry that is _RAD, _URELP, _VRELP, _WRELP, _VOLSRC or
+   _DMDT is GFSHIP_EUNSUPPORTED: it would read what the walk is writing.
+   gfship_tree_particulate_source_set_fields: each argument is its designated variable or -1 (not written): rad =
+   GFSHIP_TREE_RAD, urel[c] = GFSHIP_TREE_URELP + c (urel[2] is -1 on a quadtree), deposit = GFSHIP_TREE_VOLSRC
+   for a volume source and GFSHIP_TREE_DMDT for a mass source; anything else is GFSHIP_EINVAL.  With all five at -1
+   the event sorts nothing.
+   gfship_particulate_source_event, _time_event and _destroy work on such a handle (it knows what made it); the dt
+   is gfship_tree_dt, t is gfship_tree_time.  Per event, on the stream of the tree:
+   the reset of the deposit, which the reference does NOT do on the whole tree: both events pass max_depth = 1 to
+   gfs_domain_cell_traverse (:2844, :3004) and ftt_cell_traverse stops below level 1 (src/ftt.c:696, :745).  For a
+   volume the interior cells of levels 0 and 1 are zeroed (FTT_TRAVERSE_ALL), for a mass the interior LEAVES of levels
+   0 and 1 (FTT_TRAVERSE_LEAFS: none on a tree whose leaves are all deeper).  Every other cell keeps what it held and
+   deposit[cell] += source (:2830, :2989) adds onto it, event after event.  (The box path resets every level / every
+   leaf: a known deviation)
+   Then for every particle in list order (update_vol, :2806-2832; update_mass, :2964-2991): cell = gfs_domain_locate
+   (pos, -1), the leaf whatever its level; Rad[cell] = pow (3.0*volume/4.0/M_PI, 1./3.); Urelp ...[cell] =
+   gfs_interpolate (cell, pos, U ...) - vel with the corner interpolators of gfship_tree_interpolate; source = the
+   function at the cell -- the particle's own Rad and Urelp ..., x, y, z = ftt_cell_pos of the leaf (dyadic, of its
+   level), t, any other name = its variable at the leaf; volume (mass) += source*dt; deposit[cell] += source.  A
+   leaf is left with the value it held plus the sources of its particles added left to right in list order, bit for
+   bit, whatever the storage order (gfship_particles_sort), and with Rad, Urelp ... of its last particle in list
+   order: records keyed (leaf << 32 | list position), leaf = the index of the leaf in the concatenated levels,
+   radix-sorted and added serially per leaf, never with atomics.  Leaves without a particle, cells with children and
+   ghost cells keep what they held (but levels 0 and 1 of a volume's deposit).  A particle without a leaf -- off the
+   list, or outside a GfsBoundary side -- is skipped as on the box (the reference would dereference NULL).  pow: as on
+   the box.  Destroy the source before its list, and the list before its tree. */
+int  gfship_tree_particulate_source_create (gfship_particulate_source ** src, gfship_particles * pl, int kind,
+					    const char * function, int nvars, const char * const * names,
+					    const int * vars);
+int  gfship_tree_particulate_source_set_fields (gfship_particulate_source * src, int rad, const int urel[3],
+						int deposit);
 
 /* ---- instrumentation -------------------------------------------------------------------- */
 

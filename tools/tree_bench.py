@@ -3,6 +3,7 @@
 extra levels inside the central cube / square: leaves, dependency levels of the finest sweep, ms per
 step, Mleaf-steps/s.  Not the benchmarked path (that is bench.py); a measurement to quote.
 usage: tree_bench.py [dim] [level] [box] [steps] [nu] [--snapshot] [--tracers N] [--particulates N] [--two-way N]
+                     [--sources N [--source-function constant|field]]
 nu: GfsSourceDiffusion on every velocity component (default 0: inviscid)
 --snapshot: also time the file image of the tree (gfship_tree_snapshot_write) for P, Pmac, U, V
 (, W): the first call, which builds the offset tables, and the median of 20 more (kernel + copy to the host),
@@ -18,7 +19,13 @@ tree_particulate_list_event_kernel and, after it, the copy of U, V, W into Un, V
 --two-way N: the two-way coupling of a tree for the list of --particulates N, rkernel = 1.5 h of the
 finest leaves, the polynomial kernel: one call to warm up, then the mean of 10 and the least and the largest of them,
 each ended by a stream synchronise, of Tree.particulate_field, Tree.forces_on_fluid, Tree.spread_forces and, last (it
-moves the particles), of the event of the same list: the yardstick of forces_on_fluid."""
+moves the particles), of the event of the same list: the yardstick of forces_on_fluid.
+--sources N: GfsSourceParticulateVol on a tree for a list of N GfsParticulate with GfsForceDrag, the
+storage sorted by leaf, Rad, Urelp ... and the deposit written: a volume source with a constant function and one with
+compiled text that reads one variable (--source-function picks one of the two).  Medians of 10 calls after two
+uncounted ones, with the least and the largest: the whole event (each call ended by a stream synchronise), the
+passes per particle and the sort with the pass per leaf (gfship_particulate_source_time_event: device time between
+events on the stream), and last (it moves the particles) the event of the same list."""
 import os
 import sys
 import time
@@ -45,6 +52,16 @@ ntwoway = 0
 if "--two-way" in sys.argv:
     k = sys.argv.index("--two-way")
     ntwoway = int(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
+nsources, source_function = 0, "both"
+if "--source-function" in sys.argv:
+    k = sys.argv.index("--source-function")
+    source_function = sys.argv[k + 1]
+    assert source_function in ("constant", "field", "both")
+    del sys.argv[k:k + 2]
+if "--sources" in sys.argv:
+    k = sys.argv.index("--sources")
+    nsources = int(sys.argv[k + 1])
     del sys.argv[k:k + 2]
 dim = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 level = int(sys.argv[2]) if len(sys.argv) > 2 else 4
@@ -181,10 +198,56 @@ if ntwoway:
         two[name] = mean_ms(call)
     two["leaves_with_a_deposit"] = int(sum(np.count_nonzero(g.download(g.FX, l)) for l in range(g.depth + 1)))
     pl.destroy()
+srcs = {}
+if nsources:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from particle_cases import lcg_positions_fast
+    pos, ids = lcg_positions_fast(nsources)
+    if dim == 2:
+        pos[:, 2] = 0.
+    rng = np.random.default_rng(1)
+    vol = 1e-6 * (0.5 + rng.random(nsources))
+    pl = g.particulates(pos, ids, np.zeros((nsources, 3)), 2. * vol, vol)
+    pl.set_forces([gfship.FORCE_DRAG], (0., 0., 0.))
+    pl.sort()
+    w = " + Wrelp*Wrelp" if dim == 3 else ""
+    # rates small enough that no volume changes sign over the calls of this run; P stands for any variable of the tree
+    texts = {"constant": ("1e-9", None), "field": ("1e-9*T*(Urelp*Urelp + Vrelp*Vrelp%s)" % w, {"T": g.P})}
+    urel = [g.URELP, g.VRELP, g.WRELP][:dim]
+
+    def stats(t):
+        return {"median": round(float(np.median(t)), 3), "min": round(min(t), 3), "max": round(max(t), 3)}
+
+    def median_ms(call):
+        for _ in range(2):
+            call()
+        pl.count()
+        t = []
+        for _ in range(10):
+            t0 = time.perf_counter()
+            call()
+            pl.count()
+            t.append((time.perf_counter() - t0) * 1e3)
+        return stats(t)
+
+    srcs = {"sources_particulates": nsources}
+    for name in ("constant", "field"):
+        if source_function not in (name, "both"):
+            continue
+        src = gfship.TreeParticulateSource(g, pl, gfship.SOURCE_VOLUME, texts[name][0], texts[name][1])
+        src.set_fields(g.RAD, urel, g.VOLSRC)
+        srcs["vol_%s_ms" % name] = median_ms(src.event)
+        runs = [src.time_event() for _ in range(10)]
+        srcs["vol_%s_per_particle_ms" % name] = stats([r[0] for r in runs])
+        srcs["vol_%s_leaves_ms" % name] = stats([r[1] for r in runs])
+        src.destroy()
+    srcs["leaves_with_a_deposit"] = int(sum(np.count_nonzero(g.download(g.VOLSRC, l)) for l in range(g.depth + 1)))
+    srcs["sources_event_ms"] = median_ms(pl.event)
+    pl.destroy()
 print({"dim": dim, "levels": [level, g.depth], "leaves": nleaves, "finest_sweep_cells": nc,
        "finest_sweep_dependency_levels": nl, "tree_build_s": round(t_build, 2),
        "ms_per_step": round(ms, 2), "Mleaf_steps_per_s": round(nleaves / ms / 1e3, 3),
        "niter": [g.projection_params.niter, g.approx_projection_params.niter],
-       **snap, **trac, **part, **two,
+       **snap, **trac, **part, **two, **srcs,
        **({"nu": nu, "diffusion_niter": [g.diffusion_params(c).niter for c in range(dim)]} if nu != 0. else {})})
 g.destroy()
