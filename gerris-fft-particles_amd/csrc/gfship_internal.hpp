@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
 #include <cstdarg>
 #include <cstring>
@@ -169,6 +170,10 @@ struct gfship_domain {
   // the relax loop being launched decides whether its level may run on the 2 x 2 ring kernels (which
   // know no per-cell weights): -1 outside such a call (the Poisson path: by `weighted'), else 0 / 1
   int patch_call = -1;
+  // the level whose residual the solve has already restricted onto the level below and copied into the layout of
+  // its relax loop, together with computing it (launch_residual_restrict_pack): the next cycle skips that
+  // restriction; -1 none
+  int restricted_level = -1;
 };
 
 namespace gfship {
@@ -303,6 +308,21 @@ int launch_residual_norm (gfship_domain * dom, int level, const double * u, cons
 			  double * out /* 5 values, or nullptr: left in h_pinned[8..12], not waited for */, bool dia_zero = false,
 			  bool * store = nullptr /* in: false asks for the norm alone; out: whether res was stored */);
 int launch_norm_async (gfship_domain * dom, int level, const double * a, double scale, double weight);
+// the end of a residual norm whose nblocks partial records another launch has left in d_scratch: the result lands
+// in h_pinned[8..12], not waited for; reports RN_BLOCKS_LIMIT / RN_BLOCKS_MAX as launch_residual_norm does
+int launch_residual_norm_final (gfship_domain * dom, int nblocks);
+// most workgroups of a residual norm (GFSHIP_RN_BLOCKS; d_scratch holds 5*8192 partials)
+inline int rn_blocks_limit (const gfship_domain * dom)
+{
+  const int rn_blocks = dom->sw.rn_blocks;
+  return rn_blocks < 64 || rn_blocks > 8192 ? 4096 : rn_blocks;
+}
+// 1/x is exact and x*(1/x) == 1: the h*h of the residual norms
+inline bool power_of_two (double x)
+{
+  int e;
+  return x > 0. && frexp (x, &e) == 0.5;
+}
 
 // poisson.hip: gfship_poisson_solve for a caller whose res is a temporary that nobody reads after the
 // solve (res_unread): the residual after the cycle expected to be the last is then not stored
@@ -421,6 +441,15 @@ int  patch_restrict_pack (gfship_domain * dom, int level, SkewPlan * S, const do
 // the skewed layout of the relax loop of `level' (and of level - 1 where that is a 2 x 2 level too)
 int  launch_restrict_pack (gfship_domain * dom, unsigned dimension, int level, Field * res,
 			   bool coarse_fused);
+// the same for the first residual of a solve, computed from u and rhs (dia is zero on the level) by the same pass,
+// with the partial sums of its norm (*nblocks records in d_scratch); the natural residual of `level' is not written
+int  patch_residual_restrict_pack (gfship_domain * dom, int level, SkewPlan * S, const double * u,
+				   const double * rhs, double * res_coarse, SkewPlan * Sc, unsigned dimension,
+				   double scale, double weight, int * nblocks);
+// launch_restrict_pack with that kernel, and the end of the norm (in h_pinned[8..12] once the stream gets there,
+// launch_norm_async's convention); sets dom->restricted_level
+int  launch_residual_restrict_pack (gfship_domain * dom, unsigned dimension, int level, const double * u,
+				    const double * rhs, Field * res, bool coarse_fused, double scale, double weight);
 void skew_dump_stats (gfship_domain * dom, int level);
 int  skew_time_sweeps (gfship_domain * dom, int level, Field * u, const double * rhs,
 		       const double * dia, bool dia_zero, int reps, double * ms_per_sweep);

@@ -354,6 +354,58 @@ int gfship_norm_variable (gfship_domain * dom, gfship_field v, gfship_norm * out
 
 } // extern "C"
 
+// What a V-cycle with these parameters runs where: poisson_cycle follows it, and poisson_solve reads from it
+// whether the cycle would start by restricting the leaf residual with launch_restrict_pack -- its first residual
+// is then restricted and copied by the pass that computes it (launch_residual_restrict_pack)
+struct CyclePlan {
+  unsigned minlevel;                    /* MAX (domain->rootlevel, p->minlevel), rootlevel = 0 */
+  unsigned nrl[GFSHIP_MAXLEVEL + 1];    /* relaxations per level (nrelax at the leaves, times erelax per level above) */
+  int ctop, ltop;                       /* top of the coarse end that runs in one launch (coarse / lattice kernel), or -1 */
+  int lowest;                           /* the coarsest level the cycle restricts onto level by level */
+};
+
+static CyclePlan cycle_plan (gfship_domain * dom, const gfship_multilevel_params * p, Field * D)
+{
+  CyclePlan C;
+  const int L = dom->depth;
+  C.minlevel = p->minlevel;
+  if (C.minlevel > (unsigned) L) C.minlevel = L;
+  unsigned nr = p->nrelax;
+  for (int l = L; l >= 0; l--) {
+    C.nrl[l] = nr;
+    if (l > (int) C.minlevel) nr *= p->erelax;
+  }
+  /* the coarse end of the cycle (restrictions, relax loops and prolongations of the levels that
+     fit in LDS together) in one launch where that applies */
+  C.ctop = dom->weighted ? -1 : coarse_cycle_top (dom, (int) C.minlevel);
+  /* ... or, on a box of a lattice of boxes, computed for all boxes on every rank after one
+     all-gather instead of one halo exchange per sweep and level (lattice_cycle_kernel) */
+  C.ltop = C.ctop >= 0 ? -1 : lattice_cycle_top (dom, (int) C.minlevel, D);
+  C.lowest = C.ctop >= 0 ? C.ctop + 1 : C.ltop >= 0 ? C.ltop : 0;
+  return C;
+}
+
+// where level `fine' runs its relax loop on the 2 x 2 kernels its residual is copied into their layout by the pass
+// that restricts it onto fine - 1 (unless the restriction onto `fine' has left it there already: rs_ready) ...
+static bool cycle_restrict_packs (gfship_domain * dom, unsigned dimension, const CyclePlan & C, int fine)
+{
+  return fine - 1 >= C.lowest && prolongation_fused (dom, dimension, fine, C.nrl[fine]);
+}
+
+// ... and so is the restricted one, where level fine - 1 does
+static bool cycle_restrict_packs_coarse (gfship_domain * dom, unsigned dimension, const CyclePlan & C, int fine)
+{
+  return fine - 1 > (int) C.minlevel && prolongation_fused (dom, dimension, fine - 1, C.nrl[fine - 1]);
+}
+
+// what a cycle leaves behind it of the state that lasts from its restrictions to its relax loops
+static void cycle_state_reset (gfship_domain * dom)
+{
+  for (int l = 0; l <= dom->depth; l++)
+    dom->skew[l].rs_ready = false;
+  dom->restricted_level = -1;
+}
+
 // gfs_poisson_cycle; with norm != nullptr the norm of the new residual (scaled by dt) comes out of
 // the same pass that computes it (the solve loop asks for it right after the cycle); store_res: in,
 // false asks for that norm alone where the kernel can leave the store out; out, whether res holds
@@ -379,45 +431,35 @@ static int poisson_cycle (gfship_domain * dom, gfship_multilevel_params * p,
   bool corrected = false;      /* u += dp already done while the finest level was unpacked */
   if (!U || !R || !D || !S) return GFSHIP_EINVAL;
   const int L = dom->depth;
-  unsigned minlevel = p->minlevel; /* MAX (domain->rootlevel, p->minlevel), rootlevel = 0 */
-  if (minlevel > (unsigned) L) minlevel = L;
   p->depth = L;
 
 #define TRY(x) do { if ((r = (x)) != GFSHIP_OK) goto done; } while (0)
   for (int l = 0; l <= L; l++)
     S->zero[l] = U->zero[l] = false;
   {
-    /* relaxations per level (nrelax at the leaves, times erelax per level above) */
-    unsigned nrl[GFSHIP_MAXLEVEL + 1];
-    {
-      unsigned nr = p->nrelax;
-      for (int l = L; l >= 0; l--) {
-	nrl[l] = nr;
-	if (l > (int) minlevel) nr *= p->erelax;
-      }
-    }
+    const CyclePlan C = cycle_plan (dom, p, D);
+    const unsigned minlevel = C.minlevel;
+    const unsigned * const nrl = C.nrl;
+    const int ctop = C.ctop, ltop = C.ltop;
     for (int l = 0; l <= L; l++)
       DP->zero[l] = false;
-    /* the coarse end of the cycle (restrictions, relax loops and prolongations of the levels that
-       fit in LDS together) in one launch where that applies */
-    const int ctop = dom->weighted ? -1 : coarse_cycle_top (dom, (int) minlevel);
-    /* ... or, on a box of a lattice of boxes, computed for all boxes on every rank after one
-       all-gather instead of one halo exchange per sweep and level (lattice_cycle_kernel) */
-    const int ltop = ctop >= 0 ? -1 : lattice_cycle_top (dom, (int) minlevel, D);
     /* compute residual on non-leafs cells (get_from_below, post-order: finest parents first) */
-    for (int l = L - 1; l >= (ctop >= 0 ? ctop + 1 : ltop >= 0 ? ltop : 0); l--) {
+    for (int l = L - 1; l >= C.lowest; l--) {
       /* the hand-off granules of the relax loop of level l + 1, which comes on the way up, are armed
 	 from here on the side stream, beside the loops of the levels below */
       if (dom->relax_mode == GFSHIP_RELAX_EXACT && p->dimension == 3 && !dom->weighted &&
 	  !dom->force_hyperplane && skew_supported (dom, l + 1))
 	TRY (skew_arm_ahead (dom, l + 1, nrl[l + 1]));
+      /* the solve has restricted its first residual together with computing it */
+      if (dom->restricted_level == l + 1)
+	continue;
       /* where level l + 1 runs its relax loop on the 2 x 2 kernels the residual is copied into their
 	 layout by the same pass that restricts it (and so is the restricted one, where level l does) */
-      const bool rp = !dom->skew[l + 1].rs_ready && prolongation_fused (dom, p->dimension, l + 1, nrl[l + 1]);
+      const bool rp = !dom->skew[l + 1].rs_ready && cycle_restrict_packs (dom, p->dimension, C, l + 1);
       if (rp) dom->kc[dom->sw.fused_restriction ? GFSHIP_KC_RESTRICTION_FUSED : GFSHIP_KC_RESTRICTION_DECLINED]++;
       if (dom->sw.fused_restriction && rp)
 	TRY (launch_restrict_pack (dom, p->dimension, l + 1, S,
-				   l > (int) minlevel && prolongation_fused (dom, p->dimension, l, nrl[l])));
+				   cycle_restrict_packs_coarse (dom, p->dimension, C, l + 1)));
       else
 	TRY (launch_restrict (dom, p->dimension, l, S->lev[l], S->lev[l + 1]));
     }
@@ -469,8 +511,7 @@ static int poisson_cycle (gfship_domain * dom, gfship_multilevel_params * p,
     TRY (launch_residual (dom, L, U->lev[L], R->lev[L], D->lev[L], S->lev[L]));
 #undef TRY
  done:
-  for (int l = 0; l <= L; l++)
-    dom->skew[l].rs_ready = false;
+  cycle_state_reset (dom);
   return r;
 }
 
@@ -536,6 +577,24 @@ int poisson_solve (gfship_domain * dom, gfship_multilevel_params * par,
       if ((r = launch_residual_weighted (dom, L, U->lev[L], R->lev[L], D->lev[L], S->lev[L]))) return r;
       if ((r = launch_norm_async (dom, L, S->lev[L], 1.*size*size, 1.))) return r;
     }
+    /* the first cycle starts by restricting this residual and copying it into the layout of the leaves' relax
+       loop; where nobody else reads it, that is done by the pass that computes it, and the residual itself
+       is not stored (the 2 x 2 levels of 3-D boxes, the pair arithmetic, dia known to be zero: a dia that is
+       not is left to the two launches) */
+    else if (res_unread && par->dimension == 3 && dom->sw.residual_pairs && dom->sw.fused_restriction &&
+	     power_of_two (1.*size*size) && Ly.n >= 64 && D->zero[L] && par->nrelax > 0 && par->erelax > 0 &&
+	     par->minlevel < (unsigned) L) {
+      const CyclePlan C = cycle_plan (dom, par, D);
+      if (cycle_restrict_packs (dom, par->dimension, C, L)) {
+	dom->kc[GFSHIP_KC_RESTRICTION_FUSED]++;
+	r = launch_residual_restrict_pack (dom, par->dimension, L, U->lev[L], R->lev[L], S,
+					   cycle_restrict_packs_coarse (dom, par->dimension, C, L), 1.*size*size, 1.);
+      }
+      else
+	r = launch_residual_norm (dom, L, U->lev[L], R->lev[L], D->lev[L], S->lev[L], 1.*size*size, 1., nullptr,
+				  D->zero[L]);
+      if (r) { cycle_state_reset (dom); return r; }
+    }
     else if ((r = launch_residual_norm (dom, L, U->lev[L], R->lev[L], D->lev[L], S->lev[L], 1.*size*size,
 					1., nullptr, D->zero[L])))
       return r;
@@ -556,6 +615,7 @@ int poisson_solve (gfship_domain * dom, gfship_multilevel_params * par,
     }
     bool store = !(predicted > 0 && par->niter + 1 == predicted);
     r = poisson_cycle (dom, par, lhs, rhs, dia, res, dt, &par->residual, &store);
+    cycle_state_reset (dom);      /* a cycle that was refused before it began has left it */
     res_stored = store;
     if (r) {
       if (deferred) {

@@ -1744,12 +1744,7 @@ norm_final_kernel (const double * __restrict__ partial, int nblocks, double * __
   }
 }
 
-// 1/scale is exact when scale is a power of two (the h*h of the residual norms, 1. elsewhere)
-static bool power_of_two (double x)
-{
-  int e;
-  return x > 0. && frexp (x, &e) == 0.5;
-}
+// 1/scale is exact when scale is a power of two (the h*h of the residual norms, 1. elsewhere): power_of_two
 #define NORM_PARTIAL_LAUNCH() do {					\
     if (power_of_two (scale))						\
       hipLaunchKernelGGL (norm_partial_kernel<true>, dim3 (nblocks), dim3 (block), 0, dom->stream, \
@@ -1937,8 +1932,7 @@ int launch_residual_norm (gfship_domain * dom, int level, const double * u, cons
   int block = L.n >= 256 ? 256 : L.n >= 128 ? 128 : 64;
   /* d_scratch holds 5*8192 partials; GFSHIP_RN_BLOCKS: tuning knob (4096 = 16 workgroups per CU:
      the 7-point reads of a row keep more rows in flight than the norm alone needs) */
-  int rn_blocks = dom->sw.rn_blocks;
-  if (rn_blocks < 64 || rn_blocks > 8192) rn_blocks = 4096;
+  const int rn_blocks = rn_blocks_limit (dom);
   int nblocks = (int) (nrows > rn_blocks ? rn_blocks : nrows);
   double * partial = dom->d_scratch;
   double * result = out ? dom->h_pinned : dom->h_pinned + 8;
@@ -1968,6 +1962,17 @@ int launch_residual_norm (gfship_domain * dom, int level, const double * u, cons
     GFSHIP_HIP (stream_wait_spin (dom->stream));
     memcpy (out, dom->h_pinned, 5*sizeof (double));
   }
+  return GFSHIP_OK;
+}
+
+int launch_residual_norm_final (gfship_domain * dom, int nblocks)
+{
+  hipLaunchKernelGGL (norm_final_kernel, dim3 (1), dim3 (256), 0, dom->stream,
+		      dom->d_scratch, nblocks, dom->h_pinned + 8);
+  GFSHIP_HIP (hipGetLastError ());
+  dom->kc[GFSHIP_KC_RN_BLOCKS_LIMIT] = rn_blocks_limit (dom);
+  if ((unsigned long long) nblocks > dom->kc[GFSHIP_KC_RN_BLOCKS_MAX])
+    dom->kc[GFSHIP_KC_RN_BLOCKS_MAX] = nblocks;
   return GFSHIP_OK;
 }
 

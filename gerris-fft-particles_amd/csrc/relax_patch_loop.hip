@@ -29,6 +29,8 @@
 //     hand-off granule of cell I of line (15, m) / (m, 15): row I + (m >> 1)       (consumer's step)
 //     snapshot granule of cell I of line (0, m) / (m, 0):   row I + (m >> 1) + 7
 #include "relax_skew.hpp"
+#include "cell_loop.hpp"
+#include "residual_pack_map.hpp"
 #include <cstdlib>
 #include <vector>
 
@@ -1277,6 +1279,134 @@ patch_restrict_pack_kernel (PatchRestrictArgs A)
   }
 }
 
+// The first residual of a solve whose natural copy nobody reads (poisson_solve, res_unread): what
+// residual_norm2_kernel computes of a cell goes straight into the buffer that patch_restrict_pack_kernel fills
+// from the natural residual, and from there where that kernel puts it -- the skewed rhs of the level, the
+// natural and the skewed residual of the coarse level.  The natural residual of the level is not written.
+//
+// A task is what a workgroup of patch_restrict_pack_kernel does: (tile, PB, block of PPR_ROWS skewed rows);
+// which cells it computes and which it owns is residual_pack_map.hpp.  The cells are computed as the aligned
+// pairs of the pair kernel, with its loads (16 bytes but for the two cells beside the pair), its expressions and
+// its operand order: per cell the bits of residual_norm2_kernel.  u is read through L1/L2, not staged.
+struct ResidualRestrictArgs {
+  PatchRestrictArgs R;     // src is not used
+  const double * u, * rhs; // natural arrays of the fine level; the BC has been applied to u
+  double inv, weight;      // the norm: 1/scale and the weight of a cell
+  double * partial;        // five sums per workgroup (NORM)
+  int nrb;                 // blocks of PPR_ROWS rows of a tile
+  int ntasks;
+};
+
+#define RRP_PAIRS (PPR_ROWS/2 + 1)   /* pairs of a line of a task */
+#define RRP_W (PPR_SPAN + 1)         /* cells of a line in the buffer */
+
+template <bool NORM>
+__global__ void __launch_bounds__(256)
+residual_restrict_pack_kernel (ResidualRestrictArgs B)
+{
+  __shared__ __attribute__((aligned(16))) double buf[32][RRP_W];
+  const PatchRestrictArgs & A = B.R;
+  const int tid = threadIdx.x;
+  const int n = A.L.n, ntiles = A.ntj*A.ntj;
+  double s0 = 0., s1 = 0., s2 = 0., s3 = 0., s4 = 0.;
+  for (int t = blockIdx.x; t < B.ntasks; t += gridDim.x) {
+    const ResidualRestrictTask T = residual_restrict_task (t, B.nrb);
+    if (T.tile < ntiles) {       /* the same for every thread of the workgroup */
+      const int tile = T.tile, PB = T.PB, r0 = T.rb*PPR_ROWS;
+      const int P = tile % A.ntj, Q = tile / A.ntj;
+      const long tbase = (long) tile*(A.RT + 2*SK_FP)*SK_NL + SK_FP*SK_NL;
+      const int I0 = residual_restrict_origin (r0, PB);
+      for (int e = tid; e < 32*RRP_PAIRS; e += 256) {
+	const ResidualRestrictPair pr = residual_restrict_pair<PPR_ROWS> (e, r0, PB);
+	if (residual_restrict_pair_needed<PPR_ROWS> (pr, n)) {
+	  const int I = pr.I;
+	  const int j = n - (SK_T*P + pr.a), k = n - (SK_T*Q + 2*PB + pr.db);
+	  const double * __restrict__ u = B.u;
+	  const long c = A.L.idx (I + 1, j, k);           /* even index: 16-byte aligned */
+	  const d2 uc = *(const d2 *) (u + c);
+	  const double ul = u[c - 1], ur = u[c + 2];
+	  const d2 ut = *(const d2 *) (u + c + A.L.sy), ub = *(const d2 *) (u + c - A.L.sy);
+	  const d2 uf = *(const d2 *) (u + c + A.L.sz), uk = *(const d2 *) (u + c - A.L.sz);
+	  const d2 rh = *(const d2 *) (B.rhs + c);
+	  d2 out;
+	  // the two cells as residual_norm2_kernel writes them, dia = 0
+	  {
+	    double sa = 0., sb = 0.;
+	    sa += 1.; sb += 1.*uc.y;
+	    sa += 1.; sb += 1.*ul;
+	    sa += 1.; sb += 1.*ut.x;
+	    sa += 1.; sb += 1.*ub.x;
+	    sa += 1.; sb += 1.*uf.x;
+	    sa += 1.; sb += 1.*uk.x;
+	    out.x = rh.x - (sb - uc.x*sa);
+	  }
+	  {
+	    double sa = 0., sb = 0.;
+	    sa += 1.; sb += 1.*ur;
+	    sa += 1.; sb += 1.*uc.x;
+	    sa += 1.; sb += 1.*ut.y;
+	    sa += 1.; sb += 1.*ub.y;
+	    sa += 1.; sb += 1.*uf.y;
+	    sa += 1.; sb += 1.*uk.y;
+	    out.y = rh.y - (sb - uc.y*sa);
+	  }
+	  *(d2 *) &buf[pr.line][I - I0] = out;
+	  if (NORM)
+	    // a cell counts in the task that owns its skewed row
+#pragma unroll
+	    for (int q = 0; q < 2; q++)
+	      if (residual_restrict_owns<PPR_ROWS> (pr, q)) {
+		const double raw = q ? out.y : out.x;
+		double val = raw*B.inv;
+		s0 += B.weight*val;
+		val = fabs (val);
+		s3 = fmax (s3, val);
+		s1 += B.weight*val;
+		s2 += B.weight*val*val;
+		s4 += raw;
+	      }
+	}
+      }
+      __syncthreads ();
+      // from here on patch_restrict_pack_kernel, the buffer indexed from I0
+      for (int e = tid; e < PPR_ROWS*32; e += 256) {
+	const int row = e / 32, col = e % 32;
+	const int PA = col >> 2, p = col & 3;
+	const int a = 2*PA + (p & 1), db = p >> 1;
+	const int rho = r0 + row;
+	const int I = rho - PA - PB;
+	if (I >= 0 && I < n)
+	  A.dst[tbase + (long) rho*SK_NL + 128*(p >> 1) + 2*(PA + 8*PB) + (p & 1)] = buf[a + 16*db][I - I0];
+      }
+      for (int e = tid; e < 8*(PPR_ROWS/2); e += 256) {
+	const ResidualRestrictCoarse cc = residual_restrict_coarse<PPR_ROWS> (e, r0, PB);
+	const int PA = cc.PA, I = cc.I;
+	if (I >= 0 && I < n) {
+	  const int di = I - I0;
+	  double val = 0.;
+	  // children in child-id order: bit 0 -> +x, bit 1 -> -y (da = 1), bit 2 -> -z (db = 1)
+#pragma unroll
+	  for (int id = 0; id < 8; id++)
+	    val += buf[2*PA + ((id >> 1) & 1) + 16*(id >> 2)][di + (id & 1)];
+	  const double v = A.dimension == 2 ? val : val/2.;
+	  const int m = I >> 1;
+	  const int pj = (n - SK_T*P - 2*PA) >> 1, pk = (n - SK_T*Q - 2*PB) >> 1;
+	  A.cnat[A.Lc.idx (m + 1, pj, pk)] = v;
+	  if (A.cskew) {
+	    const int ca = 8*(P & 1) + PA, cb = 8*(Q & 1) + PB;
+	    const long ctile = (P >> 1) + (long) A.cntj*(Q >> 1);
+	    A.cskew[ctile*(A.cRT + 2*SK_FP)*SK_NL + SK_FP*SK_NL +
+		    (long) (m + (ca >> 1) + (cb >> 1))*SK_NL + 128*(cb & 1) + 2*((ca >> 1) + 8*(cb >> 1)) + (ca & 1)] = v;
+	  }
+	}
+      }
+    }
+    __syncthreads ();       /* the buffer is filled again */
+  }
+  if (NORM)
+    block_norm_sums (s0, s1, s2, s3, s4, B.partial, blockIdx.x);
+}
+
 // G: the ghost planes the loop has left to this launch, taken by the blocks behind those of the tiles
 __global__ void __launch_bounds__(256)
 patch_unpack_kernel (PatchPackArgs A, LoopGhosts G)
@@ -1393,6 +1523,33 @@ int patch_restrict_pack (gfship_domain * dom, int level, SkewPlan * S, const dou
   const int rows = A.L.n + PK_SKEW + 1;
   dim3 grid ((rows + PPR_ROWS - 1)/PPR_ROWS, 8, S->ntj*S->ntj);
   hipLaunchKernelGGL (patch_restrict_pack_kernel, grid, dim3 (256), 0, dom->stream, A);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
+int patch_residual_restrict_pack (gfship_domain * dom, int level, SkewPlan * S, const double * u,
+				  const double * rhs, double * res_coarse, SkewPlan * Sc, unsigned dimension,
+				  double scale, double weight, int * nblocks)
+{
+  ResidualRestrictArgs B;
+  PatchRestrictArgs & A = B.R;
+  A.L = dom->lay[level]; A.Lc = dom->lay[level - 1];
+  A.ntj = S->ntj; A.RT = S->RT;
+  A.src = nullptr; A.dst = S->rs;
+  A.cnat = res_coarse;
+  A.cskew = Sc ? Sc->rs : nullptr;
+  A.cntj = Sc ? Sc->ntj : 0; A.cRT = Sc ? Sc->RT : 0;
+  A.dimension = dimension;
+  B.u = u; B.rhs = rhs;
+  B.inv = 1./scale; B.weight = weight;
+  B.partial = dom->d_scratch;
+  const int rows = A.L.n + PK_SKEW + 1;
+  B.nrb = (rows + PPR_ROWS - 1)/PPR_ROWS;
+  B.ntasks = residual_restrict_ntasks (B.nrb, S->ntj*S->ntj);
+  /* one partial record per workgroup: d_scratch holds 5*8192 of them */
+  const int limit = rn_blocks_limit (dom);
+  *nblocks = B.ntasks > limit ? limit : B.ntasks;
+  hipLaunchKernelGGL (residual_restrict_pack_kernel<true>, dim3 (*nblocks), dim3 (256), 0, dom->stream, B);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }

@@ -685,21 +685,46 @@ int launch_relax_loop_skew (gfship_domain * dom, int level, Field * dp, Field * 
   return skew_unpack (dom, level, S, u, correct_into);
 }
 
+// the plans of `level' (and of level - 1 where its skewed rhs is filled too), ready to have their skewed rhs written
+static int restrict_pack_plans (gfship_domain * dom, int level, bool coarse_fused, SkewPlan ** S, SkewPlan ** Sc)
+{
+  int r;
+  *Sc = nullptr;
+  if ((r = skew_plan (dom, level, S))) return r;
+  /* the trial run of the fused loop overwrites the skewed arrays: before they are filled */
+  if ((r = skew_loop_trial (dom, level, *S, 4, true))) return r;
+  if (coarse_fused) {
+    if ((r = skew_plan (dom, level - 1, Sc))) return r;
+    if ((r = skew_loop_trial (dom, level - 1, *Sc, 4, true))) return r;
+  }
+  return GFSHIP_OK;
+}
+
 int launch_restrict_pack (gfship_domain * dom, unsigned dimension, int level, Field * res, bool coarse_fused)
 {
-  SkewPlan * S, * Sc = nullptr;
+  SkewPlan * S, * Sc;
   int r;
-  if ((r = skew_plan (dom, level, &S))) return r;
-  /* the trial run of the fused loop overwrites the skewed arrays: before they are filled */
-  if ((r = skew_loop_trial (dom, level, S, 4, true))) return r;
-  if (coarse_fused) {
-    if ((r = skew_plan (dom, level - 1, &Sc))) return r;
-    if ((r = skew_loop_trial (dom, level - 1, Sc, 4, true))) return r;
-  }
+  if ((r = restrict_pack_plans (dom, level, coarse_fused, &S, &Sc))) return r;
   res->zero[level - 1] = false;
   if ((r = patch_restrict_pack (dom, level, S, res->lev[level], res->lev[level - 1], Sc, dimension))) return r;
   S->rs_ready = true;
   if (Sc) Sc->rs_ready = true;
+  return GFSHIP_OK;
+}
+
+int launch_residual_restrict_pack (gfship_domain * dom, unsigned dimension, int level, const double * u,
+				   const double * rhs, Field * res, bool coarse_fused, double scale, double weight)
+{
+  SkewPlan * S, * Sc;
+  int r, nblocks = 0;
+  if ((r = restrict_pack_plans (dom, level, coarse_fused, &S, &Sc))) return r;
+  res->zero[level - 1] = false;
+  if ((r = patch_residual_restrict_pack (dom, level, S, u, rhs, res->lev[level - 1], Sc, dimension,
+					 scale, weight, &nblocks))) return r;
+  if ((r = launch_residual_norm_final (dom, nblocks))) return r;
+  S->rs_ready = true;
+  if (Sc) Sc->rs_ready = true;
+  dom->restricted_level = level;
   return GFSHIP_OK;
 }
 
