@@ -24,7 +24,10 @@
 //   A particle owns `stride' record slots -- an upper bound of the leaves cond_kernel can pass, see
 //   kernel_stride -- and a chunk holds at most RECORD_CAP slots: the work arrays take 56 bytes per
 //   slot, 224 MiB at the most, whatever the number of particles.
+// The sums of steps 3 and 4 and of the void fraction are the kernels of cell_sums.hpp on BoxCells; the lists of a
+// tree (tree_particles.hip) launch the same kernels on TreeCells.
 #include "particles.hpp"
+#include "cell_sums.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <cmath>
@@ -108,6 +111,7 @@ where_kernel (int n, const unsigned * __restrict__ orig, unsigned * __restrict__
 
 // key of the cell that holds each particle, (cell << 32 | creation slot); pad (cell = number of cells) for
 // the particles that are off the list or have no cell (:1949-1950)
+// (tree_field_keys_kernel, tree_particles.hip, is this kernel on the leaves of a tree)
 template <int DIM>
 __global__ void __launch_bounds__(256)
 field_keys_kernel (int nside, int depth, int n, const double * __restrict__ x, const double * __restrict__ y,
@@ -125,36 +129,6 @@ field_keys_kernel (int nside, int depth, int n, const double * __restrict__ x, c
 				(DIM == 3 ? (unsigned long long) nside*(c[2] - 1) : 0ull));
   }
   key[q] = k << 32 | orig[q];
-}
-
-// leaf index of the Layout of linear cell number `cell'
-template <int DIM>
-__device__ __forceinline__ long cell_index (const Layout & L, unsigned long long cell)
-{
-  const unsigned n = (unsigned) L.n;
-  const int i = (int) (cell % n) + 1, j = (int) ((cell/n) % n) + 1;
-  const int k = DIM == 3 ? (int) (cell/((unsigned long long) n*n)) + 1 : 0;
-  return L.idx (i, j, k);
-}
-
-// voidfraction_from_particles (:1929-1932) for the particles of one cell, in list order
-template <int DIM>
-__global__ void __launch_bounds__(256)
-field_sum_kernel (Layout L, int n, const unsigned long long * __restrict__ key, unsigned long long ncell,
-		  const double * __restrict__ volume, double * __restrict__ v)
-{
-  int r = blockIdx.x*blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  const unsigned long long cell = key[r] >> 32;
-  if (cell >= ncell) return;
-  if (r > 0 && key[r - 1] >> 32 == cell) return;      /* not the first of its cell */
-  const double h = 1./L.n;
-  const double cellvol = DIM == 3 ? h*h*h : h*h;        /* ftt_cell_volume */
-  const long idx = cell_index<DIM> (L, cell);
-  double s = v[idx];
-  for (int m = r; m < n && key[m] >> 32 == cell; m++)
-    s += volume[(unsigned) (key[m] & 0xFFFFFFFFull)]/cellvol;
-  v[idx] = s;
 }
 
 struct SpreadArgs {
@@ -210,66 +184,12 @@ spread_emit_kernel (SpreadArgs A)
     A.key[base + j] = A.pad << 32 | 0xFFFFFFFFull;
 }
 
+// a constant GfsFunction: of the kernel of a GfsSourceParticulate, of a GfsSourceParticulateVol / ...Mass
 __global__ void __launch_bounds__(256)
-spread_constant_kernel (long nrec, double value, double * __restrict__ out)
+fill_kernel (long n, double value, double * __restrict__ out)
 {
   long r = (long) blockIdx.x*blockDim.x + threadIdx.x;
-  if (r < nrec) out[r] = value;
-}
-
-// step 3: kernel_volume (:2108-2119) over the leaves of each particle in traversal order, then :2216
-template <int DIM>
-__global__ void __launch_bounds__(256)
-spread_correction_kernel (int nchunk, int stride, int nside, const int * __restrict__ cnt,
-			  const double * __restrict__ K, double * __restrict__ corr)
-{
-  int t = blockIdx.x*blockDim.x + threadIdx.x;
-  if (t >= nchunk) return;
-  const double h = 1./nside;
-  const double cellvol = DIM == 3 ? h*h*h : h*h;        /* gfs_cell_volume of a cell without solid */
-  double volume = 0., correction = 0.;
-  const size_t base = (size_t) t*stride;
-  for (int j = 0; j < cnt[t]; j++) {
-    volume += cellvol;
-    correction += K[base + j]*cellvol;
-  }
-  correction /= volume;      /* no leaf: 0./0., which is not > 1.e-10 -- and there is nothing to add to */
-  corr[t] = correction;
-}
-
-// step 4: diffuse_force (:2158-2175) for the records of one cell, in list order
-template <int DIM, bool RHO>
-__global__ void __launch_bounds__(256)
-spread_sum_kernel (Layout L, long nrec, const unsigned long long * __restrict__ key, unsigned long long ncell,
-		   const double * __restrict__ K, int o0, const double * __restrict__ corr,
-		   const double * __restrict__ fx, const double * __restrict__ fy, const double * __restrict__ fz,
-		   const double * __restrict__ alpha_cell,
-		   double * __restrict__ Fx, double * __restrict__ Fy, double * __restrict__ Fz)
-{
-  long r = (long) blockIdx.x*blockDim.x + threadIdx.x;
-  if (r >= nrec) return;
-  const unsigned long long cell = key[r] >> 32;
-  if (cell >= ncell) return;
-  if (r > 0 && key[r - 1] >> 32 == cell) return;
-  const double h = 1./L.n;
-  const double cellvol = DIM == 3 ? h*h*h : h*h;
-  const long idx = cell_index<DIM> (L, cell);
-  double liq_rho = 1.;
-  if constexpr (RHO) liq_rho = 1./alpha_cell[idx];     /* :2167-2168 */
-  double F[3] = { Fx[idx], Fy[idx], DIM == 3 ? Fz[idx] : 0. };
-  for (long m = r; m < nrec && key[m] >> 32 == cell; m++) {
-    const unsigned o = (unsigned) (key[m] & 0xFFFFFFFFull);
-    const double correction = corr[o - (unsigned) o0];
-    if (correction > 1.e-10) {
-      const double k = K[m];
-      F[0] -= fx[o]/liq_rho/cellvol*k/correction;
-      F[1] -= fy[o]/liq_rho/cellvol*k/correction;
-      if (DIM == 3) F[2] -= fz[o]/liq_rho/cellvol*k/correction;
-    }
-  }
-  Fx[idx] = F[0];
-  Fy[idx] = F[1];
-  if (DIM == 3) Fz[idx] = F[2];
+  if (r < n) out[r] = value;
 }
 
 // source_particulate_value (:2029-2065): gfs_face_interpolated_value_generic of F on the positive face of
@@ -427,6 +347,23 @@ static int coupling_check (gfship_particles * pl, const char * what)
   return GFSHIP_OK;
 }
 
+int launch_where (gfship_particles * pl)
+{
+  const int block = 256;
+  hipLaunchKernelGGL (where_kernel, dim3 ((pl->n + block - 1)/block), dim3 (block), 0, pl->stream, pl->n, pl->orig,
+		      pl->where);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
+int launch_fill (hipStream_t stream, long n, double value, double * out)
+{
+  const int block = 256;
+  hipLaunchKernelGGL (fill_kernel, dim3 ((unsigned) ((n + block - 1)/block)), dim3 (block), 0, stream, n, value, out);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
 } // namespace gfship
 
 using namespace gfship;
@@ -466,8 +403,8 @@ int gfship_particulate_field (gfship_particles * pl, gfship_field v)
 						 dom->stream));
   with_bools ([&] (auto D3) {
     constexpr int DIM = decltype (D3)::value ? 3 : 2;
-    hipLaunchKernelGGL (field_sum_kernel<DIM>, dim3 (grid), dim3 (block), 0, dom->stream, L, pl->n,
-			pl->ckey2, ncell, pl->volume, a);
+    hipLaunchKernelGGL ((field_sum_kernel<DIM, BoxCells<DIM>>), dim3 (grid), dim3 (block), 0, dom->stream,
+			BoxCells<DIM> { L }, pl->n, pl->ckey2, ncell, pl->volume, a);
   }, dom->dim == 3);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
@@ -545,9 +482,7 @@ static int spread_forces (gfship_particles * pl, const gfship_field F[3], double
   const unsigned long long ncell = (unsigned long long) ncells (L);
   const int bits = coupling_key_bits (ncell);
   const int block = 256;
-  hipLaunchKernelGGL (where_kernel, dim3 ((pl->n + block - 1)/block), dim3 (block), 0, dom->stream, pl->n,
-		      pl->orig, pl->where);
-  GFSHIP_HIP (hipGetLastError ());
+  if ((r = launch_where (pl))) return r;
   GFSHIP_HIP (hipMemsetAsync (pl->cflag, 0, sizeof (int), dom->stream));
   const bool rho = v.alpha_cell >= 0;
   const double * alpha = rho ? dom->fields[v.alpha_cell].lev[dom->depth] : nullptr;
@@ -574,15 +509,12 @@ static int spread_forces (gfship_particles * pl, const gfship_field F[3], double
 				   pl->cq[2], t, pl->cval)))
 	return r;
     }
-    else {
-      hipLaunchKernelGGL (spread_constant_kernel, dim3 (rgrid), dim3 (block), 0, dom->stream, nrec,
-			  pl->kernel_value, pl->cval);
-      GFSHIP_HIP (hipGetLastError ());
-    }
+    else if ((r = launch_fill (dom->stream, nrec, pl->kernel_value, pl->cval)))
+      return r;
     with_bools ([&] (auto D3) {
       constexpr int DIM = decltype (D3)::value ? 3 : 2;
-      hipLaunchKernelGGL (spread_correction_kernel<DIM>, dim3 (pgrid), dim3 (block), 0, dom->stream, nchunk,
-			  stride, L.n, pl->ccnt, pl->cval, pl->ccorr);
+      hipLaunchKernelGGL ((spread_correction_kernel<DIM, BoxCells<DIM>>), dim3 (pgrid), dim3 (block), 0, dom->stream,
+			  BoxCells<DIM> { L }, nchunk, stride, pl->ccnt, pl->ckey, pl->cval, pl->ccorr);
     }, dom->dim == 3);
     GFSHIP_HIP (hipGetLastError ());
     GFSHIP_HIP (mark ());
@@ -595,8 +527,8 @@ static int spread_forces (gfship_particles * pl, const gfship_field F[3], double
 						    pl->cval2, nrec, 0, bits, dom->stream));
     with_bools ([&] (auto D3, auto RHO) {
       constexpr int DIM = decltype (D3)::value ? 3 : 2;
-      hipLaunchKernelGGL ((spread_sum_kernel<DIM, decltype (RHO)::value>), dim3 (rgrid), dim3 (block), 0,
-			  dom->stream, L, nrec, pl->ckey2, ncell, pl->cval2, o0, pl->ccorr, pl->force[0],
+      hipLaunchKernelGGL ((spread_sum_kernel<DIM, decltype (RHO)::value, BoxCells<DIM>>), dim3 (rgrid), dim3 (block), 0,
+			  dom->stream, BoxCells<DIM> { L }, nrec, pl->ckey2, ncell, pl->cval2, o0, pl->ccorr, pl->force[0],
 			  pl->force[1], pl->force[2], alpha, Fa[0], Fa[1], Fa[2]);
     }, dom->dim == 3, rho);
     GFSHIP_HIP (hipGetLastError ());

@@ -26,6 +26,7 @@
 // order).  Tracers move less than one cell per step (CFL < 1), so the order stays good between
 // sorts.
 #include "particles.hpp"
+#include "particulate_forces.hpp"
 #include "tree_particles.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -241,30 +242,19 @@ particle_list_event_kernel (PartArgs A, int depth)
 }
 
 // ---------------------------------------------------------------------------------------------
-// GfsParticulate with forces (modules/particulatecommon.c:91-842): uniform box.  Same operand order
-// as the reference; pow (Re, 0.5) of the drag law is evaluated as sqrt (Re) (correctly rounded;
-// glibc's pow is within 0.52 ulp of it).  The density and the viscosity of the fluid are those of the
+// GfsParticulate with forces (modules/particulatecommon.c:91-842): uniform box.  The forces, the integration
+// step and the coefficient inputs are those of particulate_forces.hpp (shared with tree_particles.hip); the
+// kernels here locate the particle, gather what the forces read of the fluid, store and apply gfs_particle_bc.
+// The density and the viscosity of the fluid are those of the
 // cell that holds the particle (:273-279, 349-359, 439-445, 534-541, 631-632): the kernels are
 // instantiated on RHO (fluid_rho = 1./alpha_cell[idx]; false: alpha = NULL, fluid_rho = 1.) and on MU
 // (viscosity = mu_cell[idx], gfs_diffusion_cell; false: the constant of the launch).  <false, false>
-// takes ParticulateArgs itself: the kernel arguments, and with them the device code, of a build
-// without the two fields.
+// takes ParticulateArgs itself: the kernel arguments of a build without the two fields.
 // ---------------------------------------------------------------------------------------------
-enum { FORCE_INERTIAL = GFSHIP_FORCE_INERTIAL, FORCE_ADDEDMASS = GFSHIP_FORCE_ADDEDMASS,
-       FORCE_LIFT = GFSHIP_FORCE_LIFT, FORCE_DRAG = GFSHIP_FORCE_DRAG, FORCE_BUOY = GFSHIP_FORCE_BUOY };
-
-struct ParticulateArgs {
-  PartArgs P;
-  const unsigned * orig;
-  double * vel[3], * force[3], * mass;
-  const double * volume, * dia;
-  const double * uold[3];
-  int nforces, forces[8];
-  double gravity[3], viscosity;
-  const double * coef[8];      // values of the GfsFunction of force f per slot; nullptr: the default
-  double * cin[6];             // Rep, Urelp, Vrelp, Wrelp, Pdia per slot (coefficient inputs); [5]: the Rep of
-                               // GfsForceDrag in 2-D (two-component norm, particulatecommon.c:549-556)
-};
+// the arguments of <false, false>: the list's box, then the state and the forces of its particulates, in the layout
+// the kernels have always had
+struct BoxListArgs { PartArgs P; };
+struct ParticulateArgs : BoxListArgs, ParticleForceArgs {};
 
 // the arguments of an instantiation that reads a field of the fluid at the particle's cell
 struct ParticulateFieldArgs : ParticulateArgs {
@@ -298,37 +288,44 @@ __device__ __forceinline__ double center_gradient (const double * __restrict__ v
   return ((v2 - v0) + (v0 - v1))/2.;
 }
 
-// compute_inertial_force, :285-336
-// (fvel: the fluid velocity interpolated at the particle, computed once per particle and shared with
-// the lift and drag forces: the same gfs_interpolate of the same fields)
+// the sources of particulate_forces.hpp on a box: gfs_center_gradient (cell, c2, u[c]) and u[c2] at cell idx,
+// gfs_interpolate of component c of U (or Un) at p
+struct BoxGradient {
+  const PartArgs & P; long idx; const long * off;
+  __device__ __forceinline__ double operator() (int c, int c2) const { return center_gradient (P.u[c], idx, off[c2]); }
+};
+struct BoxCellU {
+  const PartArgs & P; long idx;
+  __device__ __forceinline__ double operator() (int c2) const { return P.u[c2][idx]; }
+};
+template <int DIM>
+struct BoxInterpolated {
+  const Layout & L; const double * const * u; const int * cell; const double * p;
+  __device__ __forceinline__ double operator() (int c) const { return interpolate<DIM> (L, u[c], cell, p); }
+};
+
+// compute_inertial_force at cell idx: a function of its own, which takes the three interpolations of Un with it
+// when it is inlined
 template <int DIM, bool RHO, class Args>
-__device__ void inertial_force (const Args & A, const int cell[3], const double p[3],
-				long idx, const double fvel[3], double force[3])
+__device__ void box_inertial_force (const Args & A, const int cell[3], const double p[3], long idx,
+				    const double fvel[3], double force[3])
 {
   const Layout & L = A.P.L;
   const long off[3] = { 1, (long) L.sy, (long) L.sz };
-  const double size = 1./L.n;
-  const double fluid_rho = cell_fluid_rho<RHO> (A, idx);
-  force[0] = force[1] = force[2] = 0.;
-  if (!(A.P.dt > 0.))
-    return;
-#pragma unroll
-  for (int c = 0; c < DIM; c++) {
-    const double fluid_vel = fvel[c];
-    const double fluid_veln = interpolate<DIM> (L, A.uold[c], cell, p);
-    force[c] = fluid_rho*(fluid_vel - fluid_veln)/A.P.dt;
-  }
-#pragma unroll
-  for (int c = 0; c < DIM; c++)
-#pragma unroll
-    for (int c2 = 0; c2 < DIM; c2++)
-      force[c] += fluid_rho*center_gradient (A.P.u[c], idx, off[c2])*A.P.u[c2][idx]/size;
+  inertial_force<DIM> (cell_fluid_rho<RHO> (A, idx), A.P.dt, 1./L.n, fvel, BoxInterpolated<DIM> { L, A.uold, cell, p },
+		       BoxGradient { A.P, idx, off }, BoxCellU { A.P, idx }, force);
 }
 
-// the variables a GfsFunction of a GfsForceCoeff sees (:364-384,462-485,545-573): the particle
-// Reynolds number from the relative velocity (all three components of the FttVectors), the sphere
-// diameter and the viscosity (0.001 where the reference substitutes it for a zero viscosity in the
-// added-mass and lift coefficients; the drag is then zero whatever its coefficient)
+// the viscosity of the fluid at the particle: that of its cell, or the constant of the launch read at its use
+template <bool MU, class Args>
+__device__ __forceinline__ auto viscosity_source (const Args & A, double mu)
+{
+  if constexpr (MU) return ValueOf { mu };
+  else return ListViscosity { A };
+}
+
+// the variables a GfsFunction of a GfsForceCoeff sees: coefficient_inputs (particulate_forces.hpp) at the
+// particle's cell
 template <int DIM, bool RHO, bool MU>
 __global__ void __launch_bounds__(256)
 particulate_coeff_inputs_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
@@ -345,19 +342,11 @@ particulate_coeff_inputs_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
   const long idx = RHO || MU ? L.idx (cell[0], cell[1], DIM == 3 ? cell[2] : 0) : 0;
   const double fluid_rho = cell_fluid_rho<RHO> (A, idx);
   const double mu = cell_viscosity<MU> (A, idx);
-  double rel[3] = { 0. - A.vel[0][o], 0. - A.vel[1][o], 0. - A.vel[2][o] };
+  double fvel[3] = { 0., 0., 0. };
 #pragma unroll
   for (int c = 0; c < DIM; c++)
-    rel[c] = interpolate<DIM> (L, P.u[c], cell, p) - A.vel[c][o];
-  const double norm = sqrt (rel[0]*rel[0] + rel[1]*rel[1] + rel[2]*rel[2]);
-  const double dia = A.dia[o];
-  const double cell_visc = MU ? mu : A.viscosity;
-  const double viscosity = cell_visc == 0 ? 0.001 : cell_visc;      /* :372-375, 461-464 */
-  A.cin[0][q] = norm*dia*fluid_rho/viscosity;
-  A.cin[1][q] = rel[0]; A.cin[2][q] = rel[1]; A.cin[3][q] = rel[2];
-  A.cin[4][q] = dia;
-  if (DIM == 2)      /* compute_drag_force takes the norm of the two components in 2-D (:549-556) */
-    A.cin[5][q] = sqrt (rel[0]*rel[0] + rel[1]*rel[1])*dia*fluid_rho/viscosity;
+    fvel[c] = interpolate<DIM> (L, P.u[c], cell, p);
+  coefficient_inputs<DIM> (A, q, o, fvel, fluid_rho, viscosity_source<MU> (A, mu));
 }
 
 // gfs_particulate_event (:768-842) in a gfs_particle_list_event (:980-1015)
@@ -367,6 +356,7 @@ particulate_coeff_inputs_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
 // compute_addedmass_force adds to particulate->mass here as in an event (:391) and nothing takes it back.
 // The particle does not move and stays on the list; a particle without a cell gets the zero force every
 // compute_*_force returns there and keeps its mass
+// (tree_particulate_list_event_kernel, tree_particles.hip, is this kernel on the leaves of a tree)
 template <int DIM, bool RHO, bool MU, bool ONFLUID = false>
 __global__ void __launch_bounds__(256)
 particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
@@ -404,112 +394,19 @@ particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
   double mass = A.mass[o];
   const double volume = A.volume[o];
   double pf[3] = { 0., 0., 0. };
-  // every force is a function of the state at the start of the event: what several of them need --
-  // the fluid velocity at the particle, Du/Dt -- is evaluated once (the reference re-evaluates the
-  // same expressions per force: same bits)
-  bool need_fvel = false, need_dudt = false;
-  for (int f = 0; f < A.nforces; f++) {
-    if (ONFLUID && A.forces[f] == FORCE_BUOY)
-      continue;
-    need_fvel = need_fvel || A.forces[f] != FORCE_BUOY;
-    need_dudt = need_dudt || A.forces[f] == FORCE_INERTIAL || A.forces[f] == FORCE_ADDEDMASS;
-  }
+  ForceNeeds need;
+  force_needs<ONFLUID> (A, need);
+  const BoxGradient grad = { P, idx, off };
   double fvel[3] = { 0., 0., 0. }, dudt[3] = { 0., 0., 0. };
-  if (need_fvel) {
+  if (need.fvel) {
 #pragma unroll
     for (int c = 0; c < DIM; c++)
       fvel[c] = interpolate<DIM> (L, P.u[c], cell, p);
   }
-  if (need_dudt)
-    inertial_force<DIM, RHO> (A, cell, p, idx, fvel, dudt);
-  for (int f = 0; f < A.nforces; f++) {
-    double force[3] = { 0., 0., 0. };
-    if (ONFLUID && A.forces[f] == FORCE_BUOY)      /* :756 */
-      continue;
-    switch (A.forces[f]) {
-    case FORCE_INERTIAL:
-      force[0] = dudt[0]; force[1] = dudt[1]; force[2] = dudt[2];
-      break;
-    case FORCE_ADDEDMASS: {     // compute_addedmass_force, :363-427
-      force[0] = dudt[0]; force[1] = dudt[1]; force[2] = dudt[2];
-      const double cm = A.coef[f] ? A.coef[f][q] : 0.5;
-#pragma unroll
-      for (int c = 0; c < DIM; c++)
-	force[c] *= cm;
-      mass += fluid_rho*volume*cm;      /* :391, in compute_forces_onfluid too */
-      break;
-    }
-    case FORCE_LIFT: {          // compute_lift_force, :455-524; vorticity_vector, :146-168
-      double rel[3] = { 0., 0., 0. }, vort[3];
-#pragma unroll
-      for (int c = 0; c < DIM; c++)
-	rel[c] = fvel[c] - vel[c];
-      if (DIM == 2) {
-	vort[0] = 0.; vort[1] = 0.;
-	vort[2] = (center_gradient (P.u[1], idx, off[0]) - center_gradient (P.u[0], idx, off[1]))/size;
-      }
-      else {
-	vort[0] = (center_gradient (P.u[2], idx, off[1]) - center_gradient (P.u[1], idx, off[2]))/size;
-	vort[1] = (center_gradient (P.u[0], idx, off[2]) - center_gradient (P.u[2], idx, off[0]))/size;
-	vort[2] = (center_gradient (P.u[1], idx, off[0]) - center_gradient (P.u[0], idx, off[1]))/size;
-      }
-      const double cl = A.coef[f] ? A.coef[f][q] : 0.5;
-      if (DIM == 2) {
-	force[0] = fluid_rho*cl*rel[1]*vort[2];
-	force[1] = -fluid_rho*cl*rel[0]*vort[2];
-      }
-      else {
-	force[0] = fluid_rho*cl*(rel[1]*vort[2] - rel[2]*vort[1]);
-	force[1] = fluid_rho*cl*(rel[2]*vort[0] - rel[0]*vort[2]);
-	force[2] = fluid_rho*cl*(rel[0]*vort[1] - rel[1]*vort[0]);
-      }
-      break;
-    }
-    case FORCE_DRAG: {          // compute_drag_force, :527-588
-      double rel[3] = { 0., 0., 0. };
-#pragma unroll
-      for (int c = 0; c < DIM; c++)
-	rel[c] = fvel[c] - vel[c];
-      const double dia = A.dia[o];
-      const double norm = DIM == 3 ? sqrt (rel[0]*rel[0] + rel[1]*rel[1] + rel[2]*rel[2]) :
-	sqrt (rel[0]*rel[0] + rel[1]*rel[1]);
-      double Re;
-      if constexpr (MU) {
-	if (mu == 0)              /* :561-562: no drag in a cell without viscosity */
-	  break;
-	Re = norm*dia*fluid_rho/mu;
-      }
-      else {
-	if (A.viscosity == 0)
-	  break;
-	Re = norm*dia*fluid_rho/A.viscosity;
-      }
-      double cd;
-      if (A.coef[f])
-	cd = A.coef[f][q];
-      else if (Re < 1e-8)
-	break;
-      else if (Re < 50.0)
-	cd = 16.*(1. + 0.15*sqrt (Re))/Re;
-      else
-	cd = 48.*(1. - 2.21/sqrt (Re))/Re;
-#pragma unroll
-      for (int c = 0; c < DIM; c++)
-	force[c] += 3./(4.*dia)*cd*norm*rel[c]*fluid_rho;
-      break;
-    }
-    case FORCE_BUOY:            // compute_buoyancy_force, :619-653
-#pragma unroll
-      for (int c = 0; c < DIM; c++)
-	force[c] += (mass/volume - fluid_rho)*A.gravity[c];
-      break;
-    }
-    // compute_forces, :738-752
-#pragma unroll
-    for (int c = 0; c < DIM; c++)
-      pf[c] = force[c]*volume + pf[c];
-    if (DIM == 2) pf[2] = 0.;
-  }
+  if (need.dudt)
+    box_inertial_force<DIM, RHO> (A, cell, p, idx, fvel, dudt);
+  particulate_forces<DIM, ONFLUID> (A, q, o, fluid_rho, viscosity_source<MU> (A, mu), size, grad, fvel, dudt, vel,
+				    volume, mass, pf);
   if constexpr (ONFLUID) {
 #pragma unroll
     for (int c = 0; c < 3; c++)
@@ -517,12 +414,7 @@ particulate_list_event_kernel (ParticulateArgsOf<RHO, MU> A, int depth)
     A.mass[o] = mass;
     return;
   }
-#pragma unroll
-  for (int c = 0; c < DIM; c++) {
-    p[c] += vel[c]*dt/2.;
-    vel[c] += pf[c]*dt/mass;
-    p[c] += vel[c]*dt/2.;
-  }
+  particulate_advance<DIM> (p, vel, pf, dt, mass);
 #pragma unroll
   for (int c = 0; c < 3; c++) {
     A.vel[c][o] = vel[c];
@@ -582,6 +474,7 @@ particle_outbox_kernel (OutboxArgs A)
 }
 
 // key = linear index of the containing leaf cell, dead or outside particles last
+// (tree_particle_keys_kernel, tree_particles.hip, is this kernel on the leaves of a tree)
 template <int DIM>
 __global__ void __launch_bounds__(256)
 particle_keys_kernel (Layout L, int depth, int n, const double * __restrict__ x,
@@ -674,6 +567,7 @@ struct SourceGatherArgs {
   double * rad, * urel[3];
 };
 
+// (tree_particulate_source_gather_kernel, tree_particles.hip, is this kernel on the leaves of a tree)
 template <int DIM>
 __global__ void __launch_bounds__(256)
 particulate_source_gather_kernel (SourceGatherArgs A)
@@ -1104,6 +998,62 @@ int gfship::particulate_fluid_check (const gfship_sim_view & v)
   return GFSHIP_OK;
 }
 
+// the state of the particulates of a list and its forces, with the default coefficients
+void gfship::particulate_force_args (const gfship_particles * pl, ParticleForceArgs & A)
+{
+  A.orig = pl->orig;
+  for (int c = 0; c < 3; c++) {
+    A.vel[c] = pl->vel[c];
+    A.force[c] = pl->force[c];
+    A.gravity[c] = pl->gravity[c];
+  }
+  A.mass = pl->mass; A.volume = pl->volume; A.dia = pl->dia;
+  A.nforces = pl->nforces;
+  for (int f = 0; f < 8; f++) {
+    A.forces[f] = pl->forces[f];
+    A.coef[f] = nullptr;
+  }
+  for (int q = 0; q < 6; q++) A.cin[q] = nullptr;
+}
+
+// the GfsFunction coefficients of the forces of a list: the inputs of every particle (launch_inputs: the
+// coefficient-input kernel of the caller, which reads A), then one compiled kernel per function
+int gfship::particulate_coefficients (gfship_particles * pl, ParticleForceArgs & A, hipStream_t stream, double t,
+				      const std::function<void ()> & launch_inputs)
+{
+  bool any = false;
+  for (int f = 0; f < pl->nforces; f++)
+    if (pl->coef_fn[f]) any = true;
+  if (!any)
+    return GFSHIP_OK;
+  if (pl->coef_cap < pl->cap) {
+    for (int q = 0; q < 6; q++) {
+      if (pl->cin[q]) GFSHIP_HIP (hipFree (pl->cin[q]));
+      pl->cin[q] = nullptr;
+      GFSHIP_HIP (hipMalloc ((void **) &pl->cin[q], (size_t) pl->cap*sizeof (double)));
+    }
+    for (int f = 0; f < 8; f++) {
+      if (pl->coef[f]) GFSHIP_HIP (hipFree (pl->coef[f]));
+      pl->coef[f] = nullptr;
+    }
+    pl->coef_cap = pl->cap;
+  }
+  for (int q = 0; q < 6; q++) A.cin[q] = pl->cin[q];
+  launch_inputs ();
+  GFSHIP_HIP (hipGetLastError ());
+  const double * rel[3] = { pl->cin[1], pl->cin[2], pl->cin[3] };
+  for (int f = 0; f < pl->nforces; f++)
+    if (pl->coef_fn[f]) {
+      if (!pl->coef[f])
+	GFSHIP_HIP (hipMalloc ((void **) &pl->coef[f], (size_t) pl->coef_cap*sizeof (double)));
+      const double * rep = pl->dim == 2 && pl->forces[f] == GFSHIP_FORCE_DRAG ? pl->cin[5] : pl->cin[0];
+      int r = rtc_launch_coefficient (pl->coef_fn[f], stream, pl->n, pl->alive, rep, rel, pl->cin[4], t, pl->coef[f]);
+      if (r) return r;
+      A.coef[f] = pl->coef[f];
+    }
+  return GFSHIP_OK;
+}
+
 extern "C" {
 
 // onfluid: the forces on the fluid alone (particulate_list_event_kernel <ONFLUID>): `force' changes, and `mass'
@@ -1117,60 +1067,20 @@ static int particulate_event (gfship_particles * pl, const PartArgs & P, const g
   A.alpha_cell = rho ? dom->fields[v.alpha_cell].lev[dom->depth] : nullptr;
   A.mu_cell = mu ? dom->fields[v.mu].lev[dom->depth] : nullptr;
   A.P = P;
-  A.orig = pl->orig;
-  for (int c = 0; c < 3; c++) {
-    A.vel[c] = pl->vel[c];
-    A.force[c] = pl->force[c];
+  particulate_force_args (pl, A);
+  for (int c = 0; c < 3; c++)
     A.uold[c] = c < dom->dim && pl->uold[c] >= 0 ? dom->fields[pl->uold[c]].lev[dom->depth] : nullptr;
-    A.gravity[c] = pl->gravity[c];
-  }
-  A.mass = pl->mass; A.volume = pl->volume; A.dia = pl->dia;
-  A.nforces = pl->nforces;
-  for (int f = 0; f < 8; f++) A.forces[f] = pl->forces[f];
   A.viscosity = v.visc;
   int block = 256, grid = (pl->n + block - 1)/block;
-  bool any = false;
-  for (int f = 0; f < 8; f++) {
-    A.coef[f] = nullptr;
-    if (f < pl->nforces && pl->coef_fn[f]) any = true;
-  }
-  for (int q = 0; q < 6; q++) A.cin[q] = nullptr;
-  if (any) {
-    /* the GfsFunction coefficients: inputs of every particle, then one compiled kernel per function */
-    if (pl->coef_cap < pl->cap) {
-      for (int q = 0; q < 6; q++) {
-	if (pl->cin[q]) GFSHIP_HIP (hipFree (pl->cin[q]));
-	pl->cin[q] = nullptr;
-	GFSHIP_HIP (hipMalloc ((void **) &pl->cin[q], (size_t) pl->cap*sizeof (double)));
-      }
-      for (int f = 0; f < 8; f++) {
-	if (pl->coef[f]) GFSHIP_HIP (hipFree (pl->coef[f]));
-	pl->coef[f] = nullptr;
-	if (pl->coef_fn[f])
-	  GFSHIP_HIP (hipMalloc ((void **) &pl->coef[f], (size_t) pl->cap*sizeof (double)));
-      }
-      pl->coef_cap = pl->cap;
-    }
-    for (int q = 0; q < 6; q++) A.cin[q] = pl->cin[q];
+  int r = particulate_coefficients (pl, A, dom->stream, gfship_sim_time (pl->sim), [&] {
     with_bools ([&] (auto D3, auto RHO, auto MU) {
       constexpr int DIM = decltype (D3)::value ? 3 : 2;
       constexpr bool R = decltype (RHO)::value, M = decltype (MU)::value;
       hipLaunchKernelGGL ((particulate_coeff_inputs_kernel<DIM, R, M>), dim3 (grid), dim3 (block), 0, dom->stream,
 			  static_cast<const ParticulateArgsOf<R, M> &> (A), dom->depth);
     }, dom->dim == 3, rho, mu);
-    GFSHIP_HIP (hipGetLastError ());
-    const double * rel[3] = { pl->cin[1], pl->cin[2], pl->cin[3] };
-    for (int f = 0; f < pl->nforces; f++)
-      if (pl->coef_fn[f]) {
-	if (!pl->coef[f])
-	  GFSHIP_HIP (hipMalloc ((void **) &pl->coef[f], (size_t) pl->coef_cap*sizeof (double)));
-	const double * rep = dom->dim == 2 && pl->forces[f] == GFSHIP_FORCE_DRAG ? pl->cin[5] : pl->cin[0];
-	int r = rtc_launch_coefficient (pl->coef_fn[f], dom->stream, pl->n, P.alive, rep, rel, pl->cin[4],
-					gfship_sim_time (pl->sim), pl->coef[f]);
-	if (r) return r;
-	A.coef[f] = pl->coef[f];
-      }
-  }
+  });
+  if (r) return r;
   if (onfluid) {
     with_bools ([&] (auto D3, auto RHO, auto MU) {
       constexpr int DIM = decltype (D3)::value ? 3 : 2;

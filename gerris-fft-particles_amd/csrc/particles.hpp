@@ -1,6 +1,7 @@
 // particles.hpp -- the particle list and the cell search shared by particles.hip and coupling.hip.
 #pragma once
 #include "gfship_internal.hpp"
+#include <functional>
 #include <vector>
 
 namespace gfship {
@@ -119,6 +120,14 @@ gfship_sim_view gfship_sim_view_get (gfship_sim * s);   /* simulation.hip */
 namespace gfship {
 // the refusals of every entry that evaluates the forces of a list (particles.hip)
 int particulate_fluid_check (const gfship_sim_view & v);
+// what the event kernels of a box and of a tree share of their arguments (particulate_forces.hpp): the state of
+// the particulates and the forces of the list with the default coefficients; then, where a force has a GfsFunction
+// coefficient, cin and coef of the list (allocated for its capacity), the caller's coefficient-input kernel
+// through launch_inputs, one rtc_launch_coefficient per function at time t, and A.coef[] (particles.hip)
+struct ParticleForceArgs;
+void particulate_force_args (const gfship_particles * pl, ParticleForceArgs & A);
+int particulate_coefficients (gfship_particles * pl, ParticleForceArgs & A, hipStream_t stream, double t,
+			      const std::function<void ()> & launch_inputs);
 void coupling_free (gfship_particles * pl);   // coupling.hip
 // the work arrays of the void fraction and of the spreading (coupling.hip), shared with the lists of a tree
 // (tree_particles.hip): nrec record slots, npart particles of a chunk, on the stream of the list; a chunk holds
@@ -127,6 +136,10 @@ constexpr size_t COUPLING_RECORD_CAP = (size_t) 1 << 22;
 int coupling_reserve (gfship_particles * pl, size_t nrec, size_t npart, bool spreading);
 int coupling_sort_reserve (gfship_particles * pl, size_t need);
 int coupling_key_bits (unsigned long long ncell);
+// where[creation slot] = slot for the n slots of the list, and out[0 .. n - 1] = value (a constant GfsFunction), on
+// the stream of the list / the stream given (coupling.hip)
+int launch_where (gfship_particles * pl);
+int launch_fill (hipStream_t stream, long n, double value, double * out);
 // the per-particle arrays of a new list of np tracers (particles.hip); pl->stream is set by the caller
 int particles_alloc (gfship_particles * pl, int np, const double * pos, const unsigned * id);
 // a list on a tree (tree_particles.hip): the event of its tracers, the keys of gfship_particles_sort and their bits
@@ -141,10 +154,10 @@ int tree_particulate_list_event (gfship_particles * pl);
 // interpolate of the event kernels (particles.hip): per creation slot the linear number of the particle's cell
 // (PSOURCE_NO_CELL off the list or without a cell), pow (3.0*volume/4.0/M_PI, 1./3.) and fluid velocity - vel
 int launch_particulate_source_gather (gfship_particles * pl, unsigned * cell, double * rad, double * const urel[3]);
-// the passes of particulate_sources.hip that the event of a tree shares: the per-slot arrays of the object, the
-// constant function, and step 3 (volume or mass += source*dt, diameter and rb, the key cell << 32 | slot)
+// the passes of particulate_sources.hip that the event of a tree shares: the per-slot arrays of the object and
+// step 3 (volume or mass += source*dt, diameter and rb, the key cell << 32 | slot); the constant function is
+// launch_fill
 int particulate_source_reserve (gfship_particulate_source * s);
-int launch_particulate_source_constant (hipStream_t stream, int n, double value, double * out);
 int launch_particulate_source_update (gfship_particulate_source * s, hipStream_t stream, double dt,
 				      unsigned long long pad, unsigned long long * key);
 // the event of a source on a list of a tree (tree_particles.hip); info as in source_event

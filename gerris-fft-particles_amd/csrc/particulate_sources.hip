@@ -15,7 +15,8 @@
 //      (:2091) of the particle, and the key (cell << 32 | creation slot);
 //   4. where a field is to be written: radix sort of the keys (the arrays and the key bits of coupling.hip),
 //      then one thread per run of equal cells adds the sources serially and copies the values of the last
-//      record.  No atomics: the result does not depend on where a particle is stored nor on the scheduling.
+//      record (particulate_source_cell_kernel, cell_sums.hpp, shared with the lists of a tree).  No atomics: the
+//      result does not depend on where a particle is stored nor on the scheduling.
 // The event has no chunks: one record of 8 bytes per particle (the spreading needs chunks because one particle
 // owns many records).
 //
@@ -24,6 +25,7 @@
 // operation by operation.  A list no volume event has run on keeps the diameter and rb computed on the host
 // (particulate_alloc).
 #include "particles.hpp"
+#include "cell_sums.hpp"
 #include "tree_particles.hpp"
 #include <hipcub/hipcub.hpp>
 #include <cmath>
@@ -54,49 +56,6 @@ particulate_source_update_kernel (int n, const unsigned * __restrict__ cell, con
     rb[o] = pow (3.*s/(4.*M_PI), 1./3.);
   }
   if (key) key[o] = (unsigned long long) c << 32 | (unsigned) o;
-}
-
-__global__ void __launch_bounds__(256)
-particulate_source_constant_kernel (int n, double value, double * __restrict__ out)
-{
-  int o = blockIdx.x*blockDim.x + threadIdx.x;
-  if (o < n) out[o] = value;
-}
-
-struct SourceCellArgs {
-  Layout L;
-  int n;
-  const unsigned long long * key;
-  unsigned long long ncell;
-  const double * src, * prad, * purel[3];
-  double * deposit, * rad, * urel[3];      // nullptr: not written
-};
-
-// step 4: the records of one cell in list order: deposit += source from the 0. of the reset (:2830, :2989),
-// Rad, Urelp ... of the last one (:2812-2824: every particle overwrites what the one before left)
-template <int DIM>
-__global__ void __launch_bounds__(256)
-particulate_source_cell_kernel (SourceCellArgs A)
-{
-  int r = blockIdx.x*blockDim.x + threadIdx.x;
-  if (r >= A.n) return;
-  const unsigned long long cell = A.key[r] >> 32;
-  if (cell >= A.ncell) return;
-  if (r > 0 && A.key[r - 1] >> 32 == cell) return;      /* not the first of its cell */
-  const unsigned nside = (unsigned) A.L.n;
-  const int i = (int) (cell % nside) + 1, j = (int) ((cell/nside) % nside) + 1;
-  const int k = DIM == 3 ? (int) (cell/((unsigned long long) nside*nside)) + 1 : 0;
-  const long idx = A.L.idx (i, j, k);
-  double s = 0.;
-  int m = r;
-  for (; m < A.n && A.key[m] >> 32 == cell; m++)
-    s += A.src[(unsigned) (A.key[m] & 0xFFFFFFFFull)];
-  const unsigned last = (unsigned) (A.key[m - 1] & 0xFFFFFFFFull);
-  if (A.deposit) A.deposit[idx] = s;
-  if (A.rad) A.rad[idx] = A.prad[last];
-#pragma unroll
-  for (int c = 0; c < DIM; c++)
-    if (A.urel[c]) A.urel[c][idx] = A.purel[c][last];
 }
 
 static bool c_identifier (const char * s)
@@ -164,14 +123,6 @@ int particulate_source_reserve (gfship_particulate_source * s)
     GFSHIP_HIP (hipMalloc (p, (size_t) pl->cap*(p == (void **) &s->cell ? sizeof (unsigned) : sizeof (double))));
   }
   s->cap = pl->cap;
-  return GFSHIP_OK;
-}
-
-int launch_particulate_source_constant (hipStream_t stream, int n, double value, double * out)
-{
-  const int block = 256, grid = (n + block - 1)/block;
-  hipLaunchKernelGGL (particulate_source_constant_kernel, dim3 (grid), dim3 (block), 0, stream, n, value, out);
-  GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
 
@@ -245,7 +196,7 @@ static int source_event (gfship_particulate_source * s, double * info)
 				(int) read.size (), read.data (), s->src)))
       return r;
   }
-  else if ((r = launch_particulate_source_constant (dom->stream, n, s->value, s->src)))
+  else if ((r = launch_fill (dom->stream, n, s->value, s->src)))
     return r;
   const unsigned long long ncell = (unsigned long long) ncells (L);
   if (fields && (r = coupling_reserve (pl, (size_t) n, 0, false))) return r;
@@ -262,7 +213,7 @@ static int source_event (gfship_particulate_source * s, double * info)
     GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, n, 0, bits,
 						   dom->stream));
     SourceCellArgs A;
-    A.L = L; A.n = n; A.key = pl->ckey2; A.ncell = ncell;
+    A.n = n; A.key = pl->ckey2; A.ncell = ncell;
     A.src = s->src; A.prad = s->prad;
     A.deposit = D ? D->lev[dom->depth] : nullptr;
     A.rad = R ? R->lev[dom->depth] : nullptr;
@@ -272,7 +223,8 @@ static int source_event (gfship_particulate_source * s, double * info)
     }
     with_bools ([&] (auto D3) {
       constexpr int DIM = decltype (D3)::value ? 3 : 2;
-      hipLaunchKernelGGL (particulate_source_cell_kernel<DIM>, dim3 (grid), dim3 (block), 0, dom->stream, A);
+      hipLaunchKernelGGL ((particulate_source_cell_kernel<DIM, false, BoxCells<DIM>>), dim3 (grid), dim3 (block), 0,
+			  dom->stream, BoxCells<DIM> { L }, A);
     }, dom->dim == 3);
     GFSHIP_HIP (hipGetLastError ());
   }

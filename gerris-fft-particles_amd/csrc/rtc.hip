@@ -249,7 +249,7 @@ int rtc_launch_source (RtcKernel * k, hipStream_t stream, int n, const Layout & 
 
 // the same function on a list of a tree (update_vol / update_mass with cell = the leaf of gfs_domain_locate
 // (pos, -1)): cell[o] is the index of the leaf in the concatenated levels.  Its level is the last one whose offset
-// is not beyond it (level_of, tree_particles.hip; the loop has constant bounds, so the offsets are read from the
+// is not beyond it (level_of, cell_sums.hpp; the loop has constant bounds, so the offsets are read from the
 // kernel arguments with constant indices), its integer coordinates come from its index in the dense (2^l + 2)^dim
 // level, and ftt_cell_pos is -0.5 + (i - 0.5)*2^-l, dyadic and exact.  The variables are arrays of all levels
 struct TreeSourceOffsets { int v[GFSHIP_MAXLEVEL + 2]; };

@@ -19,10 +19,13 @@
 // written from the reference) in tests/test_gpu_tree_sampler.py.
 //
 // GfsParticulate with forces on a tree (gfship_particulates_create_tree): the force arithmetic of
-// particles.hip on the locate / interpolate above, with gfs_center_gradient (src/fluid.c:434-475) of Du/Dt and of the
-// vorticity taken at the leaf through tree::center_gradient (tree.hpp) -- a coarser neighbour at x = 3/2, a neighbour
-// with children at x = 3/4.  Pinned on tests/tree_forces_reference.py in tests/test_gpu_tree_particulates.py.
+// particulate_forces.hpp, which the kernels of particles.hip call too, on the locate / interpolate above, with
+// gfs_center_gradient (src/fluid.c:434-475) of Du/Dt and of the vorticity taken at the leaf through
+// tree::center_gradient (tree.hpp) -- a coarser neighbour at x = 3/2, a neighbour with children at x = 3/4.  Pinned
+// on tests/tree_forces_reference.py in tests/test_gpu_tree_particulates.py.
 #include "particles.hpp"
+#include "particulate_forces.hpp"
+#include "cell_sums.hpp"
 #include "tree_particles.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -637,32 +640,32 @@ tree_particle_list_event_kernel (TreeSamp S, TreePartArgs A)
 }
 
 // ---------------------------------------------------------------------------------------------
-// GfsParticulate with forces on a tree (modules/particulatecommon.c:91-842): the arithmetic of
-// particulate_list_event_kernel (particles.hip) with the cell search, the interpolation and gfs_center_gradient of a
-// tree.  fluid_rho = 1. (a tree has no alpha), the viscosity is the constant of GfsSourceDiffusion {} U.
+// GfsParticulate with forces on a tree (modules/particulatecommon.c:91-842): the forces of particulate_forces.hpp with
+// the cell search, the interpolation and gfs_center_gradient of a tree.  fluid_rho = 1. (a tree has no alpha), the
+// viscosity is the constant of GfsSourceDiffusion {} U.
 // ---------------------------------------------------------------------------------------------
-enum { FORCE_INERTIAL = GFSHIP_FORCE_INERTIAL, FORCE_ADDEDMASS = GFSHIP_FORCE_ADDEDMASS,
-       FORCE_LIFT = GFSHIP_FORCE_LIFT, FORCE_DRAG = GFSHIP_FORCE_DRAG, FORCE_BUOY = GFSHIP_FORCE_BUOY };
-
-struct TreeParticulateArgs {
-  TreePartArgs P;
-  const unsigned * orig;
-  double * vel[3], * force[3], * mass;
-  const double * volume, * dia;
-  const double * uold[3];      // GFSHIP_TREE_UPREV ...
-  int nforces, forces[8];
-  double gravity[3], viscosity;
-  const double * coef[8];      // values of the GfsFunction of force f per slot; nullptr: the default
-  double * cin[6];             // Rep, Urelp, Vrelp, Wrelp, Pdia per slot; [5]: the Rep of GfsForceDrag in 2-D
-};
+struct TreeListArgs { TreePartArgs P; };
+struct TreeParticulateArgs : TreeListArgs, ParticleForceArgs {};      // uold: GFSHIP_TREE_UPREV ...
 
 struct DevValue {            // GFS_VALUEI (cell, v)
   const double * p;
   __device__ __forceinline__ double operator() (const Topo & T, Cell c) const { return p[T.gi (c)]; }
 };
 
-// the variables a GfsFunction of a GfsForceCoeff sees (:364-384,462-485,545-573), as particulate_coeff_inputs_kernel
-// writes them on the uniform box
+// the sources of particulate_forces.hpp on a tree: the gradients the kernel has filled, u[c2] at the leaf
+template <int DIM>
+struct TreeGradient {
+  const double (* g)[DIM];
+  __device__ __forceinline__ double operator() (int c, int c2) const { return g[c][c2]; }
+};
+struct TreeCellU {
+  const TreePartArgs & P; int g;
+  __device__ __forceinline__ double operator() (int c2) const { return P.u[c2][g]; }
+};
+
+// the variables a GfsFunction of a GfsForceCoeff sees: coefficient_inputs (particulate_forces.hpp) at the
+// particle's leaf
+// (particulate_coeff_inputs_kernel, particles.hip, is this kernel on a box)
 template <int DIM>
 __global__ void __launch_bounds__(256)
 tree_particulate_coeff_inputs_kernel (TreeSamp S, TreeParticulateArgs A)
@@ -675,30 +678,19 @@ tree_particulate_coeff_inputs_kernel (TreeSamp S, TreeParticulateArgs A)
   Leaf c0;
   if (!tree_locate<DIM> (S, p, c0)) return;
   const unsigned o = A.orig[q];
-  const double fluid_rho = 1.;
   Vars<DIM> uu;
 #pragma unroll
   for (int a = 0; a < DIM; a++) uu.p[a] = P.u[a];
   double fvel[DIM];
   tree_interpolate<DIM, DIM> (S, uu, c0, p, fvel);
-  double rel[3] = { 0. - A.vel[0][o], 0. - A.vel[1][o], 0. - A.vel[2][o] };
-#pragma unroll
-  for (int c = 0; c < DIM; c++)
-    rel[c] = fvel[c] - A.vel[c][o];
-  const double norm = sqrt (rel[0]*rel[0] + rel[1]*rel[1] + rel[2]*rel[2]);
-  const double dia = A.dia[o];
-  const double viscosity = A.viscosity == 0 ? 0.001 : A.viscosity;      /* :372-375, 461-464 */
-  A.cin[0][q] = norm*dia*fluid_rho/viscosity;
-  A.cin[1][q] = rel[0]; A.cin[2][q] = rel[1]; A.cin[3][q] = rel[2];
-  A.cin[4][q] = dia;
-  if (DIM == 2)      /* compute_drag_force takes the norm of the two components in 2-D (:549-556) */
-    A.cin[5][q] = sqrt (rel[0]*rel[0] + rel[1]*rel[1])*dia*fluid_rho/viscosity;
+  coefficient_inputs<DIM> (A, q, o, fvel, 1., ListViscosity { A });
 }
 
 // gfs_particulate_event (:768-842) in a gfs_particle_list_event (:980-1015)
 // ONFLUID: compute_forces_onfluid (:753-765) in source_particulate_event (:2199-2206), as in particles.hip: every
 // force of the list but GfsForceBuoy; `force' is written, and `mass' (compute_addedmass_force, :391); the particle
 // does not move and stays on the list; a particle without a leaf gets the zero force and keeps its mass
+// (particulate_list_event_kernel, particles.hip, is this kernel on a box)
 template <int DIM, bool ONFLUID = false>
 __global__ void __launch_bounds__(256)
 tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
@@ -731,19 +723,12 @@ tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
   double mass = A.mass[o];
   const double volume = A.volume[o];
   double pf[3] = { 0., 0., 0. };
-  // every force is a function of the state at the start of the event: what several of them need -- the fluid
-  // velocity at the particle, Du/Dt, the gradients of the velocity at the leaf -- is evaluated once (the reference
-  // re-evaluates the same expressions per force: same bits)
-  bool need_fvel = false, need_dudt = false, need_grad = false;
-  for (int f = 0; f < A.nforces; f++) {
-    if (ONFLUID && A.forces[f] == FORCE_BUOY)
-      continue;
-    need_fvel = need_fvel || A.forces[f] != FORCE_BUOY;
-    need_dudt = need_dudt || A.forces[f] == FORCE_INERTIAL || A.forces[f] == FORCE_ADDEDMASS;
-    need_grad = need_grad || A.forces[f] == FORCE_INERTIAL || A.forces[f] == FORCE_ADDEDMASS || A.forces[f] == FORCE_LIFT;
-  }
+  // what several forces need -- the fluid velocity at the particle, Du/Dt, the gradients of the velocity at the
+  // leaf -- is evaluated once
+  ForceNeeds need;
+  force_needs<ONFLUID> (A, need);
   double fvel[3] = { 0., 0., 0. }, fveln[3] = { 0., 0., 0. }, dudt[3] = { 0., 0., 0. };
-  if (need_dudt) {
+  if (need.dudt) {
     // U and Un at the particle in one pass over the corner rows of the leaf
     Vars<2*DIM> uu;
 #pragma unroll
@@ -753,7 +738,7 @@ tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
 #pragma unroll
     for (int a = 0; a < DIM; a++) { fvel[a] = r[a]; fveln[a] = r[DIM + a]; }
   }
-  else if (need_fvel) {
+  else if (need.fvel) {
     Vars<DIM> uu;
 #pragma unroll
     for (int a = 0; a < DIM; a++) uu.p[a] = P.u[a];
@@ -770,7 +755,7 @@ tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
 #pragma unroll
     for (int c2 = 0; c2 < DIM; c2++)
       grad[c][c2] = 0.;
-  if (need_grad) {
+  if (need.grad) {
     // (no unroll request on the loop over the rows: the stencil code holds loops over the children of a face, the
     // early unroll pass cannot take the loop around them and a later one does -- the build log shows no scratch,
     // DESIGN.md 11.28; spelling the rows out by hand sends the tables of the tree to scratch)
@@ -781,96 +766,10 @@ tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
 	grad[c][c2] = tree::center_gradient (S.T, cell, c2, uc);
     }
   }
-  if (need_dudt && dt > 0.) {      // compute_inertial_force, :285-336
-#pragma unroll
-    for (int c = 0; c < DIM; c++)
-      dudt[c] = fluid_rho*(fvel[c] - fveln[c])/dt;
-#pragma unroll
-    for (int c = 0; c < DIM; c++)
-#pragma unroll
-      for (int c2 = 0; c2 < DIM; c2++)
-	dudt[c] += fluid_rho*grad[c][c2]*P.u[c2][c0.g]/size;
-  }
-  for (int f = 0; f < A.nforces; f++) {
-    double force[3] = { 0., 0., 0. };
-    if (ONFLUID && A.forces[f] == FORCE_BUOY)      /* :756 */
-      continue;
-    switch (A.forces[f]) {
-    case FORCE_INERTIAL:
-      force[0] = dudt[0]; force[1] = dudt[1]; force[2] = dudt[2];
-      break;
-    case FORCE_ADDEDMASS: {     // compute_addedmass_force, :363-427
-      force[0] = dudt[0]; force[1] = dudt[1]; force[2] = dudt[2];
-      const double cm = A.coef[f] ? A.coef[f][q] : 0.5;
-#pragma unroll
-      for (int c = 0; c < DIM; c++)
-	force[c] *= cm;
-      mass += fluid_rho*volume*cm;      /* :391, in compute_forces_onfluid too */
-      break;
-    }
-    case FORCE_LIFT: {          // compute_lift_force, :455-524; vorticity_vector, :146-168
-      double rel[3] = { 0., 0., 0. }, vort[3];
-#pragma unroll
-      for (int c = 0; c < DIM; c++)
-	rel[c] = fvel[c] - vel[c];
-      if (DIM == 2) {
-	vort[0] = 0.; vort[1] = 0.;
-	vort[2] = (grad[1][0] - grad[0][1])/size;
-      }
-      else {
-	vort[0] = (grad[DIM - 1][1] - grad[1][DIM - 1])/size;
-	vort[1] = (grad[0][DIM - 1] - grad[DIM - 1][0])/size;
-	vort[2] = (grad[1][0] - grad[0][1])/size;
-      }
-      const double cl = A.coef[f] ? A.coef[f][q] : 0.5;
-      if (DIM == 2) {
-	force[0] = fluid_rho*cl*rel[1]*vort[2];
-	force[1] = -fluid_rho*cl*rel[0]*vort[2];
-      }
-      else {
-	force[0] = fluid_rho*cl*(rel[1]*vort[2] - rel[2]*vort[1]);
-	force[1] = fluid_rho*cl*(rel[2]*vort[0] - rel[0]*vort[2]);
-	force[2] = fluid_rho*cl*(rel[0]*vort[1] - rel[1]*vort[0]);
-      }
-      break;
-    }
-    case FORCE_DRAG: {          // compute_drag_force, :527-588
-      double rel[3] = { 0., 0., 0. };
-#pragma unroll
-      for (int c = 0; c < DIM; c++)
-	rel[c] = fvel[c] - vel[c];
-      const double dia = A.dia[o];
-      const double norm = DIM == 3 ? sqrt (rel[0]*rel[0] + rel[1]*rel[1] + rel[2]*rel[2]) :
-	sqrt (rel[0]*rel[0] + rel[1]*rel[1]);
-      if (A.viscosity == 0)       /* :561-562: no drag without viscosity */
-	break;
-      const double Re = norm*dia*fluid_rho/A.viscosity;
-      double cd;
-      if (A.coef[f])
-	cd = A.coef[f][q];
-      else if (Re < 1e-8)
-	break;
-      else if (Re < 50.0)
-	cd = 16.*(1. + 0.15*sqrt (Re))/Re;
-      else
-	cd = 48.*(1. - 2.21/sqrt (Re))/Re;
-#pragma unroll
-      for (int c = 0; c < DIM; c++)
-	force[c] += 3./(4.*dia)*cd*norm*rel[c]*fluid_rho;
-      break;
-    }
-    case FORCE_BUOY:            // compute_buoyancy_force, :619-653
-#pragma unroll
-      for (int c = 0; c < DIM; c++)
-	force[c] += (mass/volume - fluid_rho)*A.gravity[c];
-      break;
-    }
-    // compute_forces, :738-752
-#pragma unroll
-    for (int c = 0; c < DIM; c++)
-      pf[c] = force[c]*volume + pf[c];
-    if (DIM == 2) pf[2] = 0.;
-  }
+  const TreeGradient<DIM> G = { grad };
+  if (need.dudt)
+    inertial_force<DIM> (fluid_rho, dt, size, fvel, Value3 { fveln }, G, TreeCellU { P, c0.g }, dudt);
+  particulate_forces<DIM, ONFLUID> (A, q, o, fluid_rho, ListViscosity { A }, size, G, fvel, dudt, vel, volume, mass, pf);
   if constexpr (ONFLUID) {
 #pragma unroll
     for (int c = 0; c < 3; c++)
@@ -878,12 +777,7 @@ tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
     A.mass[o] = mass;
     return;
   }
-#pragma unroll
-  for (int c = 0; c < DIM; c++) {      /* :828-837 */
-    p[c] += vel[c]*dt/2.;
-    vel[c] += pf[c]*dt/mass;
-    p[c] += vel[c]*dt/2.;
-  }
+  particulate_advance<DIM> (p, vel, pf, dt, mass);
 #pragma unroll
   for (int c = 0; c < 3; c++) {
     A.vel[c][o] = vel[c];
@@ -901,6 +795,7 @@ tree_particulate_list_event_kernel (TreeSamp S, TreeParticulateArgs A)
 }
 
 // key of the sort: the leaf that holds the particle (its index in the concatenated levels), dead or outside last
+// (particle_keys_kernel, particles.hip, is this kernel on a box)
 template <int DIM>
 __global__ void __launch_bounds__(256)
 tree_particle_keys_kernel (TreeSamp S, int n, const double * __restrict__ x, const double * __restrict__ y,
@@ -921,25 +816,11 @@ tree_particle_keys_kernel (TreeSamp S, int n, const double * __restrict__ x, con
 }
 
 // ---------------------------------------------------------------------------------------------
-// Two-way coupling on a tree (GfsParticulateField, GfsSourceParticulate): the records, the sort and
-// the serial sums of coupling.hip, with the leaf of a tree -- its index in the concatenated levels, Topo::gi -- as
-// the cell of a key, the cellvol of the leaf's own level, and the pruned descent as a walk of the tree itself.
+// Two-way coupling on a tree (GfsParticulateField, GfsSourceParticulate): the records and the sort
+// of coupling.hip and the serial sums of cell_sums.hpp on TreeCells -- the leaf of a tree, its index in the
+// concatenated levels (Topo::gi), as the cell of a key, the cellvol of the leaf's own level -- and the pruned descent
+// as a walk of the tree itself.
 // ---------------------------------------------------------------------------------------------
-
-// the level of cell g of the concatenated levels
-__device__ __forceinline__ int level_of (const Topo & T, unsigned g)
-{
-  int l = 0;
-  while (l < T.depth && (int) g >= T.off[l + 1]) l++;
-  return l;
-}
-
-template <int DIM>
-__device__ __forceinline__ double level_cellvol (int l)      /* ftt_cell_volume */
-{
-  const double h = 1./(double) (1 << l);
-  return DIM == 3 ? h*h*h : h*h;
-}
 
 // gfs_cell_reset on the interior leaves of every level, for up to three variables
 __global__ void __launch_bounds__(256)
@@ -953,22 +834,9 @@ tree_reset_leaves_kernel (Topo T, const Cell * __restrict__ cells, int n, double
   if (a2) a2[g] = 0.;
 }
 
-__global__ void __launch_bounds__(256)
-tree_where_kernel (int n, const unsigned * __restrict__ orig, unsigned * __restrict__ where)
-{
-  const int q = blockIdx.x*blockDim.x + threadIdx.x;
-  if (q < n) where[orig[q]] = (unsigned) q;
-}
-
-__global__ void __launch_bounds__(256)
-tree_spread_constant_kernel (long nrec, double value, double * __restrict__ out)
-{
-  const long r = (long) blockIdx.x*blockDim.x + threadIdx.x;
-  if (r < nrec) out[r] = value;
-}
-
 // key of the leaf that holds each particle, (leaf << 32 | creation slot); pad (leaf = number of cells of the tree)
 // for the particles that are off the list or have no leaf (:1949-1950)
+// (field_keys_kernel, coupling.hip, is this kernel on a box)
 template <int DIM>
 __global__ void __launch_bounds__(256)
 tree_field_keys_kernel (TreeSamp S, int n, const double * __restrict__ x, const double * __restrict__ y,
@@ -985,24 +853,6 @@ tree_field_keys_kernel (TreeSamp S, int n, const double * __restrict__ x, const 
       k = (unsigned long long) c.g;
   }
   key[q] = k << 32 | orig[q];
-}
-
-// voidfraction_from_particles (:1929-1932) for the particles of one leaf, in list order
-template <int DIM>
-__global__ void __launch_bounds__(256)
-tree_field_sum_kernel (Topo T, int n, const unsigned long long * __restrict__ key, unsigned long long ncell,
-		       const double * __restrict__ volume, double * __restrict__ v)
-{
-  const int r = blockIdx.x*blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  const unsigned long long cell = key[r] >> 32;
-  if (cell >= ncell) return;
-  if (r > 0 && key[r - 1] >> 32 == cell) return;      /* not the first of its leaf */
-  const double cellvol = level_cellvol<DIM> (level_of (T, (unsigned) cell));
-  double s = v[cell];
-  for (int m = r; m < n && key[m] >> 32 == cell; m++)
-    s += volume[(unsigned) (key[m] & 0xFFFFFFFFull)]/cellvol;
-  v[cell] = s;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1022,6 +872,7 @@ struct TreeSourceGatherArgs {
 
 // update_vol / update_mass (:2806-2824, :2964-2982) up to the call of the function: gfs_domain_locate (pos, -1), the
 // radius, gfs_interpolate of the velocity and the relative velocity of one particle, stored at its creation slot
+// (particulate_source_gather_kernel, particles.hip, is this kernel on a box)
 template <int DIM>
 __global__ void __launch_bounds__(256)
 tree_particulate_source_gather_kernel (TreeSamp S, TreeSourceGatherArgs A)
@@ -1057,36 +908,6 @@ tree_particulate_source_reset_kernel (TreeSourceResetCells C, double * __restric
 #pragma unroll
   for (int m = 0; m < 9; m++)
     if (t == m && m < C.n) a[C.g[m]] = 0.;
-}
-
-struct TreeSourceCellArgs {
-  int n;
-  const unsigned long long * key;
-  unsigned long long ncell;
-  const double * src, * prad, * purel[3];
-  double * deposit, * rad, * urel[3];      // nullptr: not written
-};
-
-// the records of one leaf in list order: deposit += source onto what the leaf HOLDS (:2830, :2989: nothing has reset
-// it below level 1), Rad, Urelp ... of the last one (:2812-2824)
-__global__ void __launch_bounds__(256)
-tree_particulate_source_cell_kernel (TreeSourceCellArgs A)
-{
-  const int r = blockIdx.x*blockDim.x + threadIdx.x;
-  if (r >= A.n) return;
-  const unsigned long long cell = A.key[r] >> 32;
-  if (cell >= A.ncell) return;
-  if (r > 0 && A.key[r - 1] >> 32 == cell) return;      /* not the first of its leaf */
-  double s = A.deposit ? A.deposit[cell] : 0.;
-  int m = r;
-  for (; m < A.n && A.key[m] >> 32 == cell; m++)
-    s += A.src[(unsigned) (A.key[m] & 0xFFFFFFFFull)];
-  const unsigned last = (unsigned) (A.key[m - 1] & 0xFFFFFFFFull);
-  if (A.deposit) A.deposit[cell] = s;
-  if (A.rad) A.rad[cell] = A.prad[last];
-  if (A.urel[0]) A.urel[0][cell] = A.purel[0][last];
-  if (A.urel[1]) A.urel[1][cell] = A.purel[1][last];
-  if (A.urel[2]) A.urel[2][cell] = A.purel[2][last];
 }
 
 struct TreeSpreadArgs {
@@ -1185,57 +1006,6 @@ tree_spread_emit_kernel (TreeSamp S, TreeSpreadArgs A)
     A.key[base + j] = A.pad << 32 | 0xFFFFFFFFull;
 }
 
-// step 3: kernel_volume (:2108-2119) over the leaves of each particle in traversal order, then :2216
-template <int DIM>
-__global__ void __launch_bounds__(256)
-tree_spread_correction_kernel (Topo T, int nchunk, int stride, const int * __restrict__ cnt,
-			       const unsigned long long * __restrict__ key, const double * __restrict__ K,
-			       double * __restrict__ corr)
-{
-  const int t = blockIdx.x*blockDim.x + threadIdx.x;
-  if (t >= nchunk) return;
-  double volume = 0., correction = 0.;
-  const size_t base = (size_t) t*stride;
-  for (int j = 0; j < cnt[t]; j++) {
-    const double cellvol = level_cellvol<DIM> (level_of (T, (unsigned) (key[base + j] >> 32)));
-    volume += cellvol;
-    correction += K[base + j]*cellvol;
-  }
-  correction /= volume;      /* no leaf: 0./0., which is not > 1.e-10 -- and there is nothing to add to */
-  corr[t] = correction;
-}
-
-// step 4: diffuse_force (:2158-2175) for the records of one leaf, in list order; liq_rho = 1. (no alpha on a tree)
-template <int DIM>
-__global__ void __launch_bounds__(256)
-tree_spread_sum_kernel (Topo T, long nrec, const unsigned long long * __restrict__ key, unsigned long long ncell,
-			const double * __restrict__ K, int o0, const double * __restrict__ corr,
-			const double * __restrict__ fx, const double * __restrict__ fy, const double * __restrict__ fz,
-			double * __restrict__ Fx, double * __restrict__ Fy, double * __restrict__ Fz)
-{
-  const long r = (long) blockIdx.x*blockDim.x + threadIdx.x;
-  if (r >= nrec) return;
-  const unsigned long long cell = key[r] >> 32;
-  if (cell >= ncell) return;
-  if (r > 0 && key[r - 1] >> 32 == cell) return;
-  const double cellvol = level_cellvol<DIM> (level_of (T, (unsigned) cell));
-  const double liq_rho = 1.;
-  double F[3] = { Fx[cell], Fy[cell], DIM == 3 ? Fz[cell] : 0. };
-  for (long m = r; m < nrec && key[m] >> 32 == cell; m++) {
-    const unsigned o = (unsigned) (key[m] & 0xFFFFFFFFull);
-    const double correction = corr[o - (unsigned) o0];
-    if (correction > 1.e-10) {
-      const double k = K[m];
-      F[0] -= fx[o]/liq_rho/cellvol*k/correction;
-      F[1] -= fy[o]/liq_rho/cellvol*k/correction;
-      if (DIM == 3) F[2] -= fz[o]/liq_rho/cellvol*k/correction;
-    }
-  }
-  Fx[cell] = F[0];
-  Fy[cell] = F[1];
-  if (DIM == 3) Fz[cell] = F[2];
-}
-
 // record slots per particle: the bound of kernel_stride (coupling.hip) per level -- the centres of the leaves of
 // level l that pass cond_kernel lie within rho_l = rkernel + (h_l/2) sqrt (dim) of the particle along every axis and
 // are h_l apart -- summed over the levels that hold interior leaves; on a uniform tree the stride of the box
@@ -1322,60 +1092,26 @@ static int tree_particulate_event (gfship_particles * pl, bool onfluid)
     P.pos[c] = pl->pos[c];
     P.old[c] = pl->old[c];
     P.u[c] = c < dim ? tree_variable (pl->tree, uvar[c]) : nullptr;
-    A.vel[c] = pl->vel[c];
-    A.force[c] = pl->force[c];
     A.uold[c] = c < dim ? V.uprev[c] : nullptr;
-    A.gravity[c] = pl->gravity[c];
   }
   P.alive = pl->alive;
   P.dt = V.dt;
-  A.orig = pl->orig;
-  A.mass = pl->mass; A.volume = pl->volume; A.dia = pl->dia;
-  A.nforces = pl->nforces;
-  bool any = false, reads_un = false;
-  for (int f = 0; f < 8; f++) {
-    A.forces[f] = pl->forces[f];
-    A.coef[f] = nullptr;
-    if (f < pl->nforces && pl->coef_fn[f]) any = true;
-    if (f < pl->nforces && (pl->forces[f] == GFSHIP_FORCE_INERTIAL || pl->forces[f] == GFSHIP_FORCE_ADDEDMASS))
+  particulate_force_args (pl, A);
+  bool reads_un = false;
+  for (int f = 0; f < pl->nforces; f++)
+    if (pl->forces[f] == GFSHIP_FORCE_INERTIAL || pl->forces[f] == GFSHIP_FORCE_ADDEDMASS)
       reads_un = true;
-  }
   GFSHIP_CHECK (!reads_un || V.uprev[0], GFSHIP_EINVAL, "the tree has no Un, Vn, Wn (gfship_particles_set_forces)");
   A.viscosity = V.viscosity;
-  for (int q = 0; q < 6; q++) A.cin[q] = nullptr;
   const int block = 256, grid = (pl->n + block - 1)/block;
   const TreeSamp TS = tree_samp (V, S);
-  if (any) {
-    /* the GfsFunction coefficients: inputs of every particle, then one compiled kernel per function */
-    if (pl->coef_cap < pl->cap) {
-      for (int q = 0; q < 6; q++) {
-	if (pl->cin[q]) GFSHIP_HIP (hipFree (pl->cin[q]));
-	pl->cin[q] = nullptr;
-	GFSHIP_HIP (hipMalloc ((void **) &pl->cin[q], (size_t) pl->cap*sizeof (double)));
-      }
-      for (int f = 0; f < 8; f++) {
-	if (pl->coef[f]) GFSHIP_HIP (hipFree (pl->coef[f]));
-	pl->coef[f] = nullptr;
-      }
-      pl->coef_cap = pl->cap;
-    }
-    for (int q = 0; q < 6; q++) A.cin[q] = pl->cin[q];
+  r = particulate_coefficients (pl, A, V.stream, V.t, [&] {
     if (dim == 3)
       hipLaunchKernelGGL (tree_particulate_coeff_inputs_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
     else
       hipLaunchKernelGGL (tree_particulate_coeff_inputs_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
-    GFSHIP_HIP (hipGetLastError ());
-    const double * rel[3] = { pl->cin[1], pl->cin[2], pl->cin[3] };
-    for (int f = 0; f < pl->nforces; f++)
-      if (pl->coef_fn[f]) {
-	if (!pl->coef[f])
-	  GFSHIP_HIP (hipMalloc ((void **) &pl->coef[f], (size_t) pl->coef_cap*sizeof (double)));
-	const double * rep = dim == 2 && pl->forces[f] == GFSHIP_FORCE_DRAG ? pl->cin[5] : pl->cin[0];
-	r = rtc_launch_coefficient (pl->coef_fn[f], V.stream, pl->n, P.alive, rep, rel, pl->cin[4], V.t, pl->coef[f]);
-	if (r) return r;
-	A.coef[f] = pl->coef[f];
-      }
-  }
+  });
+  if (r) return r;
   if (onfluid) {
     if (dim == 3)
       hipLaunchKernelGGL ((tree_particulate_list_event_kernel<3, true>), dim3 (grid), dim3 (block), 0, V.stream, TS, A);
@@ -1494,7 +1230,7 @@ int tree_particulate_source_event (gfship_particulate_source * s, double * info)
 				     (int) read.size (), read.data (), s->src)))
       return r;
   }
-  else if ((r = launch_particulate_source_constant (V.stream, n, s->value, s->src)))
+  else if ((r = launch_fill (V.stream, n, s->value, s->src)))
     return r;
   const unsigned long long ncell = (unsigned long long) V.ncell;
   if (fields && (r = coupling_reserve (pl, (size_t) n, 0, false))) return r;
@@ -1507,7 +1243,7 @@ int tree_particulate_source_event (gfship_particulate_source * s, double * info)
     if ((r = coupling_sort_reserve (pl, need))) return r;
     size_t tmp_bytes = pl->sort_tmp_bytes;
     GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, n, 0, bits, V.stream));
-    TreeSourceCellArgs A;
+    SourceCellArgs A;
     A.n = n; A.key = pl->ckey2; A.ncell = ncell;
     A.src = s->src; A.prad = s->prad;
     A.deposit = D; A.rad = R;
@@ -1515,7 +1251,12 @@ int tree_particulate_source_event (gfship_particulate_source * s, double * info)
       A.purel[c] = s->purel[c];
       A.urel[c] = c < dim ? U[c] : nullptr;
     }
-    hipLaunchKernelGGL (tree_particulate_source_cell_kernel, dim3 (grid), dim3 (block), 0, V.stream, A);
+    if (dim == 3)
+      hipLaunchKernelGGL ((particulate_source_cell_kernel<3, true, TreeCells<3>>), dim3 (grid), dim3 (block), 0, V.stream,
+			  TreeCells<3> { V.D }, A);
+    else
+      hipLaunchKernelGGL ((particulate_source_cell_kernel<2, true, TreeCells<2>>), dim3 (grid), dim3 (block), 0, V.stream,
+			  TreeCells<2> { V.D }, A);
     GFSHIP_HIP (hipGetLastError ());
   }
   if (info) {
@@ -1668,11 +1409,11 @@ int gfship_tree_particulate_field (gfship_particles * pl, int var)
   GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, pl->n, 0, bits,
 						 V.stream));
   if (V.H.dim == 3)
-    hipLaunchKernelGGL (tree_field_sum_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, V.D, pl->n, pl->ckey2, ncell,
-			pl->volume, a);
+    hipLaunchKernelGGL ((field_sum_kernel<3, TreeCells<3>>), dim3 (grid), dim3 (block), 0, V.stream, TreeCells<3> { V.D },
+			pl->n, pl->ckey2, ncell, pl->volume, a);
   else
-    hipLaunchKernelGGL (tree_field_sum_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, V.D, pl->n, pl->ckey2, ncell,
-			pl->volume, a);
+    hipLaunchKernelGGL ((field_sum_kernel<2, TreeCells<2>>), dim3 (grid), dim3 (block), 0, V.stream, TreeCells<2> { V.D },
+			pl->n, pl->ckey2, ncell, pl->volume, a);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
@@ -1742,9 +1483,7 @@ int gfship_tree_particles_spread_forces (gfship_particles * pl)
   if ((r = coupling_reserve (pl, (size_t) per_chunk*stride, (size_t) per_chunk, true))) return r;
   const unsigned long long ncell = (unsigned long long) V.ncell;
   const int bits = coupling_key_bits (ncell);
-  hipLaunchKernelGGL (tree_where_kernel, dim3 ((pl->n + block - 1)/block), dim3 (block), 0, V.stream, pl->n, pl->orig,
-		      pl->where);
-  GFSHIP_HIP (hipGetLastError ());
+  if ((r = launch_where (pl))) return r;
   GFSHIP_HIP (hipMemsetAsync (pl->cflag, 0, sizeof (int), V.stream));
   const TreeSamp TS = tree_samp (V, S);
   TreeSpreadArgs A;
@@ -1768,17 +1507,14 @@ int gfship_tree_particles_spread_forces (gfship_particles * pl)
 				   V.t, pl->cval)))
 	return r;
     }
-    else {
-      hipLaunchKernelGGL (tree_spread_constant_kernel, dim3 (rgrid), dim3 (block), 0, V.stream, nrec, pl->kernel_value,
-			  pl->cval);
-      GFSHIP_HIP (hipGetLastError ());
-    }
+    else if ((r = launch_fill (V.stream, nrec, pl->kernel_value, pl->cval)))
+      return r;
     if (dim == 3)
-      hipLaunchKernelGGL (tree_spread_correction_kernel<3>, dim3 (pgrid), dim3 (block), 0, V.stream, V.D, nchunk, stride,
-			  pl->ccnt, pl->ckey, pl->cval, pl->ccorr);
+      hipLaunchKernelGGL ((spread_correction_kernel<3, TreeCells<3>>), dim3 (pgrid), dim3 (block), 0, V.stream,
+			  TreeCells<3> { V.D }, nchunk, stride, pl->ccnt, pl->ckey, pl->cval, pl->ccorr);
     else
-      hipLaunchKernelGGL (tree_spread_correction_kernel<2>, dim3 (pgrid), dim3 (block), 0, V.stream, V.D, nchunk, stride,
-			  pl->ccnt, pl->ckey, pl->cval, pl->ccorr);
+      hipLaunchKernelGGL ((spread_correction_kernel<2, TreeCells<2>>), dim3 (pgrid), dim3 (block), 0, V.stream,
+			  TreeCells<2> { V.D }, nchunk, stride, pl->ccnt, pl->ckey, pl->cval, pl->ccorr);
     GFSHIP_HIP (hipGetLastError ());
     size_t need = 0;
     GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (nullptr, need, pl->ckey, pl->ckey2, pl->cval, pl->cval2, nrec, 0,
@@ -1788,11 +1524,13 @@ int gfship_tree_particles_spread_forces (gfship_particles * pl)
     GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, pl->cval, pl->cval2,
 						    nrec, 0, bits, V.stream));
     if (dim == 3)
-      hipLaunchKernelGGL (tree_spread_sum_kernel<3>, dim3 (rgrid), dim3 (block), 0, V.stream, V.D, nrec, pl->ckey2, ncell,
-			  pl->cval2, o0, pl->ccorr, pl->force[0], pl->force[1], pl->force[2], Fa[0], Fa[1], Fa[2]);
+      hipLaunchKernelGGL ((spread_sum_kernel<3, false, TreeCells<3>>), dim3 (rgrid), dim3 (block), 0, V.stream,
+			  TreeCells<3> { V.D }, nrec, pl->ckey2, ncell, pl->cval2, o0, pl->ccorr, pl->force[0], pl->force[1],
+			  pl->force[2], nullptr, Fa[0], Fa[1], Fa[2]);
     else
-      hipLaunchKernelGGL (tree_spread_sum_kernel<2>, dim3 (rgrid), dim3 (block), 0, V.stream, V.D, nrec, pl->ckey2, ncell,
-			  pl->cval2, o0, pl->ccorr, pl->force[0], pl->force[1], pl->force[2], Fa[0], Fa[1], Fa[2]);
+      hipLaunchKernelGGL ((spread_sum_kernel<2, false, TreeCells<2>>), dim3 (rgrid), dim3 (block), 0, V.stream,
+			  TreeCells<2> { V.D }, nrec, pl->ckey2, ncell, pl->cval2, o0, pl->ccorr, pl->force[0], pl->force[1],
+			  pl->force[2], nullptr, Fa[0], Fa[1], Fa[2]);
     GFSHIP_HIP (hipGetLastError ());
   }
   int flag = 0;

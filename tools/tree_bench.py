@@ -15,7 +15,8 @@ by gfship_particles_count (a stream synchronise); Mparticle-steps/s of the event
 of the sampler.
 --particulates N: the same for a list of N GfsParticulate with the five forces and their default coefficients (the
 particles and forces of tools/particles_bench.py --particulates; the drag acts where nu is given): the event of
-tree_particulate_list_event_kernel and, after it, the copy of U, V, W into Un, Vn, Wn.
+tree_particulate_list_event_kernel (the forces of csrc/particulate_forces.hpp) and, after it, the copy of U, V, W
+into Un, Vn, Wn.
 --two-way N: the two-way coupling of a tree for the list of --particulates N, rkernel = 1.5 h of the
 finest leaves, the polynomial kernel: one call to warm up, then the mean of 10 and the least and the largest of them,
 each ended by a stream synchronise, of Tree.particulate_field, Tree.forces_on_fluid, Tree.spread_forces and, last (it
