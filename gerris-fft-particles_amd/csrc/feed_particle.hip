@@ -1,0 +1,293 @@
+// feed_particle.hip -- particles join a list during a run: GfsFeedParticle (modules/particulatecommon.c:2375-2647)
+// on a list of particulates of a uniform box, and idlast of a GfsParticleList.
+//
+// The event of the reference (gfs_feed_particle_event, :2404-2418) calls feed_particulate (:2377-2402) once per
+// candidate: the position from three functions without a cell, gfs_domain_locate (no cell: the candidate is
+// dropped), the velocity of the fluid interpolated there, the mass and the volume from two functions at the cell,
+// then add_particulate (:1237-1276): nothing below a mass of 1.e-20, else a new object at the END of the list
+// with id = ++idlast.  The positions are the host's business (functions with state, evaluated in order); what
+// follows is independent per candidate except for the id, which counts the accepted candidates before it.  Here:
+//   1. one thread per candidate: locate, interpolate, and the slot of a new object (feed_gather_kernel,
+//      particles.hip: the locate and the interpolate of the event kernels);
+//   2. the two functions of every candidate with a cell: a constant, or the kernel hipRTC compiled around the
+//      text (rtc.hip), written straight into the mass and the volume of the new slots;
+//   3. the ids, an ordered prefix count of the accept flags in three passes: per block of 256 candidates the
+//      number accepted (ballot and popcount per wave, the waves added in LDS), one block scans those counts and
+//      moves idlast, then every candidate takes idlast + 1 + (accepted before it) and its flag; an accepted one
+//      also gets its diameter (:552) and rb (:2091).  No atomic counter: the ids do not depend on the scheduling
+//      nor on the shape of the launch.
+// Slots: the np candidates take the np slots after those in use, in candidate order; a refused candidate is a
+// dead slot (alive = 0), which every reader of the list already skips.  The download order (creation slots) is
+// therefore the reference's list order.  idlast lives on the device; only its getter reads it back.
+//
+// pow: the diameter and rb of a new particle are values of the device's pow in the reference's expressions, as
+// after a volume event (particulate_sources.hip); everything else is the reference's arithmetic.
+#include "particles.hpp"
+#include <cctype>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace gfship {
+
+constexpr int FEED_BLOCK = 256, FEED_WAVES = FEED_BLOCK/64;
+
+// add_particulate, :1244: `if (mass < 1.e-20) return;' -- a NaN passes, as in C
+__device__ __forceinline__ bool feed_accept (int i, int np, const unsigned * __restrict__ cell,
+					     const double * __restrict__ mass)
+{
+  return i < np && cell[i] != PSOURCE_NO_CELL && !(mass[i] < 1.e-20);
+}
+
+// pass 1 of the ids: accepted candidates per block
+__global__ void __launch_bounds__(FEED_BLOCK)
+feed_count_kernel (int np, const unsigned * __restrict__ cell, const double * __restrict__ mass,
+		   unsigned * __restrict__ block)
+{
+  __shared__ unsigned wave[FEED_WAVES];
+  const int i = blockIdx.x*FEED_BLOCK + threadIdx.x;
+  const unsigned long long m = __ballot (feed_accept (i, np, cell, mass));
+  if ((threadIdx.x & 63) == 0) wave[threadIdx.x >> 6] = (unsigned) __popcll (m);
+  __syncthreads ();
+  if (threadIdx.x == 0) {
+    unsigned s = 0;
+#pragma unroll
+    for (int w = 0; w < FEED_WAVES; w++) s += wave[w];
+    block[blockIdx.x] = s;
+  }
+}
+
+// pass 2: one block turns the counts into the id before the first accepted candidate of every block (idlast +
+// the accepted candidates of the blocks before it), FEED_BLOCK counts at a time, and moves idlast
+__global__ void __launch_bounds__(FEED_BLOCK)
+feed_scan_kernel (int nblocks, unsigned * __restrict__ block, unsigned * __restrict__ idlast)
+{
+  __shared__ unsigned wave[FEED_WAVES];
+  __shared__ unsigned carry;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (threadIdx.x == 0) carry = *idlast;
+  __syncthreads ();
+  for (int b0 = 0; b0 < nblocks; b0 += FEED_BLOCK) {
+    const int b = b0 + threadIdx.x;
+    const unsigned v = b < nblocks ? block[b] : 0u;
+    unsigned s = v;      /* inclusive scan of the wave */
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const unsigned up = __shfl_up (s, d, 64);
+      if (lane >= d) s += up;
+    }
+    if (lane == 63) wave[w] = s;
+    __syncthreads ();
+    unsigned before = carry;
+#pragma unroll
+    for (int q = 0; q < FEED_WAVES; q++)
+      if (q < w) before += wave[q];
+    if (b < nblocks) block[b] = before + s - v;
+    __syncthreads ();
+    if (threadIdx.x == FEED_BLOCK - 1) carry = before + s;
+    __syncthreads ();
+  }
+  if (threadIdx.x == 0) *idlast = carry;
+}
+
+// pass 3: id and flag of every candidate; diameter and rb of an accepted one (compute_drag_force, :552,
+// distance_normalization, :2091), zeros for a refused one (its functions may not have been evaluated)
+__global__ void __launch_bounds__(FEED_BLOCK)
+feed_scatter_kernel (int np, const unsigned * __restrict__ cell, const unsigned * __restrict__ block,
+		     double * __restrict__ mass, double * __restrict__ volume, double * __restrict__ dia,
+		     double * __restrict__ rb, unsigned * __restrict__ id, unsigned char * __restrict__ alive)
+{
+  __shared__ unsigned wave[FEED_WAVES];
+  const int i = blockIdx.x*FEED_BLOCK + threadIdx.x;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const bool ok = feed_accept (i, np, cell, mass);
+  const unsigned long long m = __ballot (ok);
+  if (lane == 0) wave[w] = (unsigned) __popcll (m);
+  __syncthreads ();
+  if (i >= np) return;
+  unsigned before = block[blockIdx.x];
+#pragma unroll
+  for (int q = 0; q < FEED_WAVES; q++)
+    if (q < w) before += wave[q];
+  before += (unsigned) __popcll (m & ((1ull << lane) - 1ull));
+  alive[i] = ok ? 1 : 0;
+  if (ok) {
+    const double v = volume[i];
+    id[i] = before + 1u;
+    dia[i] = 2.*pow (3.0*v/4.0/M_PI, 1./3.);
+    rb[i] = pow (3.*v/(4.*M_PI), 1./3.);
+  }
+  else {
+    id[i] = 0u;
+    mass[i] = volume[i] = dia[i] = rb[i] = 0.;
+  }
+}
+
+// what gfship_feed_particle_create and the event refuse: the refusals of a GfsSourceParticulateVol
+// (source_check, particulate_sources.hip)
+static int feed_check (gfship_particles * pl)
+{
+  const char * what = "GfsFeedParticle";
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_NO_TREE_LIST (pl, what);
+  GFSHIP_CHECK (pl->particulate, GFSHIP_EUNSUPPORTED,
+		"%s needs a list of particulates (gfship_particles_set_particulate): it sets the mass, the volume "
+		"and the velocity of what it adds", what);
+  GFSHIP_CHECK (!pl->dom->has_external, GFSHIP_EUNSUPPORTED,
+		"%s on a box with GfsBoundaryMpi sides is not supported: the ids of the boxes are not numbered "
+		"together (mpi_particle_numbering)", what);
+  GFSHIP_CHECK (pl->dom->dim*pl->dom->depth < 32, GFSHIP_EUNSUPPORTED,
+		"%s: the %d-D box of level %d has 2^32 cells or more", what, pl->dom->dim, pl->dom->depth);
+  return GFSHIP_OK;
+}
+
+static int feed_reserve (gfship_feed_particle * f, int np)
+{
+  if (f->cap >= np) return GFSHIP_OK;
+  gfship_particles * pl = f->pl;
+  GFSHIP_HIP (hipStreamSynchronize (pl->stream));
+  void ** a[] = { (void **) &f->cand, (void **) &f->cell, (void **) &f->block };
+  f->cap = 0;
+  for (void ** p : a) {
+    if (*p) (void) hipFree (*p);
+    *p = nullptr;
+  }
+  const size_t m = (size_t) np;
+  GFSHIP_HIP (hipMalloc ((void **) &f->cand, 3*m*sizeof (double)));
+  GFSHIP_HIP (hipMalloc ((void **) &f->cell, m*sizeof (unsigned)));
+  GFSHIP_HIP (hipMalloc ((void **) &f->block, (m + FEED_BLOCK - 1)/FEED_BLOCK*sizeof (unsigned)));
+  f->cap = np;
+  return GFSHIP_OK;
+}
+
+} // namespace gfship
+
+using namespace gfship;
+
+extern "C" {
+
+int gfship_feed_particle_create (gfship_feed_particle ** out, gfship_particles * pl, const char * mass,
+				 const char * volume, int nvars, const char * const * names,
+				 const gfship_field * fields)
+{
+  GFSHIP_CHECK (out != nullptr, GFSHIP_EINVAL, "null output pointer");
+  *out = nullptr;
+  int r = feed_check (pl);
+  if (r) return r;
+  GFSHIP_CHECK (nvars >= 0 && (nvars == 0 || (names && fields)), GFSHIP_EINVAL, "invalid table of variables");
+  gfship_domain * dom = pl->dom;
+  static const char * builtin[] = { "x", "y", "z", "t" };
+  for (int q = 0; q < nvars; q++) {
+    GFSHIP_CHECK (c_identifier (names[q]), GFSHIP_EINVAL, "variable %d of the table has no C name", q);
+    for (const char * b : builtin)
+      GFSHIP_CHECK (strcmp (names[q], b) != 0, GFSHIP_EINVAL,
+		    "`%s' is a variable of the function itself: it cannot name a field", b);
+    for (int p = 0; p < q; p++)
+      GFSHIP_CHECK (strcmp (names[q], names[p]) != 0, GFSHIP_EINVAL, "`%s' is in the table twice", names[q]);
+    if (!get_field (dom, fields[q])) return GFSHIP_EINVAL;
+  }
+  gfship_feed_particle * f = new gfship_feed_particle;
+  f->pl = pl;
+  const char * text[2] = { mass, volume };
+  for (int w = 0; w < 2; w++) {
+    if (!text[w]) continue;
+    /* a constant (gfs_function_read: a number is kept as f->val) needs no compilation */
+    char * end = nullptr;
+    f->value[w] = strtod (text[w], &end);
+    while (end != text[w] && (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r')) end++;
+    if (end != text[w] && *end == '\0') continue;
+    f->value[w] = 0.;
+    std::vector<const char *> named;
+    for (int q = 0; q < nvars; q++)
+      if (names_identifier (text[w], names[q])) {
+	named.push_back (names[q]);
+	f->read[w].push_back (fields[q]);
+      }
+    if ((r = rtc_compile_cell (dom, text[w], (int) named.size (), named.data (), &f->fn[w]))) {
+      gfship_feed_particle_destroy (f);
+      return r;
+    }
+  }
+  *out = f;
+  return GFSHIP_OK;
+}
+
+int gfship_feed_particle_event (gfship_feed_particle * f, int np, const double * pos)
+{
+  GFSHIP_CHECK (f != nullptr, GFSHIP_EINVAL, "null GfsFeedParticle");
+  GFSHIP_CHECK (np >= 0 && (np == 0 || pos), GFSHIP_EINVAL, "invalid argument");
+  gfship_particles * pl = f->pl;
+  int r = feed_check (pl);
+  if (r) return r;
+  if (np == 0) return GFSHIP_OK;
+  GFSHIP_CHECK ((long) pl->n + np <= 0x7fffffffL, GFSHIP_ENOMEM, "the list would hold 2^31 slots or more");
+  gfship_domain * dom = pl->dom;
+  const Layout & L = dom->lay[dom->depth];
+  std::vector<const double *> read[2];
+  for (int w = 0; w < 2; w++)
+    for (gfship_field v : f->read[w]) {
+      Field * F = get_field (dom, v);
+      if (!F) return GFSHIP_EINVAL;
+      read[w].push_back (F->lev[dom->depth]);
+    }
+  if ((r = feed_reserve (f, np))) return r;
+  if ((r = particles_reserve (pl, pl->n + np))) return r;
+  /* the candidates come from pageable memory: the copy is staged before the call returns */
+  GFSHIP_HIP (hipMemcpyAsync (f->cand, pos, 3*(size_t) np*sizeof (double), hipMemcpyHostToDevice, dom->stream));
+  const int base = pl->n;
+  if ((r = launch_feed_gather (pl, base, np, f->cand, f->cell))) return r;
+  double * out[2] = { pl->mass + base, pl->volume + base };
+  for (int w = 0; w < 2; w++) {
+    if (f->fn[w])
+      r = rtc_launch_cell (f->fn[w], dom->stream, np, L, f->cell, gfship_sim_time (pl->sim), (int) read[w].size (),
+			   read[w].data (), out[w]);
+    else
+      r = launch_fill (dom->stream, np, f->value[w], out[w]);
+    if (r) return r;
+  }
+  const int grid = (np + FEED_BLOCK - 1)/FEED_BLOCK;
+  hipLaunchKernelGGL (feed_count_kernel, dim3 (grid), dim3 (FEED_BLOCK), 0, dom->stream, np, f->cell, out[0],
+		      f->block);
+  hipLaunchKernelGGL (feed_scan_kernel, dim3 (1), dim3 (FEED_BLOCK), 0, dom->stream, grid, f->block, pl->d_idlast);
+  hipLaunchKernelGGL (feed_scatter_kernel, dim3 (grid), dim3 (FEED_BLOCK), 0, dom->stream, np, f->cell, f->block,
+		      out[0], out[1], pl->dia + base, pl->rb + base, pl->id + base, pl->alive + base);
+  GFSHIP_HIP (hipGetLastError ());
+  pl->n += np;
+  return GFSHIP_OK;
+}
+
+void gfship_feed_particle_destroy (gfship_feed_particle * f)
+{
+  if (!f) return;
+  (void) hipStreamSynchronize (f->pl->stream);
+  void * a[] = { f->cand, f->cell, f->block };
+  for (void * p : a)
+    if (p) (void) hipFree (p);
+  rtc_free (f->fn[0]);
+  rtc_free (f->fn[1]);
+  delete f;
+}
+
+int gfship_particles_set_idlast (gfship_particles * pl, int idlast)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_set_idlast");
+  GFSHIP_CHECK (idlast >= 0, GFSHIP_EINVAL, "idlast is a guint");
+  const unsigned v = (unsigned) idlast;
+  GFSHIP_HIP (hipMemcpyAsync (pl->d_idlast, &v, sizeof (unsigned), hipMemcpyHostToDevice, pl->stream));
+  GFSHIP_HIP (hipStreamSynchronize (pl->stream));
+  return GFSHIP_OK;
+}
+
+int gfship_particles_idlast (gfship_particles * pl)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_idlast");
+  unsigned v = 0;
+  GFSHIP_HIP (hipMemcpyAsync (&v, pl->d_idlast, sizeof (unsigned), hipMemcpyDeviceToHost, pl->stream));
+  GFSHIP_HIP (hipStreamSynchronize (pl->stream));
+  return (int) v;
+}
+
+} // extern "C"

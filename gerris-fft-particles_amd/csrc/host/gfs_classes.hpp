@@ -439,13 +439,32 @@ inline void read_particle_list (Run & R, Reader & r, Object & ob)
     if (ps->forces.size () > 8) r.fail ("at most 8 forces");
   }
   char c = r.peek (false);
-  if ((c >= '0' && c <= '9') || c == '-' || c == '+' || c == '.') r.number ();           /* idlast */
+  if ((c >= '0' && c <= '9') || c == '-' || c == '+' || c == '.')
+    ps->idlast = atoi (r.word (false).c_str ());                                         /* idlast, :1087-1090 */
   ob.e->action = [ps, &R] () {
     /* the forces read the density and the viscosity of the fluid at the time of the event */
     if (ps->pl && !ps->forces.empty () && (refresh_alpha_cell (R) || refresh_viscosity_cell (R)))
       exit (1);
     if (ps->pl) must (gfship_particle_list_event (ps->pl));
   };
+}
+
+// LIST: the `*name' of a GfsParticleList of GfsParticulate objects read above (gfs_object_from_name), with the
+// messages of the readers of the reference (particulate_field_read, :1959-1984, and the like)
+inline ParticleSpec * read_particulate_list_name (Run & R, Reader & r, const Object & ob)
+{
+  if (r.at_end_of_object () || r.peek (false) == '{')
+    r.fail ("expecting a string (object name)");
+  const std::string lname = r.word (false);
+  ParticleSpec * ps = R.plist_by_name (lname);
+  if (!ps) {
+    if (R.var_index (lname) >= 0)
+      r.fail ("object '" + lname + "' is not a GfsParticleList");
+    r.fail ("unknown object '" + lname + "'");
+  }
+  if (!ps->particulate)
+    r.fail ("the list `" + lname + "' holds GfsParticle objects: Gfs" + ob.cls + " needs GfsParticulate objects");
+  return ps;
 }
 
 inline void read_particulate_field (Run & R, Reader & r, Object & ob)
@@ -458,17 +477,7 @@ inline void read_particulate_field (Run & R, Reader & r, Object & ob)
   read_event_params (r, *ob.e);
   std::string vname;
   if (field) vname = r.word (false);            /* gfs_variable_read: the name of the variable */
-  if (r.at_end_of_object () || r.peek (false) == '{')
-    r.fail ("expecting a string (object name)");
-  const std::string lname = r.word (false);
-  ParticleSpec * ps = R.plist_by_name (lname);
-  if (!ps) {
-    if (R.var_index (lname) >= 0)
-      r.fail ("object '" + lname + "' is not a GfsParticleList");
-    r.fail ("unknown object '" + lname + "'");
-  }
-  if (!ps->particulate)
-    r.fail ("the list `" + lname + "' holds GfsParticle objects: Gfs" + ob.cls + " needs GfsParticulate objects");
+  ParticleSpec * ps = read_particulate_list_name (R, r, ob);
   if (field) {
     const int v = R.get_or_add_variable (vname);
     R.device_vars.push_back (vname);
@@ -523,17 +532,7 @@ inline void read_source_particulate_change (Run & R, Reader & r, Object & ob)
   const bool vol = ob.cls == "SourceParticulateVol";
   ob.e->istep = 1;                              /* source_generic_init, src/source.c:149-152 */
   read_event_params (r, *ob.e);
-  if (r.at_end_of_object () || r.peek (false) == '{')
-    r.fail ("expecting a string (object name)");
-  const std::string lname = r.word (false);
-  ParticleSpec * ps = R.plist_by_name (lname);
-  if (!ps) {
-    if (R.var_index (lname) >= 0)
-      r.fail ("object '" + lname + "' is not a GfsParticleList");
-    r.fail ("unknown object '" + lname + "'");
-  }
-  if (!ps->particulate)
-    r.fail ("the list `" + lname + "' holds GfsParticle objects: Gfs" + ob.cls + " needs GfsParticulate objects");
+  ParticleSpec * ps = read_particulate_list_name (R, r, ob);
   R.particulate_sources.emplace_back (new ParticulateSourceSpec);
   ParticulateSourceSpec * sp = R.particulate_sources.back ().get ();
   sp->ps = ps;
@@ -581,6 +580,69 @@ inline void read_source_particulate_change (Run & R, Reader & r, Object & ob)
     must (gfship_particulate_source_event (sp->src));
     for (int v : { sp->rad, sp->urel[0], sp->urel[1], sp->urel[2], sp->deposit })
       if (v >= 0) R.vars[v].host_time = -1.;
+  };
+}
+
+inline void read_feed_particle (Run & R, Reader & r, Object & ob)
+{
+  // gfs_feed_particle_read (modules/particulatecommon.c:2435-2575):
+  //   GfsFeedParticle [{ event }] LIST { nparts = F xfeed = F yfeed = F zfeed = F velx = F vely = F velz = F
+  //                                      mass = F volume = F }
+  // LIST is the `*name' of a GfsParticleList read above.  nparts and the three positions are evaluated without a
+  // cell (gfs_function_value (f, NULL), :2381-2383, :2411): functions of the host; velx, vely, velz are read and
+  // never evaluated (:2388-2392); mass and volume are evaluated at the cell of the candidate, on the device
+  // (gfship_feed_particle_create), with the device variables of the run they name
+  read_event_params (r, *ob.e);
+  ParticleSpec * ps = read_particulate_list_name (R, r, ob);
+  R.feed_particles.emplace_back (new FeedParticleSpec);
+  FeedParticleSpec * sp = R.feed_particles.back ().get ();
+  sp->ps = ps;
+  sp->line = ob.line;
+  if (r.peek (false) != '{') r.fail ("expecting an opening brace");
+  Reader b = block (r);
+  static const char * keywords[] = { "nparts", "xfeed", "yfeed", "zfeed", "velx", "vely", "velz", "mass", "volume" };
+  while (!b.eof ()) {
+    if (b.peek () == '{' || b.peek () == '=') b.fail ("expecting a keyword");
+    const std::string k = b.word ();
+    int q = 0;
+    while (q < 9 && k != keywords[q]) q++;
+    if (q == 9) b.fail ("unknown keyword `" + k + "'");
+    if (b.peek (false) != '=') b.fail ("expecting '='");
+    b.expect ('=');
+    const int line = b.line ();
+    const FunctionText t = b.function ();
+    if (q < 4) {
+      /* the reference would read the variable at the cell NULL */
+      for (const std::string & id : FunctionSet::identifiers (t.text))
+        if (R.var_index (id) >= 0)
+          b.fail ("`" + k + "' of GfsFeedParticle is evaluated without a cell: it cannot read the variable `" + id + "'");
+      (q == 0 ? sp->np : sp->feed[q - 1]) = R.functions.add (t, line);
+    }
+    else if (q >= 7) {
+      if (t.block || !Reader::is_number (t.text) || atof (t.text.c_str ()) != 0.)
+        (q == 7 ? sp->mass : sp->volume) = t.text;
+      for (const std::string & id : FunctionSet::identifiers (t.text)) {
+        if (id == "x" || id == "y" || id == "z" || id == "t" || R.var_index (id) < 0)
+          continue;                                /* anything else is left to the compiler of the device */
+        if (!R.on_device (id))
+          b.fail ("`" + k + "' of GfsFeedParticle reads `" + id +
+                  "', which is not kept on the device (the variables of the simulation, tracers and the variables "
+                  "of GfsParticulateField, GfsSourceParticulate, GfsSourceParticulateVol and ...Mass are)");
+        if (std::find (sp->reads.begin (), sp->reads.end (), id) == sp->reads.end ())
+          sp->reads.push_back (id);
+      }
+    }
+  }
+  ob.e->action = [&R, sp] () {
+    const double nowhere[3] = { 0., 0., 0. };
+    /* guint np = gfs_function_value (feedp->np, NULL), once (:2411); then x, y, z of every candidate in that
+       order (:2381-2383): the order a function with state sees */
+    const unsigned np = sp->np ? (unsigned) eval (R, sp->np, nowhere, -1) : 1u;
+    std::vector<double> pos (3*(size_t) np, 0.);
+    for (unsigned i = 0; i < np; i++)
+      for (int c = 0; c < 3; c++)
+        if (sp->feed[c]) pos[3*(size_t) i + c] = eval (R, sp->feed[c], nowhere, -1);
+    must (gfship_feed_particle_event (sp->handle, (int) np, pos.data ()));
   };
 }
 
@@ -1050,6 +1112,8 @@ inline const ClassRow class_table[] = {
   { "SourceParticulate", read_particulate_field, EVENT },
   { "SourceParticulateVol", read_source_particulate_change, EVENT },     // LIST FUNCTION [VARIABLE]: the volumes and
   { "SourceParticulateMass", read_source_particulate_change, EVENT },    //   the masses of a list change (uniform boxes)
+  { "FeedParticle", read_feed_particle, EVENT },          // LIST { nparts xfeed yfeed zfeed mass volume }: particles
+                                                          //   join a list of particulates (uniform boxes)
   { "OutputEnergySpectra", read_output_energy_spectra, OUT },
   { "OutputSpectra", read_output_spectra, OUT },
   { "VariableTurbulentViscosity", read_variable_turbulent_viscosity, EVENT },

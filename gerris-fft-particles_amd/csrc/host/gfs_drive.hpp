@@ -904,6 +904,7 @@ inline int create_simulation (Run & R, gfship_field & div)
   for (auto & ps : R.plists) {
     int np = (int) ps->id.size ();
     CHECK (gfship_particles_create (&ps->pl, R.sim, np, ps->pos.data (), ps->id.data ()));
+    if (ps->idlast) CHECK (gfship_particles_set_idlast (ps->pl, ps->idlast));
     if (ps->particulate) {
       CHECK (gfship_particles_set_particulate (ps->pl, ps->vel.data (), ps->mass.data (), ps->volume.data ()));
       /* gravity of GfsForceBuoy = the GfsSource intensities on U, V, W (compute_buoyancy_force) */
@@ -938,6 +939,21 @@ inline int create_simulation (Run & R, gfship_field & div)
     for (int c = 0; c < R.dim; c++) urel[c] = R.vars[sp->urel[c]].dev;
     CHECK (gfship_particulate_source_set_fields (sp->src, R.vars[sp->rad].dev, urel,
                                                  sp->deposit >= 0 ? R.vars[sp->deposit].dev : -1));
+  }
+  // GfsFeedParticle: mass and volume compiled for the device, with the device variables they name
+  for (auto & sp : R.feed_particles) {
+    std::vector<const char *> names;
+    std::vector<gfship_field> fields;
+    for (const std::string & nm : sp->reads) {
+      names.push_back (nm.c_str ());
+      fields.push_back (R.vars[R.var_index (nm)].dev);
+    }
+    if (gfship_feed_particle_create (&sp->handle, sp->ps->pl, sp->mass.empty () ? nullptr : sp->mass.c_str (),
+                                     sp->volume.empty () ? nullptr : sp->volume.c_str (), (int) names.size (),
+                                     names.data (), fields.data ()) < 0) {
+      fprintf (stderr, "gfship: line %d: %s\n", sp->line, gfship_last_error ());
+      return 1;
+    }
   }
   set_boundary_conditions (R);
   apply_init (R);
@@ -1177,6 +1193,7 @@ inline int run (Run & R)
     return 1;
   if (!R.particles_out.empty () && write_particles (R)) return 1;
   for (auto & sp : R.particulate_sources) gfship_particulate_source_destroy (sp->src);
+  for (auto & sp : R.feed_particles) gfship_feed_particle_destroy (sp->handle);
   for (auto & ps : R.plists) gfship_particles_destroy (ps->pl);
   for (auto & o : R.outputs) o->close ();
   gfship_sim_destroy (R.sim);

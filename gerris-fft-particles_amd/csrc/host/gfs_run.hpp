@@ -163,6 +163,7 @@ struct ParticleSpec {
   std::vector<std::string> force_functions;      // the GfsFunction of a GfsForceCoeff ("" = none)
   std::string name;                              // the optional `*name' of the event (gfs_event_read, src/event.c:198-203)
   int line = 0;                                  // of the GfsParticleList in the file
+  int idlast = 0;                                // the integer that may end the list (:1087-1090)
   gfship_particles * pl = nullptr;
 };
 
@@ -186,6 +187,18 @@ struct ParticulateSourceSpec {
   std::vector<std::string> reads;
   int rad = -1, urel[3] = { -1, -1, -1 }, deposit = -1;
   gfship_particulate_source * src = nullptr;
+};
+
+// GfsFeedParticle (modules/particulatecommon.c:2375-2647): the list, the host functions nparts, xfeed, yfeed, zfeed
+// (nullptr: the default of gfs_feed_particle_init, 1 for nparts and 0 for the others) and the texts of mass and
+// volume with the device variables they name
+struct FeedParticleSpec {
+  ParticleSpec * ps = nullptr;
+  int line = 0;
+  Function * np = nullptr, * feed[3] = { nullptr, nullptr, nullptr };
+  std::string mass, volume;                      // "" = the constant 0
+  std::vector<std::string> reads;
+  gfship_feed_particle * handle = nullptr;
 };
 
 // a cell: its indices on its level (1..2^l inside the box; k = 0 in 2-D)
@@ -233,6 +246,7 @@ struct Run {
   std::vector<std::unique_ptr<ParticleSpec>> plists;
   std::vector<std::unique_ptr<SourceParticulateSpec>> source_particulates;
   std::vector<std::unique_ptr<ParticulateSourceSpec>> particulate_sources;
+  std::vector<std::unique_ptr<FeedParticleSpec>> feed_particles;
   // a variable of the file that is kept on the device: those of the simulation, the tracers and device_vars
   bool on_device (const std::string & name) const {
     if (name == "P" || name == "Pmac" || velocity_component (name) >= 0) return true;

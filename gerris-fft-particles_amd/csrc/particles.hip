@@ -589,6 +589,49 @@ particulate_source_gather_kernel (SourceGatherArgs A)
     A.urel[a][o] = interpolate<DIM> (A.L, A.u[a], c, p) - A.vel[a][o];
 }
 
+// feed_particulate (modules/particulatecommon.c:2377-2393) for one candidate per thread: gfs_domain_locate, then
+// vel[c] = gfs_interpolate (cell, pos, u[c]) (vel.z = 0. in 2-D); the slot is that of a new object (pos_old = 0,
+// force = 0) whose fate the ordered passes of feed_particle.hip decide
+struct FeedGatherArgs {
+  Layout L;
+  int depth, np, base;
+  const double * cand;
+  const double * u[3];
+  double * pos[3], * old[3], * vel[3], * force[3];
+  unsigned * orig, * cell;
+};
+
+template <int DIM>
+__global__ void __launch_bounds__(256)
+feed_gather_kernel (FeedGatherArgs A)
+{
+  int i = blockIdx.x*blockDim.x + threadIdx.x;
+  if (i >= A.np) return;
+  const int s = A.base + i;
+  const double p[3] = { A.cand[3*(size_t) i], A.cand[3*(size_t) i + 1], A.cand[3*(size_t) i + 2] };
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    A.pos[c][s] = p[c];
+    A.old[c][s] = 0.;
+    A.force[c][s] = 0.;
+  }
+  A.orig[s] = (unsigned) s;
+  int c[3];
+  double vel[3] = { 0., 0., 0. };
+  unsigned cell = PSOURCE_NO_CELL;
+  if (locate<DIM> (A.depth, p, c)) {
+    const unsigned n = (unsigned) A.L.n;
+    cell = (unsigned) (c[0] - 1) + n*((unsigned) (c[1] - 1) + (DIM == 3 ? n*(unsigned) (c[2] - 1) : 0u));
+#pragma unroll
+    for (int a = 0; a < DIM; a++)
+      vel[a] = interpolate<DIM> (A.L, A.u[a], c, p);
+  }
+  A.cell[i] = cell;
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+    A.vel[a][s] = vel[a];
+}
+
 } // namespace gfship
 
 using namespace gfship;
@@ -632,6 +675,8 @@ int gfship::particles_alloc (gfship_particles * pl, int np, const double * pos, 
   GFSHIP_HIP (hipMalloc ((void **) &pl->alive, m));
   GFSHIP_HIP (hipMemset (pl->alive, 1, m));
   GFSHIP_HIP (hipMalloc ((void **) &pl->d_count, sizeof (unsigned)));
+  GFSHIP_HIP (hipMalloc ((void **) &pl->d_idlast, sizeof (unsigned)));
+  GFSHIP_HIP (hipMemset (pl->d_idlast, 0, sizeof (unsigned)));      /* gfs_particle_list_init */
   for (int c = 0; c < 3; c++) {
     GFSHIP_HIP (hipMalloc ((void **) &pl->pos2[c], m*sizeof (double)));
     GFSHIP_HIP (hipMalloc ((void **) &pl->old2[c], m*sizeof (double)));
@@ -661,6 +706,7 @@ void gfship_particles_destroy (gfship_particles * pl)
   if (pl->id) (void) hipFree (pl->id);
   if (pl->alive) (void) hipFree (pl->alive);
   if (pl->d_count) (void) hipFree (pl->d_count);
+  if (pl->d_idlast) (void) hipFree (pl->d_idlast);
   for (int c = 0; c < 3; c++) {
     if (pl->pos2[c]) (void) hipFree (pl->pos2[c]);
     if (pl->old2[c]) (void) hipFree (pl->old2[c]);
@@ -794,8 +840,10 @@ int gfship_particles_sort (gfship_particles * pl)
   return GFSHIP_OK;
 }
 
+} // extern "C"
+
 // grow the per-particle arrays to at least `need` slots (contents of the live arrays kept)
-static int particles_reserve (gfship_particles * pl, int need)
+int gfship::particles_reserve (gfship_particles * pl, int need)
 {
   if (need <= pl->cap) return GFSHIP_OK;
   gfship_domain * dom = pl->dom;
@@ -831,13 +879,15 @@ static int particles_reserve (gfship_particles * pl, int need)
     GFSHIP_HIP (grow ((void **) &pl->mass, sizeof (double), true));
     GFSHIP_HIP (grow ((void **) &pl->volume, sizeof (double), true));
     GFSHIP_HIP (grow ((void **) &pl->dia, sizeof (double), true));
-    /* (rb is not kept for newcomers: particles arrive through GfsBoundaryMpi sides only, and every reader
-       of rb refuses a box with such sides, coupling.hip) */
+    /* rb of the particles on the list is kept; a GfsFeedParticle writes it for its newcomers, a GfsBoundaryMpi
+       side does not (every reader of rb refuses a box with such sides, coupling.hip) */
     GFSHIP_HIP (grow ((void **) &pl->rb, sizeof (double), true));
   }
   pl->cap = (int) m;
   return GFSHIP_OK;
 }
+
+extern "C" {
 
 // send_particles / rcv_particles through the GfsBoundaryMpi sides
 // (modules/particulatecommon.c:3247-3312): packets per side out, the neighbours' packets in
@@ -1448,6 +1498,30 @@ int gfship::launch_particulate_source_gather (gfship_particles * pl, unsigned * 
   with_bools ([&] (auto D3) {
     constexpr int DIM = decltype (D3)::value ? 3 : 2;
     hipLaunchKernelGGL (particulate_source_gather_kernel<DIM>, dim3 (grid), dim3 (block), 0, dom->stream, A);
+  }, dom->dim == 3);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
+int gfship::launch_feed_gather (gfship_particles * pl, int base, int np, const double * cand, unsigned * cell)
+{
+  gfship_domain * dom = pl->dom;
+  const gfship_sim_view v = gfship_sim_view_get (pl->sim);
+  FeedGatherArgs A;
+  A.L = dom->lay[dom->depth];
+  A.depth = dom->depth;
+  A.np = np; A.base = base;
+  A.cand = cand;
+  for (int c = 0; c < 3; c++) {
+    A.u[c] = c < dom->dim ? dom->fields[v.u[c]].lev[dom->depth] : nullptr;
+    A.pos[c] = pl->pos[c]; A.old[c] = pl->old[c];
+    A.vel[c] = pl->vel[c]; A.force[c] = pl->force[c];
+  }
+  A.orig = pl->orig; A.cell = cell;
+  const int block = 256, grid = (np + block - 1)/block;
+  with_bools ([&] (auto D3) {
+    constexpr int DIM = decltype (D3)::value ? 3 : 2;
+    hipLaunchKernelGGL (feed_gather_kernel<DIM>, dim3 (grid), dim3 (block), 0, dom->stream, A);
   }, dom->dim == 3);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;

@@ -2,6 +2,7 @@
 #pragma once
 #include "gfship_internal.hpp"
 #include <functional>
+#include <string>
 #include <vector>
 
 namespace gfship {
@@ -27,6 +28,11 @@ int  rtc_compile_source (gfship_domain * dom, const char * text, int nf, const c
 int  rtc_launch_source (RtcKernel * k, hipStream_t stream, int n, const Layout & L, const unsigned * cell,
 			const double * rad, const double * const urel[3], double t, int nf,
 			const double * const * fields, double * out);
+// the mass and the volume of a GfsFeedParticle (feed_particle.hip): a GfsFunction of x, y, z (the centre of the
+// candidate's cell), t and of the nf variables `names', evaluated for every candidate o < n with a cell
+int  rtc_compile_cell (gfship_domain * dom, const char * text, int nf, const char * const * names, RtcKernel ** out);
+int  rtc_launch_cell (RtcKernel * k, hipStream_t stream, int n, const Layout & L, const unsigned * cell, double t,
+		      int nf, const double * const * fields, double * out);
 // the same function on a list of a tree: cell[o] is the index of the leaf in the concatenated levels (Topo::gi);
 // the kernel finds the level of the leaf from the level offsets off[0 .. depth + 1] and its integer coordinates
 // from its index in the dense level, x, y, z = ftt_cell_pos of the leaf, and reads the variables (arrays of all
@@ -53,6 +59,19 @@ struct gfship_particulate_source {
   int cap = 0;
 };
 
+// a GfsFeedParticle (feed_particle.hip) on a list of particulates of a box: its two functions of the cell
+// (0: mass, 1: volume) and the work arrays of an event
+struct gfship_feed_particle {
+  gfship_particles * pl = nullptr;
+  gfship::RtcKernel * fn[2] = {};        // nullptr: the constant `value'
+  double value[2] = {};
+  std::vector<gfship_field> read[2];     // the fields each function names, in the order of its arguments
+  double * cand = nullptr;               // 3 doubles per candidate
+  unsigned * cell = nullptr;             // per candidate: the linear number of its cell, or PSOURCE_NO_CELL
+  unsigned * block = nullptr;            // per block of candidates: accepted, then the id before its first
+  int cap = 0;
+};
+
 struct gfship_particles {
   gfship_sim * sim = nullptr;
   gfship_domain * dom = nullptr;
@@ -65,6 +84,7 @@ struct gfship_particles {
   unsigned * id = nullptr;
   unsigned char * alive = nullptr;
   unsigned * d_count = nullptr;
+  unsigned * d_idlast = nullptr;      // idlast of the GfsParticleList (particle_id, :1231-1234): lists of a box
   // sort by cell
   unsigned * orig = nullptr;          // creation slot of the particle stored in each slot
   double * pos2[3] = {}, * old2[3] = {};   // gather targets (swapped with pos/old after a sort)
@@ -142,6 +162,13 @@ int launch_where (gfship_particles * pl);
 int launch_fill (hipStream_t stream, long n, double value, double * out);
 // the per-particle arrays of a new list of np tracers (particles.hip); pl->stream is set by the caller
 int particles_alloc (gfship_particles * pl, int np, const double * pos, const unsigned * id);
+// grow the per-particle arrays to at least `need' slots, contents kept (particles.hip)
+int particles_reserve (gfship_particles * pl, int need);
+// feed_particulate (:2377-2396) up to the two functions, for the np candidates `cand' (3 doubles each, device) of
+// a GfsFeedParticle with the locate and the interpolate of the event kernels (particles.hip): slot base + i gets
+// the position, pos_old = 0, force = 0, orig = its own number and the interpolated velocity of the fluid;
+// cell[i] = the linear number of the candidate's cell or PSOURCE_NO_CELL
+int launch_feed_gather (gfship_particles * pl, int base, int np, const double * cand, unsigned * cell);
 // a list on a tree (tree_particles.hip): the event of its tracers, the keys of gfship_particles_sort and their bits
 int tree_particle_list_event (gfship_particles * pl);
 int tree_particle_keys (gfship_particles * pl, int * bits);
@@ -160,6 +187,11 @@ int launch_particulate_source_gather (gfship_particles * pl, unsigned * cell, do
 int particulate_source_reserve (gfship_particulate_source * s);
 int launch_particulate_source_update (gfship_particulate_source * s, hipStream_t stream, double dt,
 				      unsigned long long pad, unsigned long long * key);
+// the checks of a table of variables and of the text of a function (particulate_sources.hip), shared with
+// feed_particle.hip: is `s' a C identifier; does the C text `e' name `id' (a whole identifier, not a member and
+// not inside a string)?
+bool c_identifier (const char * s);
+bool names_identifier (const std::string & e, const std::string & id);
 // the event of a source on a list of a tree (tree_particles.hip); info as in source_event
 int tree_particulate_source_event (gfship_particulate_source * s, double * info);
 }

@@ -58,7 +58,7 @@ particulate_source_update_kernel (int n, const unsigned * __restrict__ cell, con
   if (key) key[o] = (unsigned long long) c << 32 | (unsigned) o;
 }
 
-static bool c_identifier (const char * s)
+bool c_identifier (const char * s)
 {
   if (!s || !(isalpha ((unsigned char) *s) || *s == '_')) return false;
   for (; *s; s++)
@@ -67,7 +67,7 @@ static bool c_identifier (const char * s)
 }
 
 // does the C text name `id' (a whole identifier, not a member and not inside a string)?
-static bool names_identifier (const std::string & e, const std::string & id)
+bool names_identifier (const std::string & e, const std::string & id)
 {
   size_t p = 0;
   while (p < e.size ()) {

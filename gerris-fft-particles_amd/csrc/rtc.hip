@@ -187,14 +187,19 @@ int rtc_launch_spatial (RtcKernel * k, hipStream_t stream, long nrec, int stride
 // the function of a GfsSourceParticulateVol / ...Mass (modules/particulatecommon.c:2826, 2984:
 // gfs_function_value (source, cell) right after the particle wrote Rad, Urelp ... into its cell): the values
 // of the particle for those four, the centre of the cell for x, y, z, and the value at the cell of every other
-// variable it names.  One thread per creation slot; cell[o] is the linear number of the cell, i fastest
-int rtc_compile_source (gfship_domain * dom, const char * text, int nf, const char * const * names,
-			RtcKernel ** out)
+// variable it names.  One thread per creation slot; cell[o] is the linear number of the cell, i fastest.
+// particle = false: the same kernel around a plain spatial GfsFunction at the cell (the mass and the volume of a
+// GfsFeedParticle, feed_particle.hip): no Rad, Urelp ... among its variables nor among the kernel's arguments
+static int compile_cell_function (gfship_domain * dom, bool particle, const char * text, int nf,
+				  const char * const * names, RtcKernel ** out)
 {
   GFSHIP_CHECK (dom != nullptr, GFSHIP_EINVAL, "null argument");
   const bool d3 = dom->dim == 3;
-  std::string sig = "static __device__ double gfship_f (double Rad, double Urelp, double Vrelp, ";
-  if (d3) sig += "double Wrelp, ";
+  std::string sig = "static __device__ double gfship_f (";
+  if (particle) {
+    sig += "double Rad, double Urelp, double Vrelp, ";
+    if (d3) sig += "double Wrelp, ";
+  }
   sig += "double x, double y, double z, double t";
   std::string params, values;
   for (int q = 0; q < nf; q++) {
@@ -205,8 +210,13 @@ int rtc_compile_source (gfship_domain * dom, const char * text, int nf, const ch
   sig += ")\n";
   std::string kern =
     "extern \"C\" __global__ void gfship_psource (int n, unsigned nside, int xo, long sy, long sz,\n"
-    "    const unsigned * cell, const double * rad, const double * urel, const double * vrel,\n";
-  if (d3) kern += "    const double * wrel,\n";
+    "    const unsigned * cell,";
+  if (particle) {
+    kern += " const double * rad, const double * urel, const double * vrel,\n";
+    if (d3) kern += "    const double * wrel,\n";
+  }
+  else
+    kern += "\n";
   kern += "    double t,\n" + params + "    double * out)\n"
     "{\n"
     "  int o = blockIdx.x*blockDim.x + threadIdx.x;\n"
@@ -219,12 +229,46 @@ int rtc_compile_source (gfship_domain * dom, const char * text, int nf, const ch
     "  const long idx = xo + i + sy*j + sz*k;\n"
     "  (void) idx;\n"
     "  const double h = 1./nside;\n"      /* ftt_cell_pos: dyadic, exact */
-    "  out[o] = gfship_f (rad[o], urel[o], vrel[o], ";
-  if (d3) kern += "wrel[o], ";
+    "  out[o] = gfship_f (";
+  if (particle) {
+    kern += "rad[o], urel[o], vrel[o], ";
+    if (d3) kern += "wrel[o], ";
+  }
   kern += "-0.5 + (i - 0.5)*h, -0.5 + (j - 0.5)*h, ";
   kern += d3 ? "-0.5 + (k - 0.5)*h" : "0.";
   kern += ", t" + values + ");\n}\n";
   return rtc_compile (dom->device, text, sig.c_str (), kern.c_str (), "gfship_psource", out);
+}
+
+int rtc_compile_source (gfship_domain * dom, const char * text, int nf, const char * const * names,
+			RtcKernel ** out)
+{
+  return compile_cell_function (dom, true, text, nf, names, out);
+}
+
+// the mass and the volume of a GfsFeedParticle (modules/particulatecommon.c:2394-2395: gfs_function_value
+// (feedp->mass, cell)): the centre of the cell for x, y, z, the time, and the value at the cell of every variable
+// the text names.  One thread per candidate; cell[o] as for a source
+int rtc_compile_cell (gfship_domain * dom, const char * text, int nf, const char * const * names,
+		      RtcKernel ** out)
+{
+  return compile_cell_function (dom, false, text, nf, names, out);
+}
+
+int rtc_launch_cell (RtcKernel * k, hipStream_t stream, int n, const Layout & L, const unsigned * cell,
+		     double t, int nf, const double * const * fields, double * out)
+{
+  if (n <= 0) return GFSHIP_OK;
+  unsigned nside = (unsigned) L.n;
+  int xo = L.xo;
+  long sy = L.sy, sz = L.sz;
+  std::vector<const double *> f (fields, fields + nf);
+  std::vector<void *> args = { &n, &nside, &xo, &sy, &sz, &cell, &t };
+  for (int q = 0; q < nf; q++) args.push_back (&f[q]);
+  args.push_back (&out);
+  GFSHIP_HIP (hipModuleLaunchKernel (k->fn, (unsigned) ((n + 255)/256), 1, 1, 256, 1, 1, 0, stream, args.data (),
+				     nullptr));
+  return GFSHIP_OK;
 }
 
 int rtc_launch_source (RtcKernel * k, hipStream_t stream, int n, const Layout & L, const unsigned * cell,

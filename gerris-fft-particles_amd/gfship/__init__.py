@@ -184,6 +184,12 @@ SIGNATURES = {
     "gfship_particulate_source_time_event": (_i, [_vp, _pd]),
     "gfship_particulate_source_destroy": (None, [_vp]),
     "gfship_particles_download_volume": (_i, [_vp, _pd]),
+    "gfship_feed_particle_create": (_i, [C.POINTER(_vp), _vp, C.c_char_p, C.c_char_p, _i, C.POINTER(C.c_char_p),
+                                         C.POINTER(_i)]),
+    "gfship_feed_particle_event": (_i, [_vp, _i, _pd]),
+    "gfship_feed_particle_destroy": (None, [_vp]),
+    "gfship_particles_set_idlast": (_i, [_vp, _i]),
+    "gfship_particles_idlast": (_i, [_vp]),
     "gfship_tree_create": (_i, [C.POINTER(_vp), _i, C.c_void_p, _vp, _i]),
     "gfship_tree_create_sides": (_i, [C.POINTER(_vp), _i, C.c_void_p, _vp, _pi, _i]),
     "gfship_tree_set_bc": (_i, [_vp, _i, _i]),
@@ -924,6 +930,15 @@ class ParticleList:
         k = _check(lib().gfship_particles_download_volume(self.ptr, vol.ctypes.data_as(_pd)))
         return vol[:k].copy()
 
+    @property
+    def idlast(self):
+        """idlast of the GfsParticleList: the id the last particle a FeedParticle added took (lists of a box)"""
+        return _check(lib().gfship_particles_idlast(self.ptr))
+
+    @idlast.setter
+    def idlast(self, value):
+        _check(lib().gfship_particles_set_idlast(self.ptr, int(value)))
+
     def destroy(self):
         if self.ptr:
             lib().gfship_particles_destroy(self.ptr)
@@ -966,6 +981,32 @@ class ParticulateSource:
     def destroy(self):
         if self.ptr:
             lib().gfship_particulate_source_destroy(self.ptr)
+            self.ptr = None
+
+
+class FeedParticle:
+    """GfsFeedParticle on a list of particulates of a uniform box.  mass, volume: C text of x, y, z, t and of the
+    names of `variables' (a dict name -> Variable), a number, or None (the constant 0: nothing is fed without a
+    mass).  Close it before its list."""
+
+    def __init__(self, plist, mass=None, volume=None, variables={}):
+        variables = dict(variables or {})
+        names = (C.c_char_p * max(len(variables), 1))(*[k.encode() for k in variables])
+        fields = (_i * max(len(variables), 1))(*[v.h for v in variables.values()])
+        p = _vp()
+        _check(lib().gfship_feed_particle_create(
+            C.byref(p), plist.ptr, None if mass is None else str(mass).encode(),
+            None if volume is None else str(volume).encode(), len(variables), names, fields))
+        self.ptr, self.plist = p, plist
+
+    def event(self, pos):
+        """the candidates pos, an (np, 3) array, in order: those with a cell and a mass join the end of the list"""
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        _check(lib().gfship_feed_particle_event(self.ptr, len(pos), pos.ctypes.data_as(_pd)))
+
+    def close(self):
+        if self.ptr:
+            lib().gfship_feed_particle_destroy(self.ptr)
             self.ptr = None
 
 

@@ -650,6 +650,46 @@ int  gfship_particulate_source_time_event (gfship_particulate_source * src, doub
 void gfship_particulate_source_destroy (gfship_particulate_source * src);
 int  gfship_particles_download_volume (gfship_particles * pl, double * volume);
 
+/* Particles join a list during a run: GfsFeedParticle (modules/particulatecommon.c:2375-2647), an object on a
+   list of particulates of a uniform box.  GFSHIP_EUNSUPPORTED on a list of a tree, on a list of tracers (the
+   reference would write the members of a GfsParticulate into GfsParticle objects), on a box with
+   GFSHIP_SIDE_EXTERNAL sides (mpi_particle_numbering, :51-87, is not written) and on a box of 2^32 cells or more.
+   gfship_feed_particle_create (gfs_feed_particle_read, :2435-2575): mass and volume are the GfsFunction texts of
+   the keywords of the same names -- C text as in the simulation file, an expression or a { block } with a return
+   -- compiled for the device of the domain with hipRTC exactly as the function of a GfsSourceParticulateVol is
+   (-ffp-contract=off, the device's libm; GFSHIP_EINVAL with the compiler's messages in gfship_last_error () where
+   one does not compile).  A number is a constant and compiles nothing; NULL is the constant 0 of
+   gfs_feed_particle_init (:2614-2625), and an object without mass feeds nothing.  The texts may name x, y, z, t
+   and the nvars variables of the table (names[q], fields[q]); a name of the table that is one of those four, or
+   no C identifier, is GFSHIP_EINVAL.  Rad, Urelp ... are not variables of these functions: they are what the
+   table says, or unknown to the compiler.  Destroy the object before its list.
+   gfship_feed_particle_event (gfs_feed_particle_event, :2404-2418, from the position on), on the stream of the
+   list: for each of the np candidates pos (x y z each, host memory; all three are kept in 2-D as well) in the
+   order given, feed_particulate (:2377-2402): cell = gfs_domain_locate (pos) -- a candidate without a cell is
+   dropped -- vel[c] = gfs_interpolate (cell, pos, U ...) for c < dim with the velocity of the simulation as it
+   is now (vel.z = 0. in 2-D; the velx, vely, velz of the object are never evaluated, :2388-2392), mass and volume
+   = the two functions at the cell (its centre for x, y, z, gfship_sim_time for t, the cell's value of every
+   variable of the table), then add_particulate (:1237-1276): a candidate with mass < 1.e-20 is dropped before it
+   takes an id (a NaN is not less: it joins), any other joins the END of the list with id = ++idlast, force = 0
+   and pos_old = 0 until its first gfship_particle_list_event, and the forces of the list.  The new particles
+   follow every particle of the list in the order of gfship_particles_download, in candidate order; their ids are
+   idlast + 1 + the number of accepted candidates before them, an ordered count (never an atomic counter): the
+   same from run to run.  Candidates and results stay on the device; a dropped candidate leaves a dead slot
+   (gfship_particles_slots counts it, gfship_particles_count does not).  The diameter (:552) and rb (:2091) of a
+   new particle are values of the device's pow, as after a volume event.  np = 0 does nothing.
+   gfship_particles_set_idlast, gfship_particles_idlast: idlast of a GfsParticleList (particle_id, :1231-1234; 0
+   from gfs_particle_list_init, or the integer that ends the list in the file, :1087-1090), on any list of a box.
+   Nothing makes the new ids differ from those the list was created with unless idlast says so, as in the
+   reference.  The getter waits for the stream of the list. */
+typedef struct gfship_feed_particle gfship_feed_particle;
+int  gfship_feed_particle_create (gfship_feed_particle ** feed, gfship_particles * pl,
+				  const char * mass, const char * volume,
+				  int nvars, const char * const * names, const gfship_field * fields);
+int  gfship_feed_particle_event (gfship_feed_particle * feed, int np, const double * pos /* 3*np, host */);
+void gfship_feed_particle_destroy (gfship_feed_particle * feed);
+int  gfship_particles_set_idlast (gfship_particles * pl, int idlast);
+int  gfship_particles_idlast (gfship_particles * pl);
+
 /* ---- one box per GPU: GfsBoundaryMpi sides (src/mpi_boundary.c:78-246) ----------------------- */
 
 /* Either the in-library RCCL transport below (gfship_domain_comm_init: what bench.py uses), or two
