@@ -1,5 +1,5 @@
 // feed_particle.hip -- particles join a list during a run: GfsFeedParticle (modules/particulatecommon.c:2375-2647)
-// on a list of particulates of a uniform box, and idlast of a GfsParticleList.
+// on a list of particulates of a uniform box or of a refined tree, and idlast of a GfsParticleList.
 //
 // The event of the reference (gfs_feed_particle_event, :2404-2418) calls feed_particulate (:2377-2402) once per
 // candidate: the position from three functions without a cell, gfs_domain_locate (no cell: the candidate is
@@ -8,14 +8,16 @@
 // with id = ++idlast.  The positions are the host's business (functions with state, evaluated in order); what
 // follows is independent per candidate except for the id, which counts the accepted candidates before it.  Here:
 //   1. one thread per candidate: locate, interpolate, and the slot of a new object (feed_gather_kernel,
-//      particles.hip: the locate and the interpolate of the event kernels);
+//      particles.hip, and tree_feed_gather_kernel, tree_particles.hip: the locate and the interpolate of the event
+//      kernels of a box and of a tree; on a tree the cell is the leaf, whatever its level);
 //   2. the two functions of every candidate with a cell: a constant, or the kernel hipRTC compiled around the
-//      text (rtc.hip), written straight into the mass and the volume of the new slots;
+//      text (rtc.hip: at the cell of a box, or at the leaf of a tree), written straight into the mass and the
+//      volume of the new slots;
 //   3. the ids, an ordered prefix count of the accept flags in three passes: per block of 256 candidates the
 //      number accepted (ballot and popcount per wave, the waves added in LDS), one block scans those counts and
 //      moves idlast, then every candidate takes idlast + 1 + (accepted before it) and its flag; an accepted one
 //      also gets its diameter (:552) and rb (:2091).  No atomic counter: the ids do not depend on the scheduling
-//      nor on the shape of the launch.
+//      nor on the shape of the launch.  launch_feed_ids is these three passes, for a box and for a tree alike.
 // Slots: the np candidates take the np slots after those in use, in candidate order; a refused candidate is a
 // dead slot (alive = 0), which every reader of the list already skips.  The download order (creation slots) is
 // therefore the reference's list order.  idlast lives on the device; only its getter reads it back.
@@ -23,6 +25,7 @@
 // pow: the diameter and rb of a new particle are values of the device's pow in the reference's expressions, as
 // after a volume event (particulate_sources.hip); everything else is the reference's arithmetic.
 #include "particles.hpp"
+#include "tree_particles.hpp"
 #include <cctype>
 #include <cstdlib>
 #include <cstring>
@@ -124,6 +127,18 @@ feed_scatter_kernel (int np, const unsigned * __restrict__ cell, const unsigned 
   }
 }
 
+int launch_feed_ids (gfship_particles * pl, int base, int np, const unsigned * cell, unsigned * block)
+{
+  const int grid = (np + FEED_BLOCK - 1)/FEED_BLOCK;
+  double * mass = pl->mass + base, * volume = pl->volume + base;
+  hipLaunchKernelGGL (feed_count_kernel, dim3 (grid), dim3 (FEED_BLOCK), 0, pl->stream, np, cell, mass, block);
+  hipLaunchKernelGGL (feed_scan_kernel, dim3 (1), dim3 (FEED_BLOCK), 0, pl->stream, grid, block, pl->d_idlast);
+  hipLaunchKernelGGL (feed_scatter_kernel, dim3 (grid), dim3 (FEED_BLOCK), 0, pl->stream, np, cell, block,
+		      mass, volume, pl->dia + base, pl->rb + base, pl->id + base, pl->alive + base);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
 // what gfship_feed_particle_create and the event refuse: the refusals of a GfsSourceParticulateVol
 // (source_check, particulate_sources.hip)
 static int feed_check (gfship_particles * pl)
@@ -140,6 +155,33 @@ static int feed_check (gfship_particles * pl)
   GFSHIP_CHECK (pl->dom->dim*pl->dom->depth < 32, GFSHIP_EUNSUPPORTED,
 		"%s: the %d-D box of level %d has 2^32 cells or more", what, pl->dom->dim, pl->dom->depth);
   return GFSHIP_OK;
+}
+
+// the table of variables of a GfsFeedParticle: C names, none of them a variable of the function itself, none twice
+static int feed_names_check (int nvars, const char * const * names, const void * vars, const char * kind)
+{
+  GFSHIP_CHECK (nvars >= 0 && (nvars == 0 || (names && vars)), GFSHIP_EINVAL, "invalid table of variables");
+  static const char * builtin[] = { "x", "y", "z", "t" };
+  for (int q = 0; q < nvars; q++) {
+    GFSHIP_CHECK (c_identifier (names[q]), GFSHIP_EINVAL, "variable %d of the table has no C name", q);
+    for (const char * b : builtin)
+      GFSHIP_CHECK (strcmp (names[q], b) != 0, GFSHIP_EINVAL,
+		    "`%s' is a variable of the function itself: it cannot name a %s", b, kind);
+    for (int p = 0; p < q; p++)
+      GFSHIP_CHECK (strcmp (names[q], names[p]) != 0, GFSHIP_EINVAL, "`%s' is in the table twice", names[q]);
+  }
+  return GFSHIP_OK;
+}
+
+// is the text a constant (gfs_function_read: a number is kept as f->val, and needs no compilation)?
+static bool feed_constant (const char * text, double * value)
+{
+  char * end = nullptr;
+  *value = strtod (text, &end);
+  while (end != text && (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r')) end++;
+  if (end != text && *end == '\0') return true;
+  *value = 0.;
+  return false;
 }
 
 static int feed_reserve (gfship_feed_particle * f, int np)
@@ -161,6 +203,58 @@ static int feed_reserve (gfship_feed_particle * f, int np)
   return GFSHIP_OK;
 }
 
+// does the tree have the variable `var' for a function to read at a leaf?  tree_has_variable, but not the variables
+// of an octree alone on a quadtree: the arrays of W, its gradients and its face values are allocated there too, and
+// nothing ever writes them
+static bool tree_feed_variable (gfship_particles * pl, int var)
+{
+  static const int octree_only[] = { GFSHIP_TREE_W, GFSHIP_TREE_GZ, GFSHIP_TREE_GMACZ, GFSHIP_TREE_UN4, GFSHIP_TREE_UN5,
+				     GFSHIP_TREE_BCW, GFSHIP_TREE_WPREV, GFSHIP_TREE_FZ, GFSHIP_TREE_WRELP };
+  if (pl->dim == 2)
+    for (int v : octree_only)
+      if (var == v) return false;
+  return tree_has_variable (pl->tree, var);
+}
+
+// gfship_feed_particle_event on a list of particulates of a tree: the passes of the box with the leaf as the cell,
+// on the stream of the tree
+static int tree_feed_event (gfship_feed_particle * f, int np, const double * pos)
+{
+  gfship_particles * pl = f->pl;
+  GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_feed_particle_event");
+  if (np == 0) return GFSHIP_OK;
+  GFSHIP_CHECK ((long) pl->n + np <= 0x7fffffffL, GFSHIP_ENOMEM, "the list would hold 2^31 slots or more");
+  TreeView V;
+  tree_view (pl->tree, &V);
+  GFSHIP_HIP (hipSetDevice (V.device));
+  std::vector<const double *> read[2];
+  for (int w = 0; w < 2; w++)
+    for (int var : f->read[w]) {
+      const double * a = tree_feed_variable (pl, var) ? tree_variable (pl->tree, var) : nullptr;
+      GFSHIP_CHECK (a != nullptr, GFSHIP_EINVAL, "the tree has no variable %d", var);
+      read[w].push_back (a);
+    }
+  int r;
+  if ((r = feed_reserve (f, np))) return r;
+  if ((r = particles_reserve (pl, pl->n + np))) return r;
+  /* the candidates come from pageable memory: the copy is staged before the call returns */
+  GFSHIP_HIP (hipMemcpyAsync (f->cand, pos, 3*(size_t) np*sizeof (double), hipMemcpyHostToDevice, V.stream));
+  const int base = pl->n;
+  if ((r = launch_tree_feed_gather (pl, base, np, f->cand, f->cell))) return r;
+  double * out[2] = { pl->mass + base, pl->volume + base };
+  for (int w = 0; w < 2; w++) {
+    if (f->fn[w])
+      r = rtc_launch_tree_cell (f->fn[w], V.stream, np, V.H.depth, V.H.off, f->cell, V.t, (int) read[w].size (),
+				read[w].data (), out[w]);
+    else
+      r = launch_fill (V.stream, np, f->value[w], out[w]);
+    if (r) return r;
+  }
+  if ((r = launch_feed_ids (pl, base, np, f->cell, f->block))) return r;
+  pl->n += np;
+  return GFSHIP_OK;
+}
+
 } // namespace gfship
 
 using namespace gfship;
@@ -175,29 +269,16 @@ int gfship_feed_particle_create (gfship_feed_particle ** out, gfship_particles *
   *out = nullptr;
   int r = feed_check (pl);
   if (r) return r;
-  GFSHIP_CHECK (nvars >= 0 && (nvars == 0 || (names && fields)), GFSHIP_EINVAL, "invalid table of variables");
+  if ((r = feed_names_check (nvars, names, fields, "field"))) return r;
   gfship_domain * dom = pl->dom;
-  static const char * builtin[] = { "x", "y", "z", "t" };
-  for (int q = 0; q < nvars; q++) {
-    GFSHIP_CHECK (c_identifier (names[q]), GFSHIP_EINVAL, "variable %d of the table has no C name", q);
-    for (const char * b : builtin)
-      GFSHIP_CHECK (strcmp (names[q], b) != 0, GFSHIP_EINVAL,
-		    "`%s' is a variable of the function itself: it cannot name a field", b);
-    for (int p = 0; p < q; p++)
-      GFSHIP_CHECK (strcmp (names[q], names[p]) != 0, GFSHIP_EINVAL, "`%s' is in the table twice", names[q]);
+  for (int q = 0; q < nvars; q++)
     if (!get_field (dom, fields[q])) return GFSHIP_EINVAL;
-  }
   gfship_feed_particle * f = new gfship_feed_particle;
   f->pl = pl;
   const char * text[2] = { mass, volume };
   for (int w = 0; w < 2; w++) {
     if (!text[w]) continue;
-    /* a constant (gfs_function_read: a number is kept as f->val) needs no compilation */
-    char * end = nullptr;
-    f->value[w] = strtod (text[w], &end);
-    while (end != text[w] && (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r')) end++;
-    if (end != text[w] && *end == '\0') continue;
-    f->value[w] = 0.;
+    if (feed_constant (text[w], &f->value[w])) continue;
     std::vector<const char *> named;
     for (int q = 0; q < nvars; q++)
       if (names_identifier (text[w], names[q])) {
@@ -218,6 +299,7 @@ int gfship_feed_particle_event (gfship_feed_particle * f, int np, const double *
   GFSHIP_CHECK (f != nullptr, GFSHIP_EINVAL, "null GfsFeedParticle");
   GFSHIP_CHECK (np >= 0 && (np == 0 || pos), GFSHIP_EINVAL, "invalid argument");
   gfship_particles * pl = f->pl;
+  if (pl && pl->tree) return tree_feed_event (f, np, pos);      /* a handle of gfship_tree_feed_particle_create */
   int r = feed_check (pl);
   if (r) return r;
   if (np == 0) return GFSHIP_OK;
@@ -246,13 +328,7 @@ int gfship_feed_particle_event (gfship_feed_particle * f, int np, const double *
       r = launch_fill (dom->stream, np, f->value[w], out[w]);
     if (r) return r;
   }
-  const int grid = (np + FEED_BLOCK - 1)/FEED_BLOCK;
-  hipLaunchKernelGGL (feed_count_kernel, dim3 (grid), dim3 (FEED_BLOCK), 0, dom->stream, np, f->cell, out[0],
-		      f->block);
-  hipLaunchKernelGGL (feed_scan_kernel, dim3 (1), dim3 (FEED_BLOCK), 0, dom->stream, grid, f->block, pl->d_idlast);
-  hipLaunchKernelGGL (feed_scatter_kernel, dim3 (grid), dim3 (FEED_BLOCK), 0, dom->stream, np, f->cell, f->block,
-		      out[0], out[1], pl->dia + base, pl->rb + base, pl->id + base, pl->alive + base);
-  GFSHIP_HIP (hipGetLastError ());
+  if ((r = launch_feed_ids (pl, base, np, f->cell, f->block))) return r;
   pl->n += np;
   return GFSHIP_OK;
 }
@@ -269,10 +345,9 @@ void gfship_feed_particle_destroy (gfship_feed_particle * f)
   delete f;
 }
 
-int gfship_particles_set_idlast (gfship_particles * pl, int idlast)
+// idlast of a list, of a box or of a tree, on its stream
+static int set_idlast (gfship_particles * pl, int idlast)
 {
-  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
-  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_set_idlast");
   GFSHIP_CHECK (idlast >= 0, GFSHIP_EINVAL, "idlast is a guint");
   const unsigned v = (unsigned) idlast;
   GFSHIP_HIP (hipMemcpyAsync (pl->d_idlast, &v, sizeof (unsigned), hipMemcpyHostToDevice, pl->stream));
@@ -280,14 +355,81 @@ int gfship_particles_set_idlast (gfship_particles * pl, int idlast)
   return GFSHIP_OK;
 }
 
-int gfship_particles_idlast (gfship_particles * pl)
+static int get_idlast (gfship_particles * pl)
 {
-  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
-  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_idlast");
   unsigned v = 0;
   GFSHIP_HIP (hipMemcpyAsync (&v, pl->d_idlast, sizeof (unsigned), hipMemcpyDeviceToHost, pl->stream));
   GFSHIP_HIP (hipStreamSynchronize (pl->stream));
   return (int) v;
+}
+
+int gfship_particles_set_idlast (gfship_particles * pl, int idlast)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_set_idlast");
+  return set_idlast (pl, idlast);
+}
+
+int gfship_particles_idlast (gfship_particles * pl)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_NO_TREE_LIST (pl, "gfship_particles_idlast");
+  return get_idlast (pl);
+}
+
+// gfs_feed_particle_read (:2435-2575) on a list made by gfship_particulates_create_tree: the table names variables
+// of the tree, read at the leaf, and the texts are compiled for the device of the tree
+int gfship_tree_feed_particle_create (gfship_feed_particle ** out, gfship_particles * pl, const char * mass,
+				      const char * volume, int nvars, const char * const * names, const int * vars)
+{
+  GFSHIP_CHECK (out != nullptr, GFSHIP_EINVAL, "null output pointer");
+  *out = nullptr;
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_tree_feed_particle_create");
+  int r = feed_names_check (nvars, names, vars, "variable of the tree");
+  if (r) return r;
+  for (int q = 0; q < nvars; q++)
+    GFSHIP_CHECK (tree_feed_variable (pl, vars[q]), GFSHIP_EINVAL,
+		  "`%s': the tree has no variable %d", names[q], vars[q]);
+  const int device = tree_device (pl->tree);
+  GFSHIP_HIP (hipSetDevice (device));
+  gfship_feed_particle * f = new gfship_feed_particle;
+  f->pl = pl;
+  const char * text[2] = { mass, volume };
+  for (int w = 0; w < 2; w++) {
+    if (!text[w]) continue;
+    if (feed_constant (text[w], &f->value[w])) continue;
+    std::vector<const char *> named;
+    for (int q = 0; q < nvars; q++)
+      if (names_identifier (text[w], names[q])) {
+	named.push_back (names[q]);
+	f->read[w].push_back (vars[q]);
+      }
+    if ((r = rtc_compile_tree_cell (device, pl->dim, text[w], (int) named.size (), named.data (), &f->fn[w]))) {
+      gfship_feed_particle_destroy (f);
+      return r;
+    }
+  }
+  *out = f;
+  return GFSHIP_OK;
+}
+
+int gfship_tree_particles_set_idlast (gfship_particles * pl, int idlast)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_CHECK (pl->tree != nullptr, GFSHIP_EUNSUPPORTED,
+		"gfship_tree_particles_set_idlast: a list of a box (gfship_particles_set_idlast)");
+  GFSHIP_HIP (hipSetDevice (tree_device (pl->tree)));
+  return set_idlast (pl, idlast);
+}
+
+int gfship_tree_particles_idlast (gfship_particles * pl)
+{
+  GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
+  GFSHIP_CHECK (pl->tree != nullptr, GFSHIP_EUNSUPPORTED,
+		"gfship_tree_particles_idlast: a list of a box (gfship_particles_idlast)");
+  GFSHIP_HIP (hipSetDevice (tree_device (pl->tree)));
+  return get_idlast (pl);
 }
 
 } // extern "C"

@@ -846,8 +846,7 @@ int gfship_particles_sort (gfship_particles * pl)
 int gfship::particles_reserve (gfship_particles * pl, int need)
 {
   if (need <= pl->cap) return GFSHIP_OK;
-  gfship_domain * dom = pl->dom;
-  GFSHIP_HIP (hipStreamSynchronize (dom->stream));
+  GFSHIP_HIP (hipStreamSynchronize (pl->stream));      /* of the box or of the tree */
   size_t m = std::max (need, 2*pl->cap), old = pl->cap;
   auto grow = [&] (void ** a, size_t elem, bool keep) -> hipError_t {
     void * nw = nullptr;

@@ -42,6 +42,13 @@ int  rtc_compile_tree_source (int device, int dim, const char * text, int nf, co
 int  rtc_launch_tree_source (RtcKernel * k, hipStream_t stream, int n, int dim, int depth, const int * off,
 			     const unsigned * cell, const double * rad, const double * const urel[3], double t,
 			     int nf, const double * const * fields, double * out);
+// the mass and the volume of a GfsFeedParticle on a list of a tree: the function of rtc_compile_cell with the leaf
+// of rtc_compile_tree_source as the cell (the same text and options; no Rad, Urelp ...), for every candidate o < n
+// with a leaf
+int  rtc_compile_tree_cell (int device, int dim, const char * text, int nf, const char * const * names,
+			    RtcKernel ** out);
+int  rtc_launch_tree_cell (RtcKernel * k, hipStream_t stream, int n, int depth, const int * off,
+			   const unsigned * cell, double t, int nf, const double * const * fields, double * out);
 }
 
 // a GfsSourceParticulateVol / ...Mass (particulate_sources.hip) on a list of a box, or of a tree (pl->tree: the
@@ -59,15 +66,18 @@ struct gfship_particulate_source {
   int cap = 0;
 };
 
-// a GfsFeedParticle (feed_particle.hip) on a list of particulates of a box: its two functions of the cell
-// (0: mass, 1: volume) and the work arrays of an event
+// a GfsFeedParticle (feed_particle.hip) on a list of particulates of a box, or of a tree (pl->tree: the variables
+// are GFSHIP_TREE_* numbers and the cell is the leaf): its two functions of the cell (0: mass, 1: volume) and the
+// work arrays of an event
 struct gfship_feed_particle {
   gfship_particles * pl = nullptr;
   gfship::RtcKernel * fn[2] = {};        // nullptr: the constant `value'
   double value[2] = {};
   std::vector<gfship_field> read[2];     // the fields each function names, in the order of its arguments
   double * cand = nullptr;               // 3 doubles per candidate
-  unsigned * cell = nullptr;             // per candidate: the linear number of its cell, or PSOURCE_NO_CELL
+  // per candidate: the linear number of its cell (a box), the index of its leaf in the concatenated levels (a
+  // tree), or PSOURCE_NO_CELL
+  unsigned * cell = nullptr;
   unsigned * block = nullptr;            // per block of candidates: accepted, then the id before its first
   int cap = 0;
 };
@@ -84,7 +94,7 @@ struct gfship_particles {
   unsigned * id = nullptr;
   unsigned char * alive = nullptr;
   unsigned * d_count = nullptr;
-  unsigned * d_idlast = nullptr;      // idlast of the GfsParticleList (particle_id, :1231-1234): lists of a box
+  unsigned * d_idlast = nullptr;      // idlast of the GfsParticleList (particle_id, :1231-1234), 0 at creation: every list
   // sort by cell
   unsigned * orig = nullptr;          // creation slot of the particle stored in each slot
   double * pos2[3] = {}, * old2[3] = {};   // gather targets (swapped with pos/old after a sort)
@@ -169,6 +179,13 @@ int particles_reserve (gfship_particles * pl, int need);
 // the position, pos_old = 0, force = 0, orig = its own number and the interpolated velocity of the fluid;
 // cell[i] = the linear number of the candidate's cell or PSOURCE_NO_CELL
 int launch_feed_gather (gfship_particles * pl, int base, int np, const double * cand, unsigned * cell);
+// the same on a list of particulates of a tree (tree_particles.hip): tree_locate and tree_interpolate of the event
+// kernels; cell[i] = the index of the candidate's leaf in the concatenated levels (Topo::gi) or PSOURCE_NO_CELL
+int launch_tree_feed_gather (gfship_particles * pl, int base, int np, const double * cand, unsigned * cell);
+// the ids of the np candidates that took the slots from `base' on (feed_particle.hip), after their mass and volume
+// are written: the accepted candidates per block, the scan that moves idlast, then id, flag, diameter and rb of
+// every slot; `block' holds one count per 256 candidates.  On the stream of the list, for a box and for a tree
+int launch_feed_ids (gfship_particles * pl, int base, int np, const unsigned * cell, unsigned * block);
 // a list on a tree (tree_particles.hip): the event of its tracers, the keys of gfship_particles_sort and their bits
 int tree_particle_list_event (gfship_particles * pl);
 int tree_particle_keys (gfship_particles * pl, int * bits);
@@ -200,8 +217,10 @@ int tree_particulate_source_event (gfship_particulate_source * s, double * info)
 #define GFSHIP_TREE_PARTICULATES_ONLY(pl, what) GFSHIP_CHECK ((pl)->tree && (pl)->particulate, GFSHIP_EUNSUPPORTED, \
     "%s needs a list of particulates of a tree (gfship_particulates_create_tree)", what)
 
-// coupling and migration exist on uniform boxes only, and a list of a tree is born as tracers
-// (gfship_particles_create_tree) or as particulates (gfship_particulates_create_tree)
+// the calls of a box: migration exists on uniform boxes only, and the coupling, the sources and the feed of a list
+// of a tree have entries of their own (gfship_tree_particulate_field ..., gfship_tree_particulate_source_create,
+// gfship_tree_feed_particle_create).  A list of a tree is born as tracers (gfship_particles_create_tree) or as
+// particulates (gfship_particulates_create_tree)
 #define GFSHIP_NO_TREE_LIST(pl, what) GFSHIP_CHECK (!(pl)->tree, GFSHIP_EUNSUPPORTED, \
     "%s: a particle list on a refined tree holds GfsParticle tracers only (no particulates, forces, " \
     "coupling or migration)", what)

@@ -298,12 +298,18 @@ int rtc_launch_source (RtcKernel * k, hipStream_t stream, int n, const Layout & 
 // level, and ftt_cell_pos is -0.5 + (i - 0.5)*2^-l, dyadic and exact.  The variables are arrays of all levels
 struct TreeSourceOffsets { int v[GFSHIP_MAXLEVEL + 2]; };
 
-int rtc_compile_tree_source (int device, int dim, const char * text, int nf, const char * const * names,
-			     RtcKernel ** out)
+// particle = false: the same kernel around a plain spatial GfsFunction at the leaf (the mass and the volume of a
+// GfsFeedParticle on a list of a tree, feed_particle.hip): no Rad, Urelp ... among its variables nor among the
+// kernel's arguments, as in compile_cell_function
+static int compile_tree_cell_function (int device, int dim, bool particle, const char * text, int nf,
+				       const char * const * names, RtcKernel ** out)
 {
   const bool d3 = dim == 3;
-  std::string sig = "static __device__ double gfship_f (double Rad, double Urelp, double Vrelp, ";
-  if (d3) sig += "double Wrelp, ";
+  std::string sig = "static __device__ double gfship_f (";
+  if (particle) {
+    sig += "double Rad, double Urelp, double Vrelp, ";
+    if (d3) sig += "double Wrelp, ";
+  }
   sig += "double x, double y, double z, double t";
   std::string params, values;
   for (int q = 0; q < nf; q++) {
@@ -316,8 +322,13 @@ int rtc_compile_tree_source (int device, int dim, const char * text, int nf, con
   std::string kern =
     "struct gfship_offsets { int v[" + maxlevel + " + 2]; };\n"
     "extern \"C\" __global__ void gfship_tree_psource (int n, int depth, gfship_offsets off,\n"
-    "    const unsigned * cell, const double * rad, const double * urel, const double * vrel,\n";
-  if (d3) kern += "    const double * wrel,\n";
+    "    const unsigned * cell,";
+  if (particle) {
+    kern += " const double * rad, const double * urel, const double * vrel,\n";
+    if (d3) kern += "    const double * wrel,\n";
+  }
+  else
+    kern += "\n";
   kern += "    double t,\n" + params + "    double * out)\n"
     "{\n"
     "  int o = blockIdx.x*blockDim.x + threadIdx.x;\n"
@@ -334,12 +345,44 @@ int rtc_compile_tree_source (int device, int dim, const char * text, int nf, con
   kern +=
     "  (void) k;\n"
     "  const double h = 1./(double) (1u << l);\n"      /* ftt_cell_pos: dyadic, exact */
-    "  out[o] = gfship_f (rad[o], urel[o], vrel[o], ";
-  if (d3) kern += "wrel[o], ";
+    "  out[o] = gfship_f (";
+  if (particle) {
+    kern += "rad[o], urel[o], vrel[o], ";
+    if (d3) kern += "wrel[o], ";
+  }
   kern += "-0.5 + (i - 0.5)*h, -0.5 + (j - 0.5)*h, ";
   kern += d3 ? "-0.5 + (k - 0.5)*h" : "0.";
   kern += ", t" + values + ");\n}\n";
   return rtc_compile (device, text, sig.c_str (), kern.c_str (), "gfship_tree_psource", out);
+}
+
+int rtc_compile_tree_source (int device, int dim, const char * text, int nf, const char * const * names,
+			     RtcKernel ** out)
+{
+  return compile_tree_cell_function (device, dim, true, text, nf, names, out);
+}
+
+// the mass and the volume of a GfsFeedParticle on a list of a tree (gfs_function_value (feedp->mass, cell) with cell =
+// the leaf of gfs_domain_locate (pos, -1), modules/particulatecommon.c:2382, 2394-2395)
+int rtc_compile_tree_cell (int device, int dim, const char * text, int nf, const char * const * names,
+			   RtcKernel ** out)
+{
+  return compile_tree_cell_function (device, dim, false, text, nf, names, out);
+}
+
+int rtc_launch_tree_cell (RtcKernel * k, hipStream_t stream, int n, int depth, const int * off,
+			  const unsigned * cell, double t, int nf, const double * const * fields, double * out)
+{
+  if (n <= 0) return GFSHIP_OK;
+  TreeSourceOffsets O;
+  for (int l = 0; l < GFSHIP_MAXLEVEL + 2; l++) O.v[l] = off[l];
+  std::vector<const double *> f (fields, fields + nf);
+  std::vector<void *> args = { &n, &depth, &O, &cell, &t };
+  for (int q = 0; q < nf; q++) args.push_back (&f[q]);
+  args.push_back (&out);
+  GFSHIP_HIP (hipModuleLaunchKernel (k->fn, (unsigned) ((n + 255)/256), 1, 1, 256, 1, 1, 0, stream, args.data (),
+				     nullptr));
+  return GFSHIP_OK;
 }
 
 int rtc_launch_tree_source (RtcKernel * k, hipStream_t stream, int n, int dim, int depth, const int * off,

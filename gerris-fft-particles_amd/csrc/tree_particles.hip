@@ -898,6 +898,55 @@ tree_particulate_source_gather_kernel (TreeSamp S, TreeSourceGatherArgs A)
     A.urel[a][o] = fvel[a] - A.vel[a][o];
 }
 
+// GfsFeedParticle on a list of a tree: feed_particulate (:2377-2393) for one candidate per thread,
+// gfs_domain_locate (pos, -1) -- the leaf, whatever its level; no wrap of a periodic side -- then vel[c] =
+// gfs_interpolate (cell, pos, u[c]) with the corner interpolators of the event kernels (vel.z = 0. in 2-D); the slot
+// is that of a new object (pos_old = 0, force = 0) whose fate the ordered passes of feed_particle.hip decide
+// (feed_gather_kernel, particles.hip, is this kernel on a box)
+struct TreeFeedGatherArgs {
+  int np, base;
+  const double * cand;
+  const double * u[3];
+  double * pos[3], * old[3], * vel[3], * force[3];
+  unsigned * orig, * cell;
+};
+
+template <int DIM>
+__global__ void __launch_bounds__(256)
+tree_feed_gather_kernel (TreeSamp S, TreeFeedGatherArgs A)
+{
+  const int i = blockIdx.x*blockDim.x + threadIdx.x;
+  if (i >= A.np) return;
+  const int s = A.base + i;
+  const double p[3] = { A.cand[3*(size_t) i], A.cand[3*(size_t) i + 1], A.cand[3*(size_t) i + 2] };
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    A.pos[c][s] = p[c];
+    A.old[c][s] = 0.;
+    A.force[c][s] = 0.;
+  }
+  A.orig[s] = (unsigned) s;
+  double vel[3] = { 0., 0., 0. };
+  unsigned cell = PSOURCE_NO_CELL;
+  /* the readers of a list of a quadtree take z = 0. for the walk of the tree: so does the candidate */
+  const double q[3] = { p[0], p[1], DIM == 3 ? p[2] : 0. };
+  Leaf c;
+  if (tree_locate<DIM> (S, q, c)) {
+    cell = (unsigned) c.g;
+    Vars<DIM> uu;
+#pragma unroll
+    for (int a = 0; a < DIM; a++) uu.p[a] = A.u[a];
+    double fvel[DIM];
+    tree_interpolate<DIM, DIM> (S, uu, c, q, fvel);
+#pragma unroll
+    for (int a = 0; a < DIM; a++) vel[a] = fvel[a];
+  }
+  A.cell[i] = cell;
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+    A.vel[a][s] = vel[a];
+}
+
 // gfs_cell_reset with max_depth = 1 (:2844, :3004): the few interior cells of levels 0 and 1 the traversal reaches
 struct TreeSourceResetCells { int n, g[9]; };
 
@@ -1152,6 +1201,31 @@ int tree_particle_keys (gfship_particles * pl, int * bits)
   int b = 0;
   while (b < 31 && (V.ncell >> b)) b++;
   *bits = b + 1;
+  return GFSHIP_OK;
+}
+
+int launch_tree_feed_gather (gfship_particles * pl, int base, int np, const double * cand, unsigned * cell)
+{
+  TreeView V;
+  SamplerTables * S;
+  int r = sampler_get (pl->tree, &V, &S);
+  if (r) return r;
+  TreeFeedGatherArgs A;
+  A.np = np; A.base = base;
+  A.cand = cand;
+  const int uvar[3] = { GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP_TREE_W };
+  for (int c = 0; c < 3; c++) {
+    A.u[c] = c < V.H.dim ? tree_variable (pl->tree, uvar[c]) : nullptr;
+    A.pos[c] = pl->pos[c]; A.old[c] = pl->old[c];
+    A.vel[c] = pl->vel[c]; A.force[c] = pl->force[c];
+  }
+  A.orig = pl->orig; A.cell = cell;
+  const int block = 256, grid = (np + block - 1)/block;
+  if (V.H.dim == 3)
+    hipLaunchKernelGGL (tree_feed_gather_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), A);
+  else
+    hipLaunchKernelGGL (tree_feed_gather_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), A);
+  GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
 

@@ -235,6 +235,10 @@ SIGNATURES = {
     "gfship_tree_particulate_source_create": (_i, [C.POINTER(_vp), _vp, _i, C.c_char_p, _i, C.POINTER(C.c_char_p),
                                                    C.POINTER(_i)]),
     "gfship_tree_particulate_source_set_fields": (_i, [_vp, _i, C.POINTER(_i), _i]),
+    "gfship_tree_feed_particle_create": (_i, [C.POINTER(_vp), _vp, C.c_char_p, C.c_char_p, _i,
+                                              C.POINTER(C.c_char_p), C.POINTER(_i)]),
+    "gfship_tree_particles_set_idlast": (_i, [_vp, _i]),
+    "gfship_tree_particles_idlast": (_i, [_vp]),
 }
 
 
@@ -1033,6 +1037,22 @@ class TreeParticulateSource(ParticulateSource):
             self.ptr, -1 if rad is None else int(rad), (_i * 3)(*u), -1 if deposit is None else int(deposit)))
 
 
+class TreeFeedParticle(FeedParticle):
+    """GfsFeedParticle on a list of Tree.particulates.  mass, volume: as for FeedParticle; variables: a dict name ->
+    Tree.* number, read at the leaf of the candidate.  event and close are those of FeedParticle.  Close it before its
+    list."""
+
+    def __init__(self, tree, plist, mass=None, volume=None, variables=None):
+        variables = dict(variables or {})
+        names = (C.c_char_p * max(len(variables), 1))(*[k.encode() for k in variables])
+        numbers = (_i * max(len(variables), 1))(*[int(v) for v in variables.values()])
+        p = _vp()
+        _check(lib().gfship_tree_feed_particle_create(
+            C.byref(p), plist.ptr, None if mass is None else str(mass).encode(),
+            None if volume is None else str(volume).encode(), len(variables), names, numbers))
+        self.ptr, self.plist, self.tree = p, plist, tree
+
+
 REFINE_FN = C.CFUNCTYPE(C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p)
 
 
@@ -1223,6 +1243,14 @@ class Tree:
     def source_particulate_event(self, pl):
         """forces_on_fluid, then spread_forces"""
         _check(lib().gfship_tree_source_particulate_event(pl.ptr))
+
+    # idlast of a list of this tree, tracers or particulates (ParticleList.idlast is the call of a box)
+    def idlast(self, pl):
+        """idlast of the GfsParticleList: the id the last particle a TreeFeedParticle added took"""
+        return _check(lib().gfship_tree_particles_idlast(pl.ptr))
+
+    def set_idlast(self, pl, value):
+        _check(lib().gfship_tree_particles_set_idlast(pl.ptr, int(value)))
 
     def set_source_fields(self, on=True):
         """U, V(, W) take the velocity source of Tree.FX ... (GfsSourceParticulate in the time step)"""

@@ -651,7 +651,8 @@ void gfship_particulate_source_destroy (gfship_particulate_source * src);
 int  gfship_particles_download_volume (gfship_particles * pl, double * volume);
 
 /* Particles join a list during a run: GfsFeedParticle (modules/particulatecommon.c:2375-2647), an object on a
-   list of particulates of a uniform box.  GFSHIP_EUNSUPPORTED on a list of a tree, on a list of tracers (the
+   list of particulates of a uniform box.  GFSHIP_EUNSUPPORTED on a list of a tree (its object is made by
+   gfship_tree_feed_particle_create, below, and its idlast has calls of its own), on a list of tracers (the
    reference would write the members of a GfsParticulate into GfsParticle objects), on a box with
    GFSHIP_SIDE_EXTERNAL sides (mpi_particle_numbering, :51-87, is not written) and on a box of 2^32 cells or more.
    gfship_feed_particle_create (gfs_feed_particle_read, :2435-2575): mass and volume are the GfsFunction texts of
@@ -1141,6 +1142,47 @@ int  gfship_tree_particulate_source_create (gfship_particulate_source ** src, gf
 					    const int * vars);
 int  gfship_tree_particulate_source_set_fields (gfship_particulate_source * src, int rad, const int urel[3],
 						int deposit);
+
+/* GfsFeedParticle (modules/particulatecommon.c:2375-2647) on a refined quadtree / octree, on a list made by
+   gfship_particulates_create_tree (GFSHIP_EUNSUPPORTED on a list of tracers of a tree and on a list of a box;
+   gfship_feed_particle_create, gfship_particles_set_idlast and gfship_particles_idlast keep refusing a list of a
+   tree).
+   gfship_tree_feed_particle_create (gfs_feed_particle_read, :2435-2575): mass, volume and NULL as for
+   gfship_feed_particle_create -- a number, C text (an expression or a { block } with a return) or NULL, the constant
+   0 -- compiled for the device of the tree with the text and the options of the function of
+   gfship_tree_particulate_source_create (-ffp-contract=off, the device's libm), without Rad, Urelp ...: those are what
+   the table says, or unknown to the compiler.  vars[q] is the GFSHIP_TREE_* variable the name names[q] reads at the
+   leaf.  A name that is x, y, z or t, a name given twice or a name that is no C identifier, and a variable the tree
+   does not have now (GFSHIP_TREE_W on a quadtree, a tracer that was not added, a variable no call has allocated
+   yet), are GFSHIP_EINVAL; a text that does not compile is GFSHIP_EINVAL with the compiler's messages in
+   gfship_last_error (), as on the box.
+   gfship_feed_particle_event and gfship_feed_particle_destroy work on such a handle (it knows what made it).  Per
+   event, on the stream of the tree, for each of the np candidates in the order given, feed_particulate (:2377-2402):
+   cell = gfs_domain_locate (pos, -1), the leaf whatever its level.  The position is not wrapped: a candidate outside a
+   periodic side has no cell, exactly like one outside a GfsBoundary side, and is dropped; one exactly on a side of
+   the box (a coordinate of 0.5 or -0.5) is inside (ftt_cell_locate tests with >).  vel[c] = gfs_interpolate (cell,
+   pos, U ...) for c < dim (vel.z = 0. in 2-D) as gfship_tree_interpolate reads it, ghost cells included, the bits of
+   Urelp + vel of a source: call the event after gfship_tree_start / _step, or after an upload that gives the ghosts.
+   mass and volume = the two functions at the leaf: x, y, z = ftt_cell_pos of the leaf (dyadic, of its level), t =
+   gfship_tree_time, any other name = its variable at the leaf.  Then add_particulate (:1237-1276) as on the box: a
+   candidate with mass < 1.e-20 is dropped before it takes an id (a NaN is not less: it joins), any other joins the END
+   of the list with id = ++idlast, force = 0 and pos_old = 0, in candidate order; the ids are an ordered count
+   (never an atomic counter), the same from run to run.  The np candidates take the np slots after those in use; a
+   dropped candidate leaves a dead slot (gfship_particles_slots counts it, gfship_particles_count does not, the
+   next gfship_particles_sort moves it behind the live ones).  All three coordinates of a candidate are kept on a
+   quadtree as well; gfship_particles_download returns z = 0 there.  The arrays of the list, of its forces, of its
+   coupling and of its sources follow a list that has grown; nothing waits for the device but such a growth.  A list
+   that would hold 2^31 slots or more is GFSHIP_ENOMEM.  The diameter (:552) and rb (:2091) of a new particle are
+   values of the device's pow, as on the box.  np = 0 does nothing.
+   gfship_tree_particles_set_idlast (idlast >= 0, else GFSHIP_EINVAL), gfship_tree_particles_idlast: idlast of the
+   GfsParticleList (particle_id, :1231-1234; 0 from gfs_particle_list_init) of any list of a tree, tracers included;
+   GFSHIP_EUNSUPPORTED on a list of a box.  The getter waits for the stream of the tree.
+   Destroy the feed before its list, and the list before its tree. */
+int  gfship_tree_feed_particle_create (gfship_feed_particle ** feed, gfship_particles * pl,
+				       const char * mass, const char * volume,
+				       int nvars, const char * const * names, const int * vars);
+int  gfship_tree_particles_set_idlast (gfship_particles * pl, int idlast);
+int  gfship_tree_particles_idlast (gfship_particles * pl);
 
 /* ---- instrumentation -------------------------------------------------------------------- */
 
