@@ -123,6 +123,7 @@ void gfship_domain_destroy (gfship_domain * dom)
   comm_free (dom);
   mpi_order_free (dom);
   skew_free (dom);
+  droplets_free (dom);
   if (dom->d_scratch) (void) hipFree (dom->d_scratch);
   if (dom->cfl_partial) (void) hipFree (dom->cfl_partial);
   for (int d = 0; d < 6; d++) {

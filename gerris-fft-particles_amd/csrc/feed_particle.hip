@@ -141,9 +141,8 @@ int launch_feed_ids (gfship_particles * pl, int base, int np, const unsigned * c
 
 // what gfship_feed_particle_create and the event refuse: the refusals of a GfsSourceParticulateVol
 // (source_check, particulate_sources.hip)
-static int feed_check (gfship_particles * pl)
+int feed_check (gfship_particles * pl, const char * what)
 {
-  const char * what = "GfsFeedParticle";
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
   GFSHIP_NO_TREE_LIST (pl, what);
   GFSHIP_CHECK (pl->particulate, GFSHIP_EUNSUPPORTED,
@@ -158,7 +157,7 @@ static int feed_check (gfship_particles * pl)
 }
 
 // the table of variables of a GfsFeedParticle: C names, none of them a variable of the function itself, none twice
-static int feed_names_check (int nvars, const char * const * names, const void * vars, const char * kind)
+int feed_names_check (int nvars, const char * const * names, const void * vars, const char * kind)
 {
   GFSHIP_CHECK (nvars >= 0 && (nvars == 0 || (names && vars)), GFSHIP_EINVAL, "invalid table of variables");
   static const char * builtin[] = { "x", "y", "z", "t" };
@@ -174,7 +173,7 @@ static int feed_names_check (int nvars, const char * const * names, const void *
 }
 
 // is the text a constant (gfs_function_read: a number is kept as f->val, and needs no compilation)?
-static bool feed_constant (const char * text, double * value)
+bool feed_constant (const char * text, double * value)
 {
   char * end = nullptr;
   *value = strtod (text, &end);

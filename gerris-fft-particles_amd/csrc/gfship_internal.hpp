@@ -174,6 +174,7 @@ struct gfship_domain {
   // its relax loop, together with computing it (launch_residual_restrict_pack): the next cycle skips that
   // restriction; -1 none
   int restricted_level = -1;
+  void * droplets = nullptr;      // the work arrays of the droplet labelling (droplets.hip), kept between calls
 };
 
 namespace gfship {
@@ -275,6 +276,7 @@ int launch_relax_mpi_first (gfship_domain * dom, unsigned dimension, int level, 
 			    double * u, const double * rhs, const double * dia, const RelaxOp * op,
 			    int (* after_shell) (void *), void * ctx);
 void mpi_order_free (gfship_domain * dom);
+void droplets_free (gfship_domain * dom);    // droplets.hip
 int launch_relax_loop_small (gfship_domain * dom, unsigned dimension, int level, double omega,
 			     Field * dp, Field * ubc, const double * rhs, const double * dia,
 			     unsigned nrelax, bool * done, const RelaxOp * op = nullptr);

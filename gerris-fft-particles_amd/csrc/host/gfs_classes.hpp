@@ -646,6 +646,120 @@ inline void read_feed_particle (Run & R, Reader & r, Object & ob)
   };
 }
 
+// the variable of a GfsDropletToParticle or of a GfsRemoveDroplets, and the variables its function names: they must
+// exist and be kept on the device
+inline int read_droplet_variable (Run & R, Reader & r, const Object & ob)
+{
+  if (r.at_end_of_object () || r.peek (false) == '{')
+    r.fail ("expecting a string (variable)");
+  const std::string vname = r.word (false);
+  const int v = R.var_index (vname);
+  if (v < 0) r.fail ("unknown variable `" + vname + "'");
+  if (!R.on_device (vname))
+    r.fail ("Gfs" + ob.cls + " works on `" + vname +
+            "', which is not kept on the device (the variables of the simulation, tracers and the variables "
+            "of GfsParticulateField, GfsSourceParticulate, GfsSourceParticulateVol and ...Mass are)");
+  return v;
+}
+
+inline void droplet_function_reads (Run & R, Reader & r, const Object & ob, const std::string & text,
+                                    std::vector<std::string> & reads)
+{
+  for (const std::string & id : FunctionSet::identifiers (text)) {
+    if (id == "x" || id == "y" || id == "z" || id == "t" || R.var_index (id) < 0)
+      continue;                                    /* anything else is left to the compiler of the device */
+    if (!R.on_device (id))
+      r.fail ("the function of Gfs" + ob.cls + " reads `" + id +
+              "', which is not kept on the device (the variables of the simulation, tracers and the variables "
+              "of GfsParticulateField, GfsSourceParticulate, GfsSourceParticulateVol and ...Mass are)");
+    if (std::find (reads.begin (), reads.end (), id) == reads.end ())
+      reads.push_back (id);
+  }
+}
+
+inline void read_droplet_to_particle (Run & R, Reader & r, Object & ob)
+{
+  // gfs_droplet_to_particle_read (modules/particulatecommon.c:1407-1467):
+  //   GfsDropletToParticle [{ event }] LIST VARIABLE [{ min = I reset = X density = X }] [FUNCTION]
+  // LIST is the `*name' of a GfsParticleList read above; the droplets of VARIABLE (or of FUNCTION, evaluated at
+  // every cell on the device) smaller than min cells join the list (gfship_droplet_to_particle_create)
+  read_event_params (r, *ob.e);
+  ParticleSpec * ps = read_particulate_list_name (R, r, ob);
+  R.droplet_to_particles.emplace_back (new DropletToParticleSpec);
+  DropletToParticleSpec * sp = R.droplet_to_particles.back ().get ();
+  sp->ps = ps;
+  sp->line = ob.line;
+  sp->c = read_droplet_variable (R, r, ob);
+  if (r.peek (false) == '{') {                   /* gts_file_assign_variables, :1448-1461 */
+    Reader b = block (r);
+    while (!b.eof ()) {
+      if (b.peek () == '{' || b.peek () == '=') b.fail ("expecting a keyword");
+      const std::string k = b.word ();
+      if (k != "min" && k != "reset" && k != "density") b.fail ("unknown identifier `" + k + "'");
+      if (b.peek (false) != '=') b.fail ("expecting `='");
+      b.expect ('=');
+      const std::string w = b.word ();
+      char * end = nullptr;
+      if (k == "min") {
+        const long m = strtol (w.c_str (), &end, 10);
+        if (w.empty () || *end != '\0') b.fail ("expecting an integer (min)");
+        sp->min = (int) m;
+      }
+      else {
+        if (!Reader::is_number (w)) b.fail ("expecting a number (" + k + ")");
+        (k == "reset" ? sp->reset : sp->density) = atof (w.c_str ());
+      }
+    }
+  }
+  if (!r.at_end_of_object ()) {                  /* :1463-1466 */
+    const FunctionText t = r.function ();
+    sp->function = t.text;
+    droplet_function_reads (R, r, ob, t.text, sp->reads);
+  }
+  ob.e->action = [&R, sp] () {
+    /* mass = volume/alpha at the cell of the new particle: alpha at the time of the event */
+    if (refresh_alpha_cell (R))
+      exit (1);
+    must (gfship_droplet_to_particle_event (sp->handle, nullptr));
+    R.vars[sp->c].host_time = -1.;
+  };
+}
+
+inline void read_remove_droplets (Run & R, Reader & r, Object & ob)
+{
+  // gfs_remove_droplets_read (src/event.c:2155-2190):  GfsRemoveDroplets [{ event }] VARIABLE MIN [FUNCTION [VAL]]
+  // the droplets of FUNCTION (or of VARIABLE) smaller than MIN cells get VARIABLE = VAL (gfship_remove_droplets).
+  // FUNCTION: the name of a variable (gfs_function_get_variable, :2138); the library has no entry that evaluates
+  // any other function into a temporary variable
+  read_event_params (r, *ob.e);
+  const int c = read_droplet_variable (R, r, ob);
+  if (r.at_end_of_object ()) r.fail ("expecting an integer (min)");
+  const std::string w = r.word (false);
+  char * end = nullptr;
+  const long min = strtol (w.c_str (), &end, 10);
+  if (w.empty () || *end != '\0') r.fail ("expecting an integer (min)");
+  int mask = c;
+  double val = 0.;
+  if (!r.at_end_of_object ()) {
+    const std::string f = r.word (false);
+    mask = R.var_index (f);
+    if (mask < 0 && Reader::is_number (f))
+      r.fail ("the function of GfsRemoveDroplets is the name of a variable here: the constant `" + f +
+              "' is not supported");
+    if (mask < 0)
+      r.fail ("the function of GfsRemoveDroplets is the name of a variable here: `" + f + "' is none");
+    if (!R.on_device (f))
+      r.fail ("the function of GfsRemoveDroplets reads `" + f +
+              "', which is not kept on the device (the variables of the simulation, tracers and the variables "
+              "of GfsParticulateField, GfsSourceParticulate, GfsSourceParticulateVol and ...Mass are)");
+    if (!r.at_end_of_object ()) val = r.number ();
+  }
+  ob.e->action = [&R, c, mask, min, val] () {
+    must (gfship_remove_droplets (R.dom, R.vars[mask].dev, R.vars[c].dev, (int) min, val));
+    R.vars[c].host_time = -1.;
+  };
+}
+
 // the optional level that ends the outputs of modules/fft.c
 inline void skip_level (Reader & r)
 {
@@ -1114,6 +1228,9 @@ inline const ClassRow class_table[] = {
   { "SourceParticulateMass", read_source_particulate_change, EVENT },    //   the masses of a list change (uniform boxes)
   { "FeedParticle", read_feed_particle, EVENT },          // LIST { nparts xfeed yfeed zfeed mass volume }: particles
                                                           //   join a list of particulates (uniform boxes)
+  { "DropletToParticle", read_droplet_to_particle, EVENT },   // LIST VARIABLE [{ min reset density }] [FUNCTION]: small
+                                                          //   droplets of a tracer join a list (uniform boxes)
+  { "RemoveDroplets", read_remove_droplets, EVENT },      // VARIABLE MIN [VARIABLE [VAL]] (uniform boxes)
   { "OutputEnergySpectra", read_output_energy_spectra, OUT },
   { "OutputSpectra", read_output_spectra, OUT },
   { "VariableTurbulentViscosity", read_variable_turbulent_viscosity, EVENT },

@@ -955,6 +955,21 @@ inline int create_simulation (Run & R, gfship_field & div)
       return 1;
     }
   }
+  // GfsDropletToParticle: the function compiled for the device, with the device variables it names
+  for (auto & sp : R.droplet_to_particles) {
+    std::vector<const char *> names;
+    std::vector<gfship_field> fields;
+    for (const std::string & nm : sp->reads) {
+      names.push_back (nm.c_str ());
+      fields.push_back (R.vars[R.var_index (nm)].dev);
+    }
+    if (gfship_droplet_to_particle_create (&sp->handle, sp->ps->pl, R.vars[sp->c].dev, sp->min, sp->reset, sp->density,
+                                           sp->function.empty () ? nullptr : sp->function.c_str (), (int) names.size (),
+                                           names.data (), fields.data ()) < 0) {
+      fprintf (stderr, "gfship: line %d: %s\n", sp->line, gfship_last_error ());
+      return 1;
+    }
+  }
   set_boundary_conditions (R);
   apply_init (R);
   for (auto & is : R.init_spectra) {
@@ -1194,6 +1209,7 @@ inline int run (Run & R)
   if (!R.particles_out.empty () && write_particles (R)) return 1;
   for (auto & sp : R.particulate_sources) gfship_particulate_source_destroy (sp->src);
   for (auto & sp : R.feed_particles) gfship_feed_particle_destroy (sp->handle);
+  for (auto & sp : R.droplet_to_particles) gfship_droplet_to_particle_destroy (sp->handle);
   for (auto & ps : R.plists) gfship_particles_destroy (ps->pl);
   for (auto & o : R.outputs) o->close ();
   gfship_sim_destroy (R.sim);

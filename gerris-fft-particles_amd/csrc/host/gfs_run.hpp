@@ -201,6 +201,20 @@ struct FeedParticleSpec {
   gfship_feed_particle * handle = nullptr;
 };
 
+// GfsDropletToParticle (modules/particulatecommon.c:1163-1527): the list, the variable, min, reset and density
+// (gfs_droplet_to_particle_init, :1492-1497), and the text of the optional function with the device variables it
+// names
+struct DropletToParticleSpec {
+  ParticleSpec * ps = nullptr;
+  int line = 0;
+  int c = -1;                                    // the variable
+  int min = 20;
+  double reset = 0., density = 1.;
+  std::string function;                          // "" = none
+  std::vector<std::string> reads;
+  gfship_droplet_to_particle * handle = nullptr;
+};
+
 // a cell: its indices on its level (1..2^l inside the box; k = 0 in 2-D)
 struct Cell { int i, j, k, l; };
 
@@ -247,6 +261,7 @@ struct Run {
   std::vector<std::unique_ptr<SourceParticulateSpec>> source_particulates;
   std::vector<std::unique_ptr<ParticulateSourceSpec>> particulate_sources;
   std::vector<std::unique_ptr<FeedParticleSpec>> feed_particles;
+  std::vector<std::unique_ptr<DropletToParticleSpec>> droplet_to_particles;
   // a variable of the file that is kept on the device: those of the simulation, the tracers and device_vars
   bool on_device (const std::string & name) const {
     if (name == "P" || name == "Pmac" || velocity_component (name) >= 0) return true;

@@ -186,6 +186,11 @@ int launch_tree_feed_gather (gfship_particles * pl, int base, int np, const doub
 // are written: the accepted candidates per block, the scan that moves idlast, then id, flag, diameter and rb of
 // every slot; `block' holds one count per 256 candidates.  On the stream of the list, for a box and for a tree
 int launch_feed_ids (gfship_particles * pl, int base, int np, const unsigned * cell, unsigned * block);
+// what an object that adds particulates to a list of a box refuses (feed_particle.hip): a list of a tree, a list of
+// tracers, GfsBoundaryMpi sides, 2^32 cells or more; the checks of its table of variables; is a text a number?
+int feed_check (gfship_particles * pl, const char * what = "GfsFeedParticle");
+int feed_names_check (int nvars, const char * const * names, const void * vars, const char * kind);
+bool feed_constant (const char * text, double * value);
 // a list on a tree (tree_particles.hip): the event of its tracers, the keys of gfship_particles_sort and their bits
 int tree_particle_list_event (gfship_particles * pl);
 int tree_particle_keys (gfship_particles * pl, int * bits);

@@ -239,6 +239,13 @@ SIGNATURES = {
                                               C.POINTER(C.c_char_p), C.POINTER(_i)]),
     "gfship_tree_particles_set_idlast": (_i, [_vp, _i]),
     "gfship_tree_particles_idlast": (_i, [_vp]),
+    "gfship_tag_droplets": (_i, [_vp, _i, _i, C.POINTER(C.c_uint)]),
+    "gfship_tag_droplets_time": (_i, [_vp, _i, _i, _i, _pd]),
+    "gfship_remove_droplets": (_i, [_vp, _i, _i, _i, C.c_double]),
+    "gfship_droplet_to_particle_create": (_i, [C.POINTER(_vp), _vp, _i, _i, C.c_double, C.c_double, C.c_char_p, _i,
+                                               C.POINTER(C.c_char_p), C.POINTER(_i)]),
+    "gfship_droplet_to_particle_event": (_i, [_vp, C.POINTER(C.c_uint)]),
+    "gfship_droplet_to_particle_destroy": (None, [_vp]),
 }
 
 
@@ -419,6 +426,24 @@ class Domain:
     def bc(self, v, v1=None, level=None):
         level = self.depth if level is None else level
         _check(lib().gfship_bc(self.ptr, v.h, (v1 or v).h, level))
+
+    def tag_droplets(self, c, tag):
+        """gfs_domain_tag_droplets: the leaves of `tag' get the index (1 ..) of their droplet of c, 0 outside;
+        returns the number of droplets"""
+        n = C.c_uint(0)
+        _check(lib().gfship_tag_droplets(self.ptr, c.h, tag.h, C.byref(n)))
+        return int(n.value)
+
+    def time_tag_droplets(self, c, tag, reps=10):
+        """tag_droplets, measured between two events after a warm-up call: milliseconds per call"""
+        ms = C.c_double(0.)
+        _check(lib().gfship_tag_droplets_time(self.ptr, c.h, tag.h, int(reps), C.byref(ms)))
+        return float(ms.value)
+
+    def remove_droplets(self, c, v, min, val=0.):
+        """gfs_domain_remove_droplets: v = val in the droplets of c smaller than min cells (min < 0: all but the
+        -min largest)"""
+        _check(lib().gfship_remove_droplets(self.ptr, c.h, v.h, int(min), float(val)))
 
     def homogeneous_bc(self, ov, v, level=None):
         level = self.depth if level is None else level
@@ -1011,6 +1036,33 @@ class FeedParticle:
     def close(self):
         if self.ptr:
             lib().gfship_feed_particle_destroy(self.ptr)
+            self.ptr = None
+
+
+class DropletToParticle:
+    """GfsDropletToParticle on a list of particulates of a uniform box: the droplets of the Variable c (or of
+    `function': C text of x, y, z, t and of the names of `variables', a number, or the name of one of them) smaller
+    than min cells become particulates, and c = reset there.  Close it before its list."""
+
+    def __init__(self, plist, c, min=20, reset=0., density=1., function=None, variables=None):
+        variables = dict(variables or {})
+        names = (C.c_char_p * max(len(variables), 1))(*[k.encode() for k in variables])
+        fields = (_i * max(len(variables), 1))(*[v.h for v in variables.values()])
+        p = _vp()
+        _check(lib().gfship_droplet_to_particle_create(
+            C.byref(p), plist.ptr, c.h, int(min), float(reset), float(density),
+            None if function is None else str(function).encode(), len(variables), names, fields))
+        self.ptr, self.plist = p, plist
+
+    def event(self):
+        """one event; returns (droplets, the min used, particles made, cells reset)"""
+        info = (C.c_uint * 4)()
+        _check(lib().gfship_droplet_to_particle_event(self.ptr, info))
+        return tuple(int(v) for v in info)
+
+    def close(self):
+        if self.ptr:
+            lib().gfship_droplet_to_particle_destroy(self.ptr)
             self.ptr = None
 
 

@@ -691,6 +691,56 @@ void gfship_feed_particle_destroy (gfship_feed_particle * feed);
 int  gfship_particles_set_idlast (gfship_particles * pl, int idlast);
 int  gfship_particles_idlast (gfship_particles * pl);
 
+/* Droplets: the connected regions of the leaves where a variable exceeds THRESHOLD = 1e-4 (src/domain.c:3564),
+   across faces and through periodic sides, on a uniform box.  GFSHIP_EUNSUPPORTED on a box with
+   GFSHIP_SIDE_EXTERNAL sides (unify_tag_range, src/domain.c:3662-3687, is not written) and on a box of 2^32 cells or
+   more (a label is a 32-bit traversal index).  All on the stream of the domain.
+   gfship_tag_droplets (gfs_domain_tag_droplets, src/domain.c:3727-3796): the leaves of `tag' receive, as doubles,
+   the strictly positive index of their droplet, 0 outside; *n = the number of droplets.  The tag of a droplet is
+   1 + its rank by the smallest traversal index (FTT_PRE_ORDER over the leaves) of its cells, which is what the
+   flood fill, the `touch' table and the renumbering of the reference give.  The ghost cells of `tag' are left as
+   they are, and the ghost cells of c are not read: the reference's fill may run along the ghost cells of a side,
+   which with periodic or homogeneous Neumann ghosts joins nothing the interior does not.  c and
+   tag are two fields.  Host reads: n.
+   gfship_tag_droplets_time: a warm-up call, then `reps' calls between two events; *ms = milliseconds per call.
+   gfship_remove_droplets (gfs_domain_remove_droplets, src/domain.c:3836-3880): the droplets of c, their sizes
+   counting all their leaves (compute_droplet_size, :3805-3810); min >= 0 is the bound itself, min < 0 the
+   (-1 - min)-th largest size; nothing happens unless n > 0 && -min < n (:3851); v = val on the leaves of every
+   droplet with size < min (unsigned, :3812-3817), then the ghost cells of v by its boundary conditions.  c and v may
+   be the same field.  Host reads: n, and the size that a negative min selects.
+   GfsDropletToParticle (modules/particulatecommon.c:1163-1527), an object on a list of particulates of a uniform
+   box; the refusals are those of gfship_feed_particle_create.  gfship_droplet_to_particle_create
+   (gfs_droplet_to_particle_read, :1407-1467): c is the variable, min, reset and density the keywords (density is
+   kept and never used, as in the reference); function is the optional GfsFunction that makes the mask instead of c
+   -- NULL, a number (a constant), the name of a variable of the table (gfs_function_get_variable: that variable), or
+   C text of x, y, z, t and of the names of the table, compiled with hipRTC as the functions of a GfsFeedParticle are
+   (GFSHIP_EINVAL with the compiler's messages in gfship_last_error () where it does not compile) and evaluated at
+   every leaf at the start of an event.  Destroy the object before its list.
+   gfship_droplet_to_particle_event (gfs_droplet_to_particle_event, :1362-1404, convert_droplets, :1278-1348): the
+   droplets of the mask; per droplet, over its leaves in traversal order that touch no side of the box (every side
+   is a boundary, a periodic one included), sizes++, volume += h^dim*c, pos += the centre, vel += U
+   (compute_droplet_properties, :1194-1229: fp64 sums in that order, bit for bit), and boundary = whether its LAST
+   leaf touches a side; min as above; in tag order a droplet with boundary == 0 and 1 < sizes < min becomes a
+   candidate at pos/sizes with velocity vel/sizes, cell = gfs_domain_locate (pos), volume, mass = (alpha ?
+   1./alpha (cell) : 1.)*volume with alpha at the cell centres (gfship_sim_set_alpha_cell; GFSHIP_EUNSUPPORTED
+   where the simulation has an alpha and no such field), pos.z = vel.z = 0 in 2-D; add_particulate (:1237-1276) as
+   for gfship_feed_particle_event: the n droplets take the n slots after those in use, in tag order, and one that
+   does not convert or whose mass is below 1.e-20 leaves a dead slot and takes no id.  Then c = reset on the leaves
+   of every droplet with sizes < min (reset_small_fraction, :1187-1192: those on a side, of size 0 or 1, or refused
+   for their mass included), and the ghost cells of c by its boundary conditions.  info may be NULL; otherwise it
+   receives the number of droplets, the min used, the particles made and the cells reset (0, 0, 0 where the event
+   does nothing).  Host reads: n, and the size that a negative min selects; with info, one more at the end. */
+typedef struct gfship_droplet_to_particle gfship_droplet_to_particle;
+typedef struct { unsigned n, min, converted, reset; } gfship_droplet_info;
+int  gfship_tag_droplets (gfship_domain * dom, gfship_field c, gfship_field tag, unsigned * n);
+int  gfship_tag_droplets_time (gfship_domain * dom, gfship_field c, gfship_field tag, int reps, double * ms);
+int  gfship_remove_droplets (gfship_domain * dom, gfship_field c, gfship_field v, int min, double val);
+int  gfship_droplet_to_particle_create (gfship_droplet_to_particle ** d, gfship_particles * pl, gfship_field c,
+					int min, double reset, double density, const char * function,
+					int nvars, const char * const * names, const gfship_field * fields);
+int  gfship_droplet_to_particle_event (gfship_droplet_to_particle * d, gfship_droplet_info * info);
+void gfship_droplet_to_particle_destroy (gfship_droplet_to_particle * d);
+
 /* ---- one box per GPU: GfsBoundaryMpi sides (src/mpi_boundary.c:78-246) ----------------------- */
 
 /* Either the in-library RCCL transport below (gfship_domain_comm_init: what bench.py uses), or two
