@@ -25,11 +25,10 @@
 //   kernel_stride -- and a chunk holds at most RECORD_CAP slots: the work arrays take 56 bytes per
 //   slot, 224 MiB at the most, whatever the number of particles.
 // The sums of steps 3 and 4 and of the void fraction are the kernels of cell_sums.hpp on BoxCells; the lists of a
-// tree (tree_particles.hip) launch the same kernels on TreeCells.
-#include "particles.hpp"
-#include "cell_sums.hpp"
-#include <hipcub/hipcub.hpp>
-#include <algorithm>
+// tree (tree_particles.hip) launch the same kernels on TreeCells.  The host side of both events (the chunk loop, the
+// sorts, the timing of `info') is particle_events.hpp, instantiated here on BoxMesh; this file keeps the checks of
+// the entries of a box, the key and emit kernels with their launches and stride (BoxMesh::) and the work arrays.
+#include "particle_events.hpp"
 #include <cmath>
 #include <cstdlib>
 
@@ -43,9 +42,9 @@ constexpr int DESCENT_MAXDEPTH = 15;
 // (the second case: <= h/2 < rho).  Centres are h apart, so at most floor (2 rho/h) + 1 of them lie in an
 // interval of length 2 rho; one more for the rounding of the comparison, and never more than the box has.
 // (a 64-bit count: the callers refuse a kernel whose slots do not fit into one chunk, see stride_check)
-static unsigned long long kernel_stride (const gfship_domain * dom, double rkernel)
+unsigned long long BoxMesh::kernel_stride (double rkernel) const
 {
-  const int n = dom->lay[dom->depth].n;
+  const int n = L.n;
   const double h = 1./n;
   const double rho = rkernel + h/2.*sqrt ((double) dom->dim);
   double m = floor (2.*rho/h) + 2.;
@@ -55,9 +54,9 @@ static unsigned long long kernel_stride (const gfship_domain * dom, double rkern
 }
 
 // a particle's slots must fit into one chunk: that is what bounds the work arrays at 56 B x RECORD_CAP
-static int stride_check (const gfship_domain * dom, double rkernel)
+int BoxMesh::stride_check (double rkernel) const
 {
-  const unsigned long long stride = kernel_stride (dom, rkernel);
+  const unsigned long long stride = kernel_stride (rkernel);
   GFSHIP_CHECK (stride <= RECORD_CAP, GFSHIP_EUNSUPPORTED,
 		"GfsSourceParticulate: a kernel of rkernel = %g may reach %llu leaves of this box, more than "
 		"the %llu records of a chunk", rkernel, stride, (unsigned long long) RECORD_CAP);
@@ -356,6 +355,34 @@ int launch_where (gfship_particles * pl)
   return GFSHIP_OK;
 }
 
+int BoxMesh::field_keys (unsigned long long * key) const
+{
+  const int block = 256, grid = (pl->n + block - 1)/block;
+  with_bools ([&] (auto D3) {
+    constexpr int DIM = decltype (D3)::value ? 3 : 2;
+    hipLaunchKernelGGL (field_keys_kernel<DIM>, dim3 (grid), dim3 (block), 0, stream, L.n, dom->depth, pl->n,
+			pl->pos[0], pl->pos[1], pl->pos[2], pl->alive, pl->orig, ncell, key);
+  }, dim == 3);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
+int BoxMesh::spread_emit (int o0, int nchunk, int stride) const
+{
+  SpreadArgs A;
+  A.L = L; A.depth = dom->depth; A.o0 = o0; A.nchunk = nchunk; A.stride = stride; A.rkernel = pl->rkernel;
+  A.where = pl->where; A.alive = pl->alive; A.rb = pl->rb;
+  for (int c = 0; c < 3; c++) { A.pos[c] = pl->pos[c]; A.q[c] = pl->cq[c]; }
+  A.pad = ncell; A.key = pl->ckey; A.cnt = pl->ccnt; A.flag = pl->cflag;
+  const int block = 256;
+  with_bools ([&] (auto D3) {
+    constexpr int DIM = decltype (D3)::value ? 3 : 2;
+    hipLaunchKernelGGL (spread_emit_kernel<DIM>, dim3 ((nchunk + block - 1)/block), dim3 (block), 0, stream, A);
+  }, dim == 3);
+  GFSHIP_HIP (hipGetLastError ());
+  return GFSHIP_OK;
+}
+
 int launch_fill (hipStream_t stream, long n, double value, double * out)
 {
   const int block = 256;
@@ -378,77 +405,28 @@ int gfship_particulate_field (gfship_particles * pl, gfship_field v)
   Field * V = get_field (dom, v);
   GFSHIP_CHECK (V != nullptr, GFSHIP_EINVAL, "v is not a field of the domain");
   if ((r = before_write (dom))) return r;
-  const Layout & L = dom->lay[dom->depth];
-  double * a = V->lev[dom->depth];
+  const BoxMesh M (pl);
   /* gfs_cell_reset on the leaves (:1944-1945) */
-  GFSHIP_HIP (hipMemsetAsync (a, 0, L.total*sizeof (double), dom->stream));
-  V->zero[dom->depth] = false;
-  if (pl->n == 0) return GFSHIP_OK;
-  if ((r = coupling_reserve (pl, (size_t) pl->n, 0, false))) return r;
-  const unsigned long long ncell = (unsigned long long) ncells (L);
-  const int block = 256, grid = (pl->n + block - 1)/block;
-  with_bools ([&] (auto D3) {
-    constexpr int DIM = decltype (D3)::value ? 3 : 2;
-    hipLaunchKernelGGL (field_keys_kernel<DIM>, dim3 (grid), dim3 (block), 0, dom->stream, L.n, dom->depth,
-			pl->n, pl->pos[0], pl->pos[1], pl->pos[2], pl->alive, pl->orig, ncell, pl->ckey);
-  }, dom->dim == 3);
-  GFSHIP_HIP (hipGetLastError ());
-  size_t need = 0;
-  const int bits = coupling_key_bits (ncell);
-  GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (nullptr, need, pl->ckey, pl->ckey2, pl->n, 0, bits,
-						 dom->stream));
-  if ((r = coupling_sort_reserve (pl, need))) return r;
-  size_t tmp_bytes = pl->sort_tmp_bytes;
-  GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, pl->n, 0, bits,
-						 dom->stream));
-  with_bools ([&] (auto D3) {
-    constexpr int DIM = decltype (D3)::value ? 3 : 2;
-    hipLaunchKernelGGL ((field_sum_kernel<DIM, BoxCells<DIM>>), dim3 (grid), dim3 (block), 0, dom->stream,
-			BoxCells<DIM> { L }, pl->n, pl->ckey2, ncell, pl->volume, a);
-  }, dom->dim == 3);
-  GFSHIP_HIP (hipGetLastError ());
-  return GFSHIP_OK;
+  if ((r = M.reset_leaves (V))) return r;
+  return particulate_field_body (M, pl, V->lev[dom->depth]);
 }
 
 int gfship_particles_set_kernel (gfship_particles * pl, double rkernel, const char * function)
 {
   int r = coupling_check (pl, "GfsSourceParticulate");
   if (r) return r;
-  GFSHIP_CHECK (rkernel >= 0. && std::isfinite (rkernel), GFSHIP_EINVAL, "rkernel must be a length >= 0");
-  if ((r = stride_check (pl->dom, rkernel))) return r;
-  RtcKernel * k = nullptr;
-  double value = 0.;
-  if (function) {
-    /* a constant (gfs_function_read: a number is kept as f->val) needs no compilation */
-    char * end = nullptr;
-    value = strtod (function, &end);
-    while (end != function && (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r')) end++;
-    if (end == function || *end != '\0') {
-      value = 0.;
-      if ((r = rtc_compile_spatial (pl->dom, function, &k))) return r;
-    }
-  }
-  GFSHIP_HIP (hipStreamSynchronize (pl->dom->stream));
-  rtc_free (pl->kernel_fn);
-  pl->kernel_fn = k;
-  pl->kernel_value = value;
-  pl->rkernel = rkernel;
-  return GFSHIP_OK;
+  return set_kernel_body (BoxMesh (pl), pl, rkernel, function);
 }
 
 } // extern "C"
 
-// info != nullptr: the milliseconds of pass 1 (emit, kernel function, corrections) and of pass 2 (sort, sums)
-// summed over the chunks from events on the stream, the record slots per particle, the particles per chunk
-// and the bytes of the work arrays
 static int spread_forces (gfship_particles * pl, const gfship_field F[3], double * info)
 {
   int r = coupling_check (pl, "GfsSourceParticulate");
   if (r) return r;
   GFSHIP_CHECK (F != nullptr, GFSHIP_EINVAL, "null argument");
   gfship_domain * dom = pl->dom;
-  const gfship_sim_view v = gfship_sim_view_get (pl->sim);
-  if ((r = particulate_fluid_check (v))) return r;
+  if ((r = particulate_fluid_check (gfship_sim_view_get (pl->sim)))) return r;
   double * Fa[3] = { nullptr, nullptr, nullptr };
   for (int c = 0; c < dom->dim; c++) {
     Field * Fc = get_field (dom, F[c]);
@@ -458,100 +436,11 @@ static int spread_forces (gfship_particles * pl, const gfship_field F[3], double
     Fa[c] = Fc->lev[dom->depth];
   }
   if ((r = before_write (dom))) return r;
-  const Layout & L = dom->lay[dom->depth];
+  const BoxMesh M (pl);
   /* gfs_cell_reset on the leaves (:2189-2191) */
-  for (int c = 0; c < dom->dim; c++) {
-    GFSHIP_HIP (hipMemsetAsync (Fa[c], 0, L.total*sizeof (double), dom->stream));
-    get_field (dom, F[c])->zero[dom->depth] = false;
-  }
-  if (info) for (int q = 0; q < 5; q++) info[q] = 0.;
-  if (pl->n == 0) return GFSHIP_OK;
-  if ((r = stride_check (dom, pl->rkernel))) return r;
-  const int stride = (int) kernel_stride (dom, pl->rkernel);
-  const int per_chunk = (int) std::min ((size_t) pl->n, RECORD_CAP/(size_t) stride);
-  if ((r = coupling_reserve (pl, (size_t) per_chunk*stride, (size_t) per_chunk, true))) return r;
-  std::vector<hipEvent_t> ev;
-  auto mark = [&] () -> hipError_t {
-    if (!info) return hipSuccess;
-    hipEvent_t e;
-    hipError_t err = hipEventCreate (&e);
-    if (err != hipSuccess) return err;
-    ev.push_back (e);
-    return hipEventRecord (e, dom->stream);
-  };
-  const unsigned long long ncell = (unsigned long long) ncells (L);
-  const int bits = coupling_key_bits (ncell);
-  const int block = 256;
-  if ((r = launch_where (pl))) return r;
-  GFSHIP_HIP (hipMemsetAsync (pl->cflag, 0, sizeof (int), dom->stream));
-  const bool rho = v.alpha_cell >= 0;
-  const double * alpha = rho ? dom->fields[v.alpha_cell].lev[dom->depth] : nullptr;
-  const double t = gfship_sim_time (pl->sim);
-  SpreadArgs A;
-  A.L = L; A.depth = dom->depth; A.stride = stride; A.rkernel = pl->rkernel;
-  A.where = pl->where; A.alive = pl->alive; A.rb = pl->rb;
-  for (int c = 0; c < 3; c++) { A.pos[c] = pl->pos[c]; A.q[c] = pl->cq[c]; }
-  A.pad = ncell; A.key = pl->ckey; A.cnt = pl->ccnt; A.flag = pl->cflag;
-  for (int o0 = 0; o0 < pl->n; o0 += per_chunk) {
-    const int nchunk = std::min (per_chunk, pl->n - o0);
-    const long nrec = (long) nchunk*stride;
-    const int pgrid = (nchunk + block - 1)/block;
-    const unsigned rgrid = (unsigned) ((nrec + block - 1)/block);
-    A.o0 = o0; A.nchunk = nchunk;
-    GFSHIP_HIP (mark ());
-    with_bools ([&] (auto D3) {
-      constexpr int DIM = decltype (D3)::value ? 3 : 2;
-      hipLaunchKernelGGL (spread_emit_kernel<DIM>, dim3 (pgrid), dim3 (block), 0, dom->stream, A);
-    }, dom->dim == 3);
-    GFSHIP_HIP (hipGetLastError ());
-    if (pl->kernel_fn) {
-      if ((r = rtc_launch_spatial (pl->kernel_fn, dom->stream, nrec, stride, pl->ccnt, pl->cq[0], pl->cq[1],
-				   pl->cq[2], t, pl->cval)))
-	return r;
-    }
-    else if ((r = launch_fill (dom->stream, nrec, pl->kernel_value, pl->cval)))
-      return r;
-    with_bools ([&] (auto D3) {
-      constexpr int DIM = decltype (D3)::value ? 3 : 2;
-      hipLaunchKernelGGL ((spread_correction_kernel<DIM, BoxCells<DIM>>), dim3 (pgrid), dim3 (block), 0, dom->stream,
-			  BoxCells<DIM> { L }, nchunk, stride, pl->ccnt, pl->ckey, pl->cval, pl->ccorr);
-    }, dom->dim == 3);
-    GFSHIP_HIP (hipGetLastError ());
-    GFSHIP_HIP (mark ());
-    size_t need = 0;
-    GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (nullptr, need, pl->ckey, pl->ckey2, pl->cval, pl->cval2,
-						    nrec, 0, bits, dom->stream));
-    if ((r = coupling_sort_reserve (pl, need))) return r;
-    size_t tmp_bytes = pl->sort_tmp_bytes;
-    GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, pl->cval,
-						    pl->cval2, nrec, 0, bits, dom->stream));
-    with_bools ([&] (auto D3, auto RHO) {
-      constexpr int DIM = decltype (D3)::value ? 3 : 2;
-      hipLaunchKernelGGL ((spread_sum_kernel<DIM, decltype (RHO)::value, BoxCells<DIM>>), dim3 (rgrid), dim3 (block), 0,
-			  dom->stream, BoxCells<DIM> { L }, nrec, pl->ckey2, ncell, pl->cval2, o0, pl->ccorr, pl->force[0],
-			  pl->force[1], pl->force[2], alpha, Fa[0], Fa[1], Fa[2]);
-    }, dom->dim == 3, rho);
-    GFSHIP_HIP (hipGetLastError ());
-    GFSHIP_HIP (mark ());
-  }
-  int flag = 0;
-  GFSHIP_HIP (hipMemcpyAsync (&flag, pl->cflag, sizeof (int), hipMemcpyDeviceToHost, dom->stream));
-  GFSHIP_HIP (hipStreamSynchronize (dom->stream));
-  if (info) {
-    for (size_t q = 0; q + 2 < ev.size (); q += 3) {
-      float a = 0.f, b = 0.f;
-      (void) hipEventElapsedTime (&a, ev[q], ev[q + 1]);
-      (void) hipEventElapsedTime (&b, ev[q + 1], ev[q + 2]);
-      info[0] += a;
-      info[1] += b;
-    }
-    for (hipEvent_t e : ev) (void) hipEventDestroy (e);
-    info[2] = stride;
-    info[3] = per_chunk;
-    info[4] = 56.*(double) per_chunk*stride;
-  }
-  GFSHIP_CHECK (flag == 0, GFSHIP_EHIP, "GfsSourceParticulate: a kernel reaches more than %d leaves", stride);
-  return GFSHIP_OK;
+  for (int c = 0; c < dom->dim; c++)
+    if ((r = M.reset_leaves (get_field (dom, F[c])))) return r;
+  return spread_forces_body (M, pl, Fa, info);
 }
 
 extern "C" {

@@ -27,7 +27,7 @@
 //   6. the droplets are the candidates of launch_feed_ids (feed_particle.hip), in tag order: n slots after those
 //      in use, cell = PSOURCE_NO_CELL for a droplet that does not convert.
 //   7. the reset of the variable on the leaves, then its ghosts by its boundary conditions.
-#include "particles.hpp"
+#include "particle_events.hpp"
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <cstdlib>
@@ -720,14 +720,9 @@ int gfship_droplet_to_particle_create (gfship_droplet_to_particle ** out, gfship
     if (!variable) {
       const DropGeom G = drop_geom (dom);
       d->mask = -1;
-      if (feed_constant (function, &d->value)) d->constant = true;
+      if (text_constant (function, &d->value)) d->constant = true;
       else {
-	std::vector<const char *> named;
-	for (int q = 0; q < nvars; q++)
-	  if (names_identifier (function, names[q])) {
-	    named.push_back (names[q]);
-	    d->read.push_back (fields[q]);
-	  }
+	const std::vector<const char *> named = named_variables (function, nvars, names, fields, d->read);
 	if ((r = rtc_compile_cell (dom, function, (int) named.size (), named.data (), &d->fn))) {
 	  gfship_droplet_to_particle_destroy (d);
 	  return r;

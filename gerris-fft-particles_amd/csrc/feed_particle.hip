@@ -18,18 +18,17 @@
 //      moves idlast, then every candidate takes idlast + 1 + (accepted before it) and its flag; an accepted one
 //      also gets its diameter (:552) and rb (:2091).  No atomic counter: the ids do not depend on the scheduling
 //      nor on the shape of the launch.  launch_feed_ids is these three passes, for a box and for a tree alike.
+// The passes are issued by feed_event_body (particle_events.hpp), once for the lists of a box (here, on BoxMesh) and of
+// a tree (tree_feed_event, tree_particles.hip); the two create entries share feed_create below.
 // Slots: the np candidates take the np slots after those in use, in candidate order; a refused candidate is a
 // dead slot (alive = 0), which every reader of the list already skips.  The download order (creation slots) is
 // therefore the reference's list order.  idlast lives on the device; only its getter reads it back.
 //
 // pow: the diameter and rb of a new particle are values of the device's pow in the reference's expressions, as
 // after a volume event (particulate_sources.hip); everything else is the reference's arithmetic.
-#include "particles.hpp"
+#include "particle_events.hpp"
 #include "tree_particles.hpp"
-#include <cctype>
 #include <cstdlib>
-#include <cstring>
-#include <string>
 #include <vector>
 
 namespace gfship {
@@ -156,34 +155,7 @@ int feed_check (gfship_particles * pl, const char * what)
   return GFSHIP_OK;
 }
 
-// the table of variables of a GfsFeedParticle: C names, none of them a variable of the function itself, none twice
-int feed_names_check (int nvars, const char * const * names, const void * vars, const char * kind)
-{
-  GFSHIP_CHECK (nvars >= 0 && (nvars == 0 || (names && vars)), GFSHIP_EINVAL, "invalid table of variables");
-  static const char * builtin[] = { "x", "y", "z", "t" };
-  for (int q = 0; q < nvars; q++) {
-    GFSHIP_CHECK (c_identifier (names[q]), GFSHIP_EINVAL, "variable %d of the table has no C name", q);
-    for (const char * b : builtin)
-      GFSHIP_CHECK (strcmp (names[q], b) != 0, GFSHIP_EINVAL,
-		    "`%s' is a variable of the function itself: it cannot name a %s", b, kind);
-    for (int p = 0; p < q; p++)
-      GFSHIP_CHECK (strcmp (names[q], names[p]) != 0, GFSHIP_EINVAL, "`%s' is in the table twice", names[q]);
-  }
-  return GFSHIP_OK;
-}
-
-// is the text a constant (gfs_function_read: a number is kept as f->val, and needs no compilation)?
-bool feed_constant (const char * text, double * value)
-{
-  char * end = nullptr;
-  *value = strtod (text, &end);
-  while (end != text && (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r')) end++;
-  if (end != text && *end == '\0') return true;
-  *value = 0.;
-  return false;
-}
-
-static int feed_reserve (gfship_feed_particle * f, int np)
+int feed_reserve (gfship_feed_particle * f, int np)
 {
   if (f->cap >= np) return GFSHIP_OK;
   gfship_particles * pl = f->pl;
@@ -202,55 +174,25 @@ static int feed_reserve (gfship_feed_particle * f, int np)
   return GFSHIP_OK;
 }
 
-// does the tree have the variable `var' for a function to read at a leaf?  tree_has_variable, but not the variables
-// of an octree alone on a quadtree: the arrays of W, its gradients and its face values are allocated there too, and
-// nothing ever writes them
-static bool tree_feed_variable (gfship_particles * pl, int var)
+// gfs_feed_particle_read (:2435-2575) once the entry has made its checks and those of its table of variables: each
+// of the two functions is a constant, or compile (text, nf, names, &kernel) around the names of the table it uses
+template <class Compile>
+static int feed_create (gfship_feed_particle ** out, gfship_particles * pl, const char * mass, const char * volume,
+			int nvars, const char * const * names, const int * vars, Compile compile)
 {
-  static const int octree_only[] = { GFSHIP_TREE_W, GFSHIP_TREE_GZ, GFSHIP_TREE_GMACZ, GFSHIP_TREE_UN4, GFSHIP_TREE_UN5,
-				     GFSHIP_TREE_BCW, GFSHIP_TREE_WPREV, GFSHIP_TREE_FZ, GFSHIP_TREE_WRELP };
-  if (pl->dim == 2)
-    for (int v : octree_only)
-      if (var == v) return false;
-  return tree_has_variable (pl->tree, var);
-}
-
-// gfship_feed_particle_event on a list of particulates of a tree: the passes of the box with the leaf as the cell,
-// on the stream of the tree
-static int tree_feed_event (gfship_feed_particle * f, int np, const double * pos)
-{
-  gfship_particles * pl = f->pl;
-  GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_feed_particle_event");
-  if (np == 0) return GFSHIP_OK;
-  GFSHIP_CHECK ((long) pl->n + np <= 0x7fffffffL, GFSHIP_ENOMEM, "the list would hold 2^31 slots or more");
-  TreeView V;
-  tree_view (pl->tree, &V);
-  GFSHIP_HIP (hipSetDevice (V.device));
-  std::vector<const double *> read[2];
-  for (int w = 0; w < 2; w++)
-    for (int var : f->read[w]) {
-      const double * a = tree_feed_variable (pl, var) ? tree_variable (pl->tree, var) : nullptr;
-      GFSHIP_CHECK (a != nullptr, GFSHIP_EINVAL, "the tree has no variable %d", var);
-      read[w].push_back (a);
-    }
-  int r;
-  if ((r = feed_reserve (f, np))) return r;
-  if ((r = particles_reserve (pl, pl->n + np))) return r;
-  /* the candidates come from pageable memory: the copy is staged before the call returns */
-  GFSHIP_HIP (hipMemcpyAsync (f->cand, pos, 3*(size_t) np*sizeof (double), hipMemcpyHostToDevice, V.stream));
-  const int base = pl->n;
-  if ((r = launch_tree_feed_gather (pl, base, np, f->cand, f->cell))) return r;
-  double * out[2] = { pl->mass + base, pl->volume + base };
+  gfship_feed_particle * f = new gfship_feed_particle;
+  f->pl = pl;
+  const char * text[2] = { mass, volume };
   for (int w = 0; w < 2; w++) {
-    if (f->fn[w])
-      r = rtc_launch_tree_cell (f->fn[w], V.stream, np, V.H.depth, V.H.off, f->cell, V.t, (int) read[w].size (),
-				read[w].data (), out[w]);
-    else
-      r = launch_fill (V.stream, np, f->value[w], out[w]);
-    if (r) return r;
+    if (!text[w] || text_constant (text[w], &f->value[w])) continue;
+    const std::vector<const char *> named = named_variables (text[w], nvars, names, vars, f->read[w]);
+    const int r = compile (text[w], (int) named.size (), named.data (), &f->fn[w]);
+    if (r) {
+      gfship_feed_particle_destroy (f);
+      return r;
+    }
   }
-  if ((r = launch_feed_ids (pl, base, np, f->cell, f->block))) return r;
-  pl->n += np;
+  *out = f;
   return GFSHIP_OK;
 }
 
@@ -272,25 +214,10 @@ int gfship_feed_particle_create (gfship_feed_particle ** out, gfship_particles *
   gfship_domain * dom = pl->dom;
   for (int q = 0; q < nvars; q++)
     if (!get_field (dom, fields[q])) return GFSHIP_EINVAL;
-  gfship_feed_particle * f = new gfship_feed_particle;
-  f->pl = pl;
-  const char * text[2] = { mass, volume };
-  for (int w = 0; w < 2; w++) {
-    if (!text[w]) continue;
-    if (feed_constant (text[w], &f->value[w])) continue;
-    std::vector<const char *> named;
-    for (int q = 0; q < nvars; q++)
-      if (names_identifier (text[w], names[q])) {
-	named.push_back (names[q]);
-	f->read[w].push_back (fields[q]);
-      }
-    if ((r = rtc_compile_cell (dom, text[w], (int) named.size (), named.data (), &f->fn[w]))) {
-      gfship_feed_particle_destroy (f);
-      return r;
-    }
-  }
-  *out = f;
-  return GFSHIP_OK;
+  return feed_create (out, pl, mass, volume, nvars, names, fields,
+		      [&] (const char * text, int nf, const char * const * named, RtcKernel ** k) -> int {
+			return rtc_compile_cell (dom, text, nf, named, k);
+		      });
 }
 
 int gfship_feed_particle_event (gfship_feed_particle * f, int np, const double * pos)
@@ -302,34 +229,7 @@ int gfship_feed_particle_event (gfship_feed_particle * f, int np, const double *
   int r = feed_check (pl);
   if (r) return r;
   if (np == 0) return GFSHIP_OK;
-  GFSHIP_CHECK ((long) pl->n + np <= 0x7fffffffL, GFSHIP_ENOMEM, "the list would hold 2^31 slots or more");
-  gfship_domain * dom = pl->dom;
-  const Layout & L = dom->lay[dom->depth];
-  std::vector<const double *> read[2];
-  for (int w = 0; w < 2; w++)
-    for (gfship_field v : f->read[w]) {
-      Field * F = get_field (dom, v);
-      if (!F) return GFSHIP_EINVAL;
-      read[w].push_back (F->lev[dom->depth]);
-    }
-  if ((r = feed_reserve (f, np))) return r;
-  if ((r = particles_reserve (pl, pl->n + np))) return r;
-  /* the candidates come from pageable memory: the copy is staged before the call returns */
-  GFSHIP_HIP (hipMemcpyAsync (f->cand, pos, 3*(size_t) np*sizeof (double), hipMemcpyHostToDevice, dom->stream));
-  const int base = pl->n;
-  if ((r = launch_feed_gather (pl, base, np, f->cand, f->cell))) return r;
-  double * out[2] = { pl->mass + base, pl->volume + base };
-  for (int w = 0; w < 2; w++) {
-    if (f->fn[w])
-      r = rtc_launch_cell (f->fn[w], dom->stream, np, L, f->cell, gfship_sim_time (pl->sim), (int) read[w].size (),
-			   read[w].data (), out[w]);
-    else
-      r = launch_fill (dom->stream, np, f->value[w], out[w]);
-    if (r) return r;
-  }
-  if ((r = launch_feed_ids (pl, base, np, f->cell, f->block))) return r;
-  pl->n += np;
-  return GFSHIP_OK;
+  return feed_event_body (BoxMesh (pl), f, np, pos);
 }
 
 void gfship_feed_particle_destroy (gfship_feed_particle * f)
@@ -392,25 +292,10 @@ int gfship_tree_feed_particle_create (gfship_feed_particle ** out, gfship_partic
 		  "`%s': the tree has no variable %d", names[q], vars[q]);
   const int device = tree_device (pl->tree);
   GFSHIP_HIP (hipSetDevice (device));
-  gfship_feed_particle * f = new gfship_feed_particle;
-  f->pl = pl;
-  const char * text[2] = { mass, volume };
-  for (int w = 0; w < 2; w++) {
-    if (!text[w]) continue;
-    if (feed_constant (text[w], &f->value[w])) continue;
-    std::vector<const char *> named;
-    for (int q = 0; q < nvars; q++)
-      if (names_identifier (text[w], names[q])) {
-	named.push_back (names[q]);
-	f->read[w].push_back (vars[q]);
-      }
-    if ((r = rtc_compile_tree_cell (device, pl->dim, text[w], (int) named.size (), named.data (), &f->fn[w]))) {
-      gfship_feed_particle_destroy (f);
-      return r;
-    }
-  }
-  *out = f;
-  return GFSHIP_OK;
+  return feed_create (out, pl, mass, volume, nvars, names, vars,
+		      [&] (const char * text, int nf, const char * const * named, RtcKernel ** k) -> int {
+			return rtc_compile_tree_cell (device, pl->dim, text, nf, named, k);
+		      });
 }
 
 int gfship_tree_particles_set_idlast (gfship_particles * pl, int idlast)

@@ -25,7 +25,7 @@
 // and gfship_particles_download returns the survivors in that order (the reference's list
 // order).  Tracers move less than one cell per step (CFL < 1), so the order stays good between
 // sorts.
-#include "particles.hpp"
+#include "particle_events.hpp"
 #include "particulate_forces.hpp"
 #include "tree_particles.hpp"
 #include <hipcub/hipcub.hpp>
@@ -1476,23 +1476,20 @@ int gfship_particles_download_old (gfship_particles * pl, double * old)
 
 } // extern "C"
 
-int gfship::launch_particulate_source_gather (gfship_particles * pl, unsigned * cell, double * rad,
-					      double * const urel[3])
+int gfship::BoxMesh::source_gather (gfship_particulate_source * s) const
 {
-  gfship_domain * dom = pl->dom;
-  const gfship_sim_view v = gfship_sim_view_get (pl->sim);
   SourceGatherArgs A;
-  A.L = dom->lay[dom->depth];
+  A.L = L;
   A.depth = dom->depth;
   A.n = pl->n;
   for (int c = 0; c < 3; c++) {
     A.pos[c] = pl->pos[c];
     A.u[c] = c < dom->dim ? dom->fields[v.u[c]].lev[dom->depth] : nullptr;
     A.vel[c] = pl->vel[c];
-    A.urel[c] = urel[c];
+    A.urel[c] = s->purel[c];
   }
   A.alive = pl->alive; A.orig = pl->orig; A.volume = pl->volume;
-  A.cell = cell; A.rad = rad;
+  A.cell = s->cell; A.rad = s->prad;
   const int block = 256, grid = (pl->n + block - 1)/block;
   with_bools ([&] (auto D3) {
     constexpr int DIM = decltype (D3)::value ? 3 : 2;
@@ -1502,12 +1499,10 @@ int gfship::launch_particulate_source_gather (gfship_particles * pl, unsigned * 
   return GFSHIP_OK;
 }
 
-int gfship::launch_feed_gather (gfship_particles * pl, int base, int np, const double * cand, unsigned * cell)
+int gfship::BoxMesh::feed_gather (int base, int np, const double * cand, unsigned * cell) const
 {
-  gfship_domain * dom = pl->dom;
-  const gfship_sim_view v = gfship_sim_view_get (pl->sim);
   FeedGatherArgs A;
-  A.L = dom->lay[dom->depth];
+  A.L = L;
   A.depth = dom->depth;
   A.np = np; A.base = base;
   A.cand = cand;

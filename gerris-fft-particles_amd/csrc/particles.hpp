@@ -1,4 +1,7 @@
-// particles.hpp -- the particle list and the cell search shared by particles.hip and coupling.hip.
+// particles.hpp -- the particle list, the objects of its events and the cell search shared by particles.hip,
+// coupling.hip, particulate_sources.hip, feed_particle.hip, droplets.hip and tree_particles.hip.  The host side of the
+// events that run on a box and on a tree alike is particle_events.hpp; the checks of a function's text and of a table
+// of variables are function_text.hpp.
 #pragma once
 #include "gfship_internal.hpp"
 #include <functional>
@@ -174,23 +177,18 @@ int launch_fill (hipStream_t stream, long n, double value, double * out);
 int particles_alloc (gfship_particles * pl, int np, const double * pos, const unsigned * id);
 // grow the per-particle arrays to at least `need' slots, contents kept (particles.hip)
 int particles_reserve (gfship_particles * pl, int need);
-// feed_particulate (:2377-2396) up to the two functions, for the np candidates `cand' (3 doubles each, device) of
-// a GfsFeedParticle with the locate and the interpolate of the event kernels (particles.hip): slot base + i gets
-// the position, pos_old = 0, force = 0, orig = its own number and the interpolated velocity of the fluid;
-// cell[i] = the linear number of the candidate's cell or PSOURCE_NO_CELL
-int launch_feed_gather (gfship_particles * pl, int base, int np, const double * cand, unsigned * cell);
-// the same on a list of particulates of a tree (tree_particles.hip): tree_locate and tree_interpolate of the event
-// kernels; cell[i] = the index of the candidate's leaf in the concatenated levels (Topo::gi) or PSOURCE_NO_CELL
-int launch_tree_feed_gather (gfship_particles * pl, int base, int np, const double * cand, unsigned * cell);
 // the ids of the np candidates that took the slots from `base' on (feed_particle.hip), after their mass and volume
 // are written: the accepted candidates per block, the scan that moves idlast, then id, flag, diameter and rb of
 // every slot; `block' holds one count per 256 candidates.  On the stream of the list, for a box and for a tree
 int launch_feed_ids (gfship_particles * pl, int base, int np, const unsigned * cell, unsigned * block);
 // what an object that adds particulates to a list of a box refuses (feed_particle.hip): a list of a tree, a list of
-// tracers, GfsBoundaryMpi sides, 2^32 cells or more; the checks of its table of variables; is a text a number?
+// tracers, GfsBoundaryMpi sides, 2^32 cells or more; the work arrays of an event of np candidates
 int feed_check (gfship_particles * pl, const char * what = "GfsFeedParticle");
-int feed_names_check (int nvars, const char * const * names, const void * vars, const char * kind);
-bool feed_constant (const char * text, double * value);
+int feed_reserve (gfship_feed_particle * f, int np);
+// a GfsFeedParticle on a list of a tree (tree_particles.hip): does the tree have the variable `var' for a function to
+// read at a leaf; the event of np candidates (feed_event_body, particle_events.hpp, on the stream of the tree)
+bool tree_feed_variable (gfship_particles * pl, int var);
+int tree_feed_event (gfship_feed_particle * f, int np, const double * pos);
 // a list on a tree (tree_particles.hip): the event of its tracers, the keys of gfship_particles_sort and their bits
 int tree_particle_list_event (gfship_particles * pl);
 int tree_particle_keys (gfship_particles * pl, int * bits);
@@ -199,22 +197,12 @@ int tree_particle_keys (gfship_particles * pl, int * bits);
 int particulate_alloc (gfship_particles * pl, const double * vel, const double * mass, const double * volume);
 // a list of particulates on a tree (gfship_particulates_create_tree, tree_particles.hip): its event with forces
 int tree_particulate_list_event (gfship_particles * pl);
-// the first pass of a GfsSourceParticulateVol / ...Mass (particulate_sources.hip) with the locate and the
-// interpolate of the event kernels (particles.hip): per creation slot the linear number of the particle's cell
-// (PSOURCE_NO_CELL off the list or without a cell), pow (3.0*volume/4.0/M_PI, 1./3.) and fluid velocity - vel
-int launch_particulate_source_gather (gfship_particles * pl, unsigned * cell, double * rad, double * const urel[3]);
-// the passes of particulate_sources.hip that the event of a tree shares: the per-slot arrays of the object and
-// step 3 (volume or mass += source*dt, diameter and rb, the key cell << 32 | slot); the constant function is
-// launch_fill
+// the passes of particulate_sources.hip that are no kernel of a mesh: the per-slot arrays of the object and step 3
+// (volume or mass += source*dt, diameter and rb, the key cell << 32 | slot); the constant function is launch_fill
 int particulate_source_reserve (gfship_particulate_source * s);
 int launch_particulate_source_update (gfship_particulate_source * s, hipStream_t stream, double dt,
 				      unsigned long long pad, unsigned long long * key);
-// the checks of a table of variables and of the text of a function (particulate_sources.hip), shared with
-// feed_particle.hip: is `s' a C identifier; does the C text `e' name `id' (a whole identifier, not a member and
-// not inside a string)?
-bool c_identifier (const char * s);
-bool names_identifier (const std::string & e, const std::string & id);
-// the event of a source on a list of a tree (tree_particles.hip); info as in source_event
+// the event of a source on a list of a tree (tree_particles.hip); info as in source_event_body
 int tree_particulate_source_event (gfship_particulate_source * s, double * info);
 }
 

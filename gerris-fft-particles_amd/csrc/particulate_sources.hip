@@ -19,18 +19,17 @@
 //      result does not depend on where a particle is stored nor on the scheduling.
 // The event has no chunks: one record of 8 bytes per particle (the spreading needs chunks because one particle
 // owns many records).
+// The passes are issued by source_event_body (particle_events.hpp), for a box here and for a tree in
+// tree_particles.hip; an entry finds and resets the variables it writes, each mesh by its own rule.
 //
 // pow: Rad, and the diameter and rb of a particle whose volume an event has changed, are values of the
 // device's pow (the reference's expression, glibc's pow there); everything else is the reference's arithmetic,
 // operation by operation.  A list no volume event has run on keeps the diameter and rb computed on the host
 // (particulate_alloc).
-#include "particles.hpp"
-#include "cell_sums.hpp"
+#include "particle_events.hpp"
 #include "tree_particles.hpp"
-#include <hipcub/hipcub.hpp>
 #include <cmath>
 #include <cstdlib>
-#include <string>
 #include <vector>
 
 namespace gfship {
@@ -56,36 +55,6 @@ particulate_source_update_kernel (int n, const unsigned * __restrict__ cell, con
     rb[o] = pow (3.*s/(4.*M_PI), 1./3.);
   }
   if (key) key[o] = (unsigned long long) c << 32 | (unsigned) o;
-}
-
-bool c_identifier (const char * s)
-{
-  if (!s || !(isalpha ((unsigned char) *s) || *s == '_')) return false;
-  for (; *s; s++)
-    if (!(isalnum ((unsigned char) *s) || *s == '_')) return false;
-  return true;
-}
-
-// does the C text name `id' (a whole identifier, not a member and not inside a string)?
-bool names_identifier (const std::string & e, const std::string & id)
-{
-  size_t p = 0;
-  while (p < e.size ()) {
-    if (isalpha ((unsigned char) e[p]) || e[p] == '_') {
-      size_t b = p;
-      while (p < e.size () && (isalnum ((unsigned char) e[p]) || e[p] == '_')) p++;
-      const bool member = b > 0 && (e[b - 1] == '.' || isdigit ((unsigned char) e[b - 1]));
-      if (!member && e.compare (b, p - b, id) == 0) return true;
-    }
-    else if (e[p] == '"') {
-      p++;
-      while (p < e.size () && e[p] != '"') p++;
-      p++;
-    }
-    else
-      p++;
-  }
-  return false;
 }
 
 // what gfship_particulate_source_create and the event refuse: coupling_check of coupling.hip, word for word
@@ -141,8 +110,6 @@ int launch_particulate_source_update (gfship_particulate_source * s, hipStream_t
   return GFSHIP_OK;
 }
 
-// info != nullptr: the milliseconds of the per-particle passes (steps 1 to 3) and of the sort with the pass per
-// cell (step 4), from events on the stream
 static int source_event (gfship_particulate_source * s, double * info)
 {
   GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null particulate source");
@@ -154,18 +121,14 @@ static int source_event (gfship_particulate_source * s, double * info)
   if (r) return r;
   gfship_domain * dom = pl->dom;
   const bool volume = s->kind == GFSHIP_PARTICULATE_SOURCE_VOLUME;
-  const Layout & L = dom->lay[dom->depth];
+  const BoxMesh M (pl);
   Field * D = nullptr, * R = nullptr, * U[3] = { nullptr, nullptr, nullptr };
   if (s->deposit >= 0 && !(D = get_field (dom, s->deposit))) return GFSHIP_EINVAL;
   if (s->rad >= 0 && !(R = get_field (dom, s->rad))) return GFSHIP_EINVAL;
   for (int c = 0; c < dom->dim; c++)
     if (s->urel[c] >= 0 && !(U[c] = get_field (dom, s->urel[c]))) return GFSHIP_EINVAL;
   std::vector<const double *> read;
-  for (gfship_field f : s->read) {
-    Field * F = get_field (dom, f);
-    if (!F) return GFSHIP_EINVAL;
-    read.push_back (F->lev[dom->depth]);
-  }
+  if ((r = M.arrays (s->read, read))) return r;
   const bool fields = D || R || U[0] || U[1] || U[2];
   if (fields && (r = before_write (dom))) return r;
   if (D) {
@@ -177,66 +140,37 @@ static int source_event (gfship_particulate_source * s, double * info)
     }
   }
   if (R) R->zero[dom->depth] = false;
+  double * Ua[3] = { nullptr, nullptr, nullptr };
   for (int c = 0; c < dom->dim; c++)
-    if (U[c]) U[c]->zero[dom->depth] = false;
-  if (info) info[0] = info[1] = 0.;
-  if (pl->n == 0) return GFSHIP_OK;
-  if ((r = particulate_source_reserve (s))) return r;
-  hipEvent_t ev[3] = { nullptr, nullptr, nullptr };
-  auto mark = [&] (int q) -> hipError_t {
-    if (!info) return hipSuccess;
-    hipError_t e = hipEventCreate (&ev[q]);
-    return e != hipSuccess ? e : hipEventRecord (ev[q], dom->stream);
-  };
-  GFSHIP_HIP (mark (0));
-  if ((r = launch_particulate_source_gather (pl, s->cell, s->prad, s->purel))) return r;
-  const int n = pl->n, block = 256, grid = (n + block - 1)/block;
-  if (s->fn) {
-    if ((r = rtc_launch_source (s->fn, dom->stream, n, L, s->cell, s->prad, s->purel, gfship_sim_time (pl->sim),
-				(int) read.size (), read.data (), s->src)))
-      return r;
-  }
-  else if ((r = launch_fill (dom->stream, n, s->value, s->src)))
-    return r;
-  const unsigned long long ncell = (unsigned long long) ncells (L);
-  if (fields && (r = coupling_reserve (pl, (size_t) n, 0, false))) return r;
-  unsigned long long * key = fields ? pl->ckey : nullptr;
-  const double dt = gfship_sim_view_get (pl->sim).dt;      /* sim->advection_params.dt */
-  if ((r = launch_particulate_source_update (s, dom->stream, dt, ncell, key))) return r;
-  GFSHIP_HIP (mark (1));
-  if (fields) {
-    size_t need = 0;
-    const int bits = coupling_key_bits (ncell);
-    GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (nullptr, need, pl->ckey, pl->ckey2, n, 0, bits, dom->stream));
-    if ((r = coupling_sort_reserve (pl, need))) return r;
-    size_t tmp_bytes = pl->sort_tmp_bytes;
-    GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, n, 0, bits,
-						   dom->stream));
-    SourceCellArgs A;
-    A.n = n; A.key = pl->ckey2; A.ncell = ncell;
-    A.src = s->src; A.prad = s->prad;
-    A.deposit = D ? D->lev[dom->depth] : nullptr;
-    A.rad = R ? R->lev[dom->depth] : nullptr;
-    for (int c = 0; c < 3; c++) {
-      A.purel[c] = s->purel[c];
-      A.urel[c] = c < dom->dim && U[c] ? U[c]->lev[dom->depth] : nullptr;
+    if (U[c]) {
+      U[c]->zero[dom->depth] = false;
+      Ua[c] = U[c]->lev[dom->depth];
     }
-    with_bools ([&] (auto D3) {
-      constexpr int DIM = decltype (D3)::value ? 3 : 2;
-      hipLaunchKernelGGL ((particulate_source_cell_kernel<DIM, false, BoxCells<DIM>>), dim3 (grid), dim3 (block), 0,
-			  dom->stream, BoxCells<DIM> { L }, A);
-    }, dom->dim == 3);
-    GFSHIP_HIP (hipGetLastError ());
+  return source_event_body (M, s, D ? D->lev[dom->depth] : nullptr, R ? R->lev[dom->depth] : nullptr, Ua, read, info);
+}
+
+// gfs_source_particulatevol_read / ...mass_read once the entry has made its checks: the table of variables (kind:
+// what a name of the table stands for; extra: the caller's check of variable q), then the function -- a constant,
+// or compile (text, nf, names, &kernel) around the names of the table the text uses
+template <class Extra, class Compile>
+static int source_create (gfship_particulate_source ** out, gfship_particles * pl, int kind, const char * function,
+			  int nvars, const char * const * names, const int * vars, const char * var_kind, Extra extra,
+			  Compile compile)
+{
+  int r = names_table_check (nvars, names, vars, { "Rad", "Urelp", "Vrelp", "Wrelp", "x", "y", "z", "t" }, var_kind,
+			     extra);
+  if (r) return r;
+  RtcKernel * k = nullptr;
+  double value = 0.;
+  std::vector<gfship_field> read;
+  /* a constant (gfs_function_read: a number is kept as f->val) needs no compilation */
+  if (function && !text_constant (function, &value)) {
+    const std::vector<const char *> named = named_variables (function, nvars, names, vars, read);
+    if ((r = compile (function, (int) named.size (), named.data (), &k))) return r;
   }
-  if (info) {
-    GFSHIP_HIP (mark (2));
-    GFSHIP_HIP (hipStreamSynchronize (dom->stream));
-    float a = 0.f, b = 0.f;
-    (void) hipEventElapsedTime (&a, ev[0], ev[1]);
-    (void) hipEventElapsedTime (&b, ev[1], ev[2]);
-    info[0] = a; info[1] = b;
-    for (hipEvent_t e : ev) (void) hipEventDestroy (e);
-  }
+  gfship_particulate_source * s = new gfship_particulate_source;
+  s->pl = pl; s->kind = kind; s->fn = k; s->value = value; s->read = read;
+  *out = s;
   return GFSHIP_OK;
 }
 
@@ -256,41 +190,12 @@ int gfship_particulate_source_create (gfship_particulate_source ** out, gfship_p
 		"kind must be GFSHIP_PARTICULATE_SOURCE_VOLUME or GFSHIP_PARTICULATE_SOURCE_MASS");
   int r = source_check (pl, kind_name (kind));
   if (r) return r;
-  GFSHIP_CHECK (nvars >= 0 && (nvars == 0 || (names && fields)), GFSHIP_EINVAL, "invalid table of variables");
   gfship_domain * dom = pl->dom;
-  static const char * builtin[] = { "Rad", "Urelp", "Vrelp", "Wrelp", "x", "y", "z", "t" };
-  for (int q = 0; q < nvars; q++) {
-    GFSHIP_CHECK (c_identifier (names[q]), GFSHIP_EINVAL, "variable %d of the table has no C name", q);
-    for (const char * b : builtin)
-      GFSHIP_CHECK (strcmp (names[q], b) != 0, GFSHIP_EINVAL,
-		    "`%s' is a variable of the function itself: it cannot name a field", b);
-    for (int p = 0; p < q; p++)
-      GFSHIP_CHECK (strcmp (names[q], names[p]) != 0, GFSHIP_EINVAL, "`%s' is in the table twice", names[q]);
-    if (!get_field (dom, fields[q])) return GFSHIP_EINVAL;
-  }
-  RtcKernel * k = nullptr;
-  double value = 0.;
-  std::vector<gfship_field> read;
-  if (function) {
-    /* a constant (gfs_function_read: a number is kept as f->val) needs no compilation */
-    char * end = nullptr;
-    value = strtod (function, &end);
-    while (end != function && (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r')) end++;
-    if (end == function || *end != '\0') {
-      value = 0.;
-      std::vector<const char *> named;
-      for (int q = 0; q < nvars; q++)
-	if (names_identifier (function, names[q])) {
-	  named.push_back (names[q]);
-	  read.push_back (fields[q]);
-	}
-      if ((r = rtc_compile_source (dom, function, (int) named.size (), named.data (), &k))) return r;
-    }
-  }
-  gfship_particulate_source * s = new gfship_particulate_source;
-  s->pl = pl; s->kind = kind; s->fn = k; s->value = value; s->read = read;
-  *out = s;
-  return GFSHIP_OK;
+  return source_create (out, pl, kind, function, nvars, names, fields, "field",
+			[&] (int q) -> int { return get_field (dom, fields[q]) ? GFSHIP_OK : GFSHIP_EINVAL; },
+			[&] (const char * text, int nf, const char * const * named, RtcKernel ** k) -> int {
+			  return rtc_compile_source (dom, text, nf, named, k);
+			});
 }
 
 int gfship_tree_particulate_source_create (gfship_particulate_source ** out, gfship_particles * pl, int kind,
@@ -303,47 +208,20 @@ int gfship_tree_particulate_source_create (gfship_particulate_source ** out, gfs
 		"kind must be GFSHIP_PARTICULATE_SOURCE_VOLUME or GFSHIP_PARTICULATE_SOURCE_MASS");
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
   GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_tree_particulate_source_create");
-  GFSHIP_CHECK (nvars >= 0 && (nvars == 0 || (names && vars)), GFSHIP_EINVAL, "invalid table of variables");
-  static const char * builtin[] = { "Rad", "Urelp", "Vrelp", "Wrelp", "x", "y", "z", "t" };
-  for (int q = 0; q < nvars; q++) {
-    GFSHIP_CHECK (c_identifier (names[q]), GFSHIP_EINVAL, "variable %d of the table has no C name", q);
-    for (const char * b : builtin)
-      GFSHIP_CHECK (strcmp (names[q], b) != 0, GFSHIP_EINVAL,
-		    "`%s' is a variable of the function itself: it cannot name a variable of the tree", b);
-    for (int p = 0; p < q; p++)
-      GFSHIP_CHECK (strcmp (names[q], names[p]) != 0, GFSHIP_EINVAL, "`%s' is in the table twice", names[q]);
+  auto written = [&] (int q) -> int {
     GFSHIP_CHECK (!(vars[q] >= GFSHIP_TREE_RAD && vars[q] <= GFSHIP_TREE_DMDT), GFSHIP_EUNSUPPORTED,
 		  "%s: `%s' names a variable the walk of the list writes (Rad, Urelp, Vrelp, Wrelp or a deposit)",
 		  kind_name (kind), names[q]);
     GFSHIP_CHECK (tree_has_variable (pl->tree, vars[q]), GFSHIP_EINVAL,
 		  "`%s': the tree has no variable %d", names[q], vars[q]);
-  }
-  RtcKernel * k = nullptr;
-  double value = 0.;
-  std::vector<gfship_field> read;
-  if (function) {
-    /* a constant (gfs_function_read: a number is kept as f->val) needs no compilation */
-    char * end = nullptr;
-    value = strtod (function, &end);
-    while (end != function && (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r')) end++;
-    if (end == function || *end != '\0') {
-      value = 0.;
-      std::vector<const char *> named;
-      for (int q = 0; q < nvars; q++)
-	if (names_identifier (function, names[q])) {
-	  named.push_back (names[q]);
-	  read.push_back (vars[q]);
-	}
-      const int device = tree_device (pl->tree);
-      GFSHIP_HIP (hipSetDevice (device));
-      int r = rtc_compile_tree_source (device, pl->dim, function, (int) named.size (), named.data (), &k);
-      if (r) return r;
-    }
-  }
-  gfship_particulate_source * s = new gfship_particulate_source;
-  s->pl = pl; s->kind = kind; s->fn = k; s->value = value; s->read = read;
-  *out = s;
-  return GFSHIP_OK;
+    return GFSHIP_OK;
+  };
+  return source_create (out, pl, kind, function, nvars, names, vars, "variable of the tree", written,
+			[&] (const char * text, int nf, const char * const * named, RtcKernel ** k) -> int {
+			  const int device = tree_device (pl->tree);
+			  GFSHIP_HIP (hipSetDevice (device));
+			  return rtc_compile_tree_source (device, pl->dim, text, nf, named, k);
+			});
 }
 
 int gfship_tree_particulate_source_set_fields (gfship_particulate_source * s, int rad, const int urel[3], int deposit)

@@ -23,12 +23,12 @@
 // gfs_center_gradient (src/fluid.c:434-475) of Du/Dt and of the vorticity taken at the leaf through
 // tree::center_gradient (tree.hpp) -- a coarser neighbour at x = 3/2, a neighbour with children at x = 3/4.  Pinned
 // on tests/tree_forces_reference.py in tests/test_gpu_tree_particulates.py.
-#include "particles.hpp"
+//
+// The events of a list of particulates that run on a box too (void fraction, spreading, sources, feed) keep here the
+// kernels that walk the tree and TreeMesh, which launches them; their host side is particle_events.hpp.
+#include "particle_events.hpp"
 #include "particulate_forces.hpp"
-#include "cell_sums.hpp"
 #include "tree_particles.hpp"
-#include <hipcub/hipcub.hpp>
-#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <vector>
@@ -1055,36 +1055,6 @@ tree_spread_emit_kernel (TreeSamp S, TreeSpreadArgs A)
     A.key[base + j] = A.pad << 32 | 0xFFFFFFFFull;
 }
 
-// record slots per particle: the bound of kernel_stride (coupling.hip) per level -- the centres of the leaves of
-// level l that pass cond_kernel lie within rho_l = rkernel + (h_l/2) sqrt (dim) of the particle along every axis and
-// are h_l apart -- summed over the levels that hold interior leaves; on a uniform tree the stride of the box
-unsigned long long tree_kernel_stride (const TreeView & V, double rkernel)
-{
-  bool has[GFSHIP_MAXLEVEL + 1] = {};
-  for (int t = 0; t < V.nleaves; t++) has[V.hleaves[t].l] = true;
-  unsigned long long sum = 0;
-  for (int l = 0; l <= V.H.depth; l++)
-    if (has[l]) {
-      const double n = (double) (1 << l), h = 1./n;
-      const double rho = rkernel + h/2.*sqrt ((double) V.H.dim);
-      double m = floor (2.*rho/h) + 2.;
-      if (!(m < n)) m = n;
-      const unsigned long long s = (unsigned long long) m;
-      sum += V.H.dim == 3 ? s*s*s : s*s;
-      if (sum > COUPLING_RECORD_CAP) break;      /* refused by the callers: no need to go on (nor to overflow) */
-    }
-  return sum;
-}
-
-int tree_stride_check (const TreeView & V, double rkernel)
-{
-  const unsigned long long stride = tree_kernel_stride (V, rkernel);
-  GFSHIP_CHECK (stride <= COUPLING_RECORD_CAP, GFSHIP_EUNSUPPORTED,
-		"GfsSourceParticulate: a kernel of rkernel = %g may reach %llu leaves of this tree or more, more than "
-		"the %llu records of a chunk", rkernel, stride, (unsigned long long) COUPLING_RECORD_CAP);
-  return GFSHIP_OK;
-}
-
 TreeSamp tree_samp (const TreeView & V, const SamplerTables * S)
 {
   TreeSamp A;
@@ -1095,7 +1065,174 @@ TreeSamp tree_samp (const TreeView & V, const SamplerTables * S)
   return A;
 }
 
+// u[c] = the array of GFSHIP_TREE_U, _V, _W of the tree for c < dim
+void tree_velocity (gfship_tree * tr, int dim, const double * (& u)[3])
+{
+  const int uvar[3] = { GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP_TREE_W };
+  for (int c = 0; c < 3; c++)
+    u[c] = c < dim ? tree_variable (tr, uvar[c]) : nullptr;
+}
+
+// the leaves of a refined tree as the mesh of a list (particle_events.hpp)
+struct TreeMesh {
+  static constexpr bool TREE = true;
+  gfship_particles * pl;
+  TreeView V;
+  SamplerTables * S = nullptr;
+  int dim = 0;
+  hipStream_t stream = nullptr;
+  double t = 0., dt = 0.;
+  unsigned long long ncell = 0;
+  explicit TreeMesh (gfship_particles * p) : pl (p) {}
+  // the view of the tree; sampler: also the tables its kernels read, on the device of the tree
+  int init (bool sampler = true) {
+    if (sampler) {
+      int r = sampler_get (pl->tree, &V, &S);
+      if (r) return r;
+    }
+    else
+      tree_view (pl->tree, &V);
+    dim = V.H.dim; stream = V.stream; t = V.t; dt = V.dt; ncell = (unsigned long long) V.ncell;
+    return GFSHIP_OK;
+  }
+  template <int DIM> TreeCells<DIM> cells () const { return TreeCells<DIM> { V.D }; }
+  const double * alpha () const { return nullptr; }      /* a tree has no alpha */
+  // gfs_cell_reset on the interior leaves of every level, for up to three variables
+  int reset_leaves (double * a0, double * a1 = nullptr, double * a2 = nullptr) const {
+    const int block = 256;
+    hipLaunchKernelGGL (tree_reset_leaves_kernel, dim3 ((V.nleaves + block - 1)/block), dim3 (block), 0, stream, V.D,
+			V.dleaves, V.nleaves, a0, a1, a2);
+    GFSHIP_HIP (hipGetLastError ());
+    return GFSHIP_OK;
+  }
+  // feed: the variables a function of a GfsFeedParticle may read (tree_feed_variable)
+  int arrays (const std::vector<gfship_field> & vars, std::vector<const double *> & out, bool feed = false) const {
+    for (int var : vars) {
+      const double * a = !feed || tree_feed_variable (pl, var) ? tree_variable (pl->tree, var) : nullptr;
+      GFSHIP_CHECK (a != nullptr, GFSHIP_EINVAL, "the tree has no variable %d", var);
+      out.push_back (a);
+    }
+    return GFSHIP_OK;
+  }
+  int compile_spatial (const char * text, RtcKernel ** k) const {
+    GFSHIP_HIP (hipSetDevice (V.device));
+    return rtc_compile_spatial_on (V.device, text, k);
+  }
+  int launch_source (const gfship_particulate_source * s, const std::vector<const double *> & read) const {
+    return rtc_launch_tree_source (s->fn, stream, pl->n, dim, V.H.depth, V.H.off, s->cell, s->prad, s->purel, t,
+				   (int) read.size (), read.data (), s->src);
+  }
+  int launch_cell (RtcKernel * k, int np, const unsigned * cell, const std::vector<const double *> & read,
+		   double * out) const {
+    return rtc_launch_tree_cell (k, stream, np, V.H.depth, V.H.off, cell, t, (int) read.size (), read.data (), out);
+  }
+
+  // record slots per particle: the bound of BoxMesh::kernel_stride (coupling.hip) per level -- the centres of the
+  // leaves of level l that pass cond_kernel lie within rho_l = rkernel + (h_l/2) sqrt (dim) of the particle along every
+  // axis and are h_l apart -- summed over the levels that hold interior leaves; on a uniform tree the stride of the box
+  unsigned long long kernel_stride (double rkernel) const {
+    bool has[GFSHIP_MAXLEVEL + 1] = {};
+    for (int t = 0; t < V.nleaves; t++) has[V.hleaves[t].l] = true;
+    unsigned long long sum = 0;
+    for (int l = 0; l <= V.H.depth; l++)
+      if (has[l]) {
+	const double n = (double) (1 << l), h = 1./n;
+	const double rho = rkernel + h/2.*sqrt ((double) V.H.dim);
+	double m = floor (2.*rho/h) + 2.;
+	if (!(m < n)) m = n;
+	const unsigned long long s = (unsigned long long) m;
+	sum += V.H.dim == 3 ? s*s*s : s*s;
+	if (sum > COUPLING_RECORD_CAP) break;      /* refused by stride_check: no need to go on (nor to overflow) */
+      }
+    return sum;
+  }
+  int stride_check (double rkernel) const {
+    const unsigned long long stride = kernel_stride (rkernel);
+    GFSHIP_CHECK (stride <= COUPLING_RECORD_CAP, GFSHIP_EUNSUPPORTED,
+		  "GfsSourceParticulate: a kernel of rkernel = %g may reach %llu leaves of this tree or more, more than "
+		  "the %llu records of a chunk", rkernel, stride, (unsigned long long) COUPLING_RECORD_CAP);
+    return GFSHIP_OK;
+  }
+
+  int field_keys (unsigned long long * key) const {
+    const int block = 256, grid = (pl->n + block - 1)/block;
+    with_bools ([&] (auto D3) {
+      constexpr int DIM = decltype (D3)::value ? 3 : 2;
+      hipLaunchKernelGGL (tree_field_keys_kernel<DIM>, dim3 (grid), dim3 (block), 0, stream, tree_samp (V, S), pl->n,
+			  pl->pos[0], pl->pos[1], pl->pos[2], pl->alive, pl->orig, ncell, key);
+    }, dim == 3);
+    GFSHIP_HIP (hipGetLastError ());
+    return GFSHIP_OK;
+  }
+  int spread_emit (int o0, int nchunk, int stride) const {
+    TreeSpreadArgs A;
+    A.o0 = o0; A.nchunk = nchunk; A.stride = stride; A.rkernel = pl->rkernel;
+    A.where = pl->where; A.alive = pl->alive; A.rb = pl->rb;
+    for (int c = 0; c < 3; c++) { A.pos[c] = pl->pos[c]; A.q[c] = pl->cq[c]; }
+    A.pad = ncell; A.key = pl->ckey; A.cnt = pl->ccnt; A.flag = pl->cflag;
+    const int block = 256;
+    with_bools ([&] (auto D3) {
+      constexpr int DIM = decltype (D3)::value ? 3 : 2;
+      hipLaunchKernelGGL (tree_spread_emit_kernel<DIM>, dim3 ((nchunk + block - 1)/block), dim3 (block), 0, stream,
+			  tree_samp (V, S), A);
+    }, dim == 3);
+    GFSHIP_HIP (hipGetLastError ());
+    return GFSHIP_OK;
+  }
+  int source_gather (gfship_particulate_source * s) const {
+    TreeSourceGatherArgs G;
+    G.n = pl->n;
+    tree_velocity (pl->tree, dim, G.u);
+    for (int c = 0; c < 3; c++) {
+      G.pos[c] = pl->pos[c];
+      G.vel[c] = pl->vel[c];
+      G.urel[c] = s->purel[c];
+    }
+    G.alive = pl->alive; G.orig = pl->orig; G.volume = pl->volume;
+    G.cell = s->cell; G.rad = s->prad;
+    const int block = 256, grid = (pl->n + block - 1)/block;
+    with_bools ([&] (auto D3) {
+      constexpr int DIM = decltype (D3)::value ? 3 : 2;
+      hipLaunchKernelGGL (tree_particulate_source_gather_kernel<DIM>, dim3 (grid), dim3 (block), 0, stream,
+			  tree_samp (V, S), G);
+    }, dim == 3);
+    GFSHIP_HIP (hipGetLastError ());
+    return GFSHIP_OK;
+  }
+  int feed_gather (int base, int np, const double * cand, unsigned * cell) const {
+    TreeFeedGatherArgs A;
+    A.np = np; A.base = base;
+    A.cand = cand;
+    tree_velocity (pl->tree, dim, A.u);
+    for (int c = 0; c < 3; c++) {
+      A.pos[c] = pl->pos[c]; A.old[c] = pl->old[c];
+      A.vel[c] = pl->vel[c]; A.force[c] = pl->force[c];
+    }
+    A.orig = pl->orig; A.cell = cell;
+    const int block = 256, grid = (np + block - 1)/block;
+    with_bools ([&] (auto D3) {
+      constexpr int DIM = decltype (D3)::value ? 3 : 2;
+      hipLaunchKernelGGL (tree_feed_gather_kernel<DIM>, dim3 (grid), dim3 (block), 0, stream, tree_samp (V, S), A);
+    }, dim == 3);
+    GFSHIP_HIP (hipGetLastError ());
+    return GFSHIP_OK;
+  }
+};
+
 } // namespace
+
+// does the tree have the variable `var' for a function to read at a leaf?  tree_has_variable, but not the variables
+// of an octree alone on a quadtree: the arrays of W, its gradients and its face values are allocated there too, and
+// nothing ever writes them
+bool tree_feed_variable (gfship_particles * pl, int var)
+{
+  static const int octree_only[] = { GFSHIP_TREE_W, GFSHIP_TREE_GZ, GFSHIP_TREE_GMACZ, GFSHIP_TREE_UN4, GFSHIP_TREE_UN5,
+				     GFSHIP_TREE_BCW, GFSHIP_TREE_WPREV, GFSHIP_TREE_FZ, GFSHIP_TREE_WRELP };
+  if (pl->dim == 2)
+    for (int v : octree_only)
+      if (var == v) return false;
+  return tree_has_variable (pl->tree, var);
+}
 
 int tree_particle_list_event (gfship_particles * pl)
 {
@@ -1106,19 +1243,18 @@ int tree_particle_list_event (gfship_particles * pl)
   TreePartArgs A;
   for (int d = 0; d < 6; d++) A.side[d] = d < 2*V.H.dim ? V.side[d] : GFSHIP_SIDE_PERIODIC;
   A.n = pl->n;
-  const int uvar[3] = { GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP_TREE_W };
+  tree_velocity (pl->tree, V.H.dim, A.u);
   for (int c = 0; c < 3; c++) {
     A.pos[c] = pl->pos[c];
     A.old[c] = pl->old[c];
-    A.u[c] = c < V.H.dim ? tree_variable (pl->tree, uvar[c]) : nullptr;
   }
   A.alive = pl->alive;
   A.dt = V.dt;
   const int block = 256, grid = (pl->n + block - 1)/block;
-  if (V.H.dim == 3)
-    hipLaunchKernelGGL (tree_particle_list_event_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), A);
-  else
-    hipLaunchKernelGGL (tree_particle_list_event_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), A);
+  with_bools ([&] (auto D3) {
+    constexpr int DIM = decltype (D3)::value ? 3 : 2;
+    hipLaunchKernelGGL (tree_particle_list_event_kernel<DIM>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), A);
+  }, V.H.dim == 3);
   GFSHIP_HIP (hipGetLastError ());
   return GFSHIP_OK;
 }
@@ -1136,11 +1272,10 @@ static int tree_particulate_event (gfship_particles * pl, bool onfluid)
   TreePartArgs & P = A.P;
   for (int d = 0; d < 6; d++) P.side[d] = d < 2*dim ? V.side[d] : GFSHIP_SIDE_PERIODIC;
   P.n = pl->n;
-  const int uvar[3] = { GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP_TREE_W };
+  tree_velocity (pl->tree, dim, P.u);
   for (int c = 0; c < 3; c++) {
     P.pos[c] = pl->pos[c];
     P.old[c] = pl->old[c];
-    P.u[c] = c < dim ? tree_variable (pl->tree, uvar[c]) : nullptr;
     A.uold[c] = c < dim ? V.uprev[c] : nullptr;
   }
   P.alive = pl->alive;
@@ -1155,24 +1290,24 @@ static int tree_particulate_event (gfship_particles * pl, bool onfluid)
   const int block = 256, grid = (pl->n + block - 1)/block;
   const TreeSamp TS = tree_samp (V, S);
   r = particulate_coefficients (pl, A, V.stream, V.t, [&] {
-    if (dim == 3)
-      hipLaunchKernelGGL (tree_particulate_coeff_inputs_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
-    else
-      hipLaunchKernelGGL (tree_particulate_coeff_inputs_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+    with_bools ([&] (auto D3) {
+      constexpr int DIM = decltype (D3)::value ? 3 : 2;
+      hipLaunchKernelGGL (tree_particulate_coeff_inputs_kernel<DIM>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+    }, dim == 3);
   });
   if (r) return r;
   if (onfluid) {
-    if (dim == 3)
-      hipLaunchKernelGGL ((tree_particulate_list_event_kernel<3, true>), dim3 (grid), dim3 (block), 0, V.stream, TS, A);
-    else
-      hipLaunchKernelGGL ((tree_particulate_list_event_kernel<2, true>), dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+    with_bools ([&] (auto D3) {
+      constexpr int DIM = decltype (D3)::value ? 3 : 2;
+      hipLaunchKernelGGL ((tree_particulate_list_event_kernel<DIM, true>), dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+    }, dim == 3);
     GFSHIP_HIP (hipGetLastError ());
     return GFSHIP_OK;
   }
-  if (dim == 3)
-    hipLaunchKernelGGL (tree_particulate_list_event_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
-  else
-    hipLaunchKernelGGL (tree_particulate_list_event_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+  with_bools ([&] (auto D3) {
+    constexpr int DIM = decltype (D3)::value ? 3 : 2;
+    hipLaunchKernelGGL (tree_particulate_list_event_kernel<DIM>, dim3 (grid), dim3 (block), 0, V.stream, TS, A);
+  }, dim == 3);
   GFSHIP_HIP (hipGetLastError ());
   // the velocity of this step for the inertial force of the next one (:1003-1012: only for GfsForceInertial objects)
   for (int f = 0; f < pl->nforces; f++)
@@ -1190,12 +1325,11 @@ int tree_particle_keys (gfship_particles * pl, int * bits)
   int r = sampler_get (pl->tree, &V, &S);
   if (r) return r;
   const int block = 256, grid = (pl->n + block - 1)/block;
-  if (V.H.dim == 3)
-    hipLaunchKernelGGL (tree_particle_keys_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), pl->n,
+  with_bools ([&] (auto D3) {
+    constexpr int DIM = decltype (D3)::value ? 3 : 2;
+    hipLaunchKernelGGL (tree_particle_keys_kernel<DIM>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), pl->n,
 			pl->pos[0], pl->pos[1], pl->pos[2], pl->alive, pl->key, pl->slot);
-  else
-    hipLaunchKernelGGL (tree_particle_keys_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), pl->n,
-			pl->pos[0], pl->pos[1], pl->pos[2], pl->alive, pl->key, pl->slot);
+  }, V.H.dim == 3);
   GFSHIP_HIP (hipGetLastError ());
   /* the bits of a cell index (+1 so that the all-ones key of the dead sorts last) */
   int b = 0;
@@ -1204,41 +1338,27 @@ int tree_particle_keys (gfship_particles * pl, int * bits)
   return GFSHIP_OK;
 }
 
-int launch_tree_feed_gather (gfship_particles * pl, int base, int np, const double * cand, unsigned * cell)
+// gfship_feed_particle_event on a list of particulates of a tree
+int tree_feed_event (gfship_feed_particle * f, int np, const double * pos)
 {
-  TreeView V;
-  SamplerTables * S;
-  int r = sampler_get (pl->tree, &V, &S);
+  gfship_particles * pl = f->pl;
+  GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_feed_particle_event");
+  if (np == 0) return GFSHIP_OK;
+  TreeMesh M (pl);
+  int r = M.init ();
   if (r) return r;
-  TreeFeedGatherArgs A;
-  A.np = np; A.base = base;
-  A.cand = cand;
-  const int uvar[3] = { GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP_TREE_W };
-  for (int c = 0; c < 3; c++) {
-    A.u[c] = c < V.H.dim ? tree_variable (pl->tree, uvar[c]) : nullptr;
-    A.pos[c] = pl->pos[c]; A.old[c] = pl->old[c];
-    A.vel[c] = pl->vel[c]; A.force[c] = pl->force[c];
-  }
-  A.orig = pl->orig; A.cell = cell;
-  const int block = 256, grid = (np + block - 1)/block;
-  if (V.H.dim == 3)
-    hipLaunchKernelGGL (tree_feed_gather_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), A);
-  else
-    hipLaunchKernelGGL (tree_feed_gather_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), A);
-  GFSHIP_HIP (hipGetLastError ());
-  return GFSHIP_OK;
+  return feed_event_body (M, f, np, pos);
 }
 
-// source_particulatevol_event (:2834-2852) / source_particulatemass_event (:2993-3012) on a list of a tree.
-// info != nullptr: the milliseconds of the per-particle passes and of the sort with the pass per leaf
+// source_particulatevol_event (:2834-2852) / source_particulatemass_event (:2993-3012) on a list of a tree
 int tree_particulate_source_event (gfship_particulate_source * s, double * info)
 {
   gfship_particles * pl = s->pl;
   GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_particulate_source_event");
-  TreeView V;
-  SamplerTables * S;
-  int r = sampler_get (pl->tree, &V, &S);
+  TreeMesh M (pl);
+  int r = M.init ();
   if (r) return r;
+  const TreeView & V = M.V;
   const int dim = V.H.dim;
   const bool volume = s->kind == GFSHIP_PARTICULATE_SOURCE_VOLUME;
   double * D = nullptr, * R = nullptr, * U[3] = { nullptr, nullptr, nullptr };
@@ -1247,12 +1367,7 @@ int tree_particulate_source_event (gfship_particulate_source * s, double * info)
   for (int c = 0; c < dim; c++)
     if (s->urel[c] >= 0 && (r = tree_source_variable (pl->tree, s->urel[c], &U[c]))) return r;
   std::vector<const double *> read;
-  for (int var : s->read) {
-    const double * a = tree_variable (pl->tree, var);
-    GFSHIP_CHECK (a != nullptr, GFSHIP_EINVAL, "the tree has no variable %d", var);
-    read.push_back (a);
-  }
-  const bool fields = D || R || U[0] || U[1] || U[2];
+  if ((r = M.arrays (s->read, read))) return r;
   if (D) {
     /* gfs_domain_cell_traverse (..., FTT_TRAVERSE_ALL | FTT_TRAVERSE_LEAFS, 1, gfs_cell_reset): the interior cells of
        levels 0 and 1 for a volume, the leaves among them for a mass; every deeper cell keeps what it holds */
@@ -1271,78 +1386,7 @@ int tree_particulate_source_event (gfship_particulate_source * s, double * info)
       GFSHIP_HIP (hipGetLastError ());
     }
   }
-  if (info) info[0] = info[1] = 0.;
-  if (pl->n == 0) return GFSHIP_OK;
-  if ((r = particulate_source_reserve (s))) return r;
-  hipEvent_t ev[3] = { nullptr, nullptr, nullptr };
-  auto mark = [&] (int q) -> hipError_t {
-    if (!info) return hipSuccess;
-    hipError_t e = hipEventCreate (&ev[q]);
-    return e != hipSuccess ? e : hipEventRecord (ev[q], V.stream);
-  };
-  GFSHIP_HIP (mark (0));
-  const int n = pl->n, block = 256, grid = (n + block - 1)/block;
-  const TreeSamp TS = tree_samp (V, S);
-  TreeSourceGatherArgs G;
-  G.n = n;
-  const int uvar[3] = { GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP_TREE_W };
-  for (int c = 0; c < 3; c++) {
-    G.pos[c] = pl->pos[c];
-    G.u[c] = c < dim ? tree_variable (pl->tree, uvar[c]) : nullptr;
-    G.vel[c] = pl->vel[c];
-    G.urel[c] = s->purel[c];
-  }
-  G.alive = pl->alive; G.orig = pl->orig; G.volume = pl->volume;
-  G.cell = s->cell; G.rad = s->prad;
-  if (dim == 3)
-    hipLaunchKernelGGL (tree_particulate_source_gather_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, TS, G);
-  else
-    hipLaunchKernelGGL (tree_particulate_source_gather_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, TS, G);
-  GFSHIP_HIP (hipGetLastError ());
-  if (s->fn) {
-    if ((r = rtc_launch_tree_source (s->fn, V.stream, n, dim, V.H.depth, V.H.off, s->cell, s->prad, s->purel, V.t,
-				     (int) read.size (), read.data (), s->src)))
-      return r;
-  }
-  else if ((r = launch_fill (V.stream, n, s->value, s->src)))
-    return r;
-  const unsigned long long ncell = (unsigned long long) V.ncell;
-  if (fields && (r = coupling_reserve (pl, (size_t) n, 0, false))) return r;
-  if ((r = launch_particulate_source_update (s, V.stream, V.dt, ncell, fields ? pl->ckey : nullptr))) return r;
-  GFSHIP_HIP (mark (1));
-  if (fields) {
-    size_t need = 0;
-    const int bits = coupling_key_bits (ncell);
-    GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (nullptr, need, pl->ckey, pl->ckey2, n, 0, bits, V.stream));
-    if ((r = coupling_sort_reserve (pl, need))) return r;
-    size_t tmp_bytes = pl->sort_tmp_bytes;
-    GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, n, 0, bits, V.stream));
-    SourceCellArgs A;
-    A.n = n; A.key = pl->ckey2; A.ncell = ncell;
-    A.src = s->src; A.prad = s->prad;
-    A.deposit = D; A.rad = R;
-    for (int c = 0; c < 3; c++) {
-      A.purel[c] = s->purel[c];
-      A.urel[c] = c < dim ? U[c] : nullptr;
-    }
-    if (dim == 3)
-      hipLaunchKernelGGL ((particulate_source_cell_kernel<3, true, TreeCells<3>>), dim3 (grid), dim3 (block), 0, V.stream,
-			  TreeCells<3> { V.D }, A);
-    else
-      hipLaunchKernelGGL ((particulate_source_cell_kernel<2, true, TreeCells<2>>), dim3 (grid), dim3 (block), 0, V.stream,
-			  TreeCells<2> { V.D }, A);
-    GFSHIP_HIP (hipGetLastError ());
-  }
-  if (info) {
-    GFSHIP_HIP (mark (2));
-    GFSHIP_HIP (hipStreamSynchronize (V.stream));
-    float a = 0.f, b = 0.f;
-    (void) hipEventElapsedTime (&a, ev[0], ev[1]);
-    (void) hipEventElapsedTime (&b, ev[1], ev[2]);
-    info[0] = a; info[1] = b;
-    for (hipEvent_t e : ev) (void) hipEventDestroy (e);
-  }
-  return GFSHIP_OK;
+  return source_event_body (M, s, D, R, U, read, info);
 }
 
 } // namespace gfship
@@ -1370,12 +1414,11 @@ int gfship_tree_interpolate (gfship_tree * tr, int var, int np, const double * p
   hipError_t e = hipMemcpyAsync (dpos, pos, 3*(size_t) np*sizeof (double), hipMemcpyHostToDevice, V.stream);
   if (e == hipSuccess) {
     const int block = 256, grid = (np + block - 1)/block;
-    if (V.H.dim == 3)
-      hipLaunchKernelGGL (tree_sample_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), np, dpos, v,
+    with_bools ([&] (auto D3) {
+      constexpr int DIM = decltype (D3)::value ? 3 : 2;
+      hipLaunchKernelGGL (tree_sample_kernel<DIM>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), np, dpos, v,
 			  dout, din);
-    else
-      hipLaunchKernelGGL (tree_sample_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, tree_samp (V, S), np, dpos, v,
-			  dout, din);
+    }, V.H.dim == 3);
     e = hipGetLastError ();
   }
   if (e == hipSuccess)
@@ -1452,44 +1495,14 @@ int gfship_tree_particulate_field (gfship_particles * pl, int var)
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
   GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_tree_particulate_field");
   GFSHIP_CHECK (var == GFSHIP_TREE_VF, GFSHIP_EINVAL, "the variable of a GfsParticulateField is GFSHIP_TREE_VF");
-  TreeView V;
-  SamplerTables * S;
-  int r = sampler_get (pl->tree, &V, &S);
+  TreeMesh M (pl);
+  int r = M.init ();
   if (r) return r;
   double * a = nullptr;
   if ((r = tree_coupling_variable (pl->tree, var, &a))) return r;
-  const int block = 256;
   /* gfs_cell_reset on the leaves (:1944-1945) */
-  hipLaunchKernelGGL (tree_reset_leaves_kernel, dim3 ((V.nleaves + block - 1)/block), dim3 (block), 0, V.stream, V.D,
-		      V.dleaves, V.nleaves, a, (double *) nullptr, (double *) nullptr);
-  GFSHIP_HIP (hipGetLastError ());
-  if (pl->n == 0) return GFSHIP_OK;
-  if ((r = coupling_reserve (pl, (size_t) pl->n, 0, false))) return r;
-  const unsigned long long ncell = (unsigned long long) V.ncell;
-  const int grid = (pl->n + block - 1)/block;
-  const TreeSamp TS = tree_samp (V, S);
-  if (V.H.dim == 3)
-    hipLaunchKernelGGL (tree_field_keys_kernel<3>, dim3 (grid), dim3 (block), 0, V.stream, TS, pl->n, pl->pos[0],
-			pl->pos[1], pl->pos[2], pl->alive, pl->orig, ncell, pl->ckey);
-  else
-    hipLaunchKernelGGL (tree_field_keys_kernel<2>, dim3 (grid), dim3 (block), 0, V.stream, TS, pl->n, pl->pos[0],
-			pl->pos[1], pl->pos[2], pl->alive, pl->orig, ncell, pl->ckey);
-  GFSHIP_HIP (hipGetLastError ());
-  size_t need = 0;
-  const int bits = coupling_key_bits (ncell);
-  GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (nullptr, need, pl->ckey, pl->ckey2, pl->n, 0, bits, V.stream));
-  if ((r = coupling_sort_reserve (pl, need))) return r;
-  size_t tmp_bytes = pl->sort_tmp_bytes;
-  GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, pl->n, 0, bits,
-						 V.stream));
-  if (V.H.dim == 3)
-    hipLaunchKernelGGL ((field_sum_kernel<3, TreeCells<3>>), dim3 (grid), dim3 (block), 0, V.stream, TreeCells<3> { V.D },
-			pl->n, pl->ckey2, ncell, pl->volume, a);
-  else
-    hipLaunchKernelGGL ((field_sum_kernel<2, TreeCells<2>>), dim3 (grid), dim3 (block), 0, V.stream, TreeCells<2> { V.D },
-			pl->n, pl->ckey2, ncell, pl->volume, a);
-  GFSHIP_HIP (hipGetLastError ());
-  return GFSHIP_OK;
+  if ((r = M.reset_leaves (a))) return r;
+  return particulate_field_body (M, pl, a);
 }
 
 // the forces of source_particulate_event (:2199-2206)
@@ -1506,30 +1519,9 @@ int gfship_tree_particles_set_kernel (gfship_particles * pl, double rkernel, con
 {
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
   GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_tree_particles_set_kernel");
-  GFSHIP_CHECK (rkernel >= 0. && std::isfinite (rkernel), GFSHIP_EINVAL, "rkernel must be a length >= 0");
-  TreeView V;
-  tree_view (pl->tree, &V);
-  int r = tree_stride_check (V, rkernel);
-  if (r) return r;
-  RtcKernel * k = nullptr;
-  double value = 0.;
-  if (function) {
-    /* a constant (gfs_function_read: a number is kept as f->val) needs no compilation */
-    char * end = nullptr;
-    value = strtod (function, &end);
-    while (end != function && (*end == ' ' || *end == '\t' || *end == '\n' || *end == '\r')) end++;
-    if (end == function || *end != '\0') {
-      value = 0.;
-      GFSHIP_HIP (hipSetDevice (V.device));
-      if ((r = rtc_compile_spatial_on (V.device, function, &k))) return r;
-    }
-  }
-  GFSHIP_HIP (hipStreamSynchronize (pl->stream));
-  rtc_free (pl->kernel_fn);
-  pl->kernel_fn = k;
-  pl->kernel_value = value;
-  pl->rkernel = rkernel;
-  return GFSHIP_OK;
+  TreeMesh M (pl);
+  M.init (false);
+  return set_kernel_body (M, pl, rkernel, function);
 }
 
 // source_particulate_event from the stored forces (:2208-2222) into GFSHIP_TREE_FX ...
@@ -1537,81 +1529,15 @@ int gfship_tree_particles_spread_forces (gfship_particles * pl)
 {
   GFSHIP_CHECK (pl != nullptr, GFSHIP_EINVAL, "null particle list");
   GFSHIP_TREE_PARTICULATES_ONLY (pl, "gfship_tree_particles_spread_forces");
-  TreeView V;
-  SamplerTables * S;
-  int r = sampler_get (pl->tree, &V, &S);
+  TreeMesh M (pl);
+  int r = M.init ();
   if (r) return r;
-  const int dim = V.H.dim;
   double * Fa[3] = { nullptr, nullptr, nullptr };
-  for (int c = 0; c < dim; c++)
+  for (int c = 0; c < M.dim; c++)
     if ((r = tree_coupling_variable (pl->tree, GFSHIP_TREE_FX + c, &Fa[c]))) return r;
-  const int block = 256;
   /* gfs_cell_reset on the leaves (:2189-2191) */
-  hipLaunchKernelGGL (tree_reset_leaves_kernel, dim3 ((V.nleaves + block - 1)/block), dim3 (block), 0, V.stream, V.D,
-		      V.dleaves, V.nleaves, Fa[0], Fa[1], Fa[2]);
-  GFSHIP_HIP (hipGetLastError ());
-  if (pl->n == 0) return GFSHIP_OK;
-  if ((r = tree_stride_check (V, pl->rkernel))) return r;
-  const int stride = (int) tree_kernel_stride (V, pl->rkernel);
-  const int per_chunk = (int) std::min ((size_t) pl->n, COUPLING_RECORD_CAP/(size_t) stride);
-  if ((r = coupling_reserve (pl, (size_t) per_chunk*stride, (size_t) per_chunk, true))) return r;
-  const unsigned long long ncell = (unsigned long long) V.ncell;
-  const int bits = coupling_key_bits (ncell);
-  if ((r = launch_where (pl))) return r;
-  GFSHIP_HIP (hipMemsetAsync (pl->cflag, 0, sizeof (int), V.stream));
-  const TreeSamp TS = tree_samp (V, S);
-  TreeSpreadArgs A;
-  A.stride = stride; A.rkernel = pl->rkernel;
-  A.where = pl->where; A.alive = pl->alive; A.rb = pl->rb;
-  for (int c = 0; c < 3; c++) { A.pos[c] = pl->pos[c]; A.q[c] = pl->cq[c]; }
-  A.pad = ncell; A.key = pl->ckey; A.cnt = pl->ccnt; A.flag = pl->cflag;
-  for (int o0 = 0; o0 < pl->n; o0 += per_chunk) {
-    const int nchunk = std::min (per_chunk, pl->n - o0);
-    const long nrec = (long) nchunk*stride;
-    const int pgrid = (nchunk + block - 1)/block;
-    const unsigned rgrid = (unsigned) ((nrec + block - 1)/block);
-    A.o0 = o0; A.nchunk = nchunk;
-    if (dim == 3)
-      hipLaunchKernelGGL (tree_spread_emit_kernel<3>, dim3 (pgrid), dim3 (block), 0, V.stream, TS, A);
-    else
-      hipLaunchKernelGGL (tree_spread_emit_kernel<2>, dim3 (pgrid), dim3 (block), 0, V.stream, TS, A);
-    GFSHIP_HIP (hipGetLastError ());
-    if (pl->kernel_fn) {
-      if ((r = rtc_launch_spatial (pl->kernel_fn, V.stream, nrec, stride, pl->ccnt, pl->cq[0], pl->cq[1], pl->cq[2],
-				   V.t, pl->cval)))
-	return r;
-    }
-    else if ((r = launch_fill (V.stream, nrec, pl->kernel_value, pl->cval)))
-      return r;
-    if (dim == 3)
-      hipLaunchKernelGGL ((spread_correction_kernel<3, TreeCells<3>>), dim3 (pgrid), dim3 (block), 0, V.stream,
-			  TreeCells<3> { V.D }, nchunk, stride, pl->ccnt, pl->ckey, pl->cval, pl->ccorr);
-    else
-      hipLaunchKernelGGL ((spread_correction_kernel<2, TreeCells<2>>), dim3 (pgrid), dim3 (block), 0, V.stream,
-			  TreeCells<2> { V.D }, nchunk, stride, pl->ccnt, pl->ckey, pl->cval, pl->ccorr);
-    GFSHIP_HIP (hipGetLastError ());
-    size_t need = 0;
-    GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (nullptr, need, pl->ckey, pl->ckey2, pl->cval, pl->cval2, nrec, 0,
-						    bits, V.stream));
-    if ((r = coupling_sort_reserve (pl, need))) return r;
-    size_t tmp_bytes = pl->sort_tmp_bytes;
-    GFSHIP_HIP (hipcub::DeviceRadixSort::SortPairs (pl->sort_tmp, tmp_bytes, pl->ckey, pl->ckey2, pl->cval, pl->cval2,
-						    nrec, 0, bits, V.stream));
-    if (dim == 3)
-      hipLaunchKernelGGL ((spread_sum_kernel<3, false, TreeCells<3>>), dim3 (rgrid), dim3 (block), 0, V.stream,
-			  TreeCells<3> { V.D }, nrec, pl->ckey2, ncell, pl->cval2, o0, pl->ccorr, pl->force[0], pl->force[1],
-			  pl->force[2], nullptr, Fa[0], Fa[1], Fa[2]);
-    else
-      hipLaunchKernelGGL ((spread_sum_kernel<2, false, TreeCells<2>>), dim3 (rgrid), dim3 (block), 0, V.stream,
-			  TreeCells<2> { V.D }, nrec, pl->ckey2, ncell, pl->cval2, o0, pl->ccorr, pl->force[0], pl->force[1],
-			  pl->force[2], nullptr, Fa[0], Fa[1], Fa[2]);
-    GFSHIP_HIP (hipGetLastError ());
-  }
-  int flag = 0;
-  GFSHIP_HIP (hipMemcpyAsync (&flag, pl->cflag, sizeof (int), hipMemcpyDeviceToHost, V.stream));
-  GFSHIP_HIP (hipStreamSynchronize (V.stream));
-  GFSHIP_CHECK (flag == 0, GFSHIP_EHIP, "GfsSourceParticulate: a kernel reaches more than %d leaves", stride);
-  return GFSHIP_OK;
+  if ((r = M.reset_leaves (Fa[0], Fa[1], Fa[2]))) return r;
+  return spread_forces_body (M, pl, Fa, nullptr);
 }
 
 // source_particulate_event, :2177-2228

@@ -14,6 +14,8 @@ import tree_sampler_cases as TC
 import tree_sampler_reference as T
 import tree_two_way_cases as C
 import tree_two_way_reference as TW
+import two_way_cases as BC
+import two_way_reference as BR
 
 pytestmark = pytest.mark.gpu
 G = gfship.Tree
@@ -402,6 +404,46 @@ def test_uniform_tree_equals_uniform_box(dim, level):
             assert np.array_equal(got[inner], want[inner]) and np.abs(want).max() > 0., (rk, c)
     for x in (tl, ul, sim, dom, g):
         x.destroy()
+
+
+def test_spreading_in_two_chunks_on_a_uniform_octree():
+    """the chunk loop with a second chunk, as in tests/test_gpu_two_way.py: the uniform octree of level 5 and
+    rkernel = 16 h.  The record slots of a particle are those of the levels that hold leaves, min (floor (2 (rkernel
+    + (h/2) sqrt (3))/h) + 2, 2^level)^3 for the one level of this tree -- the stride of the box -- and 130 particles
+    times that many slots do not fit the 2^22 slots of a chunk.  Bit for bit the restatement of the box on the
+    forces of the device, which are order-sensitive inputs"""
+    level = BC.CHUNKS_DEPTH
+    n = 1 << level
+    h = 1./n
+    rkernel = BC.CHUNKS_RKERNEL_H*h
+    pos, ids, vel, mass, volume, _ = BC.spreading_chunks_case()
+    stride = min(int(np.floor(2.*(rkernel + h/2.*np.sqrt(3.))/h)) + 2, n)**3
+    assert stride == n**3 and len(pos)*stride > 1 << 22 and (1 << 22)//stride == BC.CHUNKS_PER_CHUNK < len(pos)
+    g = gfship.Tree(lambda x, y, z: level, dim=3)
+    u0 = TC.initial_velocity("cube", g.centres(level))
+    for c in range(3):
+        g.upload(UVARS[c], level, np.ascontiguousarray(np.broadcast_to(u0[c], (n + 2,)*3)))
+    for p in (g.projection_params, g.approx_projection_params):
+        p.tolerance = 1e-4
+    g.set_time(1e30, 0.8)
+    pl = g.particulates(pos, ids, vel, mass, volume)
+    pl.set_sort_interval(0)
+    try:
+        g.start()
+        g.set_viscosity(0, NU)
+        pl.set_forces([F.DRAG], (0., 0., 0.))
+        g.forces_on_fluid(pl)
+        force = pl.particulate_state()[2]
+        assert (np.abs(force).max(axis=1) > 0.).all()
+        want = BC.assert_two_chunks_are_order_sensitive(BR, pos, volume, force)
+        g.set_kernel(pl, rkernel, BC.CHUNKS_TEXT)
+        g.spread_forces(pl)
+        inner = (slice(1, -1),)*3
+        for c in range(3):
+            assert np.array_equal(g.download(FVARS[c], level)[inner], want[c]), c
+    finally:
+        pl.destroy()
+        g.destroy()
 
 
 # -------------------------------------------------------------------------------------------------

@@ -8,8 +8,8 @@ import pytest
 import gfship
 import two_way_reference as R
 from conftest import has_gpu
-from two_way_cases import (BOXES, RKERNEL_H, alpha_cell_case, poly_kernel, spreading_case,
-                           void_fraction_case)
+from two_way_cases import (BOXES, RKERNEL_H, alpha_cell_case, assert_two_chunks_are_order_sensitive, poly_kernel,
+                           spreading_case, spreading_chunks_case, void_fraction_case)
 
 
 @pytest.mark.parametrize("dim,depth", [(2, 3), (3, 2)])
@@ -116,6 +116,37 @@ def test_spreading_defaults_deposit_nothing():
     pos, ids, vel, mass, volume, force = spreading_case(2, 4)
     F, corr = R.spread(2, 4, pos, volume, force, 0., lambda x, y, z, t: 0.)
     assert all(not f.any() for f in F) and not (corr > 1.e-10).any()
+
+
+@pytest.mark.parametrize("rk", RKERNEL_H)
+@pytest.mark.parametrize("dim,depth", BOXES)
+def test_spread_flat_is_spread(dim, depth, rk):
+    """the restatement vectorised over the cells, bit for bit on every small case of this file, either list order,
+    with and without alpha"""
+    pos, ids, vel, mass, volume, force = spreading_case(dim, depth)
+    h = 1. / (1 << depth)
+    for alpha in (alpha_cell_case(dim, depth), None):
+        for s in (slice(None), slice(None, None, -1)):
+            F, corr = R.spread(dim, depth, pos[s], volume[s], force[s], rk * h, poly_kernel, alpha_cell=alpha)
+            G, gcorr = R.spread_flat(dim, depth, pos[s], volume[s], force[s], rk * h, poly_kernel, alpha_cell=alpha)
+            assert np.array_equal(corr, gcorr, equal_nan=True)
+            for c in range(dim):
+                assert np.array_equal(F[c], G[c]), c
+    assert any(f.any() for f in F)
+
+
+def test_spread_flat_of_the_defaults_deposits_nothing():
+    pos, ids, vel, mass, volume, force = spreading_case(2, 4)
+    F, corr = R.spread_flat(2, 4, pos, volume, force, 0., lambda x, y, z, t: 0.)
+    assert all(not f.any() for f in F) and not (corr > 1.e-10).any()
+
+
+def test_the_two_chunk_case_is_order_sensitive_on_the_restatement():
+    """the inputs of the multi-chunk GPU tests (with the stand-in forces), with and without alpha"""
+    pos, ids, vel, mass, volume, force = spreading_chunks_case()
+    for alpha in (alpha_cell_case(3, 5), None):
+        want = assert_two_chunks_are_order_sensitive(R, pos, volume, force, alpha)
+        assert all(f.all() for f in want)       # rkernel = 16 h: every particle reaches most of the box
 
 
 NEW_SYMBOLS = ["gfship_particulate_field", "gfship_particles_forces_on_fluid", "gfship_particles_set_kernel",

@@ -78,6 +78,43 @@ def spreading_case(dim, depth, seed=3):
     return pos, np.arange(1, npart + 1, dtype=np.uint32), vel, mass, volume, force
 
 
+# the spreading in more than one chunk (a chunk holds 2^22 record slots): a 3-D box of level 5, or the uniform octree
+# of that level, and rkernel = 16 h -- the slots of a particle are capped at the 32^3 leaves, 128 particles fill a
+# chunk, and the 130 particulates of spreading_chunks_case make a second chunk of two.  The kernel is positive
+# everywhere: every particle deposits
+CHUNKS_DEPTH, CHUNKS_RKERNEL_H, CHUNKS_PER_CHUNK, CHUNKS_N = 5, 16., 128, 130
+CHUNKS_TEXT = "(1. + 1e-6*(x*x + y*y + z*z))"
+
+
+def chunks_kernel(x, y, z, t):
+    return (1. + 1e-6 * (x * x + y * y + z * z))
+
+
+def spreading_chunks_case(seed=11):
+    """130 particulates anywhere in the 3-D box, volumes over three decades; `force' as in spreading_case"""
+    rng = np.random.default_rng(seed)
+    npart = CHUNKS_N
+    pos = rng.random((npart, 3)) - 0.5
+    volume = 10. ** rng.uniform(-4., -1., npart)
+    vel = rng.standard_normal((npart, 3))
+    vel *= (10. ** rng.uniform(-3., 4., npart) / np.sqrt((vel * vel).sum(axis=1)))[:, None]
+    mass = volume * (0.5 + 2.5 * rng.random(npart))
+    force = volume[:, None] * 10. * rng.standard_normal((npart, 3))
+    return pos, np.arange(1, npart + 1, dtype=np.uint32), vel, mass, volume, force
+
+
+def assert_two_chunks_are_order_sensitive(R, pos, volume, force, alpha=None):
+    """spread_flat of the two-chunk case with these forces: at least 20 particles of the first chunk and both of the
+    second deposit, and reversing the list changes at least one component.  Returns F of the list order"""
+    rk = CHUNKS_RKERNEL_H / (1 << CHUNKS_DEPTH)
+    want, corr = R.spread_flat(3, CHUNKS_DEPTH, pos, volume, force, rk, chunks_kernel, alpha_cell=alpha)
+    assert len(pos) == CHUNKS_N > CHUNKS_PER_CHUNK
+    assert (corr[:CHUNKS_PER_CHUNK] > 1.e-10).sum() >= 20 and (corr[CHUNKS_PER_CHUNK:] > 1.e-10).all()
+    rev, _ = R.spread_flat(3, CHUNKS_DEPTH, pos[::-1], volume[::-1], force[::-1], rk, chunks_kernel, alpha_cell=alpha)
+    assert any(not np.array_equal(want[c], rev[c]) for c in range(3))
+    return want
+
+
 def device_sim(gfship, osim, side):
     """a device simulation initialised from the current state of an oracle simulation, with its solver and
     advection parameters"""

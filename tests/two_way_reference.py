@@ -171,3 +171,51 @@ def spread(dim, depth, pos, volume, force, rkernel, K, t=0., alpha_cell=None):
             for c in range(dim):
                 F[c][at] -= float(f[c]) / liq_rho / cellvol * k / correction
     return F, np.array(corrections)
+
+
+def spread_flat(dim, depth, pos, volume, force, rkernel, K, t=0., alpha_cell=None):
+    """spread, with the loops over the cells as numpy operations (a box of 32^3 cells and a kernel that reaches all
+    of them is out of reach of the loops of spread).  Per particle in list order: the leaves in the order of the
+    traversal that pass cond_kernel themselves (flat_filter: the leaves of the pruned descent, see
+    test_pruned_descent_visits_the_leaves_of_the_flat_filter), kernel_volume as a strictly sequential accumulation
+    over them (np.add.accumulate, never a pairwise np.sum), then the subtraction of diffuse_force in every one of
+    them -- one cell at most once per particle, so the additions into a cell keep the list order.  Every operation
+    is the elementwise double operation of spread, in its order.  K takes arrays x, y, z."""
+    n = 1 << depth
+    h = 1. / n
+    cellvol = h * h * h if dim == 3 else h * h
+    order = np.array(traversal_order(dim, depth))             # [leaf][axis]
+    centre = -0.5 + (order + 0.5) * h                         # cell_centre
+    at = order[:, 1] * n + order[:, 0] if dim == 2 else (order[:, 2] * n + order[:, 1]) * n + order[:, 0]
+    size = h / 2.
+    radeq = size * math.sqrt(2.) if dim == 2 else size * math.sqrt(3.)
+    F = [np.zeros(n ** dim) for _ in range(dim)]
+    liq_rho = 1. / np.asarray(alpha_cell, dtype=float).reshape(-1) if alpha_cell is not None else None
+    corrections = []
+    for p, vol, f in zip(pos, volume, force):
+        p = [float(a) for a in p]
+        vol = float(vol)
+        d = [centre[:, c] - p[c] for c in range(dim)]         # cond_kernel
+        dist = np.sqrt(d[0] * d[0] + d[1] * d[1]) if dim == 2 else np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+        inside = np.ones(len(order), dtype=bool)
+        for c in range(dim):
+            inside &= ~((p[c] > centre[:, c] + size) | (p[c] < centre[:, c] - size))
+        leaves = np.flatnonzero((dist - radeq <= rkernel) | inside)
+        if len(leaves) == 0:
+            corrections.append(float("nan"))
+            continue
+        rb = (3. * vol / (4. * math.pi)) ** (1. / 3.)         # normalized_distance
+        x = (centre[leaves, 0] - p[0]) / rb
+        y = (centre[leaves, 1] - p[1]) / rb
+        z = np.full(len(leaves), (0. - p[2]) / rb if dim == 3 else 0.)
+        k = np.broadcast_to(np.asarray(K(x, y, z, t), dtype=float), x.shape)
+        ksum_volume = np.add.accumulate(np.full(len(leaves), cellvol))[-1]
+        correction = float(np.add.accumulate(k * cellvol)[-1] / ksum_volume)
+        corrections.append(correction)
+        if not correction > 1.e-10:
+            continue
+        cells = at[leaves]
+        for c in range(dim):
+            fc = float(f[c]) / (liq_rho[cells] if liq_rho is not None else 1.)
+            F[c][cells] -= fc / cellvol * k / correction
+    return [a.reshape((n,) * dim) for a in F], np.array(corrections)
