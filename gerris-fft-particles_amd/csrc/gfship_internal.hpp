@@ -380,7 +380,9 @@ int launch_project_correct_weighted (gfship_domain * dom, const double * p, doub
 				     double * const g[3], double * const u[3], double dt);
 int launch_project_correct_lazy (gfship_domain * dom, const double * p, double * const u[3],
 				 double * const g[3], double * const uo[3], double dt,
-				 bool * ghosts_done = nullptr);
+				 bool * ghosts_done = nullptr, bool store_g = true /* false: g stays unstored (pair kernel) */);
+bool project_pairs_apply (const gfship_domain * dom);    // the box is one the pair kernels of the projection take
+bool advect3_sweep_fits (const gfship_domain * dom);     // ... and one the sweeps along z of the advection take
 // div != nullptr: the caller's next operation is the MAC projection with time step div_dt; where the
 // predictor runs as the sweep along z it also leaves the scaled divergence of the new face velocities
 // in div (*div_done set): mac_projection then skips its divergence pass
@@ -388,10 +390,12 @@ int launch_predict_un_fused (gfship_domain * dom, double * const u[3], double dt
 			     const double visc[3], double * const un[3], double * div = nullptr,
 			     double div_dt = 0., bool * div_done = nullptr);
 // corr_dt != 0: gfs_correct_centered_velocities with gc and corr_dt applied in the same pass, and with uc
-// the level below the leaves of the corrected velocities (gfs_cell_coarse_init's first level)
+// the level below the leaves of the corrected velocities (gfs_cell_coarse_init's first level).  pr != nullptr: gc
+// is not read, it is formed as the centred gradient of the pressure pr (the sweep with the correction only)
 int launch_advect3_fused (gfship_domain * dom, double * const v[3], double * const out[3],
 			  double * const un[3], double * const gm[3], double * const gc[3],
-			  double dt, int gradient, double corr_dt = 0., double * const uc[3] = nullptr);
+			  double dt, int gradient, double corr_dt = 0., double * const uc[3] = nullptr,
+			  const double * pr = nullptr);
 int launch_advect_fused (gfship_domain * dom, bool velocity, const double * v, double * out,
 			 double * const un[3], const double * gm, const double * gc, double dt,
 			 int gradient, double visc, double gsrc = 0.);

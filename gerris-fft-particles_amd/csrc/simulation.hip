@@ -63,6 +63,13 @@ struct gfship_sim {
   bool un_lazy = false;
   double un_lazy_dt = 0.;
   bool un_handle_given = false;        // the caller holds the field handles of un: no lazy path any more
+  // the centred gradient g of the last approximate projection has not been stored: its one reader in the loop
+  // body, the advection of the next step, forms it from P (untouched in between), and materialize_g stores it
+  // when anybody else asks or is about to write P.  in_step: gfship_sim_step is under way and keeps g unstored
+  // across its own solves (which announce their writes like everybody else: before_write)
+  bool g_unstored = false, in_step = false;
+  bool g_handle_given = false;         // the caller holds the field handles of g: it is stored from then on
+  unsigned long long gradients_unstored = 0;   // projections that left g unstored (gfship_sim_gradients_unstored)
   gfship_field adv_tmp = -1;           // output of the fused advection kernel (swapped with v)
   gfship_field adv_tmp3[3] = {-1, -1, -1};   // the same for the three-component kernel
   gfship_next_event_fn next_event = nullptr; void * next_event_ctx = nullptr;
@@ -201,12 +208,49 @@ int materialize_un (gfship_sim * s)
   return GFSHIP_OK;
 }
 
+// the centred gradient the last approximate projection left unstored (gfship_sim.g_unstored): the kernel and the
+// ghost fill of a restart (gfship_sim_start), which rebuild g from P bit for bit -- one definition of the
+// expression (centered_gradient.hpp), and on the periodic boxes that leave g unstored the face ghosts the pair
+// kernel writes are the periodic images bc_leaf copies
+int materialize_g (gfship_sim * s)
+{
+  if (!s->g_unstored) return GFSHIP_OK;
+  s->g_unstored = false;
+  double * gp[3];
+  ptrs3 (s, s->g, gp);
+  TRY (launch_centered_gradient (s->dom, leaf (s, s->p), gp));
+  for (int c = 0; c < s->dom->dim; c++) {
+    s->dom->fields[s->g[c]].zero[s->dom->depth] = false;
+    TRY (bc_leaf (s, s->g[c]));
+  }
+  return GFSHIP_OK;
+}
+
+// Whether a step of the loop body may leave g unstored and advect with the gradient formed from P: the box and
+// the switches take advect3_sweep2_kernel with the fused correction and the pair kernel of the lazy approximate
+// projection, and nothing else reads g (mac_projection decides the rest: the conditions of its lazy path)
+bool g_unstored_applies (const gfship_sim * s)
+{
+  const gfship_domain * dom = s->dom;
+  if (s->g_handle_given || dom->dim != 3 || !godunov_fused_supported (dom) || dom->has_external) return false;
+  if (!advect3_sweep_fits (dom) || !project_pairs_apply (dom)) return false;
+  const Switches & sw = dom->sw;
+  if (!(sw.advect_sweep && !sw.advect_sweep1 && sw.advect3 && sw.fused_correction && sw.lazy_un && sw.project_pairs))
+    return false;
+  if (s->has_alpha || diffusion_faces (s) || s->has_srcf || s->advection_params.gradient > 1) return false;
+  for (int c = 0; c < 3; c++)
+    if (s->visc[c] != 0. || s->has_viscf[c] || dom->src[c] != 0.) return false;
+  return s->tracers.empty () && !s->un_handle_given;
+}
+
 // mac_projection, src/timestep.c:356-444.  `pdata` supplies the storage of the pressure and
 // `pbc` the boundary conditions (gfs_variables_swap swaps storage only, src/variable.c:234-243).
 // lazy: the approximate projection of the loop body of simulation_run, whose corrected MAC velocities
 // nobody reads (no tracers, no handle given out): they are not stored (see gfship_sim.un_lazy)
+// g_unstored (with lazy, and only where lazy holds; the caller has checked g_unstored_applies): the centred
+// gradient is not stored either (see gfship_sim.g_unstored)
 int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, gfship_field p,
-		    const gfship_field g[3], bool approximate = false, bool lazy = false)
+		    const gfship_field g[3], bool approximate = false, bool lazy = false, bool g_unstored = false)
 {
   gfship_domain * dom = s->dom;
   double * un[3], * gp[3], * u[3];
@@ -269,7 +313,13 @@ int mac_projection (gfship_sim * s, gfship_multilevel_params * par, double dt, g
       if (s->adv_tmp3[c] < 0) return s->adv_tmp3[c];
     }
     ptrs3 (s, s->adv_tmp3, uo);
-    TRY (launch_project_correct_lazy (dom, leaf (s, p), u, gp, uo, dt, &ghosts_done));
+    const bool store_g = !(g_unstored && g == s->g);
+    TRY (launch_project_correct_lazy (dom, leaf (s, p), u, gp, uo, dt, &ghosts_done, store_g));
+    if (!store_g) {
+      GFSHIP_CHECK (ghosts_done, GFSHIP_EINVAL, "g unstored on a box whose ghosts the kernel does not write");
+      s->g_unstored = true;
+      s->gradients_unstored++;
+    }
     for (int c = 0; c < dom->dim; c++) {
       std::swap (dom->fields[s->u[c]].lev[L], dom->fields[s->adv_tmp3[c]].lev[L]);
       dom->fields[s->u[c]].zero[L] = false;
@@ -483,8 +533,13 @@ int gfship_sim_create (gfship_sim ** out, gfship_domain * dom)
     gfship_sim_destroy (s);
     return GFSHIP_ENOMEM;
   }
-  /* the MAC velocities a step leaves unstored are stored before anybody overwrites a field */
-  dom->before_write = [] (void * ctx) -> int { return materialize_un ((gfship_sim *) ctx); };
+  /* the MAC velocities and the centred gradient a step leaves unstored are stored before anybody overwrites a
+     field (the solves of gfship_sim_step itself leave the gradient alone: it sees to it, see in_step) */
+  dom->before_write = [] (void * ctx) -> int {
+    gfship_sim * s = (gfship_sim *) ctx;
+    TRY (materialize_un (s));
+    return s->in_step ? GFSHIP_OK : materialize_g (s);
+  };
   dom->before_write_ctx = s;
   *out = s;
   return GFSHIP_OK;
@@ -514,7 +569,10 @@ gfship_field gfship_sim_variable (gfship_sim * s, int which, int c)
   case GFSHIP_VAR_P: return s->p;
   case GFSHIP_VAR_PMAC: return s->pmac;
   case GFSHIP_VAR_U: return s->u[c];
-  case GFSHIP_VAR_G: return s->g[c];
+  case GFSHIP_VAR_G:
+    if (materialize_g (s) != GFSHIP_OK) return GFSHIP_EHIP;
+    s->g_handle_given = true;
+    return s->g[c];
   case GFSHIP_VAR_GMAC: return s->gmac[c];
   case GFSHIP_VAR_TRACER:
     GFSHIP_CHECK ((size_t) c < s->tracers.size (), GFSHIP_EINVAL, "no tracer %d", c);
@@ -762,6 +820,7 @@ int gfship_mac_projection (gfship_sim * s, gfship_multilevel_params * par, doubl
 			   gfship_field p, const gfship_field g[3])
 {
   GFSHIP_CHECK (s && par && g, GFSHIP_EINVAL, "null argument");
+  TRY (materialize_g (s));             /* p may be P */
   return mac_projection (s, par, dt, p, g);
 }
 
@@ -770,6 +829,7 @@ int gfship_approximate_projection (gfship_sim * s, gfship_multilevel_params * pa
 {
   GFSHIP_CHECK (s && par && g, GFSHIP_EINVAL, "null argument");
   /* MAC velocities from the centred ones, projection, correction of the centred velocities */
+  TRY (materialize_g (s));             /* p may be P */
   TRY (mac_projection (s, par, dt, p, g, true));
   return GFSHIP_OK;
 }
@@ -777,9 +837,10 @@ int gfship_approximate_projection (gfship_sim * s, gfship_multilevel_params * pa
 // corr_dt != 0 (the loop body of simulation_run): the caller's next operation is
 // gfs_correct_centered_velocities (g, corr_dt) followed by gfs_cell_coarse_init -- where the three
 // components are advected in one pass that pass also applies the correction and fills the level below
-// the leaves of U, V, W (*corrected, *u_coarse set)
+// the leaves of U, V, W (*corrected, *u_coarse set).  g_pressure != nullptr: g is unstored, it is the centred
+// gradient of this pressure (the caller has checked g_unstored_applies: the one pass with the correction runs)
 static int centered_velocity_advection (gfship_sim * s, const gfship_field gmac[3], const gfship_field g[3],
-					 double corr_dt, bool * corrected, bool * u_coarse);
+					 double corr_dt, bool * corrected, bool * u_coarse, const double * g_pressure);
 
 int gfship_centered_velocity_advection (gfship_sim * s, const gfship_field gmac[3],
 					const gfship_field g[3])
@@ -788,11 +849,12 @@ int gfship_centered_velocity_advection (gfship_sim * s, const gfship_field gmac[
   /* the MAC velocities are an input, and the pass over the three components overwrites the scratch
      (adv_tmp3) they would be rebuilt from */
   TRY (materialize_un (s));
-  return centered_velocity_advection (s, gmac, g, 0., nullptr, nullptr);
+  TRY (materialize_g (s));             /* g may be the simulation's */
+  return centered_velocity_advection (s, gmac, g, 0., nullptr, nullptr, nullptr);
 }
 
 static int centered_velocity_advection (gfship_sim * s, const gfship_field gmac[3], const gfship_field g[3],
-					 double corr_dt, bool * corrected, bool * u_coarse)
+					 double corr_dt, bool * corrected, bool * u_coarse, const double * g_pressure)
 {
   if (corrected) *corrected = false;
   if (u_coarse) *u_coarse = false;
@@ -824,8 +886,9 @@ static int centered_velocity_advection (gfship_sim * s, const gfship_field gmac[
 	uc[c] = F->lev[L - 1];
 	F->zero[L - 1] = false;
       }
+    GFSHIP_CHECK (!g_pressure || fuse, GFSHIP_EINVAL, "g unstored without the fused correction");
     TRY (launch_advect3_fused (dom, v, out, un, gm, g ? gc : nullptr, s->advection_params.dt,
-			       s->advection_params.gradient, fuse ? corr_dt : 0., uc[0] ? uc : nullptr));
+			       s->advection_params.gradient, fuse ? corr_dt : 0., uc[0] ? uc : nullptr, g_pressure));
     for (int c = 0; c < 3; c++) {
       std::swap (dom->fields[s->u[c]].lev[L], dom->fields[s->adv_tmp3[c]].lev[L]);
       dom->fields[s->u[c]].zero[L] = false;
@@ -837,6 +900,7 @@ static int centered_velocity_advection (gfship_sim * s, const gfship_field gmac[
     TRY (bc_leaf_vector (s, s->u));
     return GFSHIP_OK;
   }
+  GFSHIP_CHECK (!g_pressure, GFSHIP_EINVAL, "g unstored on a path that reads it");
   for (int c = 0; c < s->dom->dim; c++) {
     if (has_viscosity (s, c)) {
       /* source_diffusion (v[c]): rhs = copy of v on the leaves, sources into rhs, implicit
@@ -969,6 +1033,13 @@ int gfship_sim_tracer_diffusion_counts (gfship_sim * s, unsigned long long count
   GFSHIP_CHECK (s && counts, GFSHIP_EINVAL, "null argument");
   counts[0] = s->tracer_diffusion_counts[0];
   counts[1] = s->tracer_diffusion_counts[1];
+  return GFSHIP_OK;
+}
+
+int gfship_sim_gradients_unstored (gfship_sim * s, unsigned long long * count)
+{
+  GFSHIP_CHECK (s && count, GFSHIP_EINVAL, "null argument");
+  *count = s->gradients_unstored;
   return GFSHIP_OK;
 }
 
@@ -1125,6 +1196,7 @@ int gfship_sim_start (gfship_sim * s)
 {
   GFSHIP_CHECK (s != nullptr, GFSHIP_EINVAL, "null simulation");
   GFSHIP_CHECK (s->advection_params.gc, GFSHIP_EUNSUPPORTED, "gc = 0 is not supported");
+  TRY (materialize_g (s));             /* both branches below write g; P may have been replaced */
   /* gfs_simulation_init (src/simulation.c:1068-1103): BCs on every variable, coarse cells */
   TRY (bc_leaf (s, s->p));
   TRY (bc_leaf (s, s->pmac));
@@ -1195,6 +1267,19 @@ int gfship_sim_step (gfship_sim * s)
   gfship_domain * dom = s->dom;
   const gfship_field * gc = s->g;
 
+  /* g of the approximate projection that ended the step before: where that one left it unstored and this step
+     still qualifies, the advection below forms it from P, which nothing writes before the approximate projection
+     of this step; anything else stores it now.  The first step uses gmac in its place and stays as it is. */
+  const bool unstored_applies = g_unstored_applies (s);
+  if (!(s->i > 0 && unstored_applies))
+    TRY (materialize_g (s));
+  const bool g_from_p = s->g_unstored;
+  struct InStep {
+    gfship_sim * s;
+    InStep (gfship_sim * s_) : s (s_) { s->in_step = true; }
+    ~InStep () { s->in_step = false; }
+  } in_step (s);
+
   TRY (predicted_face_velocities (s, s->advection_params.dt/2.));
 
   /* gfs_variables_swap (p, pmac); gfs_mac_projection (...dt/2, p, gmac); swap back
@@ -1209,7 +1294,7 @@ int gfship_sim_step (gfship_sim * s)
 
   bool u_coarse = false, corrected = false;
   TRY (centered_velocity_advection (s, s->gmac, s->i > 0 ? gc : s->gmac, - s->advection_params.dt,
-				    &corrected, &u_coarse));
+				    &corrected, &u_coarse, g_from_p ? leaf (s, s->p) : nullptr));
   if (!corrected)
     TRY (correct_centered_velocities (s, s->i > 0 ? gc : s->gmac, - s->advection_params.dt, &u_coarse));
 
@@ -1217,7 +1302,10 @@ int gfship_sim_step (gfship_sim * s)
      values are those of the state before the approximate projection, so it cannot be deferred */
   TRY (coarse_init (s, u_coarse));
 
-  TRY (mac_projection (s, &s->approx_projection_params, s->advection_params.dt, s->p, s->g, true, true));
+  s->g_unstored = false;               /* g is rewritten (or declared unstored) below */
+  TRY (mac_projection (s, &s->approx_projection_params, s->advection_params.dt, s->p, s->g, true, true,
+		       unstored_applies));
+  s->in_step = false;                  /* the hook of set_timestep below is the caller's code again */
   s->t = s->tnext;
   s->i++;
 

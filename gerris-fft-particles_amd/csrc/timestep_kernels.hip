@@ -14,6 +14,7 @@
 // cell in that same order (see flux_update_kernel).
 #include "gfship_internal.hpp"
 #include "cell_loop.hpp"
+#include "centered_gradient.hpp"
 #include <cfloat>
 
 namespace gfship {
@@ -116,18 +117,10 @@ centered_gradient_kernel (Layout L, const double * __restrict__ p, Ptr3 g)
 {
   CELL_LOOP_PROLOGUE (L);
   const long off[3] = { 1, L.sy, L.sz };
-  double h = 1./L.n;
+  const double rn = (double) L.n;
 #pragma unroll
-  for (int cc = 0; cc < DIM; cc++) {
-    double dpm = (1.*p[c] - 1.*p[c - off[cc]])/h;
-    dpm /= 1.;
-    double dpp = (1.*p[c + off[cc]] - 1.*p[c])/h;
-    dpp /= 1.;
-    double v = 0.;
-    v += dpm*1.;
-    v += dpp*1.;
-    g.p[cc][c] = v/2.;
-  }
+  for (int cc = 0; cc < DIM; cc++)
+    g.p[cc][c] = centered_gradient (p[c - off[cc]], p[c], p[c + off[cc]], rn);
 }
 
 // K11b: correct (src/timestep.c:486-496): u[c] -= g[c]*dt
@@ -362,12 +355,8 @@ project_correct2_kernel (Layout L, const double * __restrict__ p, Ptr3 un, Ptr3 
 	dpp /= 1.;
 	double w = e ? W.y : W.x;
 	w -= dpp*dt;
-	double dpm = (1.*pc - 1.*pm)*rn;
-	dpm /= 1.;
-	double v = 0.;
-	v += dpm*1.;
-	v += dpp*1.;
-	if (e) { W.y = w; G.y = v/2.; } else { W.x = w; G.x = v/2.; }
+	const double gg = centered_gradient (pm, pc, pn, rn);
+	if (e) { W.y = w; G.y = gg; } else { W.x = w; G.x = gg; }
       }
       *(d2 *) (un.p[cc] + c) = W;
       *(d2 *) (g.p[cc] + c) = G;
@@ -387,8 +376,9 @@ project_correct2_kernel (Layout L, const double * __restrict__ p, Ptr3 un, Ptr3 
 // and z and the six results move as 16-byte accesses (19 memory instructions per two cells instead of 38: the
 // 8-byte version is bound by the number of requests, not by bytes).  Same expressions per cell.  Rows of the
 // ghost planes (j = 0 or k = 0) and the column i = 0 keep the one-cell body.  PER: all six sides are periodic and
-// the face ghosts of g and of uo are written here (periodic_images_pair)
-template <bool PER>
+// the face ghosts of g and of uo are written here (periodic_images_pair).  STORE_G = false: g and its ghosts are
+// not stored (its only reader forms it from p: advect3_sweep2_kernel<..., GP>), everything else is the same
+template <bool PER, bool STORE_G>
 __global__ void __launch_bounds__(128)
 project_correct_lazy2_kernel (Layout L, const double * __restrict__ p, CPtr3 u, Ptr3 g, Ptr3 uo,
 			      double dt, double * __restrict__ partial_max)
@@ -422,7 +412,7 @@ project_correct_lazy2_kernel (Layout L, const double * __restrict__ p, CPtr3 u, 
 	  v += dpm*1.;
 	  v += dpp*1.;
 	  double gg = v/2.;
-	  g.p[cc][c] = gg;
+	  if (STORE_G) g.p[cc][c] = gg;
 	  double w = uc;
 	  w -= gg*dt;
 	  uo.p[cc][c] = w;
@@ -455,21 +445,16 @@ project_correct_lazy2_kernel (Layout L, const double * __restrict__ p, CPtr3 u, 
 	  double w = face_interp (uc, un_);
 	  w -= dpp*dt;
 	  mx = fmax (mx, fabs (w));
-	  double dpm = (1.*pc - 1.*pm)*rn;
-	  dpm /= 1.;
-	  double v = 0.;
-	  v += dpm*1.;
-	  v += dpp*1.;
-	  const double gg = v/2.;
+	  const double gg = centered_gradient (pm, pc, pn, rn);
 	  double w2 = uc;
 	  w2 -= gg*dt;
 	  mx = fmax (mx, fabs (1.*w2));
 	  if (e) { G.y = gg; W.y = w2; } else { G.x = gg; W.x = w2; }
 	}
-	*(d2 *) (g.p[cc] + c) = G;
+	if (STORE_G) *(d2 *) (g.p[cc] + c) = G;
 	*(d2 *) (uo.p[cc] + c) = W;
 	if (PER) {
-	  periodic_images_pair (L, g.p[cc], c, i1, j, k, G.x, G.y);
+	  if (STORE_G) periodic_images_pair (L, g.p[cc], c, i1, j, k, G.x, G.y);
 	  periodic_images_pair (L, uo.p[cc], c, i1, j, k, W.x, W.y);
 	}
       }
@@ -2287,6 +2272,12 @@ struct Sweep2Lds {
   double FL[3][3][SWY][SWX];                           // left states of plane p - 1: every thread its own slots
 };
 
+// GP (the centred gradient gc is not read but formed from the pressure it is the gradient of, centered_gradient):
+// the pressure of plane o = p - 1 of the tile and of the ring cells around it, by the parity of o -- the update of
+// plane o reads it after barrier (2) of iteration p, while the threads ahead write plane o + 1 into the other half
+template <bool GP> struct Sweep2Pressure { double P[2][SWY + 2][SWX + 2]; };
+template <> struct Sweep2Pressure<false> { double P[1][1][1]; };
+
 // MPI: a box with GfsBoundaryMpi sides (G.r[d] != nullptr: side d is one).  A ring cell beyond such a side is the
 // ghost cell itself (its value, gm and the MAC velocities of its faces are those the neighbour box sent), and its
 // state towards the column is what the neighbour computed for its own cell (boundary_face_values_kernel, one
@@ -2308,11 +2299,12 @@ __device__ __forceinline__ void sweep2_landed (double & x)
   asm volatile ("" : "+v" (x));
 }
 
-template <bool VL, bool SRC, bool MPI>
+template <bool VL, bool SRC, bool MPI, bool GP>
 __device__ __forceinline__ void sweep2_ring_path (Sweep2Lds & S_, const Layout & L, const CPtr3 & v, const CPtr3 & un,
 						  const CPtr3 & gm, double dt, const Visc3 & src3, int rid,
-						  const GhostFv & G)
+						  const GhostFv & G, Sweep2Pressure<GP> & SP_, const double * __restrict__ pr)
 {
+  static_assert (!(GP && MPI), "the gradient from the pressure: periodic boxes only");
   const int n = L.n;
   const double rn = (double) n, rsize2 = (double) n/2.;
   const int sy0 = (int) L.sy, sz = (int) L.sz;
@@ -2377,6 +2369,7 @@ __device__ __forceinline__ void sweep2_ring_path (Sweep2Lds & S_, const Layout &
   double huan[3] = { 0., 0., 0. }, hubn[2] = { 0., 0. };
   double hunb = 0., hunzb = 0., hlo[3] = { 0., 0., 0. }, hgmo[3] = { 0., 0., 0. }, hgmn[3] = { 0., 0., 0. };
   double hrcn[3] = { 0., 0., 0. };                   // the state beyond an MPI side
+  double hpn = 0.;                                   // GP: the pressure of the ring cell, plane p
   auto recv_at = [=] (int q, int k) { return recv[q*nf + (size_t) n*(k < 1 ? 0 : k > n ? n - 1 : k - 1)]; };
   if (fills) {
 #pragma unroll
@@ -2397,10 +2390,12 @@ __device__ __forceinline__ void sweep2_ring_path (Sweep2Lds & S_, const Layout &
     huan[1] = un.p[1][hc]; hubn[1] = un.p[1][hc - sy];
     huan[2] = un.p[2][hc];
     hunzb = un.p[2][hcol + plane (kb - 1)];
+    if (GP) hpn = pr[hcol + plane (kb - 1)];
   }
   for (int p = kb; p <= kb + SWZ + 1; p++) {
     const int zp = plane (p);
     double hua[3], hub[3], hno[3], hrc[3];
+    const double hpo = hpn;                          // the pressure of plane p - 1
 #pragma unroll
     for (int q = 0; q < 3; q++) {
       hvm[q] = hv0[q]; hv0[q] = hvp[q]; hvp[q] = hvn[q];
@@ -2429,6 +2424,7 @@ __device__ __forceinline__ void sweep2_ring_path (Sweep2Lds & S_, const Layout &
       huan[0] = un.p[0][hc1]; hubn[0] = un.p[0][hc1 - 1];
       huan[1] = un.p[1][hc1]; hubn[1] = un.p[1][hc1 - sy];
       huan[2] = un.p[2][hc1];
+      if (GP) hpn = pr[hcol + zp];
 #pragma unroll
       for (int q = 0; q < 3; q++) {
 	if (role == 3) S_.GM[q][hslot][SWX] = hgmo[q];
@@ -2440,6 +2436,10 @@ __device__ __forceinline__ void sweep2_ring_path (Sweep2Lds & S_, const Layout &
     __syncthreads ();                                // (1)
     double hl[3] = { 0., 0., 0. };
     if (ring) {
+      // the pressure of plane p - 1 is read after barrier (2); written here and not before barrier (1), the value
+      // loaded an iteration ago stays in its register past that barrier, and the copy that carries the new load
+      // round the loop cannot sit (with its wait) before it
+      if (GP) SP_.P[(p - 1) & 1][ry][rx] = hpo;
       const AdvShared S = adv_shared_v (hua, hub, dt, rsize2);
 #pragma unroll
       for (int q = 0; q < 3; q++) {
@@ -2491,18 +2491,22 @@ __device__ __forceinline__ void sweep2_ring_path (Sweep2Lds & S_, const Layout &
       if (MPI) sweep2_landed (hrcn[q]);
     }
     sweep2_landed (hubn[0]); sweep2_landed (hubn[1]);
+    if (GP) sweep2_landed (hpn);
   }
 }
 
-template <bool VL, bool SRC, bool CORR, bool MPI>
+// GP: gc is the centred gradient of the pressure pr, which is read in its place (8 B per cell instead of 24): the
+// column carries pr of the planes o - 1, o, o + 1, the x and y neighbours of plane o come from Sweep2Pressure
+template <bool VL, bool SRC, bool CORR, bool MPI, bool GP>
 __global__ void __launch_bounds__(SWN + SW_RING)
 advect3_sweep2_kernel (Layout L, CPtr3 v, Ptr3 out, CPtr3 un, CPtr3 gm, CPtr3 gc, double dt, Visc3 src3,
-		       AdvCorr K, GhostFv G)
+		       AdvCorr K, GhostFv G, const double * __restrict__ pr)
 {
   __shared__ Sweep2Lds S_;
+  __shared__ Sweep2Pressure<GP> SP_;
   const int tid = threadIdx.x;
   if (tid >= SWN) {
-    sweep2_ring_path<VL, SRC, MPI> (S_, L, v, un, gm, dt, src3, tid - SWN, G);
+    sweep2_ring_path<VL, SRC, MPI, GP> (S_, L, v, un, gm, dt, src3, tid - SWN, G, SP_, pr);
     return;
   }
   const int tx = tid % SWX, ty = tid / SWX;
@@ -2522,6 +2526,8 @@ advect3_sweep2_kernel (Layout L, CPtr3 v, Ptr3 out, CPtr3 un, CPtr3 gm, CPtr3 gc
   double fpz[3] = { 0., 0., 0. };                    // fluxes through the z face below plane p - 1
   double gmo[3], gmc[3];                             // gm (p - 1), gm (p) of the own cell
   double low[3] = { 0., 0., 0. };                    // corrected values of the odd plane (coarse cells)
+  double pcm = 0., pc0 = 0., pcp = 0.;               // GP: pr (p - 2), pr (p - 1), pr (p) of the column
+  if (GP) pcp = pr[col + plane (kb - 1)];
 #pragma unroll
   for (int q = 0; q < 3; q++) {
     v0[q] = v.p[q][col + plane (kb - 1)];
@@ -2558,9 +2564,15 @@ advect3_sweep2_kernel (Layout L, CPtr3 v, Ptr3 out, CPtr3 un, CPtr3 gm, CPtr3 gc
       gmo[q] = gmc[q];
       gmc[q] = gm.p[q][col + zp];
     }
+    if (GP) {
+      pcm = pc0; pc0 = pcp;
+      pcp = pr[col + zp];
+    }
+    else {
 #pragma unroll
-    for (int q = 0; q < 3; q++)
-      gcv[q] = gcl[q][col + plane (p - 1)];
+      for (int q = 0; q < 3; q++)
+	gcv[q] = gcl[q][col + plane (p - 1)];
+    }
 #pragma unroll
     for (int q = 0; q < 3; q++)
       vn[q] = v.p[q][col + plane (p + 2)];
@@ -2579,6 +2591,7 @@ advect3_sweep2_kernel (Layout L, CPtr3 v, Ptr3 out, CPtr3 un, CPtr3 gm, CPtr3 gc
     }
     S_.UNx[ty][tx + 1] = una[0];
     S_.UNy[ty + 1][tx] = una[1];
+    if (GP) SP_.P[ro][ty + 1][tx + 1] = pc0;
     __syncthreads ();                                // (1)
     double flz[3] = { 0., 0., 0. };
     if (p > kb) {
@@ -2642,9 +2655,16 @@ advect3_sweep2_kernel (Layout L, CPtr3 v, Ptr3 out, CPtr3 un, CPtr3 gm, CPtr3 gc
     for (int q = 0; q < 3; q++) {
       sweep2_landed (vn[q]); sweep2_landed (unn[q]);
     }
+    if (GP) sweep2_landed (pcp);
     if (p > kb) {
       const int o = p - 1, co = col + plane (o);
       if (p > kb + 1) {
+	if (GP) {
+	  // the centred gradient of plane o, as the projection that left pr formed it
+	  gcv[0] = centered_gradient (SP_.P[ro][ty + 1][tx], pc0, SP_.P[ro][ty + 1][tx + 2], rn);
+	  gcv[1] = centered_gradient (SP_.P[ro][ty][tx + 1], pc0, SP_.P[ro][ty + 2][tx + 1], rn);
+	  gcv[2] = centered_gradient (pcm, pc0, pcp, rn);
+	}
 	// ---- C (o): the gather in the reference's scatter order (flux_update_kernel), the update
 	const int k = o;
 	const unsigned J = n - j, K_ = n - k;
@@ -2676,7 +2696,7 @@ advect3_sweep2_kernel (Layout L, CPtr3 v, Ptr3 out, CPtr3 un, CPtr3 gm, CPtr3 gc
 	    acc += Fmz;
 	  double val = vm[q];
 	  val += acc/1.;
-	  if (gc.p[q])
+	  if (GP || gc.p[q])
 	    val -= gcv[q]*dt;
 	  if (SRC && src3.g[q] != 0.) { /* gfs_domain_variable_centered_sources, src/source.c:62-108 */
 	    double sum = 0;
@@ -3386,9 +3406,16 @@ int launch_face_interp_div (gfship_domain * dom, double * const u[3], double * c
 
 // the update of the approximate projection without the MAC velocities (project_correct_lazy_kernel):
 // g and the corrected centred velocities uo from p and the uncorrected u; the maxima for the CFL
-// condition are always left behind
+// condition are always left behind.  store_g = false (pair kernel only): g is not written
+bool project_pairs_apply (const gfship_domain * dom)
+{
+  const Layout & L = dom->lay[dom->depth];
+  return dom->dim == 3 && L.n >= 64 && L.n % 2 == 0;
+}
+
 int launch_project_correct_lazy (gfship_domain * dom, const double * p, double * const u[3],
-				 double * const g[3], double * const uo[3], double dt, bool * ghosts_done)
+				 double * const g[3], double * const uo[3], double dt, bool * ghosts_done,
+				 bool store_g)
 {
   if (ghosts_done) *ghosts_done = false;
   const Layout & L = dom->lay[dom->depth];
@@ -3405,16 +3432,18 @@ int launch_project_correct_lazy (gfship_domain * dom, const double * p, double *
     GFSHIP_HIP (hipMemsetAsync (dom->cfl_partial, 0, nb*sizeof (double), dom->stream));
   dom->cfl_dirty = true;
   const bool pairs = dom->sw.project_pairs;
-  const bool pairs_apply = dom->dim == 3 && L.n >= 64 && L.n % 2 == 0;
+  const bool pairs_apply = project_pairs_apply (dom);
+  GFSHIP_CHECK (store_g || (pairs_apply && pairs), GFSHIP_EINVAL, "only the pair kernel leaves g unstored");
   if (pairs_apply) dom->kc[pairs ? GFSHIP_KC_PROJECT_PAIRS : GFSHIP_KC_PROJECT_SCALAR]++;
   if (pairs_apply && pairs) {
     /* two cells per thread, 16-byte accesses */
     const int b = 128, half = L.n/2;
     const bool per = ghosts_done && all_sides_periodic (dom);
-    with_bools ([&] (auto PER) {
-      hipLaunchKernelGGL (project_correct_lazy2_kernel<decltype (PER)::value>, dim3 ((half + b - 1)/b, L.n + 1, L.n + 1), dim3 (b), 0,
+    with_bools ([&] (auto PER, auto STORE_G) {
+      hipLaunchKernelGGL ((project_correct_lazy2_kernel<decltype (PER)::value, decltype (STORE_G)::value>),
+			  dim3 ((half + b - 1)/b, L.n + 1, L.n + 1), dim3 (b), 0,
 			  dom->stream, L, p, c3 (u), m3 (g), m3 (uo), dt, dom->cfl_partial);
-    }, per);
+    }, per, store_g);
     if (per) *ghosts_done = true;
   }
   else if (dom->dim == 3)
@@ -3545,10 +3574,18 @@ int launch_advect_diffuse_fused (gfship_domain * dom, const double * v, double *
   return GFSHIP_OK;
 }
 
-// the three velocity components at once (3-D box of periodic / MPI sides, no viscosity)
+bool advect3_sweep_fits (const gfship_domain * dom)
+{
+  const Layout & L = dom->lay[dom->depth];
+  return dom->sw.advect_sweep && L.n % SWX == 0 && L.n % SWY == 0 && L.n % SWZ == 0;
+}
+
+// the three velocity components at once (3-D box of periodic / MPI sides, no viscosity).  pr != nullptr: gc is
+// not stored, it is the centred gradient of the pressure pr (advect3_sweep2_kernel with the fused correction on
+// a periodic box without sources, or an error)
 int launch_advect3_fused (gfship_domain * dom, double * const v[3], double * const out[3],
 			  double * const un[3], double * const gm[3], double * const gc[3],
-			  double dt, int gradient, double corr_dt, double * const uc[3])
+			  double dt, int gradient, double corr_dt, double * const uc[3], const double * pr)
 {
   const Layout & L = dom->lay[dom->depth];
   dim3 grid (L.n/GX, L.n/GY, L.n/GZ);
@@ -3565,6 +3602,9 @@ int launch_advect3_fused (gfship_domain * dom, double * const v[3], double * con
   GFSHIP_CHECK (!corr || gc, GFSHIP_EINVAL, "the fused correction needs the centred gradient");
   const bool srcs = dom->src[0] != 0. || dom->src[1] != 0. || dom->src[2] != 0.;
   const bool mpi = dom->has_external;
+  const bool sweep_fits = advect3_sweep_fits (dom);
+  GFSHIP_CHECK (!pr || (sweep_fits && !mpi && !dom->sw.advect_sweep1 && corr && !srcs), GFSHIP_EINVAL,
+		"the gradient from the pressure: advect3_sweep2_kernel with the correction and no sources only");
   if (mpi) {
     int r = ghost_fv (dom, &G);
     if (r) return r;
@@ -3577,7 +3617,6 @@ int launch_advect3_fused (gfship_domain * dom, double * const v[3], double * con
     if ((r = comm_exchange_raw (dom, dom->gfv_send, dom->gfv_recv, (size_t) 3*L.n*L.n))) return r;
     dom->n_fused_mpi++;
   }
-  const bool sweep_fits = dom->sw.advect_sweep && L.n % SWX == 0 && L.n % SWY == 0 && L.n % SWZ == 0;
   if (sweep_fits && (!mpi || dom->sw.mpi_sweep)) {
     /* the sweep along z; on a box with MPI sides the states beyond those sides come from the received buffers */
     const dim3 sgrid (L.n/SWX, L.n/SWY, L.n/SWZ);
@@ -3587,10 +3626,16 @@ int launch_advect3_fused (gfship_domain * dom, double * const v[3], double * con
 	hipLaunchKernelGGL ((advect3_sweep_kernel<decltype (VL)::value, decltype (SRC)::value, decltype (CORR)::value>),
 			    sgrid, dim3 (SWN + SW_RING), 0, dom->stream, L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K);
       }, gradient != 0, srcs, corr);
+    else if (pr)
+      with_bools ([&] (auto VL) {
+	hipLaunchKernelGGL ((advect3_sweep2_kernel<decltype (VL)::value, false, true, false, true>),
+			    sgrid, dim3 (SWN + SW_RING), 0, dom->stream, L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K, G, pr);
+      }, gradient != 0);
     else
       with_bools ([&] (auto VL, auto SRC, auto CORR, auto MPI) {
-	hipLaunchKernelGGL ((advect3_sweep2_kernel<decltype (VL)::value, decltype (SRC)::value, decltype (CORR)::value, decltype (MPI)::value>),
-			    sgrid, dim3 (SWN + SW_RING), 0, dom->stream, L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K, G);
+	hipLaunchKernelGGL ((advect3_sweep2_kernel<decltype (VL)::value, decltype (SRC)::value, decltype (CORR)::value, decltype (MPI)::value, false>),
+			    sgrid, dim3 (SWN + SW_RING), 0, dom->stream, L, c3 (v), m3 (out), c3 (un), c3 (gm), gcp, dt, vs, K, G,
+			    (const double *) nullptr);
       }, gradient != 0, srcs, corr, mpi);
     GFSHIP_HIP (hipGetLastError ());
     dom->kc[mpi ? GFSHIP_KC_ADVECT3_SWEEP2_MPI : sweep1 ? GFSHIP_KC_ADVECT3_SWEEP1 : GFSHIP_KC_ADVECT3_SWEEP2]++;

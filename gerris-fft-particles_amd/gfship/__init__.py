@@ -114,6 +114,7 @@ SIGNATURES = {
     "gfship_sim_tracer_diffusion_params": (C.POINTER(MultilevelParams), [_vp, _i]),
     "gfship_sim_tracer_diffusion_path": (_i, [_vp, _i]),
     "gfship_sim_tracer_diffusion_counts": (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    "gfship_sim_gradients_unstored": (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     "gfship_predicted_face_velocities": (_i, [_vp]),
     "gfship_mac_projection": (_i, [_vp, C.POINTER(MultilevelParams), _d, _i, _pi]),
     "gfship_approximate_projection": (_i, [_vp, C.POINTER(MultilevelParams), _d, _i, _pi]),
@@ -630,7 +631,7 @@ class Simulation:
         self.p = self._var(self.VAR_P)
         self.pmac = self._var(self.VAR_PMAC)
         self.u = [self._var(self.VAR_U, c) for c in range(dim)]
-        self.g = [self._var(self.VAR_G, c) for c in range(dim)]
+        self._g = None
         self.gmac = [self._var(self.VAR_GMAC, c) for c in range(dim)]
         self.projection_params = L.gfship_sim_projection_params(self.ptr).contents
         self.approx_projection_params = L.gfship_sim_approx_projection_params(self.ptr).contents
@@ -638,6 +639,14 @@ class Simulation:
 
     def _var(self, which, c=0):
         return _SimVariable(self.dom, _check(lib().gfship_sim_variable(self.ptr, which, c)))
+
+    @property
+    def g(self):
+        """the centred pressure gradient: the handles are fetched on first use, and from then on the time
+        step stores g (a simulation whose g nobody asks for leaves it unstored between steps)"""
+        if self._g is None:
+            self._g = [self._var(self.VAR_G, c) for c in range(self.dom.dim)]
+        return self._g
 
     def set_source(self, c, g):
         """GfsSource {} U/V/W g: constant intensity"""
@@ -730,6 +739,12 @@ class Simulation:
     def mac_velocity(self, c):
         """MAC velocity of the + face of every cell along c (GFSHIP_VAR_UN)"""
         return self._var(self.VAR_UN, c)
+
+    def gradients_unstored(self):
+        """how many projections of step() have left their centred gradient unstored so far"""
+        c = C.c_ulonglong()
+        _check(lib().gfship_sim_gradients_unstored(self.ptr, C.byref(c)))
+        return int(c.value)
 
     def advection_step(self):
         """loop body of advection_run (GfsAdvection) with the MAC velocities as they are"""

@@ -236,7 +236,10 @@ enum { GFSHIP_VAR_P = 0, GFSHIP_VAR_PMAC = 1, GFSHIP_VAR_U = 2, GFSHIP_VAR_G = 3
    gfship_sim_variable (GFSHIP_VAR_UN)) or that lets the caller write a field of the domain
    (gfship_field_upload, _fill, _device_ptr, gfship_bc, the snapshot reader, the solvers called on
    their own) stores them first, from the fields as the step left them.  So the pieces and
-   gfship_sim_step can be mixed in any order, and the fields can be rewritten between two calls. */
+   gfship_sim_step can be mixed in any order, and the fields can be rewritten between two calls.
+   Likewise the centred gradient g of that projection where its only reader is the advection of the
+   next gfship_sim_step, which forms it from P: it is stored before the caller can write a field, and
+   for good once gfship_sim_variable (GFSHIP_VAR_G) has given out its handles. */
 int  gfship_sim_create (gfship_sim ** sim, gfship_domain * dom);
 void gfship_sim_destroy (gfship_sim * sim);
 gfship_field gfship_sim_variable (gfship_sim * sim, int which, int c);
@@ -283,6 +286,9 @@ gfship_multilevel_params * gfship_sim_tracer_diffusion_params (gfship_sim * sim,
    and by the composed path since the simulation was created. */
 int      gfship_sim_tracer_diffusion_path (gfship_sim * sim, int fused);
 int      gfship_sim_tracer_diffusion_counts (gfship_sim * sim, unsigned long long counts[2]);
+/* How many projections of gfship_sim_step have left their centred gradient unstored so far (see
+   gfship_sim_create: for tests, the stored and the unstored path give the same bits). */
+int      gfship_sim_gradients_unstored (gfship_sim * sim, unsigned long long * count);
 /* GfsSourceDiffusion {} U|V|W nu (src/source.c:933-1160): constant implicit viscosity of
    velocity component c (0. removes it), and the GfsMultilevelParams of its solver
    (tolerance 1e-6, beta 1: diffusion_init, src/source.c:966-974) */

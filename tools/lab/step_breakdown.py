@@ -1,15 +1,23 @@
 #!/usr/bin/env python3
 """Per-step kernel shares from a rocprofv3 kernel trace of bench.py: the dispatches between the
 starts of the 2nd and the last advection launch, summed by kernel (sweep-loop kernels by grid size).
-usage: step_breakdown.py <dir with *_kernel_trace.csv> [name of the once-per-step kernel]"""
+usage: step_breakdown.py <dir with *_kernel_trace.csv or *_results.db> [name of the once-per-step kernel]
+(a rocprofv3 that writes its database by default: the same columns from the `kernels` view of *_results.db)"""
 import collections
 import csv
 import glob
+import sqlite3
 import sys
 
-f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
+f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)
 mark = sys.argv[2] if len(sys.argv) > 2 else "advect3"
-rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
+if f:
+    rows = list(csv.DictReader(open(f[0])))
+else:
+    db = sqlite3.connect(glob.glob(sys.argv[1] + "/**/*_results.db", recursive=True)[0])
+    cols = ("Kernel_Name", "Start_Timestamp", "End_Timestamp", "Grid_Size_X")
+    rows = [dict(zip(cols, r)) for r in db.execute("select name, start, end, grid_x from kernels")]
+rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 adv = [i for i, r in enumerate(rows) if mark in r["Kernel_Name"]]
 if len(adv) < 3:
     sys.exit("fewer than 3 launches of %s" % mark)
