@@ -10,9 +10,9 @@
 //    per face and a kernel in which every cell gathers the numbers of its faces IN THE ORDER the
 //    reference's traversal visits them -- the same floating-point sums, no atomics;
 //  * the Gauss-Seidel sweep of gfs_relax visits the cells of a level and the coarser leaves in tree
-//    order (src/poisson.c:604-632): the host derives, from the very stencil code the kernels run
-//    (tree.hpp with a recording reader), which cells each cell reads, and groups the cells of the
-//    sweep into dependency levels; one workgroup then runs a whole relax loop (nrelax sweeps with
+//    order (src/poisson.c:604-632): the planner (tree_plan.hip, plain host code) derives, from the very
+//    stencil code the kernels run (tree.hpp with a recording reader), which cells each cell reads, and groups
+//    the cells of the sweep into dependency levels; one workgroup then runs a whole relax loop (nrelax sweeps with
 //    the periodic copies between them, src/poisson.c:1070-1089), level after level, barrier between
 //    -- by default as a dataflow program of fixed-format micro-operations (tree_flow.hpp, t_relax_flow),
 //    else from the tapes of the compiled stencils (t_relax_nodes_pf, t_relax_tape) or by the code that
@@ -23,18 +23,17 @@
 // Restated here: src/poisson.c:998-1269 (cycle, solve), src/timestep.c:36-187,356-444,498-530,560-596,
 // 644-717,872-921,976-1016, src/advection.c:27-99,132-180,267-343,398-435,513-587,
 // src/fluid.c:1843-1864,2310-2324, src/domain.c:2239-2288,2824-2923, src/simulation.c:432-557,
-// 1569-1633, src/ftt.c:45-83,169-192,2013-2074 (refinement with the neighbour and corner rules).
+// 1569-1633.  The tree itself, its lists and every plan are made by tree_plan.hip (tree_plan.hpp has the types):
+// this file uploads them (one `upload' per type) and runs them.
 #include "gfship_internal.hpp"
 #include "cell_loop.hpp"
-#include "tree.hpp"
+#include "tree_plan.hpp"
+#include "tree_tape.hpp"
 #include "tree_particles.hpp"
 #include <algorithm>
-#include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstring>
-#include <functional>
-#include <map>
 #include <new>
 
 using namespace gfship;
@@ -57,52 +56,39 @@ const int abi_nvar = sizeof (abi_var)/sizeof (abi_var[0]);
 struct P3 { double * p[3]; };       // the components of a vector
 struct P6 { double * p[6]; };       // a number per direction
 
-struct FaceRec { Cell cell, neighbor; int d; };
-struct Ghost { int g, img, side, l; };   // img: the periodic image, or the cell the ghost touches (GfsBoundary)
-struct Sgn6 { double s[6]; };            // homogeneous condition of each side: ghost = s * cell
+// The plans of tree_plan.hpp on the device: pointers and sizes, plus only the host data that is read again later
 
-struct FaceSet {            // the faces of one ftt_face_traverse, in its order
+struct FaceSet {            // FacePlan
   int nfaces = 0;
-  FaceRec * faces = nullptr;          // device
-  int * inc_off = nullptr;            // device, per leaf (position in the leaf list) + 1
-  int * inc = nullptr;                // device: face << 1 | role (0: the cell of the face, 1: its neighbour)
-  double * fval = nullptr;            // device, one number per face
+  FaceRec * faces = nullptr;
+  int * inc_off = nullptr, * inc = nullptr;
+  double * fval = nullptr;            // one number per face
 };
 
-struct FlowPlan;            // tree_flow.hpp: the relax loop as a dataflow program of micro-operations
+struct FlowPlan {           // FlowProgram, and the working copies of the loop
+  int nlev = 0, nct = 0, npos = 0, width = FLOW_WIDTH;
+  FlowRec * rec = nullptr;
+  int * lev_off = nullptr, * gidx = nullptr;
+  double * ct = nullptr;
+  double * up = nullptr, * rp = nullptr;   // the values and the right-hand side in the order of the plan
+};
 
-struct Sweep {              // T_LEVEL_LEAFS (m) in dependency levels
-  int ncells = 0, nlev = 0;
-  Cell * cells = nullptr;             // device, sorted by level (stable: traversal order inside)
-  int * lev_off = nullptr;            // device, nlev + 1
-  Ghost * ghosts = nullptr; int nghosts = 0;   // ghost cells of the selection
-  // the stencils of the sweep compiled once (the tree is static): per cell, in the order of `cells',
-  // a stream of codes / counts (ti), of constant coefficients (td) and of the cells whose values it
-  // reads (tv); the cells of a dependency level in chunks that fit the LDS (stencil_tape)
-  int * ti = nullptr, * tv = nullptr;
+struct Sweep {              // SweepPlan
+  int ncells = 0, nlev = 0, nghosts = 0, nchunks = 0;
+  Cell * cells = nullptr;
+  int * lev_off = nullptr, * ti = nullptr, * tv = nullptr, * cell_off = nullptr, * chunk = nullptr;
+  Ghost * ghosts = nullptr;
   double * td = nullptr;
-  int * cell_off = nullptr;           // device, 3*(ncells + 1): start of each cell in ti / td / tv
-  int * chunk = nullptr; int nchunks = 0;   // device, 2*(nchunks): first cell, dependency level; + end marker
   bool taped = false;
-  // host copies of the streams and of the order, for the plan of a whole relax loop (loop_plan)
-  std::vector<int> h_ti, h_tv, h_cell_off, h_g;
-  std::vector<double> h_td;
-  std::vector<Ghost> h_ghosts;
-  // a whole relax loop (nrelax sweeps + the copies of the ghosts between them) as ONE list of
-  // nodes in dependency levels: sweep s + 1 of a cell starts as soon as what it reads is final
-  struct Loop {
+  SweepPlan h;              // what plan_loop reads for another nrelax (cells, lev_off and chunk are dropped once uploaded)
+  struct Loop {             // LoopPlan: nothing of it is needed on the host once it is uploaded
     unsigned nrelax = 0;
     int nnodes = 0, nlev = 0, nchunks = 0;
     int * ti = nullptr, * tv = nullptr, * node_off = nullptr, * node_g = nullptr, * chunk = nullptr;
     double * td = nullptr;
-    // the same plan for t_relax_nodes_pf: per chunk { c0, c1, i0, i1, d0, d1, v0, v1 }, per node { start in ti, td,
-    // tv, cell } -- one load each, issued a chunk ahead
     int * desc = nullptr, * rec = nullptr;
-    // host copies (gfship_tree_host_check)
-    std::vector<int> h_ti, h_tv, h_node_off, h_node_g, h_node_level;
-    std::vector<double> h_td;
-    double sg[6] = { 0., 0., 0., 0., 0., 0. };   // the homogeneous conditions compiled into the copies of the ghosts
-    FlowPlan * flow = nullptr;                   // the same loop for t_relax_flow (nullptr: not expressible)
+    double sg[6] = { 0., 0., 0., 0., 0., 0. };
+    FlowPlan * flow = nullptr;        // nullptr: not expressible, or not uploaded
   } loop;
   // the loops of the diffusion solves (10 nrelax sweeps on the first level, the conditions of U, V, W)
   Loop dloop[6];
@@ -114,29 +100,21 @@ struct DevReader {
   __device__ inline double operator() (const Topo & T, Cell c) const { return p[T.gi (c)]; }
 };
 
-struct Recorder {           // host: which cells does the stencil read?
-  std::vector<int> * out;
-  inline double operator() (const Topo & T, Cell c) const { out->push_back (T.gi (c)); return 1.; }
-};
-
 } // namespace
 
-struct gfship_tree {
+// the tree on the host (H, ncell, hflag, the tables, hleaves, side, has_boundary: TreePlan, whose lists of non-leaf
+// cells and of ghost leaves are dropped once uploaded) and what the device holds of it
+struct gfship_tree : TreePlan {
   int device = 0;
   gfship::Switches sw;                            // the GFSHIP_* environment switches, read by gfship_tree_create
   hipStream_t stream = nullptr;
-  Topo H, D;
-  std::vector<unsigned char> hflag;
+  Topo D;
   unsigned char * dflag = nullptr;
-  std::vector<int> h_nbtab, h_child0;
-  std::vector<unsigned char> h_cmask, h_idtab;
   int * d_nbtab = nullptr, * d_child0 = nullptr;
   unsigned char * d_cmask = nullptr, * d_idtab = nullptr;
-  int ncell = 0;
   double * var[V_NVAR] = {};
   int nleaves = 0;
   Cell * leaves = nullptr;                        // device: interior leaves in traversal order
-  std::vector<Cell> hleaves;
   int nnonleaf[GFSHIP_MAXLEVEL + 1] = {};
   Cell * nonleaf[GFSHIP_MAXLEVEL + 1] = {};       // device: interior non-leaf cells of a level
   Ghost * ghost_leaves = nullptr; int nghost_leaves = 0;
@@ -148,9 +126,7 @@ struct gfship_tree {
   double cfl = 0.8, dt = 0., t = 0., end = DBL_MAX, tnext = 0.;
   unsigned iter = 0;
   gfship_next_event_fn next_event = nullptr; void * next_event_ctx = nullptr;
-  int side[6] = { 0, 0, 0, 0, 0, 0 };             // GFSHIP_SIDE_PERIODIC / GFSHIP_SIDE_BOUNDARY
   int bc_p[6] = { 0, 0, 0, 0, 0, 0 };             // condition of P on a GfsBoundary side (GFSHIP_BC_*)
-  bool has_boundary = false;
   bool tape_attr_set = false;                     // dynamic-LDS limit of t_relax_tape raised on this device
   int ntracers = 0, tracer_gradient[TREE_MAXTRACERS] = { 1, 1 };   // GfsVariableTracer: 0 centred, 1 van Leer
   // conditions of U, V, W on GfsBoundary sides (GFSHIP_BC_SYMMETRY: the default GfsBc) with their values in
@@ -340,101 +316,12 @@ t_relax_loop (Topo T, const Cell * cells, const int * lev_off, int nlev, const G
   }
 }
 
-// ---- compiled stencils ------------------------------------------------------------------------
-// relax_cell / face_gradient (tree.hpp) walk the tree for every cell of every sweep: a chain of
-// dependent loads (neighbour table, flags, children, values) that one thread pays in full, and the
-// slowest cell of a dependency level -- a coarse leaf with fine neighbours reads ~40 values through
-// two levels of interpolation -- sets the time of the level.  The tree does not change: the host
-// walks it once per cell (stencil_tape, below) and writes down what the walk found: which values are
-// read, with which constant coefficients, combined in which order.  The sweep kernel stages the
-// streams of a chunk of cells in LDS together with the gathered values (one independent load per
-// thread), then evaluates them from LDS: same operations in the same order as the template code.
-enum { K_NONE = 0, K_SAME = 1, K_FC = 2, K_DEEP = 3, K_GHOST = 4 };
-
-struct TapeCursor {          // the streams of a cell, the values gathered beforehand (LDS / host)
-  const int * ti; const double * td; const double * tv;
-  __host__ __device__ inline double val () { return *tv++; }
-};
 struct TapeCursorG {         // the same with the values read through the stream of cells (global memory)
   const int * ti; const double * td; const int * tvi; const double * u;
   __device__ inline double val () { return u[*tvi++]; }
 };
 
-// p.b of interpolate_1D1 / interpolate_2D1 from the streams: sum of a_j * P_j, P_j a value or the
-// average of the children of a refined neighbour (average_neighbor_value)
-template <class CUR>
-__host__ __device__ inline double tape_interpolation (CUR & c)
-{
-  const int nt = *c.ti++;
-  double pb = 0.;
-  for (int t = 0; t < nt; t++) {
-    const double a = *c.td++;
-    const int cnt = *c.ti++;
-    double P;
-    if (cnt == 0)
-      P = c.val ();
-    else {
-      double av = 0., n = 0.;
-      for (int k = 0; k < cnt; k++) {
-	n += 1.;
-	av += 1.*(c.val ());
-      }
-      P = av/n;
-    }
-    pb += a*P;
-  }
-  return pb;
-}
-
-// the sums g.a, g.b of relax / residual_set over the faces of a cell (src/poisson.c:507-557,634-678)
-// w: the weight every face carries (1. for the Poisson problem with alpha = NULL; the diffusion
-// coefficient of a quadtree, face_gradient_w of tree.hpp) -- the products by 1. leave the bits alone
-template <class CUR>
-__host__ __device__ inline void tape_cell (CUR & c, int nd, int dim, int ncd, double & ga, double & gb,
-					   double w = 1.)
-{
-  ga = 0.; gb = 0.;
-  for (int d = 0; d < nd; d++) {
-    const int kind = *c.ti++;
-    if (kind == K_NONE)
-      continue;
-    double na, nb;
-    if (kind == K_SAME) {
-      na = w;
-      nb = w*(c.val ());
-    }
-    else if (kind == K_FC) {      /* gradient_fine_coarse towards a coarser neighbour */
-      const double cb = *c.td++;
-      const double uN = c.val ();
-      const double pb = tape_interpolation (c);
-      const double gc = 2.*pb/3.;
-      na = w*(2./3.);
-      nb = w*(cb*uN + gc);
-    }
-    else {                        /* the fine cells behind a face of a coarser leaf */
-      const int nch = *c.ti++;
-      na = 0.; nb = 0.;
-      for (int i = 0; i < nch; i++) {
-	const double gbi = *c.td++;
-	const double uch = c.val ();
-	const double pb = tape_interpolation (c);
-	const double gc = 2.*pb/3.;
-	na += w*gbi;
-	nb += w*((2./3.)*uch - gc);
-      }
-      if (dim > 2) {
-	na /= ncd/2.;
-	nb /= ncd/2.;
-      }
-    }
-    ga += na;
-    gb += nb;
-  }
-}
-
 #include "tree_flow.hpp"
-
-#define TAPE_LDS_BYTES (120*1024)
 
 // relax_loop (src/poisson.c:1070-1089) of one level from the compiled stencils: one workgroup; per
 // chunk of a dependency level: stage the streams and gather the values (all threads), barrier,
@@ -1227,595 +1114,57 @@ __global__ void t_mac_source (Topo T, const Cell * cells, int n, int c, const do
 
 inline int blocks (int n) { return (n + 255)/256; }
 
-// ---- host: tree construction and lists --------------------------------------------------------
-
-struct Builder {
-  int dim = 2;
-  std::vector<std::vector<unsigned char>> flag;     // per level, (n + 2)^dim
-  int r (int l) const { return (1 << l) + 2; }
-  size_t idx (int l, int i, int j, int k) const { return i + (size_t) r (l)*(j + (dim == 3 ? (size_t) r (l)*k : 0)); }
-  // cells of the dense levels allocated so far; the limit of gfship_tree_create (32-bit cell indices
-  // times the number of directions in the tables) is enforced BEFORE a level is allocated: a Refine
-  // function asking for level 10 in 3-D would otherwise allocate 1, 8.6, 68 GB on the host first
-  long long total = 0;
-  bool too_large = false;
-  static constexpr long long MAX_CELLS = 1ll << 27;
-  bool ensure (int l) {
-    if ((int) flag.size () <= l) flag.resize (l + 1);
-    if (flag[l].empty ()) {
-      const long long cells = (long long) r (l)*r (l)*(dim == 3 ? r (l) : 1);
-      if (total + cells > MAX_CELLS) { too_large = true; return false; }
-      total += cells;
-      flag[l].assign ((size_t) cells, NONE);
-    }
-    return true;
-  }
-  // oct_new with check_neighbors, src/ftt.c:45-83
-  int refine_single (int l, int i, int j, int k) {
-    if (l + 1 > GFSHIP_MAXLEVEL) return GFSHIP_EUNSUPPORTED;
-    static const int di[6] = { 1, -1, 0, 0, 0, 0 }, dj[6] = { 0, 0, 1, -1, 0, 0 }, dk[6] = { 0, 0, 0, 0, 1, -1 };
-    const int n = 1 << l;
-    for (int d = 0; d < 2*dim; d++) {
-      const int ni = i + di[d], nj = j + dj[d], nk = k + dk[d];
-      if (ni < 1 || nj < 1 || ni > n || nj > n || (dim == 3 && (nk < 1 || nk > n)))
-	continue;                   // the ghost trees are matched at the end (gfs_domain_match)
-      if (flag[l][idx (l, ni, nj, nk)] == NONE) {
-	const int pi = (ni + 1)/2, pj = (nj + 1)/2, pk = (nk + 1)/2;
-	if (flag[l - 1][idx (l - 1, pi, pj, pk)] == LEAF) {
-	  int e = refine_single (l - 1, pi, pj, pk);
-	  if (e) return e;
-	}
-      }
-    }
-    if (!ensure (l + 1)) return GFSHIP_EUNSUPPORTED;
-    flag[l][idx (l, i, j, k)] = NODE;
-    for (int c = 0; c < (1 << dim); c++)
-      flag[l + 1][idx (l + 1, 2*i - 1 + (c & 1), 2*j - ((c >> 1) & 1), 2*k - ((c >> 2) & 1))] = LEAF;
-    return 0;
-  }
-  // ftt_cell_refine (src/ftt.c:169-192) with refine_maxlevel (src/refine.c:35-38)
-  int refine_rec (int l, int i, int j, int k, gfship_refine_fn fn, void * ctx) {
-    if (flag[l][idx (l, i, j, k)] == LEAF) {
-      const double h = 1./(1 << l);
-      const double x = -0.5 + (i - 0.5)*h, y = -0.5 + (j - 0.5)*h, z = dim == 3 ? -0.5 + (k - 0.5)*h : 0.;
-      if (!(l < (* fn) (x, y, z, ctx)))
-	return 0;
-      int e = refine_single (l, i, j, k);
-      if (e) return e;
-    }
-    for (int c = 0; c < (1 << dim); c++) {
-      int e = refine_rec (l + 1, 2*i - 1 + (c & 1), 2*j - ((c >> 1) & 1), 2*k - ((c >> 2) & 1), fn, ctx);
-      if (e) return e;
-    }
-    return 0;
-  }
-};
-
-typedef std::function<void (Cell)> CellFn;
-enum { T_ALL, T_LEAFS, T_NON_LEAFS, T_LEVEL, T_LEVEL_LEAFS, T_LEVEL_NON_LEAFS };
-
-// ftt_cell_traverse, src/ftt.c:689-926 (pre-order; the post-order loops are done level by level)
-void traverse (const Topo & T, Cell c, int flags, int max_depth, const CellFn & fn)
-{
-  const bool leaf = T.leaf (c);
-  bool visit = false, descend = !leaf;
-  if (flags == T_ALL || flags == T_LEAFS || flags == T_NON_LEAFS) {
-    if (max_depth >= 0 && c.l > max_depth)
-      return;
-    visit = flags == T_ALL || (flags == T_LEAFS ? leaf : !leaf);
-  }
-  else if (flags == T_LEVEL) {
-    visit = c.l == max_depth;
-    descend = !visit && !leaf;
-  }
-  else if (flags == T_LEVEL_LEAFS) {
-    visit = c.l == max_depth || leaf;
-    descend = !visit;
-  }
-  else {
-    visit = c.l == max_depth && !leaf;
-    descend = !visit && !leaf;
-  }
-  if (visit)
-    fn (c);
-  if (descend)
-    for (int k = 0; k < T.nc (); k++) {
-      const Cell ch = T.child (c, k);
-      if (exists (ch))
-	traverse (T, ch, flags, max_depth, fn);
-    }
-}
-
-inline Cell root_cell (const Topo & T) { return T.make (0, 1, 1, 1); }
-
-// ftt_refine_corner, src/ftt.c:2013-2074
-bool refine_corner (const Topo & T, Cell cell)
-{
-  static const int perp2[4][2] = { {2, 3}, {2, 3}, {1, 0}, {1, 0} };
-  static const int perp3[6][4][2] =
-    {{{4,2},{4,3},{5,2},{5,3}}, {{4,2},{4,3},{5,2},{5,3}},
-     {{4,1},{4,0},{5,1},{5,0}}, {{4,1},{4,0},{5,1},{5,0}},
-     {{2,1},{2,0},{3,1},{3,0}}, {{2,1},{2,0},{3,1},{3,0}}};
-  for (int i = 0; i < T.nd (); i++) {
-    const Cell nb = T.neighbor (cell, i);
-    if (exists (nb) && !T.leaf (nb))
-      for (int j = 0; j < T.ncd (); j++) {
-	const Cell c = T.child_direction (nb, i ^ 1, j);
-	if (exists (c)) {
-	  if (T.dim == 2) {
-	    const Cell nc = T.neighbor (c, perp2[i][j]);
-	    if (exists (nc) && !T.leaf (nc))
-	      return true;
-	  }
-	  else
-	    for (int w = 0; w < 2; w++) {
-	      const Cell nc = T.neighbor (c, perp3[i][j][w]);
-	      if (exists (nc) && !T.leaf (nc))
-		return true;
-	    }
-	  if (!T.leaf (c))
-	    return true;
-	}
-      }
-  }
-  return false;
-}
-
-// traverse_face, src/ftt_internal.c:1-42 (leaves, max_depth = -1; the FTT_FLAG_TRAVERSED check
-// only matters for the second pass, whose neighbours are ghost cells)
-void traverse_face (const Topo & T, Cell cell, int d, std::vector<FaceRec> & out)
-{
-  FaceRec f = { cell, T.neighbor (cell, d), d };
-  if (!exists (f.neighbor))
-    return;
-  if (T.leaf (cell) && !T.leaf (f.neighbor)) {
-    const Cell coarse = cell, node = f.neighbor;
-    f.d = d ^ 1;
-    f.neighbor = coarse;
-    for (int i = 0; i < T.ncd (); i++) {
-      f.cell = T.child_direction (node, f.d, i);
-      if (exists (f.cell))
-	out.push_back (f);
-    }
-  }
-  else
-    out.push_back (f);
-}
-
-bool touches_side (const Topo & T, Cell c, int d)
-{
-  const int i = T.ci (c), j = T.cj (c), k = T.ck (c), n = T.n (c.l);
-  return (d == 0 && i == n) || (d == 1 && i == 1) || (d == 2 && j == n) || (d == 3 && j == 1) ||
-    (d == 4 && k == n) || (d == 5 && k == 1);
-}
-
-// ftt_face_traverse (src/ftt.c:2152-2215) as called by gfs_domain_face_traverse: kind 0 = FTT_XYZ,
-// 1 + c = component c
-void face_list (const Topo & T, const std::vector<Cell> & leaves, int kind, std::vector<FaceRec> & out)
-{
-  if (kind == 0) {
-    for (Cell c : leaves)
-      for (int d = 0; d < T.nd (); d += 2)
-	traverse_face (T, c, d, out);
-    for (int d = 1; d < T.nd (); d += 2)
-      for (Cell c : leaves)
-	if (touches_side (T, c, d))
-	  traverse_face (T, c, d, out);
-  }
-  else {
-    const int c0 = kind - 1;
-    for (Cell c : leaves)
-      traverse_face (T, c, 2*c0, out);
-    for (Cell c : leaves)
-      if (touches_side (T, c, 2*c0 + 1))
-	traverse_face (T, c, 2*c0 + 1, out);
-  }
-}
-
-// gfship_tree_host_check builds the host side of a tree (flags, tables, lists, dependency levels,
-// compiled stencils, loop plans) without a device: nothing is uploaded
-bool g_host_only = false;
+// ---- host: the plans of tree_plan.hpp onto the device -------------------------------------------
 
 template <class X> int to_device (const std::vector<X> & h, X ** d)
 {
-  *d = nullptr;
-  if (h.empty () || g_host_only) return 0;
+  *d = nullptr;       /* stays nullptr for an empty array: never dereferenced */
+  if (h.empty ()) return 0;
   GFSHIP_HIP (hipMalloc ((void **) d, h.size ()*sizeof (X)));
   GFSHIP_HIP (hipMemcpy (*d, h.data (), h.size ()*sizeof (X), hipMemcpyHostToDevice));
   return 0;
 }
 
-// the ghost cells of a selection of the traversal and their periodic images
-void ghost_list (const Topo & T, const int * sides, int flags, int max_depth, std::vector<Ghost> & out)
-{
-  for (int l = 0; l <= T.depth; l++) {
-    if (max_depth >= 0 && l > max_depth)
-      break;
-    const int n = T.n (l), r = T.r (l);
-    for (int side = 0; side < T.nd (); side++)
-      for (int tb = 1; tb <= (T.dim == 3 ? n : 1); tb++)
-	for (int ta = 1; ta <= n; ta++) {
-	  int g[3], im[3];
-	  const int a = side/2, o1 = a == 0 ? 1 : 0, o2 = a == 2 ? 1 : 2;
-	  g[a] = (side & 1) ? 0 : n + 1;
-	  im[a] = (side & 1) ? n : 1;
-	  if (sides[side] != GFSHIP_SIDE_PERIODIC)     /* GfsBoundary: the cell the ghost touches */
-	    im[a] = (side & 1) ? 1 : n;
-	  g[o1] = im[o1] = ta;
-	  g[o2] = im[o2] = T.dim == 3 ? tb : 0;
-	  const int G = g[0] + r*(g[1] + r*g[2]), I = im[0] + r*(im[1] + r*im[2]);
-	  const unsigned char f = T.flag[T.off[l] + G];
-	  if (f == NONE)
-	    continue;
-	  const bool take = flags == T_LEAFS ? f == LEAF : (l == max_depth || f == LEAF);
-	  if (take) {
-	    Ghost gh = { T.off[l] + G, T.off[l] + I, side, l };
-	    out.push_back (gh);
-	  }
-	}
-  }
-}
+template <class X> void release (std::vector<X> & v) { std::vector<X> ().swap (v); }
 
-int stencil_tape (gfship_tree * tr, int m, Sweep * S, const std::vector<Cell> & sorted,
-		  const std::vector<int> & lev_off);
-Sgn6 homogeneous_signs (const gfship_tree * tr);
-
-// dependency levels of an exact-order sweep over `order': a cell runs after every earlier cell
-// it reads (it must see the new value) and after every earlier cell that reads it (which must
-// still see the old one)
-int sweep_plan (gfship_tree * tr, int m, Sweep * S)
+// the plan S->h; keeps of it what plan_loop reads
+int upload (Sweep * S)
 {
-  const Topo & T = tr->H;
-  std::vector<Cell> order;
-  traverse (T, root_cell (T), T_LEVEL_LEAFS, m, [&] (Cell c) { order.push_back (c); });
-  std::vector<int> pos (tr->ncell, -1);
-  for (size_t k = 0; k < order.size (); k++)
-    pos[T.gi (order[k])] = (int) k;
-  std::vector<int> lev (order.size (), 0), minlev (order.size (), 0), reads;
-  Recorder R = { &reads };
-  int nlev = 0;
-  for (size_t k = 0; k < order.size (); k++) {
-    reads.clear ();
-    relax_cell (T, order[k], R, 0., 1., m);
-    int L = minlev[k];
-    for (int g : reads) {
-      const int p = pos[g];
-      if (p >= 0 && p < (int) k)
-	L = std::max (L, lev[p] + 1);
-    }
-    lev[k] = L;
-    for (int g : reads) {
-      const int p = pos[g];
-      if (p > (int) k)
-	minlev[p] = std::max (minlev[p], L + 1);
-    }
-    nlev = std::max (nlev, L + 1);
-  }
-  if (tr->sw.tree_debug) {
-    // what pipelining the nrelax sweeps of a loop would give: the sequential program [copies of the
-    // ghosts][sweep 0][copies][sweep 1]... scheduled into levels that keep its RAW / WAR / WAW order
-    const int nrelax = 4;
-    std::vector<Ghost> gh0;
-    ghost_list (T, tr->side, T_LEVEL_LEAFS, m, gh0);
-    std::vector<int> wlev (tr->ncell, 0), rlev (tr->ncell, 0);
-    int tot = 0;
-    std::vector<std::vector<int>> rd (order.size ());
-    for (size_t k = 0; k < order.size (); k++) {
-      reads.clear ();
-      relax_cell (T, order[k], R, 0., 1., m);
-      rd[k] = reads;
-    }
-    for (int sw = 0; sw < nrelax; sw++) {
-      for (const Ghost & G : gh0) {
-	int L = std::max (wlev[G.img], std::max (rlev[G.g], wlev[G.g])) + 1;
-	rlev[G.img] = std::max (rlev[G.img], L);
-	wlev[G.g] = L; rlev[G.g] = 0;
-	tot = std::max (tot, L);
-      }
-      for (size_t k = 0; k < order.size (); k++) {
-	const int w = T.gi (order[k]);
-	int L = std::max (rlev[w], wlev[w]);
-	for (int g : rd[k]) L = std::max (L, wlev[g]);
-	L++;
-	for (int g : rd[k]) rlev[g] = std::max (rlev[g], L);
-	wlev[w] = L; rlev[w] = 0;
-	tot = std::max (tot, L);
-      }
-    }
-    fprintf (stderr, "gfship_tree: sweep of level %d: %zu cells, %d dependency levels per sweep, %d x %d = %d sequential, %d pipelined\n",
-	     m, order.size (), nlev, nrelax, nlev, nrelax*nlev, tot);
-  }
-  std::vector<int> off (nlev + 1, 0);
-  for (size_t k = 0; k < order.size (); k++)
-    off[lev[k] + 1]++;
-  for (int L = 0; L < nlev; L++)
-    off[L + 1] += off[L];
-  std::vector<Cell> sorted (order.size ());
-  std::vector<int> cur (off.begin (), off.end () - 1);
-  for (size_t k = 0; k < order.size (); k++)
-    sorted[cur[lev[k]]++] = order[k];
-  std::vector<Ghost> gh;
-  ghost_list (T, tr->side, T_LEVEL_LEAFS, m, gh);
-  S->ncells = (int) order.size ();
-  S->nlev = nlev;
-  S->nghosts = (int) gh.size ();
-  S->h_ghosts = gh;
+  const SweepPlan & h = S->h;
+  S->ncells = (int) h.cells.size ();
+  S->nlev = h.nlev;
+  S->nghosts = (int) h.ghosts.size ();
+  S->nchunks = (int) h.chunk.size () - 1;
   int e;
-  if ((e = to_device (sorted, &S->cells)) || (e = to_device (off, &S->lev_off)) ||
-      (e = to_device (gh, &S->ghosts)))
+  if ((e = to_device (h.cells, &S->cells)) || (e = to_device (h.lev_off, &S->lev_off)) ||
+      (e = to_device (h.ghosts, &S->ghosts)) ||
+      (e = to_device (h.ti, &S->ti)) || (e = to_device (h.td, &S->td)) || (e = to_device (h.tv, &S->tv)) ||
+      (e = to_device (h.cell_off, &S->cell_off)) || (e = to_device (h.chunk, &S->chunk)))
     return e;
-  return stencil_tape (tr, m, S, sorted, off);
-}
-
-// ---- compiled stencils: the host side ---------------------------------------------------------
-
-struct TapeOut { std::vector<int> ti, tv; std::vector<double> td; };
-
-// interpolate_1D1 / interpolate_2D1 in the coarse cell A towards the fine cell (face: fine -> A in
-// direction dface), src/fluid.c:178-245: the terms of p.b go to the streams, p.a is returned
-double tape_interpolation_gen (const Topo & T, Cell fine, Cell A, int dface, TapeOut & o)
-{
-  const int id = T.id (fine);
-  int dirs[2], ndirs;
-  if (T.dim == 2) { dirs[0] = perpendicular (dface, id); ndirs = 1; }
-  else { dirs[0] = perpendicular3 (dface, id, 0); dirs[1] = perpendicular3 (dface, id, 1); ndirs = 2; }
-  double pa = 1.;
-  const size_t nt_at = o.ti.size ();
-  o.ti.push_back (0);
-  int nt = 0;
-  for (int w = 0; w < ndirs; w++) {
-    const Cell nb = T.neighbor (A, dirs[w]);
-    if (!exists (nb))
-      continue;
-    double x2 = 1.;
-    std::vector<int> idx;
-    int cnt = 0;
-    if (T.leaf (nb))
-      idx.push_back (T.gi (nb));
-    else {
-      for (int i = 0; i < T.ncd (); i++) {
-	const Cell ch = T.child_direction (nb, dirs[w] ^ 1, i);
-	if (exists (ch)) { idx.push_back (T.gi (ch)); cnt++; }
-      }
-      if (cnt > 0)
-	x2 = 3./4.;
-      else
-	idx.push_back (T.gi (A));       /* average_neighbor_value falls back on the cell of the face */
-    }
-    const double a = (1./4.)/x2;
-    o.td.push_back (a);
-    o.ti.push_back (cnt);
-    for (int g : idx) o.tv.push_back (g);
-    pa -= a;
-    nt++;
-  }
-  o.ti[nt_at] = nt;
-  return pa;
-}
-
-// ---- the diffusion coefficients of a tree ----------------------------------------------------
-// gfs_diffusion_coefficients with a constant D (src/poisson.c:1280-1303,826-853,1350-1390): diffusion_coef
-// over the faces of the leaves -- f[d].v = w on the cell of a face, = w on the neighbour of the same level,
-// += w/(FTT_CELLS/2) on a coarser neighbour -- then face_coeff_from_below on the non-leaf cells, children
-// first: (c0 + c1 + c2 + c3)/4, and 0 on every face of a cell with exactly one non-zero face towards an interior
-// neighbour.  In 2-D all of this is exactly w; in 3-D (w/4 + w/4) + w/4 and the sums of four children may
-// round on the way.  Written once for two arithmetics: A::V = double (the coefficients of one w, as the reference
-// computes them: the host check) or the form of the expression in w (WArithForm, below).
-template <class A>
-void diffusion_coefficients_gen (const Topo & T, A & ar, std::vector<typename A::V> & f)
-{
-  const int nd = T.nd ();
-  int ncell = 0;
-  for (int l = 0; l <= T.depth; l++) ncell += T.lsize (l);
-  f.assign ((size_t) ncell*nd, ar.zero ());
-  auto at = [&] (Cell c, int d) -> typename A::V & { return f[(size_t) T.gi (c)*nd + d]; };
-  // diffusion_coef, ftt_face_traverse of the leaves: a coarse leaf sees the faces of its fine neighbours
-  // from the fine side (each face once)
-  for (int l = 0; l <= T.depth; l++)
-    for (int q = 0; q < T.lsize (l); q++) {
-      const Cell c = { l, q };
-      if (T.flag[T.gi (c)] != LEAF || !T.interior (c)) continue;
-      for (int d = 0; d < nd; d++) {
-	const Cell nb = T.neighbor (c, d);
-	if (!exists (nb)) continue;
-	if (nb.l < c.l) {
-	  at (c, d) = ar.leaf ();
-	  at (nb, d ^ 1) = ar.addq (at (nb, d ^ 1));
-	}
-	else if (T.leaf (nb)) {
-	  at (c, d) = ar.leaf ();
-	  at (nb, d ^ 1) = ar.leaf ();
-	}
-	else if (!T.interior (nb))      /* a refined ghost cell: its children are not leaves of the traversal */
-	  for (int i = 0; i < T.ncd (); i++) {
-	    const Cell ch = T.child_direction (nb, d ^ 1, i);
-	    if (!exists (ch)) continue;
-	    at (ch, d ^ 1) = ar.leaf ();
-	    at (c, d) = ar.addq (at (c, d));
-	  }
-      }
-    }
-  // face_coeff_from_below, the interior non-leaf cells from the deepest level up
-  for (int l = T.depth; l >= 0; l--)
-    for (int q = 0; q < T.lsize (l); q++) {
-      const Cell c = { l, q };
-      if (T.flag[T.gi (c)] != NODE || !T.interior (c)) continue;
-      unsigned neighbors = 0;
-      for (int d = 0; d < nd; d++) {
-	typename A::V ch[4];
-	int n = 0;
-	for (int i = 0; i < T.ncd (); i++) {
-	  const Cell cc = T.child_direction (c, d, i);
-	  ch[i] = exists (cc) ? at (cc, d) : ar.zero ();
-	  n += exists (cc);
-	}
-	at (c, d) = ar.below (ch, T.ncd (), n);
-	const Cell nb = T.neighbor (c, d);
-	if (ar.nonzero (at (c, d)) && exists (nb) && T.interior (nb))
-	  neighbors++;
-      }
-      if (neighbors == 1)
-	for (int d = 0; d < nd; d++) at (c, d) = ar.zero ();
-    }
-}
-
-struct WArithDouble {       // the reference's arithmetic for one w
-  typedef double V;
-  double w, q;
-  V zero () const { return 0.; }
-  V leaf () const { return w; }
-  V addq (V a) const { return a + q; }
-  V below (const V * c, int nc, int n) const
-  {
-    (void) n;
-    double f = 0.;
-    for (int i = 0; i < nc; i++) f += c[i];
-    return f/nc;
-  }
-  bool nonzero (V a) const { return a != 0.; }
-};
-
-// The form of a coefficient as an expression in w: EXACT (= w for every w > 0), ZERO, a sum of k quarters (k < 0
-// stores -k), or anything else (OTHER).  Four equal addends summed from 0 give four times the addend exactly in
-// binary floating point: 2x is exact, fl (3x) is off by at most half an ulp of 4x, and when it is off by exactly that
-// (a tie, 3M = 2 mod 4 for the mantissa M of x) M is even and fl (fl (3x) + x) rounds back to 4x.  So the coarse side
-// of a fine-coarse face, 0 + w/4 + w/4 + w/4 + w/4 (3-D) or 0 + w/2 + w/2 (2-D), is w, and so is
-// face_coeff_from_below of children that are all w -- whatever w is, although (w + w) + w itself may round.
-struct WArithForm {
-  typedef int V;
-  enum { ZERO = 0, EXACT = 1, OTHER = 2 };
-  int ncd;                          /* FTT_CELLS/2 */
-  V zero () const { return ZERO; }
-  V leaf () const { return EXACT; }
-  V addq (V a) const
-  {
-    const int k = a == ZERO ? 1 : a < 0 ? - a + 1 : 0;      /* quarters so far + 1, or 0: not a sum of quarters */
-    if (k == 0) return OTHER;
-    return k == ncd ? EXACT : - k;
-  }
-  V below (const V * c, int nc, int n) const
-  {
-    bool all = n == nc && (nc == 2 || nc == 4);
-    for (int i = 0; i < nc; i++) all = all && c[i] == EXACT;
-    if (all) return EXACT;
-    for (int i = 0; i < nc; i++) if (c[i] != ZERO) return OTHER;
-    return ZERO;
-  }
-  bool nonzero (V a) const { return a != ZERO; }
-};
-
-// the device runs the diffusion stencils of a tree with the same weight w on every face (WConst): true when every
-// coefficient that diffusion_relax / _residual / _rhs read on this tree, on any level of the multigrid cycle, is w
-// for every w (a coefficient of another form would make the device differ from the reference: refused)
-bool diffusion_weights_exact (const Topo & T)
-{
-  WArithForm ar = { T.ncd () };
-  std::vector<int> form;
-  diffusion_coefficients_gen (T, ar, form);
-  struct ZeroReader { double operator() (const Topo &, Cell) const { return 0.; } };
-  struct WRecord {          // which f[d].v does the stencil read?
-    std::vector<size_t> * out;
-    double operator() (const Topo & T, Cell c, int d) const { out->push_back ((size_t) T.gi (c)*T.nd () + d); return 1.; }
-  };
-  std::vector<size_t> read;
-  ZeroReader zr;
-  WRecord wr = { &read };
-  for (int l = 0; l <= T.depth; l++)
-    for (int q = 0; q < T.lsize (l); q++) {
-      const Cell c = { l, q };
-      if (T.flag[T.gi (c)] == NONE || !T.interior (c)) continue;
-      read.clear ();
-      (void) diffusion_relax_cell (T, c, zr, 0., wr, l);           /* a cell of the sweep of its own level */
-      if (T.leaf (c))
-	(void) diffusion_residual_cell (T, c, zr, 0., wr);         /* a leaf on the finer levels, residual, rhs */
-      for (size_t k : read)
-	if (form[k] != WArithForm::EXACT) return false;
-    }
-  return true;
-}
-
-// one cell of the sweep of level max_level: what face_gradient (tree.hpp) does for each direction
-void tape_cell_gen (const Topo & T, Cell cell, int max_level, TapeOut & o)
-{
-  o.tv.push_back (T.gi (cell));          /* the value of the cell itself */
-  for (int d = 0; d < T.nd (); d++) {
-    const Cell nb = T.neighbor (cell, d);
-    if (!exists (nb)) { o.ti.push_back (K_NONE); continue; }
-    if (nb.l < cell.l) {
-      o.ti.push_back (K_FC);
-      const size_t cb_at = o.td.size ();
-      o.td.push_back (0.);
-      o.tv.push_back (T.gi (nb));
-      const double pa = tape_interpolation_gen (T, cell, nb, d, o);
-      o.td[cb_at] = 2.*pa/3.;
-    }
-    else if (cell.l == max_level || T.leaf (nb)) {
-      o.ti.push_back (K_SAME);
-      o.tv.push_back (T.gi (nb));
-    }
-    else {
-      o.ti.push_back (K_DEEP);
-      const size_t n_at = o.ti.size ();
-      o.ti.push_back (0);
-      int nch = 0;
-      for (int i = 0; i < T.ncd (); i++) {
-	const Cell ch = T.child_direction (nb, d ^ 1, i);
-	if (!exists (ch))
-	  continue;
-	const size_t gb_at = o.td.size ();
-	o.td.push_back (0.);
-	o.tv.push_back (T.gi (ch));
-	const double pa = tape_interpolation_gen (T, ch, cell, d ^ 1, o);
-	o.td[gb_at] = 2.*pa/3.;
-	nch++;
-      }
-      o.ti[n_at] = nch;
-    }
-  }
-}
-
-int stencil_tape (gfship_tree * tr, int m, Sweep * S, const std::vector<Cell> & sorted,
-		  const std::vector<int> & lev_off)
-{
-  const Topo & T = tr->H;
-  TapeOut o;
-  std::vector<int> cell_off;
-  for (size_t c = 0; c < sorted.size (); c++) {
-    cell_off.push_back ((int) o.ti.size ()); cell_off.push_back ((int) o.td.size ()); cell_off.push_back ((int) o.tv.size ());
-    tape_cell_gen (T, sorted[c], m, o);
-  }
-  cell_off.push_back ((int) o.ti.size ()); cell_off.push_back ((int) o.td.size ()); cell_off.push_back ((int) o.tv.size ());
-  // chunks: consecutive cells of one dependency level whose streams fit the LDS
-  std::vector<int> chunk;
-  for (size_t L = 0; L + 1 < lev_off.size (); L++) {
-    int c = lev_off[L];
-    while (c < lev_off[L + 1]) {
-      chunk.push_back (c);
-      int e = c;
-      while (e < lev_off[L + 1]) {
-	const size_t bytes = 8*(size_t) (cell_off[3*(e + 1) + 2] - cell_off[3*c + 2]) +
-	  8*(size_t) (cell_off[3*(e + 1) + 1] - cell_off[3*c + 1]) + 4*(size_t) (cell_off[3*(e + 1)] - cell_off[3*c]) + 8;
-	if (bytes > TAPE_LDS_BYTES)
-	  break;
-	e++;
-      }
-      if (e == c) return GFSHIP_EUNSUPPORTED;      /* one cell larger than the LDS: cannot happen */
-      c = e;
-    }
-  }
-  S->nchunks = (int) chunk.size ();
-  chunk.push_back ((int) sorted.size ());
-  int e;
-  if ((e = to_device (o.ti, &S->ti)) || (e = to_device (o.td, &S->td)) || (e = to_device (o.tv, &S->tv)) ||
-      (e = to_device (cell_off, &S->cell_off)) || (e = to_device (chunk, &S->chunk)))
-    return e;
-  if (o.td.empty ())      /* to_device leaves nullptr for an empty stream: never dereferenced */
-    S->td = nullptr;
   S->taped = true;
-  S->h_ti = o.ti; S->h_tv = o.tv; S->h_td = o.td; S->h_cell_off = cell_off;
-  S->h_g.resize (sorted.size ());
-  for (size_t c = 0; c < sorted.size (); c++) S->h_g[c] = T.gi (sorted[c]);
+  release (S->h.cells); release (S->h.lev_off); release (S->h.chunk);
   return 0;
+}
+
+void flow_free (FlowPlan & F)
+{
+  (void) hipFree (F.rec); (void) hipFree (F.lev_off); (void) hipFree (F.ct);
+  (void) hipFree (F.gidx); (void) hipFree (F.up); (void) hipFree (F.rp);
+  F = FlowPlan ();
+}
+
+// false: no memory for it (the caller keeps the tape kernels)
+bool upload (const FlowProgram & h, FlowPlan * F)
+{
+  F->nlev = h.nlev; F->nct = h.nct; F->npos = h.npos; F->width = h.width;
+  if (to_device (h.rec, &F->rec) || to_device (h.lev_off, &F->lev_off) || to_device (h.ct, &F->ct) ||
+      to_device (h.gidx, &F->gidx) ||
+      hipMalloc ((void **) &F->up, h.gidx.size ()*sizeof (double)) != hipSuccess ||
+      hipMalloc ((void **) &F->rp, h.gidx.size ()*sizeof (double)) != hipSuccess) {
+    flow_free (*F);
+    return false;
+  }
+  return true;
 }
 
 void loop_free (Sweep::Loop & P)
@@ -1827,181 +1176,57 @@ void loop_free (Sweep::Loop & P)
   P = Sweep::Loop ();
 }
 
-// The relax loop of level m as one program: [copies of the ghosts][sweep 0 in tree order][copies]
-// [sweep 1] ... [sweep nrelax - 1], scheduled into levels that keep the order of every read after the
-// write it must see, and of every write after the reads of the value it replaces (RAW, WAR, WAW of
-// the sequential program): the results are those of the sequential program, and sweep s + 1 follows
-// sweep s a few levels behind instead of waiting for its end
+int upload (const LoopPlan & h, Sweep::Loop * P)
+{
+  for (int d = 0; d < 6; d++) P->sg[d] = h.sg[d];
+  P->nchunks = h.nchunks ();
+  P->nnodes = h.nnodes ();
+  P->nlev = h.nlev;
+  int e;
+  if ((e = to_device (h.ti, &P->ti)) || (e = to_device (h.td, &P->td)) || (e = to_device (h.tv, &P->tv)) ||
+      (e = to_device (h.node_off, &P->node_off)) || (e = to_device (h.node_g, &P->node_g)) ||
+      (e = to_device (h.chunk, &P->chunk)) || (e = to_device (h.desc, &P->desc)) || (e = to_device (h.rec, &P->rec)))
+    return e;
+  P->nrelax = h.nrelax;
+  if (h.flow) {
+    P->flow = new FlowPlan;
+    if (!upload (*h.flow, P->flow)) {
+      delete P->flow;
+      P->flow = nullptr;
+    }
+  }
+  return 0;
+}
+
+int upload (const FacePlan & h, FaceSet * F)
+{
+  F->nfaces = (int) h.faces.size ();
+  int e;
+  if ((e = to_device (h.faces, &F->faces)) || (e = to_device (h.inc_off, &F->inc_off)) ||
+      (e = to_device (h.inc, &F->inc)))
+    return e;
+  GFSHIP_HIP (hipMalloc ((void **) &F->fval, std::max<size_t> (1, h.faces.size ())*sizeof (double)));
+  return 0;
+}
+
+Sgn6 homogeneous_signs (const gfship_tree * tr) { return tree::homogeneous_signs (tr->side, tr->bc_p); }
+
+// the relax loop of nrelax sweeps of level m with the conditions `signs' (those of P by default), planned and
+// uploaded into `out' (S->loop by default)
 int loop_plan (gfship_tree * tr, int m, unsigned nrelax, Sweep * S, Sweep::Loop * out = nullptr,
 	       const Sgn6 * signs = nullptr)
 {
   Sweep::Loop & P = out ? *out : S->loop;
   loop_free (P);
-  const Sgn6 sg = signs ? *signs : homogeneous_signs (tr);
-  const size_t nc = S->h_g.size ();
-  // the cells were sorted by single-sweep dependency level; the sequential order inside a sweep is
-  // the tree order: recover it from the positions the sweep plan kept (sorted is stable per level,
-  // and any order consistent with the single-sweep levels is a valid sequential order)
-  struct Node { int kind, idx, sweep, level; };   /* kind 0: cell idx of the sweep, 1: ghost idx */
-  std::vector<Node> nodes;
-  nodes.reserve (nrelax*(nc + S->h_ghosts.size ()));
-  std::vector<int> wlev (tr->ncell, 0), rlev (tr->ncell, 0);
-  int nlev = 0;
-  for (unsigned sw = 0; sw < nrelax; sw++) {
-    for (size_t q = 0; q < S->h_ghosts.size (); q++) {
-      const Ghost & G = S->h_ghosts[q];
-      const int L = std::max (wlev[G.img], std::max (rlev[G.g], wlev[G.g])) + 1;
-      rlev[G.img] = std::max (rlev[G.img], L);
-      wlev[G.g] = L; rlev[G.g] = 0;
-      nodes.push_back ({ 1, (int) q, (int) sw, L });
-      nlev = std::max (nlev, L);
-    }
-    for (size_t c = 0; c < nc; c++) {
-      const int w = S->h_g[c];
-      int L = std::max (rlev[w], wlev[w]);
-      for (int k = S->h_cell_off[3*c + 2]; k < S->h_cell_off[3*(c + 1) + 2]; k++)
-	L = std::max (L, wlev[S->h_tv[k]]);
-      L++;
-      for (int k = S->h_cell_off[3*c + 2]; k < S->h_cell_off[3*(c + 1) + 2]; k++)
-	rlev[S->h_tv[k]] = std::max (rlev[S->h_tv[k]], L);
-      wlev[w] = L; rlev[w] = 0;
-      nodes.push_back ({ 0, (int) c, (int) sw, L });
-      nlev = std::max (nlev, L);
-    }
-  }
-  std::stable_sort (nodes.begin (), nodes.end (), [] (const Node & a, const Node & b) { return a.level < b.level; });
-  std::vector<int> ti, tv, node_off, node_g, chunk;
-  std::vector<double> td;
-  for (const Node & N : nodes) {
-    node_off.push_back ((int) ti.size ()); node_off.push_back ((int) td.size ()); node_off.push_back ((int) tv.size ());
-    if (N.kind == 1) {
-      const Ghost & G = S->h_ghosts[N.idx];
-      ti.push_back (K_GHOST);
-      td.push_back (sg.s[G.side]);
-      tv.push_back (G.img);
-      node_g.push_back (G.g);
-    }
-    else {
-      const int c = N.idx;
-      ti.insert (ti.end (), S->h_ti.begin () + S->h_cell_off[3*c], S->h_ti.begin () + S->h_cell_off[3*(c + 1)]);
-      td.insert (td.end (), S->h_td.begin () + S->h_cell_off[3*c + 1], S->h_td.begin () + S->h_cell_off[3*(c + 1) + 1]);
-      tv.insert (tv.end (), S->h_tv.begin () + S->h_cell_off[3*c + 2], S->h_tv.begin () + S->h_cell_off[3*(c + 1) + 2]);
-      node_g.push_back (S->h_g[c]);
-    }
-  }
-  node_off.push_back ((int) ti.size ()); node_off.push_back ((int) td.size ()); node_off.push_back ((int) tv.size ());
-  // chunks: consecutive nodes of one level whose streams fit the LDS
-  size_t c = 0;
-  while (c < nodes.size ()) {
-    chunk.push_back ((int) c);
-    size_t e = c;
-    while (e < nodes.size () && nodes[e].level == nodes[c].level) {
-      const size_t bytes = 8*(size_t) (node_off[3*(e + 1) + 2] - node_off[3*c + 2]) +
-	8*(size_t) (node_off[3*(e + 1) + 1] - node_off[3*c + 1]) + 4*(size_t) (node_off[3*(e + 1)] - node_off[3*c]) + 8;
-      if (bytes > TAPE_LDS_BYTES)
-	break;
-      e++;
-    }
-    if (e == c) return GFSHIP_EUNSUPPORTED;
-    c = e;
-  }
-  for (int d = 0; d < 6; d++) P.sg[d] = sg.s[d];
-  P.nchunks = (int) chunk.size ();
-  chunk.push_back ((int) nodes.size ());
-  P.nnodes = (int) nodes.size ();
-  P.nlev = nlev;
-  int e;
-  if ((e = to_device (ti, &P.ti)) || (e = to_device (td, &P.td)) || (e = to_device (tv, &P.tv)) ||
-      (e = to_device (node_off, &P.node_off)) || (e = to_device (node_g, &P.node_g)) ||
-      (e = to_device (chunk, &P.chunk)))
-    return e;
-  {
-    std::vector<int> desc, rec;
-    for (int k = 0; k < P.nchunks; k++) {
-      const int c0 = chunk[k], c1 = chunk[k + 1];
-      const int v[8] = { c0, c1, node_off[3*c0], node_off[3*c1], node_off[3*c0 + 1], node_off[3*c1 + 1],
-			 node_off[3*c0 + 2], node_off[3*c1 + 2] };
-      desc.insert (desc.end (), v, v + 8);
-    }
-    for (int q = 0; q < 8; q++) desc.push_back (0);          /* the descriptor read past the last chunk */
-    for (size_t c = 0; c < nodes.size (); c++) {
-      rec.push_back (node_off[3*c]); rec.push_back (node_off[3*c + 1]); rec.push_back (node_off[3*c + 2]);
-      rec.push_back (node_g[c]);
-    }
-    for (int q = 0; q < 4; q++) rec.push_back (0);
-    if ((e = to_device (desc, &P.desc)) || (e = to_device (rec, &P.rec)))
-      return e;
-  }
-  P.nrelax = nrelax;
-  if (g_host_only) {
-    P.h_ti = ti; P.h_tv = tv; P.h_td = td; P.h_node_off = node_off; P.h_node_g = node_g;
-    for (const Node & N : nodes) P.h_node_level.push_back (N.level);
-  }
-  {
-    // the same loop as a flow plan (tree_flow.hpp)
-    std::vector<int> level_of (tr->ncell, 0);
-    for (int l = 0; l <= tr->H.depth; l++)
-      for (int g = tr->H.off[l]; g < tr->H.off[l + 1]; g++) level_of[g] = l;
-    P.flow = new FlowPlan;
-    const int flow_width = std::min (FLOW_WIDTH, tr->sw.flow_width);      /* lab: operations per level (a multiple of 64 up to 512) */
-    /* a level costs about the same whatever its width: the widest plan wins on octrees; the levels of a quadtree
-       are narrow, 256 operations per level are as few levels and fewer idle wavefronts (measured: 11.5 against
-       12.5 ms per step on the quadtree bench) */
-    const int width = flow_width ? flow_width : tr->H.dim == 2 ? 256 : FLOW_WIDTH;
-    if (!flow_plan (tr->ncell, tr->H.dim, S, nrelax, sg, level_of.data (), tr->H.dim == 2, P.flow, g_host_only, tr->sw.tree_debug, width)) {
-      flow_free (*P.flow);
-      delete P.flow;
-      P.flow = nullptr;
-    }
-  }
-  if (tr->sw.tree_debug)
-    fprintf (stderr, "gfship_tree: relax loop of level %d: %u sweeps, %d nodes in %d levels, %d chunks; flow plan: %d operations in %d levels, %d constants\n",
-	     m, nrelax, P.nnodes, P.nlev, P.nchunks, P.flow ? P.flow->nops : -1, P.flow ? P.flow->nlev : -1,
-	     P.flow ? P.flow->nct : -1);
-  return 0;
-}
-
-int face_set (gfship_tree * tr, int kind, FaceSet * F)
-{
-  const Topo & T = tr->H;
-  std::vector<FaceRec> faces;
-  face_list (T, tr->hleaves, kind, faces);
-  std::vector<int> leafpos (tr->ncell, -1);
-  for (size_t k = 0; k < tr->hleaves.size (); k++)
-    leafpos[T.gi (tr->hleaves[k])] = (int) k;
-  std::vector<std::vector<int>> inc (tr->hleaves.size ());
-  for (size_t k = 0; k < faces.size (); k++) {
-    const int a = leafpos[T.gi (faces[k].cell)], b = leafpos[T.gi (faces[k].neighbor)];
-    if (a >= 0) inc[a].push_back ((int) (k << 1));
-    if (b >= 0) inc[b].push_back ((int) (k << 1 | 1));
-  }
-  std::vector<int> off (inc.size () + 1, 0), flat;
-  for (size_t k = 0; k < inc.size (); k++) {
-    off[k + 1] = off[k] + (int) inc[k].size ();
-    flat.insert (flat.end (), inc[k].begin (), inc[k].end ());
-  }
-  F->nfaces = (int) faces.size ();
-  int e;
-  if ((e = to_device (faces, &F->faces)) || (e = to_device (off, &F->inc_off)) ||
-      (e = to_device (flat, &F->inc)))
-    return e;
-  if (!g_host_only)
-    GFSHIP_HIP (hipMalloc ((void **) &F->fval, std::max<size_t> (1, faces.size ())*sizeof (double)));
-  return 0;
+  LoopPlan h;
+  int e = plan_loop (*tr, S->h, m, nrelax, signs ? *signs : homogeneous_signs (tr), tr->sw.flow_width,
+		     tr->sw.tree_debug, h);
+  return e ? e : upload (h, &P);
 }
 
 #define KCHECK() GFSHIP_HIP (hipGetLastError ())
 
 // ---- host: the algorithms ----------------------------------------------------------------------
-
-// the homogeneous form of the conditions (gfs_domain_homogeneous_bc): ghost = s * cell
-Sgn6 homogeneous_signs (const gfship_tree * tr)
-{
-  Sgn6 sg;
-  for (int d = 0; d < 6; d++)
-    sg.s[d] = tr->side[d] != GFSHIP_SIDE_PERIODIC && tr->bc_p[d] == GFSHIP_BC_DIRICHLET ? -1. : 1.;
-  return sg;
-}
 
 // gfs_domain_bc of P on the leaves of a tree with GfsBoundary sides
 int bc_solution (gfship_tree * tr, double * v)
@@ -2054,18 +1279,7 @@ int bc_velocity (gfship_tree * tr, int c)
 
 // the homogeneous conditions of velocity component c (gfs_domain_homogeneous_bc in the relax loops of its
 // diffusion solve): ghost = s * cell
-Sgn6 homogeneous_signs_u (const gfship_tree * tr, int c)
-{
-  Sgn6 sg;
-  for (int d = 0; d < 6; d++) {
-    sg.s[d] = 1.;
-    if (tr->side[d] != GFSHIP_SIDE_PERIODIC) {
-      const int k = tr->bc_u[c][d];
-      sg.s[d] = k == GFSHIP_BC_DIRICHLET ? -1. : k == GFSHIP_BC_NEUMANN ? 1. : (c == d/2 ? -1. : 1.);
-    }
-  }
-  return sg;
-}
+Sgn6 homogeneous_signs_u (const gfship_tree * tr, int c) { return tree::homogeneous_signs_u (tr->side, tr->bc_u[c], c); }
 
 // post-order traversal of the non-leaf cells: deepest level first
 // the same for several variables in one launch per level (gfs_cell_coarse_init restricts five to seven variables:
@@ -2883,213 +2097,77 @@ int gfship_tree_create (gfship_tree ** out, int dim, gfship_refine_fn refine, vo
   return gfship_tree_create_sides (out, dim, refine, ctx, nullptr, device);
 }
 
-static int tree_create_sides (gfship_tree ** out, int dim, gfship_refine_fn refine, void * ctx,
-			      const int * side, int device);
-
-// no exception crosses the C ABI: a tree too large for the host comes back as an error
-int gfship_tree_create_sides (gfship_tree ** out, int dim, gfship_refine_fn refine, void * ctx,
-			      const int * side, int device)
+// the tree (tr is a TreePlan), the sweep plans tr->sweep[].h and the face plans onto the device
+static int tree_upload (gfship_tree * tr, const FacePlan * faces)
 {
-  try {
-    return tree_create_sides (out, dim, refine, ctx, side, device);
-  }
-  catch (const std::bad_alloc &) {
-    set_error ("gfship_tree_create: out of host memory while the tree was built");
-    return GFSHIP_EUNSUPPORTED;
-  }
-}
-
-static int tree_create_sides (gfship_tree ** out, int dim, gfship_refine_fn refine, void * ctx,
-			      const int * side, int device)
-{
-  GFSHIP_CHECK (out && refine, GFSHIP_EINVAL, "gfship_tree_create: null argument");
-  GFSHIP_CHECK (dim == 2 || dim == 3, GFSHIP_EINVAL, "gfship_tree_create: dim = %d", dim);
-  if (!g_host_only) {
-    int ndev = 0;
-    if (hipGetDeviceCount (&ndev) != hipSuccess || ndev == 0) {
-      set_error ("gfship_tree_create: no HIP device");
-      return GFSHIP_ENODEVICE;
-    }
-    GFSHIP_CHECK (device >= 0 && device < ndev, GFSHIP_EINVAL, "gfship_tree_create: device %d of %d", device, ndev);
-    GFSHIP_HIP (hipSetDevice (device));
-  }
-
-  // gfs_refine_refine + gfs_simulation_refine, src/refine.c:45-60, src/simulation.c:1203-1233
-  Builder B;
-  B.dim = dim;
-  B.ensure (0);
-  B.flag[0][B.idx (0, 1, 1, 1)] = LEAF;
-  int e = B.refine_rec (0, 1, 1, 1, refine, ctx);
-  GFSHIP_CHECK (!B.too_large, GFSHIP_EUNSUPPORTED,
-		"gfship_tree_create: more than 2^27 cells in the dense levels of the tree");
-  GFSHIP_CHECK (e == 0, e, "gfship_tree_create: more than %d levels", GFSHIP_MAXLEVEL);
-  gfship_tree * tr = new gfship_tree;
-  tr->device = device;
-  tr->sw = read_switches ();
-  for (int d = 0; d < 2*dim; d++) {
-    tr->side[d] = side ? side[d] : GFSHIP_SIDE_PERIODIC;
-    if (tr->side[d] != GFSHIP_SIDE_PERIODIC && tr->side[d] != GFSHIP_SIDE_BOUNDARY) {
-      delete tr;
-      set_error ("gfship_tree_create: side %d: periodic or boundary", d);
-      return GFSHIP_EINVAL;
-    }
-    if (tr->side[d] == GFSHIP_SIDE_BOUNDARY) tr->has_boundary = true;
-    tr->bc_p[d] = GFSHIP_BC_SYMMETRY;
-  }
-  {
-    long long total = 0;      /* 32-bit cell indices, times the number of directions in the tables */
-    for (size_t l = 0; l < B.flag.size (); l++)
-      total += (long long) B.flag[l].size ();
-    if (total > (1ll << 27)) {
-      delete tr;
-      set_error ("gfship_tree_create: more than 2^27 cells in the dense levels of the tree");
-      return GFSHIP_EUNSUPPORTED;
-    }
-  }
-  auto flatten = [&] () {
-    Topo & H = tr->H;
-    H.dim = dim;
-    H.depth = (int) B.flag.size () - 1;
-    int off = 0;
-    for (int l = 0; l <= H.depth; l++) {
-      H.off[l] = off;
-      off += H.lsize (l);
-    }
-    H.off[H.depth + 1] = off;
-    tr->ncell = off;
-    tr->hflag.assign (off, NONE);
-    for (int l = 0; l <= H.depth; l++)
-      std::copy (B.flag[l].begin (), B.flag[l].end (), tr->hflag.begin () + H.off[l]);
-    H.flag = tr->hflag.data ();
-  };
-  flatten ();
-  for (int l = tr->H.depth - 2; l >= 0; l--) {
-    // the refinements of a level are applied while the level is traversed (simulation.c:1105-1109)
-    traverse (tr->H, root_cell (tr->H), T_LEVEL, l, [&] (Cell c) {
-	if (tr->H.leaf (c) && refine_corner (tr->H, c)) {
-	  (void) B.refine_single (c.l, tr->H.ci (c), tr->H.cj (c), tr->H.ck (c));
-	  for (int ll = 0; ll <= tr->H.depth; ll++)
-	    std::copy (B.flag[ll].begin (), B.flag[ll].end (), tr->hflag.begin () + tr->H.off[ll]);
-	}
-      });
-  }
-  // gfs_domain_match: the ghost trees of the periodic sides mirror the cells they face; both cells
-  // of a periodic pair must be at the same refinement
-  {
-    std::vector<Ghost> all;
-    Topo every = tr->H;
-    for (int l = 0; l <= tr->H.depth; l++) {
-      // every ghost position of the level, whatever its flag: mark them present for the listing
-      const int n = 1 << l, r = n + 2;
-      unsigned char * f = tr->hflag.data () + tr->H.off[l];
-      for (int side = 0; side < 2*dim; side++)
-	for (int tb = 1; tb <= (dim == 3 ? n : 1); tb++)
-	  for (int ta = 1; ta <= n; ta++) {
-	    int g[3], im[3], own[3];
-	    const int a = side/2, o1 = a == 0 ? 1 : 0, o2 = a == 2 ? 1 : 2;
-	    g[a] = (side & 1) ? 0 : n + 1;
-	    im[a] = (side & 1) ? n : 1;
-	    own[a] = (side & 1) ? 1 : n;
-	    g[o1] = im[o1] = own[o1] = ta;
-	    g[o2] = im[o2] = own[o2] = dim == 3 ? tb : 0;
-	    const int G = g[0] + r*(g[1] + r*g[2]), I = im[0] + r*(im[1] + r*im[2]),
-	      O = own[0] + r*(own[1] + r*own[2]);
-	    if (tr->side[side] != GFSHIP_SIDE_PERIODIC) {    /* the ghost tree of a GfsBoundary matches its side */
-	      f[G] = f[O];
-	      continue;
-	    }
-	    if (f[O] != f[I]) {
-	      delete tr;
-	      set_error ("gfship_tree_create: the refinement differs across a periodic side (level %d)", l);
-	      return GFSHIP_EUNSUPPORTED;
-	    }
-	    f[G] = f[I];
-	  }
-    }
-    (void) every; (void) all;
-  }
-
-  const Topo & T = tr->H;
-  if (!g_host_only) {
-    hipError_t he = hipStreamCreate (&tr->stream);
-    if (he != hipSuccess) { tree_free (tr); return hip_fail (he, "hipStreamCreate", __FILE__, __LINE__); }
-  }
-#define TRY(call) do { int e_ = (call); if (e_) { tree_free (tr); return e_; } } while (0)
-#define TRYHIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { tree_free (tr); \
-      return hip_fail (e_, #call, __FILE__, __LINE__); } } while (0)
-  if (!g_host_only) {
-    TRYHIP (hipMalloc ((void **) &tr->dflag, tr->ncell));
-    TRYHIP (hipMemcpy (tr->dflag, tr->hflag.data (), tr->ncell, hipMemcpyHostToDevice));
-  }
-  {
-    // the tables of Topo (tree.hpp), from the computed answers
-    Topo & H = tr->H;
-    const int nd = H.nd ();
-    tr->h_nbtab.assign ((size_t) tr->ncell*nd, -1);
-    tr->h_child0.assign (tr->ncell, 0);
-    tr->h_cmask.assign (tr->ncell, 0);
-    tr->h_idtab.assign (tr->ncell, 0);
-    for (int l = 0; l <= H.depth; l++)
-      for (int q = 0; q < H.lsize (l); q++) {
-	const int g = H.off[l] + q;
-	if (tr->hflag[g] == NONE)
-	  continue;
-	const Cell c = { l, q };
-	for (int d = 0; d < nd; d++) {
-	  const Cell nb = H.neighbor (c, d);
-	  tr->h_nbtab[(size_t) g*nd + d] = !exists (nb) ? -1 : nb.l == l ? nb.q : - nb.q - 2;
-	}
-	tr->h_idtab[g] = (unsigned char) (H.id (c) | (H.interior (c) ? 8 : 0));
-	if (l < H.depth) {
-	  const int rr = H.r (l + 1);
-	  tr->h_child0[g] = 2*H.ci (c) - 1 + rr*(2*H.cj (c) + (dim == 3 ? rr*2*H.ck (c) : 0));
-	  for (int k = 0; k < H.nc (); k++)
-	    if (exists (H.child (c, k)))
-	      tr->h_cmask[g] |= (unsigned char) (1 << k);
-	}
-      }
-    H.nbtab = tr->h_nbtab.data ();
-    H.child0 = tr->h_child0.data ();
-    H.cmask = tr->h_cmask.data ();
-    H.idtab = tr->h_idtab.data ();
-  }
-  TRY (to_device (tr->h_nbtab, &tr->d_nbtab));
-  TRY (to_device (tr->h_child0, &tr->d_child0));
-  TRY (to_device (tr->h_cmask, &tr->d_cmask));
-  TRY (to_device (tr->h_idtab, &tr->d_idtab));
+  hipError_t he = hipStreamCreate (&tr->stream);
+  if (he != hipSuccess) return hip_fail (he, "hipStreamCreate", __FILE__, __LINE__);
+  GFSHIP_HIP (hipMalloc ((void **) &tr->dflag, tr->ncell));
+  GFSHIP_HIP (hipMemcpy (tr->dflag, tr->hflag.data (), tr->ncell, hipMemcpyHostToDevice));
+  int e;
+  if ((e = to_device (tr->h_nbtab, &tr->d_nbtab)) || (e = to_device (tr->h_child0, &tr->d_child0)) ||
+      (e = to_device (tr->h_cmask, &tr->d_cmask)) || (e = to_device (tr->h_idtab, &tr->d_idtab)))
+    return e;
   tr->D = tr->H;
   tr->D.flag = tr->dflag;
   tr->D.nbtab = tr->d_nbtab;
   tr->D.child0 = tr->d_child0;
   tr->D.cmask = tr->d_cmask;
   tr->D.idtab = tr->d_idtab;
-  for (int v = 0; v < V_NVAR && !g_host_only; v++) {
-    TRYHIP (hipMalloc ((void **) &tr->var[v], tr->ncell*sizeof (double)));
-    TRYHIP (hipMemset (tr->var[v], 0, tr->ncell*sizeof (double)));
+  for (int v = 0; v < V_NVAR; v++) {
+    GFSHIP_HIP (hipMalloc ((void **) &tr->var[v], tr->ncell*sizeof (double)));
+    GFSHIP_HIP (hipMemset (tr->var[v], 0, tr->ncell*sizeof (double)));
   }
-  if (!g_host_only) {
-    TRYHIP (hipMalloc ((void **) &tr->d_red, 8*sizeof (double)));
-    TRYHIP (hipHostMalloc ((void **) &tr->h_red, 8*sizeof (double), 0));
-  }
-  traverse (T, root_cell (T), T_LEAFS, -1, [&] (Cell c) { tr->hleaves.push_back (c); });
+  GFSHIP_HIP (hipMalloc ((void **) &tr->d_red, 8*sizeof (double)));
+  GFSHIP_HIP (hipHostMalloc ((void **) &tr->h_red, 8*sizeof (double), 0));
   tr->nleaves = (int) tr->hleaves.size ();
-  TRY (to_device (tr->hleaves, &tr->leaves));
-  for (int l = 0; l < T.depth; l++) {
-    std::vector<Cell> nl;
-    traverse (T, root_cell (T), T_LEVEL_NON_LEAFS, l, [&] (Cell c) { nl.push_back (c); });
-    tr->nnonleaf[l] = (int) nl.size ();
-    TRY (to_device (nl, &tr->nonleaf[l]));
+  if ((e = to_device (tr->hleaves, &tr->leaves))) return e;
+  for (int l = 0; l < tr->H.depth; l++) {
+    tr->nnonleaf[l] = (int) tr->hnonleaf[l].size ();
+    if ((e = to_device (tr->hnonleaf[l], &tr->nonleaf[l]))) return e;
   }
-  std::vector<Ghost> gh;
-  ghost_list (T, tr->side, T_LEAFS, -1, gh);
-  tr->nghost_leaves = (int) gh.size ();
-  TRY (to_device (gh, &tr->ghost_leaves));
-  for (int m = 0; m <= T.depth; m++)
-    TRY (sweep_plan (tr, m, &tr->sweep[m]));
-  for (int k = 0; k < 1 + dim; k++)
-    TRY (face_set (tr, k, &tr->fs[k]));
-#undef TRY
-#undef TRYHIP
+  tr->nghost_leaves = (int) tr->hghost_leaves.size ();
+  if ((e = to_device (tr->hghost_leaves, &tr->ghost_leaves))) return e;
+  release (tr->hnonleaf); release (tr->hghost_leaves);
+  for (int m = 0; m <= tr->H.depth; m++)
+    if ((e = upload (&tr->sweep[m]))) return e;
+  for (int k = 0; k < 1 + tr->H.dim; k++)
+    if ((e = upload (faces[k], &tr->fs[k]))) return e;
+  return 0;
+}
+
+// no exception crosses the C ABI: a tree too large for the host comes back as an error
+int gfship_tree_create_sides (gfship_tree ** out, int dim, gfship_refine_fn refine, void * ctx,
+			      const int * side, int device)
+try {
+  GFSHIP_CHECK (out && refine, GFSHIP_EINVAL, "gfship_tree_create: null argument");
+  GFSHIP_CHECK (dim == 2 || dim == 3, GFSHIP_EINVAL, "gfship_tree_create: dim = %d", dim);
+  // 1. the device
+  int ndev = 0;
+  if (hipGetDeviceCount (&ndev) != hipSuccess || ndev == 0) {
+    set_error ("gfship_tree_create: no HIP device");
+    return GFSHIP_ENODEVICE;
+  }
+  GFSHIP_CHECK (device >= 0 && device < ndev, GFSHIP_EINVAL, "gfship_tree_create: device %d of %d", device, ndev);
+  GFSHIP_HIP (hipSetDevice (device));
+  // 2. the plans (tree_plan.hip): nothing to free on failure but the plans themselves
+  TreePlans h;
+  int e = plan_tree_create (dim, refine, ctx, side, h);
+  if (e) return e;
+  // 3. the device tree: the plans are moved in, uploaded, and what nothing reads again is dropped
+  gfship_tree * tr = new gfship_tree;
+  static_cast<TreePlan &> (*tr) = std::move (h.T);
+  tr->device = device;
+  tr->sw = h.sw;
+  for (int m = 0; m <= tr->H.depth; m++)
+    tr->sweep[m].h = std::move (h.sweep[m]);
+  if ((e = tree_upload (tr, h.faces))) {
+    tree_free (tr);
+    return e;
+  }
+  // 4. the defaults of the parameters
+  for (int d = 0; d < 2*dim; d++)
+    tr->bc_p[d] = GFSHIP_BC_SYMMETRY;
   gfship_multilevel_params_init (&tr->projection_params, dim);
   gfship_multilevel_params_init (&tr->approx_projection_params, dim);
   for (int c = 0; c < 3; c++) {     /* diffusion_init, src/source.c:966-974 */
@@ -3098,6 +2176,10 @@ static int tree_create_sides (gfship_tree ** out, int dim, gfship_refine_fn refi
   }
   *out = tr;
   return GFSHIP_OK;
+}
+catch (const std::bad_alloc &) {
+  set_error ("gfship_tree_create: out of host memory while the tree was built");
+  return GFSHIP_EUNSUPPORTED;
 }
 
 void gfship_tree_destroy (gfship_tree * tr) { tree_free (tr); }
@@ -3201,266 +2283,6 @@ int gfship_tree_divergence (gfship_tree * tr)
   t_divergence_centered<<<blocks (tr->nleaves), 256, 0, tr->stream>>> (tr->D, tr->leaves, tr->nleaves, p3 (tr, V_U), tr->var[V_DIV]);
   KCHECK ();
   return GFSHIP_OK;
-}
-
-/* Host-side self-check of the plans of a tree, without a device (for the CPU tests): builds the tree
-   and, for every level m, runs the relax loop of nrelax sweeps on pseudo-random values three ways on
-   the host -- (1) the reference's program: copies of the ghosts, the cells in tree order through the
-   stencil code that walks the tree (tree.hpp), sweep after sweep; (2) sweep after sweep through the
-   compiled stencils, the cells of a dependency level in REVERSE order; (3) the plan of the whole loop,
-   the nodes of a level in reverse order -- and compares the three results bit for bit.
-   stats[0] = cells of all sweeps, [1] = dependency levels sweep after sweep, [2] = levels of the loop
-   plans, [3] = cells whose results differ (0 when the plans are right). */
-int gfship_tree_host_check (int dim, gfship_refine_fn refine, void * ctx, const int * side,
-			    unsigned nrelax, long long stats[4])
-{
-  GFSHIP_CHECK (refine && stats && nrelax >= 1, GFSHIP_EINVAL, "gfship_tree_host_check: bad argument");
-  gfship_tree * tr = nullptr;
-  g_host_only = true;
-  int e = gfship_tree_create_sides (&tr, dim, refine, ctx, side, 0);
-  if (e) { g_host_only = false; return e; }
-  const Topo & T = tr->H;
-  stats[0] = stats[1] = stats[2] = stats[3] = 0;
-  const Sgn6 sg = homogeneous_signs (tr);
-  struct HostReader {
-    const double * p;
-    double operator() (const Topo & T, Cell c) const { return p[T.gi (c)]; }
-  };
-  for (int m = 0; m <= T.depth && !e; m++) {
-    Sweep & S = tr->sweep[m];
-    e = loop_plan (tr, m, nrelax, &S);
-    if (e) break;
-    std::vector<double> u0 (tr->ncell), rhs (tr->ncell);
-    unsigned long long seed = 88172645463325252ull + m;
-    for (int g = 0; g < tr->ncell; g++) {
-      seed ^= seed << 13; seed ^= seed >> 7; seed ^= seed << 17;
-      u0[g] = (double) (seed % 2000001)/1e6 - 1.;
-      seed ^= seed << 13; seed ^= seed >> 7; seed ^= seed << 17;
-      rhs[g] = (double) (seed % 2000001)/1e6 - 1.;
-    }
-    const double omega = 1.;
-    // (1) the sequential program through the tree-walking stencil code
-    std::vector<double> a = u0;
-    std::vector<Cell> order;
-    traverse (T, root_cell (T), T_LEVEL_LEAFS, m, [&] (Cell c) { order.push_back (c); });
-    for (unsigned sw = 0; sw < nrelax; sw++) {
-      for (const Ghost & G : S.h_ghosts) a[G.g] = sg.s[G.side]*a[G.img];
-      HostReader R = { a.data () };
-      for (Cell c : order) {
-	const int g = T.gi (c);
-	a[g] = relax_cell (T, c, R, rhs[g], omega, m);
-      }
-    }
-    // (2) compiled stencils, sweep after sweep, each dependency level backwards
-    std::vector<double> b = u0;
-    {
-      std::vector<int> lev_of (S.h_g.size (), 0);   /* recompute the levels from the read sets */
-      std::vector<int> wl (tr->ncell, 0), rl (tr->ncell, 0);
-      int nl = 0;
-      for (size_t c = 0; c < S.h_g.size (); c++) {
-	const int w = S.h_g[c];
-	int L = std::max (rl[w], wl[w]);
-	for (int k = S.h_cell_off[3*c + 2]; k < S.h_cell_off[3*(c + 1) + 2]; k++) L = std::max (L, wl[S.h_tv[k]]);
-	L++;
-	for (int k = S.h_cell_off[3*c + 2]; k < S.h_cell_off[3*(c + 1) + 2]; k++) rl[S.h_tv[k]] = std::max (rl[S.h_tv[k]], L);
-	wl[w] = L; rl[w] = 0;
-	lev_of[c] = L; nl = std::max (nl, L);
-      }
-      stats[1] += (long long) nl*nrelax;
-      for (unsigned sw = 0; sw < nrelax; sw++) {
-	for (const Ghost & G : S.h_ghosts) b[G.g] = sg.s[G.side]*b[G.img];
-	for (int L = 1; L <= nl; L++) {
-	  std::vector<std::pair<int, double>> out;
-	  for (size_t c = S.h_g.size (); c-- > 0; )
-	    if (lev_of[c] == L) {
-	      std::vector<double> vals;
-	      for (int k = S.h_cell_off[3*c + 2]; k < S.h_cell_off[3*(c + 1) + 2]; k++) vals.push_back (b[S.h_tv[k]]);
-	      TapeCursor cur = { S.h_ti.data () + S.h_cell_off[3*c], S.h_td.data () + S.h_cell_off[3*c + 1], vals.data () };
-	      const double self = *cur.tv++;
-	      double ga, gb;
-	      tape_cell (cur, T.nd (), T.dim, T.ncd (), ga, gb);
-	      const int g = S.h_g[c];
-	      double x = 0.;
-	      if (ga != 0.)
-		x = T.dim == 2 ? (1. - omega)*self + omega*(gb - rhs[g])/ga : (gb - rhs[g])/ga;
-	      out.push_back ({ g, x });
-	    }
-	  for (auto & kv : out) b[kv.first] = kv.second;      /* the level's stores after its loads */
-	}
-      }
-    }
-    // (3) the plan of the whole loop, the nodes of a level backwards
-    std::vector<double> c3 = u0;
-    {
-      const Sweep::Loop & P = S.loop;
-      stats[2] += P.nlev;
-      size_t k0 = 0;
-      const size_t nn = P.h_node_g.size ();
-      while (k0 < nn) {
-	size_t k1 = k0;
-	while (k1 < nn && P.h_node_level[k1] == P.h_node_level[k0]) k1++;
-	std::vector<std::pair<int, double>> out;
-	for (size_t k = k1; k-- > k0; ) {
-	  std::vector<double> vals;
-	  for (int q = P.h_node_off[3*k + 2]; q < P.h_node_off[3*(k + 1) + 2]; q++) vals.push_back (c3[P.h_tv[q]]);
-	  TapeCursor cur = { P.h_ti.data () + P.h_node_off[3*k], P.h_td.data () + P.h_node_off[3*k + 1], vals.data () };
-	  const int g = P.h_node_g[k];
-	  double x;
-	  if (*cur.ti == K_GHOST)
-	    x = (*cur.td)*(*cur.tv);
-	  else {
-	    const double self = *cur.tv++;
-	    double ga, gb;
-	    tape_cell (cur, T.nd (), T.dim, T.ncd (), ga, gb);
-	    x = 0.;
-	    if (ga != 0.)
-	      x = T.dim == 2 ? (1. - omega)*self + omega*(gb - rhs[g])/ga : (gb - rhs[g])/ga;
-	  }
-	  out.push_back ({ g, x });
-	}
-	for (auto & kv : out) c3[kv.first] = kv.second;
-	k0 = k1;
-      }
-    }
-    // (4) the flow plan (tree_flow.hpp) with the kernel's timing of loads and stores
-    std::vector<double> c4 = u0;
-    if (S.loop.flow) {
-      const long long hz = flow_emulate (*S.loop.flow, T.dim, c4, rhs, omega, 0, 1.);
-      stats[3] += hz;
-      if (tr->sw.tree_debug) {
-	long long nd4 = 0;
-	for (int g = 0; g < tr->ncell; g++) nd4 += memcmp (&a[g], &c4[g], sizeof (double)) != 0;
-	fprintf (stderr, "gfship_tree: flow plan of level %d: %lld hazards, %lld values differ\n", m, hz, nd4);
-	int widest = 0;
-	for (int L = 0; L < S.loop.flow->nlev; L++)
-	  widest = std::max (widest, S.loop.flow->h_lev_off[L + 1] - S.loop.flow->h_lev_off[L]);
-	fprintf (stderr, "gfship_tree: flow plan of level %d: %d levels, widest %d\n", m, S.loop.flow->nlev, widest);
-      }
-    }
-    else
-      c4 = a;
-    stats[0] += (long long) order.size ()*nrelax;
-    for (int g = 0; g < tr->ncell; g++)
-      if (memcmp (&a[g], &b[g], sizeof (double)) || memcmp (&a[g], &c3[g], sizeof (double)) ||
-	  memcmp (&a[g], &c4[g], sizeof (double)))
-	stats[3]++;
-  }
-  tree_free (tr);
-  g_host_only = false;
-  return e;
-}
-
-namespace {
-struct WDirect {            // the coefficients f[d].v of a cell from an array of them (the host check)
-  const double * f;
-  __host__ __device__ inline double operator() (const Topo & T, Cell c, int d) const { return f[(size_t) T.gi (c)*T.nd () + d]; }
-};
-}
-
-// gfship_tree_host_check for the diffusion relax (op 1) with the coefficients of one w
-int gfship_tree_host_check_diffusion (int dim, gfship_refine_fn refine, void * ctx, const int * side,
-				      unsigned nrelax, double w, long long stats[6])
-{
-  GFSHIP_CHECK (refine && stats && nrelax >= 1 && w > 0., GFSHIP_EINVAL, "gfship_tree_host_check_diffusion: bad argument");
-  gfship_tree * tr = nullptr;
-  g_host_only = true;
-  int e = gfship_tree_create_sides (&tr, dim, refine, ctx, side, 0);
-  if (e) { g_host_only = false; return e; }
-  const Topo & T = tr->H;
-  for (int k = 0; k < 6; k++) stats[k] = 0;
-  const int nd = T.nd ();
-  // the coefficients as the reference computes them for this w (the plans of the device take w on every face)
-  std::vector<double> fdir;
-  WArithDouble ard = { w, w/(T.nc ()/2) };
-  diffusion_coefficients_gen (T, ard, fdir);
-  for (int g = 0; g < tr->ncell; g++)
-    for (int d = 0; d < nd; d++) {
-      const double a = fdir[(size_t) g*nd + d];
-      if (a != 0. && a != w) stats[2]++;
-    }
-  if (!diffusion_weights_exact (T)) stats[2] = - stats[2] - 1;      /* the tree would be refused */
-  const Sgn6 sg = homogeneous_signs_u (tr, 0);
-  struct HostReader {
-    const double * p;
-    double operator() (const Topo & T, Cell c) const { return p[T.gi (c)]; }
-  };
-  for (int m = 0; m <= T.depth && !e; m++) {
-    Sweep & S = tr->sweep[m];
-    Sweep::Loop P;
-    e = loop_plan (tr, m, nrelax, &S, &P, &sg);
-    if (e) break;
-    std::vector<double> u0 (tr->ncell), rhs (tr->ncell);
-    unsigned long long seed = 88172645463325252ull + 7*m;
-    for (int g = 0; g < tr->ncell; g++) {
-      seed ^= seed << 13; seed ^= seed >> 7; seed ^= seed << 17;
-      u0[g] = (double) (seed % 2000001)/1e6 - 1.;
-      seed ^= seed << 13; seed ^= seed >> 7; seed ^= seed << 17;
-      rhs[g] = (double) (seed % 2000001)/1e6 - 1.;
-    }
-    // (1) the sequential program through the tree-walking stencil code with the reference's coefficients
-    std::vector<double> a = u0;
-    std::vector<Cell> order;
-    traverse (T, root_cell (T), T_LEVEL_LEAFS, m, [&] (Cell c) { order.push_back (c); });
-    for (unsigned sw = 0; sw < nrelax; sw++) {
-      for (const Ghost & G : S.h_ghosts) a[G.g] = sg.s[G.side]*a[G.img];
-      HostReader R = { a.data () };
-      for (Cell c : order) {
-	const int g = T.gi (c);
-	a[g] = diffusion_relax_cell (T, c, R, rhs[g], WDirect { fdir.data () }, m);
-      }
-    }
-    // (2) the plan of the whole loop (the weight w on every face), the nodes of a level backwards
-    std::vector<double> c3 = u0;
-    {
-      stats[1] += P.nlev;
-      size_t k0 = 0;
-      const size_t nn = P.h_node_g.size ();
-      while (k0 < nn) {
-	size_t k1 = k0;
-	while (k1 < nn && P.h_node_level[k1] == P.h_node_level[k0]) k1++;
-	std::vector<std::pair<int, double>> out;
-	for (size_t k = k1; k-- > k0; ) {
-	  std::vector<double> vals;
-	  for (int q = P.h_node_off[3*k + 2]; q < P.h_node_off[3*(k + 1) + 2]; q++) vals.push_back (c3[P.h_tv[q]]);
-	  TapeCursor cur = { P.h_ti.data () + P.h_node_off[3*k], P.h_td.data () + P.h_node_off[3*k + 1], vals.data () };
-	  const int g = P.h_node_g[k];
-	  double x;
-	  if (*cur.ti == K_GHOST)
-	    x = (*cur.td)*(*cur.tv);
-	  else {      /* t_relax_nodes, op 1 */
-	    cur.tv++;
-	    double ga, gb;
-	    tape_cell (cur, nd, T.dim, T.ncd (), ga, gb, w);
-	    int l = 0;
-	    while (g >= T.off[l + 1]) l++;
-	    const double h = 1./(1 << l);
-	    const double aa = 1.*h*h;
-	    ga = 1. + ga/aa;
-	    x = (gb/aa + rhs[g])/ga;
-	  }
-	  out.push_back ({ g, x });
-	}
-	for (auto & kv : out) c3[kv.first] = kv.second;
-	k0 = k1;
-      }
-    }
-    // (3) the flow plan with the kernel's timing of loads and stores
-    std::vector<double> c4 = u0;
-    if (P.flow)
-      stats[4] += flow_emulate (*P.flow, T.dim, c4, rhs, 1., 1, w);
-    else {
-      stats[5]++;
-      c4 = a;
-    }
-    stats[0] += (long long) order.size ()*nrelax;
-    for (int g = 0; g < tr->ncell; g++)
-      if (memcmp (&a[g], &c3[g], sizeof (double)) || memcmp (&a[g], &c4[g], sizeof (double)))
-	stats[3]++;
-    loop_free (P);
-  }
-  tree_free (tr);
-  g_host_only = false;
-  return e;
 }
 
 /* the cells of the sweep of level `level' and the number of dependency levels they form */

@@ -7,7 +7,7 @@
 // exists and whether it is a leaf.  Neighbour, parent and children are index arithmetic.
 //
 // Everything in this file is __host__ __device__ and templated on how a value is read: the kernels
-// (tree.hip) read device arrays; the host instantiates the same stencil code with a reader that
+// (tree.hip) read device arrays; the planner (tree_plan.hip) instantiates the same stencil code with a reader that
 // records WHICH cells are read, and derives from that the dependency levels of an exact-order sweep
 // (the reference relaxes the cells of a level, coarser leaves included, in tree order:
 // src/poisson.c:604-632, src/ftt.c:689-926).
@@ -365,7 +365,7 @@ __host__ __device__ inline double face_interpolated_value_generic (const Topo & 
 // with the face coefficients of gfs_diffusion_coefficients for a constant D.  W gives f[d].v of a cell: the
 // kernels use WConst, the same w on every face -- what diffusion_coef and face_coeff_from_below give on a quadtree
 // (w/2 + w/2, (w + w)/2) and, exactly too, on an octree (four quarters, four children: diffusion_weights_exact in
-// tree.hip checks every face of a tree before it takes viscosity); the host check reads the reference's own
+// tree_plan.hip checks every face of a tree before it takes viscosity); the host check reads the reference's own
 // coefficients through another W
 struct WConst {
   double w;

@@ -1,6 +1,8 @@
 // tree_flow.hpp -- the relax loop of a tree level (src/poisson.c:1070-1089 over the cells of
 // T_LEVEL_LEAFS, src/poisson.c:604-632) as a dataflow program of fixed-format micro-operations.
-// Included by tree.hip inside its anonymous namespace (after Sweep, Ghost, Sgn6, the K_* codes).
+// This file holds the kernels and is included by tree.hip inside its anonymous namespace; the record format and
+// the arithmetic of one operation, which the host's emulator shares, are in tree_flow_ops.hpp; the planner
+// (FlowBuilder, plan_flow) and the emulator (flow_emulate) are in tree_plan.hip.
 //
 // Why: t_relax_nodes interprets the stencil of a cell from a variable-length tape, one thread per
 // cell -- a coarse leaf with fine neighbours is a chain of ~100 dependent LDS reads, and the slowest
@@ -27,9 +29,9 @@
 // reads of its fresh inputs, the arithmetic of ONE micro-operation, an LDS write, a barrier.
 //
 // The loop runs on copies of the values and of the right-hand side laid out in the order of the plan
-// (t_flow_pack / t_flow_unpack around it): see FlowPlan.
+// (t_flow_pack / t_flow_unpack around it): see FlowProgram (tree_plan.hpp).
 //
-// The schedule keeps the order of the sequential program as loop_plan does (a read follows the write
+// The schedule keeps the order of the sequential program as plan_loop does (a read follows the write
 // it must see, a write follows the reads of the value it replaces, one level at least), so that the
 // single image in global memory is right for every load; gfship_tree_host_check runs the plan on the
 // host with the kernel's timing of loads and stores (and its choice of the branch-free arithmetic per
@@ -48,221 +50,6 @@
 // ahead by LDS-DMA loads (out); 128 / 256 / 384 operations per level (GFSHIP_FLOW_WIDTH; 256 is the default on
 // quadtrees); on quadtrees a CELL with the FC / CHILD / SUM of its faces in the same operation (out: 38 % fewer
 // levels, each twice as expensive); a select-free CELL / FC (out: 5 % slower).
-
-enum { F_CELL = 0, F_FC = 1, F_CHILD = 2, F_SUM = 3, F_GHOST = 4, F_NOP = 5 };
-enum { FK_NONE = 0, FK_SAME = 1, FK_PAIR = 2 };
-#define FLOW_WIDTH  512             /* most operations per level = threads of the workgroup; a plan may use fewer */
-#define FLOW_PD     1               /* old values are loaded FLOW_PD levels ahead, records FLOW_PD + 2 */
-#define FLOW_NBUF   (FLOW_PD + 2)   /* a result stays in the LDS for FLOW_PD + 1 levels: its store is issued a level late */
-#define FLOW_NIN    10
-#define FLOW_NCONST 128
-// an input of a record: < 0: the result of an operation of one of the last FLOW_PD levels, bits 4-14 = its
-// slot (level % FLOW_NBUF)*FLOW_WIDTH + operation (i.e. bits 0-14 = its byte address in the LDS);
-// >= 0: a cell, as the byte offset 8 g of its value in global memory.  out_g: the same offset, or -1
-#define FLOW_IS_LDS(ref)  ((ref) < 0)
-#define FLOW_LDS_REF(slot) ((int) (0x80000000u | ((unsigned) (slot) << 4)))
-#define FLOW_LDS_ADDR(ref) ((ref) & 0x7ff0)
-#define FLOW_NONE   FLOW_LDS_REF (FLOW_LDS_SLOTS - 1)      /* no input: a slot no operation writes */
-#define FLOW_LDS_SLOTS 2048         /* 32 KB: any masked address stays inside */
-#define FLOW_MAXLEV  5900            /* levels of a plan (their first operations sit in the LDS) */
-
-struct __attribute__((aligned(16))) FlowRec { unsigned w0; int out_g; int in[FLOW_NIN]; };
-// w0: bits 0-2 the kind
-//   CELL   3-14 the kind of each face (FK_*), 15-19 the level of the cell, 20: reads its own value
-//          in[0] the cell itself, in[1 + d] the neighbour (FK_SAME) or the pair of the face (FK_PAIR)
-//   FC / CHILD  3-4 terms of the interpolation, 5-7 / 8-10 cells averaged in term 0 / 1 (0: one
-//          value), 11-17 / 18-24 / 25-31 the constants cb (gbi), a0, a1 in the table
-//          in[0] the coarse neighbour (the child), in[1 + TS t + k] value k of term t
-//   SUM    3-5 children;  in[i] the pair of child i
-//   GHOST  11-17 the constant (the sign of the homogeneous condition);  in[0] the image
-// The operations of a level are sorted by kind (CELL | FC, CHILD | SUM, GHOST), each kind starting at a multiple of
-// 64 when the plan is 256 wide at least (the schedule keeps the room): a wavefront runs one branch of flow_eval
-
-template <int DIM> struct FlowShape {
-  static constexpr int TS = DIM == 3 ? 4 : 2;            /* values of one interpolation term */
-  static constexpr int NIN = DIM == 3 ? 9 : 5;           /* inputs a record of this dimension uses */
-};
-
-struct __attribute__((aligned(16))) FlowPair { double x, y; };
-
-// one micro-operation, arithmetic only.  x[j]: the input j (a value from global memory or the result of an
-// operation of the previous level), y[j]: the second number of the pair when input j is a pair; rh: the
-// right-hand side of a CELL; ct: the constants
-template <int DIM>
-__host__ __device__ inline FlowPair flow_eval (unsigned w0, const double * x, const double * y, double rh,
-					       const double * ct, double omega, int op, double w)
-{
-  constexpr int TS = FlowShape<DIM>::TS;
-  const int kind = w0 & 7;
-  FlowPair o = { 0., 0. };
-  if (kind == F_CELL) {
-    double ga = 0., gb = 0.;
-#pragma unroll
-    for (int d = 0; d < 2*DIM; d++) {
-      const int fk = (w0 >> (3 + 2*d)) & 3;
-      if (fk == FK_SAME) {
-	const double na = w, nb = w*x[1 + d];
-	ga += na; gb += nb;
-      }
-      else if (fk == FK_PAIR) {
-	ga += y[1 + d]; gb += x[1 + d];
-      }
-    }
-    if (op == 0) {
-      double r = 0.;
-      if (ga != 0.) {
-	const double t = gb - rh;
-	const double q = ga == 4. ? t*0.25 : t/ga;      /* t/4 and t*0.25 are the same number */
-	if (DIM == 2)
-	  r = (1. - omega)*x[0] + omega*q;
-	else
-	  r = q;
-      }
-      o.x = r;
-    }
-    else {      /* diffusion_relax, src/poisson.c:1471-1498 (rhoc = 1) */
-      const int l = (w0 >> 15) & 31;
-      const double h = 1./(1 << l);
-      const double a = 1.*h*h;
-      ga = 1. + ga/a;
-      o.x = (gb/a + rh)/ga;
-    }
-  }
-  else if (kind == F_FC || kind == F_CHILD) {
-    const int nt = (w0 >> 3) & 3;
-    double pb = 0.;
-#pragma unroll
-    for (int t = 0; t < DIM - 1; t++)
-      if (t < nt) {
-	const double a = ct[(w0 >> (18 + 7*t)) & 127];
-	const int cnt = (w0 >> (5 + 3*t)) & 7;
-	double P;
-	if (cnt == 0)
-	  P = x[1 + TS*t];
-	else {
-	  double av = 0., n = 0.;
-#pragma unroll
-	  for (int k = 0; k < TS; k++)
-	    if (k < cnt) {
-	      n += 1.;
-	      av += 1.*x[1 + TS*t + k];
-	    }
-	  /* av/n; n = 1, 2, 4: the product by 1/n is the same number, without the division */
-	  P = n == 4. ? av*0.25 : n == 2. ? av*0.5 : n == 1. ? av : av/n;
-	}
-	pb += a*P;
-      }
-    const double gc = 2.*pb/3.;
-    const double c0 = ct[(w0 >> 11) & 127];
-    if (kind == F_FC) {
-      o.y = w*(2./3.);
-      o.x = w*(c0*x[0] + gc);
-    }
-    else {
-      o.y = w*c0;
-      o.x = w*((2./3.)*x[0] - gc);
-    }
-  }
-  else if (kind == F_SUM) {
-    const int nch = (w0 >> 3) & 7;
-    double na = 0., nb = 0.;
-#pragma unroll
-    for (int i = 0; i < (DIM == 3 ? 4 : 2); i++)
-      if (i < nch) {
-	na += y[i];
-	nb += x[i];
-      }
-    if (DIM > 2) {
-      na /= 4/2.;
-      nb /= 4/2.;
-    }
-    o.x = nb; o.y = na;
-  }
-  else if (kind == F_GHOST)
-    o.x = ct[(w0 >> 11) & 127]*x[0];
-  return o;
-}
-
-// The same operations without a branch, for a wavefront whose lanes all run the same kind (the operations of
-// a level are sorted by kind): what a lane does not have is added as + 0. -- the sums start from + 0. and a
-// sum that starts from + 0. is never - 0., so x + 0. = x bit for bit -- and selected afterwards.  The branches
-// of flow_eval cost more than its arithmetic (46 exec-mask branches per operation).  Divisions: one per
-// operation (t/ga; 2 pb/3); av/n is a product for n = 1, 2, 4 and a division, behind a branch the whole
-// wavefront takes together, when a lane has n = 3.
-template <int DIM, int KIND, class ANY>
-__host__ __device__ inline FlowPair flow_eval_uniform (unsigned w0, const double * x, const double * y, double rh,
-						       const double * ct, double omega, int op, double w, const ANY & any)
-{
-  constexpr int TS = FlowShape<DIM>::TS;
-  FlowPair o = { 0., 0. };
-  if (KIND == F_CELL) {
-    double ga = 0., gb = 0.;
-#pragma unroll
-    for (int d = 0; d < 2*DIM; d++) {
-      const int fk = (w0 >> (3 + 2*d)) & 3;
-      const double na = fk == FK_SAME ? w : fk == FK_PAIR ? y[1 + d] : 0.;
-      const double nb = fk == FK_SAME ? w*x[1 + d] : fk == FK_PAIR ? x[1 + d] : 0.;
-      ga += na; gb += nb;
-    }
-    if (op == 0) {
-      const double q = (gb - rh)/ga;
-      const double r = DIM == 2 ? (1. - omega)*x[0] + omega*q : q;
-      o.x = ga != 0. ? r : 0.;
-    }
-    else {
-      const int l = (w0 >> 15) & 31;
-      const double h = 1./(1 << l);
-      const double a = 1.*h*h;
-      ga = 1. + ga/a;
-      o.x = (gb/a + rh)/ga;
-    }
-  }
-  else if (KIND == F_FC) {      /* FC and CHILD */
-    const int nt = (w0 >> 3) & 3;
-    double pb = 0.;
-#pragma unroll
-    for (int t = 0; t < DIM - 1; t++) {
-      const double a = ct[(w0 >> (18 + 7*t)) & 127];
-      const int cnt = (w0 >> (5 + 3*t)) & 7;
-      double av = 0.;
-#pragma unroll
-      for (int k = 0; k < TS; k++)
-	av += k < cnt ? 1.*x[1 + TS*t + k] : 0.;
-      double P = cnt == 4 ? av*0.25 : cnt == 2 ? av*0.5 : av;      /* av/n, n = 4, 2, 1 */
-      if (any (t < nt && cnt == 3)) {
-	const double n3 = 3.;
-	P = cnt == 3 ? av/n3 : P;
-      }
-      P = cnt == 0 ? x[1 + TS*t] : P;
-      pb += t < nt ? a*P : 0.;
-    }
-    const double gc = 2.*pb/3.;
-    const double c0 = ct[(w0 >> 11) & 127];
-    const bool fc = (w0 & 7) == F_FC;
-    o.y = fc ? w*(2./3.) : w*c0;
-    o.x = fc ? w*(c0*x[0] + gc) : w*((2./3.)*x[0] - gc);
-  }
-  else if (KIND == F_SUM) {
-    const int nch = (w0 >> 3) & 7;
-    double na = 0., nb = 0.;
-#pragma unroll
-    for (int i = 0; i < (DIM == 3 ? 4 : 2); i++) {
-      na += i < nch ? y[i] : 0.;
-      nb += i < nch ? x[i] : 0.;
-    }
-    if (DIM > 2) {
-      na /= 4/2.;
-      nb /= 4/2.;
-    }
-    o.x = nb; o.y = na;
-  }
-  else if (KIND == F_GHOST)
-    o.x = ct[(w0 >> 11) & 127]*x[0];
-  return o;
-}
-
-// the kind all the operations of a wavefront share (NOPs apart), or -1
-__host__ __device__ inline int flow_class (int kind) { return kind == F_CHILD ? F_FC : kind; }
 
 struct FlowAnyDev {
   __device__ inline bool operator() (bool b) const { return __any (b); }
@@ -543,428 +330,3 @@ __global__ void t_flow_unpack (const int * __restrict__ gidx, int n, const doubl
     u[gidx[p]] = up[p];
 }
 
-// ---- host: the plan ---------------------------------------------------------------------------
-
-struct FlowPlan {
-  int nlev = 0, nops = 0, nct = 0;
-  int width = FLOW_WIDTH;          // operations per level at most = threads of the launch
-  FlowRec * rec = nullptr;         // device
-  int * lev_off = nullptr;         // device, nlev + 1
-  double * ct = nullptr;           // device
-  // the loop works on copies of the values and of the right-hand side in the ORDER OF THE PLAN (the cells in
-  // the order their operations first appear): the cells of a level, and their neighbours on the next, are
-  // then next to each other in memory -- in the tree's own arrays (one dense array per level) the cells of a
-  // dependency level lie on a skew hyperplane and every 8-byte value costs a 128-byte line from the L2
-  int npos = 0;
-  int * gidx = nullptr;            // device, npos: the cell at each place
-  double * up = nullptr, * rp = nullptr;   // device, npos
-  std::vector<int> h_gidx;
-  std::vector<FlowRec> h_rec;      // host copies (gfship_tree_host_check)
-  std::vector<int> h_lev_off;
-  std::vector<double> h_ct;
-};
-
-inline void flow_free (FlowPlan & F)
-{
-  (void) hipFree (F.rec); (void) hipFree (F.lev_off); (void) hipFree (F.ct);
-  (void) hipFree (F.gidx); (void) hipFree (F.up); (void) hipFree (F.rp);
-  F = FlowPlan ();
-}
-
-// the stencil of one cell read back from the streams tape_cell_gen wrote
-struct FlowTerm { double a; int cnt; int idx[4]; };
-struct FlowItem { double c; int g; int nt; FlowTerm t[2]; };            /* FC, or one child of a DEEP face */
-struct FlowFace { int kind; int g; FlowItem fc; int nch; FlowItem ch[4]; };
-
-inline bool flow_parse_interp (const int *& ti, const double *& td, const int *& tv, int dim, FlowItem & it)
-{
-  it.nt = *ti++;
-  if (it.nt < 0 || it.nt > dim - 1) return false;
-  for (int t = 0; t < it.nt; t++) {
-    FlowTerm & T = it.t[t];
-    T.a = *td++;
-    T.cnt = *ti++;
-    if (T.cnt < 0 || T.cnt > (dim == 3 ? 4 : 2)) return false;
-    const int n = T.cnt == 0 ? 1 : T.cnt;
-    for (int k = 0; k < n; k++) T.idx[k] = *tv++;
-  }
-  return true;
-}
-
-inline bool flow_parse_cell (const int * ti, const double * td, const int * tv, int dim, int & self, FlowFace * f)
-{
-  self = *tv++;
-  for (int d = 0; d < 2*dim; d++) {
-    FlowFace & F = f[d];
-    F.kind = *ti++;
-    F.nch = 0;
-    if (F.kind == K_NONE) continue;
-    if (F.kind == K_SAME) F.g = *tv++;
-    else if (F.kind == K_FC) {
-      F.fc.c = *td++;
-      F.fc.g = *tv++;
-      if (!flow_parse_interp (ti, td, tv, dim, F.fc)) return false;
-    }
-    else if (F.kind == K_DEEP) {
-      F.nch = *ti++;
-      if (F.nch < 0 || F.nch > (dim == 3 ? 4 : 2)) return false;
-      for (int i = 0; i < F.nch; i++) {
-	F.ch[i].c = *td++;
-	F.ch[i].g = *tv++;
-	if (!flow_parse_interp (ti, td, tv, dim, F.ch[i])) return false;
-      }
-    }
-    else return false;
-  }
-  return true;
-}
-
-struct FlowBuilder {
-  int dim;
-  int width = FLOW_WIDTH;
-  std::vector<int> wlev, wop, rlev;                 /* per cell: level and operation of its last write; last read */
-  std::vector<std::vector<FlowRec>> lev;            /* lev[L - 1]: the operations of level L */
-  std::vector<std::array<int, 3>> cls;              /* of which CELL | FC, CHILD | SUM, GHOST */
-  bool padded = true;                               /* a level has room for every kind to start at a multiple of 64 */
-  std::vector<double> ct;
-  bool ok = true;
-
-  int constant (double c)
-  {
-    for (size_t i = 0; i < ct.size (); i++)
-      if (!memcmp (&ct[i], &c, sizeof (double))) return (int) i;
-    if (ct.size () >= FLOW_NCONST) { ok = false; return 0; }
-    ct.push_back (c);
-    return (int) ct.size () - 1;
-  }
-  int slot (int L, int i) const { return ((L - 1) % FLOW_NBUF)*width + i; }   /* result i of level L */
-  int fill (int L) const { return L >= 1 && L <= (int) lev.size () ? (int) lev[L - 1].size () : 0; }
-  void need (int L) { if ((int) lev.size () < L) { lev.resize (L); cls.resize (L, std::array<int, 3> { { 0, 0, 0 } }); } }
-  static int class_of (int kind) { return kind == F_CELL ? 0 : kind == F_FC || kind == F_CHILD ? 1 : 2; }
-  // room on level L for a0 / a1 / a2 more operations of the three classes
-  bool room (int L, int a0, int a1, int a2) const
-  {
-    int c0 = a0, c1 = a1, c2 = a2;
-    if (L >= 1 && L <= (int) cls.size ()) { c0 += cls[L - 1][0]; c1 += cls[L - 1][1]; c2 += cls[L - 1][2]; }
-    if (!padded) return c0 + c1 + c2 <= width;
-    return (c0 + 63)/64*64 + (c1 + 63)/64*64 + c2 <= width;
-  }
-  int ready (const FlowItem & it) const           /* first level an FC / CHILD may run at */
-  {
-    int L = wlev[it.g];
-    for (int t = 0; t < it.nt; t++)
-      for (int k = 0; k < (it.t[t].cnt == 0 ? 1 : it.t[t].cnt); k++)
-	L = std::max (L, wlev[it.t[t].idx[k]]);
-    return L + 1;
-  }
-  int ref (int g, int L)                           /* the input g of an operation of level L */
-  {
-    rlev[g] = std::max (rlev[g], L);
-    /* level 0: the values before the loop; a value at most FLOW_PD + 1 levels old is still in the LDS */
-    return wlev[g] > 0 && L - wlev[g] <= FLOW_PD + 1 ? FLOW_LDS_REF (slot (wlev[g], wop[g])) : 8*g;
-  }
-  int emit (int L, const FlowRec & r)
-  {
-    need (L);
-    lev[L - 1].push_back (r);
-    cls[L - 1][class_of (r.w0 & 7)]++;
-    return (int) lev[L - 1].size () - 1;
-  }
-  static FlowRec blank (int kind)
-  {
-    FlowRec r;
-    r.w0 = kind; r.out_g = -1;
-    for (int j = 0; j < FLOW_NIN; j++) r.in[j] = FLOW_NONE;
-    return r;
-  }
-  int emit_item (int kind, const FlowItem & it, int L)
-  {
-    const int TS = dim == 3 ? 4 : 2;
-    FlowRec r = blank (kind);
-    r.w0 |= it.nt << 3;
-    r.w0 |= (unsigned) constant (it.c) << 11;
-    r.in[0] = ref (it.g, L);
-    for (int t = 0; t < it.nt; t++) {
-      r.w0 |= it.t[t].cnt << (5 + 3*t);
-      r.w0 |= (unsigned) constant (it.t[t].a) << (18 + 7*t);
-      for (int k = 0; k < (it.t[t].cnt == 0 ? 1 : it.t[t].cnt); k++)
-	r.in[1 + TS*t + k] = ref (it.t[t].idx[k], L);
-    }
-    return emit (L, r);
-  }
-  void ghost (int g, int img, double s)
-  {
-    int L = std::max (wlev[img], std::max (rlev[g], wlev[g])) + 1;
-    for (int tries = 0; !room (L, 0, 0, 1); L++) if (++tries > 1000000) { ok = false; return; }
-    FlowRec r = blank (F_GHOST);
-    r.w0 |= (unsigned) constant (s) << 11;
-    r.out_g = 8*g;
-    r.in[0] = ref (img, L);
-    const int i = emit (L, r);
-    wlev[g] = L; wop[g] = i; rlev[g] = 0;
-  }
-  void cell (int g, int self, const FlowFace * f, int cell_level, bool reads_self)
-  {
-    int L = std::max (rlev[g], wlev[g]) + 1;
-    int nfc = 0, nsum = 0, n2 = 0;      /* FC and SUM one level before the cell's, CHILD two levels before */
-    if (reads_self) L = std::max (L, wlev[self] + 1);
-    for (int d = 0; d < 2*dim; d++) {
-      const FlowFace & F = f[d];
-      if (F.kind == K_SAME) L = std::max (L, wlev[F.g] + 1);
-      else if (F.kind == K_FC) { L = std::max (L, ready (F.fc) + 1); nfc++; }
-      else if (F.kind == K_DEEP) {
-	for (int i = 0; i < F.nch; i++) { L = std::max (L, ready (F.ch[i]) + 2); n2++; }
-	nsum++;
-      }
-    }
-    if (n2) L = std::max (L, 3); else if (nfc + nsum) L = std::max (L, 2);
-    for (int tries = 0; !room (L, 1, 0, 0) || ((nfc || nsum) && !room (L - 1, 0, nfc, nsum)) || (n2 && !room (L - 2, 0, n2, 0)); L++)
-      if (++tries > 1000000) { ok = false; return; }
-    FlowRec r = blank (F_CELL);
-    r.w0 |= (unsigned) cell_level << 15;
-    r.out_g = 8*g;
-    if (reads_self) { r.w0 |= 1u << 20; r.in[0] = ref (self, L); }
-    for (int d = 0; d < 2*dim; d++) {
-      const FlowFace & F = f[d];
-      if (F.kind == K_SAME) {
-	r.w0 |= FK_SAME << (3 + 2*d);
-	r.in[1 + d] = ref (F.g, L);
-      }
-      else if (F.kind == K_FC) {
-	r.w0 |= FK_PAIR << (3 + 2*d);
-	r.in[1 + d] = FLOW_LDS_REF (slot (L - 1, emit_item (F_FC, F.fc, L - 1)));
-      }
-      else if (F.kind == K_DEEP) {
-	FlowRec s = blank (F_SUM);
-	s.w0 |= F.nch << 3;
-	for (int i = 0; i < F.nch; i++)
-	  s.in[i] = FLOW_LDS_REF (slot (L - 2, emit_item (F_CHILD, F.ch[i], L - 2)));
-	r.w0 |= FK_PAIR << (3 + 2*d);
-	r.in[1 + d] = FLOW_LDS_REF (slot (L - 1, emit (L - 1, s)));
-      }
-    }
-    const int i = emit (L, r);
-    wlev[g] = L; wop[g] = i; rlev[g] = 0;
-  }
-};
-
-// the loop of nrelax sweeps of Sweep S (its cells in the order S->h_g, a valid sequential order) with
-// the copies of the ghosts between the sweeps, as a flow plan; returns false when the loop does not fit
-// the format (the caller keeps the tape kernels)
-inline bool flow_plan (int ncell, int dim, const Sweep * S, unsigned nrelax, const Sgn6 & sg, const int * cell_level_of,
-		       bool reads_self, FlowPlan * out, bool host_only, bool debug, int width = FLOW_WIDTH)
-{
-  flow_free (*out);
-  FlowBuilder B;
-  B.dim = dim;
-  B.width = width;
-  B.padded = width >= 256;      /* narrower plans (lab) pack the kinds: three kinds at multiples of 64 need the room */
-  B.wlev.assign (ncell, 0); B.wop.assign (ncell, 0); B.rlev.assign (ncell, 0);
-  const size_t nc = S->h_g.size ();
-  std::vector<FlowFace> faces (nc*6);
-  std::vector<int> selfs (nc);
-  for (size_t c = 0; c < nc; c++)
-    if (!flow_parse_cell (S->h_ti.data () + S->h_cell_off[3*c], S->h_td.data () + S->h_cell_off[3*c + 1],
-			  S->h_tv.data () + S->h_cell_off[3*c + 2], dim, selfs[c], &faces[6*c]))
-      return false;
-  for (unsigned sw = 0; sw < nrelax && B.ok; sw++) {
-    for (const Ghost & G : S->h_ghosts) B.ghost (G.g, G.img, sg.s[G.side]);
-    for (size_t c = 0; c < nc && B.ok; c++)
-      B.cell (S->h_g[c], selfs[c], &faces[6*c], cell_level_of[S->h_g[c]], reads_self);
-  }
-  if (!B.ok || (int) B.lev.size () > FLOW_MAXLEV) return false;
-  int nmixed_out = 0;
-  {
-    // the operations of a level sorted by kind (stable); the inputs that name an operation of the level by its
-    // place follow.  An input of level L in buffer b was produced by the level L' in [L - FLOW_PD - 1, L - 1]
-    // with (L' - 1) % FLOW_NBUF == b (FLOW_NBUF = FLOW_PD + 2: one such level).
-    static const int order_of[8] = { 0, 1, 1, 2, 3, 4, 4, 4 };       /* CELL, FC / CHILD, SUM, GHOST */
-    const int nl = (int) B.lev.size ();
-    std::vector<std::vector<int>> place (nl);      /* place[L - 1][old] = new */
-    int nmixed = 0;      /* levels where CELL and FC / CHILD (or CELL and the short kinds) share a wavefront */
-    for (int L = 1; L <= nl; L++) {
-      std::vector<FlowRec> & ops = B.lev[L - 1];
-      std::vector<int> idx (ops.size ());
-      for (size_t i = 0; i < idx.size (); i++) idx[i] = (int) i;
-      std::stable_sort (idx.begin (), idx.end (), [&] (int a, int b) {
-	  return order_of[ops[a].w0 & 7] < order_of[ops[b].w0 & 7]; });
-      // where the level has room, a kind starts at a multiple of 64: a wavefront with two kinds runs the
-      // branchy arithmetic, twice the time of the others, and the level waits for it.  CELL | FC, CHILD |
-      // SUM, GHOST (the last two are short and share)
-      int count[3] = { 0, 0, 0 };
-      for (const FlowRec & r : ops) count[std::min (order_of[r.w0 & 7], 2)]++;
-      int base[3] = { 0, count[0], count[0] + count[1] };
-      {
-	const int b1 = (count[0] + 63)/64*64, b2a = (b1 + count[1] + 63)/64*64, b2b = (count[0] + count[1] + 63)/64*64;
-	if (count[1] + count[2] > 0 && b1 + count[1] + count[2] <= width) {
-	  base[1] = b1;
-	  base[2] = count[2] > 0 && b2a + count[2] <= width ? b2a : b1 + count[1];
-	}
-	else if (count[2] > 0 && b2b + count[2] <= width)
-	  base[2] = b2b;
-      }
-      const int total = std::max (base[2] + count[2], std::max (base[1] + count[1], count[0]));
-      if ((count[1] > 0 && base[1] % 64) || (count[2] > 0 && count[0] + count[1] > 0 && base[2] % 64 && count[1] == 0)) nmixed++;
-      place[L - 1].resize (ops.size ());
-      std::vector<FlowRec> sorted (total, FlowBuilder::blank (F_NOP));
-      int rank[3] = { 0, 0, 0 };
-      for (size_t i = 0; i < idx.size (); i++) {
-	const int k = std::min (order_of[ops[idx[i]].w0 & 7], 2);
-	const int at = base[k] + rank[k]++;
-	sorted[at] = ops[idx[i]];
-	place[L - 1][idx[i]] = at;
-      }
-      ops.swap (sorted);
-    }
-    for (int L = 1; L <= nl; L++)
-      for (FlowRec & r : B.lev[L - 1])
-	for (int j = 0; j < FLOW_NIN; j++)
-	  if (FLOW_IS_LDS (r.in[j]) && r.in[j] != FLOW_NONE) {
-	    const int sl = FLOW_LDS_ADDR (r.in[j]) >> 4, b = sl/width, i = sl % width;
-	    int Lp = -1;
-	    for (int q = L - 1; q >= std::max (1, L - FLOW_PD - 1); q--)
-	      if ((q - 1) % FLOW_NBUF == b) Lp = q;
-	    if (Lp < 0 || i >= (int) place[Lp - 1].size ()) return false;
-	    r.in[j] = FLOW_LDS_REF (b*width + place[Lp - 1][i]);
-	  }
-    nmixed_out = nmixed;
-  }
-  FlowPlan & F = *out;
-  F.width = width;
-  if (debug) fprintf (stderr, "gfship_tree: flow plan: %d of %zu levels have a wavefront with two kinds\n", nmixed_out, B.lev.size ());
-  {
-    // places in the order of the plan
-    std::vector<int> pos (ncell, -1);
-    std::vector<int> & gidx = F.h_gidx;
-    gidx.clear ();
-    auto place_of = [&] (int g) { if (pos[g] < 0) { pos[g] = (int) gidx.size (); gidx.push_back (g); } return pos[g]; };
-    for (auto & l : B.lev) for (FlowRec & r : l) if (r.out_g >= 0) place_of (r.out_g/8);
-    for (auto & l : B.lev) for (FlowRec & r : l)
-      for (int j = 0; j < FLOW_NIN; j++) if (!FLOW_IS_LDS (r.in[j])) place_of (r.in[j]/8);
-    for (auto & l : B.lev) for (FlowRec & r : l) {
-      if (r.out_g >= 0) r.out_g = 8*pos[r.out_g/8];
-      for (int j = 0; j < FLOW_NIN; j++) if (!FLOW_IS_LDS (r.in[j])) r.in[j] = 8*pos[r.in[j]/8];
-    }
-    if (gidx.empty ()) gidx.push_back (0);
-    F.npos = (int) gidx.size ();
-    while (gidx.size () < FLOW_WIDTH + 64) gidx.push_back (gidx[0]);      /* spare places the idle lanes load (not unpacked) */
-  }
-  F.nlev = (int) B.lev.size ();
-  std::vector<FlowRec> rec;
-  std::vector<int> off (1, 0);
-  for (const auto & l : B.lev) {
-    rec.insert (rec.end (), l.begin (), l.end ());
-    off.push_back ((int) rec.size ());
-  }
-  F.nops = (int) rec.size ();
-  for (int k = 0; k < FLOW_PD + 2; k++) {        /* the records the kernel loads ahead of the last level */
-    rec.push_back (FlowBuilder::blank (F_NOP));
-    off.push_back ((int) rec.size ());
-  }
-  for (int k = 0; k < FLOW_WIDTH; k++) rec.push_back (FlowBuilder::blank (F_NOP));      /* what the idle lanes read */
-  F.nct = (int) B.ct.size ();
-  if (host_only) { F.h_rec = rec; F.h_lev_off = off; F.h_ct = B.ct; return true; }
-  const std::vector<int> gidx = F.h_gidx;
-  F.h_gidx.clear (); F.h_gidx.shrink_to_fit ();
-  if (rec.empty ()) return false;
-  std::vector<double> ct = B.ct;
-  if (ct.empty ()) ct.push_back (0.);
-  if (hipMalloc ((void **) &F.rec, rec.size ()*sizeof (FlowRec)) != hipSuccess ||
-      hipMalloc ((void **) &F.lev_off, off.size ()*sizeof (int)) != hipSuccess ||
-      hipMalloc ((void **) &F.ct, ct.size ()*sizeof (double)) != hipSuccess ||
-      hipMalloc ((void **) &F.gidx, gidx.size ()*sizeof (int)) != hipSuccess ||
-      hipMalloc ((void **) &F.up, gidx.size ()*sizeof (double)) != hipSuccess ||
-      hipMalloc ((void **) &F.rp, gidx.size ()*sizeof (double)) != hipSuccess ||
-      hipMemcpy (F.gidx, gidx.data (), gidx.size ()*sizeof (int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy (F.rec, rec.data (), rec.size ()*sizeof (FlowRec), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy (F.lev_off, off.data (), off.size ()*sizeof (int), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy (F.ct, ct.data (), ct.size ()*sizeof (double), hipMemcpyHostToDevice) != hipSuccess) {
-    flow_free (F);
-    return false;
-  }
-  return true;
-}
-
-// the kernel's program on the host, with its timing: the global inputs of level L are read BEFORE the
-// stores of level L - 1 (they are loaded a level ahead), the operations of a level run backwards, the
-// stores of a level land after its loads.  Returns the number of hazards: a store of level L - 1 or L
-// onto a cell that level L reads from global memory (which the schedule must exclude).
-inline long long flow_emulate (const FlowPlan & F, int dim, std::vector<double> & u, const std::vector<double> & rhs,
-			       double omega, int op, double w)
-{
-  long long hazards = 0;
-  std::vector<double> & ucells = u;
-  std::vector<double> up (F.npos), rp (F.npos);
-  for (int p = 0; p < F.npos; p++) { up[p] = ucells[F.h_gidx[p]]; rp[p] = rhs[F.h_gidx[p]]; }
-  std::vector<FlowPair> lo (FLOW_LDS_SLOTS, FlowPair { 0., 0. });
-  std::vector<std::vector<double>> pre (FLOW_NBUF, std::vector<double> ((size_t) FLOW_WIDTH*(FLOW_NIN + 1)));
-  std::vector<int> stored_at (F.npos, -10);
-  auto prefetch = [&] (int L, std::vector<double> & v) {      /* what flow_prefetch loads for level L (0-based) */
-    if (L >= F.nlev) return;
-    for (int i = F.h_lev_off[L]; i < F.h_lev_off[L + 1]; i++) {
-      const FlowRec & r = F.h_rec[i];
-      double * vi = &v[(size_t) (i - F.h_lev_off[L])*(FLOW_NIN + 1)];
-      for (int j = 0; j < FLOW_NIN; j++)
-	vi[j] = up[std::max (r.in[j], 0)/8];
-      vi[FLOW_NIN] = rp[std::max (r.out_g, 0)/8];
-    }
-  };
-  for (int L = 0; L < FLOW_PD; L++) prefetch (L, pre[L % FLOW_NBUF]);
-  std::vector<std::pair<int, double>> late;      /* the stores of the level before: issued during this one */
-  for (int L = 0; L < F.nlev; L++) {
-    prefetch (L + FLOW_PD, pre[(L + FLOW_PD) % FLOW_NBUF]);
-    for (auto & st : late) {
-      if (stored_at[st.first] == L - 1) hazards++;      /* two stores of one level onto one cell */
-      up[st.first] = st.second;
-      stored_at[st.first] = L - 1;
-    }
-    late.clear ();
-    std::vector<std::pair<int, double>> stores;
-    std::vector<FlowPair> cur (FLOW_WIDTH, FlowPair { 0., 0. });
-    for (int i = F.h_lev_off[L + 1]; i-- > F.h_lev_off[L]; ) {
-      const FlowRec & r = F.h_rec[i];
-      const double * vi = &pre[L % FLOW_NBUF][(size_t) (i - F.h_lev_off[L])*(FLOW_NIN + 1)];
-      double x[FLOW_NIN], y[FLOW_NIN];
-      for (int j = 0; j < FLOW_NIN; j++) {
-	const int sl = FLOW_LDS_ADDR (r.in[j]) >> 4;
-	if (FLOW_IS_LDS (r.in[j]) && r.in[j] != FLOW_NONE && sl/F.width == L % FLOW_NBUF)
-	  hazards++;       /* an input in the buffer this level writes */
-	const FlowPair p = lo[sl];
-	x[j] = FLOW_IS_LDS (r.in[j]) ? p.x : vi[j];
-	y[j] = p.y;
-      }
-      // the wavefront of this operation: the 64 operations around it (flow_eval_wave)
-      const int w0i = F.h_lev_off[L] + (i - F.h_lev_off[L])/64*64, w1i = std::min (w0i + 64, F.h_lev_off[L + 1]);
-      int first = F_NOP;      /* the kind of the first operation that is not a NOP, as flow_eval_wave takes it */
-      for (int q = w0i; q < w1i && first == F_NOP; q++) first = flow_class (F.h_rec[q].w0 & 7);
-      bool uniform = true, any3 = false;
-      for (int q = w0i; q < w1i; q++) {
-	const unsigned qw = F.h_rec[q].w0;
-	if (flow_class (qw & 7) != first && flow_class (qw & 7) != F_NOP) uniform = false;
-	if (flow_class (qw & 7) == F_FC)
-	  for (int t = 0; t < dim - 1; t++)
-	    if (t < (int) ((qw >> 3) & 3) && ((qw >> (5 + 3*t)) & 7) == 3) any3 = true;
-      }
-      struct AnyHost { bool v; bool operator() (bool) const { return v; } } any = { any3 };
-      FlowPair o = { 0., 0. };
-#define FLOW_EMU(D)							\
-      o = !uniform ? flow_eval<D> (r.w0, x, y, vi[FLOW_NIN], F.h_ct.data (), omega, op, w) : \
-	first == F_CELL ? flow_eval_uniform<D, F_CELL> (r.w0, x, y, vi[FLOW_NIN], F.h_ct.data (), omega, op, w, any) : \
-	first == F_FC ? flow_eval_uniform<D, F_FC> (r.w0, x, y, vi[FLOW_NIN], F.h_ct.data (), omega, op, w, any) : \
-	first == F_SUM ? flow_eval_uniform<D, F_SUM> (r.w0, x, y, vi[FLOW_NIN], F.h_ct.data (), omega, op, w, any) : \
-	flow_eval_uniform<D, F_GHOST> (r.w0, x, y, vi[FLOW_NIN], F.h_ct.data (), omega, op, w, any)
-      if ((r.w0 & 7) != F_NOP) { if (dim == 3) { FLOW_EMU (3); } else { FLOW_EMU (2); } }
-#undef FLOW_EMU
-      cur[i - F.h_lev_off[L]] = o;
-      if (r.out_g >= 0) stores.push_back ({ r.out_g/8, o.x });
-      for (int j = 0; j < FLOW_NIN; j++)
-	if (!FLOW_IS_LDS (r.in[j]) && stored_at[r.in[j]/8] >= L - FLOW_PD - 1)
-	  hazards++;         /* the load was issued in level L - FLOW_PD, beside the stores of L - FLOW_PD - 1 */
-    }
-    late = stores;
-    for (int i = 0; i < F.width; i++) lo[(size_t) (L % FLOW_NBUF)*F.width + i] = cur[i];
-  }
-  for (auto & st : late) up[st.first] = st.second;
-  for (int p = 0; p < F.npos; p++) ucells[F.h_gidx[p]] = up[p];
-  return hazards;
-}

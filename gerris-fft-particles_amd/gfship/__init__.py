@@ -222,6 +222,7 @@ SIGNATURES = {
     "gfship_tree_divergence": (_i, [_vp]),
     "gfship_tree_host_check": (_i, [_i, C.c_void_p, _vp, _pi, _u, C.POINTER(C.c_longlong)]),
     "gfship_tree_host_check_diffusion": (_i, [_i, C.c_void_p, _vp, _pi, _u, _d, C.POINTER(C.c_longlong)]),
+    "gfship_tree_host_plan_digest": (_i, [_i, C.c_void_p, _vp, _pi, _u, C.POINTER(C.c_ulonglong)]),
     "gfship_tree_interpolate": (_i, [_vp, _i, _i, _pd, _pd, C.POINTER(C.c_ubyte)]),
     "gfship_tree_sampler_stats": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "gfship_particles_create_tree": (_i, [C.POINTER(_vp), _vp, _i, _pd, C.POINTER(C.c_uint)]),
@@ -1148,6 +1149,19 @@ def tree_host_check_diffusion(refine, w, dim=3, sides=None, nrelax=4):
     stats = (C.c_longlong * 6)()
     _check(lib().gfship_tree_host_check_diffusion(dim, C.cast(cb, C.c_void_p), None, arr, nrelax, float(w), stats))
     return tuple(stats)
+
+
+def tree_host_plan_digest(refine, dim=2, sides=None, nrelax=4):
+    """gfship_tree_host_plan_digest: FNV-1a-64 digests of (topology, sweep plans, loop plans, flow plans, face sets)
+    as a device tree of these arguments would upload them (no device needed)"""
+    if dim == 2:
+        cb = REFINE_FN(lambda x, y, z, ctx: float(refine(x, y)))
+    else:
+        cb = REFINE_FN(lambda x, y, z, ctx: float(refine(x, y, z)))
+    arr = (C.c_int * 6)(*(list(sides) + [0] * 6)[:6]) if sides is not None else None
+    out = (C.c_ulonglong * 5)()
+    _check(lib().gfship_tree_host_plan_digest(dim, C.cast(cb, C.c_void_p), None, arr, nrelax, out))
+    return tuple(out)
 
 
 class Tree:

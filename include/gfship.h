@@ -915,9 +915,9 @@ int  gfship_halo_unpack_sides (gfship_domain * dom, void * dev_ptr, int level, i
    src/advection.c:183-249): Euler equations, centred gradients, alpha = NULL, all sides periodic,
    refinement equal across each periodic pair (else GFSHIP_EUNSUPPORTED).  Results are those of the
    reference's traversal orders: the sweeps of gfs_relax run in tree order, the face loops accumulate
-   in face-traversal order.  gfship_tree_host_check is not reentrant (it switches the library into a
-   host-only mode while it runs); everything else follows the threading rule of the rest of the ABI:
-   one thread per tree. */
+   in face-traversal order.  The host checks (gfship_tree_host_check ...) touch no device and no shared
+   state: they may run on any thread at any time; everything else follows the threading rule of the rest
+   of the ABI: one thread per tree. */
 typedef struct gfship_tree gfship_tree;
 typedef double (* gfship_refine_fn) (double x, double y, double z, void * ctx);
 enum { GFSHIP_TREE_P = 0, GFSHIP_TREE_PMAC, GFSHIP_TREE_U, GFSHIP_TREE_V, GFSHIP_TREE_GX, GFSHIP_TREE_GY,
@@ -1039,6 +1039,13 @@ int  gfship_tree_host_check (int dim, gfship_refine_fn refine, void * ctx, const
    valid plans, [4] = hazards of the flow plans, [5] = levels without a flow plan */
 int  gfship_tree_host_check_diffusion (int dim, gfship_refine_fn refine, void * ctx, const int * side,
 				       unsigned nrelax, double w, long long stats[6]);
+/* lab: FNV-1a-64 digests of every array a device tree of these arguments uploads (the members of each element, no
+   padding; each array preceded by its length as 64 bits), with the GFSHIP_* switches of the moment: out[0] the
+   flags, the tables and the lists of leaves, non-leaf cells and ghost leaves; [1] the sweep plans of all levels;
+   [2] their loop plans for nrelax sweeps with the homogeneous conditions of P; [3] the flow plans of those (an
+   absent one hashed as such); [4] the face sets.  Needs no device */
+int  gfship_tree_host_plan_digest (int dim, gfship_refine_fn refine, void * ctx, const int * side,
+				   unsigned nrelax, unsigned long long out[5]);
 /* diagnostics: the cells of the sweep of gfs_relax on `level' (the cells of the level and the
    coarser leaves) and the number of dependency levels its tree order leaves on the device */
 int  gfship_tree_sweep_levels (const gfship_tree * tree, int level, int * ncells, int * nlevels);

@@ -629,3 +629,83 @@ def test_poiseuille_channel_on_a_refined_tree_bit_exact():
         _same_leaves(o, g, [(G.U, T.U), (G.V, T.V), (G.P, T.P)], "step %d" % k)
     o.destroy()
     g.destroy()
+
+
+# ---- the host checks share nothing with the device trees of the process (csrc/tree_plan.hip: no host-only mode)
+
+def _every_variable(g):
+    """every variable of the C ABI on every level, ghost cells and non-leaf cells included, as bytes"""
+    return [g.download(v, l).tobytes() for v in range(gfship.Tree.BCW + 1) for l in range(g.depth + 1)]
+
+
+def _two_steps(pair, same):
+    o, g = pair()
+    o.start()
+    g.start()
+    for k in range(2):
+        o.step()
+        g.step()
+        assert g.t == o.t and g.dt == o.dt, k
+    same(o, g)
+    return o, g
+
+
+def _host_check_between(pair, same, check):
+    """a tree, two steps; host checks of another tree; the same tree again, two steps: the second tree holds what the
+    first holds, bit for bit, and both hold what the oracle holds"""
+    o1, g1 = _two_steps(pair, same)
+    first = _every_variable(g1)
+    check()
+    o2, g2 = _two_steps(pair, same)
+    assert _every_variable(g2) == first
+    assert _every_variable(g1) == first      # the first tree is still whole
+    for s in (o1, g1, o2, g2):
+        s.destroy()
+
+
+def _host_checks_of(refine, dim):
+    def check():
+        updates, _, levels, differ = gfship.tree_host_check(refine, dim=dim)
+        assert updates > 0 and levels > 0 and differ == 0
+        stats = gfship.tree_host_check_diffusion(refine, 0.37, dim=dim)
+        assert stats[0] > 0 and stats[3] == 0 and stats[4] == 0 and stats[5] == 0
+    return check
+
+
+def test_host_check_between_device_trees():
+    octree = lambda x, y, z: 3 if max(abs(x), abs(y), abs(z)) <= 0.25 else 2
+    _host_check_between(lambda: periodic_pair(4, 1), lambda o, g: assert_same_leaves(o, g, "step 2"),
+                        _host_checks_of(octree, 3))
+
+
+def test_host_check_between_viscous_octrees_with_walls():
+    """an octree 2/3 with six GfsBoundary sides, a lid, implicit viscosity and ten sweeps on the first level of the
+    diffusion cycle: the loop plans with the homogeneous conditions of U, V, W"""
+    refine = lambda x, y, z: 3 if max(abs(x), abs(y), abs(z)) > 0.3 else 2
+    sides = [gfship.SIDE_BOUNDARY] * 6
+    T, G = O.Tree, gfship.Tree
+
+    def pair():
+        o = O.Tree(refine=refine, dim=3, sides=sides)
+        g = gfship.Tree(refine, dim=3, sides=sides)
+        for c in range(3):
+            for d in range(6):
+                o.set_bc_u(c, d, O.BC_DIRICHLET, 1. if (c == 0 and d == 2) else 0.)
+            for s in (o, g):
+                s.set_viscosity(c, 2e-3)
+                s.diffusion_params(c).nrelax = 1
+            vals = _bc_values(o, c, None)
+            for d in range(6):
+                g.set_bc_u(c, d, gfship.BC_DIRICHLET, vals)
+        o.set_time(300., 0.8)
+        g.set_time(300., 0.8)
+        return o, g
+
+    def same(o, g):
+        _same_leaves(o, g, [(G.U, T.U), (G.V, T.V), (G.W, T.W), (G.P, T.P), (G.PMAC, T.PMAC)], "step 2")
+        for c in range(3):
+            pg, po = g.diffusion_params(c), o.diffusion_params(c)
+            assert pg.niter == po.niter and pg.residual.infty == po.residual.infty, c
+        assert max(o.diffusion_params(c).niter for c in range(3)) >= 1
+
+    _host_check_between(pair, same, _host_checks_of(lambda x, y: 5 if max(abs(x), abs(y)) <= 0.25 else 4, 2))

@@ -1,9 +1,9 @@
-"""Host logic of the refined-tree path (csrc/tree.hip) without a device: gfship_tree_host_check builds
+"""Host logic of the refined-tree path (csrc/tree_plan.hip) without a device: gfship_tree_host_check builds
 the tree, the lists, the dependency levels, the compiled stencils and the plans of the relax loops on
 the host and runs every relax loop three ways there -- the reference's program through the stencil
 code that walks the tree (ghost copies, cells in tree order, sweep after sweep), the compiled stencils
 by dependency level with every level BACKWARDS, the plan of the whole loop with every level backwards,
-the flow plan (csrc/tree_flow.hpp: fixed-format micro-operations, results forwarded through a ring of
+the flow plan (csrc/tree_flow.hpp, csrc/tree_flow_ops.hpp: fixed-format micro-operations, results forwarded through a ring of
 buffers, old values loaded a level ahead, stores a level late, the branch-free arithmetic wherever the 64
 operations of a wavefront are of one kind) with the kernel's timing of loads and stores -- and counts the
 values that differ (bit for bit) plus the hazards of the flow plan (a load that a store of the levels

@@ -34,7 +34,7 @@ def test_the_sums_of_the_coefficients_round_on_the_way():
 
 
 def test_four_equal_addends_sum_exactly():
-    """what diffusion_weights_exact (csrc/tree.hip) rests on: 0 + x + x + x + x is 4 x for every x"""
+    """what diffusion_weights_exact (csrc/tree_plan.hip) rests on: 0 + x + x + x + x is 4 x for every x"""
     import random
     rnd = random.Random(7)
     for _ in range(100000):
