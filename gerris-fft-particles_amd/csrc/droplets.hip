@@ -27,8 +27,10 @@
 //   6. the droplets are the candidates of launch_feed_ids (feed_particle.hip), in tag order: n slots after those
 //      in use, cell = PSOURCE_NO_CELL for a droplet that does not convert.
 //   7. the reset of the variable on the leaves, then its ghosts by its boundary conditions.
+// Steps 1c to 7 and the union-find itself are in droplets.hpp, templated on a geometry: the refined trees
+// (tree_droplets.hip) label differently and share the rest.
 #include "particle_events.hpp"
-#include <hipcub/hipcub.hpp>
+#include "droplets.hpp"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -37,9 +39,6 @@
 
 namespace gfship {
 
-constexpr unsigned DROP_NONE = 0xFFFFFFFFu;
-constexpr int DROP_BLOCK = 256;
-constexpr double DROP_THRESHOLD = 1e-4;        /* src/domain.c:3564 */
 constexpr int DROP_TILE_BITS_2D = 4, DROP_TILE_BITS_3D = 3;
 
 struct DropGeom {
@@ -47,21 +46,6 @@ struct DropGeom {
   int depth, n, tb;      // levels, cells per side, log2 of the side of a tile
   unsigned N;            // cells
   int per[3];            // both sides of the direction are periodic
-};
-
-// the work arrays of the labelling, kept by the domain between calls
-struct DropWork {
-  unsigned * parent = nullptr, * rank = nullptr, * tagi = nullptr;      // per cell, by traversal index
-  size_t ncap = 0;
-  // per droplet
-  unsigned * sizes = nullptr, * last = nullptr, * segsize = nullptr, * seg = nullptr, * cursor = nullptr,
-    * sorted = nullptr, * cell = nullptr, * block = nullptr;
-  size_t dcap = 0;
-  unsigned long long * key = nullptr, * key2 = nullptr;                 // per counted leaf of a droplet that converts
-  size_t kcap = 0;
-  void * tmp = nullptr;                                                 // of hipCUB
-  size_t tmp_bytes = 0;
-  unsigned * counters = nullptr;     // n, the size that min < 0 selects, particles made, cells reset
 };
 
 template <int DIM>
@@ -106,31 +90,44 @@ __device__ __forceinline__ bool drop_on_side (const DropGeom & G, const int x[3]
   return side;
 }
 
-// the root of x in p (LDS or global): parents only decrease, and a parent read late is still an ancestor.  The loads
-// are relaxed agent-scope atomic loads through a generic pointer (flat atomics, on LDS too): they bypass the L1 of
-// the CU on the global array, and the compiler may not keep a parent in a register while other threads lower it
-__device__ __forceinline__ unsigned drop_find (unsigned * p, unsigned x)
-{
-  unsigned q;
-  while ((q = __hip_atomic_load (&p[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != x)
-    x = q;
-  return x;
-}
-
-// join the regions of a and b: the larger root takes the smaller as its parent.  Lock-free: a thread whose
-// atomicMin finds the root already moved goes on with where it moved to
-__device__ __forceinline__ void drop_union (unsigned * p, unsigned a, unsigned b)
-{
-  for (;;) {
-    a = drop_find (p, a);
-    b = drop_find (p, b);
-    if (a == b) return;
-    if (a < b) { const unsigned s = a; a = b; b = s; }
-    const unsigned old = atomicMin (&p[a], b);
-    if (old == a) return;
-    a = old;
+// the leaves of the box as the geometry of droplets.hpp
+template <int DIM>
+struct BoxDrops {
+  DropGeom G;
+  unsigned N;
+  __device__ __forceinline__ long index (unsigned t) const {
+    int x[3];
+    drop_decode<DIM> (G.depth, t, x);
+    return drop_index<DIM> (G, x);
   }
-}
+  __device__ __forceinline__ bool on_side (unsigned t) const {
+    int x[3];
+    drop_decode<DIM> (G.depth, t, x);
+    return drop_on_side<DIM> (G, x);
+  }
+  __device__ __forceinline__ double volume (unsigned) const {
+    const double h = 1./(double) G.n;
+    return DIM == 3 ? h*h*h : h*h;      /* pow (h, FTT_DIMENSION): powers of two */
+  }
+  __device__ __forceinline__ void pos (unsigned t, double p[3]) const {
+    int x[3];
+    drop_decode<DIM> (G.depth, t, x);
+    const int ix[3] = { x[0], G.n - 1 - x[1], G.n - 1 - x[2] };
+    const double h = 1./(double) G.n;
+    p[2] = 0.;
+#pragma unroll
+    for (int a = 0; a < DIM; a++)
+      p[a] = -0.5 + (ix[a] + 0.5)*h;      /* ftt_cell_pos: dyadic, exact */
+  }
+  __device__ __forceinline__ bool locate (const double p[3], unsigned & cell, long & at) const {
+    int c[3];
+    if (!gfship::locate<DIM> (G.depth, p, c)) return false;
+    const unsigned n = (unsigned) G.n;
+    cell = (unsigned) (c[0] - 1) + n*((unsigned) (c[1] - 1) + (DIM == 3 ? n*(unsigned) (c[2] - 1) : 0u));
+    at = G.L.idx (c[0], c[1], c[2]);
+    return true;
+  }
+};
 
 // 1a. the labels of one tile, in LDS.  c: the variable (a field), or fv: the values of the function by traversal index
 template <int DIM>
@@ -210,196 +207,6 @@ drop_border_kernel (DropGeom G, unsigned long long count, unsigned * __restrict_
   drop_union (parent, t1, t2);
 }
 
-// 1c. every cell takes its root; flag = the cell is a root
-__global__ void __launch_bounds__(DROP_BLOCK)
-drop_flatten_kernel (unsigned N, unsigned * __restrict__ parent, unsigned * __restrict__ flag)
-{
-  const unsigned t = blockIdx.x*(unsigned) DROP_BLOCK + threadIdx.x;
-  if (t >= N) return;
-  unsigned p = parent[t];
-  if (p != DROP_NONE) {
-    p = drop_find (parent, t);
-    /* a root keeps itself; any other cell moves to an ancestor: the finds of others stay right */
-    __hip_atomic_store (&parent[t], p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  flag[t] = p == t ? 1u : 0u;
-}
-
-__global__ void drop_count_kernel (unsigned N, const unsigned * __restrict__ rank, const unsigned * __restrict__ flag,
-				   unsigned * __restrict__ counters)
-{
-  counters[0] = rank[N - 1] + flag[N - 1];
-  counters[1] = counters[2] = counters[3] = 0u;
-}
-
-// 2 and 3. tag = 1 + the rank of the root (0 outside), into tagi and, as a double, into the field tagf; the size of
-// every droplet -- all its leaves (compute_droplet_size, src/domain.c:3805-3810), or those that touch no side
-// (compute_droplet_properties) -- and its last leaf
-template <int DIM>
-__global__ void __launch_bounds__(DROP_BLOCK)
-drop_tag_kernel (DropGeom G, const unsigned * __restrict__ parent, const unsigned * __restrict__ rank,
-		 unsigned * __restrict__ tagi, double * __restrict__ tagf, unsigned * __restrict__ sizes,
-		 unsigned * __restrict__ last, int all)
-{
-  const unsigned t = blockIdx.x*(unsigned) DROP_BLOCK + threadIdx.x;
-  const bool valid = t < G.N;
-  unsigned tag = 0u;
-  bool counted = false;
-  if (valid) {
-    const unsigned p = parent[t];
-    tag = p == DROP_NONE ? 0u : 1u + rank[p];
-    tagi[t] = tag;
-    int x[3];
-    drop_decode<DIM> (G.depth, t, x);
-    if (tagf) tagf[drop_index<DIM> (G, x)] = (double) tag;
-    counted = tag && (all || !drop_on_side<DIM> (G, x));
-  }
-  if (!sizes) return;
-  /* the lanes of a wave that share a tag add once (a wave is 64 consecutive traversal indices: mostly one droplet),
-     so that a large droplet is not one atomic per cell on one address; the sums are integers: any grouping gives
-     the same result */
-  const int lane = threadIdx.x & 63;
-  bool pending = tag != 0u;
-  unsigned long long todo = __ballot (pending);
-  while (todo) {
-    const int lead = __ffsll ((long long) todo) - 1;
-    const unsigned ltag = (unsigned) __shfl ((int) tag, lead, 64);
-    const bool mine = pending && tag == ltag;
-    const unsigned long long m = __ballot (mine), mc = __ballot (mine && counted);
-    if (lane == lead) {
-      if (mc) atomicAdd (&sizes[ltag - 1], (unsigned) __popcll (mc));
-      atomicMax (&last[ltag - 1], t - (unsigned) lane + (unsigned) (63 - __clzll ((long long) m)));
-    }
-    pending = pending && !mine;
-    todo &= ~m;
-  }
-}
-
-// convert_droplets, :1323-1325: which droplets convert, and the length of their segment of keys
-template <int DIM>
-__global__ void __launch_bounds__(DROP_BLOCK)
-drop_candidate_kernel (DropGeom G, unsigned n, unsigned min, const unsigned * __restrict__ sizes,
-		       const unsigned * __restrict__ last, unsigned * __restrict__ segsize,
-		       unsigned * __restrict__ cursor)
-{
-  const unsigned i = blockIdx.x*(unsigned) DROP_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  int x[3];
-  drop_decode<DIM> (G.depth, last[i], x);
-  const unsigned s = sizes[i];
-  segsize[i] = !drop_on_side<DIM> (G, x) && s < min && s > 1u ? s : 0u;
-  cursor[i] = 0u;
-}
-
-// 5. the keys of the counted leaves of the droplets that convert, anywhere in the segment of their droplet: the sort
-// puts them in traversal order
-template <int DIM>
-__global__ void __launch_bounds__(DROP_BLOCK)
-drop_keys_kernel (DropGeom G, const unsigned * __restrict__ tagi, const unsigned * __restrict__ segsize,
-		  const unsigned * __restrict__ seg, unsigned * __restrict__ cursor, unsigned long long cap,
-		  unsigned long long * __restrict__ key)
-{
-  const unsigned t = blockIdx.x*(unsigned) DROP_BLOCK + threadIdx.x;
-  if (t >= G.N) return;
-  const unsigned tag = tagi[t];
-  if (!tag || !segsize[tag - 1]) return;
-  int x[3];
-  drop_decode<DIM> (G.depth, t, x);
-  if (drop_on_side<DIM> (G, x)) return;
-  const unsigned long long slot = (unsigned long long) seg[tag - 1] + atomicAdd (&cursor[tag - 1], 1u);
-  if (slot < cap) key[slot] = (unsigned long long) (tag - 1) << 32 | t;
-}
-
-struct DropConvertArgs {
-  DropGeom G;
-  unsigned n;
-  int base;
-  const unsigned * sizes, * segsize, * seg;
-  const unsigned long long * key;
-  const double * c, * u[3], * alpha;
-  double * pos[3], * old[3], * vel[3], * force[3], * mass, * volume;
-  unsigned * orig, * cell;
-};
-
-// 5 and 6. compute_droplet_properties (:1214-1228) over the leaves of a droplet in traversal order, then
-// convert_droplets (:1326-1338) up to add_particulate: one droplet per thread, one slot of the list per droplet
-template <int DIM>
-__global__ void __launch_bounds__(DROP_BLOCK)
-drop_convert_kernel (DropConvertArgs A)
-{
-  const unsigned i = blockIdx.x*(unsigned) DROP_BLOCK + threadIdx.x;
-  if (i >= A.n) return;
-  const int s = A.base + (int) i;
-  double pos[3] = { 0., 0., 0. }, vel[3] = { 0., 0., 0. }, volume = 0., mass = 0.;
-  unsigned cell = PSOURCE_NO_CELL;
-  const unsigned size = A.segsize[i];
-  if (size) {
-    const double h = 1./(double) A.G.n, vol = DIM == 3 ? h*h*h : h*h;      /* pow (h, FTT_DIMENSION): powers of two */
-    const unsigned long long * key = A.key + A.seg[i];
-    for (unsigned q = 0; q < size; q++) {
-      int x[3];
-      drop_decode<DIM> (A.G.depth, (unsigned) key[q], x);
-      const long idx = drop_index<DIM> (A.G, x);
-      const int ix[3] = { x[0], A.G.n - 1 - x[1], A.G.n - 1 - x[2] };
-      volume += vol*A.c[idx];
-#pragma unroll
-      for (int a = 0; a < DIM; a++) {
-	pos[a] += -0.5 + (ix[a] + 0.5)*h;      /* ftt_cell_pos: dyadic, exact */
-	vel[a] += A.u[a][idx];
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < DIM; a++) {
-      pos[a] = pos[a]/(double) A.sizes[i];
-      vel[a] = vel[a]/(double) A.sizes[i];
-    }
-    int c[3];
-    if (locate<DIM> (A.G.depth, pos, c)) {
-      const unsigned n = (unsigned) A.G.n;
-      cell = (unsigned) (c[0] - 1) + n*((unsigned) (c[1] - 1) + (DIM == 3 ? n*(unsigned) (c[2] - 1) : 0u));
-      mass = A.alpha ? 1./A.alpha[A.G.L.idx (c[0], c[1], c[2])] : 1.;
-      mass *= volume;
-    }
-    else
-      volume = 0.;
-  }
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    A.pos[a][s] = pos[a];
-    A.old[a][s] = 0.;
-    A.force[a][s] = 0.;
-    A.vel[a][s] = vel[a];
-  }
-  A.orig[s] = (unsigned) s;
-  A.mass[s] = mass;
-  A.volume[s] = volume;
-  A.cell[i] = cell;
-}
-
-// the particles the ordered passes of feed_particle.hip made of the n slots
-__global__ void __launch_bounds__(DROP_BLOCK)
-drop_made_kernel (unsigned n, const unsigned char * __restrict__ alive, unsigned * __restrict__ counters)
-{
-  const unsigned i = blockIdx.x*(unsigned) DROP_BLOCK + threadIdx.x;
-  if (i < n && alive[i]) atomicAdd (&counters[2], 1u);
-}
-
-// 7. reset_small_fraction (:1187-1192, src/domain.c:3812-3817): v = val on the leaves of every droplet smaller than min
-template <int DIM>
-__global__ void __launch_bounds__(DROP_BLOCK)
-drop_reset_kernel (DropGeom G, const unsigned * __restrict__ tagi, const unsigned * __restrict__ sizes,
-		   unsigned min, double val, double * __restrict__ v, unsigned * __restrict__ counters)
-{
-  const unsigned t = blockIdx.x*(unsigned) DROP_BLOCK + threadIdx.x;
-  if (t >= G.N) return;
-  const unsigned tag = tagi[t];
-  if (!tag || !(sizes[tag - 1] < min)) return;
-  int x[3];
-  drop_decode<DIM> (G.depth, t, x);
-  v[drop_index<DIM> (G, x)] = val;
-  atomicAdd (&counters[3], 1u);
-}
-
 // the linear number (rtc_launch_cell) of the cell of every traversal index
 template <int DIM>
 __global__ void __launch_bounds__(DROP_BLOCK)
@@ -426,100 +233,32 @@ static DropGeom drop_geom (const gfship_domain * dom)
   return G;
 }
 
-static inline unsigned drop_grid (unsigned long long n) { return (unsigned) ((n + DROP_BLOCK - 1)/DROP_BLOCK); }
-
-template <class T> static int drop_grow (T ** p, size_t count)
-{
-  if (*p) (void) hipFree (*p);
-  *p = nullptr;
-  GFSHIP_HIP (hipMalloc ((void **) p, count*sizeof (T)));
-  return GFSHIP_OK;
-}
+// the box as the host mesh of droplets.hpp
+struct BoxDropMesh {
+  DropGeom G;
+  int dim;
+  hipStream_t stream;
+  unsigned N;
+  explicit BoxDropMesh (const gfship_domain * dom) : G (drop_geom (dom)), dim (dom->dim), stream (dom->stream), N (G.N) {}
+  template <int DIM> BoxDrops<DIM> geom () const { return BoxDrops<DIM> { G, G.N }; }
+};
 
 static int drop_work (gfship_domain * dom, DropWork ** out)
 {
   if (!dom->droplets) {
-    DropWork * W = new DropWork;
-    hipError_t e = hipMalloc ((void **) &W->counters, 4*sizeof (unsigned));
-    if (e != hipSuccess) {
-      delete W;
-      GFSHIP_HIP (e);
-    }
+    DropWork * W;
+    int r = drop_work_new (&W);
+    if (r) return r;
     dom->droplets = W;
   }
   *out = (DropWork *) dom->droplets;
   return GFSHIP_OK;
 }
 
-static int drop_reserve_cells (gfship_domain * dom, DropWork * W, size_t N)
-{
-  if (W->ncap >= N) return GFSHIP_OK;
-  GFSHIP_HIP (hipStreamSynchronize (dom->stream));
-  W->ncap = 0;
-  int r;
-  if ((r = drop_grow (&W->parent, N)) || (r = drop_grow (&W->rank, N)) || (r = drop_grow (&W->tagi, N))) return r;
-  W->ncap = N;
-  return GFSHIP_OK;
-}
-
-static int drop_reserve_droplets (gfship_domain * dom, DropWork * W, size_t n)
-{
-  if (W->dcap >= n) return GFSHIP_OK;
-  GFSHIP_HIP (hipStreamSynchronize (dom->stream));
-  W->dcap = 0;
-  int r;
-  unsigned ** a[] = { &W->sizes, &W->last, &W->segsize, &W->seg, &W->cursor, &W->sorted, &W->cell };
-  for (unsigned ** p : a)
-    if ((r = drop_grow (p, n))) return r;
-  if ((r = drop_grow (&W->block, (n + 255)/256))) return r;
-  W->dcap = n;
-  return GFSHIP_OK;
-}
-
-static int drop_reserve_keys (gfship_domain * dom, DropWork * W, size_t n)
-{
-  if (W->kcap >= n) return GFSHIP_OK;
-  GFSHIP_HIP (hipStreamSynchronize (dom->stream));
-  W->kcap = 0;
-  int r;
-  if ((r = drop_grow (&W->key, n)) || (r = drop_grow (&W->key2, n))) return r;
-  W->kcap = n;
-  return GFSHIP_OK;
-}
-
-static int drop_reserve_tmp (gfship_domain * dom, DropWork * W, size_t bytes)
-{
-  if (W->tmp_bytes >= bytes) return GFSHIP_OK;
-  GFSHIP_HIP (hipStreamSynchronize (dom->stream));
-  if (W->tmp) (void) hipFree (W->tmp);
-  W->tmp = nullptr;
-  W->tmp_bytes = 0;
-  GFSHIP_HIP (hipMalloc (&W->tmp, bytes));
-  W->tmp_bytes = bytes;
-  return GFSHIP_OK;
-}
-
 void droplets_free (gfship_domain * dom)
 {
-  DropWork * W = (DropWork *) dom->droplets;
-  if (!W) return;
-  void * a[] = { W->parent, W->rank, W->tagi, W->sizes, W->last, W->segsize, W->seg, W->cursor, W->sorted, W->cell,
-		 W->block, W->key, W->key2, W->tmp, W->counters };
-  for (void * p : a)
-    if (p) (void) hipFree (p);
-  delete W;
+  drop_work_free ((DropWork *) dom->droplets);
   dom->droplets = nullptr;
-}
-
-static int drop_scan (gfship_domain * dom, DropWork * W, const unsigned * in, unsigned * out, size_t count)
-{
-  size_t need = 0;
-  int r;
-  GFSHIP_HIP (hipcub::DeviceScan::ExclusiveSum (nullptr, need, in, out, count, dom->stream));
-  if ((r = drop_reserve_tmp (dom, W, need))) return r;
-  size_t bytes = W->tmp_bytes;
-  GFSHIP_HIP (hipcub::DeviceScan::ExclusiveSum (W->tmp, bytes, in, out, count, dom->stream));
-  return GFSHIP_OK;
 }
 
 // what the labelling refuses
@@ -539,7 +278,7 @@ static int drop_labels (gfship_domain * dom, DropWork * W, const DropGeom & G, c
 			unsigned * n)
 {
   int r;
-  if ((r = drop_reserve_cells (dom, W, G.N))) return r;
+  if ((r = drop_reserve_cells (dom->stream, W, G.N))) return r;
   const unsigned ns = (unsigned) G.n >> G.tb;
   const unsigned long long plane = dom->dim == 3 ? (unsigned long long) G.n*G.n : (unsigned long long) G.n;
   const unsigned long long border = (unsigned long long) dom->dim*ns*plane;
@@ -550,66 +289,16 @@ static int drop_labels (gfship_domain * dom, DropWork * W, const DropGeom & G, c
     hipLaunchKernelGGL (drop_border_kernel<DIM>, dim3 (drop_grid (border)), dim3 (DROP_BLOCK), 0, dom->stream, G,
 			border, W->parent);
   }, dom->dim == 3);
-  hipLaunchKernelGGL (drop_flatten_kernel, dim3 (drop_grid (G.N)), dim3 (DROP_BLOCK), 0, dom->stream, G.N, W->parent,
-		      W->tagi);
   GFSHIP_HIP (hipGetLastError ());
-  if ((r = drop_scan (dom, W, W->tagi, W->rank, G.N))) return r;
-  hipLaunchKernelGGL (drop_count_kernel, dim3 (1), dim3 (1), 0, dom->stream, G.N, W->rank, W->tagi, W->counters);
-  GFSHIP_HIP (hipGetLastError ());
-  GFSHIP_HIP (hipMemcpyAsync (n, W->counters, sizeof (unsigned), hipMemcpyDeviceToHost, dom->stream));
-  GFSHIP_HIP (hipStreamSynchronize (dom->stream));
-  return GFSHIP_OK;
-}
-
-// steps 2 and 3: the tags (into tagf too where given) and, with sizes, the size and the last leaf of the n droplets
-static int drop_tags (gfship_domain * dom, DropWork * W, const DropGeom & G, double * tagf, unsigned n, bool sizes,
-		      bool all)
-{
-  int r;
-  if (sizes) {
-    if ((r = drop_reserve_droplets (dom, W, n))) return r;
-    GFSHIP_HIP (hipMemsetAsync (W->sizes, 0, n*sizeof (unsigned), dom->stream));
-    GFSHIP_HIP (hipMemsetAsync (W->last, 0, n*sizeof (unsigned), dom->stream));
-  }
-  with_bools ([&] (auto D3) {
-    constexpr int DIM = decltype (D3)::value ? 3 : 2;
-    hipLaunchKernelGGL (drop_tag_kernel<DIM>, dim3 (drop_grid (G.N)), dim3 (DROP_BLOCK), 0, dom->stream, G, W->parent,
-			W->rank, W->tagi, tagf, sizes ? W->sizes : nullptr, W->last, all ? 1 : 0);
-  }, dom->dim == 3);
-  GFSHIP_HIP (hipGetLastError ());
-  return GFSHIP_OK;
-}
-
-// step 4 (convert_droplets, :1311-1321; src/domain.c:3863-3872): min itself, or the (-1 - min)-th largest size
-static int drop_min (gfship_domain * dom, DropWork * W, unsigned n, int min, unsigned * out)
-{
-  if (min >= 0) {
-    *out = (unsigned) min;
-    return GFSHIP_OK;
-  }
-  size_t need = 0;
-  int r;
-  GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeysDescending (nullptr, need, W->sizes, W->sorted, n, 0, 32, dom->stream));
-  if ((r = drop_reserve_tmp (dom, W, need))) return r;
-  size_t bytes = W->tmp_bytes;
-  GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeysDescending (W->tmp, bytes, W->sizes, W->sorted, n, 0, 32, dom->stream));
-  GFSHIP_HIP (hipMemcpyAsync (out, W->sorted + (size_t) (-1 - min), sizeof (unsigned), hipMemcpyDeviceToHost,
-			      dom->stream));
-  GFSHIP_HIP (hipStreamSynchronize (dom->stream));
-  return GFSHIP_OK;
+  return drop_ranks (dom->stream, W, G.N, n);
 }
 
 // step 7, on the leaves of the field and then on its ghosts
-static int drop_reset (gfship_domain * dom, DropWork * W, const DropGeom & G, Field * V, unsigned min, double val)
+static int drop_reset (gfship_domain * dom, DropWork * W, const BoxDropMesh & M, Field * V, unsigned min, double val)
 {
   int r;
   if ((r = coarse_flush (dom, V, dom->depth, true))) return r;
-  with_bools ([&] (auto D3) {
-    constexpr int DIM = decltype (D3)::value ? 3 : 2;
-    hipLaunchKernelGGL (drop_reset_kernel<DIM>, dim3 (drop_grid (G.N)), dim3 (DROP_BLOCK), 0, dom->stream, G, W->tagi,
-			W->sizes, min, val, V->lev[dom->depth], W->counters);
-  }, dom->dim == 3);
-  GFSHIP_HIP (hipGetLastError ());
+  if ((r = drop_reset_leaves (M, W, V->lev[dom->depth], min, val))) return r;
   V->zero[dom->depth] = false;
   return launch_bc (dom, V, V, dom->depth, 0);
 }
@@ -617,22 +306,6 @@ static int drop_reset (gfship_domain * dom, DropWork * W, const DropGeom & G, Fi
 } // namespace gfship
 
 using namespace gfship;
-
-// a GfsDropletToParticle on a list of particulates of a box
-struct gfship_droplet_to_particle {
-  gfship_particles * pl = nullptr;
-  gfship_field c = -1;
-  int min = 0;
-  double reset = 0., density = 0.;
-  // the mask: the variable c, the variable the function names, or the values of the function by traversal index
-  gfship_field mask = -1;
-  gfship::RtcKernel * fn = nullptr;
-  bool constant = false;
-  double value = 0.;
-  std::vector<gfship_field> read;
-  double * fv = nullptr;
-  unsigned * cells = nullptr;
-};
 
 extern "C" {
 
@@ -648,9 +321,9 @@ int gfship_tag_droplets (gfship_domain * dom, gfship_field c, gfship_field tag, 
   if ((r = coarse_flush (dom, T, dom->depth, true))) return r;
   DropWork * W;
   if ((r = drop_work (dom, &W))) return r;
-  const DropGeom G = drop_geom (dom);
-  if ((r = drop_labels (dom, W, G, C->lev[dom->depth], nullptr, n))) return r;
-  if ((r = drop_tags (dom, W, G, T->lev[dom->depth], *n, false, false))) return r;
+  const BoxDropMesh M (dom);
+  if ((r = drop_labels (dom, W, M.G, C->lev[dom->depth], nullptr, n))) return r;
+  if ((r = drop_tags (M, W, T->lev[dom->depth], *n, false, false))) return r;
   T->zero[dom->depth] = false;
   return GFSHIP_OK;
 }
@@ -682,13 +355,13 @@ int gfship_remove_droplets (gfship_domain * dom, gfship_field c, gfship_field v,
   if ((r = before_write (dom))) return r;
   DropWork * W;
   if ((r = drop_work (dom, &W))) return r;
-  const DropGeom G = drop_geom (dom);
+  const BoxDropMesh M (dom);
   unsigned n = 0, umin = 0;
-  if ((r = drop_labels (dom, W, G, C->lev[dom->depth], nullptr, &n))) return r;
+  if ((r = drop_labels (dom, W, M.G, C->lev[dom->depth], nullptr, &n))) return r;
   if (!(n > 0 && -(long) min < (long) n)) return GFSHIP_OK;      /* src/domain.c:3851 */
-  if ((r = drop_tags (dom, W, G, nullptr, n, true, true))) return r;
-  if ((r = drop_min (dom, W, n, min, &umin))) return r;
-  return drop_reset (dom, W, G, V, umin, val);
+  if ((r = drop_tags (M, W, nullptr, n, true, true))) return r;
+  if ((r = drop_min (dom->stream, W, n, min, &umin))) return r;
+  return drop_reset (dom, W, M, V, umin, val);
 }
 
 int gfship_droplet_to_particle_create (gfship_droplet_to_particle ** out, gfship_particles * pl, gfship_field c,
@@ -755,6 +428,7 @@ int gfship_droplet_to_particle_event (gfship_droplet_to_particle * d, gfship_dro
   GFSHIP_CHECK (d != nullptr, GFSHIP_EINVAL, "null GfsDropletToParticle");
   if (info) info->n = info->min = info->converted = info->reset = 0u;
   gfship_particles * pl = d->pl;
+  if (pl && pl->tree) return tree_droplet_event (d, info);      /* a handle of gfship_tree_droplet_to_particle_create */
   int r = feed_check (pl, "GfsDropletToParticle");
   if (r) return r;
   gfship_domain * dom = pl->dom;
@@ -768,14 +442,15 @@ int gfship_droplet_to_particle_event (gfship_droplet_to_particle * d, gfship_dro
   if (!C) return GFSHIP_EINVAL;
   DropWork * W;
   if ((r = drop_work (dom, &W))) return r;
-  const DropGeom G = drop_geom (dom);
+  const BoxDropMesh M (dom);
+  const DropGeom & G = M.G;
   const Layout & L = dom->lay[dom->depth];
   /* the mask (gfs_droplet_to_particle_event, :1368-1393) */
   const double * mask = nullptr;
   if (d->mask >= 0) {
-    Field * M = get_field (dom, d->mask);
-    if (!M) return GFSHIP_EINVAL;
-    mask = M->lev[dom->depth];
+    Field * F = get_field (dom, d->mask);
+    if (!F) return GFSHIP_EINVAL;
+    mask = F->lev[dom->depth];
   }
   else if (d->constant) {
     if ((r = launch_fill (dom->stream, (long) G.N, d->value, d->fv))) return r;
@@ -796,70 +471,16 @@ int gfship_droplet_to_particle_event (gfship_droplet_to_particle * d, gfship_dro
   if (info) info->n = n;
   if (!(n > 0 && -(long) d->min < (long) n)) return GFSHIP_OK;      /* :1381 */
   GFSHIP_CHECK ((long) pl->n + (long) n <= 0x7fffffffL, GFSHIP_ENOMEM, "the list would hold 2^31 slots or more");
-  if ((r = drop_tags (dom, W, G, nullptr, n, true, false))) return r;
-  if ((r = drop_min (dom, W, n, d->min, &umin))) return r;
+  if ((r = drop_tags (M, W, nullptr, n, true, false))) return r;
+  if ((r = drop_min (dom->stream, W, n, d->min, &umin))) return r;
   if (info) info->min = umin;
-  /* the segments of keys of the droplets that convert: at most min - 1 leaves each */
-  unsigned long long cap = umin > 2u ? std::min ((unsigned long long) G.N, (unsigned long long) n*(umin - 1u)) : 0ull;
-  if ((r = drop_reserve_keys (dom, W, (size_t) cap))) return r;
-  if ((r = particles_reserve (pl, pl->n + (int) n))) return r;
-  with_bools ([&] (auto D3) {
-    constexpr int DIM = decltype (D3)::value ? 3 : 2;
-    hipLaunchKernelGGL (drop_candidate_kernel<DIM>, dim3 (drop_grid (n)), dim3 (DROP_BLOCK), 0, dom->stream, G, n, umin,
-			W->sizes, W->last, W->segsize, W->cursor);
-  }, dom->dim == 3);
-  GFSHIP_HIP (hipGetLastError ());
-  if ((r = drop_scan (dom, W, W->segsize, W->seg, n))) return r;
-  const unsigned long long * sorted = W->key;
-  if (cap) {
-    GFSHIP_HIP (hipMemsetAsync (W->key, 0xFF, (size_t) cap*sizeof (unsigned long long), dom->stream));
-    with_bools ([&] (auto D3) {
-      constexpr int DIM = decltype (D3)::value ? 3 : 2;
-      hipLaunchKernelGGL (drop_keys_kernel<DIM>, dim3 (drop_grid (G.N)), dim3 (DROP_BLOCK), 0, dom->stream, G, W->tagi,
-			  W->segsize, W->seg, W->cursor, cap, W->key);
-    }, dom->dim == 3);
-    GFSHIP_HIP (hipGetLastError ());
-    int bits = 33;
-    while (bits < 64 && (1ull << (bits - 32)) <= (unsigned long long) n) bits++;
-    size_t need = 0;
-    GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (nullptr, need, W->key, W->key2, cap, 0, bits, dom->stream));
-    if ((r = drop_reserve_tmp (dom, W, need))) return r;
-    size_t bytes = W->tmp_bytes;
-    GFSHIP_HIP (hipcub::DeviceRadixSort::SortKeys (W->tmp, bytes, W->key, W->key2, cap, 0, bits, dom->stream));
-    sorted = W->key2;
-  }
-  DropConvertArgs A;
-  A.G = G; A.n = n; A.base = pl->n;
-  A.sizes = W->sizes; A.segsize = W->segsize; A.seg = W->seg; A.key = sorted;
-  A.c = C->lev[dom->depth];
-  A.alpha = sv.alpha_cell >= 0 ? dom->fields[sv.alpha_cell].lev[dom->depth] : nullptr;
-  for (int a = 0; a < 3; a++) {
-    A.u[a] = a < dom->dim ? dom->fields[sv.u[a]].lev[dom->depth] : nullptr;
-    A.pos[a] = pl->pos[a]; A.old[a] = pl->old[a]; A.vel[a] = pl->vel[a]; A.force[a] = pl->force[a];
-  }
-  A.mass = pl->mass; A.volume = pl->volume; A.orig = pl->orig; A.cell = W->cell;
-  with_bools ([&] (auto D3) {
-    constexpr int DIM = decltype (D3)::value ? 3 : 2;
-    hipLaunchKernelGGL (drop_convert_kernel<DIM>, dim3 (drop_grid (n)), dim3 (DROP_BLOCK), 0, dom->stream, A);
-  }, dom->dim == 3);
-  GFSHIP_HIP (hipGetLastError ());
-  const int base = pl->n;
-  if ((r = launch_feed_ids (pl, base, (int) n, W->cell, W->block))) return r;
-  pl->n += (int) n;
-  if (info) {
-    hipLaunchKernelGGL (drop_made_kernel, dim3 (drop_grid (n)), dim3 (DROP_BLOCK), 0, dom->stream, n, pl->alive + base,
-			W->counters);
-    GFSHIP_HIP (hipGetLastError ());
-  }
-  if ((r = drop_reset (dom, W, G, C, umin, d->reset))) return r;
-  if (info) {
-    unsigned h[4];
-    GFSHIP_HIP (hipMemcpyAsync (h, W->counters, sizeof h, hipMemcpyDeviceToHost, dom->stream));
-    GFSHIP_HIP (hipStreamSynchronize (dom->stream));
-    info->converted = h[2];
-    info->reset = h[3];
-  }
-  return GFSHIP_OK;
+  const double * u[3];
+  for (int a = 0; a < 3; a++)
+    u[a] = a < dom->dim ? dom->fields[sv.u[a]].lev[dom->depth] : nullptr;
+  const double * alpha = sv.alpha_cell >= 0 ? dom->fields[sv.alpha_cell].lev[dom->depth] : nullptr;
+  if ((r = drop_convert (M, W, pl, n, umin, C->lev[dom->depth], u, alpha, info != nullptr))) return r;
+  if ((r = drop_reset (dom, W, M, C, umin, d->reset))) return r;
+  return info ? drop_info (dom->stream, W, info) : GFSHIP_OK;
 }
 
 void gfship_droplet_to_particle_destroy (gfship_droplet_to_particle * d)

@@ -156,6 +156,12 @@ struct gfship_tree : TreePlan {
   // same way (tree_source_variable)
   double * svar[6] = {};
   bool src_fields = false;          // gfship_tree_set_source_fields: U, V, W take the velocity source of _FX ...
+  // gfs_domain_tag_droplets (tree_droplets.hip): the plan of the contacts of the leaves, made on first use; what that
+  // file keeps on the device of it, with its work arrays; the tags (GFSHIP_TREE_TAG), allocated zeroed on first use
+  std::optional<DropletPlan> droplet_plan;
+  void * droplets = nullptr;
+  void (* droplets_free) (void *) = nullptr;
+  double * tagvar = nullptr;
 };
 
 namespace {
@@ -1978,6 +1984,8 @@ void tree_free (gfship_tree * tr)
 {
   if (!tr) return;
   if (tr->sampler && tr->sampler_free) tr->sampler_free (tr->sampler);
+  if (tr->droplets && tr->droplets_free) tr->droplets_free (tr->droplets);
+  (void) hipFree (tr->tagvar);
   snapshot_tables_free (tr);
   (void) hipFree (tr->dflag);
   (void) hipFree (tr->d_nbtab); (void) hipFree (tr->d_child0); (void) hipFree (tr->d_cmask); (void) hipFree (tr->d_idtab);
@@ -2030,6 +2038,8 @@ double * gfship::tree_variable (gfship_tree * tr, int var)
     return tr->cvar[var - GFSHIP_TREE_VF];
   if (var >= GFSHIP_TREE_RAD && var <= GFSHIP_TREE_DMDT)
     return tr->svar[var - GFSHIP_TREE_RAD];
+  if (var == GFSHIP_TREE_TAG)
+    return tr->tagvar;
   return var >= 0 && var < abi_nvar ? tr->var[abi_var[var]] : nullptr;
 }
 
@@ -2062,6 +2072,27 @@ int gfship::tree_source_variable (gfship_tree * tr, int var, double ** out)
   GFSHIP_CHECK (var != GFSHIP_TREE_WRELP || tr->H.dim == 3, GFSHIP_EINVAL, "a quadtree has no GFSHIP_TREE_WRELP");
   return lazy_variable (tr, tr->svar[var - GFSHIP_TREE_RAD], out);
 }
+
+int gfship::tree_tag_variable (gfship_tree * tr, double ** out)
+{
+  return lazy_variable (tr, tr->tagvar, out);
+}
+
+int gfship::tree_droplet_plan (gfship_tree * tr, TreeDropletSlot * slot)
+{
+  if (!tr->droplet_plan) {
+    DropletPlan P;
+    int e = plan_droplets (*tr, P);
+    if (e) return e;
+    tr->droplet_plan = std::move (P);
+  }
+  slot->plan = &*tr->droplet_plan;
+  slot->state = &tr->droplets;
+  slot->state_free = &tr->droplets_free;
+  return GFSHIP_OK;
+}
+
+int gfship::tree_bc_scalar (gfship_tree * tr, double * v) { return bc_scalar (tr, v); }
 
 bool gfship::tree_has_variable (gfship_tree * tr, int var)
 {

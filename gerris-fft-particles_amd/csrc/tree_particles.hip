@@ -348,39 +348,9 @@ struct TreeSamp {
   const double * w;
 };
 
-struct Leaf { int l, q, g, i, j, k; };
-template <int NV> struct Vars { const double * p[NV]; };    // the arrays (all levels) of NV variables      // g = Topo::gi; i, j, k: the indices in the dense level (with ghosts)
+template <int NV> struct Vars { const double * p[NV]; };    // the arrays (all levels) of NV variables
 
-// ftt_cell_locate (root, target, -1), src/ftt.c:1535-1574, on the unit box centred on the origin
-template <int DIM>
-__device__ __forceinline__ bool tree_locate (const TreeSamp & S, const double target[3], Leaf & c)
-{
-  double pos[3] = { 0., 0., 0. };
-  double size = 1./2.;
-#pragma unroll
-  for (int a = 0; a < DIM; a++)
-    if (target[a] > pos[a] + size || target[a] < pos[a] - size)
-      return false;
-  int l = 0, i = 1, j = 1, k = DIM == 3 ? 1 : 0;
-  int q = 1 + 3*(1 + (DIM == 3 ? 3 : 0));
-  int g = S.T.off[0] + q;
-  while (l < S.T.depth && S.T.cmask[g] != 0) {
-    const bool ux = target[0] > pos[0], uy = target[1] > pos[1], uz = DIM == 3 && target[2] > pos[2];
-    const int rr = (2 << l) + 2;
-    q = S.T.child0[g] + (ux ? 1 : 0) - (uy ? 0 : rr) - (DIM == 3 && !uz ? rr*rr : 0);
-    i = 2*i - 1 + (ux ? 1 : 0);
-    j = 2*j - (uy ? 0 : 1);
-    if (DIM == 3) k = 2*k - (uz ? 0 : 1);
-    size /= 2.;
-    pos[0] += (ux ? 1. : -1.)*size;
-    pos[1] += (uy ? 1. : -1.)*size;
-    if (DIM == 3) pos[2] += (uz ? 1. : -1.)*size;
-    l++;
-    g = S.T.off[l] + q;
-  }
-  c.l = l; c.q = q; c.g = g; c.i = i; c.j = j; c.k = k;
-  return true;
-}
+// ftt_cell_locate (root, target, -1): tree_locate, tree_particles.hpp, over S.T
 
 // gfs_interpolate (src/fluid.c:2697-2710) of NV variables at p inside the leaf c; v[]: the arrays of all levels
 template <int DIM, int NV>

@@ -1190,6 +1190,119 @@ bool diffusion_weights_exact (const Topo & T)
   return true;
 }
 
+// the contacts of the leaves for gfs_domain_tag_droplets.  From a leaf, ftt_cell_neighbors (src/ftt.h:432-480) gives
+// in each direction the cell of its level or the coarser leaf: a leaf of its level is a contact without a gate; a
+// coarser leaf k is a contact whose gate is the parent N of the leaf, the cell of the level of k that k sees there
+// (tag_cell_fraction, src/domain.c:3577, tests c on N before it looks at the children of N, :3587-3593); a cell of
+// its level with children is the same contact seen from its coarse end, taken from the fine one
+int plan_droplets (const TreePlan & P, DropletPlan & out)
+{
+  const Topo & T = P.H;
+  const size_t nl = P.hleaves.size ();
+  GFSHIP_CHECK (P.ncell < (1 << 30), GFSHIP_EUNSUPPORTED, "gfs_domain_tag_droplets: the tree has 2^30 cells or more");
+  std::vector<int> leafpos (P.ncell, -1);
+  for (size_t k = 0; k < nl; k++)
+    leafpos[T.gi (P.hleaves[k])] = (int) k;
+  out = DropletPlan ();
+  out.cells.assign (P.ncell, 0xFFFFFFFFu);
+  for (int l = 0; l <= T.depth; l++)
+    for (int q = 0; q < T.lsize (l); q++) {
+      const Cell c = { l, q };
+      if (T.flag[T.gi (c)] != NONE && T.interior (c)) out.cells[T.gi (c)] = (unsigned) T.gi (c);
+    }
+  out.on_side.assign (nl, 0);
+  std::vector<std::vector<DropContact>> con (nl);
+  for (size_t p = 0; p < nl; p++) {
+    const Cell c = P.hleaves[p];
+    for (int d = 0; d < T.nd (); d++) {
+      if (touches_side (T, c, d)) {
+	out.on_side[p] = 1;
+	if (P.side[d] != GFSHIP_SIDE_PERIODIC) continue;
+	/* match_periodic_bc, :3689-3698: the leaf across the box; gfship_tree_create has made the refinement of the
+	   two sides equal, so that it is a leaf of this level */
+	const int n = T.n (c.l), a = d >> 1;
+	int x[3] = { T.ci (c), T.cj (c), T.ck (c) };
+	x[a] = x[a] == n ? 1 : n;
+	const Cell o = T.make (c.l, x[0], x[1], x[2]);
+	GFSHIP_CHECK (exists (o) && leafpos[T.gi (o)] >= 0, GFSHIP_EUNSUPPORTED,
+		      "gfs_domain_tag_droplets: the refinement differs across a periodic side");
+	const unsigned q = (unsigned) leafpos[T.gi (o)];
+	if (q < p) {
+	  out.periodic.push_back ((unsigned) p);
+	  out.periodic.push_back (q);
+	}
+	continue;
+      }
+      const Cell nb = T.neighbor (c, d);
+      if (!exists (nb) || !T.interior (nb) || !T.leaf (nb)) continue;
+      const unsigned q = (unsigned) leafpos[T.gi (nb)];
+      if (nb.l == c.l) {
+	if (q < p) con[p].push_back (DropContact { q, -1 });
+	continue;
+      }
+      /* nb is a coarser leaf: the gate is the parent of c */
+      const Cell N = T.make (c.l - 1, (T.ci (c) + 1)/2, (T.cj (c) + 1)/2, T.dim == 3 ? (T.ck (c) + 1)/2 : 0);
+      GFSHIP_CHECK (exists (N) && nb.l == c.l - 1, GFSHIP_EUNSUPPORTED, "gfs_domain_tag_droplets: the tree is not graded");
+      if (q < p) con[p].push_back (DropContact { q, T.gi (N) << 1 | 1 });
+      else con[q].push_back (DropContact { (unsigned) p, T.gi (N) << 1 });
+      out.ngated++;
+    }
+  }
+  out.con_off.assign (nl + 1, 0);
+  for (size_t p = 0; p < nl; p++) {
+    out.con_off[p + 1] = out.con_off[p] + (int) con[p].size ();
+    out.con.insert (out.con.end (), con[p].begin (), con[p].end ());
+  }
+  return GFSHIP_OK;
+}
+
+// DESIGN.md 11.41 on the host, a test aid (gfship_tree_host_tag_droplets): the steps of tree_droplets.hip in their
+// order, which must stay in step with that file -- the components of the contacts that are symmetric
+// (tdrop_block_kernel, tdrop_cross_kernel), the one-way contacts until nothing changes and parent[root] = L[root]
+// (tdrop_oneway_kernel), then the periodic pairs (tdrop_periodic_kernel), the ranks
+unsigned droplet_tags_host (const TreePlan & P, const DropletPlan & D, const double * c, std::vector<unsigned> & tag)
+{
+  const Topo & T = P.H;
+  const unsigned nl = (unsigned) P.hleaves.size (), none = 0xFFFFFFFFu;
+  std::vector<unsigned> parent (nl), L (nl);
+  for (unsigned p = 0; p < nl; p++)
+    parent[p] = L[p] = c[T.gi (P.hleaves[p])] > 1e-4 ? p : none;
+  auto find = [&] (unsigned x) { while (parent[x] != x) x = parent[x]; return x; };
+  auto unite = [&] (unsigned a, unsigned b) {
+    a = find (a); b = find (b);
+    if (a != b) parent[a > b ? a : b] = a > b ? b : a;
+  };
+  std::vector<std::pair<unsigned, unsigned>> oneway;      /* (f, k) */
+  for (unsigned p = 0; p < nl; p++)
+    for (int o = D.con_off[p]; o < D.con_off[p + 1]; o++) {
+      const unsigned q = D.con[o].other;
+      const int gate = D.con[o].gate;
+      if (parent[p] == none || parent[q] == none) continue;
+      if (gate < 0 || c[gate >> 1] > 1e-4) unite (p, q);
+      else oneway.push_back ((gate & 1) ? std::make_pair (p, q) : std::make_pair (q, p));
+    }
+  for (bool changed = true; changed; ) {
+    changed = false;
+    for (const auto & r : oneway) {
+      const unsigned f = find (r.first), k = find (r.second);
+      if (L[f] < L[k]) { L[k] = L[f]; changed = true; }
+    }
+  }
+  for (unsigned p = 0; p < nl; p++)
+    if (parent[p] == p) parent[p] = L[p];
+  for (size_t o = 0; o + 1 < D.periodic.size (); o += 2)
+    if (parent[D.periodic[o]] != none && parent[D.periodic[o + 1]] != none)
+      unite (D.periodic[o], D.periodic[o + 1]);
+  std::vector<unsigned> rank (nl, 0);
+  unsigned n = 0;
+  for (unsigned p = 0; p < nl; p++)
+    if (parent[p] == p) rank[p] = n++;
+  tag.assign (nl, 0);
+  for (unsigned p = 0; p < nl; p++)
+    if (parent[p] != none) tag[p] = 1 + rank[find (p)];
+  return n;
+}
+
 // no exception crosses the C ABI: a tree too large for the host comes back as an error
 int plan_tree_create (int dim, gfship_refine_fn refine, void * ctx, const int * side, TreePlans & h)
 try {
@@ -1425,6 +1538,30 @@ int gfship_tree_host_check_diffusion (int dim, gfship_refine_fn refine, void * c
   stats[0] = st.updates; stats[1] = st.loop_levels; stats[2] = not_w; stats[3] = st.differ; stats[4] = st.hazards;
   stats[5] = st.no_flow;
   return e;
+}
+
+/* The droplet plan of a tree and the closed form of gfs_domain_tag_droplets on it, without a device (for the CPU
+   tests; see gfship.h) */
+int gfship_tree_host_tag_droplets (int dim, gfship_refine_fn refine, void * ctx, const int * side, long long ncell,
+				   const double * c, long long nleaves, unsigned * tags, unsigned * n, long long counts[3])
+try {
+  GFSHIP_CHECK (refine && c && tags && n && counts, GFSHIP_EINVAL, "gfship_tree_host_tag_droplets: bad argument");
+  TreePlans tr;
+  int e = plan_tree_create (dim, refine, ctx, side, tr);
+  if (e) return e;
+  GFSHIP_CHECK (ncell == tr.T.ncell && nleaves == (long long) tr.T.hleaves.size (), GFSHIP_EINVAL,
+		"gfship_tree_host_tag_droplets: the tree has %d cells and %zu leaves", tr.T.ncell, tr.T.hleaves.size ());
+  DropletPlan D;
+  if ((e = plan_droplets (tr.T, D))) return e;
+  std::vector<unsigned> tag;
+  *n = droplet_tags_host (tr.T, D, c, tag);
+  std::copy (tag.begin (), tag.end (), tags);
+  counts[0] = (long long) D.con.size (); counts[1] = D.ngated; counts[2] = (long long) D.periodic.size ()/2;
+  return GFSHIP_OK;
+}
+catch (const std::bad_alloc &) {
+  set_error ("gfship_tree_host_tag_droplets: out of host memory");
+  return GFSHIP_EUNSUPPORTED;
 }
 
 /* lab: FNV-1a-64 digests of everything a device tree of these arguments uploads, with the Poisson loop plans of

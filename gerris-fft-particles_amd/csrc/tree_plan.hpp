@@ -89,6 +89,26 @@ struct TreePlans {
   FacePlan faces[4];                   // 0: FTT_XYZ, 1 + c: the faces normal to c
 };
 
+// gfs_domain_tag_droplets (src/domain.c:3727-3796) on a static tree, DESIGN.md 11.41: the face contacts of the interior
+// leaves.  A label is the position of a leaf in hleaves.  con_off[p] .. con_off[p + 1]: the contacts of leaf p with
+// leaves of lower position.  gate < 0: two leaves of one level.  Otherwise a fine leaf f beside a coarser leaf k, and
+// gate = (index in the concatenated levels of the cell N beside k that holds f, the one whose value of c decides
+// whether the fill steps from k into f, tag_cell_fraction :3577) << 1 | (leaf p is the fine end)
+struct DropContact { unsigned other; int gate; };
+struct DropletPlan {
+  std::vector<int> con_off;            // nleaves + 1
+  std::vector<DropContact> con;
+  std::vector<unsigned> periodic;      // pairs (p, q < p) of leaves of one level that meet through a periodic side
+  std::vector<unsigned char> on_side;  // per leaf: it touches a side of the box, periodic or not
+  std::vector<unsigned> cells;         // per cell of the concatenated levels: itself if it is an interior cell of the
+                                       // tree (a leaf or not: compute_v runs over FTT_TRAVERSE_ALL), else 0xFFFFFFFF
+  unsigned ngated = 0;                 // contacts with a gate: the one-way records of a call are at most as many
+};
+int plan_droplets (const TreePlan & T, DropletPlan & out);
+// the closed form of the fill on the host: tag[p] of every leaf (0 outside the mask) from the values c of every cell
+// of the concatenated levels; returns the number of droplets
+unsigned droplet_tags_host (const TreePlan & T, const DropletPlan & P, const double * c, std::vector<unsigned> & tag);
+
 // gfs_refine_refine + gfs_simulation_refine with the corner rule, gfs_domain_match, the tables of Topo, the lists of
 // cells, the sweeps and the face sets; side: nullptr = all periodic.  Returns GFSHIP_OK or the error of
 // gfship_tree_create; no exception leaves it

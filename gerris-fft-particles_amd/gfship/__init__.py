@@ -248,6 +248,13 @@ SIGNATURES = {
                                                C.POINTER(C.c_char_p), C.POINTER(_i)]),
     "gfship_droplet_to_particle_event": (_i, [_vp, C.POINTER(C.c_uint)]),
     "gfship_droplet_to_particle_destroy": (None, [_vp]),
+    "gfship_tree_tag_droplets": (_i, [_vp, _i, C.POINTER(C.c_uint)]),
+    "gfship_tree_tag_droplets_time": (_i, [_vp, _i, _i, _pd]),
+    "gfship_tree_remove_droplets": (_i, [_vp, _i, _i, _i, C.c_double]),
+    "gfship_tree_droplet_to_particle_create": (_i, [C.POINTER(_vp), _vp, _i, _i, C.c_double, C.c_double, C.c_char_p,
+                                                    _i, C.POINTER(C.c_char_p), C.POINTER(_i)]),
+    "gfship_tree_host_tag_droplets": (_i, [_i, C.c_void_p, _vp, _pi, C.c_longlong, _pd, C.c_longlong,
+                                           C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_longlong)]),
 }
 
 
@@ -1121,6 +1128,23 @@ class TreeFeedParticle(FeedParticle):
         self.ptr, self.plist, self.tree = p, plist, tree
 
 
+class TreeDropletToParticle(DropletToParticle):
+    """GfsDropletToParticle on a list of Tree.particulates: the droplets of the variable c (a Tree.* number), or of
+    `function' -- as for DropletToParticle; variables: a dict name -> Tree.* number -- smaller than min leaves become
+    particulates, and c = reset on their leaves.  A function that is no variable is evaluated at every cell of every
+    level.  event and close are those of DropletToParticle.  Close it before its list."""
+
+    def __init__(self, tree, plist, c, min=20, reset=0., density=1., function=None, variables=None):
+        variables = dict(variables or {})
+        names = (C.c_char_p * max(len(variables), 1))(*[k.encode() for k in variables])
+        numbers = (_i * max(len(variables), 1))(*[int(v) for v in variables.values()])
+        p = _vp()
+        _check(lib().gfship_tree_droplet_to_particle_create(
+            C.byref(p), plist.ptr, int(c), int(min), float(reset), float(density),
+            None if function is None else str(function).encode(), len(variables), names, numbers))
+        self.ptr, self.plist, self.tree = p, plist, tree
+
+
 REFINE_FN = C.CFUNCTYPE(C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p)
 
 
@@ -1164,6 +1188,26 @@ def tree_host_plan_digest(refine, dim=2, sides=None, nrelax=4):
     return tuple(out)
 
 
+def tree_host_tag_droplets(refine, levels, nleaves, dim=2, sides=None):
+    """gfship_tree_host_tag_droplets: the droplet plan of a tree and the closed form of gfs_domain_tag_droplets on
+    it, on the host (no device needed).  levels: the mask, one array with ghosts per level; nleaves: the number of
+    interior leaves.  Returns (the tag of every leaf in traversal order, the number of droplets, (contacts, contacts
+    with a gate, periodic pairs))"""
+    if dim == 2:
+        cb = REFINE_FN(lambda x, y, z, ctx: float(refine(x, y)))
+    else:
+        cb = REFINE_FN(lambda x, y, z, ctx: float(refine(x, y, z)))
+    arr = (C.c_int * 6)(*(list(sides) + [0] * 6)[:6]) if sides is not None else None
+    c = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64).ravel() for a in levels]))
+    tags = np.zeros(int(nleaves), dtype=np.uint32)
+    n = C.c_uint(0)
+    counts = (C.c_longlong * 3)()
+    _check(lib().gfship_tree_host_tag_droplets(dim, C.cast(cb, C.c_void_p), None, arr, c.size, c.ctypes.data_as(_pd),
+                                               tags.size, tags.ctypes.data_as(C.POINTER(C.c_uint)), C.byref(n),
+                                               counts))
+    return tags, int(n.value), tuple(counts)
+
+
 class Tree:
     """gfship_tree: a GfsSimulation on one periodic box refined by a GfsRefine function (coarse-fine
     stencils; quadtree or octree).  refine (x, y) or refine (x, y, z) -> level wanted there."""
@@ -1172,6 +1216,7 @@ class Tree:
     VF, FX, FY, FZ = 28, 29, 30, 31       # GfsParticulateField, GfsSourceParticulate: once a call has needed them
     # Rad, Urelp, Vrelp, Wrelp, volsource, dmdtvariable of GfsSourceParticulateVol / ...Mass: in the same way
     RAD, URELP, VRELP, WRELP, VOLSRC, DMDT = 32, 33, 34, 35, 36, 37
+    TAG = 38                              # the tags of tag_droplets: once a call has needed them
 
     def __init__(self, refine, dim=2, device=0, sides=None):
         self.dim = dim
@@ -1333,6 +1378,24 @@ class Tree:
     def set_idlast(self, pl, value):
         _check(lib().gfship_tree_particles_set_idlast(pl.ptr, int(value)))
 
+    def tag_droplets(self, c):
+        """gfs_domain_tag_droplets: the leaves of Tree.TAG get the index (1 ..) of their droplet of the variable c, 0
+        outside; returns the number of droplets"""
+        n = C.c_uint(0)
+        _check(lib().gfship_tree_tag_droplets(self.ptr, int(c), C.byref(n)))
+        return int(n.value)
+
+    def time_tag_droplets(self, c, reps=10):
+        """tag_droplets, measured between two events after a warm-up call: milliseconds per call"""
+        ms = C.c_double(0.)
+        _check(lib().gfship_tree_tag_droplets_time(self.ptr, int(c), int(reps), C.byref(ms)))
+        return ms.value
+
+    def remove_droplets(self, c, v, min, val=0.):
+        """gfs_domain_remove_droplets: v = val on the leaves of the droplets of c smaller than min leaves (min < 0: all
+        but the -min largest)"""
+        _check(lib().gfship_tree_remove_droplets(self.ptr, int(c), int(v), int(min), float(val)))
+
     def set_source_fields(self, on=True):
         """U, V(, W) take the velocity source of Tree.FX ... (GfsSourceParticulate in the time step)"""
         _check(lib().gfship_tree_set_source_fields(self.ptr, 1 if on else 0))
@@ -1357,3 +1420,6 @@ class Tree:
         if self.ptr:
             lib().gfship_tree_destroy(self.ptr)
             self.ptr = None
+
+
+TREE_TAG = Tree.TAG      # GFSHIP_TREE_TAG

@@ -1247,6 +1247,67 @@ int  gfship_tree_feed_particle_create (gfship_feed_particle ** feed, gfship_part
 int  gfship_tree_particles_set_idlast (gfship_particles * pl, int idlast);
 int  gfship_tree_particles_idlast (gfship_particles * pl);
 
+/* ---- droplets on a tree (src/domain.c:3564-3880, modules/particulatecommon.c:1163-1527) -------- */
+
+/* gfs_domain_tag_droplets, gfs_domain_remove_droplets and GfsDropletToParticle on a refined quadtree / octree
+   (DESIGN.md 11.41).  c_var, v_var and the variables of a table are GFSHIP_TREE_* variables the tree has now
+   (GFSHIP_EINVAL otherwise).  The tags go to GFSHIP_TREE_TAG, a variable of the library (gfship_tree_upload does not
+   take it) allocated zeroed -- every level, ghost cells included -- by the first call that needs it; before that
+   gfship_tree_download returns GFSHIP_EINVAL.
+   gfship_tree_tag_droplets (gfs_domain_tag_droplets, src/domain.c:3727-3796, with tag_new_fraction_region and
+   tag_cell_fraction, :3566-3615): the leaves of GFSHIP_TREE_TAG receive, as doubles, the index of their droplet, 0
+   outside; every other cell keeps what it held; *n = the number of droplets.  On a tree the fill is directed: from a
+   fine leaf it always steps into the coarser leaf beside it (:3578-3581), from the coarse leaf k it steps into the
+   fine leaves only if c > 1e-4 on the cell N of the level of k that holds them (:3577: the test is made on N, with the
+   value c holds on that cell with children -- what gfship_tree_upload gave that level, or what the step's
+   coarse init left).  The tag of a leaf is 1 + the rank, among the seeds, of the smallest traversal index (FTT_PRE_ORDER
+   over the leaves) of a leaf from which a directed path inside the mask reaches it; then the periodic sides join
+   the regions of the fill (match_periodic_bc, touching_regions, :3620-3711) and the final tag is 1 + the rank by the
+   smallest such label.  As on the box the fill does not step into the ghost cells of a side; on a tree the
+   reference's route through the ghost cells of a periodic side may also pass a gate, through the image of N, where
+   the interior gate is shut.  Integer atomics only: the same tags from run to run.
+   gfship_tree_tag_droplets_time: a warm-up call, then `reps' calls between two events; *ms = milliseconds per call.
+   gfship_tree_remove_droplets (gfs_domain_remove_droplets, :3836-3880): sizes count the leaves of a droplet whatever
+   their level (compute_droplet_size, :3805-3810), min as for gfship_remove_droplets, v_var = val on the LEAVES of every
+   droplet with size < min (:3812-3817; the cells with children keep their values), then the ghost cells of v_var
+   as those of a tracer: the periodic image, and on a GfsBoundary side the default GfsBc of a scalar.  The conditions
+   a variable has of its own on such a side (those of gfship_tree_set_bc for P, of gfship_tree_set_bc_u for U, V, W)
+   are NOT applied: for such a v_var the caller restores its ghost cells.  The same holds for c_var in the event of a
+   GfsDropletToParticle.
+   gfship_tree_droplet_to_particle_create (gfs_droplet_to_particle_read, modules/particulatecommon.c:1407-1467) on a
+   list made by gfship_particulates_create_tree (GFSHIP_EUNSUPPORTED on a list of tracers of a tree and on a list of
+   a box; gfship_droplet_to_particle_create keeps refusing a list of a tree): c_var, min, reset, density and function
+   as for gfship_droplet_to_particle_create; the function is compiled as those of gfship_tree_feed_particle_create
+   and the refusals of the table are the same.  A function that is the name of a variable of the table is that
+   variable; any other is evaluated at EVERY cell of every level, cells with children included (compute_v, :1357-1390,
+   FTT_TRAVERSE_ALL: x, y, z = ftt_cell_pos of that cell, a name = its variable at that cell), and the gates read those
+   values.
+   gfship_droplet_to_particle_event and _destroy work on such a handle (it knows what made it).  Per event, on the
+   stream of the tree (compute_droplet_properties, :1194-1229; convert_droplets, :1278-1348): over the leaves of a
+   droplet in traversal order that touch no side, sizes++ whatever the level, volume += pow (h, dim)*c with h the size of
+   the leaf, pos += ftt_cell_pos, vel += U ...; boundary = whether its last leaf touches a side; the position and
+   velocity are the sums over sizes, cell = gfs_domain_locate (pos, -1), the leaf whatever its level (a droplet whose
+   centre lies outside the box is skipped); a tree has no alpha: mass = 1.*volume; then add_particulate and the slots
+   as for gfship_droplet_to_particle_event.  c_var = reset on the leaves of every droplet with sizes < min, then its
+   ghost cells.  The host reads n, the size a negative min selects, and with info one more word.
+   Destroy the object before its list, and the list before its tree. */
+enum { GFSHIP_TREE_TAG = GFSHIP_TREE_DMDT + 1 };
+int  gfship_tree_tag_droplets (gfship_tree * tree, int c_var, unsigned * n);
+int  gfship_tree_tag_droplets_time (gfship_tree * tree, int c_var, int reps, double * ms);
+int  gfship_tree_remove_droplets (gfship_tree * tree, int c_var, int v_var, int min, double val);
+int  gfship_tree_droplet_to_particle_create (gfship_droplet_to_particle ** d, gfship_particles * pl, int c_var,
+					     int min, double reset, double density, const char * function,
+					     int nvars, const char * const * names, const int * vars);
+/* A test aid, not the device path: the droplet plan of a tree (the same plan_droplets the device uploads) and the
+   closed form of the fill on the host, without a device, in the order of the steps of tree_droplets.hip (symmetric
+   contacts, one-way contacts, periodic pairs), so that the CPU suite pins the plan on the literal fill.  c holds
+   ncell values, every cell of the levels 0, 1 ... one after the other ((2^l + 2)^dim each); tags receives one tag per
+   interior leaf in traversal order, *n the number of droplets; counts: the contacts between leaves, those with a gate,
+   the periodic pairs */
+int  gfship_tree_host_tag_droplets (int dim, gfship_refine_fn refine, void * ctx, const int * side, long long ncell,
+				    const double * c, long long nleaves, unsigned * tags, unsigned * n,
+				    long long counts[3]);
+
 /* ---- instrumentation -------------------------------------------------------------------- */
 
 /* time (HIP events on the domain's stream) of `reps` back-to-back sweeps of gfship_relax on

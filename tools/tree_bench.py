@@ -3,7 +3,7 @@
 extra levels inside the central cube / square: leaves, dependency levels of the finest sweep, ms per
 step, Mleaf-steps/s.  Not the benchmarked path (that is bench.py); a measurement to quote.
 usage: tree_bench.py [dim] [level] [box] [steps] [nu] [--snapshot] [--tracers N] [--particulates N] [--two-way N]
-                     [--sources N [--source-function constant|field]]
+                     [--sources N [--source-function constant|field]] [--droplets]
 nu: GfsSourceDiffusion on every velocity component (default 0: inviscid)
 --snapshot: also time the file image of the tree (gfship_tree_snapshot_write) for P, Pmac, U, V
 (, W): the first call, which builds the offset tables, and the median of 20 more (kernel + copy to the host),
@@ -26,7 +26,12 @@ storage sorted by leaf, Rad, Urelp ... and the deposit written: a volume source 
 compiled text that reads one variable (--source-function picks one of the two).  Medians of 10 calls after two
 uncounted ones, with the least and the largest: the whole event (each call ended by a stream synchronise), the
 passes per particle and the sort with the pass per leaf (gfship_particulate_source_time_event: device time between
-events on the stream), and last (it moves the particles) the event of the same list."""
+events on the stream), and last (it moves the particles) the event of the same list.
+--droplets: a second line, gfship_tree_tag_droplets_time (a warm-up call, then the milliseconds per call
+of 20 between two events on the stream, each call ended by the read of n) of a tracer given on every level: a
+few balls, noise (every cell of every level in the mask or not by a hash of its place: many droplets, and gates shut
+at random), and the whole tree as one droplet; with the number of droplets, and for context gfship_tag_droplets_time
+of the same three on the uniform box whose cell count is nearest to the leaves of the tree."""
 import os
 import sys
 import time
@@ -64,6 +69,8 @@ if "--sources" in sys.argv:
     k = sys.argv.index("--sources")
     nsources = int(sys.argv[k + 1])
     del sys.argv[k:k + 2]
+droplets = "--droplets" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--droplets"]
 dim = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 level = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 box = int(sys.argv[3]) if len(sys.argv) > 3 else 2
@@ -95,6 +102,7 @@ for l in range(g.depth + 1):
 if nu != 0.:
     for c in range(dim):
         g.set_viscosity(c, nu)
+cvar = g.add_tracer() if droplets else None      # the tracer whose droplets are tagged: a variable of the run
 g.set_time(1e30, 0.8)
 g.start()
 g.step()
@@ -251,4 +259,38 @@ print({"dim": dim, "levels": [level, g.depth], "leaves": nleaves, "finest_sweep_
        "niter": [g.projection_params.niter, g.approx_projection_params.niter],
        **snap, **trac, **part, **two, **srcs,
        **({"nu": nu, "diffusion_niter": [g.diffusion_params(c).niter for c in range(dim)]} if nu != 0. else {})})
+if droplets:
+    balls = (((0.12, 0.1, 0.05), 0.17), ((-0.27, 0.04, 0.), 0.09), ((0.5, -0.22, 0.1), 0.11), ((-0.3, -0.3, -0.3), 0.1))
+
+    def fields(centres):
+        r2 = [sum((centres[a] - c[a])**2 for a in range(dim)) for c, _ in balls]
+        blob = np.zeros_like(centres[0])
+        for d2, (_, r) in zip(r2, balls):
+            blob = np.maximum(blob, (d2 < r*r)*0.75)
+        h = np.zeros(centres[0].shape)
+        for a in range(dim):
+            h = h*7919.13 + np.floor((centres[a] + 0.75)*4096.)
+        noise = (np.modf(np.sin(h)*43758.5453)[0] % 1. > 0.5)*0.75
+        return {"blobs": blob, "noise": noise, "whole": 0.*blob + 0.75}
+
+    drop = {"leaves": nleaves}
+    per_level = [fields(g.centres(l)) for l in range(g.depth + 1)]
+    for name in ("blobs", "noise", "whole"):
+        for l in range(g.depth + 1):
+            g.upload(cvar, l, per_level[l][name])
+        n = g.tag_droplets(cvar)
+        drop["tree_%s" % name] = {"droplets": n, "ms_per_call": round(g.time_tag_droplets(cvar, 20), 4)}
+    blevel = int(round(np.log2(nleaves)/dim))
+    gd = gfship.Domain(dim, blevel, [gfship.SIDE_PERIODIC]*6)
+    c, tag = gd.variable(), gd.variable()
+    nb = 1 << blevel
+    cc = -0.5 + (np.arange(nb + 2) - 0.5)/nb
+    centres = np.meshgrid(cc, cc, indexing="xy") if dim == 2 else np.meshgrid(cc, cc, cc, indexing="ij")[::-1]
+    drop["box_level"], drop["box_cells"] = blevel, nb**dim
+    for name, a in fields(centres).items():
+        c.upload(np.ascontiguousarray(a))
+        n = gd.tag_droplets(c, tag)
+        drop["box_%s" % name] = {"droplets": n, "ms_per_call": round(gd.time_tag_droplets(c, tag, 20), 4)}
+    gd.destroy()
+    print(drop)
 g.destroy()
